@@ -10,7 +10,9 @@ Workload (BASELINE.json metric: "clips/sec (segment+embed+retrieve) @1M x 512 DB
   therefore constant in N ("weak"); value = N*1024 clips / max-over-ranks step time.  The store is the same 1 M rows for every N
   (random rows + two near-duplicates of each of rank 0's 1024 clips).
 
-One JSON line on rank 0 (contract in the task statement), including
+One JSON line on rank 0 (contract in the task statement).  A plain run only sets up, warms up, times --steps steps and prints the
+headline (metric, value, unit, higher_is_better, dtype, ms_per_step, config); --dump-outputs DIR also writes the embeddings, distances
+and ids of the last timed step.  --full adds, after the timed steps:
   roofline     : the dominant kernel (the scan: k_knn_hi on the f16 matrix pipe, or k_knn_f32_reg with --scan f32), timed
                  with HIP events on the launch stream over the timed region; `kernels` adds the same accounting for the log-mel and
                  projection kernels, from event pairs over as many steps right after it
@@ -79,6 +81,38 @@ def scan_traffic_from_profiles(section):
     return None, None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """--dump-outputs: arrays {name: tensor or array} -> out_dir/<name>.npy (out_dir/<name>_rank<r>.npy when N > 1).  Floating
+    arrays are written as float32 (float64 stays float64), integer ids as float64 (exact below 2^53).  Above DUMP_LIMIT_BYTES in all
+    (over all ranks), every array with the common leading dimension keeps the same seeded sample of rows, and the sampled row numbers go to rows.npy."""
+    import numpy as np
+    import torch
+    out = {}
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach()
+            a = (a.double() if a.dtype in (torch.float64, torch.int64, torch.int32) else a.float()).cpu().numpy()
+        a = np.asarray(a)
+        out[name] = a.astype(np.float64 if a.dtype in (np.float64, np.int64, np.int32) else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    limit = DUMP_LIMIT_BYTES // world - 4096                             # (every rank writes its share; .npy headers)
+    if total > limit:
+        n = {a.shape[0] for a in out.values()}
+        assert len(n) == 1, "a sampled dump needs one leading dimension"
+        n = n.pop()
+        keep = max(1, int(limit / (total / n + 8)))                      # (+ 8 bytes a row: its number in rows.npy)
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        out = {name: a[rows] for name, a in out.items()}
+        out["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -126,6 +160,14 @@ def main():
                     help="f16 = the reference's use_float16 knob (fp16 rows); NOT the headline configuration")
     ap.add_argument("--embed-dtype", choices=["f32", "bf16"], default="f32",
                     help="bf16 = embeddings emitted and searched as bfloat16 (BASELINE config 5); NOT the headline configuration")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: scan events in the timed region (roofline), per-kernel "
+                         "timings, --sustain, --unstructured, --pcie, the planted-neighbour check, the CPU baseline and the float64 "
+                         "parity sample (and, N > 1, the per-rank collective / re-rank split).  Off: set up, warm up, time --steps "
+                         "steps, dump, print the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: a fixed, seeded sample of rows beyond that)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -209,6 +251,10 @@ def main():
             t0 = time.perf_counter()
             out_p = pipe.predict("/eval/q.wav", _DS(), model)
             lat.append(1e3 * (time.perf_counter() - t0))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"probability_spoof": np.array([out_p["probability_spoof"]]),
+                                             "logit": np.array([out_p["logit"]]),
+                                             "retrieved_labels": np.array(out_p["retrieved_labels"], np.float64)})
         # the device part alone: the same calls queued without reading anything back
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -256,6 +302,8 @@ def main():
             D, I = index.search_device(qp, k)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"distances": D, "ids": I})
         scan = float(np.mean(index.profile_read()))
         launch = index.last_launch()
         esz = 2.0 if (args.store_dtype == "f16" or launch["scan_kind"] in ("hi_smallq", "hi_tile")) else 4.0
@@ -362,7 +410,7 @@ def main():
     if replicate:                                           # the whole store on every rank: a rank's search is the one-GPU search
         searcher = ReplicatedSearch(lambda q, k: vdb.index.search_device(q, k))
     else:
-        searcher = ShardedSearch(local_search, vdb.index.metric, bounded=bounded, timing=world > 1)
+        searcher = ShardedSearch(local_search, vdb.index.metric, bounded=bounded, timing=world > 1 and args.full)
 
     def barrier():
         if world > 1:
@@ -390,6 +438,8 @@ def main():
             D, I = vdb.index.search_device(qp, TOP_K)
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"distances": D, "ids": I})
         ms = vdb.index.profile_read()
         scan = float(np.mean(ms))
         launch = vdb.index.last_launch()
@@ -427,29 +477,36 @@ def main():
     # an event record between dependent kernels holds the next one back ~6 us (rocprofv3 trace, profiles/r4_*_step_trace.txt: 6.0-6.5 us
     # before and after each of the step's two scan launches, 0.0 between the kernels without events), i.e. 0.024 ms per step when every
     # step carries them.  The two embedding kernels' event pairs (the `kernels` extras) are taken right AFTER the timed region.
-    vdb.index.profile(True, every=4 if args.steps >= 8 else 1)
+    # Both are --full only: a plain run times the steps without events.
+    if args.full:
+        vdb.index.profile(True, every=4 if args.steps >= 8 else 1)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         emb, (D, I) = step()
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0)
-    knn_ms = vdb.index.profile_read()
-    fe.profile(True)
-    for _ in range(min(args.steps, 20)):
-        step()
-    barrier()
-    vdb.index.profile_read()
-    lm_ms, pp_ms = fe.profile_read()
-    fe.profile(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"embeddings": emb, "distances": D, "ids": I}, rank, world)
+    knn_ms, lm_ms, pp_ms, shard_ms = [], [], [], []
+    if args.full:
+        knn_ms = vdb.index.profile_read()
+        fe.profile(True)
+        for _ in range(min(args.steps, 20)):
+            step()
+        barrier()
+        vdb.index.profile_read()
+        lm_ms, pp_ms = fe.profile_read()
+        fe.profile(False)
     launch = vdb.index.last_launch()
     rechecked = launch["rechecked_queries"]
     n_launch = max(1, launch.get("scan_launches", 1))       # the tile scan covers a large store in several launches: one entry each
-    shard_ms = searcher.timings() if (world > 1 and not replicate) else []
+    if args.full and world > 1 and not replicate:
+        shard_ms = searcher.timings()
     searcher.timing = False                                   # (the legs below are not broken down: no events to create)
 
     # ---- sustained: the same step, looped for >= args.sustain seconds (the chip settles at its steady-state clock) ------
     sustained = None
-    if args.sustain > 0:
+    if args.full and args.sustain > 0:
         t1 = time.perf_counter()
         n_s = 0
         while True:
@@ -467,7 +524,7 @@ def main():
     # sample-based admission floor is low and the epilogue's push / drain path works hardest -- what a store of unrelated
     # embeddings looks like to the filter), cosine on the benchmark's store and L2 (the reference's default metric) on a copy
     scan_unstructured = None
-    if world == 1 and args.unstructured > 0:
+    if args.full and world == 1 and args.unstructured > 0:
         qu = torch.empty((B, DIM), device=dev, dtype=torch.float32)
         _lib.check(lib.radad_synth_rows(qu.data_ptr(), 0, B, DIM, 977, local_rank, _lib.stream_ptr(dev)))
         scan_unstructured = {}
@@ -496,7 +553,7 @@ def main():
     # device buffers on a copy stream while the previous step computes (what a caller that streams clips from the host gets)
     pcie = None
     pcie_pcm16 = None
-    if args.pcie > 0 and args.workload == "fixed":
+    if args.full and args.pcie > 0 and args.workload == "fixed":
         def pcie_leg(pcm16):
             # pcm16: the batch crosses PCIe as 16-bit PCM (what audio files hold) and is converted on the device as the reference's
             # loader would (sample / 32768, radad_pcm16_to_f32) -- half the bytes; the timing does not depend on the values
@@ -544,18 +601,20 @@ def main():
         pcie = pcie_leg(False)
         pcie_pcm16 = pcie_leg(True)
 
-    # ---- correctness of the result (cheap, every rank): batch 0's planted rows lead every list ------------------------
-    emb = embed(0)
-    D, I = searcher.search(emb, TOP_K)
-    # rank 0: the top hit of clip j is ITS planted row; other ranks (their clips have no planted row of their own): some planted row
-    if rank == 0:
-        planted_ok = bool((I[:, 0] == (torch.arange(B, device=dev) * 977 + 17) % n_total).all().item())
-    else:
-        planted_ok = bool(torch.isin(I[:, 0], planted_ids).all().item())
-    if world > 1:                                   # rank 0 reports the verdict of ALL ranks
-        t = torch.tensor([1.0 if planted_ok else 0.0], dtype=torch.float64, device="cpu" if rehearse else dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MIN)
-        planted_ok = bool(t.item() > 0.5)
+    # ---- correctness of the result (cheap, every rank; --full): batch 0's planted rows lead every list ---------------
+    planted_ok = None
+    if args.full:
+        emb = embed(0)
+        D, I = searcher.search(emb, TOP_K)
+        # rank 0: the top hit of clip j is ITS planted row; other ranks (their clips have no planted row of their own): some planted row
+        if rank == 0:
+            planted_ok = bool((I[:, 0] == (torch.arange(B, device=dev) * 977 + 17) % n_total).all().item())
+        else:
+            planted_ok = bool(torch.isin(I[:, 0], planted_ids).all().item())
+        if world > 1:                                   # rank 0 reports the verdict of ALL ranks
+            t = torch.tensor([1.0 if planted_ok else 0.0], dtype=torch.float64, device="cpu" if rehearse else dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MIN)
+            planted_ok = bool(t.item() > 0.5)
 
     ms_step = 1e3 * dt / args.steps
     value = world * B * args.steps / dt
@@ -588,7 +647,7 @@ def main():
         scan_desc = "fp32 MFMA scan; float64 re-rank from the stored rows"
     dtype = ("f32" if args.embed_dtype == "f32" else "bf16 embeddings") + (" / f16 store" if f16 else "") + " (" + scan_desc + ")"
     traffic, traffic_source = None, None
-    if world == 1 and B == CLIPS_PER_GPU and n_total == DB_ROWS and not f16 and args.workload == "fixed" and wide:
+    if args.full and world == 1 and B == CLIPS_PER_GPU and n_total == DB_ROWS and not f16 and args.workload == "fixed" and wide:
         traffic, traffic_source = scan_traffic_from_profiles("k_knn_hi")
     logmel_kind = fe.last_logmel_kind()
     lm_avg = float(np.mean(lm_ms)) if lm_ms else float("nan")
@@ -636,30 +695,33 @@ def main():
                    "clips_per_gpu": B, "db_rows": n_total, "dim": DIM, "k": TOP_K, "parallelism": (f"replicate{world}" if replicate else f"shard{world}"),
                    # fixed workload: the clip offsets do not change between steps, so radad_embed_forward reuses the segment plan
                    # (k_build_plan, 14 us, skipped); --workload ragged rebuilds it on the device every step
-                   "plan_rebuilt_every_step": args.workload != "fixed",
-                   "planted_neighbours_found": planted_ok},
-        "roofline": {"kernel": kname, "bound": "mfma", "achieved": round(achieved, 2),
-                     "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
-                     "traffic": traffic, "traffic_source": traffic_source,
-                     "kernel_ms": round(knn_launch_avg, 4), "launches_per_step": n_launch, "scan_ms_per_step": round(knn_avg, 4),
-                     "flops_per_launch": flops / n_launch, "algorithmic_bytes_per_launch": alg_bytes / n_launch,
-                     "algorithmic_bytes_per_search": alg_bytes, "scanned_bytes_per_element": esz,
-                     "store_bytes_resident": store_bytes,
-                     # what the launches of one search read and write, queries re-read once per chunk of the store included
-                     "kernel_operand_bytes_per_launch": ((2.0 * (hi - lo) * DIM + 2.0 * Q * DIM * max(1, launch["db_splits"]) / max(1, launch["query_tiles"])
-                                                          + 8.0 * Q * 330) if wide else alg_bytes) / n_launch,
-                     "hbm_GBps_algorithmic": round(alg_bytes / (knn_avg * 1e-3) / 1e9, 1),
-                     "queries_rejected_by_certificate_last_step": rechecked,
-                     "launch": launch},
-        # (log-mel: the event pair spans k_seg_stats and the log-mel kernel; `frac` is FLOPs executed against the pipe that executes
-        # them -- the fp32 vector ALU for the FFT kernel, the f16 matrix pipe otherwise --, `frac_hbm` the algorithmic bytes against HBM)
-        "kernels": {lm_name: kroof(lm_avg, lm_flops, lm_bytes, lm_bound, lm_peak),
-                    "k_proj_pool2": kroof(pp_avg, pp_flops, pp_bytes, "mfma", PEAK_MFMA_F16_TFLOPS)},
-        "frames_transformed_per_step": n_transforms,
-        "kernels_measured": "HIP events over %d steps right after the timed region (the timed region carries the scan's events only)" % min(args.steps, 20),
-        "logmel_kind": logmel_kind,
-        "kernels_ms": {"k_logmel": round(lm_avg, 4), "k_proj_pool": round(pp_avg, 4), "scan": round(knn_avg, 4)},
+                   "plan_rebuilt_every_step": args.workload != "fixed"},
     }
+    if args.full:
+        out["config"]["planted_neighbours_found"] = planted_ok
+        out.update({
+            "roofline": {"kernel": kname, "bound": "mfma", "achieved": round(achieved, 2),
+                         "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
+                         "traffic": traffic, "traffic_source": traffic_source,
+                         "kernel_ms": round(knn_launch_avg, 4), "launches_per_step": n_launch, "scan_ms_per_step": round(knn_avg, 4),
+                         "flops_per_launch": flops / n_launch, "algorithmic_bytes_per_launch": alg_bytes / n_launch,
+                         "algorithmic_bytes_per_search": alg_bytes, "scanned_bytes_per_element": esz,
+                         "store_bytes_resident": store_bytes,
+                         # what the launches of one search read and write, queries re-read once per chunk of the store included
+                         "kernel_operand_bytes_per_launch": ((2.0 * (hi - lo) * DIM + 2.0 * Q * DIM * max(1, launch["db_splits"]) / max(1, launch["query_tiles"])
+                                                              + 8.0 * Q * 330) if wide else alg_bytes) / n_launch,
+                         "hbm_GBps_algorithmic": round(alg_bytes / (knn_avg * 1e-3) / 1e9, 1),
+                         "queries_rejected_by_certificate_last_step": rechecked,
+                         "launch": launch},
+            # (log-mel: the event pair spans k_seg_stats and the log-mel kernel; `frac` is FLOPs executed against the pipe that executes
+            # them -- the fp32 vector ALU for the FFT kernel, the f16 matrix pipe otherwise --, `frac_hbm` the algorithmic bytes against HBM)
+            "kernels": {lm_name: kroof(lm_avg, lm_flops, lm_bytes, lm_bound, lm_peak),
+                        "k_proj_pool2": kroof(pp_avg, pp_flops, pp_bytes, "mfma", PEAK_MFMA_F16_TFLOPS)},
+            "frames_transformed_per_step": n_transforms,
+            "kernels_measured": "HIP events over %d steps right after the timed region (the timed region carries the scan's events only)" % min(args.steps, 20),
+            "logmel_kind": logmel_kind,
+            "kernels_ms": {"k_logmel": round(lm_avg, 4), "k_proj_pool": round(pp_avg, 4), "scan": round(knn_avg, 4)},
+        })
     if shard_ms:     # this rank's share of a step outside the scan: collectives (query all-gather, bound all-reduce, list exchange) and
         # the re-rank half of the search (float64 re-rank + exact kernel)
         cm, rm = float(np.mean([a for a, _ in shard_ms])), float(np.mean([b for _, b in shard_ms]))
@@ -677,7 +739,7 @@ def main():
         out["pcie_inclusive_pcm16"] = pcie_pcm16
 
     # ---- CPU side (rank 0, one GPU): the float64 oracle CHECKS the GPU result; the float32 torch-CPU port is TIMED ------
-    if rank == 0 and world == 1 and (args.cpu_sample > 0 or args.cpu_baseline_clips > 0):
+    if args.full and rank == 0 and world == 1 and (args.cpu_sample > 0 or args.cpu_baseline_clips > 0):
         from oracle import radad_oracle as O
         from oracle import cpu_baseline as CB
         w0, o0 = batches[0][0], batches[0][3]

@@ -32,7 +32,7 @@ def test_more_ranks_than_gpus_is_an_error():
 def test_bare_bench_with_two_ranks_launches_itself(gpu):
     import torch
     env = {} if torch.cuda.device_count() >= 2 else {"RADAD_BENCH_REHEARSE": "1"}
-    r = _run(env, "--gpus", "2", "--steps", "4", "--warmup", "1", "--db-rows", "200000", "--clips", "256", "--sustain", "0",
+    r = _run(env, "--gpus", "2", "--steps", "4", "--warmup", "1", "--db-rows", "200000", "--clips", "256", "--full", "--sustain", "0",
              "--pcie", "0", "--unstructured", "0", "--cpu-sample", "0", "--cpu-baseline-clips", "0")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

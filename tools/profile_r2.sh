@@ -3,21 +3,22 @@
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 T=$1
+RESULTS_DIR=${RESULTS_DIR:-results}; mkdir -p "$RESULTS_DIR"
 echo stats; timeout -k 10 300 bash tools/profile_stats.sh ${T} > /dev/null 2>&1
-echo pmc; timeout -k 10 600 bash tools/profile_r1.sh ${T} > gpurun_out/pmc_${T}.out 2>&1
+echo pmc; timeout -k 10 600 bash tools/profile_r1.sh ${T} > $RESULTS_DIR/pmc_${T}.out 2>&1
 echo benches
-python bench.py > gpurun_out/${T}_bench_default.json 2> gpurun_out/${T}_bench_default.err
-python bench.py --workload ragged --pcie 0 > gpurun_out/${T}_bench_ragged.json 2> /dev/null
-python bench.py --store-dtype f16 --cpu-baseline-clips 0 --pcie 0 --sustain 0 > gpurun_out/${T}_bench_f16.json 2> /dev/null
-python bench.py --store-dtype f16 --embed-dtype bf16 --cpu-baseline-clips 0 --pcie 0 --sustain 0 > gpurun_out/${T}_bench_bf16_f16.json 2> /dev/null
-python bench.py --scan f32 --cpu-sample 0 --cpu-baseline-clips 0 --pcie 0 --sustain 0 > gpurun_out/${T}_bench_scan_f32.json 2> /dev/null
-python bench.py --mode predict --steps 200 --warmup 10 > gpurun_out/${T}_predict_1.json 2> /dev/null
-python bench.py --mode predict --predict-queries 16 --steps 200 --warmup 10 > gpurun_out/${T}_predict_16.json 2> /dev/null
+python bench.py --full > $RESULTS_DIR/${T}_bench_default.json 2> $RESULTS_DIR/${T}_bench_default.err
+python bench.py --full --workload ragged --pcie 0 > $RESULTS_DIR/${T}_bench_ragged.json 2> /dev/null
+python bench.py --full --store-dtype f16 --cpu-baseline-clips 0 --pcie 0 --sustain 0 > $RESULTS_DIR/${T}_bench_f16.json 2> /dev/null
+python bench.py --full --store-dtype f16 --embed-dtype bf16 --cpu-baseline-clips 0 --pcie 0 --sustain 0 > $RESULTS_DIR/${T}_bench_bf16_f16.json 2> /dev/null
+python bench.py --full --scan f32 --cpu-sample 0 --cpu-baseline-clips 0 --pcie 0 --sustain 0 > $RESULTS_DIR/${T}_bench_scan_f32.json 2> /dev/null
+python bench.py --mode predict --steps 200 --warmup 10 > $RESULTS_DIR/${T}_predict_1.json 2> /dev/null
+python bench.py --mode predict --predict-queries 16 --steps 200 --warmup 10 > $RESULTS_DIR/${T}_predict_16.json 2> /dev/null
 for f in default ragged f16 bf16_f16 scan_f32; do python - <<PY
 import json
-d=json.load(open("gpurun_out/${T}_bench_$f.json"))
+d=json.load(open("$RESULTS_DIR/${T}_bench_$f.json"))
 print("$f", d["value"], d["ms_per_step"], d["kernels_ms"], d.get("sustained",{}).get("value"), d.get("pcie_inclusive",{}).get("value"), d.get("cpu_baseline",{}).get("value"), d.get("parity_on_sample",{}).get("ids_bit_exact"), d["roofline"]["launch"].get("certificate"))
 PY
 done
 for f in predict_1 predict_16; do python -c "
-import json; d=json.load(open('gpurun_out/${T}_$f.json')); print('$f', d['value'], d['roofline']['achieved'], d['roofline']['kernel_ms'])"; done
+import json; d=json.load(open('$RESULTS_DIR/${T}_$f.json')); print('$f', d['value'], d['roofline']['achieved'], d['roofline']['kernel_ms'])"; done
