@@ -19,7 +19,7 @@ Q_F32, Q_BF16 = 0, 1
 OUT_F32, OUT_BF16 = 0, 1
 MAX_LEVELS = 8
 KNN_MAX_K = 1024
-KNN_OPT_HI_PLANE, KNN_OPT_CENTRE, KNN_OPT_SMALLQ_HI, KNN_OPT_WIDE_MIN_Q, KNN_OPT_DENSE, KNN_OPT_LIVE_FLOOR = 0, 1, 2, 3, 4, 5
+KNN_OPT_HI_PLANE, KNN_OPT_CENTRE, KNN_OPT_SMALLQ_HI, KNN_OPT_WIDE_MIN_Q, KNN_OPT_DENSE = 0, 1, 2, 3, 4
 IVF_OPT_HI_SCAN = 0
 IVF_SCAN_KINDS = ("f32_lists", "hi_lists", "exact_flat")
 EMBED_NO_SHARED_FRAMES, EMBED_LOGMEL_F32, EMBED_LOGMEL_DFT_GEMM = 1, 2, 4

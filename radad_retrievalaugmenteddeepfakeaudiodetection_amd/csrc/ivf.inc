@@ -30,22 +30,23 @@
 namespace {
 
 struct IvfScanParams {
-    const float* lrows;        // [N, dim] list-major
-    const float* lnorm;        // [N]
-    const int* loff;           // [nlist + 1]
-    const float* q;            // [nq, dim]
-    const int* task_list;      // [T]
-    const int* task_pbeg;      // [T] first pair of the task in the list-sorted pair order
-    const int* task_cnt;       // [T] pairs (queries) of the task, <= qcap
-    const int* n_tasks_dev;    // [1] T, built on the device: the grid is an upper bound, workgroups beyond T leave
-    const int* pair_q;         // [nq * nprobe] query of each sorted pair
-    const int* pair_slot;      // [nq * nprobe] output slot q * nprobe + j of each sorted pair
-    int dim, k, qcap;          // qcap: query rows that fit in LDS (16 unless dim is very large)
-    float* part_score;         // [nq * nprobe, k]
-    int* part_idx;             // [nq * nprobe, k]  positions in lrows
-    const int* only_flagged;   // optional [nq]: a task none of whose queries is flagged leaves at once (the pass behind the f16 scan)
-    const int* flagged_count;  // with only_flagged: [1] how many queries are flagged
+    const float* lrows = nullptr;       // [N, dim] list-major
+    const float* lnorm = nullptr;       // [N]
+    const int* loff = nullptr;          // [nlist + 1]
+    const float* q = nullptr;           // [nq, dim]
+    const int* task_list = nullptr;     // [T]
+    const int* task_pbeg = nullptr;     // [T] first pair of the task in the list-sorted pair order
+    const int* task_cnt = nullptr;      // [T] pairs (queries) of the task, <= qcap
+    const int* n_tasks_dev = nullptr;   // [1] T, built on the device: the grid is an upper bound, workgroups beyond T leave
+    const int* pair_q = nullptr;        // [nq * nprobe] query of each sorted pair
+    const int* pair_slot = nullptr;     // [nq * nprobe] output slot q * nprobe + j of each sorted pair
+    int dim = 0, k = 0, qcap = 0;       // qcap: query rows that fit in LDS (16 unless dim is very large)
+    float* part_score = nullptr;        // [nq * nprobe, k]
+    int* part_idx = nullptr;            // [nq * nprobe, k]  positions in lrows
+    const int* only_flagged = nullptr;  // optional [nq]: a task none of whose queries is flagged leaves at once (the pass behind the f16 scan)
+    const int* flagged_count = nullptr; // with only_flagged: [1] how many queries are flagged
 };
+static_assert(std::is_trivially_copyable_v<IvfScanParams>, "kernel argument");
 
 // ---- (query, probe) pairs grouped by list, on the device ------------------------------------------------------------
 // k_ivf_count: pairs per list.  k_ivf_tasks (one workgroup): exclusive scan -> first sorted position of every list, the
@@ -302,24 +303,25 @@ __global__ __launch_bounds__(256) void k_ivf_gather_plane(const _Float16* __rest
 }
 
 struct IvfHiParams {
-    const _Float16* lhi;       // [N][dim] list-major f16 plane
-    const float* lscale;       // [N] per-row scale, or nullptr: uscale for every row
-    float uscale;
-    const float* lbias;        // [N] |y'|^2 of the plane's operand (y' = y - mu when the plane is centred)
-    const int* loff;           // [nlist + 1]
-    const _Float16* qh;        // [nq][dim] f16 queries (k_hi_rows: scaled per query, centred as the plane)
-    const float* qscale;       // [nq]
-    const float* qconst;       // [nq] -|q'|^2
-    const float* eps;          // [nq] error bound of the scores
-    const int* task_list; const int* task_pbeg; const int* task_cnt; const int* n_tasks_dev; const int* pair_q;
-    int dim, k, qcap;          // k: neighbours asked for (<= 26: the carry holds 32 entries)
-    int split;                 // workgroups per task: each takes 1/split of the list's rows (few tasks: a one-query search has nprobe of them)
-    unsigned* gbound;          // [nq] running lower bound of a_k (the k-th best score over the query's lists) as an ordered key, 0 at launch
-    int* cand_cnt;             // [nq] entries emitted, 0 at launch; more than cand_cap = overflow (k_merge_refine rejects the query)
-    int cand_cap;
-    float* cand_score;         // [nq][cand_cap]
-    int* cand_idx;             // [nq][cand_cap] positions in the list-major order
+    const _Float16* lhi = nullptr; // [N][dim] list-major f16 plane
+    const float* lscale = nullptr; // [N] per-row scale, or nullptr: uscale for every row
+    float uscale = 1.f;
+    const float* lbias = nullptr;  // [N] |y'|^2 of the plane's operand (y' = y - mu when the plane is centred)
+    const int* loff = nullptr;     // [nlist + 1]
+    const _Float16* qh = nullptr;  // [nq][dim] f16 queries (k_hi_rows: scaled per query, centred as the plane)
+    const float* qscale = nullptr; // [nq]
+    const float* qconst = nullptr; // [nq] -|q'|^2
+    const float* eps = nullptr;    // [nq] error bound of the scores
+    const int* task_list = nullptr; const int* task_pbeg = nullptr; const int* task_cnt = nullptr; const int* n_tasks_dev = nullptr; const int* pair_q = nullptr;
+    int dim = 0, k = 0, qcap = 0;  // k: neighbours asked for (<= 26: the carry holds 32 entries)
+    int split = 1;                 // workgroups per task: each takes 1/split of the list's rows (few tasks: a one-query search has nprobe of them)
+    unsigned* gbound = nullptr;    // [nq] running lower bound of a_k (the k-th best score over the query's lists) as an ordered key, 0 at launch
+    int* cand_cnt = nullptr;       // [nq] entries emitted, 0 at launch; more than cand_cap = overflow (k_merge_refine rejects the query)
+    int cand_cap = 0;
+    float* cand_score = nullptr;   // [nq][cand_cap]
+    int* cand_idx = nullptr;       // [nq][cand_cap] positions in the list-major order
 };
+static_assert(std::is_trivially_copyable_v<IvfHiParams>, "kernel argument");
 
 constexpr int IVH_CHUNK = 256;                 // rows per chunk: 4 waves x 4 steps of 16
 constexpr int IVH_SLD = IVH_CHUNK + 4;         // score row (floats)
@@ -923,11 +925,11 @@ int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int n
         int* cand_cnt = (int*)(qb + b_qh + 3 * b_vec); unsigned* gbound = (unsigned*)(qb + b_qh + 4 * b_vec);
         int* qflag = (int*)(qb + b_qh + 5 * b_vec); int* fsel = (int*)(qb + b_qh + 6 * b_vec); int* fcount = (int*)(qb + b_qh + 7 * b_vec);
         HiRowsParams hp;
-        hp.in = q_dev; hp.in_f16 = 0; hp.hi = qh; hp.scale_out = qscale; hp.stat_max = nullptr; hp.eps_out = eps; hp.ystat = f->stat;
-        hp.n = nq; hp.dim = h->dim; hp.fixed_e = HI_E_PER_ROW; hp.l2 = 1; hp.exact_ops = 0; hp.norm_out = nullptr;
+        hp.in = q_dev; hp.hi = qh; hp.scale_out = qscale; hp.eps_out = eps; hp.ystat = f->stat;
+        hp.n = nq; hp.dim = h->dim; hp.fixed_e = HI_E_PER_ROW; hp.l2 = 1;
         hp.zero_flags = cand_cnt; hp.zero_flags2 = (int*)gbound; hp.zero_counters = fcount;
         hp.mu = f->cmu; hp.mu_norm = f->cmu ? f->mu_norm : 0.f; hp.mu_sq = f->cmu ? f->mu_sq : 0.f; hp.biased = 1;
-        hp.bias_out = nullptr; hp.qconst_out = qconst;
+        hp.qconst_out = qconst;
         launch_hi_rows(hp, st);
         IvfHiParams ip;
         ip.lhi = (const _Float16*)h->lhi.p; ip.lscale = f->rscale ? (const float*)h->lscale.p : nullptr;
@@ -944,10 +946,10 @@ int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int n
         hipLaunchKernelGGL(k_ivf_scan_hi, dim3((unsigned)(T * ip.split)), dim3(SQ_THREADS), hlds, st, ip);
         RefineParams m;
         m.score = (const float*)h->cand_s.p; m.idx = (const int*)h->cand_i.p; m.n_parts = 1; m.part_len = ccap; m.k = k; m.dim = h->dim; m.l2 = 1;
-        m.cap = std::max(k + KNN_CERT_EXTRA, KNN_CERT_CAP); m.eps = eps; m.thr_init = nullptr; m.qflag = nullptr; m.part_cnt = cand_cnt;
-        m.global_lb = nullptr; m.ak_in = nullptr; m.flag_count = fcount; m.flag_sel = fsel; m.stats = nullptr; m.nq = nq;
-        m.db = h->lrows.p; m.db_f16 = 0; m.q = q_dev; m.id_map = (const int64_t*)h->lids.p; m.id_base = 0;
-        m.out_dist = out_dist_dev; m.out_idx = out_idx_dev; m.out_key = nullptr; m.debug = 0; m.qflag_out = qflag;
+        m.cap = std::max(k + KNN_CERT_EXTRA, KNN_CERT_CAP); m.eps = eps; m.part_cnt = cand_cnt;
+        m.flag_count = fcount; m.flag_sel = fsel; m.nq = nq;
+        m.db = h->lrows.p; m.q = q_dev; m.id_map = (const int64_t*)h->lids.p;
+        m.out_dist = out_dist_dev; m.out_idx = out_idx_dev; m.qflag_out = qflag;
         const size_t rlds = refine_lds_bytes(m.cap) + (size_t)ccap * 8 + 1024;
         if (rlds > 48 * 1024)
             RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge_refine<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
@@ -987,9 +989,9 @@ int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int n
     }
     // 4) per query: merge its nprobe lists, float64 re-score, (distance, insertion id) order
     RefineParams m;
-    m.score = (const float*)h->part_s.p; m.idx = (const int*)h->part_i.p; m.n_parts = nprobe; m.cap = ksel; m.part_len = ksel; m.eps = nullptr; m.thr_init = nullptr; m.qflag = nullptr; m.part_cnt = nullptr; m.global_lb = nullptr; m.ak_in = nullptr; m.flag_count = nullptr; m.flag_sel = nullptr; m.stats = nullptr; m.k = k; m.dim = h->dim;
-    m.l2 = 1; m.nq = nq; m.db = h->lrows.p; m.db_f16 = 0; m.q = q_dev; m.id_map = (const int64_t*)h->lids.p; m.id_base = 0;
-    m.out_dist = out_dist_dev; m.out_idx = out_idx_dev; m.out_key = nullptr; m.debug = 0; m.only_flagged = d_qflag;
+    m.score = (const float*)h->part_s.p; m.idx = (const int*)h->part_i.p; m.n_parts = nprobe; m.cap = ksel; m.part_len = ksel; m.k = k; m.dim = h->dim;
+    m.l2 = 1; m.nq = nq; m.db = h->lrows.p; m.q = q_dev; m.id_map = (const int64_t*)h->lids.p;
+    m.out_dist = out_dist_dev; m.out_idx = out_idx_dev; m.only_flagged = d_qflag;
     hipLaunchKernelGGL(k_merge_refine<false>, dim3((unsigned)nq), dim3(RF_THREADS), refine_lds_bytes(ksel), st, m);
     RADAD_HIP_CHECK(hipGetLastError());
     h->last_stream = st;

@@ -41,22 +41,23 @@ constexpr int KS_LD = KT_M + 4;  // score-tile row (floats): 132-dword stride ke
 constexpr int IDX_SENTINEL = 0x7fffffff;
 
 struct KnnParams {
-    const void* db;       // [n, dim] fp32, or fp16 when db_f16
-    const float* ynorm;   // [n] (L2) or nullptr
-    const void* q;        // [nq, dim] (already normalised for cosine); fp16 for the fp16 tile kernel, fp32 otherwise
-    int db_f16;
-    int64_t n;
-    int nq;
-    int dim;
-    int k;
-    int l2;               // 1: score = 2*dot - |y|^2 ; 0: score = dot
-    int n_qtiles;
-    int n_splits;         // multiple of 8
-    int64_t chunk_rows;   // rows per split, multiple of KT_M
-    float* part_score;    // [nq, n_splits, k]
-    int* part_idx;        // [nq, n_splits, k]
-    int debug;            // timing experiments only (RADAD_DEBUG_KNN): 1 = skip the top-k epilogue
+    const void* db = nullptr;     // [n, dim] fp32, or fp16 when db_f16
+    const float* ynorm = nullptr; // [n] (L2) or nullptr
+    const void* q = nullptr;      // [nq, dim] (already normalised for cosine); fp16 for the fp16 tile kernel, fp32 otherwise
+    int db_f16 = 0;
+    int64_t n = 0;
+    int nq = 0;
+    int dim = 0;
+    int k = 0;
+    int l2 = 0;                   // 1: score = 2*dot - |y|^2 ; 0: score = dot
+    int n_qtiles = 0;
+    int n_splits = 0;             // multiple of 8
+    int64_t chunk_rows = 0;       // rows per split, multiple of KT_M
+    float* part_score = nullptr;  // [nq, n_splits, k]
+    int* part_idx = nullptr;      // [nq, n_splits, k]
+    int debug = 0;                // timing experiments only (RADAD_DEBUG_KNN): 1 = skip the top-k epilogue
 };
+static_assert(std::is_trivially_copyable_v<KnnParams>, "kernel argument");
 
 __device__ __forceinline__ bool better(float s, int i, float ws, int wi) {
     return s > ws || (s == ws && i < wi);
@@ -663,13 +664,14 @@ constexpr int SQ_SLOTS = 16;
 constexpr size_t SQ_LDS_BUDGET = 160 * 1024;      // the query block [nq][dim + pad] + slot buffers must fit one CU's LDS
 
 struct SmallQParams {
-    const float* db; const float* ynorm; const float* q;      // fp32 store only
-    int64_t n;
-    int nq, dim, k, l2;
-    int rows_per_wave;          // multiple of 16
-    int n_parts;                // workgroups = lists per query
-    float* part_score; int* part_idx;   // [nq, n_parts, k]
+    const float* db = nullptr; const float* ynorm = nullptr; const float* q = nullptr; // fp32 store only
+    int64_t n = 0;
+    int nq = 0, dim = 0, k = 0, l2 = 0;
+    int rows_per_wave = 0;      // multiple of 16
+    int n_parts = 0;            // workgroups = lists per query
+    float* part_score = nullptr; int* part_idx = nullptr; // [nq, n_parts, k]
 };
+static_assert(std::is_trivially_copyable_v<SmallQParams>, "kernel argument");
 
 template <int KSEL>
 __global__ __launch_bounds__(SQ_THREADS, 2) void k_knn_f32_smallq(SmallQParams p) {
@@ -792,12 +794,13 @@ __global__ __launch_bounds__(SQ_THREADS, 2) void k_knn_f32_smallq(SmallQParams p
 // certified tile scan (score [nq][plen], idx [nq][plen], cnt [nq] = n), and k_merge_refine<true> selects on its staged copy,
 // re-scores in float64 and certifies against eps(q) of the fp32 products (k_hi_rows, exact_ops).
 struct DenseParams {
-    const float* db; const float* ynorm; const float* q;      // fp32 store only
-    int64_t n;
-    int nq, dim, l2;
-    int plen;                   // row stride of score / idx: a multiple of 4, >= n
-    float* score; int* idx; int* cnt;
+    const float* db = nullptr; const float* ynorm = nullptr; const float* q = nullptr; // fp32 store only
+    int64_t n = 0;
+    int nq = 0, dim = 0, l2 = 0;
+    int plen = 0;               // row stride of score / idx: a multiple of 4, >= n
+    float* score = nullptr; int* idx = nullptr; int* cnt = nullptr;
 };
+static_assert(std::is_trivially_copyable_v<DenseParams>, "kernel argument");
 
 // <RT, QT>: 16-row x 16-query tiles per wave.  <1, 1> for the batches of <= 16 queries (one wave per 16 rows: parallel over the rows);
 // <2, 4> otherwise: 32 rows x 64 queries per wave -- every operand a wave loads feeds 4 resp. 2 MFMAs (<1, 1> on 1024 queries x 4096
@@ -891,20 +894,21 @@ __global__ __launch_bounds__(256) void k_knn_dense(DenseParams p) {
 // eps(q) of the certified scan (k_hi_rows), and k_merge_refine certifies or rejects every query exactly as it does for the
 // tile kernel (complete top-(k + margin) lists per workgroup, no admission floor): the online search reads 1 GB instead of 2.
 struct SmallQHiParams {
-    const _Float16* db;         // [n][dim] f16 rows
-    const float* rscale;        // [n] per-row scale, or nullptr: uscale for every row
-    float uscale;
-    const float* rbias;         // [n] per-row bias magnitude (|y'|^2 for L2, mu.y for a centred IP / cosine plane), or nullptr
-    float bias_sign, mult;      // score = mult a + bias_sign rbias[row] + qconst[query]   (knn_hi.inc, RSC 2)
-    const float* qconst;        // [nq] or nullptr
-    const _Float16* q;          // [nq][dim] f16 queries (scaled per query; centred when the plane is)
-    const float* qscale;        // [nq]
-    int64_t n;
-    int nq, dim, k;
-    int rows_per_wave;          // multiple of 16
-    int n_parts;                // workgroups = lists per query
-    float* part_score; int* part_idx;   // [nq, n_parts, k]
+    const _Float16* db = nullptr;      // [n][dim] f16 rows
+    const float* rscale = nullptr;     // [n] per-row scale, or nullptr: uscale for every row
+    float uscale = 1.f;
+    const float* rbias = nullptr;      // [n] per-row bias magnitude (|y'|^2 for L2, mu.y for a centred IP / cosine plane), or nullptr
+    float bias_sign = 1.f, mult = 1.f; // score = mult a + bias_sign rbias[row] + qconst[query]   (knn_hi.inc, RSC 2)
+    const float* qconst = nullptr;     // [nq] or nullptr
+    const _Float16* q = nullptr;       // [nq][dim] f16 queries (scaled per query; centred when the plane is)
+    const float* qscale = nullptr;     // [nq]
+    int64_t n = 0;
+    int nq = 0, dim = 0, k = 0;
+    int rows_per_wave = 0;             // multiple of 16
+    int n_parts = 0;                   // workgroups = lists per query
+    float* part_score = nullptr; int* part_idx = nullptr; // [nq, n_parts, k]
 };
+static_assert(std::is_trivially_copyable_v<SmallQHiParams>, "kernel argument");
 
 // (launch bounds: 155 VGPRs = 3 waves per SIMD for KSEL 16; forcing 4 (128 VGPRs) spills the 16-load panel: 0.41 instead of 0.21 ms)
 template <int KSEL>
@@ -1132,39 +1136,38 @@ constexpr int KNN_CERT_EXTRA = 32;       // candidates beyond k the certified re
 constexpr int KNN_CERT_CAP = 512;        // ... and this many in all: stores of near-duplicates (the benchmark plants 2048 rows
                                          // within 2e-2 of every query) put hundreds of rows within 2 eps of the k-th
 constexpr int KNN_CERT_MAX_K = 128;      // largest k the certificate + exact kernel cover
-constexpr int KNN_PROG_OFF = 64;         // the tile scan's progress counters (one per query tile) sit behind the 256-byte flag_count block ...
-constexpr int KNN_PROG_MAX = 4096;       // ... at most this many query tiles (1 M queries) raise their floors inside one launch
 constexpr int KW_SAMPLE_SPLITS = 64;     // one-tile splits of the threshold pre-pass (<= 16384 rows)
 
 struct RefineParams {
-    const float* score;       // [nq, n_parts, part_len] fp32 scan scores (larger is better), each list sorted
-    const int* idx;           // [nq, n_parts, part_len] local row or IDX_SENTINEL
-    int n_parts, k, dim, l2;
-    int part_len;             // entries per partial list
-    int cap;                  // candidates that can be re-scored per query (>= k)
-    const float* eps;         // [nq] error bound of the scan scores, or nullptr = legacy mode (exactly `cap` candidates)
-    const float* thr_init;    // optional [nq]: admission floor of the scan (rows below it were never listed)
-    const int* qflag;         // optional [nq]: the scan dropped a candidate of this query
-    const int* part_cnt;      // optional [nq] (emit-mode scan, n_parts == 1): entries filled in the query's buffer; > part_len = overflow
-    const float* global_lb;   // optional [nq] (sharded search): the best lower bound any shard has of the exact k-th best score
-    const float* ak_in;       // optional [nq] (emit-mode scan, two-half search): a_k as k_kth_floor found it for the bounds
-    int* flag_count;          // certified mode: [1] number of uncertified queries (atomicAdd) ...
-    int* flag_sel;            // ... and their indices, in arrival order
-    int* stats;               // optional [5]: sum of candidates re-scored, queries rejected for: buffer full / list used up /
-                              // floor above tau / dropped by the scan
-    int64_t nq;
-    const void* db;           // stored rows (normalised for cosine); fp16 when db_f16
-    int db_f16;
-    const float* q;           // the fp32 queries (normalised for cosine)
-    const int64_t* id_map;    // optional: reported id = id_map[row] (IVF: list-sorted position -> insertion id), ties by it
-    int64_t id_base;
-    float* out_dist;          // [nq, k]
-    int64_t* out_idx;         // [nq, k]
-    double* out_key;          // optional [nq, k] float64 distances
-    int debug;                // timing experiments only (-DRADAD_DEBUG_HOOKS, RADAD_DEBUG_KNN): 128 no statistics atomics, 256 no re-score, 512 no ranking, 1024 no fp32 funnel
-    int* qflag_out = nullptr;           // optional [nq] (certified mode): the certificate's verdict per query, 0 = certified (IVF: who takes the fp32 pass)
-    const int* only_flagged = nullptr;  // optional [nq]: workgroups of queries whose entry is 0 leave at once (IVF: the fp32 pass of the rejected)
+    const float* score = nullptr;      // [nq, n_parts, part_len] fp32 scan scores (larger is better), each list sorted
+    const int* idx = nullptr;          // [nq, n_parts, part_len] local row or IDX_SENTINEL
+    int n_parts = 0, k = 0, dim = 0, l2 = 0;
+    int part_len = 0;                  // entries per partial list
+    int cap = 0;                       // candidates that can be re-scored per query (>= k)
+    const float* eps = nullptr;        // [nq] error bound of the scan scores, or nullptr = legacy mode (exactly `cap` candidates)
+    const float* thr_init = nullptr;   // optional [nq]: admission floor of the scan (rows below it were never listed)
+    const int* qflag = nullptr;        // optional [nq]: the scan dropped a candidate of this query
+    const int* part_cnt = nullptr;     // optional [nq] (emit-mode scan, n_parts == 1): entries filled in the query's buffer; > part_len = overflow
+    const float* global_lb = nullptr;  // optional [nq] (sharded search): the best lower bound any shard has of the exact k-th best score
+    const float* ak_in = nullptr;      // optional [nq] (emit-mode scan, two-half search): a_k as k_kth_floor found it for the bounds
+    int* flag_count = nullptr;         // certified mode: [1] number of uncertified queries (atomicAdd) ...
+    int* flag_sel = nullptr;           // ... and their indices, in arrival order
+    int* stats = nullptr;              // optional [5]: sum of candidates re-scored, queries rejected for: buffer full / list used up /
+                                       // floor above tau / dropped by the scan
+    int64_t nq = 0;
+    const void* db = nullptr;          // stored rows (normalised for cosine); fp16 when db_f16
+    int db_f16 = 0;
+    const float* q = nullptr;          // the fp32 queries (normalised for cosine)
+    const int64_t* id_map = nullptr;   // optional: reported id = id_map[row] (IVF: list-sorted position -> insertion id), ties by it
+    int64_t id_base = 0;
+    float* out_dist = nullptr;         // [nq, k]
+    int64_t* out_idx = nullptr;        // [nq, k]
+    double* out_key = nullptr;         // optional [nq, k] float64 distances
+    int debug = 0;                     // timing experiments only (-DRADAD_DEBUG_HOOKS, RADAD_DEBUG_KNN): 128 no statistics atomics, 256 no re-score, 512 no ranking, 1024 no fp32 funnel
+    int* qflag_out = nullptr;          // optional [nq] (certified mode): the certificate's verdict per query, 0 = certified (IVF: who takes the fp32 pass)
+    const int* only_flagged = nullptr; // optional [nq]: workgroups of queries whose entry is 0 leave at once (IVF: the fp32 pass of the rejected)
 };
+static_assert(std::is_trivially_copyable_v<RefineParams>, "kernel argument");
 
 // One workgroup (256 threads) per query: thread t looks after lists t, t + 256, ... (<= RF_MAXL of them); the k rounds
 // are block-wide arg-max reductions over cached list heads (only the winning list re-reads its head), the walk to tau and
@@ -1240,14 +1243,15 @@ __device__ __forceinline__ float radix_select_kth(const float* e_sc, int NE, int
 //             of this store (unordered; -inf where there are fewer).  Shards exchange them: the k-th largest of all shards' values
 //             is a lower bound of the exact k-th best score of the whole store.
 struct KthParams {
-    const float* score;        // [nq][cap]
-    const int* cnt;            // [nq]
-    int cap, k;
-    const float* eps;          // [nq]
-    float* floor_io;
-    float* lb_out;
-    float* ak_out;             // optional [nq]: a_k itself (the re-rank of a two-half search takes it instead of selecting again)
+    const float* score = nullptr; // [nq][cap]
+    const int* cnt = nullptr;     // [nq]
+    int cap = 0, k = 0;
+    const float* eps = nullptr;   // [nq]
+    float* floor_io = nullptr;
+    float* lb_out = nullptr;
+    float* ak_out = nullptr;      // optional [nq]: a_k itself (the re-rank of a two-half search takes it instead of selecting again)
 };
+static_assert(std::is_trivially_copyable_v<KthParams>, "kernel argument");
 __global__ __launch_bounds__(RF_THREADS) void k_kth_floor(KthParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem_k[];
     float* e_sc = reinterpret_cast<float*>(smem_k);                      // [cap]
@@ -1280,11 +1284,8 @@ __global__ __launch_bounds__(RF_THREADS) void k_kth_floor(KthParams p) {
 // index = no entry), lowered by 2 eps -- a_k over the WHOLE store is >= the rank-th best of any subset for rank >= k, so the
 // floor is <= tau = a_k - 2 eps always.  -inf when the sample holds fewer entries.  One workgroup per query (k_thr_from_parts, its
 // predecessor, walked the 512 list heads `rank` times with a wave: 19 us against 6).
-// clear / clear_n (optional): the query's candidate-score buffer, set to -inf -- the scan that raises its floors inside the launch reads
-// other workgroups' candidates while they are being written: a slot reserved but not written yet must read as "no entry".
 __global__ __launch_bounds__(RF_THREADS) void k_floor_from_sample(const float* __restrict__ score, const int* __restrict__ idx, int n_ent, int rank,
-                                                                 const float* __restrict__ eps, float* __restrict__ thr,
-                                                                 float* __restrict__ clear, int clear_n, int* __restrict__ zero, int zero_n) {
+                                                                 const float* __restrict__ eps, float* __restrict__ thr) {
     extern __shared__ __attribute__((aligned(16))) char smem_f[];
     float* e_sc = reinterpret_cast<float*>(smem_f);                      // [n_ent]
     int* hist = reinterpret_cast<int*>(e_sc + n_ent);                    // [256]
@@ -1292,8 +1293,6 @@ __global__ __launch_bounds__(RF_THREADS) void k_floor_from_sample(const float* _
     const int64_t q = blockIdx.x;
     for (int i = threadIdx.x; i < n_ent; i += RF_THREADS)
         e_sc[i] = idx[q * n_ent + i] != IDX_SENTINEL ? score[q * n_ent + i] : -INFINITY;
-    if (clear) for (int i = threadIdx.x; i < clear_n; i += RF_THREADS) clear[q * clear_n + i] = -INFINITY;
-    if (zero && q == 0) for (int i = threadIdx.x; i < zero_n; i += RF_THREADS) zero[i] = 0;      // (the scan's per-query-tile progress counters)
     const float a = radix_select_kth(e_sc, n_ent, rank, hist, xchg);
     if (threadIdx.x == 0) thr[q] = a > -INFINITY ? a - 2.f * eps[q] : -INFINITY;
 }
@@ -1894,21 +1893,22 @@ constexpr int KX_SLICES = 64;
 constexpr int KX_GROUPS_Y = 4;
 
 struct ExactParams {
-    const void* db; int db_f16;
-    const float* q;            // [nq][dim] fp32 queries (normalised for cosine)
-    const int* sel;            // [*count] query indices
-    const int* count;
-    int64_t n; int dim, k, l2, group;
-    int64_t slice_rows;
-    double* pkey;              // [nq][KX_SLICES][k]
-    int* pidx;
-    int64_t id_base;
-    float* out_dist; int64_t* out_idx; double* out_key;
-    int* host_stats;           // pinned host memory (device-visible): the kernel leaves the search's 6 counters and its batch size ([7]) there, then ...
-    int stamp;                 // ... this value in host_stats[6] (the search's sequence number + 1): the host reads a report only when its stamp is there
-    int nq_report;             // the search's batch size (travels with the report: the host may be many searches ahead when it reads it)
-    int* arrive;               // [query groups] arrival counters of the slices (zero between launches: the last arrival resets its own)
+    const void* db = nullptr; int db_f16 = 0;
+    const float* q = nullptr;  // [nq][dim] fp32 queries (normalised for cosine)
+    const int* sel = nullptr;  // [*count] query indices
+    const int* count = nullptr;
+    int64_t n = 0; int dim = 0, k = 0, l2 = 0, group = 1;
+    int64_t slice_rows = 0;
+    double* pkey = nullptr;    // [nq][KX_SLICES][k]
+    int* pidx = nullptr;
+    int64_t id_base = 0;
+    float* out_dist = nullptr; int64_t* out_idx = nullptr; double* out_key = nullptr;
+    int* host_stats = nullptr; // pinned host memory (device-visible): the kernel leaves the search's 6 counters and its batch size ([7]) there, then ...
+    int stamp = 0;             // ... this value in host_stats[6] (the search's sequence number + 1): the host reads a report only when its stamp is there
+    int nq_report = 0;         // the search's batch size (travels with the report: the host may be many searches ahead when it reads it)
+    int* arrive = nullptr;     // [query groups] arrival counters of the slices (zero between launches: the last arrival resets its own)
 };
+static_assert(std::is_trivially_copyable_v<ExactParams>, "kernel argument");
 
 __device__ __forceinline__ bool kx_better(double ka, int ia, double kb, int ib) { return ka > kb || (ka == kb && ia < ib); }
 __device__ __forceinline__ void exact_merge_slot(const ExactParams& p, int slot, int lane);
@@ -2070,14 +2070,15 @@ __device__ __forceinline__ void exact_merge_slot(const ExactParams& p, int slot,
 
 template <typename KeyT>
 struct ListMergeParams {
-    const KeyT* key;          // [n_parts, nq, k] final distances of each shard
-    const int64_t* idx;       // [n_parts, nq, k] global ids, -1 = unfilled
-    int n_parts, k, l2;
-    int64_t nq;
-    float* out_dist;
-    int64_t* out_idx;
-    double* out_key;          // optional (KeyT == double)
+    const KeyT* key = nullptr;    // [n_parts, nq, k] final distances of each shard
+    const int64_t* idx = nullptr; // [n_parts, nq, k] global ids, -1 = unfilled
+    int n_parts = 0, k = 0, l2 = 0;
+    int64_t nq = 0;
+    float* out_dist = nullptr;
+    int64_t* out_idx = nullptr;
+    double* out_key = nullptr;    // optional (KeyT == double)
 };
+static_assert(std::is_trivially_copyable_v<ListMergeParams<float>> && std::is_trivially_copyable_v<ListMergeParams<double>>, "kernel argument");
 
 template <typename KeyT>
 __global__ __launch_bounds__(256) void k_merge_lists(ListMergeParams<KeyT> p) {
@@ -2292,6 +2293,13 @@ static int merge_lists(int metric, const KeyT* in_key, const int64_t* in_idx, in
     return RADAD_OK;
 }
 
+// byte offsets of a search's buffers in the handle's workspace (knn_search_layout)
+struct SearchLayout {
+    size_t qf = 0, qn = 0, qh = 0, qscale = 0, qconst = 0, eps = 0, thr = 0, ak = 0, cnt = 0, fcount = 0, fsel = 0, ps = 0, pi = 0, xk = 0, xi = 0;
+    size_t cand_elems = 0;     // entries of the candidate buffers / partial lists in ps, pi: the sample pre-pass's lists follow them
+    size_t bytes = 0;
+};
+
 // what phase 2 of a search needs from phase 1 (knn_search_phase1 / _phase2 below)
 struct SearchCtx {
     bool valid = false;
@@ -2302,10 +2310,9 @@ struct SearchCtx {
     bool canonical = false;            // the scan's scores estimate q.y / -|q - y|^2 themselves (comparable across shards); the fp32
                                        // kernels' L2 score 2 q.y - |y|^2 lacks the -|q|^2: a cross-shard bound does not apply to it
     const float* q_use = nullptr;       // fp32 queries as the re-rank reads them (caller's buffer, or the workspace's normalised copy)
-    bool have_ak = false;              // k_kth_floor left a_k in the workspace (o_ak)
+    bool have_ak = false;              // k_kth_floor left a_k in the workspace (ws.ak)
     bool hi_tile = false;              // the certified f16 tile scan took this search
-    size_t o_ak = 0;
-    size_t o_eps = 0, o_thr = 0, o_cnt = 0, o_fcount = 0, o_fsel = 0, o_ps = 0, o_pi = 0, o_xk = 0, o_xi = 0;
+    SearchLayout ws;
 };
 
 // ---- handle -------------------------------------------------------------------------------------------
@@ -2327,11 +2334,6 @@ struct radad_knn_s {
     int opt_wide_min_q = 17;     // smallest batch that takes the 256-query tile scan
     int opt_dense = 1;           // stores of <= RF_STAGE_MAX rows: all scores + select (k_knn_dense) instead of the register-list kernels
     size_t last_o_cnt = 0, last_o_thr = 0; int64_t last_emit_nq = 0;   // the last tile-scan search's candidate counters / floors in the workspace
-    int opt_live_floor = 0;      // 1: the tile scan covers the store in ONE launch and raises its admission floors inside it; 0 (default): one
-                                 // launch per phase.  Measured on one box, three alternations (profiles/r5_ab_*.txt): the one-launch form is
-                                 // 1 % slower in the scan at 1 M x 512 (0.862-0.872 against 0.853-0.860 ms; the step equal within noise: it
-                                 // saves k_kth_floor), 1.4 % at 10 M x 512, 4 % at 50 M x 256 -- ~0.2-0.3 us per tile for the progress atomic
-                                 // and the floor reload, which go to memory past the L2s; the ramps and tails it removes are smaller than that
     int last_scan_phases = 0;    // (radad_knn_last_scan_phases)
     unsigned* stat = nullptr;    // device [3] float bits: max |y'|, max |y' - yh| (y' = y - mu when the plane is centred, else y) and
                                  // max |y| over rows [0, stat_rows)
@@ -2622,16 +2624,15 @@ static bool knn_ensure_hi(radad_knn_t h, hipStream_t st, bool want_plane) {
         hp.in = h->rows + (size_t)from * h->row_bytes(); hp.in_f16 = h->f16;
         hp.hi = have_plane ? h->hi + (size_t)from * h->dim : nullptr;
         hp.scale_out = (have_plane && h->rscale) ? h->rscale + from : nullptr;
-        hp.stat_max = h->stat; hp.eps_out = nullptr; hp.ystat = nullptr;
-        hp.norm_out = nullptr; hp.zero_flags = nullptr; hp.zero_counters = nullptr;
+        hp.stat_max = h->stat;
         hp.n = h->ntotal - from; hp.dim = h->dim;
         // un-centred cosine rows have |x| <= 1: one scale for the whole store (no per-score arithmetic in the scan);
         // an fp16 store is its own plane: statistics only, un-scaled
         hp.fixed_e = h->f16 ? 0 : ((h->metric == RADAD_METRIC_COSINE && !h->cmu) ? 14 : h->uniform_e);
         hp.l2 = h->metric == RADAD_METRIC_L2 ? 1 : 0; hp.exact_ops = h->f16 ? 1 : 0;
         // (a plane that exists keeps its centring for the statistics-only calls too: the statistics are those of ITS operands)
-        hp.mu = h->cmu; hp.mu_norm = h->mu_norm; hp.mu_sq = h->mu_sq; hp.biased = 0;
-        hp.bias_out = (have_plane && h->rbias) ? h->rbias + from : nullptr; hp.qconst_out = nullptr;
+        hp.mu = h->cmu; hp.mu_norm = h->mu_norm; hp.mu_sq = h->mu_sq;
+        hp.bias_out = (have_plane && h->rbias) ? h->rbias + from : nullptr;
         hipLaunchKernelGGL(k_hi_rows, dim3((unsigned)ceil_div64(hp.n, 4)), dim3(256), 0, st, hp);
         if (hipGetLastError() != hipSuccess) return false;
         h->stat_rows = h->ntotal;
@@ -2786,10 +2787,6 @@ int radad_knn_set_option(radad_knn_t h, int option, int value) {
             RADAD_REQUIRE(value == 0 || value == 1, "radad_knn_set_option: DENSE takes 0 or 1");
             h->opt_dense = value;
             return RADAD_OK;
-        case RADAD_KNN_OPT_LIVE_FLOOR:
-            RADAD_REQUIRE(value == 0 || value == 1, "radad_knn_set_option: LIVE_FLOOR takes 0 or 1");
-            h->opt_live_floor = value;
-            return RADAD_OK;
         default:
             radad_set_error("radad_knn_set_option: unknown option %d", option);
             return RADAD_EINVAL;
@@ -2906,6 +2903,8 @@ __global__ __launch_bounds__(256) void k_bf16_to_f32(const unsigned short* __res
 }
 
 static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+template <typename T>
+static inline T* ws_at(radad_knn_t h, size_t off) { return reinterpret_cast<T*>((char*)h->ws + off); }
 
 // K split of the tile scan over two workgroups per tile: when a launch has one tile per workgroup, at most 128 workgroups (half the
 // chip) and at least 16 K steps (dim >= 1024) -- the reference's own store, 25 423 x 5376: 100 tiles of 84 K steps.  Returns 1 or 2 and
@@ -2968,6 +2967,467 @@ static hipError_t knn_wait_last_search(radad_knn_t h) {
     return hipDeviceSynchronize();
 }
 
+// how the certificates of earlier searches fared: any report that has arrived and was not looked at yet (see the handle); this
+// search takes over slot search_seq & 1
+// (until round 4 an event behind every search was waited for here: an event record between dependent kernels costs the stream ~6 us,
+// a tenth of an online search.  The exact kernel stamps its report; one that has not arrived yet is simply not looked at.)
+static void knn_consume_reports(radad_knn_t h) {
+    for (int sl = 0; sl < 2; ++sl) {
+        volatile int* rep = reinterpret_cast<volatile int*>(h->host_count + 8 * sl);
+        const int stamp = rep[6];
+        if (stamp == 0 || stamp == h->stamp_seen[sl]) continue;
+        std::atomic_thread_fence(std::memory_order_acquire);
+        const int rejected = rep[0], rep_nq = rep[7];
+        std::atomic_thread_fence(std::memory_order_acquire);
+        if (rep[6] != stamp) continue;                    // the device is rewriting the slot right now: next search
+        h->stamp_seen[sl] = stamp;
+        ++h->reports_consumed;
+        // the report's own search: the one search at or below search_seq with that stamp's low 30 bits
+        const uint64_t cur30 = h->search_seq & 0x3fffffff, rep30 = (uint64_t)(stamp - 1);
+        const uint64_t rep_seq = h->search_seq - ((cur30 - rep30) & 0x3fffffff);
+        // (a report from before the last change of the plane or of the buffers says nothing about them)
+        if (h->hi_skip == 0 && rep_nq >= 64 && (int64_t)rejected * 4 > rep_nq && rep_seq >= h->tuned_at) knn_retune_after_mass_rejection(h);
+    }
+}
+
+// what one search scans with: the kind of scan, its launch layout, its list / buffer sizes and how its queries are prepared
+struct ScanPlan {
+    int kind = RADAD_SCAN_F32_TILE;  // RADAD_SCAN_*
+    int64_t nq = 0;
+    int k = 0, l2 = 0;
+    bool cert = false;               // k <= KNN_CERT_MAX_K: certified re-rank + exact kernel (beyond: k + margin candidates, no certificate)
+    int n_qtiles = 0, n_splits = 0;  // workgroups: query tiles x row splits (the streaming kernels: 1 x n_splits)
+    int64_t chunk_rows = 0;
+    int ksel = 0;                    // list length of the fp32 tile kernels: k + margin
+    int ksel_sq = 0;                 // ... of the small-batch kernels
+    int s_splits = 0;                // tile scan: tiles of the sample pre-pass
+    int emit_cap = 0;                // tile scan: entries of a query's candidate buffer
+    int cap = 0;                     // candidates the re-rank can take per query
+    int plen = 0, n_parts = 0;       // entries of a partial list / candidate buffer, lists per query
+    int sq_rows_per_wave = 0;        // small batches: rows per wave (per workgroup in the K-split form)
+    bool sq_ksplit = false;          // small batch over a small store of wide rows: k_knn_hi_smallq_ksplit
+    size_t sq_lds = 0;               // small batches: LDS of the streaming kernel
+    int dense_plen = 0;
+    int xgroup = 1;                  // queries per workgroup of the exact kernel
+    bool hi_q = false;               // f16 queries with a per-query scale (the certified f16 kernels)
+    bool biased = false;             // the scale + bias variant of the f16 kernels (RSC 2, 3)
+    bool prep = false;               // k_hi_rows prepares the queries: it also normalises and clears the flags
+    const float* mu = nullptr;       // centred plane: the queries are centred the same way
+    bool f16_queries() const { return kind == RADAD_SCAN_HI_TILE || kind == RADAD_SCAN_HI_SMALLQ || kind == RADAD_SCAN_F16_TILE; }
+};
+
+// The choice of the scan.  Its side effects -- counting hi_skip down, verify_next, building the plane (knn_ensure_hi) -- happen in this
+// order and under these conditions on purpose: the next searches of the handle see them.
+static int knn_plan_scan(radad_knn_t h, int64_t nq, int k, int margin, hipStream_t st, ScanPlan* out) {
+    ScanPlan p;
+    p.nq = nq; p.k = k; p.l2 = h->metric == RADAD_METRIC_L2 ? 1 : 0;
+    p.cert = k <= KNN_CERT_MAX_K;
+    p.ksel = k + margin;
+    knn_geometry(std::max<int64_t>(h->ntotal, 1), nq, &p.n_qtiles, &p.n_splits, &p.chunk_rows);
+    const int ksel = p.ksel;
+    bool use_hi = false, skipped_hi = false;
+    // small batches (<= 16 queries: the online predict() search, pipeline.py:1038-1054, is ONE query of dim 5376 / 3584) stream the
+    // store; the kernels park only the nq queries handed over in LDS, so any dim goes as long as that block fits beside the slots
+    // (16 queries of dim 5376 do not: such a batch takes the tile kernels like a large one)
+    const size_t sq_slot_bytes = std::max<size_t>(sizeof(float2) * 4 * SQ_NQ * SQ_SLOTS, sizeof(u64) * 3 * SQ_NQ * 32) + sizeof(int) * 4 * SQ_NQ;
+    const size_t sq_lds_hi = sizeof(_Float16) * (size_t)nq * (h->dim + 8) + sq_slot_bytes;
+    const size_t sq_lds_f32 = sizeof(float) * (size_t)nq * (h->dim + 4) + sq_slot_bytes;
+    const bool sq_fits = nq <= SQ_NQ && ksel <= 32 &&
+                         ((!h->hi_off && h->dim % 64 == 0 && sq_lds_hi <= SQ_LDS_BUDGET) || (!h->f16 && h->dim % 32 == 0 && sq_lds_f32 <= SQ_LDS_BUDGET));
+    // the certified tile scan: any k the certificate covers (its candidate buffers are sized from k); the floor's rank k + margin
+    // must exist in the sample (16 entries per sample tile)
+    if (p.cert && (nq >= h->opt_wide_min_q || !sq_fits) && h->ntotal > 0 && h->dim % 64 == 0 && !h->hi_off) {
+        int wq, ws; int64_t wc;
+        knn_geometry_wide(h->ntotal, nq, &wq, &ws, &wc);
+        // the sample pre-pass: one tile per workgroup, at most KW_SAMPLE_SPLITS tiles and 1/8 of the store (whatever the number of
+        // query tiles: every phase of the scan is sized from the sample, a small sample means more phases)
+        // ... and about 3 % of it: the pre-pass multiplies every query tile with its rows, so on a shard of a row-sharded store -- 1/G of
+        // the rows against G times the queries -- a fixed 16 384-row sample was 12 % of the scan's own work at G = 8 (0.16 of 1.7 ms);
+        // large enough, though, for the floor's rank to exist twice over (16 entries per sample tile)
+        const int64_t tiles = h->ntotal / KW_M;
+        int64_t want = (tiles * 3 / 100 + 4) / 8 * 8;
+        const int64_t need = ((int64_t)(2 * ksel + KW_SAMPLE_LIST - 1) / KW_SAMPLE_LIST + 7) / 8 * 8;
+        want = std::max<int64_t>(std::max<int64_t>(want, need), 8);
+        // ... but never fewer tiles than fill ONE round of the chip: the pre-pass is one tile per workgroup, its time is that one
+        // tile's latency whether 32 or 256 workgroups run it, and a larger sample is a tighter first floor (BASELINE config 2's
+        // 100 k rows took 8 tiles = 2048 rows: every tile of the scan's first layer then admitted ~2 rows per query -- 512 returning
+        // atomics per workgroup and tile; with 48 tiles the whole store is one launch behind the sample's floor alone)
+        want = std::max<int64_t>(want, std::min<int64_t>(KW_SAMPLE_SPLITS, (256 / std::max(1, std::min(wq, 256))) / 8 * 8));
+        p.s_splits = (int)std::min<int64_t>(std::min<int64_t>(KW_SAMPLE_SPLITS, want), tiles / 8 / 8 * 8);
+        if (p.s_splits >= 8 && p.s_splits * KW_SAMPLE_LIST >= 2 * ksel) {
+            if (h->hi_skip > 0) { --h->hi_skip; skipped_hi = true; if (h->hi_skip == 0) h->verify_next = true; }
+            else if (knn_ensure_hi(h, st, true)) { use_hi = true; p.n_qtiles = wq; }
+        }
+    }
+    if (!use_hi && p.cert && !knn_ensure_hi(h, st, false)) { radad_set_error("store statistics could not be computed"); return RADAD_EHIP; }
+    const bool smallq_geom = !use_hi && nq <= SQ_NQ && ksel <= 32 && h->ntotal > 0;
+    // the small batch over the f16 plane (certified like the tile scan): stores the plane is kept for, or fp16 stores
+    bool smallq_hi = false;
+    if (smallq_geom && p.cert && h->opt_smallq_hi && h->dim % 64 == 0 && h->ntotal >= 16384 && !h->hi_off && !skipped_hi &&
+        sq_lds_hi <= SQ_LDS_BUDGET) {
+        // (every search that would take a certified f16 kernel counts the skip down: a handle that only sees small batches after a
+        // mass rejection used to stay on the fp32 kernel for ever)
+        if (h->hi_skip > 0) --h->hi_skip;
+        else smallq_hi = knn_ensure_hi(h, st, true);
+    }
+    // a small fp32 store (the IVF index's centroids; a database of a few thousand files): every score + select on the staged copy
+    p.dense_plen = (int)((std::max<int64_t>(h->ntotal, 1) + 3) / 4 * 4);
+    const bool dense = p.cert && !use_hi && !smallq_hi && !h->f16 && h->opt_dense && h->ntotal >= 1 &&
+                       h->ntotal <= (nq <= SQ_NQ ? RF_STAGE_MAX_SMALLQ : RF_STAGE_MAX) && h->dim % 16 == 0 && nq * (int64_t)p.dense_plen <= ((int64_t)1 << 24);
+    const bool smallq = smallq_geom && !dense && !smallq_hi && !h->f16 && h->dim % 32 == 0 && sq_lds_f32 <= SQ_LDS_BUDGET;
+    // a small store of wide rows (the reference's own: 25 423 x 5376) has too few 16-row steps to occupy the chip with one wave per
+    // row slice: the K-split form puts four waves on every step
+    p.sq_ksplit = smallq_hi && h->dim >= 1024 && ceil_div64(h->ntotal, 16) < 4096;
+    // (its lists are 16 entries for k <= 16 -- the reference's k = 15 included -- instead of k + 6 <= 32: half the list registers,
+    // twice the waves per SIMD to hide the HBM latency behind.  A workgroup whose 16-entry list is used up by rows within the
+    // threshold rejects the query; the exact kernel over so small a store costs ~0.3 ms)
+    // (the same 16-entry lists on every f16 small-batch scan since round 4: k_knn_hi_smallq<32> streams the 1 M x 512 store in 0.40 ms,
+    // <16> in 0.20 -- 155 VGPRs against the 32-entry lists' panel of half the loads in flight)
+    p.ksel_sq = (smallq_hi && k <= 16) ? 16 : ksel;
+    if (p.sq_ksplit) {
+        int64_t rpg = 16;
+        while (ceil_div64(h->ntotal, rpg) * p.ksel_sq > RF_STAGE_MAX_SMALLQ) rpg += 16;
+        p.sq_rows_per_wave = (int)rpg;                // (rows per WORKGROUP in this form)
+        p.n_splits = (int)ceil_div64(h->ntotal, rpg);
+        p.n_qtiles = 1;
+    } else if (smallq || smallq_hi) {
+        // a wave streams >= 128 KB (128 rows at dim 512) so that its lists' hand-over stays small beside the stream, but no more
+        // rows than leave 8 waves for every CU; the lists of a query (one per workgroup) should fit the re-rank's staged form
+        // one full round of resident waves: 1024 SIMDs x the waves per SIMD the kernel's registers allow (k_knn_hi_smallq<16>: 155
+        // VGPRs = 3; the 32-entry and fp32 variants: 2).  (Measured: no difference against 2048 waves on the 1 M x 512 store -- 0.2075
+        // vs 0.208 ms, 4.93 TB/s either way: the stream is not limited by the number of waves in flight.)
+        const int64_t waves_wanted = 1024 * ((smallq_hi && p.ksel_sq <= 16) ? 3 : 2);
+        const size_t rb = smallq_hi ? (size_t)h->dim * 2 : (size_t)h->dim * 4;
+        const int64_t rows_min = std::max<int64_t>(16, std::min<int64_t>(128, ceil_div64(ceil_div64(128 * 1024, (int64_t)rb), 16) * 16));
+        int64_t rpw = std::max<int64_t>(ceil_div64(ceil_div64(h->ntotal, waves_wanted), 16) * 16, rows_min);
+        while (rpw < 128 && ceil_div64(ceil_div64(h->ntotal, rpw), 4) * p.ksel_sq > RF_STAGE_MAX_SMALLQ) rpw += 16;
+        p.sq_rows_per_wave = (int)rpw;
+        p.n_splits = (int)ceil_div64(ceil_div64(h->ntotal, rpw), 4);              // workgroups of 4 waves = lists per query
+        p.n_qtiles = 1;
+    }
+    p.sq_lds = smallq_hi ? sq_lds_hi : sq_lds_f32;
+    const bool f16_tile = !use_hi && !smallq_hi && h->f16 && ksel <= 32 && h->dim % 64 == 0;
+    p.kind = use_hi ? RADAD_SCAN_HI_TILE : dense ? RADAD_SCAN_F32_DENSE : smallq_hi ? RADAD_SCAN_HI_SMALLQ : smallq ? RADAD_SCAN_F32_SMALLQ
+           : f16_tile ? RADAD_SCAN_F16_TILE : RADAD_SCAN_F32_TILE;
+    p.emit_cap = use_hi ? std::min(RF_STAGE_MAX, std::max(1024 * h->cap_boost, 32 * ksel)) : 0;
+    h->last_qtiles = p.n_qtiles;                       // (the dense kernel's own query tiles are not reported)
+    if (dense) { p.n_qtiles = (int)ceil_div64(nq, 16); p.n_splits = 1; }
+    h->last_threads = use_hi ? KW_THREADS : ((smallq || smallq_hi || dense) ? SQ_THREADS : KNN_THREADS);
+    h->last_kind = p.kind;
+    p.plen = use_hi ? p.emit_cap : dense ? p.dense_plen : p.ksel_sq;   // entries of a partial list / of the candidate buffer
+    p.n_parts = (use_hi || dense) ? 1 : p.n_splits;
+    // (dense: eps of exact fp32 products is ~1e-6 of |q||y| -- hardly a row beyond the k best is within 2 eps; k + 32 candidates keep
+    // the re-rank's workgroup at 34 KB of LDS for 4096 staged scores, four per CU instead of three: the IVF coarse step's 1024
+    // workgroups in one round.  More near-ties than that reject the query: exact kernel.)
+    // (a handle that has widened its candidate buffers -- cap_boost: a store whose rows crowd within 2 eps of the k-th best -- also
+    // re-ranks four times as many: the fp32 funnel in front of the float64 re-score takes them at ~2 KB of row reads each)
+    p.cap = p.cert ? (dense ? k + KNN_CERT_EXTRA : std::max(k + KNN_CERT_EXTRA, KNN_CERT_CAP * (use_hi ? h->cap_boost : 1))) : ksel;
+    p.xgroup = (int)std::max<size_t>(1, std::min<size_t>(8, (size_t)(64 * 1024) / ((size_t)h->dim * 4)));
+    p.hi_q = use_hi || smallq_hi;
+    p.mu = (p.hi_q && !h->f16) ? h->cmu : nullptr;
+    p.biased = p.hi_q && (p.l2 || p.mu);
+    p.prep = p.cert || use_hi || f16_tile;
+    *out = p;
+    return RADAD_OK;
+}
+
+// The search's workspace: qf (decoded bf16) | qn (normalised) | qh (f16 queries) | qscale | qconst | eps | thr_init | a_k | cand_cnt |
+// flag_count + statistics | flag_sel | part_score | part_idx | exact partial keys | ids.  Byte offsets into the handle's workspace.
+static SearchLayout knn_search_layout(radad_knn_t h, const ScanPlan& p, int q_dtype) {
+    const int64_t nq = p.nq;
+    const size_t qrow_f32 = al256((size_t)nq * h->dim * sizeof(float));
+    const size_t b_vec = al256((size_t)nq * sizeof(float));
+    SearchLayout L;
+    // (the sample pre-pass's lists live BEHIND the candidate buffers, not in them: k_floor_from_sample writes a query's floor while
+    // other queries' sample lists are still being read)
+    L.cand_elems = (size_t)nq * (size_t)p.n_parts * p.plen;
+    const size_t part_elems = L.cand_elems + (p.kind == RADAD_SCAN_HI_TILE ? (size_t)nq * KW_SAMPLE_SPLITS * KW_SAMPLE_LIST : 0);
+    const size_t b_part = al256(part_elems * sizeof(float));
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += bytes; return o; };
+    L.qf = take(q_dtype == RADAD_Q_BF16 ? qrow_f32 : 0);
+    L.qn = take(h->metric == RADAD_METRIC_COSINE ? qrow_f32 : 0);
+    L.qh = take(p.f16_queries() ? al256((size_t)nq * h->dim * 2) : 0);
+    L.qscale = take(b_vec);
+    L.qconst = take(b_vec);
+    L.eps = take(b_vec);
+    L.thr = take(b_vec);
+    L.ak = take(b_vec);            // a_k of the candidates (two-half searches: k_kth_floor -> k_merge_refine)
+    L.cnt = take(b_vec);           // cand_cnt [nq] int (zeroed by k_hi_rows with the counters)
+    L.fcount = take(256);          // flag_count + statistics
+    L.fsel = take(b_vec);
+    L.ps = take(b_part);
+    L.pi = take(b_part);
+    L.xk = take(p.cert ? al256((size_t)nq * KX_SLICES * p.k * sizeof(double)) : 0);
+    L.xi = take(p.cert ? al256((size_t)nq * KX_SLICES * p.k * sizeof(int)) : 0);
+    L.bytes = off;
+    return L;
+}
+
+// ---- queries: decode, normalise, round (+ scale) to f16, error bound.  Returns the fp32 queries the scan and the re-rank read.
+static const float* knn_prepare_queries(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, const void* q_in, int q_dtype, hipStream_t st) {
+    const int64_t nq = p.nq;
+    const float* q_use = (const float*)q_in;
+    if (q_dtype == RADAD_Q_BF16) {
+        float* qf = ws_at<float>(h, L.qf);
+        const int64_t ne = nq * h->dim;
+        hipLaunchKernelGGL(k_bf16_to_f32, dim3((unsigned)ceil_div64(ne, 1024)), dim3(256), 0, st, (const unsigned short*)q_in, qf, ne);
+        q_use = qf;
+    }
+    const bool cosine = h->metric == RADAD_METRIC_COSINE;
+    // (with prep the normalisation happens inside k_hi_rows, which reads the raw queries)
+    if (cosine && !p.prep)
+        hipLaunchKernelGGL(k_rows_prepare<float>, dim3((unsigned)ceil_div64(nq, 4)), dim3(256), 0, st, q_use, ws_at<float>(h, L.qn), (float*)nullptr, nq, h->dim, 2);
+    // (|q|^2 is not needed: ranking uses 2 q.y - |y|^2 and the reported distance is re-scored exactly)
+    if (p.prep) {
+        const bool f16_tile = p.kind == RADAD_SCAN_F16_TILE;
+        HiRowsParams hp;
+        hp.in = q_use;
+        hp.hi = p.f16_queries() ? ws_at<_Float16>(h, L.qh) : nullptr;
+        hp.scale_out = p.hi_q ? ws_at<float>(h, L.qscale) : nullptr;
+        hp.eps_out = p.cert ? ws_at<float>(h, L.eps) : nullptr; hp.ystat = h->stat;
+        hp.n = nq; hp.dim = h->dim;
+        hp.fixed_e = p.hi_q ? HI_E_PER_ROW : 0;          // the fp16 tile kernel multiplies un-scaled fp16 queries
+        hp.l2 = p.l2; hp.exact_ops = p.f16_queries() ? 0 : 1;
+        hp.norm_out = cosine ? ws_at<float>(h, L.qn) : nullptr;
+        hp.zero_flags = p.cert ? ws_at<int>(h, L.cnt) : nullptr; hp.zero_counters = p.cert ? ws_at<int>(h, L.fcount) : nullptr;
+        hp.mu = p.mu; hp.mu_norm = p.mu ? h->mu_norm : 0.f; hp.mu_sq = p.mu ? h->mu_sq : 0.f; hp.biased = (p.biased || (f16_tile && p.l2)) ? 1 : 0;
+        hp.qconst_out = p.biased ? ws_at<float>(h, L.qconst) : nullptr;
+        launch_hi_rows(hp, st);
+    }
+    return cosine ? ws_at<const float>(h, L.qn) : q_use;
+}
+
+// ---- the certified f16 tile scan (knn_hi.inc) -------------------------------------------------------------------------------------
+// The phases of the scan, as row boundaries 0 = r[0] < r[1] < ... = n: a floor taken from m rows admits ~(rank / m) of what it is
+// applied to, so every launch covers at most 8 x the rows its floor was taken from -- the first 8 x the sample (phase0 rows) with the
+// sample's floor, the next 8 x that with the floor the candidates so far give (k_kth_floor), and so on: 2 launches up to 1.2 M rows,
+// 3 up to 9.5 M.  Each admits ~8 (k + margin) rows per query; the candidate buffer holds 32 (k + margin) (>= 1024): more (stores of
+// near-duplicates) rejects the query.  `one_go`: the sample's floor alone filters the store to a third of the buffer (~(k + margin) N /
+// sample rows): one launch.  (One launch with the floors raised inside it was measured slower and removed: DESIGN §4.1.)
+static std::vector<int64_t> knn_hi_phases(int64_t n, int64_t nq, int64_t phase0, bool one_go) {
+    std::vector<int64_t> r{0};
+    for (int64_t r0 = 0, span = phase0; r0 < n; span *= 8) {
+        // (a last phase of less than a quarter of its predecessor is not worth a launch of its own: it joins it)
+        int64_t r1 = std::min<int64_t>(n, r0 + span);
+        if (n - r1 < span / 4) r1 = n;
+        if (r0 == 0 && one_go) r1 = n;
+        // A launch deals whole tiles to its row splits, ceil(tiles / splits) each: what decides its time is that quotient, and a
+        // remainder of a few tiles costs a whole extra tile per workgroup (64 + 260 tiles over 128 splits = 1 + 3 tile times, the last
+        // round of the second launch nearly empty; 68 + 256 tiles = 1 + 2).  When the LAST launch follows this one, up to a quarter
+        // more tiles move into this one if that lowers the sum of the two quotients.  (BASELINE config 2 -- 100 k rows = 64 + 327
+        // tiles -- gains nothing from it: 1 + 3 either way; its scan stays at 0.27 of the MFMA peak, 1 564 tile tasks over 256 CUs.)
+        if (r1 < n && (n - r1 <= span * 8 || n - r1 - span * 8 < span * 2)) {
+            auto tile_time = [&](int64_t rows) {
+                int gq, gs; int64_t gc;
+                knn_geometry_wide(rows, nq, &gq, &gs, &gc);
+                return gc / KW_M;
+            };
+            const int64_t t_this = ceil_div64(r1 - r0, KW_M), t_rest = ceil_div64(n - r1, KW_M);
+            int64_t best = tile_time(r1 - r0) + tile_time(n - r1), best_s = 0;
+            for (int64_t sft = 1; sft <= std::min<int64_t>(t_this / 4, t_rest - 1); ++sft) {
+                const int64_t c = tile_time(r1 - r0 + sft * KW_M) + tile_time(n - r1 - sft * KW_M);
+                if (c < best) { best = c; best_s = sft; }
+            }
+            r1 += best_s * KW_M;
+        }
+        r.push_back(r1);
+        r0 = r1;
+    }
+    return r;
+}
+
+// the tile scan's kernel for one RSC (knn_hi.inc), the sample pre-pass's or the scan's own
+static auto knn_hi_kernel(int rsc, bool sample) -> void (*)(KnnHiParams) {
+    switch (rsc) {
+        case 0: return sample ? k_knn_hi_sample<0> : k_knn_hi<0>;
+        case 1: return sample ? k_knn_hi_sample<1> : k_knn_hi<1>;
+        case 2: return sample ? k_knn_hi_sample<2> : k_knn_hi<2>;
+        default: return sample ? k_knn_hi_sample<3> : k_knn_hi<3>;
+    }
+}
+
+static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, hipStream_t st) {
+    const int64_t nq = p.nq;
+    float* ps = ws_at<float>(h, L.ps);
+    int* pi = ws_at<int>(h, L.pi);
+    float* eps = ws_at<float>(h, L.eps);
+    float* thr_init = ws_at<float>(h, L.thr);
+    KnnHiParams wp;
+    wp.db = h->f16 ? (const void*)h->rows : (const void*)h->hi;
+    wp.rscale = h->f16 ? nullptr : h->rscale;
+    wp.uscale = h->f16 ? 1.0f : (h->uniform_e != HI_E_PER_ROW ? ldexpf(1.0f, -h->uniform_e) : (h->metric == RADAD_METRIC_COSINE ? 0x1p-14f : 1.0f));
+    // bias of the scale + bias variant: a centred plane has its own (|y - mu|^2 or mu.y); un-centred L2 uses |y|^2 as stored
+    wp.rbias = p.mu ? h->rbias : h->ynorm; wp.bias_sign = p.l2 ? -1.f : 1.f; wp.mult = p.l2 ? 2.f : 1.f;
+    wp.qconst = p.biased ? ws_at<float>(h, L.qconst) : nullptr;
+    wp.q = ws_at<_Float16>(h, L.qh); wp.qscale = ws_at<float>(h, L.qscale);
+    wp.n = h->ntotal; wp.nq = (int)nq; wp.row_bytes = h->dim * 2; wp.l2 = p.l2;
+    wp.n_qtiles = p.n_qtiles; wp.part_score = ps; wp.part_idx = pi;
+    wp.cand_cap = p.emit_cap; wp.cand_cnt = ws_at<int>(h, L.cnt);
+#ifdef RADAD_DEBUG_HOOKS        // timing experiments only (make exp); never in the shipped library
+    { const char* dbg = getenv("RADAD_DEBUG_KNN"); wp.debug = dbg ? atoi(dbg) : 0; }
+    {   // RADAD_KNN_STAMPS=<file>: in-kernel s_memtime stamps of the 8 waves of workgroup 0, dumped after the scan (synchronises)
+        static unsigned long long* stamp_buf = nullptr;
+        if (getenv("RADAD_KNN_STAMPS")) {
+            if (!stamp_buf) (void)hipMalloc(&stamp_buf, 8 * 4096 * 8);
+            (void)hipMemsetAsync(stamp_buf, 0, 8 * 4096 * 8, st);
+            wp.stamps = stamp_buf;
+        }
+    }
+#endif
+    const int rsc = p.biased ? (wp.rscale ? 2 : 3) : (wp.rscale ? 1 : 0);
+    const auto scan = knn_hi_kernel(rsc, false), sample = knn_hi_kernel(rsc, true);
+    const size_t lds = knn_hi_lds_bytes();
+    RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(sample), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // sample pre-pass: the (k + margin)-th best score over the first rows of the store is a score at least k rows reach, so the
+    // scan admits from it (minus 2 eps) instead of -inf (the score of a (row, query) pair does not depend on the tiling).
+    // Its lists live behind the candidate buffers.
+    {
+        KnnHiParams sp = wp;
+        // The sample's tiles are SPREAD over the store (every (tiles / s_splits)-th one).  The first s_splits tiles, as until round 4,
+        // are a sample of the store only while its rows are in random order: on a store whose rows arrive cluster by cluster
+        // (add_vectors_batch appends 10 000 rows at a time, vector_database.py:134-138) a query of the LAST cluster got a floor
+        // from rows of the first -- so loose that every row of its own cluster passed it, the candidate buffer overflowed and the
+        // certificate rejected all 256 queries of a batch (tests/test_gpu_reference_shapes.py::test_a_store_that_drifts...).
+        sp.n_splits = p.s_splits; sp.chunk_rows = KW_M;
+        sp.part_score = ps + L.cand_elems; sp.part_idx = pi + L.cand_elems;
+        sp.chunk_stride = std::max<int64_t>(1, (h->ntotal / KW_M) / p.s_splits) * KW_M;
+        const int sq_grid = sp.n_qtiles <= 8 ? sp.n_qtiles : (sp.n_qtiles + 7) / 8 * 8;
+        // (the K split's scratch is indexed by row0 / KW_M: the sample's tiles lie anywhere in the store)
+        sp.ksplit = knn_tile_ksplit(h, sq_grid, sp.n_splits, KW_M, h->ntotal, st);
+        sp.kacc = h->kacc; sp.kflag = h->kflag;
+        hipLaunchKernelGGL(sample, dim3((unsigned)(sq_grid * sp.n_splits * sp.ksplit)), dim3(KW_THREADS), lds, st, sp);
+        const int n_ent = sp.n_splits * KW_SAMPLE_LIST;
+        hipLaunchKernelGGL(k_floor_from_sample, dim3((unsigned)nq), dim3(RF_THREADS), (size_t)n_ent * 4 + 1040, st, (const float*)sp.part_score,
+                           (const int*)sp.part_idx, n_ent, p.ksel, (const float*)eps, thr_init);
+        wp.thr_init = thr_init;
+    }
+    const bool one_go = (int64_t)p.ksel * h->ntotal <= (int64_t)(p.emit_cap / 3) * p.s_splits * KW_M;
+    const std::vector<int64_t> r = knn_hi_phases(h->ntotal, nq, (int64_t)8 * p.s_splits * KW_M, one_go);
+    h->last_scan_launches = h->last_scan_phases = (int)r.size() - 1;
+    for (size_t i = 0; i + 1 < r.size(); ++i) {       // rows [r0, r1) of the store, one full round (or two) of workgroups
+        const int64_t r0 = r[i], r1 = r[i + 1];
+        if (r0 > 0) {
+            KthParams kp;
+            kp.score = ps; kp.cnt = wp.cand_cnt; kp.cap = p.emit_cap; kp.k = p.k; kp.eps = eps; kp.floor_io = thr_init;
+            hipLaunchKernelGGL(k_kth_floor, dim3((unsigned)nq), dim3(RF_THREADS), (size_t)p.emit_cap * 4 + 1040, st, kp);
+        }
+        KnnHiParams rp = wp;
+        rp.db = (const char*)wp.db + (size_t)r0 * wp.row_bytes;
+        rp.rscale = wp.rscale ? wp.rscale + r0 : nullptr;
+        rp.rbias = wp.rbias ? wp.rbias + r0 : nullptr;
+        rp.n = r1 - r0; rp.id_off = r0;
+        rp.loose_floor = (r0 == 0 && r1 == h->ntotal && p.s_splits < KW_SAMPLE_SPLITS) ? 1 : 0;      // one launch behind a small sample
+        // (the counting form for the FIRST phase of a large store -- its floor is the sample's, ~64 candidates per tile -- was measured
+        // too: 0.883-0.887 against 0.874-0.877 ms per search, three alternations on one box, profiles/r5_ab_counting_emit_phase0.txt: no)
+        int gq, gs; int64_t gc;
+        knn_geometry_wide(rp.n, nq, &gq, &gs, &gc);
+        rp.n_splits = gs; rp.chunk_rows = gc; rp.chunk_stride = gc;
+        h->last_splits = gs;
+        const int gq_grid = gq <= 8 ? gq : (gq + 7) / 8 * 8;                      // (more than 8 query tiles: whole groups of 8, see the kernel)
+        rp.ksplit = knn_tile_ksplit(h, gq_grid, gs, gc, rp.n, st);
+        rp.kacc = h->kacc; rp.kflag = h->kflag;
+        h->prof.begin(st);      // the event pair brackets a scan launch only (the kernel the roofline is quoted on; the phases of one
+                                // search are two entries)
+        hipLaunchKernelGGL(scan, dim3((unsigned)(gq_grid * gs * rp.ksplit)), dim3(KW_THREADS), lds, st, rp);
+        h->prof.end(st);
+    }
+#ifdef RADAD_DEBUG_HOOKS
+    if (wp.stamps) {
+        std::vector<unsigned long long> hs(8 * 4096);
+        (void)hipStreamSynchronize(st);
+        (void)hipMemcpy(hs.data(), wp.stamps, hs.size() * 8, hipMemcpyDeviceToHost);
+        if (FILE* f = fopen(getenv("RADAD_KNN_STAMPS"), "wb")) { fwrite(hs.data(), 8, hs.size(), f); fclose(f); }
+    }
+#endif
+    return RADAD_OK;
+}
+
+// ---- the other scans: one launch each ---------------------------------------------------------------------------------------------
+static void knn_scan_dense(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, const float* q_use, hipStream_t st) {
+    DenseParams dp;
+    dp.db = (const float*)h->rows; dp.ynorm = h->ynorm; dp.q = q_use; dp.n = h->ntotal; dp.nq = (int)p.nq; dp.dim = h->dim; dp.l2 = p.l2;
+    dp.plen = p.dense_plen; dp.score = ws_at<float>(h, L.ps); dp.idx = ws_at<int>(h, L.pi); dp.cnt = ws_at<int>(h, L.cnt);
+    h->prof.begin(st);
+    if (p.nq <= SQ_NQ) hipLaunchKernelGGL((k_knn_dense<1, 1>), dim3((unsigned)ceil_div64(p.dense_plen, 64), (unsigned)ceil_div64(p.nq, 16)), dim3(256), 0, st, dp);
+    else hipLaunchKernelGGL((k_knn_dense<2, 4>), dim3((unsigned)ceil_div64(p.dense_plen, 128), (unsigned)ceil_div64(p.nq, 64)), dim3(256), 0, st, dp);
+    h->prof.end(st);
+}
+
+// a kernel of 16- or 32-entry lists with its dynamic LDS, set and launched on n_splits workgroups of SQ_THREADS
+template <typename Params>
+static int knn_launch_smallq(radad_knn_t h, void (*fn)(Params), const Params& sp, int n_splits, size_t lds, hipStream_t st) {
+    RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    h->prof.begin(st);
+    hipLaunchKernelGGL(fn, dim3((unsigned)n_splits), dim3(SQ_THREADS), lds, st, sp);
+    h->prof.end(st);
+    return RADAD_OK;
+}
+
+static int knn_scan_hi_smallq(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, hipStream_t st) {
+    SmallQHiParams sp;
+    sp.db = h->f16 ? (const _Float16*)h->rows : h->hi;
+    sp.rscale = h->f16 ? nullptr : h->rscale;
+    sp.uscale = h->f16 ? 1.0f : (h->uniform_e != HI_E_PER_ROW ? ldexpf(1.0f, -h->uniform_e) : (h->metric == RADAD_METRIC_COSINE ? 0x1p-14f : 1.0f));
+    sp.rbias = p.biased ? (p.mu ? h->rbias : h->ynorm) : nullptr; sp.bias_sign = p.l2 ? -1.f : 1.f; sp.mult = p.l2 ? 2.f : 1.f;
+    sp.qconst = p.biased ? ws_at<float>(h, L.qconst) : nullptr;
+    sp.q = ws_at<_Float16>(h, L.qh); sp.qscale = ws_at<float>(h, L.qscale); sp.n = h->ntotal; sp.nq = (int)p.nq; sp.dim = h->dim; sp.k = p.ksel_sq;
+    sp.rows_per_wave = p.sq_rows_per_wave; sp.n_parts = p.n_splits; sp.part_score = ws_at<float>(h, L.ps); sp.part_idx = ws_at<int>(h, L.pi);
+    const bool l16 = p.ksel_sq <= 16;
+    const auto fn = p.sq_ksplit ? (l16 ? k_knn_hi_smallq_ksplit<16> : k_knn_hi_smallq_ksplit<32>) : (l16 ? k_knn_hi_smallq<16> : k_knn_hi_smallq<32>);
+    return knn_launch_smallq(h, fn, sp, p.n_splits, p.sq_lds, st);
+}
+
+static int knn_scan_f32_smallq(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, const float* q_use, hipStream_t st) {
+    SmallQParams sp;
+    sp.db = (const float*)h->rows; sp.ynorm = h->ynorm; sp.q = q_use; sp.n = h->ntotal; sp.nq = (int)p.nq; sp.dim = h->dim; sp.k = p.ksel;
+    sp.l2 = p.l2; sp.rows_per_wave = p.sq_rows_per_wave; sp.n_parts = p.n_splits; sp.part_score = ws_at<float>(h, L.ps); sp.part_idx = ws_at<int>(h, L.pi);
+    return knn_launch_smallq(h, p.ksel <= 16 ? k_knn_f32_smallq<16> : k_knn_f32_smallq<32>, sp, p.n_splits, p.sq_lds, st);
+}
+
+// the fp32 (or fp16-operand) tile kernels, lists of k + margin per (query, split)
+static int knn_scan_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, const float* q_use, hipStream_t st) {
+    const bool f16_tile = p.kind == RADAD_SCAN_F16_TILE;
+    KnnParams kp;
+    kp.db = h->rows; kp.db_f16 = h->f16; kp.ynorm = h->ynorm; kp.q = f16_tile ? (const void*)ws_at<_Float16>(h, L.qh) : (const void*)q_use;
+    kp.n = h->ntotal; kp.nq = (int)p.nq; kp.dim = h->dim; kp.k = p.ksel; kp.l2 = p.l2;
+    kp.n_qtiles = p.n_qtiles; kp.n_splits = p.n_splits; kp.chunk_rows = p.chunk_rows; kp.part_score = ws_at<float>(h, L.ps); kp.part_idx = ws_at<int>(h, L.pi);
+    void (*fn)(KnnParams);
+    size_t lds;
+    if (f16_tile || (!h->f16 && p.ksel <= 32 && h->dim % KT_K == 0)) {
+        // tile kernel with LDS-DMA staging and register-resident lists: <list entries, fp16 operands>
+        const bool l16 = p.ksel <= 16;
+        fn = f16_tile ? (l16 ? k_knn_f32_reg<16, true> : k_knn_f32_reg<32, true>) : (l16 ? k_knn_f32_reg<16, false> : k_knn_f32_reg<32, false>);
+        lds = knn_reg_lds_bytes();
+    } else {
+        // generic kernel (any k, any dim % 4 == 0): register staging, lists in the partial arrays; an fp16 store is
+        // decoded to fp32 while staging and multiplied with the fp32 queries
+        fn = h->f16 ? k_knn_f32<true> : k_knn_f32<false>;
+        lds = knn_lds_bytes();
+    }
+    RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    h->prof.begin(st);
+    hipLaunchKernelGGL(fn, dim3((unsigned)(p.n_qtiles * p.n_splits)), dim3(KNN_THREADS), lds, st, kp);
+    h->prof.end(st);
+    return RADAD_OK;
+}
+
+// ---- sharded search: lower bounds of the exact scores of this store's k best rows, per query -------------------------------------
+// (scan score - eps of the k rows with the best scan scores).  The scan score of the f16 tile kernel estimates q.y (inner product,
+// cosine) or -|q - y|^2 (L2) whatever the plane's centring, so the bounds of different shards compare; the other kernels report none
+// (-inf).
+static void knn_report_lower_bounds(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, float* lb_out, hipStream_t st) {
+    if (p.kind == RADAD_SCAN_HI_TILE && p.cert) {
+        KthParams kp;
+        kp.score = ws_at<float>(h, L.ps); kp.cnt = ws_at<int>(h, L.cnt); kp.cap = p.emit_cap; kp.k = p.k; kp.eps = ws_at<float>(h, L.eps);
+        kp.lb_out = lb_out; kp.ak_out = ws_at<float>(h, L.ak);
+        hipLaunchKernelGGL(k_kth_floor, dim3((unsigned)p.nq), dim3(RF_THREADS), (size_t)p.emit_cap * 4 + 1040, st, kp);
+    } else {
+        hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)ceil_div64(p.nq * p.k, 256)), dim3(256), 0, st, lb_out, p.nq * p.k, -INFINITY);
+    }
+}
+
 static int knn_search_phase1(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int margin, float* lb_out, hipStream_t st,
                              SearchCtx* ctx) {
     // one workspace per handle: a search on another stream waits for the previous one (threads are serialised by h->mu,
@@ -2986,526 +3446,67 @@ static int knn_search_phase1(radad_knn_t h, const void* q_in, int q_dtype, int64
     h->have_last = true;
 
     h->prof.next_search();
-    const bool cert = k <= KNN_CERT_MAX_K;      // beyond: legacy k + margin candidates, no certificate
-    // how the certificates of earlier searches fared: any report that has arrived and was not looked at yet (see the handle); this
-    // search takes over slot search_seq & 1
-    // (until round 4 an event behind every search was waited for here: an event record between dependent kernels costs the stream ~6 us,
-    // a tenth of an online search.  The exact kernel stamps its report; one that has not arrived yet is simply not looked at.)
-    for (int sl = 0; cert && sl < 2; ++sl) {
-        volatile int* rep = reinterpret_cast<volatile int*>(h->host_count + 8 * sl);
-        const int stamp = rep[6];
-        if (stamp == 0 || stamp == h->stamp_seen[sl]) continue;
-        std::atomic_thread_fence(std::memory_order_acquire);
-        const int rejected = rep[0], rep_nq = rep[7];
-        std::atomic_thread_fence(std::memory_order_acquire);
-        if (rep[6] != stamp) continue;                    // the device is rewriting the slot right now: next search
-        h->stamp_seen[sl] = stamp;
-        ++h->reports_consumed;
-        // the report's own search: the one search at or below search_seq with that stamp's low 30 bits
-        const uint64_t cur30 = h->search_seq & 0x3fffffff, rep30 = (uint64_t)(stamp - 1);
-        const uint64_t rep_seq = h->search_seq - ((cur30 - rep30) & 0x3fffffff);
-        // (a report from before the last change of the plane or of the buffers says nothing about them)
-        if (h->hi_skip == 0 && rep_nq >= 64 && (int64_t)rejected * 4 > rep_nq && rep_seq >= h->tuned_at) knn_retune_after_mass_rejection(h);
-    }
+    if (k <= KNN_CERT_MAX_K) knn_consume_reports(h);
     const int cslot = (int)(h->search_seq & 1);
 #ifdef RADAD_DEBUG_HOOKS
     if (getenv("RADAD_DEBUG_KNN")) h->hi_skip = 0;     // timing ablations (wrong results, every query rejected): stay on the kernel under test
 #endif
-    const int l2 = h->metric == RADAD_METRIC_L2 ? 1 : 0;
-
-    // ---- choice of the scan -------------------------------------------------------------------------------------
-    int n_qtiles, n_splits;
-    int64_t chunk_rows;
-    knn_geometry(std::max<int64_t>(h->ntotal, 1), nq, &n_qtiles, &n_splits, &chunk_rows);
-    const int wide_min_q = h->opt_wide_min_q;
-    bool use_hi = false, skipped_hi = false;
-    int s_splits = 0;
-    const int ksel = k + margin;                 // list length of the fp32 tile kernels
-    // small batches (<= 16 queries: the online predict() search, pipeline.py:1038-1054, is ONE query of dim 5376 / 3584) stream the
-    // store; the kernels park only the nq queries handed over in LDS, so any dim goes as long as that block fits beside the slots
-    // (16 queries of dim 5376 do not: such a batch takes the tile kernels like a large one)
-    const size_t sq_slot_bytes = std::max<size_t>(sizeof(float2) * 4 * SQ_NQ * SQ_SLOTS, sizeof(u64) * 3 * SQ_NQ * 32) + sizeof(int) * 4 * SQ_NQ;
-    const size_t sq_lds_hi = sizeof(_Float16) * (size_t)nq * (h->dim + 8) + sq_slot_bytes;
-    const size_t sq_lds_f32 = sizeof(float) * (size_t)nq * (h->dim + 4) + sq_slot_bytes;
-    const bool sq_fits = nq <= SQ_NQ && ksel <= 32 &&
-                         ((!h->hi_off && h->dim % 64 == 0 && sq_lds_hi <= SQ_LDS_BUDGET) || (!h->f16 && h->dim % 32 == 0 && sq_lds_f32 <= SQ_LDS_BUDGET));
-    // the certified tile scan: any k the certificate covers (its candidate buffers are sized from k); the floor's rank k + margin
-    // must exist in the sample (16 entries per sample tile)
-    if (cert && (nq >= wide_min_q || !sq_fits) && h->ntotal > 0 && h->dim % 64 == 0 && !h->hi_off) {
-        int wq, ws; int64_t wc;
-        knn_geometry_wide(h->ntotal, nq, &wq, &ws, &wc);
-        // the sample pre-pass: one tile per workgroup, at most KW_SAMPLE_SPLITS tiles and 1/8 of the store (whatever the number of
-        // query tiles: every phase of the scan is sized from the sample, a small sample means more phases)
-        // ... and about 3 % of it: the pre-pass multiplies every query tile with its rows, so on a shard of a row-sharded store -- 1/G of
-        // the rows against G times the queries -- a fixed 16 384-row sample was 12 % of the scan's own work at G = 8 (0.16 of 1.7 ms);
-        // large enough, though, for the floor's rank to exist twice over (16 entries per sample tile)
-        {
-            const int64_t tiles = h->ntotal / KW_M;
-            int64_t want = (tiles * 3 / 100 + 4) / 8 * 8;
-            const int64_t need = ((int64_t)(2 * ksel + KW_SAMPLE_LIST - 1) / KW_SAMPLE_LIST + 7) / 8 * 8;
-            want = std::max<int64_t>(std::max<int64_t>(want, need), 8);
-            // ... but never fewer tiles than fill ONE round of the chip: the pre-pass is one tile per workgroup, its time is that one
-            // tile's latency whether 32 or 256 workgroups run it, and a larger sample is a tighter first floor (BASELINE config 2's
-            // 100 k rows took 8 tiles = 2048 rows: every tile of the scan's first layer then admitted ~2 rows per query -- 512 returning
-            // atomics per workgroup and tile; with 48 tiles the whole store is one launch behind the sample's floor alone)
-            want = std::max<int64_t>(want, std::min<int64_t>(KW_SAMPLE_SPLITS, (256 / std::max(1, std::min(wq, 256))) / 8 * 8));
-            s_splits = (int)std::min<int64_t>(std::min<int64_t>(KW_SAMPLE_SPLITS, want), tiles / 8 / 8 * 8);
-        }
-        if (s_splits >= 8 && s_splits * KW_SAMPLE_LIST >= 2 * ksel) {
-            if (h->hi_skip > 0) { --h->hi_skip; skipped_hi = true; if (h->hi_skip == 0) h->verify_next = true; }
-            else if (knn_ensure_hi(h, st, true)) { use_hi = true; n_qtiles = wq; }
-        }
-    }
-    if (!use_hi && cert && !knn_ensure_hi(h, st, false)) { radad_set_error("store statistics could not be computed"); return RADAD_EHIP; }
-    const bool smallq_geom = !use_hi && nq <= SQ_NQ && ksel <= 32 && h->ntotal > 0;
-    // the small batch over the f16 plane (certified like the tile scan): stores the plane is kept for, or fp16 stores
-    const int smallq_hi_on = h->opt_smallq_hi;
-    bool smallq_hi = false;
-    if (smallq_geom && cert && smallq_hi_on && h->dim % 64 == 0 && h->ntotal >= 16384 && !h->hi_off && !skipped_hi &&
-        sq_lds_hi <= SQ_LDS_BUDGET) {
-        // (every search that would take a certified f16 kernel counts the skip down: a handle that only sees small batches after a
-        // mass rejection used to stay on the fp32 kernel for ever)
-        if (h->hi_skip > 0) --h->hi_skip;
-        else smallq_hi = knn_ensure_hi(h, st, true);
-    }
-    // a small fp32 store (the IVF index's centroids; a database of a few thousand files): every score + select on the staged copy
-    const int dense_plen = (int)((std::max<int64_t>(h->ntotal, 1) + 3) / 4 * 4);
-    const bool dense = cert && !use_hi && !smallq_hi && !h->f16 && h->opt_dense && h->ntotal >= 1 &&
-                       h->ntotal <= (nq <= SQ_NQ ? RF_STAGE_MAX_SMALLQ : RF_STAGE_MAX) && h->dim % 16 == 0 && nq * (int64_t)dense_plen <= ((int64_t)1 << 24);
-    const bool smallq = smallq_geom && !dense && !smallq_hi && !h->f16 && h->dim % 32 == 0 && sq_lds_f32 <= SQ_LDS_BUDGET;
-    int sq_rows_per_wave = 0;
-    // a small store of wide rows (the reference's own: 25 423 x 5376) has too few 16-row steps to occupy the chip with one wave per
-    // row slice: the K-split form puts four waves on every step
-    const bool sq_ksplit = smallq_hi && h->dim >= 1024 && ceil_div64(h->ntotal, 16) < 4096;
-    // (its lists are 16 entries for k <= 16 -- the reference's k = 15 included -- instead of k + 6 <= 32: half the list registers,
-    // twice the waves per SIMD to hide the HBM latency behind.  A workgroup whose 16-entry list is used up by rows within the
-    // threshold rejects the query; the exact kernel over so small a store costs ~0.3 ms)
-    // (the same 16-entry lists on every f16 small-batch scan since round 4: k_knn_hi_smallq<32> streams the 1 M x 512 store in 0.40 ms,
-    // <16> in 0.20 -- 155 VGPRs against the 32-entry lists' panel of half the loads in flight)
-    const int ksel_sq = (smallq_hi && k <= 16) ? 16 : ksel;
-    if (sq_ksplit) {
-        int64_t rpg = 16;
-        while (ceil_div64(h->ntotal, rpg) * ksel_sq > RF_STAGE_MAX_SMALLQ) rpg += 16;
-        sq_rows_per_wave = (int)rpg;                  // (rows per WORKGROUP in this form)
-        n_splits = (int)ceil_div64(h->ntotal, rpg);
-        n_qtiles = 1;
-    } else if (smallq || smallq_hi) {
-        // a wave streams >= 128 KB (128 rows at dim 512) so that its lists' hand-over stays small beside the stream, but no more
-        // rows than leave 8 waves for every CU; the lists of a query (one per workgroup) should fit the re-rank's staged form
-        // one full round of resident waves: 1024 SIMDs x the waves per SIMD the kernel's registers allow (k_knn_hi_smallq<16>: 155
-        // VGPRs = 3; the 32-entry and fp32 variants: 2).  (Measured: no difference against 2048 waves on the 1 M x 512 store -- 0.2075
-        // vs 0.208 ms, 4.93 TB/s either way: the stream is not limited by the number of waves in flight.)
-        const int64_t waves_wanted = 1024 * ((smallq_hi && ksel_sq <= 16) ? 3 : 2);
-        const size_t rb = smallq_hi ? (size_t)h->dim * 2 : (size_t)h->dim * 4;
-        const int64_t rows_min = std::max<int64_t>(16, std::min<int64_t>(128, ceil_div64(ceil_div64(128 * 1024, (int64_t)rb), 16) * 16));
-        int64_t rpw = std::max<int64_t>(ceil_div64(ceil_div64(h->ntotal, waves_wanted), 16) * 16, rows_min);
-        while (rpw < 128 && ceil_div64(ceil_div64(h->ntotal, rpw), 4) * ksel_sq > RF_STAGE_MAX_SMALLQ) rpw += 16;
-        sq_rows_per_wave = (int)rpw;
-        n_splits = (int)ceil_div64(ceil_div64(h->ntotal, rpw), 4);                // workgroups of 4 waves = lists per query
-        n_qtiles = 1;
-    }
-    const bool f16_tile = !use_hi && !smallq_hi && h->f16 && ksel <= 32 && h->dim % 64 == 0;
-    // the tile scan's phases: a floor taken from m rows admits ~(rank / m) of what it is applied to, so every launch covers at most
-    // 8 x the rows its floor was taken from -- the first 8 x the sample with the sample's floor, the next 8 x that with the floor the
-    // candidates so far give (k_kth_floor), and so on: 2 launches up to 1.2 M rows, 3 up to 9.5 M.  Each admits ~8 (k + margin) rows
-    // per query; the candidate buffer holds 32 (k + margin) (>= 1024): more (stores of near-duplicates) rejects the query.
-    const int64_t hi_phase0 = (int64_t)8 * s_splits * KW_M;
-    const int emit_cap = use_hi ? std::min(RF_STAGE_MAX, std::max(1024 * h->cap_boost, 32 * ksel)) : 0;
-    h->last_qtiles = n_qtiles;
-    if (dense) { n_qtiles = (int)ceil_div64(nq, 16); n_splits = 1; }
-    h->last_threads = use_hi ? KW_THREADS : ((smallq || smallq_hi || dense) ? SQ_THREADS : KNN_THREADS);
-    h->last_kind = use_hi ? RADAD_SCAN_HI_TILE : dense ? RADAD_SCAN_F32_DENSE : smallq_hi ? RADAD_SCAN_HI_SMALLQ : smallq ? RADAD_SCAN_F32_SMALLQ
-                          : f16_tile ? RADAD_SCAN_F16_TILE : RADAD_SCAN_F32_TILE;
-    const int plen = use_hi ? emit_cap : dense ? dense_plen : ksel_sq;   // entries of a partial list / of the candidate buffer
-    const int n_parts = (use_hi || dense) ? 1 : n_splits;
-    // (dense: eps of exact fp32 products is ~1e-6 of |q||y| -- hardly a row beyond the k best is within 2 eps; k + 32 candidates keep
-    // the re-rank's workgroup at 34 KB of LDS for 4096 staged scores, four per CU instead of three: the IVF coarse step's 1024
-    // workgroups in one round.  More near-ties than that reject the query: exact kernel.)
-    // (a handle that has widened its candidate buffers -- cap_boost: a store whose rows crowd within 2 eps of the k-th best -- also
-    // re-ranks four times as many: the fp32 funnel in front of the float64 re-score takes them at ~2 KB of row reads each)
-    const int cap = cert ? (dense ? k + KNN_CERT_EXTRA : std::max(k + KNN_CERT_EXTRA, KNN_CERT_CAP * (use_hi ? h->cap_boost : 1))) : ksel;
-    const int xgroup = (int)std::max<size_t>(1, std::min<size_t>(8, (size_t)(64 * 1024) / ((size_t)h->dim * 4)));
-
-    // ---- workspace: qf (decoded bf16) | qn (normalised) | qh (f16 queries) | qscale | qconst | eps | thr_init | cand_cnt |
-    //                 flag_count, flag_sel | part_score | part_idx | exact partial keys | ids
-    const size_t qrow_f32 = al256((size_t)nq * h->dim * sizeof(float));
-    const size_t b_qf = q_dtype == RADAD_Q_BF16 ? qrow_f32 : 0;
-    const size_t b_qn = h->metric == RADAD_METRIC_COSINE ? qrow_f32 : 0;
-    const size_t b_qh = (use_hi || f16_tile || smallq_hi) ? al256((size_t)nq * h->dim * 2) : 0;
-    const size_t b_vec = al256((size_t)nq * sizeof(float));
-    // (the sample pre-pass's lists live BEHIND the candidate buffers, not in them: k_floor_from_sample clears a query's buffer to -inf
-    // while other queries' sample lists are still being read)
-    const size_t cand_elems = (size_t)nq * (size_t)n_parts * plen;
-    const size_t part_elems = cand_elems + (use_hi ? (size_t)nq * KW_SAMPLE_SPLITS * KW_SAMPLE_LIST : 0);
-    const size_t b_part = al256(part_elems * sizeof(float));
-    const size_t b_xk = cert ? al256((size_t)nq * KX_SLICES * k * sizeof(double)) : 0;
-    const size_t b_xi = cert ? al256((size_t)nq * KX_SLICES * k * sizeof(int)) : 0;
-    size_t off = 0;
-    const size_t o_qf = off; off += b_qf;
-    const size_t o_qn = off; off += b_qn;
-    const size_t o_qh = off; off += b_qh;
-    const size_t o_qscale = off; off += b_vec;
-    const size_t o_qconst = off; off += b_vec;
-    const size_t o_eps = off; off += b_vec;
-    const size_t o_thr = off; off += b_vec;
-    const size_t o_ak = off; off += b_vec;             // a_k of the candidates (two-half searches: k_kth_floor -> k_merge_refine)
-    const size_t o_cnt = off; off += b_vec;            // cand_cnt [nq] int (zeroed by k_hi_rows with the counters)
-    const size_t o_fcount = off; off += 256 + KNN_PROG_MAX * sizeof(int);   // flag_count + statistics | the tile scan's progress counters (one per query tile)
-    const size_t o_fsel = off; off += b_vec;
-    const size_t o_ps = off; off += b_part;
-    const size_t o_pi = off; off += b_part;
-    const size_t o_xk = off; off += b_xk;
-    const size_t o_xi = off; off += b_xi;
-    if (off > h->ws_bytes) {
+    ScanPlan p;
+    int rc = knn_plan_scan(h, nq, k, margin, st, &p);
+    if (rc) return rc;
+    const SearchLayout L = knn_search_layout(h, p, q_dtype);
+    if (L.bytes > h->ws_bytes) {
         RADAD_HIP_CHECK(hipDeviceSynchronize());
-        int rc = knn_workspace(h, off);
+        rc = knn_workspace(h, L.bytes);
         if (rc) return rc;
     }
-    char* ws = (char*)h->ws;
-    _Float16* qh = (_Float16*)(ws + o_qh);
-    float* qscale = (float*)(ws + o_qscale);
-    float* qconst = (float*)(ws + o_qconst);
-    float* eps = (float*)(ws + o_eps);
-    float* thr_init = (float*)(ws + o_thr);
-    float* qconst_ak = (float*)(ws + o_ak);
-    int* cand_cnt = (int*)(ws + o_cnt);
-    int* flag_count = (int*)(ws + o_fcount);
-    float* ps = (float*)(ws + o_ps);
-    int* pi = (int*)(ws + o_pi);
-
-    // ---- queries: decode, normalise, round (+ scale) to f16, error bound ------------------------------------------
-    const float* q_use = (const float*)q_in;
-    const unsigned rgrid = (unsigned)ceil_div64(nq, 4);
-    if (q_dtype == RADAD_Q_BF16) {
-        float* qf = (float*)(ws + o_qf);
-        const int64_t ne = nq * h->dim;
-        hipLaunchKernelGGL(k_bf16_to_f32, dim3((unsigned)ceil_div64(ne, 1024)), dim3(256), 0, st, (const unsigned short*)q_in, qf, ne);
-        q_use = qf;
-    }
-    const bool hi_q = use_hi || smallq_hi;                 // f16 queries with a per-query scale
-    const float* mu = (hi_q && !h->f16) ? h->cmu : nullptr; // centred plane: the queries are centred the same way
-    const bool biased = hi_q && (l2 || mu);                // the scale + bias variant of the f16 kernels (RSC 2)
-    const bool prep = cert || use_hi || f16_tile;          // k_hi_rows runs: it also normalises and clears the flags
-    if (h->metric == RADAD_METRIC_COSINE) {
-        float* qn = (float*)(ws + o_qn);
-        if (!prep) hipLaunchKernelGGL(k_rows_prepare<float>, dim3(rgrid), dim3(256), 0, st, q_use, qn, (float*)nullptr, nq, h->dim, 2);
-        // (with prep the same normalisation happens inside k_hi_rows, which reads the raw queries)
-    }
-    // (|q|^2 is not needed: ranking uses 2 q.y - |y|^2 and the reported distance is re-scored exactly)
-    if (prep) {
-        HiRowsParams hp;
-        hp.in = q_use; hp.in_f16 = 0;
-        hp.hi = (hi_q || f16_tile) ? qh : nullptr;
-        hp.scale_out = hi_q ? qscale : nullptr;
-        hp.stat_max = nullptr; hp.eps_out = cert ? eps : nullptr; hp.ystat = h->stat;
-        hp.n = nq; hp.dim = h->dim;
-        hp.fixed_e = hi_q ? HI_E_PER_ROW : 0;            // the fp16 tile kernel multiplies un-scaled fp16 queries
-        hp.l2 = l2; hp.exact_ops = (hi_q || f16_tile) ? 0 : 1;
-        hp.norm_out = h->metric == RADAD_METRIC_COSINE ? (float*)(ws + o_qn) : nullptr;
-        hp.zero_flags = cert ? cand_cnt : nullptr; hp.zero_counters = cert ? flag_count : nullptr;
-        hp.mu = mu; hp.mu_norm = mu ? h->mu_norm : 0.f; hp.mu_sq = mu ? h->mu_sq : 0.f; hp.biased = (biased || (f16_tile && l2)) ? 1 : 0;
-        hp.bias_out = nullptr; hp.qconst_out = biased ? qconst : nullptr;
-        launch_hi_rows(hp, st);
-    }
-    if (h->metric == RADAD_METRIC_COSINE) q_use = (const float*)(ws + o_qn);
+    const float* q_use = knn_prepare_queries(h, p, L, q_in, q_dtype, st);
     RADAD_HIP_CHECK(hipGetLastError());
 
-    // ---- scan ----------------------------------------------------------------------------------------------------
-    KnnParams p;
-    p.db = h->rows; p.db_f16 = h->f16; p.ynorm = h->ynorm; p.q = f16_tile ? (const void*)qh : (const void*)q_use; p.n = h->ntotal; p.nq = (int)nq; p.dim = h->dim; p.k = ksel;
-    p.l2 = l2;
-    p.n_qtiles = n_qtiles; p.n_splits = n_splits; p.chunk_rows = chunk_rows; p.part_score = ps; p.part_idx = pi;
-    p.debug = 0;
-    const dim3 grid((unsigned)(n_qtiles * n_splits));
-    if (use_hi) {
-        KnnHiParams wp;
-        wp.db = h->f16 ? (const void*)h->rows : (const void*)h->hi;
-        wp.rscale = h->f16 ? nullptr : h->rscale;
-        wp.uscale = h->f16 ? 1.0f : (h->uniform_e != HI_E_PER_ROW ? ldexpf(1.0f, -h->uniform_e) : (h->metric == RADAD_METRIC_COSINE ? 0x1p-14f : 1.0f));
-        // bias of the scale + bias variant: a centred plane has its own (|y - mu|^2 or mu.y); un-centred L2 uses |y|^2 as stored
-        wp.rbias = mu ? h->rbias : h->ynorm; wp.bias_sign = l2 ? -1.f : 1.f; wp.mult = l2 ? 2.f : 1.f; wp.qconst = biased ? qconst : nullptr;
-        wp.q = qh; wp.qscale = qscale;
-        wp.n = h->ntotal; wp.nq = (int)nq; wp.row_bytes = h->dim * 2; wp.l2 = l2; wp.id_off = 0;
-        wp.n_qtiles = n_qtiles; wp.part_score = ps; wp.part_idx = pi;
-        wp.cand_cap = emit_cap; wp.cand_cnt = cand_cnt;
-        wp.thr_init = nullptr;
-        wp.ksplit = 1; wp.kacc = nullptr; wp.kflag = nullptr; wp.loose_floor = 0; wp.chunk_stride = 0;
-        wp.floor_live = nullptr; wp.eps = nullptr; wp.k_sel = 0; wp.prog = nullptr; wp.prog_thr[0] = wp.prog_thr[1] = wp.prog_thr[2] = wp.prog_thr[3] = 0;
-        wp.debug = 0; wp.stamps = nullptr;
-#ifdef RADAD_DEBUG_HOOKS        // timing experiments only (make exp); never in the shipped library
-        { const char* dbg = getenv("RADAD_DEBUG_KNN"); wp.debug = dbg ? atoi(dbg) : 0; }
-        {   // RADAD_KNN_STAMPS=<file>: in-kernel s_memtime stamps of the 8 waves of workgroup 0, dumped after the scan (synchronises)
-            static unsigned long long* stamp_buf = nullptr;
-            if (getenv("RADAD_KNN_STAMPS")) {
-                if (!stamp_buf) (void)hipMalloc(&stamp_buf, 8 * 4096 * 8);
-                (void)hipMemsetAsync(stamp_buf, 0, 8 * 4096 * 8, st);
-                wp.stamps = stamp_buf;
-            }
-        }
-#endif
-        const int rsc = biased ? (wp.rscale ? 2 : 3) : (wp.rscale ? 1 : 0);
-        const size_t lds = knn_hi_lds_bytes();
-        const void* fns[4] = {reinterpret_cast<const void*>(k_knn_hi<0>), reinterpret_cast<const void*>(k_knn_hi<1>),
-                              reinterpret_cast<const void*>(k_knn_hi<2>), reinterpret_cast<const void*>(k_knn_hi<3>)};
-        const void* sfns[4] = {reinterpret_cast<const void*>(k_knn_hi_sample<0>), reinterpret_cast<const void*>(k_knn_hi_sample<1>),
-                               reinterpret_cast<const void*>(k_knn_hi_sample<2>), reinterpret_cast<const void*>(k_knn_hi_sample<3>)};
-        RADAD_HIP_CHECK(hipFuncSetAttribute(fns[rsc], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        RADAD_HIP_CHECK(hipFuncSetAttribute(sfns[rsc], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        // ONE launch over the whole store with the floors raised inside it (knn_hi.inc: floor_live), when the candidate buffers are the
-        // 1024 entries a wave holds in registers and a workgroup's chunk is long enough to refresh at least once before the sample's
-        // floor alone would fill them: after t tiles of every resident chunk stream ~t x 256 x (streams per query tile) rows have been
-        // scanned, and the phases of the launch-per-phase form (8 x the sample, 8 x that, ...) become refresh points t, 8 t, 64 t.
-        // Round 4 ran one launch per phase (2 up to 1.2 M rows, 3 up to 9.5 M, k_kth_floor between them): every launch has its ramp
-        // and its tail, and a 100 k-row store (BASELINE config 2) ran 64 + 327 tiles as 1 + 3 tile times on 512 workgroups.
-        int live_nr = 0, live_at[4] = {0, 0, 0, 0};
-        const bool one_go = (int64_t)ksel * h->ntotal <= (int64_t)(emit_cap / 3) * s_splits * KW_M;
-        if (!one_go && emit_cap <= 1024 && h->opt_live_floor == 1 && h->dim >= 128 && n_qtiles <= KNN_PROG_MAX) {
-            // refresh when a query tile has started 8 x the sample's tiles, 8 x that, ... (the phases of the launch-per-phase form), as
-            // long as a fifth of the store is still to come
-            const int64_t tiles = ceil_div64(h->ntotal, KW_M);
-            for (int64_t t = hi_phase0 / KW_M; t + KW_REFRESH_WGS <= tiles - tiles / 5 && live_nr < 4; t *= 8) live_at[live_nr++] = (int)t;
-        }
-        // sample pre-pass: the (k + margin)-th best score over the first rows of the store is a score at least k rows reach, so the
-        // scan admits from it (minus 2 eps) instead of -inf (the score of a (row, query) pair does not depend on the tiling).
-        // Its lists live behind the candidate buffers.
-        {
-            KnnHiParams sp = wp;
-            // The sample's tiles are SPREAD over the store (every (tiles / s_splits)-th one).  The first s_splits tiles, as until round 4,
-            // are a sample of the store only while its rows are in random order: on a store whose rows arrive cluster by cluster
-            // (add_vectors_batch appends 10 000 rows at a time, vector_database.py:134-138) a query of the LAST cluster got a floor
-            // from rows of the first -- so loose that every row of its own cluster passed it, the candidate buffer overflowed and the
-            // certificate rejected all 256 queries of a batch (tests/test_gpu_reference_shapes.py::test_a_store_that_drifts...).
-            sp.n = h->ntotal; sp.n_splits = s_splits; sp.chunk_rows = KW_M;
-            sp.part_score = ps + cand_elems; sp.part_idx = pi + cand_elems;
-            sp.chunk_stride = std::max<int64_t>(1, (h->ntotal / KW_M) / s_splits) * KW_M;
-            const int sq_grid = sp.n_qtiles <= 8 ? sp.n_qtiles : (sp.n_qtiles + 7) / 8 * 8;
-            // (the K split's scratch is indexed by row0 / KW_M: the sample's tiles lie anywhere in the store)
-            sp.ksplit = knn_tile_ksplit(h, sq_grid, sp.n_splits, KW_M, h->ntotal, st);
-            sp.kacc = h->kacc; sp.kflag = h->kflag;
-            const dim3 sg((unsigned)(sq_grid * sp.n_splits * sp.ksplit)), sb(KW_THREADS);
-            if (rsc == 0) hipLaunchKernelGGL(k_knn_hi_sample<0>, sg, sb, lds, st, sp);
-            else if (rsc == 1) hipLaunchKernelGGL(k_knn_hi_sample<1>, sg, sb, lds, st, sp);
-            else if (rsc == 2) hipLaunchKernelGGL(k_knn_hi_sample<2>, sg, sb, lds, st, sp);
-            else hipLaunchKernelGGL(k_knn_hi_sample<3>, sg, sb, lds, st, sp);
-            const int n_ent = sp.n_splits * KW_SAMPLE_LIST;
-            hipLaunchKernelGGL(k_floor_from_sample, dim3((unsigned)nq), dim3(RF_THREADS), (size_t)n_ent * 4 + 1040, st, (const float*)sp.part_score,
-                               (const int*)sp.part_idx, n_ent, k + margin, (const float*)eps, thr_init, live_nr > 0 ? ps : (float*)nullptr, emit_cap,
-                               live_nr > 0 ? flag_count + KNN_PROG_OFF : (int*)nullptr, n_qtiles);
-            wp.thr_init = thr_init;
-        }
-        const dim3 b(KW_THREADS);
-        auto launch_range = [&](int64_t r0, int64_t r1) {      // rows [r0, r1) of the store, one full round (or two) of workgroups
-            KnnHiParams rp = wp;
-            const size_t rb = (size_t)wp.row_bytes;
-            rp.db = (const char*)wp.db + (size_t)r0 * rb;
-            rp.rscale = wp.rscale ? wp.rscale + r0 : nullptr;
-            rp.rbias = wp.rbias ? wp.rbias + r0 : nullptr;
-            rp.n = r1 - r0; rp.id_off = r0;
-            rp.loose_floor = (r0 == 0 && r1 == h->ntotal && s_splits < KW_SAMPLE_SPLITS && live_nr == 0) ? 1 : 0;      // one launch behind a small sample
-            // (the counting form for the FIRST phase of a large store -- its floor is the sample's, ~64 candidates per tile -- was measured
-            // too: 0.883-0.887 against 0.874-0.877 ms per search, three alternations on one box, profiles/r5_ab_counting_emit_phase0.txt: no)
-            if (live_nr > 0) {
-                rp.floor_live = thr_init; rp.eps = eps; rp.k_sel = k;
-                for (int i = 0; i < 4; ++i) rp.prog_thr[i] = live_at[i];
-                rp.prog = flag_count + KNN_PROG_OFF;
-            }
-            int gq, gs; int64_t gc;
-            knn_geometry_wide(rp.n, nq, &gq, &gs, &gc);
-            rp.n_splits = gs; rp.chunk_rows = gc; rp.chunk_stride = gc;
-            h->last_splits = gs;
-            const int gq_grid = gq <= 8 ? gq : (gq + 7) / 8 * 8;                      // (more than 8 query tiles: whole groups of 8, see the kernel)
-            rp.ksplit = knn_tile_ksplit(h, gq_grid, gs, gc, rp.n, st);
-            rp.kacc = h->kacc; rp.kflag = h->kflag;
-            const dim3 g2((unsigned)(gq_grid * gs * rp.ksplit));
-            h->prof.begin(st);      // the event pair brackets a scan launch only (the kernel the roofline is quoted on; the phases of one
-                                    // search are two entries)
-            if (rsc == 0) hipLaunchKernelGGL(k_knn_hi<0>, g2, b, lds, st, rp);
-            else if (rsc == 1) hipLaunchKernelGGL(k_knn_hi<1>, g2, b, lds, st, rp);
-            else if (rsc == 2) hipLaunchKernelGGL(k_knn_hi<2>, g2, b, lds, st, rp);
-            else hipLaunchKernelGGL(k_knn_hi<3>, g2, b, lds, st, rp);
-            h->prof.end(st);
-        };
-        h->last_scan_launches = 0;
-        h->last_scan_phases = 0;
-        if (live_nr > 0) {
-            launch_range(0, h->ntotal);
-            h->last_scan_launches = 1;
-            h->last_scan_phases = 1 + live_nr;
-        }
-        for (int64_t r0 = 0, span = hi_phase0; live_nr == 0 && r0 < h->ntotal; span *= 8) {
-            // (a last phase of less than a quarter of its predecessor is not worth a launch of its own: it joins it)
-            int64_t r1 = std::min<int64_t>(h->ntotal, r0 + span);
-            if (h->ntotal - r1 < span / 4) r1 = h->ntotal;
-            // a store the sample's floor alone filters to a third of the buffer (~(k + margin) N / sample rows) is scanned in one go
-            if (r0 == 0 && (int64_t)ksel * h->ntotal <= (int64_t)(emit_cap / 3) * s_splits * KW_M) r1 = h->ntotal;
-            // A launch deals whole tiles to its row splits, ceil(tiles / splits) each: what decides its time is that quotient, and a
-            // remainder of a few tiles costs a whole extra tile per workgroup (64 + 260 tiles over 128 splits = 1 + 3 tile times, the last
-            // round of the second launch nearly empty; 68 + 256 tiles = 1 + 2).  When the LAST launch follows this one, up to a quarter
-            // more tiles move into this one if that lowers the sum of the two quotients.  (BASELINE config 2 -- 100 k rows = 64 + 327
-            // tiles -- gains nothing from it: 1 + 3 either way; its scan stays at 0.27 of the MFMA peak, 1 564 tile tasks over 256 CUs.)
-            if (r1 < h->ntotal && (h->ntotal - r1 <= span * 8 || h->ntotal - r1 - span * 8 < span * 2)) {
-                auto tile_time = [&](int64_t rows) {
-                    int gq, gs; int64_t gc;
-                    knn_geometry_wide(rows, nq, &gq, &gs, &gc);
-                    return gc / KW_M;
-                };
-                const int64_t t_this = ceil_div64(r1 - r0, KW_M), t_rest = ceil_div64(h->ntotal - r1, KW_M);
-                int64_t best = tile_time(r1 - r0) + tile_time(h->ntotal - r1), best_s = 0;
-                for (int64_t sft = 1; sft <= std::min<int64_t>(t_this / 4, t_rest - 1); ++sft) {
-                    const int64_t c = tile_time(r1 - r0 + sft * KW_M) + tile_time(h->ntotal - r1 - sft * KW_M);
-                    if (c < best) { best = c; best_s = sft; }
-                }
-                r1 += best_s * KW_M;
-            }
-            if (r0 > 0) {
-                KthParams kp;
-                kp.score = ps; kp.cnt = cand_cnt; kp.cap = emit_cap; kp.k = k; kp.eps = eps; kp.floor_io = thr_init; kp.lb_out = nullptr; kp.ak_out = nullptr;
-                hipLaunchKernelGGL(k_kth_floor, dim3((unsigned)nq), dim3(RF_THREADS), (size_t)emit_cap * 4 + 1040, st, kp);
-            }
-            launch_range(r0, r1);
-            ++h->last_scan_launches;
-            ++h->last_scan_phases;
-            r0 = r1;
-        }
-#ifdef RADAD_DEBUG_HOOKS
-        if (wp.stamps) {
-            std::vector<unsigned long long> hs(8 * 4096);
-            (void)hipStreamSynchronize(st);
-            (void)hipMemcpy(hs.data(), wp.stamps, hs.size() * 8, hipMemcpyDeviceToHost);
-            if (FILE* f = fopen(getenv("RADAD_KNN_STAMPS"), "wb")) { fwrite(hs.data(), 8, hs.size(), f); fclose(f); }
-        }
-#endif
-    } else if (dense) {
-        DenseParams dp;
-        dp.db = (const float*)h->rows; dp.ynorm = h->ynorm; dp.q = q_use; dp.n = h->ntotal; dp.nq = (int)nq; dp.dim = h->dim; dp.l2 = l2;
-        dp.plen = dense_plen; dp.score = ps; dp.idx = pi; dp.cnt = cand_cnt;
-        h->prof.begin(st);
-        if (nq <= SQ_NQ) hipLaunchKernelGGL((k_knn_dense<1, 1>), dim3((unsigned)ceil_div64(dense_plen, 64), (unsigned)ceil_div64(nq, 16)), dim3(256), 0, st, dp);
-        else hipLaunchKernelGGL((k_knn_dense<2, 4>), dim3((unsigned)ceil_div64(dense_plen, 128), (unsigned)ceil_div64(nq, 64)), dim3(256), 0, st, dp);
-        h->prof.end(st);
-    } else if (smallq_hi) {
-        SmallQHiParams sp;
-        sp.db = h->f16 ? (const _Float16*)h->rows : h->hi;
-        sp.rscale = h->f16 ? nullptr : h->rscale;
-        sp.uscale = h->f16 ? 1.0f : (h->uniform_e != HI_E_PER_ROW ? ldexpf(1.0f, -h->uniform_e) : (h->metric == RADAD_METRIC_COSINE ? 0x1p-14f : 1.0f));
-        sp.rbias = biased ? (mu ? h->rbias : h->ynorm) : nullptr; sp.bias_sign = l2 ? -1.f : 1.f; sp.mult = l2 ? 2.f : 1.f;
-        sp.qconst = biased ? qconst : nullptr;
-        sp.q = qh; sp.qscale = qscale; sp.n = h->ntotal; sp.nq = (int)nq; sp.dim = h->dim; sp.k = ksel_sq;
-        sp.rows_per_wave = sq_rows_per_wave; sp.n_parts = n_splits; sp.part_score = ps; sp.part_idx = pi;
-        const size_t lds = sq_lds_hi;
-        const dim3 sgrid((unsigned)n_splits);
-        if (sq_ksplit) {
-            const void* fn = ksel_sq <= 16 ? reinterpret_cast<const void*>(k_knn_hi_smallq_ksplit<16>) : reinterpret_cast<const void*>(k_knn_hi_smallq_ksplit<32>);
-            RADAD_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            h->prof.begin(st);
-            if (ksel_sq <= 16) hipLaunchKernelGGL(k_knn_hi_smallq_ksplit<16>, sgrid, dim3(SQ_THREADS), lds, st, sp);
-            else hipLaunchKernelGGL(k_knn_hi_smallq_ksplit<32>, sgrid, dim3(SQ_THREADS), lds, st, sp);
-            h->prof.end(st);
-        } else if (ksel_sq <= 16) {
-            RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_knn_hi_smallq<16>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            h->prof.begin(st);
-            hipLaunchKernelGGL(k_knn_hi_smallq<16>, sgrid, dim3(SQ_THREADS), lds, st, sp);
-            h->prof.end(st);
-        } else {
-            RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_knn_hi_smallq<32>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            h->prof.begin(st);
-            hipLaunchKernelGGL(k_knn_hi_smallq<32>, sgrid, dim3(SQ_THREADS), lds, st, sp);
-            h->prof.end(st);
-        }
-    } else if (smallq) {
-        SmallQParams sp;
-        sp.db = (const float*)h->rows; sp.ynorm = h->ynorm; sp.q = q_use; sp.n = h->ntotal; sp.nq = (int)nq; sp.dim = h->dim; sp.k = ksel;
-        sp.l2 = p.l2; sp.rows_per_wave = sq_rows_per_wave; sp.n_parts = n_splits; sp.part_score = ps; sp.part_idx = pi;
-        const size_t lds = sq_lds_f32;
-        const dim3 sgrid((unsigned)n_splits);
-        if (ksel <= 16) {
-            RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_knn_f32_smallq<16>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            h->prof.begin(st);
-            hipLaunchKernelGGL(k_knn_f32_smallq<16>, sgrid, dim3(SQ_THREADS), lds, st, sp);
-            h->prof.end(st);
-        } else {
-            RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_knn_f32_smallq<32>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            h->prof.begin(st);
-            hipLaunchKernelGGL(k_knn_f32_smallq<32>, sgrid, dim3(SQ_THREADS), lds, st, sp);
-            h->prof.end(st);
-        }
-    } else if (f16_tile || (!h->f16 && ksel <= 32 && h->dim % KT_K == 0)) {
-        // tile kernel with LDS-DMA staging and register-resident lists: <list entries, fp16 operands>
-        const void* fn = f16_tile ? (ksel <= 16 ? reinterpret_cast<const void*>(k_knn_f32_reg<16, true>)
-                                                : reinterpret_cast<const void*>(k_knn_f32_reg<32, true>))
-                                  : (ksel <= 16 ? reinterpret_cast<const void*>(k_knn_f32_reg<16, false>)
-                                                : reinterpret_cast<const void*>(k_knn_f32_reg<32, false>));
-        RADAD_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_reg_lds_bytes()));
-        h->prof.begin(st);
-        if (f16_tile && ksel <= 16) hipLaunchKernelGGL((k_knn_f32_reg<16, true>), grid, dim3(KNN_THREADS), knn_reg_lds_bytes(), st, p);
-        else if (f16_tile) hipLaunchKernelGGL((k_knn_f32_reg<32, true>), grid, dim3(KNN_THREADS), knn_reg_lds_bytes(), st, p);
-        else if (ksel <= 16) hipLaunchKernelGGL((k_knn_f32_reg<16, false>), grid, dim3(KNN_THREADS), knn_reg_lds_bytes(), st, p);
-        else hipLaunchKernelGGL((k_knn_f32_reg<32, false>), grid, dim3(KNN_THREADS), knn_reg_lds_bytes(), st, p);
-        h->prof.end(st);
-    } else {
-        // generic kernel (any k, any dim % 4 == 0): register staging, lists in the partial arrays; an fp16 store is
-        // decoded to fp32 while staging and multiplied with the fp32 queries
-        const void* fn = h->f16 ? reinterpret_cast<const void*>(k_knn_f32<true>) : reinterpret_cast<const void*>(k_knn_f32<false>);
-        RADAD_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_lds_bytes()));
-        h->prof.begin(st);
-        if (h->f16) hipLaunchKernelGGL(k_knn_f32<true>, grid, dim3(KNN_THREADS), knn_lds_bytes(), st, p);
-        else hipLaunchKernelGGL(k_knn_f32<false>, grid, dim3(KNN_THREADS), knn_lds_bytes(), st, p);
-        h->prof.end(st);
+    switch (p.kind) {
+        case RADAD_SCAN_HI_TILE: rc = knn_scan_hi_tile(h, p, L, st); break;
+        case RADAD_SCAN_F32_DENSE: knn_scan_dense(h, p, L, q_use, st); break;
+        case RADAD_SCAN_HI_SMALLQ: rc = knn_scan_hi_smallq(h, p, L, st); break;
+        case RADAD_SCAN_F32_SMALLQ: rc = knn_scan_f32_smallq(h, p, L, q_use, st); break;
+        default: rc = knn_scan_tile(h, p, L, q_use, st); break;
     }
-    if (!use_hi) { h->last_splits = n_splits; h->last_scan_launches = 1; }
+    if (rc) return rc;
+    const bool hi_tile = p.kind == RADAD_SCAN_HI_TILE;
+    if (!hi_tile) { h->last_splits = p.n_splits; h->last_scan_launches = 1; }
     RADAD_HIP_CHECK(hipGetLastError());
-
-    // ---- sharded search: lower bounds of the exact scores of this store's k best rows, per query -------------------------------
-    // (scan score - eps of the k rows with the best scan scores).  The scan score of the f16 tile kernel estimates q.y (inner
-    // product, cosine) or -|q - y|^2 (L2) whatever the plane's centring, so the bounds of different shards compare; the other
-    // kernels report none (-inf).
     if (lb_out) {
-        if (use_hi && cert) {
-            KthParams kp;
-            kp.score = ps; kp.cnt = cand_cnt; kp.cap = emit_cap; kp.k = k; kp.eps = eps; kp.floor_io = nullptr; kp.lb_out = lb_out;
-            kp.ak_out = qconst_ak;
-            hipLaunchKernelGGL(k_kth_floor, dim3((unsigned)nq), dim3(RF_THREADS), (size_t)emit_cap * 4 + 1040, st, kp);
-        } else {
-            hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)ceil_div64(nq * k, 256)), dim3(256), 0, st, lb_out, nq * k, -INFINITY);
-        }
+        knn_report_lower_bounds(h, p, L, lb_out, st);
         RADAD_HIP_CHECK(hipGetLastError());
     }
 
     ctx->valid = true;
-    ctx->nq = nq; ctx->k = k; ctx->l2 = l2; ctx->cslot = cslot; ctx->n_parts = n_parts; ctx->plen = plen; ctx->cap = cap; ctx->xgroup = xgroup;
-    ctx->cert = cert; ctx->emit = use_hi || dense; ctx->use_floor = use_hi; ctx->hi_tile = use_hi; ctx->q_use = q_use;
-    ctx->small_lists = !use_hi && !dense && (smallq || smallq_hi);
-    ctx->canonical = use_hi || smallq_hi || !l2;
-    ctx->have_ak = lb_out != nullptr && use_hi && cert; ctx->o_ak = o_ak;
-    h->last_o_cnt = o_cnt; h->last_o_thr = o_thr; h->last_emit_nq = use_hi ? nq : 0;
-    ctx->o_eps = o_eps; ctx->o_thr = o_thr; ctx->o_cnt = o_cnt; ctx->o_fcount = o_fcount; ctx->o_fsel = o_fsel; ctx->o_ps = o_ps; ctx->o_pi = o_pi;
-    ctx->o_xk = o_xk; ctx->o_xi = o_xi;
+    ctx->nq = nq; ctx->k = k; ctx->l2 = p.l2; ctx->cslot = cslot; ctx->n_parts = p.n_parts; ctx->plen = p.plen; ctx->cap = p.cap; ctx->xgroup = p.xgroup;
+    ctx->cert = p.cert; ctx->emit = hi_tile || p.kind == RADAD_SCAN_F32_DENSE; ctx->use_floor = hi_tile; ctx->hi_tile = hi_tile; ctx->q_use = q_use;
+    ctx->small_lists = p.kind == RADAD_SCAN_HI_SMALLQ || p.kind == RADAD_SCAN_F32_SMALLQ;
+    ctx->canonical = hi_tile || p.kind == RADAD_SCAN_HI_SMALLQ || !p.l2;
+    ctx->have_ak = lb_out != nullptr && hi_tile && p.cert;
+    ctx->ws = L;
+    h->last_o_cnt = L.cnt; h->last_o_thr = L.thr; h->last_emit_nq = hi_tile ? nq : 0;
     return RADAD_OK;
 }
 
 constexpr int RADAD_RETRY_INTERNAL = 1;      // knn_search_phase2 -> knn_search_core: retuned after a mass rejection, run the search again
 static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* global_lb, bool may_retry, float* out_dist_dev, int64_t* out_idx_dev,
                              double* out_key_dev, hipStream_t st) {
-    char* ws = (char*)h->ws;
-    int* flag_count = (int*)(ws + c.o_fcount);
-    int* flag_sel = (int*)(ws + c.o_fsel);
+    int* flag_count = ws_at<int>(h, c.ws.fcount);
+    int* flag_sel = ws_at<int>(h, c.ws.fsel);
     const int64_t nq = c.nq;
     const int k = c.k;
     // ---- float64 re-rank + certificate ----------------------------------------------------------------------------
     RefineParams m;
-    m.score = (const float*)(ws + c.o_ps); m.idx = (const int*)(ws + c.o_pi); m.n_parts = c.n_parts; m.k = k; m.dim = h->dim; m.l2 = c.l2; m.nq = nq;
+    m.score = ws_at<const float>(h, c.ws.ps); m.idx = ws_at<const int>(h, c.ws.pi); m.n_parts = c.n_parts; m.k = k; m.dim = h->dim; m.l2 = c.l2; m.nq = nq;
     m.part_len = c.plen; m.cap = c.cap;
-    m.eps = c.cert ? (const float*)(ws + c.o_eps) : nullptr; m.thr_init = c.use_floor ? (const float*)(ws + c.o_thr) : nullptr; m.qflag = nullptr;
-    m.part_cnt = c.emit ? (const int*)(ws + c.o_cnt) : nullptr; m.global_lb = (c.cert && c.canonical) ? global_lb : nullptr;
-    m.ak_in = c.have_ak ? (const float*)(ws + c.o_ak) : nullptr;
+    m.eps = c.cert ? ws_at<const float>(h, c.ws.eps) : nullptr; m.thr_init = c.use_floor ? ws_at<const float>(h, c.ws.thr) : nullptr;
+    m.part_cnt = c.emit ? ws_at<const int>(h, c.ws.cnt) : nullptr; m.global_lb = (c.cert && c.canonical) ? global_lb : nullptr;
+    m.ak_in = c.have_ak ? ws_at<const float>(h, c.ws.ak) : nullptr;
     m.flag_count = flag_count; m.flag_sel = flag_sel;
-    m.db = h->rows; m.db_f16 = h->f16; m.q = c.q_use; m.id_map = nullptr; m.id_base = h->id_base; m.out_dist = out_dist_dev; m.out_idx = out_idx_dev;
+    m.db = h->rows; m.db_f16 = h->f16; m.q = c.q_use; m.id_base = h->id_base; m.out_dist = out_dist_dev; m.out_idx = out_idx_dev;
     m.out_key = out_key_dev;
-    m.debug = 0;
 #ifdef RADAD_DEBUG_HOOKS
     { const char* dbg = getenv("RADAD_DEBUG_KNN"); m.debug = dbg ? atoi(dbg) : 0; }
 #endif
@@ -3562,7 +3563,7 @@ static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* glo
         x.db = h->rows; x.db_f16 = h->f16; x.q = c.q_use; x.sel = flag_sel; x.count = flag_count;
         x.n = h->ntotal; x.dim = h->dim; x.k = k; x.l2 = c.l2; x.group = c.xgroup;
         x.slice_rows = ceil_div64(std::max<int64_t>(h->ntotal, 1), KX_SLICES);
-        x.pkey = (double*)(ws + c.o_xk); x.pidx = (int*)(ws + c.o_xi); x.id_base = h->id_base;
+        x.pkey = ws_at<double>(h, c.ws.xk); x.pidx = ws_at<int>(h, c.ws.xi); x.id_base = h->id_base;
         x.out_dist = out_dist_dev; x.out_idx = out_idx_dev; x.out_key = out_key_dev;
         x.host_stats = h->host_count_dev + 8 * c.cslot; x.stamp = (int)(h->search_seq & 0x3fffffff) + 1; x.nq_report = (int)std::min<int64_t>(nq, 0x7fffffff);
         const size_t xlds = (size_t)c.xgroup * h->dim * 4 + (size_t)KX_WAVES * c.xgroup * k * 12 + 16;

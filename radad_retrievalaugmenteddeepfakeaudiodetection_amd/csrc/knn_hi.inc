@@ -36,59 +36,43 @@ constexpr int KW_SAMPLE_LIST = 16;                 // sample pre-pass: entries p
 
 
 struct KnnHiParams {
-    const void* db;        // [n][dim] f16: hi plane of an fp32 store, or the rows of an fp16 store
-    const float* rscale;   // [n] 2^-ey of each row, or nullptr: every row uses `uscale`
-    float uscale;          // 2^-ey shared by all rows when rscale == nullptr
-    const float* rbias;    // RSC 2: [n] per-row bias magnitude: |y'|^2 (L2, bias_sign -1) or mu.y (centred IP / cosine, bias_sign +1)
-    float bias_sign;
-    float mult;            // RSC 2: 2 (L2: score = 2 a - |y'|^2 - |q'|^2 estimates -|q - y|^2) or 1 (IP: a + mu.y + q'.mu estimates q.y)
-    const float* qconst;   // RSC 2: [nq] per-query constant of the score (-|q'|^2 or q'.mu), or nullptr
-    const void* q;         // [nq][dim] f16 scaled queries (centred when the plane is)
-    const float* qscale;   // [nq] 2^-eq
-    int64_t n;
-    int nq;
-    int row_bytes;         // dim * 2; multiple of 128
-    int l2;
-    int n_qtiles;
-    int n_splits;          // multiple of 8
-    int64_t chunk_rows;    // rows per split, multiple of KW_M
-    int64_t chunk_stride;  // rows between the starts of consecutive splits: chunk_rows, or more (the sample pre-pass spreads its tiles over the store)
-    int64_t id_off;        // reported row = id_off + row inside [db, db + n): a launch may cover a row range of the store
-    float* part_score;     // sample pre-pass: [nq, n_splits, 16] as 8 holders x 2;  scan: [nq, cand_cap] candidate scores
-    int* part_idx;         //                                                         ... and rows
-    int cand_cap;          // scan: entries of a query's candidate buffer
-    int* cand_cnt;         // scan: [nq] candidates emitted so far (may exceed cand_cap: the excess is not stored, the query is rejected)
-    const float* thr_init; // [nq] admission floor, or nullptr (-inf)
+    const void* db = nullptr;             // [n][dim] f16: hi plane of an fp32 store, or the rows of an fp16 store
+    const float* rscale = nullptr;        // [n] 2^-ey of each row, or nullptr: every row uses `uscale`
+    float uscale = 1.f;                   // 2^-ey shared by all rows when rscale == nullptr
+    const float* rbias = nullptr;         // RSC 2: [n] per-row bias magnitude: |y'|^2 (L2, bias_sign -1) or mu.y (centred IP / cosine, bias_sign +1)
+    float bias_sign = 1.f;
+    float mult = 1.f;                     // RSC 2: 2 (L2: score = 2 a - |y'|^2 - |q'|^2 estimates -|q - y|^2) or 1 (IP: a + mu.y + q'.mu estimates q.y)
+    const float* qconst = nullptr;        // RSC 2: [nq] per-query constant of the score (-|q'|^2 or q'.mu), or nullptr
+    const void* q = nullptr;              // [nq][dim] f16 scaled queries (centred when the plane is)
+    const float* qscale = nullptr;        // [nq] 2^-eq
+    int64_t n = 0;
+    int nq = 0;
+    int row_bytes = 0;                    // dim * 2; multiple of 128
+    int l2 = 0;
+    int n_qtiles = 0;
+    int n_splits = 0;                     // multiple of 8
+    int64_t chunk_rows = 0;               // rows per split, multiple of KW_M
+    int64_t chunk_stride = 0;             // rows between the starts of consecutive splits: chunk_rows, or more (the sample pre-pass spreads its tiles over the store)
+    int64_t id_off = 0;                   // reported row = id_off + row inside [db, db + n): a launch may cover a row range of the store
+    float* part_score = nullptr;          // sample pre-pass: [nq, n_splits, 16] as 8 holders x 2;  scan: [nq, cand_cap] candidate scores
+    int* part_idx = nullptr;              //                                                         ... and rows
+    int cand_cap = 0;                     // scan: entries of a query's candidate buffer
+    int* cand_cnt = nullptr;              // scan: [nq] candidates emitted so far (may exceed cand_cap: the excess is not stored, the query is rejected)
+    const float* thr_init = nullptr;      // [nq] admission floor, or nullptr (-inf)
     // K split over TWO workgroups per tile (small stores of wide rows: the reference's 25 423 x 5376 is 100 tiles of 84 K steps -- 100
     // workgroups on 256 CUs, each a chain of 84 dependent DMA round trips).  Workgroups 2j and 2j + 1 take the first / second half of
     // the K steps of tile j; each publishes its 256 x 256 partial sums; the one that arrives SECOND (device-scope counter) adds the
     // other's and runs the epilogue.  a + b == b + a in fp32: the result does not depend on who arrives first.
-    int loose_floor;       // 1: the counting form of the emit (see the epilogue)
-    int ksplit;            // 1 or 2 (2 only with one tile per workgroup)
-    float* kacc;           // ksplit 2: [tiles][2][32][512] f32x4 partial accumulators
-    int* kflag;            // ksplit 2: [tiles] arrival counters (zero between launches: the second arrival resets its own)
-    int debug;             // timing experiments, only in a -DRADAD_DEBUG_HOOKS build (RADAD_DEBUG_KNN): 1 skip the epilogue,
-                           // 2 skip the DMA issue
-    unsigned long long* stamps;   // -DRADAD_DEBUG_HOOKS only: [2][4096] (tag << 56 | s_memtime) of waves 0 and 4 of workgroup 0
-    // ONE launch over the whole store (round 5): the admission floors are raised INSIDE the launch.  Every workgroup counts the tiles it
-    // starts into its query tile's progress counter (a returning atomic issued in front of the tile's first DMA: it is back long before
-    // the epilogue).  The 32 workgroups whose tile numbers fall into [prog_thr[j], prog_thr[j] + 32) -- the query tile has then scanned
-    // ~prog_thr[j] x 256 rows, in whatever order and on however many CUs its chunks run -- take 8 of the tile's 256 queries each, one
-    // per wave: the k-th best score among the candidates emitted so far -- by ANY workgroup: the buffers are read past the non-coherent
-    // caches, and a slot that was reserved but not written yet still holds the -inf the buffer was cleared to -- minus 2 eps is
-    // atomic-max'ed into floor_live[q].  Every workgroup re-reads its 256 floors at the start of each tile.  Nothing waits for
-    // anything: the k-th best of ANY subset of the store's rows is a score k rows reach, so a floor read early, late or never is only
-    // looser, never wrong.  (The first form refreshed after fixed tile counts of the workgroup's OWN chunk: right while all chunk
-    // streams of a query tile run side by side, but the second and third round of a 640-workgroup grid start their chunks one by one --
-    // BASELINE config 5 at full size, 40 query tiles x 16 chunks: the last 8 query tiles emitted twice the candidates, 181 queries
-    // overflowed.)
-    float* floor_live;     // [nq] or nullptr (floors fixed for the launch: thr_init)
-    const float* eps;      // [nq] error bound of each query (floor = a_k - 2 eps)
-    int k_sel;             // the k of "k-th best"
-    int* prog;             // [n_qtiles] tiles started per query tile (zero at launch)
-    int prog_thr[4];       // tile counts at which the floors are refreshed (ascending; 0 = unused)
+    int loose_floor = 0;                  // 1: the counting form of the emit (see the epilogue)
+    int ksplit = 1;                       // 1 or 2 (2 only with one tile per workgroup)
+    float* kacc = nullptr;                // ksplit 2: [tiles][2][32][512] f32x4 partial accumulators
+    int* kflag = nullptr;                 // ksplit 2: [tiles] arrival counters (zero between launches: the second arrival resets its own)
+    int debug = 0;                        // timing experiments, only in a -DRADAD_DEBUG_HOOKS build (RADAD_DEBUG_KNN): 1 skip the epilogue,
+                                          // 2 skip the DMA issue
+    unsigned long long* stamps = nullptr; // -DRADAD_DEBUG_HOOKS only: [2][4096] (tag << 56 | s_memtime) of waves 0 and 4 of workgroup 0
+    // (floors raised inside one launch over the whole store were measured slower and removed: DESIGN §4.1)
 };
-constexpr int KW_REFRESH_WGS = 32;   // workgroups that share one refresh of a query tile's 256 floors (x 8 waves = one query each)
+static_assert(std::is_trivially_copyable_v<KnnHiParams>, "kernel argument");
 
 constexpr size_t knn_hi_lds_bytes() {
     return 2 * KW_STAGE_BYTES + sizeof(float) * KW_N * 4 + sizeof(float) * 2 * KW_M * 2 + 16;
@@ -117,45 +101,6 @@ constexpr size_t knn_hi_lds_bytes() {
 #else
 #define KH_STAMP(tag) do { } while (0)
 #endif
-
-// One WAVE raises the floor of query q0 + slot (slot < KW_N; candidate buffers of <= 1024 entries: 16 per lane in registers).  The k-th
-// largest by a 32-step binary search on the order-preserving image of the float bits: per step 16 compares, their ballots counted on
-// the scalar unit (~3000 cycles in all: once or twice per workgroup and launch).
-__device__ __forceinline__ void knn_hi_refresh_floor(const KnnHiParams& p, int q0, int slot) {
-    if (slot >= KW_N || q0 + slot >= p.nq) return;                     // (wave-uniform)
-    int lane = threadIdx.x & 63;
-    asm volatile("" : "+v"(lane));                                     // (formed here, not kept across the tile loop)
-    const int q = q0 + slot;
-    int c = __hip_atomic_load(p.cand_cnt + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    c = c < p.cand_cap ? c : p.cand_cap;
-    if (c < p.k_sel) return;
-    const float* sc = p.part_score + (int64_t)q * p.cand_cap;
-    unsigned key[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const int i = lane + 64 * j;
-        // (a reserved slot whose score has not reached memory yet reads as the -inf the buffer was cleared to)
-        const float v = i < c ? __hip_atomic_load(sc + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : -INFINITY;
-        const unsigned u = __float_as_uint(v);
-        key[j] = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    }
-    unsigned cur = 0;
-    for (int bit = 31; bit >= 0; --bit) {
-        const unsigned t = cur | (1u << bit);
-        int n = 0;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) n += __popcll(__ballot(key[j] >= t));
-        if (n >= p.k_sel) cur = t;                                     // (wave-uniform)
-    }
-    // cur = the k_sel-th largest key; written slots only: -inf maps to 0x007fffff, a real score above it
-    const float a_k = __uint_as_float((cur & 0x80000000u) ? (cur & 0x7fffffffu) : ~cur);
-    if (lane == 0 && a_k > -INFINITY) {
-        const float f = a_k - 2.f * p.eps[q];
-        // atomic max of a float through its bits: non-negative values order as ints, negative ones inversely as unsigned
-        if (f >= 0.f) atomicMax(reinterpret_cast<int*>(p.floor_live + q), __float_as_int(f));
-        else atomicMin(reinterpret_cast<unsigned*>(p.floor_live + q), __float_as_uint(f));
-    }
-}
 
 template <int RSC, bool SAMPLE>
 __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p) {
@@ -207,8 +152,7 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p) {
     const int nk = p.ksplit == 2 ? (part == 0 ? (nk_all >> 1) : nk_all - (nk_all >> 1)) : nk_all;
 
     if (tid < KW_N) {
-        s_thr[tid] = (owner && p.thr_init) ? (p.floor_live ? __hip_atomic_load(p.floor_live + q0 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                                           : p.thr_init[q0 + tid]) : -INFINITY;
+        s_thr[tid] = (owner && p.thr_init) ? p.thr_init[q0 + tid] : -INFINITY;
         // v = a * s_qs: the accumulator domain (RSC 0, 3) or accumulator x row scale (RSC 1, 2)
         float qi = owner ? p.qscale[q0 + tid] : 1.f;
         if (RSC == 0) qi *= p.uscale;
@@ -384,16 +328,6 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p) {
         const int rowlimit = (int)min((int64_t)KW_M, chunk_end - row0);
         const __amdgpu_buffer_rsrc_t cur_desc = tile_desc(row0);
         const __amdgpu_buffer_rsrc_t next_desc = tile_desc(row0 + KW_M);
-        // the query's floor as other workgroups have raised it meanwhile: the load is issued HERE, in front of the stage's DMA
-        // (vector-memory operations return in order: issued behind it, its consumer would wait for the DMA to land, ~1 us per tile),
-        // and lands in s_thr behind the stage's barrier, which waits for everything anyway.  (A reader of s_thr in the previous
-        // tile's epilogue sees the old or the new floor: both are valid.)
-        float live_floor = -INFINITY;
-        int tile_no = 0;                             // (thread 0: this tile's number among all tiles its query tile has started)
-        if (!SAMPLE && p.floor_live) {
-            if (owner && row0 != chunk_begin) live_floor = __hip_atomic_load(p.floor_live + q0 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (tid == 0) tile_no = atomicAdd(p.prog + qt, 1);
-        }
         for (int kc = 0; kc < nk; ++kc) {
             const int stage = gbuf & 1;
             const bool more_k = kc + 1 < nk;
@@ -413,10 +347,6 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p) {
             KH_STAMP(6);
             ++gbuf;
             if (kc == 0 && has_next) park_row_terms(row0 + KW_M, tile_par ^ 1);
-            if (!SAMPLE && kc == 0 && p.floor_live) {
-                if (owner && row0 != chunk_begin) s_thr[tid] = fmaxf(s_thr[tid], live_floor);
-                if (tid == 0) reinterpret_cast<int*>(s_rb + 2 * KW_M)[1] = tile_no;      // (read behind the tile's later barriers)
-            }
         }
         KH_STAMP(8);
         if (p.ksplit == 2) {
@@ -609,16 +539,6 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p) {
         }
         KH_STAMP(9);
         if (nk < 2 && has_next) __syncthreads();     // one K step per tile: the next tile's only barrier comes after park_row_terms' reader
-        if constexpr (!SAMPLE) {
-            if (p.floor_live) {
-                const int v = reinterpret_cast<const int*>(s_rb + 2 * KW_M)[1];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int off = v - p.prog_thr[j];
-                    if (p.prog_thr[j] > 0 && off >= 0 && off < KW_REFRESH_WGS) knn_hi_refresh_floor(p, q0, off * KW_WAVES + wave);
-                }
-            }
-        }
     }
 }
 
@@ -639,35 +559,36 @@ __global__ __launch_bounds__(KW_THREADS, 1) void k_knn_hi_sample(KnnHiParams p) 
 //   eps_out   (optional) [n]: the error bound eps(q) of this row used as a QUERY against a store with the given
 //             max |y| = ystat[0], max |y - yh| = ystat[1] (read from device memory: no host round trip)
 struct HiRowsParams {
-    const void* in;          // fp32 rows, or fp16 rows when in_f16 (statistics of an fp16 store)
-    int in_f16;
-    _Float16* hi;            // [n][dim] or nullptr (statistics only)
-    float* scale_out;        // [n] or nullptr
-    unsigned* stat_max;      // [4] or nullptr: max |x'|, max |x' - xh|, max |x|, max |mu.x'| (x' = x - mu when centred)
-    float* eps_out;          // [n] or nullptr
-    const unsigned* ystat;   // [4] store statistics (float bits) for eps_out
-    int64_t n;
-    int dim;
-    int fixed_e;
-    int l2;                  // eps for the L2 ranking score 2 q.y - |y|^2
-    int exact_ops;           // 1: the scan multiplies the fp32 operands themselves (fp32 MFMA paths): rounding terms are 0
-    float* norm_out;         // optional [n][dim]: rows are first normalised x / (|x| + 1e-12) (cosine queries, the arithmetic of
-                             // k_rows_prepare mode 2) and written here; everything else is computed from the normalised row
-    int* zero_flags2 = nullptr;  // optional [n]: a second per-row array to clear (the IVF list scan's running bounds)
-    int* zero_flags;         // optional [n]: set to 0 (the search's per-query flags) ...
-    int* zero_counters;      // ... and [8] counters, cleared by the first wave: saves the search a memset launch
+    const void* in = nullptr;        // fp32 rows, or fp16 rows when in_f16 (statistics of an fp16 store)
+    int in_f16 = 0;
+    _Float16* hi = nullptr;          // [n][dim] or nullptr (statistics only)
+    float* scale_out = nullptr;      // [n] or nullptr
+    unsigned* stat_max = nullptr;    // [4] or nullptr: max |x'|, max |x' - xh|, max |x|, max |mu.x'| (x' = x - mu when centred)
+    float* eps_out = nullptr;        // [n] or nullptr
+    const unsigned* ystat = nullptr; // [4] store statistics (float bits) for eps_out
+    int64_t n = 0;
+    int dim = 0;
+    int fixed_e = 0;
+    int l2 = 0;                      // eps for the L2 ranking score 2 q.y - |y|^2
+    int exact_ops = 0;               // 1: the scan multiplies the fp32 operands themselves (fp32 MFMA paths): rounding terms are 0
+    float* norm_out = nullptr;       // optional [n][dim]: rows are first normalised x / (|x| + 1e-12) (cosine queries, the arithmetic of
+                                     // k_rows_prepare mode 2) and written here; everything else is computed from the normalised row
+    int* zero_flags2 = nullptr;      // optional [n]: a second per-row array to clear (the IVF list scan's running bounds)
+    int* zero_flags = nullptr;       // optional [n]: set to 0 (the search's per-query flags) ...
+    int* zero_counters = nullptr;    // ... and [8] counters, cleared by the first wave: saves the search a memset launch
     // CENTRED planes (knn_ensure_hi decides per store): the rounded operand is x' = x - mu, so that a common component of all
     // embeddings -- pooled encoder features share most of their mean -- does not eat the f16 mantissa: the Cauchy-Schwarz error
     // bound scales with |x'|, not |x|.  L2 is translation invariant; for IP / cosine q.y = q'.y' + mu.y + q'.mu.
-    const float* mu;         // [dim] or nullptr
-    float mu_norm;           // |mu|, rounded up (host-known: computed once, when the plane is built)
-    float mu_sq;             // |mu|^2 as the device summed it (a term of the per-query constant)
-    int biased;              // 1: the scan runs the scale + bias variant (RSC 2): L2 always, IP / cosine when centred
+    const float* mu = nullptr;       // [dim] or nullptr
+    float mu_norm = 0.f;             // |mu|, rounded up (host-known: computed once, when the plane is built)
+    float mu_sq = 0.f;               // |mu|^2 as the device summed it (a term of the per-query constant)
+    int biased = 0;                  // 1: the scan runs the scale + bias variant (RSC 2): L2 always, IP / cosine when centred
     // IP / cosine: q.y = q'.y' + mu.y' + (q'.mu + |mu|^2) -- the row's share is mu.y' (small: the centred rows are nearly
     // orthogonal to their mean), the large |mu|^2 goes with the query's constant, so the accumulators never carry it
-    float* bias_out;         // store side, optional [n]: |x'|^2 (L2) or mu.x' (IP / cosine)
-    float* qconst_out;       // query side, optional [n]: -|x'|^2 (L2) or x'.mu + |mu|^2 (IP / cosine)
+    float* bias_out = nullptr;       // store side, optional [n]: |x'|^2 (L2) or mu.x' (IP / cosine)
+    float* qconst_out = nullptr;     // query side, optional [n]: -|x'|^2 (L2) or x'.mu + |mu|^2 (IP / cosine)
 };
+static_assert(std::is_trivially_copyable_v<HiRowsParams>, "kernel argument");
 constexpr int HI_E_PER_ROW = -0x7fffffff - 1;
 
 // WPR = waves per row: 1 (a wave per row, four rows per workgroup: the plane's rows, batches of queries) or 4 (the whole workgroup on

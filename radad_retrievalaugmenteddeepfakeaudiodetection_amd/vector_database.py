@@ -74,10 +74,14 @@ def write_faiss_flat(path: str, rows: np.ndarray, metric: str):
 
 def knn_options_from_config(config):
     """the optional scan knobs, read the way the reference reads its own optional ones (getattr with a default,
-    vector_database.py:43,67,80): knn_hi_plane, knn_centre, knn_smallq_hi, knn_wide_min_q, knn_dense, knn_live_floor; absent / None = the library's default"""
+    vector_database.py:43,67,80): knn_hi_plane, knn_centre, knn_smallq_hi, knn_wide_min_q, knn_dense; absent / None = the library's default.
+    knn_live_floor is still recognised, but only None / 0 (the default): the one-launch scan form it selected was removed"""
+    if getattr(config, "knn_live_floor", None) not in (None, 0):
+        raise ValueError("knn_live_floor: the one-launch scan form was measured slower and removed (DESIGN §4.1); "
+                         "leave it None / 0 for the default, one launch per phase")
     opts = dict(hi_plane=getattr(config, "knn_hi_plane", None), centre=getattr(config, "knn_centre", None),
                 smallq_hi=getattr(config, "knn_smallq_hi", None), wide_min_q=getattr(config, "knn_wide_min_q", None),
-                dense=getattr(config, "knn_dense", None), live_floor=getattr(config, "knn_live_floor", None))
+                dense=getattr(config, "knn_dense", None))
     return {k: v for k, v in opts.items() if v is not None}
 
 
@@ -87,8 +91,8 @@ class HipFlatIndex:
     is_trained = True   # flat indexes need no training (vector_database.py:124)
 
     def __init__(self, d: int, metric: int, device: int = 0, id_base: int = 0, store_f16: bool = False, hi_plane=None, centre=None,
-                 smallq_hi=None, wide_min_q=None, dense=None, live_floor=None):
-        """hi_plane / centre / smallq_hi / wide_min_q / dense / live_floor: kernel choices of the handle (radad_knn_set_option; None = the library's
+                 smallq_hi=None, wide_min_q=None, dense=None):
+        """hi_plane / centre / smallq_hi / wide_min_q / dense: kernel choices of the handle (radad_knn_set_option; None = the library's
         default).  They change speed, never results: A/B measurements and the parity tests select kernels through them."""
         self._lib = _lib.load()
         self.d = int(d)
@@ -100,9 +104,9 @@ class HipFlatIndex:
         _lib.check(self._lib.radad_knn_create_ex(self.d, self.metric, _lib.STORE_F16 if self.store_f16 else _lib.STORE_F32,
                                                  self.device, self.id_base, C.byref(h)), "radad_knn_create")
         self._h = h
-        self.options = dict(hi_plane=hi_plane, centre=centre, smallq_hi=smallq_hi, wide_min_q=wide_min_q, dense=dense, live_floor=live_floor)
+        self.options = dict(hi_plane=hi_plane, centre=centre, smallq_hi=smallq_hi, wide_min_q=wide_min_q, dense=dense)
         for opt, val in ((_lib.KNN_OPT_HI_PLANE, hi_plane), (_lib.KNN_OPT_CENTRE, centre), (_lib.KNN_OPT_SMALLQ_HI, smallq_hi),
-                         (_lib.KNN_OPT_WIDE_MIN_Q, wide_min_q), (_lib.KNN_OPT_DENSE, dense), (_lib.KNN_OPT_LIVE_FLOOR, live_floor)):
+                         (_lib.KNN_OPT_WIDE_MIN_Q, wide_min_q), (_lib.KNN_OPT_DENSE, dense)):
             if val is not None:
                 _lib.check(self._lib.radad_knn_set_option(self._h, opt, int(val)), "radad_knn_set_option")
 

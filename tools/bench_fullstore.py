@@ -25,7 +25,6 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--plant-every", type=int, default=8)
-    ap.add_argument("--live-floor", type=int, default=-1, help="-1 = the library's default, 1 / 0 = one scan launch with the floors raised inside it / one launch per phase")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -52,7 +51,7 @@ def main():
     # 1024 queries: ~150).  --plant-every 1 measures that store: the handle widens its buffers (cap_boost) inside the first search.
     pq = torch.arange(0, B, args.plant_every, device=dev)
     planted = (pq * (n // B - 3) + 29) % n
-    idx = R.HipFlatIndex(dim, _lib.METRIC_COSINE, 0, store_f16=c5, live_floor=(None if args.live_floor < 0 else args.live_floor))
+    idx = R.HipFlatIndex(dim, _lib.METRIC_COSINE, 0, store_f16=c5)
     t_add = time.perf_counter()
     step = 1 << 20
     for r0 in range(0, n, step):
@@ -105,7 +104,7 @@ def main():
            "data": "synthetic",
            "config": {"workload": f"{B} clips x 4 s @16 kHz, F={dim}, levels=[1], cosine top-{k}, {n} x {dim} "
                                   f"{'f16' if c5 else 'f32'} store on ONE handle", "db_rows": n, "dim": dim, "k": k,
-                      "planted_for_every_nth_query": args.plant_every, "live_floor": args.live_floor,
+                      "planted_for_every_nth_query": args.plant_every,
                       # (synthetic clips come in 181 periods: clips of one period embed within cos 0.9999 of each other, so the top hit of a
                       # query may be the planted copy of a same-period clip -- with bf16 embeddings it often is)
                       "planted_row_is_top1": round(float((I[pq, 0] == planted).float().mean().item()), 4),

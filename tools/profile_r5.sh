@@ -50,8 +50,6 @@ for w in 2 4 8; do python tools/rehearse_rank.py --world $w 2> /dev/null; done >
 for w in 2 4 8; do python tools/rehearse_rank.py --world $w --plant all 2> /dev/null; done > $RESULTS_DIR/${T}_rehearse_plant_all.txt; echo rehearse
 python tools/bench_fullstore.py --config 4 > $RESULTS_DIR/${T}_config4_full.json 2> /dev/null
 python tools/bench_fullstore.py --config 5 > $RESULTS_DIR/${T}_config5_full.json 2> /dev/null; echo fullstore
-python bench.py --full --live-floor 1 --cpu-sample 0 --cpu-baseline-clips 0 --pcie 0 --sustain 0 --unstructured 0 > $RESULTS_DIR/${T}_bench_one_launch.json 2> /dev/null
-python bench.py --full --live-floor 1 --db-rows 100000 --cpu-sample 0 --cpu-baseline-clips 0 --pcie 0 --sustain 0 --unstructured 0 > $RESULTS_DIR/${T}_bench_config2_one_launch.json 2> /dev/null; echo ab2
 python tools/bench_ivf.py > $RESULTS_DIR/${T}_ivf.json 2> /dev/null
 python tools/bench_ivf.py 1,256,1024 0 > $RESULTS_DIR/${T}_ivf_f32_lists.json 2> /dev/null; echo ivf
 for f in default ragged config2 f16 bf16_f16 scan_f32 logmel_gemm; do python - <<PY
