@@ -122,8 +122,9 @@ int radad_knn_search(radad_knn_t h, const float* q_dev, int64_t nq, int k, float
  * row whose scan score is within 2 eps of the k-th best is re-scored in float64 from the stored rows (L2 as sum (q-y)^2)
  * and ordered by (float64 distance, id); a per-query certificate checks that no unlisted row can reach that threshold, and
  * the queries it rejects are searched again by an exact float64 kernel (driven from the device, no host round trip).  For
- * k <= 128 ids and order are therefore those of an exact float64 brute force, ties to the lower id, and out_dist is the
- * correctly rounded distance; for larger k the k + 6 best scan candidates are re-ranked without a certificate.  Sharded
+ * every k in [1, RADAD_KNN_MAX_K] ids and order are therefore those of an exact float64 brute force, ties to the lower id, and
+ * out_dist is the correctly rounded distance (k <= 128 takes the f16 MFMA scans where they apply; larger k the fp32 tile
+ * kernels, certified the same way).  Sharded
  * searches merge on these keys (radad_topk_merge_f64) so that no cross-shard pair is decided by fp32 rounding.
  * A handle may be searched from several threads and streams: calls are serialised by a mutex and a search enqueued on another
  * stream than the previous one waits (event) for that one's device work, since they share the handle's workspace. */

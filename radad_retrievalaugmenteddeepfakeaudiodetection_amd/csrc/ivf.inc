@@ -843,7 +843,7 @@ int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int n
                      void* stream) {
     RADAD_REQUIRE(h, "NULL handle");
     RADAD_REQUIRE(h->trained, "radad_ivf_search: the index is not trained");
-    RADAD_REQUIRE(k >= 1 && k <= KNN_CERT_MAX_K, "radad_ivf_search: k=%d outside [1,%d]", k, KNN_CERT_MAX_K);
+    RADAD_REQUIRE(k >= 1 && k <= IVF_MAX_K, "radad_ivf_search: k=%d outside [1,%d]", k, IVF_MAX_K);
     RADAD_REQUIRE(nq >= 0 && nq < (1 << 24), "radad_ivf_search: bad nq");
     if (nq == 0) return RADAD_OK;
     RADAD_REQUIRE(q_dev && out_dist_dev && out_idx_dev, "radad_ivf_search: NULL buffer");

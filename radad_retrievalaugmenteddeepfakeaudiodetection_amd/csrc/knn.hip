@@ -1129,13 +1129,14 @@ constexpr size_t knn_reg_lds_bytes() { return 4 * KD_TILE_BYTES + sizeof(float2)
 //       used up by the selection while full (its tail could hide such rows), the scan's admission floor thr_init is
 //       <= tau (rows below the floor were never listed), the scan dropped nothing for this query (qflag), and the
 //       candidate buffer (cap) sufficed.  Uncertified queries are appended to flag_sel for the exact kernel below.
-//   eps == nullptr (IVF list scans, k > 128): legacy behaviour -- the `cap` best candidates are re-scored, no certificate.
+//   eps == nullptr (IVF list scans): legacy behaviour -- the `cap` best candidates are re-scored, no certificate.
 // k_merge_lists<KeyT> (radad_topk_merge / _f64): plain P-way merge of final per-shard lists, no rescoring.
 constexpr int KNN_MARGIN = 6;            // spare entries of a (query, chunk) list on the fp32 tile kernels
 constexpr int KNN_CERT_EXTRA = 32;       // candidates beyond k the certified re-rank can take before it gives up, at least ...
 constexpr int KNN_CERT_CAP = 512;        // ... and this many in all: stores of near-duplicates (the benchmark plants 2048 rows
                                          // within 2e-2 of every query) put hundreds of rows within 2 eps of the k-th
-constexpr int KNN_CERT_MAX_K = 128;      // largest k the certificate + exact kernel cover
+constexpr int KNN_F16_MAX_K = 128;       // largest k the certified f16 scans take; beyond it the fp32 tile kernels filter (certified too)
+constexpr int IVF_MAX_K = 128;           // largest k of radad_ivf_search (HipIVFFlatIndex.MAX_K); flat searches take any k <= RADAD_KNN_MAX_K
 constexpr int KW_SAMPLE_SPLITS = 64;     // one-tile splits of the threshold pre-pass (<= 16384 rows)
 
 struct RefineParams {
@@ -1725,6 +1726,7 @@ constexpr int RS_THREADS = 1024;
 constexpr int RS_WAVES = RS_THREADS / 64;
 constexpr int RS_SPLIT = 8;
 constexpr int RS_MAX_PARTS = RS_THREADS;
+constexpr int RS_MAX_CAP = KNN_CERT_CAP + 128;     // candidates per query (rs_key's rows); larger caps take k_merge_refine
 constexpr size_t refine_small_lds_bytes(int cap) { return (size_t)cap * 20 + (size_t)RS_MAX_PARTS * 4 + 256 * 4 + 256; }
 
 __global__ __launch_bounds__(RS_THREADS) void k_refine_small(RefineParams p, double* __restrict__ wkey, int* __restrict__ wcount) {
@@ -1879,7 +1881,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_refine_small(RefineParams p, dou
 
 // ---- exact float64 search of the queries the certificate rejected --------------------------------------------------
 // Driven entirely from the device: the number of queries (*count) and their indices (sel) were written by
-// k_merge_refine; the launch geometry is fixed, workgroups with nothing to do leave at once.  Slice s of the store
+// k_merge_refine; the launch geometry is fixed, workgroups with nothing to do leave at once.  One launch takes the rejected
+// queries sel[slot0 .. slot0 + nslots) (the partial lists of nslots queries are what the workspace holds; larger batches at large
+// k take several launches, knn_exact_slots).  Slice s of the store
 // (n_slices row ranges) is scanned by workgroups (s, y); workgroup (s, y) takes the query groups y, y + gridDim.y, ...
 // of `group` (<= 8) queries each.  A wave reads one row per step (coalesced), every lane multiplies its elements with
 // the group's queries from LDS in float64, a butterfly sum leaves the (row, query) scores in all lanes; each wave keeps
@@ -1891,6 +1895,16 @@ constexpr int KX_THREADS = 512;
 constexpr int KX_WAVES = KX_THREADS / 64;
 constexpr int KX_SLICES = 64;
 constexpr int KX_GROUPS_Y = 4;
+constexpr size_t KX_LDS_MAX = 160 * 1024;              // LDS of a CU: the group's queries + KX_WAVES sorted lists of k per query
+constexpr size_t KX_PART_BUDGET = (size_t)128 << 20;   // workspace of one launch's partial lists (KX_SLICES x k x 12 B per query)
+
+// rejected queries one launch of k_exact_scan takes: as many as KX_PART_BUDGET holds partial lists for, a whole group at least.
+// (k = 1024: 170 per launch, 128 MiB -- instead of 64 x 1024 x 12 B = 768 KiB for EVERY query of the batch, 805 MB at nq = 1024;
+// k <= 128 with batches of up to 1365 queries: one launch, as before)
+static int64_t knn_exact_slots(int64_t nq, int k, int group) {
+    const int64_t per_q = (int64_t)KX_SLICES * k * (int64_t)(sizeof(double) + sizeof(int));
+    return std::min<int64_t>(nq, std::max<int64_t>(group, (int64_t)(KX_PART_BUDGET / per_q) / group * group));
+}
 
 struct ExactParams {
     const void* db = nullptr; int db_f16 = 0;
@@ -1899,7 +1913,8 @@ struct ExactParams {
     const int* count = nullptr;
     int64_t n = 0; int dim = 0, k = 0, l2 = 0, group = 1;
     int64_t slice_rows = 0;
-    double* pkey = nullptr;    // [nq][KX_SLICES][k]
+    int slot0 = 0, nslots = 0; // this launch's rejected queries: sel[slot0 ..], at most nslots of them
+    double* pkey = nullptr;    // [nslots][KX_SLICES][k]
     int* pidx = nullptr;
     int64_t id_base = 0;
     float* out_dist = nullptr; int64_t* out_idx = nullptr; double* out_key = nullptr;
@@ -1911,10 +1926,16 @@ struct ExactParams {
 static_assert(std::is_trivially_copyable_v<ExactParams>, "kernel argument");
 
 __device__ __forceinline__ bool kx_better(double ka, int ia, double kb, int ib) { return ka > kb || (ka == kb && ia < ib); }
+// the LDS reads and writes of one wave on either side stay on their side (lanes read entries that other lanes then overwrite)
+__device__ __forceinline__ void kx_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 __device__ __forceinline__ void exact_merge_slot(const ExactParams& p, int slot, int lane);
 
 __global__ __launch_bounds__(KX_THREADS) void k_exact_scan(ExactParams p) {
-    const int count = *p.count;
+    const int count = min(*p.count - p.slot0, p.nslots);       // this launch's queries
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && p.host_stats) {
         *reinterpret_cast<volatile int*>(&p.host_stats[6]) = 0;          // the slot is being rewritten: no report until the new stamp is there
         __threadfence_system();
@@ -1941,7 +1962,7 @@ __global__ __launch_bounds__(KX_THREADS) void k_exact_scan(ExactParams p) {
         for (int i = tid; i < ng * nv; i += KX_THREADS) {
             const int qq = i / nv, c4 = i % nv;
             reinterpret_cast<f32x4*>(sQ + (size_t)qq * p.dim)[c4] =
-                reinterpret_cast<const f32x4*>(p.q + (int64_t)p.sel[g * G + qq] * p.dim)[c4];
+                reinterpret_cast<const f32x4*>(p.q + (int64_t)p.sel[p.slot0 + g * G + qq] * p.dim)[c4];
         }
         double* wKey = sKey + (size_t)wave * G * p.k;
         int* wId = sId + (size_t)wave * G * p.k;
@@ -1981,16 +2002,24 @@ __global__ __launch_bounds__(KX_THREADS) void k_exact_scan(ExactParams p) {
                     double* lk = wKey + (size_t)j * p.k;
                     int* li = wId + (size_t)j * p.k;
                     if (kx_better(v, (int)row, lk[p.k - 1], li[p.k - 1])) {
-                        // lane l looks after entries l, l + 64 (k <= 128): read all, count the better ones, shift, write
-                        double e0 = -INFINITY, e1 = -INFINITY;
-                        int i0 = IDX_SENTINEL, i1 = IDX_SENTINEL;
-                        if (lane < p.k) { e0 = lk[lane]; i0 = li[lane]; }
-                        if (lane + 64 < p.k) { e1 = lk[lane + 64]; i1 = li[lane + 64]; }
-                        const bool b0 = lane < p.k && kx_better(e0, i0, v, (int)row);
-                        const bool b1 = lane + 64 < p.k && kx_better(e1, i1, v, (int)row);
-                        const int pos = __popcll(__ballot(b0)) + __popcll(__ballot(b1));
-                        if (lane < p.k && !b0 && lane + 1 < p.k) { lk[lane + 1] = e0; li[lane + 1] = i0; }
-                        if (lane + 64 < p.k && !b1 && lane + 65 < p.k) { lk[lane + 65] = e1; li[lane + 65] = i1; }
+                        // strips of 64 entries (lane l <-> entry 64 s + l), the LAST strip first: a strip reads its entries, counts
+                        // the better ones and moves the others one place down -- onto the next strip's first entry, which that
+                        // strip has already read.  The better entries are a prefix of the sorted list: a strip of nothing but
+                        // better entries ends the walk (all strips before it are better too).
+                        int pos = 0;
+                        for (int s0 = (p.k - 1) & ~63; s0 >= 0; s0 -= 64) {
+                            const int e = s0 + lane;
+                            double ek = -INFINITY;
+                            int ei = IDX_SENTINEL;
+                            if (e < p.k) { ek = lk[e]; ei = li[e]; }
+                            const bool b = e < p.k && kx_better(ek, ei, v, (int)row);
+                            const int nb = __popcll(__ballot(b));
+                            kx_wave_sync();                          // every lane has read its entry before any moves one down
+                            if (e < p.k && !b && e + 1 < p.k) { lk[e + 1] = ek; li[e + 1] = ei; }
+                            kx_wave_sync();
+                            pos += nb;
+                            if (nb == 64) { pos += s0; break; }      // (wave-uniform)
+                        }
                         if (lane == (pos & 63)) { lk[pos] = v; li[pos] = (int)row; }
                     }
                 }
@@ -2002,7 +2031,7 @@ __global__ __launch_bounds__(KX_THREADS) void k_exact_scan(ExactParams p) {
             int pos[KX_WAVES];
 #pragma unroll
             for (int w = 0; w < KX_WAVES; ++w) pos[w] = 0;
-            const int64_t ob = ((int64_t)(g * G + wave) * KX_SLICES + blockIdx.x) * p.k;
+            const int64_t ob = ((int64_t)(g * G + wave) * KX_SLICES + blockIdx.x) * p.k;       // (slot local to the launch)
             for (int o = 0; o < p.k; ++o) {
                 double bk = -INFINITY; int bi = IDX_SENTINEL, bw = -1;
 #pragma unroll
@@ -2038,11 +2067,11 @@ __global__ __launch_bounds__(KX_THREADS) void k_exact_scan(ExactParams p) {
     }
 }
 
-// one wave: merge the KX_SLICES partial lists of rejected-query slot `slot`, overwrite the query's output rows
+// one wave: merge the KX_SLICES partial lists of this launch's rejected-query slot `slot`, overwrite the query's output rows
 __device__ __forceinline__ void exact_merge_slot(const ExactParams& p, int slot, int lane) {
     static_assert(KX_SLICES == 64, "one list per lane");
     {
-    const int64_t q = p.sel[slot];
+    const int64_t q = p.sel[p.slot0 + slot];
     const double* lk = p.pkey + ((int64_t)slot * KX_SLICES + lane) * p.k;
     const int* li = p.pidx + ((int64_t)slot * KX_SLICES + lane) * p.k;
     int pos = 0;
@@ -2305,7 +2334,7 @@ struct SearchCtx {
     bool valid = false;
     int64_t nq = 0;
     int k = 0, l2 = 0, cslot = 0, n_parts = 0, plen = 0, cap = 0, xgroup = 1;
-    bool cert = false, emit = false, use_floor = false;
+    bool emit = false, use_floor = false;
     bool small_lists = false;          // the streaming kernels' output: one SORTED list per workgroup and query (k_refine_small)
     bool canonical = false;            // the scan's scores estimate q.y / -|q - y|^2 themselves (comparable across shards); the fp32
                                        // kernels' L2 score 2 q.y - |y|^2 lacks the -|q|^2: a cross-shard bound does not apply to it
@@ -2995,7 +3024,6 @@ struct ScanPlan {
     int kind = RADAD_SCAN_F32_TILE;  // RADAD_SCAN_*
     int64_t nq = 0;
     int k = 0, l2 = 0;
-    bool cert = false;               // k <= KNN_CERT_MAX_K: certified re-rank + exact kernel (beyond: k + margin candidates, no certificate)
     int n_qtiles = 0, n_splits = 0;  // workgroups: query tiles x row splits (the streaming kernels: 1 x n_splits)
     int64_t chunk_rows = 0;
     int ksel = 0;                    // list length of the fp32 tile kernels: k + margin
@@ -3011,7 +3039,6 @@ struct ScanPlan {
     int xgroup = 1;                  // queries per workgroup of the exact kernel
     bool hi_q = false;               // f16 queries with a per-query scale (the certified f16 kernels)
     bool biased = false;             // the scale + bias variant of the f16 kernels (RSC 2, 3)
-    bool prep = false;               // k_hi_rows prepares the queries: it also normalises and clears the flags
     const float* mu = nullptr;       // centred plane: the queries are centred the same way
     bool f16_queries() const { return kind == RADAD_SCAN_HI_TILE || kind == RADAD_SCAN_HI_SMALLQ || kind == RADAD_SCAN_F16_TILE; }
 };
@@ -3021,7 +3048,6 @@ struct ScanPlan {
 static int knn_plan_scan(radad_knn_t h, int64_t nq, int k, int margin, hipStream_t st, ScanPlan* out) {
     ScanPlan p;
     p.nq = nq; p.k = k; p.l2 = h->metric == RADAD_METRIC_L2 ? 1 : 0;
-    p.cert = k <= KNN_CERT_MAX_K;
     p.ksel = k + margin;
     knn_geometry(std::max<int64_t>(h->ntotal, 1), nq, &p.n_qtiles, &p.n_splits, &p.chunk_rows);
     const int ksel = p.ksel;
@@ -3034,9 +3060,13 @@ static int knn_plan_scan(radad_knn_t h, int64_t nq, int k, int margin, hipStream
     const size_t sq_lds_f32 = sizeof(float) * (size_t)nq * (h->dim + 4) + sq_slot_bytes;
     const bool sq_fits = nq <= SQ_NQ && ksel <= 32 &&
                          ((!h->hi_off && h->dim % 64 == 0 && sq_lds_hi <= SQ_LDS_BUDGET) || (!h->f16 && h->dim % 32 == 0 && sq_lds_f32 <= SQ_LDS_BUDGET));
-    // the certified tile scan: any k the certificate covers (its candidate buffers are sized from k); the floor's rank k + margin
-    // must exist in the sample (16 entries per sample tile)
-    if (p.cert && (nq >= h->opt_wide_min_q || !sq_fits) && h->ntotal > 0 && h->dim % 64 == 0 && !h->hi_off) {
+    // the certified f16 scans take k <= KNN_F16_MAX_K: their candidate buffers (emit_cap <= RF_STAGE_MAX) and phase sizes are
+    // tuned for ~8 (k + margin) admissions per launch.  Larger k is filtered by the fp32 tile kernels (lists of k + margin per
+    // split), certified the same way.
+    const bool f16_k = k <= KNN_F16_MAX_K;
+    // the certified tile scan: its candidate buffers are sized from k; the floor's rank k + margin must exist in the sample (16
+    // entries per sample tile)
+    if (f16_k && (nq >= h->opt_wide_min_q || !sq_fits) && h->ntotal > 0 && h->dim % 64 == 0 && !h->hi_off) {
         int wq, ws; int64_t wc;
         knn_geometry_wide(h->ntotal, nq, &wq, &ws, &wc);
         // the sample pre-pass: one tile per workgroup, at most KW_SAMPLE_SPLITS tiles and 1/8 of the store (whatever the number of
@@ -3059,11 +3089,11 @@ static int knn_plan_scan(radad_knn_t h, int64_t nq, int k, int margin, hipStream
             else if (knn_ensure_hi(h, st, true)) { use_hi = true; p.n_qtiles = wq; }
         }
     }
-    if (!use_hi && p.cert && !knn_ensure_hi(h, st, false)) { radad_set_error("store statistics could not be computed"); return RADAD_EHIP; }
+    if (!use_hi && !knn_ensure_hi(h, st, false)) { radad_set_error("store statistics could not be computed"); return RADAD_EHIP; }
     const bool smallq_geom = !use_hi && nq <= SQ_NQ && ksel <= 32 && h->ntotal > 0;
     // the small batch over the f16 plane (certified like the tile scan): stores the plane is kept for, or fp16 stores
     bool smallq_hi = false;
-    if (smallq_geom && p.cert && h->opt_smallq_hi && h->dim % 64 == 0 && h->ntotal >= 16384 && !h->hi_off && !skipped_hi &&
+    if (smallq_geom && f16_k && h->opt_smallq_hi && h->dim % 64 == 0 && h->ntotal >= 16384 && !h->hi_off && !skipped_hi &&
         sq_lds_hi <= SQ_LDS_BUDGET) {
         // (every search that would take a certified f16 kernel counts the skip down: a handle that only sees small batches after a
         // mass rejection used to stay on the fp32 kernel for ever)
@@ -3072,7 +3102,7 @@ static int knn_plan_scan(radad_knn_t h, int64_t nq, int k, int margin, hipStream
     }
     // a small fp32 store (the IVF index's centroids; a database of a few thousand files): every score + select on the staged copy
     p.dense_plen = (int)((std::max<int64_t>(h->ntotal, 1) + 3) / 4 * 4);
-    const bool dense = p.cert && !use_hi && !smallq_hi && !h->f16 && h->opt_dense && h->ntotal >= 1 &&
+    const bool dense = !use_hi && !smallq_hi && !h->f16 && h->opt_dense && h->ntotal >= 1 &&
                        h->ntotal <= (nq <= SQ_NQ ? RF_STAGE_MAX_SMALLQ : RF_STAGE_MAX) && h->dim % 16 == 0 && nq * (int64_t)p.dense_plen <= ((int64_t)1 << 24);
     const bool smallq = smallq_geom && !dense && !smallq_hi && !h->f16 && h->dim % 32 == 0 && sq_lds_f32 <= SQ_LDS_BUDGET;
     // a small store of wide rows (the reference's own: 25 423 x 5376) has too few 16-row steps to occupy the chip with one wave per
@@ -3121,12 +3151,13 @@ static int knn_plan_scan(radad_knn_t h, int64_t nq, int k, int margin, hipStream
     // workgroups in one round.  More near-ties than that reject the query: exact kernel.)
     // (a handle that has widened its candidate buffers -- cap_boost: a store whose rows crowd within 2 eps of the k-th best -- also
     // re-ranks four times as many: the fp32 funnel in front of the float64 re-score takes them at ~2 KB of row reads each)
-    p.cap = p.cert ? (dense ? k + KNN_CERT_EXTRA : std::max(k + KNN_CERT_EXTRA, KNN_CERT_CAP * (use_hi ? h->cap_boost : 1))) : ksel;
-    p.xgroup = (int)std::max<size_t>(1, std::min<size_t>(8, (size_t)(64 * 1024) / ((size_t)h->dim * 4)));
+    p.cap = dense ? k + KNN_CERT_EXTRA : std::max(k + KNN_CERT_EXTRA, KNN_CERT_CAP * (use_hi ? h->cap_boost : 1));
+    // (the group's lists shrink it at large k: k = 1024 takes one query per workgroup, 98 KB of lists)
+    p.xgroup = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(8, (size_t)(64 * 1024) / ((size_t)h->dim * 4)),
+                                                         (KX_LDS_MAX - 16) / ((size_t)h->dim * 4 + (size_t)KX_WAVES * k * 12)));
     p.hi_q = use_hi || smallq_hi;
     p.mu = (p.hi_q && !h->f16) ? h->cmu : nullptr;
     p.biased = p.hi_q && (p.l2 || p.mu);
-    p.prep = p.cert || use_hi || f16_tile;
     *out = p;
     return RADAD_OK;
 }
@@ -3158,8 +3189,9 @@ static SearchLayout knn_search_layout(radad_knn_t h, const ScanPlan& p, int q_dt
     L.fsel = take(b_vec);
     L.ps = take(b_part);
     L.pi = take(b_part);
-    L.xk = take(p.cert ? al256((size_t)nq * KX_SLICES * p.k * sizeof(double)) : 0);
-    L.xi = take(p.cert ? al256((size_t)nq * KX_SLICES * p.k * sizeof(int)) : 0);
+    const int64_t xslots = knn_exact_slots(nq, p.k, p.xgroup);
+    L.xk = take(al256((size_t)xslots * KX_SLICES * p.k * sizeof(double)));
+    L.xi = take(al256((size_t)xslots * KX_SLICES * p.k * sizeof(int)));
     L.bytes = off;
     return L;
 }
@@ -3175,22 +3207,20 @@ static const float* knn_prepare_queries(radad_knn_t h, const ScanPlan& p, const 
         q_use = qf;
     }
     const bool cosine = h->metric == RADAD_METRIC_COSINE;
-    // (with prep the normalisation happens inside k_hi_rows, which reads the raw queries)
-    if (cosine && !p.prep)
-        hipLaunchKernelGGL(k_rows_prepare<float>, dim3((unsigned)ceil_div64(nq, 4)), dim3(256), 0, st, q_use, ws_at<float>(h, L.qn), (float*)nullptr, nq, h->dim, 2);
+    // k_hi_rows prepares the queries of every search: normalisation (cosine), f16 copy, error bound eps, cleared flags and counters
     // (|q|^2 is not needed: ranking uses 2 q.y - |y|^2 and the reported distance is re-scored exactly)
-    if (p.prep) {
+    {
         const bool f16_tile = p.kind == RADAD_SCAN_F16_TILE;
         HiRowsParams hp;
         hp.in = q_use;
         hp.hi = p.f16_queries() ? ws_at<_Float16>(h, L.qh) : nullptr;
         hp.scale_out = p.hi_q ? ws_at<float>(h, L.qscale) : nullptr;
-        hp.eps_out = p.cert ? ws_at<float>(h, L.eps) : nullptr; hp.ystat = h->stat;
+        hp.eps_out = ws_at<float>(h, L.eps); hp.ystat = h->stat;
         hp.n = nq; hp.dim = h->dim;
         hp.fixed_e = p.hi_q ? HI_E_PER_ROW : 0;          // the fp16 tile kernel multiplies un-scaled fp16 queries
         hp.l2 = p.l2; hp.exact_ops = p.f16_queries() ? 0 : 1;
         hp.norm_out = cosine ? ws_at<float>(h, L.qn) : nullptr;
-        hp.zero_flags = p.cert ? ws_at<int>(h, L.cnt) : nullptr; hp.zero_counters = p.cert ? ws_at<int>(h, L.fcount) : nullptr;
+        hp.zero_flags = ws_at<int>(h, L.cnt); hp.zero_counters = ws_at<int>(h, L.fcount);
         hp.mu = p.mu; hp.mu_norm = p.mu ? h->mu_norm : 0.f; hp.mu_sq = p.mu ? h->mu_sq : 0.f; hp.biased = (p.biased || (f16_tile && p.l2)) ? 1 : 0;
         hp.qconst_out = p.biased ? ws_at<float>(h, L.qconst) : nullptr;
         launch_hi_rows(hp, st);
@@ -3418,7 +3448,7 @@ static int knn_scan_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout& L
 // cosine) or -|q - y|^2 (L2) whatever the plane's centring, so the bounds of different shards compare; the other kernels report none
 // (-inf).
 static void knn_report_lower_bounds(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, float* lb_out, hipStream_t st) {
-    if (p.kind == RADAD_SCAN_HI_TILE && p.cert) {
+    if (p.kind == RADAD_SCAN_HI_TILE) {
         KthParams kp;
         kp.score = ws_at<float>(h, L.ps); kp.cnt = ws_at<int>(h, L.cnt); kp.cap = p.emit_cap; kp.k = p.k; kp.eps = ws_at<float>(h, L.eps);
         kp.lb_out = lb_out; kp.ak_out = ws_at<float>(h, L.ak);
@@ -3446,7 +3476,7 @@ static int knn_search_phase1(radad_knn_t h, const void* q_in, int q_dtype, int64
     h->have_last = true;
 
     h->prof.next_search();
-    if (k <= KNN_CERT_MAX_K) knn_consume_reports(h);
+    knn_consume_reports(h);
     const int cslot = (int)(h->search_seq & 1);
 #ifdef RADAD_DEBUG_HOOKS
     if (getenv("RADAD_DEBUG_KNN")) h->hi_skip = 0;     // timing ablations (wrong results, every query rejected): stay on the kernel under test
@@ -3481,10 +3511,10 @@ static int knn_search_phase1(radad_knn_t h, const void* q_in, int q_dtype, int64
 
     ctx->valid = true;
     ctx->nq = nq; ctx->k = k; ctx->l2 = p.l2; ctx->cslot = cslot; ctx->n_parts = p.n_parts; ctx->plen = p.plen; ctx->cap = p.cap; ctx->xgroup = p.xgroup;
-    ctx->cert = p.cert; ctx->emit = hi_tile || p.kind == RADAD_SCAN_F32_DENSE; ctx->use_floor = hi_tile; ctx->hi_tile = hi_tile; ctx->q_use = q_use;
+    ctx->emit = hi_tile || p.kind == RADAD_SCAN_F32_DENSE; ctx->use_floor = hi_tile; ctx->hi_tile = hi_tile; ctx->q_use = q_use;
     ctx->small_lists = p.kind == RADAD_SCAN_HI_SMALLQ || p.kind == RADAD_SCAN_F32_SMALLQ;
     ctx->canonical = hi_tile || p.kind == RADAD_SCAN_HI_SMALLQ || !p.l2;
-    ctx->have_ak = lb_out != nullptr && hi_tile && p.cert;
+    ctx->have_ak = lb_out != nullptr && hi_tile;
     ctx->ws = L;
     h->last_o_cnt = L.cnt; h->last_o_thr = L.thr; h->last_emit_nq = hi_tile ? nq : 0;
     return RADAD_OK;
@@ -3501,8 +3531,8 @@ static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* glo
     RefineParams m;
     m.score = ws_at<const float>(h, c.ws.ps); m.idx = ws_at<const int>(h, c.ws.pi); m.n_parts = c.n_parts; m.k = k; m.dim = h->dim; m.l2 = c.l2; m.nq = nq;
     m.part_len = c.plen; m.cap = c.cap;
-    m.eps = c.cert ? ws_at<const float>(h, c.ws.eps) : nullptr; m.thr_init = c.use_floor ? ws_at<const float>(h, c.ws.thr) : nullptr;
-    m.part_cnt = c.emit ? ws_at<const int>(h, c.ws.cnt) : nullptr; m.global_lb = (c.cert && c.canonical) ? global_lb : nullptr;
+    m.eps = ws_at<const float>(h, c.ws.eps); m.thr_init = c.use_floor ? ws_at<const float>(h, c.ws.thr) : nullptr;
+    m.part_cnt = c.emit ? ws_at<const int>(h, c.ws.cnt) : nullptr; m.global_lb = c.canonical ? global_lb : nullptr;
     m.ak_in = c.have_ak ? ws_at<const float>(h, c.ws.ak) : nullptr;
     m.flag_count = flag_count; m.flag_sel = flag_sel;
     m.db = h->rows; m.db_f16 = h->f16; m.q = c.q_use; m.id_base = h->id_base; m.out_dist = out_dist_dev; m.out_idx = out_idx_dev;
@@ -3510,13 +3540,13 @@ static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* glo
 #ifdef RADAD_DEBUG_HOOKS
     { const char* dbg = getenv("RADAD_DEBUG_KNN"); m.debug = dbg ? atoi(dbg) : 0; }
 #endif
-    m.stats = c.cert ? flag_count + 1 : nullptr;
+    m.stats = flag_count + 1;
     RADAD_REQUIRE(c.n_parts <= RF_THREADS * RF_MAXL, "radad_knn_search: %d partial lists per query exceed the re-rank kernel's %d", c.n_parts,
                   RF_THREADS * RF_MAXL);
-    if (c.cert && c.small_lists && nq <= SQ_NQ && m.n_parts <= RS_MAX_PARTS && m.cap <= KNN_CERT_CAP + KNN_CERT_MAX_K) {
+    if (c.small_lists && nq <= SQ_NQ && m.n_parts <= RS_MAX_PARTS && m.cap <= RS_MAX_CAP) {
         // a small batch: RS_SPLIT workgroups per query (k_refine_small)
         if (!h->rs_key) {                                // (once per handle: allocation and clearing synchronise)
-            const size_t kb = (size_t)SQ_NQ * (KNN_CERT_CAP + KNN_CERT_MAX_K) * sizeof(double);
+            const size_t kb = (size_t)SQ_NQ * RS_MAX_CAP * sizeof(double);
             if (hipMalloc((void**)&h->rs_key, kb) != hipSuccess || hipMalloc((void**)&h->rs_count, SQ_NQ * sizeof(int)) != hipSuccess ||
                 hipMemset(h->rs_count, 0, SQ_NQ * sizeof(int)) != hipSuccess) {
                 (void)hipGetLastError();
@@ -3545,7 +3575,7 @@ static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* glo
     RADAD_HIP_CHECK(hipGetLastError());
 
     // ---- look before the exact pass (see radad_knn_s::verify_next) ---------------------------------------------------------------
-    if (c.cert && c.hi_tile && h->verify_next && nq >= 64 && (double)nq * (double)h->ntotal * (double)h->dim >= 4e11) {
+    if (c.hi_tile && h->verify_next && nq >= 64 && (double)nq * (double)h->ntotal * (double)h->dim >= 4e11) {
         int* rej = h->host_count + 16;
         RADAD_HIP_CHECK(hipMemcpyAsync(rej, flag_count, sizeof(int), hipMemcpyDeviceToHost, st));
         RADAD_HIP_CHECK(hipStreamSynchronize(st));
@@ -3558,16 +3588,19 @@ static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* glo
     }
 
     // ---- the queries the certificate rejected: exact float64 search, sized and driven by the device-side count ------
-    if (c.cert) {
+    {
         ExactParams x;
         x.db = h->rows; x.db_f16 = h->f16; x.q = c.q_use; x.sel = flag_sel; x.count = flag_count;
         x.n = h->ntotal; x.dim = h->dim; x.k = k; x.l2 = c.l2; x.group = c.xgroup;
         x.slice_rows = ceil_div64(std::max<int64_t>(h->ntotal, 1), KX_SLICES);
         x.pkey = ws_at<double>(h, c.ws.xk); x.pidx = ws_at<int>(h, c.ws.xi); x.id_base = h->id_base;
         x.out_dist = out_dist_dev; x.out_idx = out_idx_dev; x.out_key = out_key_dev;
-        x.host_stats = h->host_count_dev + 8 * c.cslot; x.stamp = (int)(h->search_seq & 0x3fffffff) + 1; x.nq_report = (int)std::min<int64_t>(nq, 0x7fffffff);
+        x.stamp = (int)(h->search_seq & 0x3fffffff) + 1;
+        // (a search beyond KNN_F16_MAX_K took no f16 scan: its rejections say nothing about the f16 scans' tuning, which reads
+        // batch sizes of >= 64 only -- knn_consume_reports)
+        x.nq_report = k <= KNN_F16_MAX_K ? (int)std::min<int64_t>(nq, 0x7fffffff) : 0;
         const size_t xlds = (size_t)c.xgroup * h->dim * 4 + (size_t)KX_WAVES * c.xgroup * k * 12 + 16;
-        RADAD_REQUIRE(xlds <= 160 * 1024, "radad_knn_search: dim %d x k %d too large for the exact kernel", h->dim, k);
+        RADAD_REQUIRE(xlds <= KX_LDS_MAX, "radad_knn_search: dim %d x k %d too large for the exact kernel", h->dim, k);
         RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_exact_scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
         if (nq > h->xarrive_cap) {                       // arrival counters of the query groups (zero between launches)
             RADAD_HIP_CHECK(hipStreamSynchronize(st));
@@ -3584,7 +3617,15 @@ static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* glo
             h->xarrive_cap = cap;
         }
         x.arrive = h->xarrive;
-        hipLaunchKernelGGL(k_exact_scan, dim3(KX_SLICES, KX_GROUPS_Y), dim3(KX_THREADS), xlds, st, x);
+        // (k beyond KNN_F16_MAX_K: groups of one or two queries, each a long insert and merge -- more of them in flight; the
+        // geometry of k <= 128 is the measured one)
+        const unsigned gy = k <= KNN_F16_MAX_K ? KX_GROUPS_Y : 8 * KX_GROUPS_Y;
+        x.nslots = (int)knn_exact_slots(nq, k, c.xgroup);
+        for (int64_t s0 = 0; s0 < nq; s0 += x.nslots) {  // (launches past the device-side count leave at once)
+            x.slot0 = (int)s0;
+            x.host_stats = s0 == 0 ? h->host_count_dev + 8 * c.cslot : nullptr;
+            hipLaunchKernelGGL(k_exact_scan, dim3(KX_SLICES, gy), dim3(KX_THREADS), xlds, st, x);
+        }
         RADAD_HIP_CHECK(hipGetLastError());
         h->count_nq[c.cslot] = nq;                                     // (k_exact_scan writes the counters and its stamp to the pinned host copy)
         ++h->search_seq;
