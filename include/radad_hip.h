@@ -454,6 +454,9 @@ int radad_group_mean(const float* in_dev, const int64_t* group_offsets_host, int
  * w54t / b54 hold the inference-time fold  W5 (W4 h + b4) + b5 = (W5 W4) h + (W5 b4 + b5): build them once
  * per set of weights with radad_projection_fold and keep them; when NULL the forward re-folds into its
  * workspace on every call (correct, slower).
+ * Any dim >= 1 and any alignment of the pointers (4-byte float alignment) are accepted. Limits, each one
+ * RADAD_EINVAL: hidden <= 4096; batch * k < 2^31 - 128; the per-row tail keeps
+ * 4 * (2*k*hidden + 2*hidden + k + 8) bytes in LDS, at most 160 KB (k = 5: hidden <= 3412; k = 16: hidden <= 1204).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct radad_proj_weights {
     const float *w1, *b1;       /* attention_score   [H, D], [H]   */
@@ -474,7 +477,10 @@ int radad_projection_fold(const radad_proj_weights* w, int dim, int hidden, floa
                           int device, void* stream);
 
 /* out[r, :] = act(W x[r, :] + bias)   nn.Linear forward, W [out_features, in_features] with row stride ldw;
- * act 0 none / 1 tanh / 2 relu.  Split-K MFMA GEMM (few rows x wide in_features still fills the chip). */
+ * act 0 none / 1 tanh / 2 relu; bias_dev may be NULL.  Split-K MFMA GEMM (few rows x wide in_features still fills
+ * the chip).  Any in_features, any strides with ldx, ldw >= in_features and ldo >= out_features, any 4-byte-aligned
+ * pointers (16-byte-aligned pointers with in_features, ldx, ldw multiples of 4 take the vector-load path);
+ * rows < 2^31 - 128.  Anything else is RADAD_EINVAL. */
 int radad_linear_forward(const float* x_dev, int64_t ldx, const float* w_dev, int64_t ldw, const float* bias_dev,
                          int act, int64_t rows, int out_features, int in_features, float* out_dev, int64_t ldo,
                          float* workspace_dev, int64_t workspace_bytes, int device, void* stream);
@@ -486,7 +492,10 @@ int64_t radad_linear_workspace_bytes(int64_t rows, int out_features, int in_feat
  *   logits = DetectionModel(fused)                       (:40; detection_model.py:41-72 in eval mode:
  *            per hidden layer Linear -> BatchNorm1d (running stats, given as scale/shift) -> ReLU;
  *            dropout = identity; last layer Linear only)
- * n_layers == 0 stops after the fuse Linear.  Either output pointer may be NULL when not wanted.
+ * n_layers == 0 stops after the fuse Linear.  fused_out_dev may be NULL when n_layers > 0; logits_out_dev is
+ * required when n_layers > 0 and unused when n_layers == 0 (then fused_out_dev is the output and required).
+ * Any dim and proj_dim >= 1 are accepted. Limits, each one RADAD_EINVAL: 0 <= n_layers <= RADAD_HEAD_MAX_LAYERS
+ * (5 hidden layers + the output layer); no width (proj_dim or any dims[i]) above 8192; batch < 2^31 - 128.
  * ---------------------------------------------------------------------------------------------- */
 #define RADAD_HEAD_MAX_LAYERS 6
 typedef struct radad_head_weights {

@@ -399,3 +399,127 @@ def radad_model_forward(neighbor_vecs, tpp_vecs, p, bn_eps=1e-5):
                 h = h * f(p[f"detection_model.model.{b}.weight"]) + f(p[f"detection_model.model.{b}.bias"])
             h = np.maximum(h, 0.0)
     return proj, fused, (h[:, 0] if h.shape[1] == 1 else h)                                         # squeeze(-1) :125
+
+
+def attention_weights(x, p):
+    """ProjectionLayer.get_attention_weights (projection.py:125-130): softmax_K(W2 tanh(W1 x + b1) + b2) -> [B,K,1]; float64."""
+    f = lambda a: np.asarray(a, np.float64)
+    s = np.tanh(f(x) @ f(p["attention_score.weight"]).T + f(p["attention_score.bias"])) @ f(p["attention_final.weight"]).T \
+        + f(p["attention_final.bias"])
+    e = np.exp(s - s.max(axis=1, keepdims=True))
+    return e / e.sum(axis=1, keepdims=True)
+
+
+# ------------------------------------------------------------------------------------------------
+# a8 error model: the float64 value together with an error scale for ANY float32 evaluation of the same arithmetic (unit
+# roundoff u = 2^-24), in the probabilistic model of rounding errors (Higham & Mary, SIAM J. Sci. Comput. 41(5), 2019): a dot
+# product over n terms carries about sqrt(n) u sum|terms| of rounding error (the worst case n u sum|terms| compounds into
+# nonsense over five stages), whatever the summation order or K-split; an error already in the inputs of a Linear layer is
+# taken as independent per input and propagates in quadrature, sqrt(e^2 W^2); tanh / exp / sqrt / division add a few u of
+# their value; the softmax and the LayerNorm pass their inputs' errors on through their first derivatives.  Tests compare a
+# float32 kernel's output with `value` at a small multiple of that scale.
+# ------------------------------------------------------------------------------------------------
+U32 = 2.0 ** -24
+
+
+def _lin_err(x, ex, w, b):
+    """y = x W^T + b with x carrying error ex: (y, error scale, sum|terms|)."""
+    f = lambda a: np.asarray(a, np.float64)
+    w = f(w)
+    ab = np.abs(f(b)) if b is not None else 0.0
+    y = f(x) @ w.T + (f(b) if b is not None else 0.0)
+    mag = np.abs(f(x)) @ np.abs(w).T + ab
+    e = np.sqrt(w.shape[1] + 1) * U32 * mag
+    if np.ndim(ex):
+        e = e + np.sqrt((ex * ex) @ (w * w).T)
+    return y, e, mag
+
+
+def linear_forward_err(x, w, b, act=0):
+    """radad_linear_forward: act(x W^T + b), act 0 none / 1 tanh / 2 relu.  (value, error scale)."""
+    y, e, _ = _lin_err(x, 0.0, w, b)
+    if act == 1:
+        y = np.tanh(y)
+        e = e + 2 * U32 * np.abs(y)
+    elif act == 2:
+        e = np.where(y > 0, e, np.maximum(y + e, 0.0))
+        y = np.maximum(y, 0.0)
+    return y, e
+
+
+def _softmax_err(s, es, axis=1):
+    """softmax along `axis` of s (error es): da_k = a_k (ds_k - sum_j a_j ds_j), plus the rounding of s - max, exp and the
+    normalisation."""
+    d = s - s.max(axis=axis, keepdims=True)
+    a = np.exp(d) / np.exp(d).sum(axis=axis, keepdims=True)
+    K = s.shape[axis]
+    spread = es + U32 * np.abs(d)
+    return a, a * (spread + (a * spread).sum(axis=axis, keepdims=True) + (K + 4) * U32)
+
+
+def attention_weights_err(x, p):
+    """get_attention_weights as two radad_linear_forward calls and a float32 softmax: (value [B,K,1], error scale)."""
+    B, K, D = np.shape(x)
+    t, et = linear_forward_err(np.reshape(x, (B * K, D)), p["attention_score.weight"], p["attention_score.bias"], 1)
+    s, es, _ = _lin_err(t, et, p["attention_final.weight"], p["attention_final.bias"])
+    return _softmax_err(s.reshape(B, K, 1), es.reshape(B, K, 1))
+
+
+def projection_forward_err(x, p):
+    """projection_forward with its float32 error scale: (value [B,O], error [B,O]).  The W5 W4 product is taken as the
+    float32-rounded fold the HIP forward keeps (one more u on each of its terms)."""
+    f = lambda a: np.asarray(a, np.float64)
+    x = f(x)
+    B, K, D = x.shape
+    t, et = linear_forward_err(x, p["attention_score.weight"], p["attention_score.bias"], 1)            # [B,K,H]
+    s, es, _ = _lin_err(t, et, p["attention_final.weight"], p["attention_final.bias"])                  # [B,K,1]
+    c, ec = linear_forward_err(x, p["cst_hidden.weight"], p["cst_hidden.bias"], 2)                      # [B,K,H]
+    a, ea = _softmax_err(s, es)
+    hb = (a * c).sum(axis=1)                                                                            # [B,H]
+    ehb = (ea * np.abs(c) + a * ec).sum(axis=1) + (K + 3) * U32 * (a * np.abs(c)).sum(axis=1)
+    w5, w4 = f(p["weight_sum.weight"]), f(p["cst_output.weight"])
+    w54 = w5 @ w4                                                                                       # [H,H]
+    b54 = w5 @ f(p["cst_output.bias"]) + f(p["weight_sum.bias"])
+    y, ey, ymag = _lin_err(hb, ehb, w54, b54)
+    ey = ey + U32 * ymag                                                                                # the fold's rounding
+    H = y.shape[1]
+    mu = y.mean(axis=1, keepdims=True)
+    d = y - mu
+    var = (d * d).mean(axis=1, keepdims=True)
+    sig = np.sqrt(var + 1e-6)
+    zh = d / sig
+    g, beta = f(p["normalization.weight"]), f(p["normalization.bias"])
+    z = zh * g + beta
+    # propagated: dz_j = g_j / sig (dy_j - mean dy - zh_j mean(zh dy)), the two means in quadrature
+    rms = lambda v: np.sqrt((v * v).sum(axis=1, keepdims=True)) / H
+    ez = np.abs(g) / sig * (ey + rms(ey) + np.abs(zh) * rms(zh * ey))
+    # rounding inside the LayerNorm: the mean, the centred values, the variance, 1/sqrt
+    emu = np.sqrt(H + 1) * U32 * np.abs(y).mean(axis=1, keepdims=True)
+    ed = U32 * np.abs(d) + emu
+    evar = np.sqrt(H + 1) * U32 * var + 2 * (np.abs(d) * ed).mean(axis=1, keepdims=True)
+    erel = 0.5 * evar / (var + 1e-6) + 3 * U32
+    ez = ez + np.abs(g) * (ed / sig + np.abs(zh) * erel) + 3 * U32 * (np.abs(zh * g) + np.abs(beta))
+    out, eout, _ = _lin_err(z, ez, p["unified_embedding.weight"], p["unified_embedding.bias"])
+    return out, eout
+
+
+def head_forward_err(tpp_vecs, proj, p, bn_eps=1e-5):
+    """radad_model.py:39-40 given the projection output (fuse Linear, then the detection MLP in eval form), each with its
+    float32 error scale: (fused, fused_err, logits [B, out], logits_err).  The BatchNorm scale / shift are formed in float32."""
+    f = lambda a: np.asarray(a, np.float64)
+    fused, ef, _ = _lin_err(np.concatenate([f(tpp_vecs), f(proj)], axis=1), 0.0, p["fuse.weight"], p["fuse.bias"])
+    idx = sorted({int(k.split(".")[2]) for k in p if k.startswith("detection_model.model.")})
+    lin = [i for i in idx if np.ndim(p[f"detection_model.model.{i}.weight"]) == 2]
+    h, eh = fused, ef
+    for n, i in enumerate(lin):
+        h, eh, _ = _lin_err(h, eh, p[f"detection_model.model.{i}.weight"], p[f"detection_model.model.{i}.bias"])
+        if n + 1 < len(lin):
+            b = i + 1
+            if f"detection_model.model.{b}.running_mean" in p:
+                scale = f(p[f"detection_model.model.{b}.weight"]) / np.sqrt(f(p[f"detection_model.model.{b}.running_var"]) + bn_eps)
+                mean, beta = f(p[f"detection_model.model.{b}.running_mean"]), f(p[f"detection_model.model.{b}.bias"])
+                eh = np.abs(scale) * eh + 6 * U32 * (np.abs(h * scale) + np.abs(beta) + np.abs(mean * scale))
+                h = (h - mean) * scale + beta
+            eh = np.where(h > 0, eh, np.maximum(h + eh, 0.0))
+            h = np.maximum(h, 0.0)
+    return fused, ef, h, eh

@@ -34,7 +34,10 @@ struct GemmParams {
     int M, N, K, chunks_per_split;
 };
 
-// part[z] = A[:, Kz] W[:, Kz]^T for the K range of split z
+// part[z] = A[:, Kz] W[:, Kz]^T for the K range of split z.  VEC: one f32x4 load per row and chunk column group, legal when K,
+// lda and ldw are multiples of 4 and every base pointer is 16-byte aligned (the host checks); otherwise four dword loads, each
+// bounded by K on its own (a K tail inside a column group, odd row strides, a view that starts mid-row).
+template <bool VEC>
 __global__ __launch_bounds__(G_THREADS, 2) void k_gemm_nt_splitk(GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* sA = reinterpret_cast<float*>(smem);   // [2][GT][GLD]
@@ -69,8 +72,17 @@ __global__ __launch_bounds__(G_THREADS, 2) void k_gemm_nt_splitk(GemmParams p) {
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            ra[i] = (kin && arow[i]) ? *reinterpret_cast<const f32x4*>(arow[i] + kcol) : z;
-            rb[i] = (kin && wrow[i]) ? *reinterpret_cast<const f32x4*>(wrow[i] + kcol) : z;
+            if constexpr (VEC) {
+                ra[i] = (kin && arow[i]) ? *reinterpret_cast<const f32x4*>(arow[i] + kcol) : z;
+                rb[i] = (kin && wrow[i]) ? *reinterpret_cast<const f32x4*>(wrow[i] + kcol) : z;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool in = kcol + j < p.K;
+                    ra[i][j] = (in && arow[i]) ? arow[i][kcol + j] : 0.f;
+                    rb[i][j] = (in && wrow[i]) ? wrow[i][kcol + j] : 0.f;
+                }
+            }
         }
     };
     auto swrite = [&](int buf) {
@@ -322,12 +334,15 @@ int gemm_nt_splitk(const float* a, int64_t lda, const float* w, const float* w_h
     int S, cps;
     split_plan(M, N, K, &S, &cps);
     GemmParams p{a, lda, w, w_hi, n_lo, ldw, part, (int)M, N, K, cps};
+    auto a16 = [](const float* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    const bool vec = K % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0 && a16(a) && a16(w) && a16(w_hi);
+    const auto kern = vec ? k_gemm_nt_splitk<true> : k_gemm_nt_splitk<false>;
     constexpr size_t lds = sizeof(float) * 4 * GT * GLD;   // 73 728 B > the 64 KB default: raise the limit
-    const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_nt_splitk),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                (int)lds);
     RADAD_HIP_CHECK(attr);
-    hipLaunchKernelGGL(k_gemm_nt_splitk, dim3((unsigned)ceil_div64(M, GT), (unsigned)ceil_div64(N, GT), (unsigned)S),
-                       dim3(G_THREADS), lds, st, p);
+    hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div64(M, GT), (unsigned)ceil_div64(N, GT), (unsigned)S), dim3(G_THREADS), lds, st,
+                       p);
     RADAD_HIP_CHECK(hipGetLastError());
     *splits_out = S;
     return RADAD_OK;
@@ -363,7 +378,8 @@ int64_t radad_projection_workspace_bytes(int64_t batch, int k, int dim, int hidd
 
 int radad_projection_fold(const radad_proj_weights* w, int dim, int hidden, float* w54t_out_dev, float* b54_out_dev, int device,
                           void* stream) {
-    RADAD_REQUIRE(w && dim > 0 && hidden > 0 && hidden <= 4096, "radad_projection_fold: bad shape");
+    RADAD_REQUIRE(w && dim > 0 && hidden > 0, "radad_projection_fold: bad shape");
+    RADAD_REQUIRE(hidden <= 4096, "radad_projection_fold: hidden %d above 4096", hidden);
     RADAD_REQUIRE(w->w4 && w->b4 && w->w5 && w->b5 && w54t_out_dev && b54_out_dev, "radad_projection_fold: NULL buffer");
     DeviceGuard g(device);
     hipLaunchKernelGGL(k_fold_w54, dim3((unsigned)ceil_div64((int64_t)hidden * hidden, 256)), dim3(256), 0, (hipStream_t)stream,
@@ -376,8 +392,8 @@ int radad_projection_forward(const radad_proj_weights* w, const float* x_dev, in
                              int out_dim, float* out_dev, float* workspace_dev, int64_t workspace_bytes, int device,
                              void* stream) {
     RADAD_REQUIRE(w && batch >= 0 && k >= 1 && dim > 0 && hidden > 0 && out_dim > 0, "radad_projection_forward: bad shape");
-    RADAD_REQUIRE(dim % 4 == 0, "radad_projection_forward: dim must be a multiple of 4");
-    RADAD_REQUIRE(batch * (int64_t)k < (1ll << 31) - GT && hidden <= 4096, "radad_projection_forward: batch*k or hidden too large");
+    RADAD_REQUIRE(hidden <= 4096, "radad_projection_forward: hidden %d above 4096", hidden);
+    RADAD_REQUIRE(batch * (int64_t)k < (1ll << 31) - GT, "radad_projection_forward: batch*k too large");
     if (batch == 0) return RADAD_OK;
     RADAD_REQUIRE(x_dev && out_dev && workspace_dev, "radad_projection_forward: NULL buffer");
     RADAD_REQUIRE(workspace_bytes >= radad_projection_workspace_bytes(batch, k, dim, hidden, out_dim),
@@ -417,9 +433,8 @@ int radad_linear_forward(const float* x_dev, int64_t ldx, const float* w_dev, in
                          int64_t workspace_bytes, int device, void* stream) {
     RADAD_REQUIRE(rows >= 0 && out_features > 0 && in_features > 0 && rows < (1ll << 31) - GT, "radad_linear_forward: bad shape");
     RADAD_REQUIRE(act >= ACT_NONE && act <= ACT_RELU, "radad_linear_forward: act must be 0 (none), 1 (tanh) or 2 (relu)");
-    RADAD_REQUIRE(in_features % 4 == 0 && ldx % 4 == 0 && ldw % 4 == 0 && ldx >= in_features && ldw >= in_features &&
-                      ldo >= out_features,
-                  "radad_linear_forward: in_features / row strides must be multiples of 4 and cover the row");
+    RADAD_REQUIRE(ldx >= in_features && ldw >= in_features && ldo >= out_features,
+                  "radad_linear_forward: row strides ldx / ldw must cover in_features and ldo out_features");
     if (rows == 0) return RADAD_OK;
     RADAD_REQUIRE(x_dev && w_dev && out_dev && workspace_dev, "radad_linear_forward: NULL buffer");
     RADAD_REQUIRE(workspace_bytes >= radad_linear_workspace_bytes(rows, out_features, in_features),
@@ -445,7 +460,6 @@ int radad_fuse_head_forward(const radad_head_weights* w, const float* tpp_dev, c
                             int proj_dim, float* fused_out_dev, float* logits_out_dev, float* workspace_dev,
                             int64_t workspace_bytes, int device, void* stream) {
     RADAD_REQUIRE(w && batch >= 0 && dim > 0 && proj_dim > 0 && batch < (1ll << 31) - GT, "radad_fuse_head_forward: bad shape");
-    RADAD_REQUIRE(dim % 4 == 0 && proj_dim % 4 == 0, "radad_fuse_head_forward: dim and proj_dim must be multiples of 4");
     RADAD_REQUIRE(w->n_layers >= 0 && w->n_layers <= HEAD_MAX_LAYERS, "radad_fuse_head_forward: too many head layers");
     RADAD_REQUIRE(w->n_layers == 0 || w->dims[0] == proj_dim, "radad_fuse_head_forward: head input width != proj_dim");
     if (batch == 0) return RADAD_OK;

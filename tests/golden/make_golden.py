@@ -4,7 +4,8 @@ methods and vector_database.py's shell around the faiss index) and the HuggingFa
 reference's extractors call (default constructors, no from_pretrained / no network).
 
 Run here (the container that has /root/reference); the GPU box never sees the reference:
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py            (every file except projection_shapes.npz)
+    python tests/golden/make_golden.py --shapes   (projection_shapes.npz only)
 Only DATA is written (inputs by seed or by value, outputs by value) -- no reference source.
 
 The reference's config.py imports torchaudio / faiss / librosa at module top (config.py:3,14,16) although the
@@ -359,5 +360,66 @@ def pipeline_fixture(ref_config, ref_segmenter, ref_pooling):
     np.savez_compressed(os.path.join(OUT, "pipeline.npz"), **g)
 
 
+# ---- a8 at shapes other than the defaults: projection_shapes.npz (`python tests/golden/make_golden.py --shapes`) ---------------
+# Widths that are not multiples of 4, hidden sizes that straddle a 128-row tile, K = 1 and 15, an output width of 1 and 130, a
+# detection head with no hidden layer, one with three odd-sized hidden layers, one without BatchNorm, and BatchNorm running
+# statistics far from the identity.  Weights are regenerated from the seed with oracle.synth.fill_state_dict; the BatchNorm
+# running statistics that replace the filled ones, the inputs and the reference's outputs are stored.
+SHAPE_CASES = (
+    # name, kind, D, H, O, K, B, detection_hidden_dims, use_batch_norm, seed
+    ("p_h100", "proj", 90, 100, 1, 1, 3, None, None, 6100),
+    ("p_h300", "proj", 45, 300, 130, 15, 2, None, None, 6200),
+    ("m_nohidden", "model", 90, 100, 130, 15, 3, [], True, 6400),
+    ("m_deep", "model", 210, 300, 130, 1, 4, [300, 7, 33], True, 6500),
+    ("m_nobn", "model", 30, 100, 1, 5, 3, [64, 32], False, 6600),
+)
+
+
+def main_shapes():
+    import torch
+    ref_config, _, _, ref_projection, ref_radad = import_reference()
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+    from oracle import synth
+    g = {"cases": np.asarray([c[0] for c in SHAPE_CASES])}
+    for name, kind, D, H, O, K, B, dims, bn, seed in SHAPE_CASES:
+        cfg = ref_config.Config()
+        cfg.device = torch.device("cpu")
+        cfg.projection_hidden_dim, cfg.projection_output_dim, cfg.top_k = H, O, K
+        if kind == "model":
+            cfg.detection_hidden_dims, cfg.use_batch_norm = list(dims), bn
+            mod = ref_radad.RADADModel(cfg, D).eval()
+        else:
+            mod = ref_projection.ProjectionLayer(cfg, D).eval()
+        sd = synth.fill_state_dict({k: tuple(v.shape) for k, v in mod.state_dict().items()}, seed)
+        rng = np.random.default_rng(seed)
+        for k in list(sd):
+            if k.endswith("running_mean"):          # far from the identity: mean ~ N(0, 1), var log-uniform over [1e-4, 1e2]
+                sd[k] = rng.standard_normal(sd[k].shape).astype(np.float32)
+                g[f"{name}_bn_{k}"] = sd[k]
+            elif k.endswith("running_var"):
+                sd[k] = (10.0 ** rng.uniform(-4, 2, sd[k].shape)).astype(np.float32)
+                g[f"{name}_bn_{k}"] = sd[k]
+        mod.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+        x = torch.from_numpy(synth.rows(0, B * K, D, seed + 99).reshape(B, K, D))
+        g[f"{name}_seed"], g[f"{name}_dims"] = np.asarray(seed), np.asarray([D, H, O, K, B])
+        g[f"{name}_names"] = np.asarray(list(sd.keys()))
+        g[f"{name}_shapes"] = np.asarray([",".join(map(str, v.shape)) for v in sd.values()])
+        g[f"{name}_x"] = x.numpy()
+        with torch.no_grad():
+            if kind == "model":
+                t = torch.from_numpy(synth.rows(0, B, D, seed + 98))
+                proj = mod.projection_layer(x)
+                g[f"{name}_t"], g[f"{name}_proj"] = t.numpy(), proj.numpy()
+                g[f"{name}_fused"] = mod.fuse(torch.cat([t, proj], dim=1)).numpy()
+                g[f"{name}_logits"] = np.atleast_1d(mod(x, t).numpy())
+            else:
+                g[f"{name}_y"] = mod(x).numpy()
+                g[f"{name}_attn"] = mod.get_attention_weights(x).numpy()
+    np.savez_compressed(os.path.join(OUT, "projection_shapes.npz"), **g)
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--shapes"]:
+        main_shapes()
+    else:
+        main()

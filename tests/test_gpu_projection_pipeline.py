@@ -146,8 +146,10 @@ def test_radad_model_matches_reference_golden(gpu, golden_dir):
 
 
 @pytest.mark.parametrize("rows,n_out,n_in,act", [(1, 256, 5376, 0), (37, 100, 516, 1), (300, 130, 64, 2), (0, 8, 8, 0)])
-def test_linear_forward_split_k(gpu, rows, n_out, n_in, act):
-    """radad_linear_forward = nn.Linear (+ tanh / relu) for shapes from one row x wide K (many K-splits) to ragged."""
+def test_linear_forward_split_k_any_width(gpu, rows, n_out, n_in, act):
+    """radad_linear_forward = nn.Linear (+ tanh / relu) for shapes from one row x wide K (many K-splits) to ragged; the same
+    buffers at in_features = n_in - 1 (not a multiple of 4) give nn.Linear's answer too, and a row stride shorter than the
+    row is refused."""
     import torch
     from radad_retrievalaugmenteddeepfakeaudiodetection_amd import _lib
     lib = _lib.load()
@@ -164,8 +166,15 @@ def test_linear_forward_split_k(gpu, rows, n_out, n_in, act):
     want = x.astype(np.float64) @ w.astype(np.float64).T + b
     want = np.tanh(want) if act == 1 else (np.maximum(want, 0) if act == 2 else want)
     np.testing.assert_allclose(out.cpu().numpy(), want, rtol=0, atol=1e-4)
-    with pytest.raises(ValueError, match="multiples of 4"):
-        _lib.check(lib.radad_linear_forward(xd.data_ptr(), n_in, wd.data_ptr(), n_in, bd.data_ptr(), act, 1, n_out, n_in - 1,
+    # in_features = n_in - 1 (not a multiple of 4) over the same buffers, rows strided by n_in: the dword-load path
+    out.fill_(7.0)
+    _lib.check(lib.radad_linear_forward(xd.data_ptr(), n_in, wd.data_ptr(), n_in, bd.data_ptr(), act, rows, n_out, n_in - 1,
+                                        out.data_ptr(), n_out, ws.data_ptr(), int(ws.numel()), xd.device.index,
+                                        _lib.stream_ptr(xd.device)), "radad_linear_forward")
+    want, err = O.linear_forward_err(x[:, :n_in - 1], w[:, :n_in - 1], b, act)
+    np.testing.assert_array_less(np.abs(out.cpu().numpy() - want), 3 * err + 1e-30)
+    with pytest.raises(ValueError, match="row strides"):       # a row stride shorter than the row is still refused
+        _lib.check(lib.radad_linear_forward(xd.data_ptr(), n_in - 2, wd.data_ptr(), n_in, bd.data_ptr(), act, 1, n_out, n_in - 1,
                                             out.data_ptr(), n_out, ws.data_ptr(), int(ws.numel()), xd.device.index,
                                             _lib.stream_ptr(xd.device)), "radad_linear_forward")
 

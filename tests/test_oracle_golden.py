@@ -110,6 +110,46 @@ def test_radad_shell_projection_and_fuse(golden_dir):
     np.testing.assert_allclose(fused, g["radad_fused"], rtol=0, atol=5e-5)
 
 
+def _shape_case(g, name):
+    """(state_dict, dims) of one projection_shapes.npz case: weights from the seed, BatchNorm running stats as stored."""
+    names = [str(n) for n in g[f"{name}_names"]]
+    shapes = {n: tuple(int(v) for v in str(s).split(",") if v) for n, s in zip(names, g[f"{name}_shapes"])}
+    sd = synth.fill_state_dict(shapes, int(g[f"{name}_seed"]))
+    for k in sd:
+        if f"{name}_bn_{k}" in g:
+            sd[k] = g[f"{name}_bn_{k}"]
+    return sd, [int(v) for v in g[f"{name}_dims"]]
+
+
+@pytest.mark.parametrize("name", ["p_h100", "p_h300", "m_nohidden", "m_deep", "m_nobn"])
+def test_projection_and_head_match_reference_at_other_shapes(golden_dir, name):
+    """The reference's ProjectionLayer / RADADModel at non-default shapes (hidden 100 / 300, output 1 / 130, K 1 / 5 / 15,
+    widths not multiples of 4, heads with 0 / 3 hidden layers or no BatchNorm, running stats far from the identity) against
+    the float64 oracle, and the reference's float32 outputs inside the oracle's float32 error bound."""
+    g = np.load(os.path.join(golden_dir, "projection_shapes.npz"))
+    sd, (D, H, Oo, K, B) = _shape_case(g, name)
+    x = g[f"{name}_x"]
+    assert x.shape == (B, K, D) and D % 4 != 0
+    close = dict(rtol=1e-6, atol=1e-6)
+    if name.startswith("p_"):
+        assert sd["attention_score.weight"].shape == (H, D) and sd["unified_embedding.weight"].shape == (Oo, H)
+        y = O.projection_forward(x, sd)
+        np.testing.assert_allclose(y, g[f"{name}_y"], **close)
+        np.testing.assert_allclose(O.attention_weights(x, sd), g[f"{name}_attn"], **close)
+        y2, ey = O.projection_forward_err(x, sd)
+        a2, ea = O.attention_weights_err(x, sd)
+        np.testing.assert_allclose(y2, y, rtol=1e-12, atol=1e-12)
+        assert (np.abs(g[f"{name}_y"] - y2) <= ey).all() and (np.abs(g[f"{name}_attn"] - a2) <= ea).all()
+        return
+    t = g[f"{name}_t"]
+    proj, fused, logits = O.radad_model_forward(x, t, sd)
+    np.testing.assert_allclose(proj, g[f"{name}_proj"], **close)
+    np.testing.assert_allclose(fused, g[f"{name}_fused"], **close)
+    np.testing.assert_allclose(logits, g[f"{name}_logits"], **close)
+    f2, ef, l2, el = O.head_forward_err(t, g[f"{name}_proj"], sd)      # the head alone, from the reference's own projection
+    assert (np.abs(g[f"{name}_fused"] - f2) <= ef).all() and (np.abs(g[f"{name}_logits"] - l2[:, 0]) <= el[:, 0]).all()
+
+
 @pytest.fixture(scope="module")
 def g_fe(golden_dir):
     return np.load(os.path.join(golden_dir, "frontend.npz"))
