@@ -281,19 +281,23 @@ int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int n
  * search could return AND the ones its probing would have missed -- a superset of faiss.IndexIVFFlat's answer (which holds only rows
  * of the nprobe lists, vector_database.py:174-179), at the flat scan's cost, nprobe ignored.  0: the nprobe lists were scanned. */
 int radad_ivf_last_search_exact(radad_ivf_t h, int* exact_out);
-/* which list scan answered the most recent radad_ivf_search, and how many of its queries the f16 scan's certificate handed to the fp32
- * pass (synchronises with that search):
- *   RADAD_IVF_SCAN_F32         fp32 rows, v_mfma_f32_16x16x4_f32, k + 6 candidates per (query, list) re-ranked in float64 (dim % 64 != 0,
- *                              no f16 plane, more probed lists than the re-rank stages, RADAD_IVF_OPT_HI_SCAN 0)
- *   RADAD_IVF_SCAN_HI          the flat store's f16 plane gathered list-major, certified per query as the flat scan is; rejected queries
- *                              are answered by the fp32 list scan in the same call
+/* which list scan answered the most recent radad_ivf_search, and how many of its queries that scan's certificate rejected
+ * (synchronises with that search).  Either scan is a FILTER: the float64 re-rank certifies per query that no row of the probed lists
+ * it did not see can reach the k-th, and the queries it cannot certify are answered in the same call by the exact float64 scan of
+ * their probed lists -- every result is the float64 brute force over the probed lists.
+ *   RADAD_IVF_SCAN_F32         fp32 rows, v_mfma_f32_16x16x4_f32, k + 6 candidates per (query, list); float64 re-rank of everything within
+ *                              2 eps of the k-th best fp32 score, eps = (dim + 16) 2^-23 (2 |q||y|max + |y|max^2) over the probed lists
+ *                              (dim % 64 != 0, no f16 plane, RADAD_IVF_OPT_HI_SCAN 0)
+ *   RADAD_IVF_SCAN_HI          the flat store's f16 plane gathered list-major, certified per query as the flat scan is
  *   RADAD_IVF_SCAN_EXACT_FLAT  k > 26: the exact scan of the flat store (radad_ivf_last_search_exact) */
 #define RADAD_IVF_SCAN_F32 0
 #define RADAD_IVF_SCAN_HI 1
 #define RADAD_IVF_SCAN_EXACT_FLAT 2
 int radad_ivf_last_search_info(radad_ivf_t h, int* kind_out, int* rejected_out);
+/* the same count, and how many queries of the most recent search the exact float64 list scan answered (all the rejected ones) */
+int radad_ivf_last_search_counts(radad_ivf_t h, int* rejected_out, int* exact_out);
 /* RADAD_IVF_OPT_HI_SCAN 1 (default) / 0: list scans over the f16 plane / over the fp32 rows (A/B measurements; same results);
- * 2 (tests): the f16 scan runs and every query is then treated as rejected by its certificate, i.e. answered by the fp32 pass */
+ * 2 (tests): the f16 scan runs and every query is then treated as rejected by its certificate, i.e. answered by the exact list scan */
 #define RADAD_IVF_OPT_HI_SCAN 0
 int radad_ivf_set_option(radad_ivf_t h, int option, int value);
 int radad_ivf_reconstruct(radad_ivf_t h, const int64_t* idx_dev, int64_t n, float* out_dev, void* stream);

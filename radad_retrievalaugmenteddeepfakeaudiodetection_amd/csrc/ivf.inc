@@ -12,7 +12,12 @@
 //      HBM-bound: a batch that touches every list reads the store once
 //   4. k_merge_refine over the nprobe lists of each query (float64 re-score, (distance, id) order, id map back to
 //      insertion ids)
-// The result equals an exact search restricted to the union of the probed lists.
+// The result equals an exact search restricted to the union of the probed lists.  That rests on three things: both list scans are
+// FILTERS whose error is bounded per query (eps); k_merge_refine re-scores in float64 everything within 2 eps of the k-th best score
+// and certifies the query only when no row the scan did not list can lie in that band; and the queries it cannot certify are
+// answered by k_ivf_exact, a float64 scan of their probed lists.  (Until the adversarial tests of tests/test_gpu_ivf_adversarial.py the
+// fp32 scan's k + 6 entries per list were merged and re-ranked unchecked: wrong ids wherever more than six rows of a list lie within
+// the fp32 error of the k-th.)
 //
 // Round 4 (k <= 26, dim % 64 == 0): the list scan reads the f16 PLANE of the flat store, gathered list-major (half the bytes, 16x the
 // MFMA rate of v_mfma_f32_16x16x4_f32), behind the flat scan's certificate restricted to the probed lists:
@@ -25,8 +30,8 @@
 //   4. k_merge_refine<true> over the nprobe lists of each query with eps(q) of the plane (k_hi_rows): float64 re-score of
 //      everything within 2 eps of the k-th, certificate per query (a list whose k + 6 entries are all within the threshold may
 //      hide more: rejected)
-//   5. rejected queries only: the fp32 list scan (k_ivf_scan) + legacy merge as until round 3 -- both launched always, their
-//      workgroups leave at once when the query's verdict is "certified"
+//   5. rejected queries only: k_ivf_exact -- launched always, its workgroups leave at once when nobody was rejected
+// Without a plane (dim % 64 != 0, RADAD_IVF_OPT_HI_SCAN 0): k_ivf_f32_eps, k_ivf_scan, k_merge_refine<false> with that eps, k_ivf_exact.
 namespace {
 
 struct IvfScanParams {
@@ -43,8 +48,6 @@ struct IvfScanParams {
     int dim = 0, k = 0, qcap = 0;       // qcap: query rows that fit in LDS (16 unless dim is very large)
     float* part_score = nullptr;        // [nq * nprobe, k]
     int* part_idx = nullptr;            // [nq * nprobe, k]  positions in lrows
-    const int* only_flagged = nullptr;  // optional [nq]: a task none of whose queries is flagged leaves at once (the pass behind the f16 scan)
-    const int* flagged_count = nullptr; // with only_flagged: [1] how many queries are flagged
 };
 static_assert(std::is_trivially_copyable_v<IvfScanParams>, "kernel argument");
 
@@ -114,11 +117,6 @@ __device__ __forceinline__ void ivf_scan_task(const IvfScanParams& p, const int 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r16 = lane & 15, g = lane >> 4;
     const int list = p.task_list[task], pbeg = p.task_pbeg[task], cnt = p.task_cnt[task];
-    if (p.only_flagged) {
-        int any = 0;
-        for (int i = tid; i < cnt; i += SQ_THREADS) any |= p.only_flagged[p.pair_q[pbeg + i]];
-        if (!__syncthreads_or(any)) return;
-    }
     for (int i = tid; i < p.qcap * (p.dim >> 2); i += SQ_THREADS) {
         const int qq = i / (p.dim >> 2), c4 = i % (p.dim >> 2);
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -217,22 +215,11 @@ __device__ __forceinline__ void ivf_scan_task(const IvfScanParams& p, const int 
     }
 }
 
-// One workgroup per task -- or, behind the f16 scan (only_flagged), a small grid whose workgroups walk the task table when the
-// certificate rejected anybody at all and leave at once when it did not (the usual case: 6 000 workgroups that only looked at their
-// queries' flags cost 12 us).
+// One workgroup per task.
 template <int KSEL>
 __global__ __launch_bounds__(SQ_THREADS, 2) void k_ivf_scan(IvfScanParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int n_tasks = *p.n_tasks_dev;
-    if (p.only_flagged) {
-        if (*p.flagged_count == 0) return;
-        for (int task = blockIdx.x; task < n_tasks; task += gridDim.x) {      // (uniform)
-            ivf_scan_task<KSEL>(p, task, smem);
-            __syncthreads();
-        }
-    } else if ((int)blockIdx.x < n_tasks) {
-        ivf_scan_task<KSEL>(p, blockIdx.x, smem);
-    }
+    if ((int)blockIdx.x < *p.n_tasks_dev) ivf_scan_task<KSEL>(p, blockIdx.x, smem);
 }
 
 // ---- grouping of a SMALL batch in one launch (npairs <= IVG_MAX_PAIRS, nlist <= IVG_MAX_LISTS): count, scan, task table and
@@ -553,6 +540,185 @@ __global__ void k_i64_to_i32(const int64_t* in, int* out, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = (int)in[i];
 }
 
+// ---- the certificate of the fp32 list scan ---------------------------------------------------------------------------------------
+// k_ivf_scan ranks by a = fl(2 fl(q.y) - fl(|y|^2)).  With S = sum |q_i y_i| <= |q||y|: the two MFMA accumulators sum dim products in
+// dim / 8 steps of four each and are added once; |y|^2 is an fp32 sum of dim squares; one subtraction forms a.  Charging EVERY product
+// and addition a relative error of 2^-23 (twice the unit roundoff: the matrix core's internal additions need not round to nearest), any
+// order of summation gives |a - (2 q.y - |y|^2)| <= (dim + 16) 2^-23 (2 |q||y| + |y|^2).  eps(q) takes the largest |y| of the query's
+// probed lists (lmax: per list, k_ivf_list_maxnorm at the layout's rebuild), so one huge row costs its own list's queries only.
+__global__ __launch_bounds__(256) void k_ivf_list_maxnorm(const float* __restrict__ lnorm, const int* __restrict__ loff, float* __restrict__ lmax) {
+    __shared__ float s_m[4];
+    const int l = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float m = 0.f;
+    for (int r = loff[l] + threadIdx.x; r < loff[l + 1]; r += 256) m = fmaxf(m, lnorm[r]);
+    m = wave_max(m);
+    if (lane == 0) s_m[wave] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) lmax[l] = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
+}
+
+// one wave per query; the first thread also clears the search's 8 counters (k_hi_rows does that on the f16 route)
+__global__ __launch_bounds__(256) void k_ivf_f32_eps(const float* __restrict__ q, int64_t nq, int dim, const int64_t* __restrict__ probes, int nprobe,
+                                                     int nlist, const float* __restrict__ lmax, float* __restrict__ eps, int* __restrict__ counters) {
+    const int lane = threadIdx.x & 63;
+    const int64_t qi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (blockIdx.x == 0 && threadIdx.x == 0) { for (int i = 0; i < 8; ++i) counters[i] = 0; }
+    if (qi >= nq) return;
+    float ss = 0.f, ym = 0.f;
+    for (int i = lane; i < dim; i += 64) { const float v = q[qi * dim + i]; ss = fmaf(v, v, ss); }
+    for (int j = lane; j < nprobe; j += 64) {
+        const int64_t l = probes[qi * nprobe + j];
+        if ((uint64_t)l < (uint64_t)nlist) ym = fmaxf(ym, lmax[l]);
+    }
+    ss = wave_sum(ss); ym = wave_max(ym);
+    if (lane == 0) eps[qi] = (float)(dim + 16) * 1.1920929e-07f * 1.01f * (2.f * sqrtf(ss) * sqrtf(ym) + ym);      // (1.01: ss, ym and this line are fp32 too)
+}
+
+// ---- exact float64 scan of the probed lists, for the queries a certificate rejected ------------------------------------------
+// Driven from the device as k_exact_scan is: *count rejected queries, their indices in sel (nullptr: slot s is query s); nobody
+// rejected = every workgroup leaves at once.  A workgroup takes (rejected query, probe) pairs in turn: its 8 waves walk the list four
+// rows at a time, sum (q - y)^2 in float64 (lanes across the row, butterfly), and keep the k best by (distance, insertion id) as a
+// sorted list ACROSS the wave's lanes (lane e holds entry e: k <= 26); the waves' lists are ranked into the pair's partial list, and
+// the workgroup that arrives last for a query (device-scope counter) merges the nprobe partial lists and overwrites the query's
+// output rows.  Keys are minus the squared distance: larger is better.
+constexpr int IVX_THREADS = 512;
+constexpr int IVX_WAVES = IVX_THREADS / 64;
+constexpr int IVX_ROWS = 4;                              // rows of a wave in flight
+constexpr int IVX_MAX_GRID = 4096;
+constexpr size_t IVX_PART_BUDGET = (size_t)128 << 20;    // partial lists of one launch (nprobe x k x 16 B per query)
+constexpr int64_t IVX_NO_ID = INT64_MAX;
+
+struct IvfExactParams {
+    const float* lrows = nullptr;      // [N, dim] list-major
+    const int64_t* lids = nullptr;     // [N] insertion id of every position
+    const int* loff = nullptr;         // [nlist + 1]
+    const float* q = nullptr;          // [nq, dim]
+    const int64_t* probes = nullptr;   // [nq, nprobe] lists; outside [0, nlist) = none
+    const int* sel = nullptr;
+    const int* count = nullptr;
+    int* done = nullptr;               // [1] queries answered here (statistics: radad_ivf_last_search_counts)
+    int dim = 0, k = 0, nprobe = 0, nlist = 0;
+    int slot0 = 0, nslots = 0;         // this launch's rejected queries: slots slot0 .. slot0 + nslots
+    double* pkey = nullptr;            // [nslots][nprobe][k]
+    int64_t* pid = nullptr;
+    int* arrive = nullptr;             // [nslots] arrival counters (zero between launches: the last arrival resets its own)
+    float* out_dist = nullptr; int64_t* out_idx = nullptr;
+};
+static_assert(std::is_trivially_copyable_v<IvfExactParams>, "kernel argument");
+
+constexpr size_t ivf_exact_lds_bytes(int dim, int k, int nprobe) {
+    return (size_t)dim * 4 + (size_t)IVX_WAVES * k * 16 + (size_t)nprobe * 4;
+}
+__device__ __forceinline__ bool ivx_better(double ka, int64_t ia, double kb, int64_t ib) { return ka > kb || (ka == kb && ia < ib); }
+
+__global__ __launch_bounds__(IVX_THREADS) void k_ivf_exact(IvfExactParams p) {
+    const int count = min(*p.count - p.slot0, p.nslots);
+    if (count <= 0) return;
+    extern __shared__ __attribute__((aligned(16))) char smem_e[];
+    __shared__ int s_last;
+    float* sQ = reinterpret_cast<float*>(smem_e);                                   // [dim]
+    double* sKey = reinterpret_cast<double*>(sQ + p.dim);                           // [IVX_WAVES][k]
+    long long* sId = reinterpret_cast<long long*>(sKey + IVX_WAVES * p.k);          // [IVX_WAVES][k]
+    int* sPos = reinterpret_cast<int*>(sId + IVX_WAVES * p.k);                      // [nprobe] heads of the final merge
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nv = p.dim >> 2, K = p.k;
+    const int64_t npairs = (int64_t)count * p.nprobe;
+    for (int64_t pr = blockIdx.x; pr < npairs; pr += gridDim.x) {                    // (uniform)
+        const int slot = (int)(pr / p.nprobe), j = (int)(pr % p.nprobe);
+        const int64_t qi = p.sel ? (int64_t)p.sel[p.slot0 + slot] : (int64_t)(p.slot0 + slot);
+        const int64_t list = p.probes[qi * p.nprobe + j];
+        int64_t r0 = 0, r1 = 0;
+        if ((uint64_t)list < (uint64_t)p.nlist) { r0 = p.loff[list]; r1 = p.loff[list + 1]; }
+        __syncthreads();                                                             // (the previous pair's LDS is free)
+        for (int i = tid; i < nv; i += IVX_THREADS)
+            reinterpret_cast<f32x4*>(sQ)[i] = reinterpret_cast<const f32x4*>(p.q + qi * p.dim)[i];
+        __syncthreads();
+        double ek = -INFINITY;                                                       // lane e: entry e of the wave's sorted list
+        long long ei = IVX_NO_ID;
+        for (int64_t row = r0 + wave * IVX_ROWS; row < r1; row += IVX_WAVES * IVX_ROWS) {
+            double acc[IVX_ROWS];
+#pragma unroll
+            for (int u = 0; u < IVX_ROWS; ++u) acc[u] = 0.0;
+            for (int i = lane; i < nv; i += 64) {
+                f32x4 y[IVX_ROWS];
+#pragma unroll
+                for (int u = 0; u < IVX_ROWS; ++u) y[u] = reinterpret_cast<const f32x4*>(p.lrows + min(row + u, r1 - 1) * p.dim)[i];
+                const f32x4 x = reinterpret_cast<const f32x4*>(sQ)[i];
+#pragma unroll
+                for (int u = 0; u < IVX_ROWS; ++u)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { const double d = (double)x[e] - (double)y[u][e]; acc[u] -= d * d; }
+            }
+#pragma unroll
+            for (int u = 0; u < IVX_ROWS; ++u) {
+                if (row + u >= r1) break;                                            // (wave-uniform)
+                double v = acc[u];
+#pragma unroll
+                for (int ofs = 32; ofs > 0; ofs >>= 1) v += __shfl_xor(v, ofs, 64);
+                const long long gid = p.lids[row + u];
+                if (ivx_better(v, gid, __shfl(ek, K - 1, 64), __shfl(ei, K - 1, 64))) {      // (wave-uniform) beats the k-th entry
+                    // the better entries are a prefix of the sorted list: the new one goes behind them, the rest moves one lane up
+                    const int nb = __popcll(__ballot(lane < K && ivx_better(ek, ei, v, gid)));
+                    const double pk = __shfl_up(ek, 1, 64);
+                    const long long pi = __shfl_up(ei, 1, 64);
+                    if (lane > nb) { ek = pk; ei = pi; }
+                    else if (lane == nb) { ek = v; ei = gid; }
+                }
+            }
+        }
+        if (lane < K) { sKey[wave * K + lane] = ek; sId[wave * K + lane] = ei; }
+        const int64_t ob = ((int64_t)slot * p.nprobe + j) * K;
+        if (tid < K) { p.pkey[ob + tid] = -INFINITY; p.pid[ob + tid] = IVX_NO_ID; }
+        __syncthreads();
+        if (tid < IVX_WAVES * K && sId[tid] != IVX_NO_ID) {                           // rank of every listed row among the waves' entries
+            const double kc = sKey[tid];
+            const long long ic = sId[tid];
+            int rank = 0;
+            for (int e = 0; e < IVX_WAVES * K; ++e) rank += (int)ivx_better(sKey[e], sId[e], kc, ic);
+            if (rank < K) { p.pkey[ob + rank] = kc; p.pid[ob + rank] = ic; }
+        }
+        __threadfence();                                 // release: this pair's list is visible device-wide before the counter moves
+        __syncthreads();
+        if (tid == 0) {
+            const int old = atomicAdd(&p.arrive[slot], 1);
+            s_last = old == p.nprobe - 1;
+            if (s_last) p.arrive[slot] = 0;              // ready for the next launch
+        }
+        __syncthreads();
+        if (s_last && wave == 0) {                       // the query's last pair: merge its nprobe partial lists (lane l owns lists l, l + 64, ...)
+            __threadfence();                             // acquire
+            for (int part = lane; part < p.nprobe; part += 64) sPos[part] = 0;
+            const int64_t lb = (int64_t)slot * p.nprobe * K;
+            for (int o = 0; o < K; ++o) {
+                double bk = -INFINITY;
+                long long bi = IVX_NO_ID;
+                int bp = -1;
+                for (int part = lane; part < p.nprobe; part += 64) {
+                    const int pos = sPos[part];
+                    if (pos >= K) continue;
+                    const long long id = p.pid[lb + (int64_t)part * K + pos];
+                    if (id == IVX_NO_ID) continue;
+                    const double key = p.pkey[lb + (int64_t)part * K + pos];
+                    if (bp < 0 || ivx_better(key, id, bk, bi)) { bk = key; bi = id; bp = part; }
+                }
+#pragma unroll
+                for (int ofs = 32; ofs > 0; ofs >>= 1) {
+                    const double ok = __shfl_xor(bk, ofs, 64);
+                    const long long oi = __shfl_xor(bi, ofs, 64);
+                    const int op = __shfl_xor(bp, ofs, 64);
+                    if (op >= 0 && (bp < 0 || ivx_better(ok, oi, bk, bi))) { bk = ok; bi = oi; bp = op; }
+                }
+                if (bp >= 0 && (bp & 63) == lane) sPos[bp] += 1;
+                if (lane == 0) {
+                    p.out_dist[qi * K + o] = bp < 0 ? INFINITY : (float)(-bk);
+                    p.out_idx[qi * K + o] = bp < 0 ? (int64_t)-1 : (int64_t)bi;
+                }
+            }
+            if (lane == 0) atomicAdd(p.done, 1);
+        }
+    }
+}
+
 struct DevMem {
     void* p = nullptr;
     size_t bytes = 0;
@@ -577,6 +743,7 @@ struct radad_ivf_s {
     radad_knn_t flat = nullptr;         // rows in insertion order (IP metric = plain copy; used for storage + reconstruct)
     std::vector<int> assign;            // list of every stored row (host copy; the device copy is rebuilt with the layout)
     DevMem lrows, lnorm, lids, loff, assign_dev, ws_a, ws_b, ws_c, part_s, part_i, tasks;
+    DevMem lmax, xkey, xid, xarrive;    // |y|^2 max of every list (the fp32 scan's error bound); partial lists + arrival counters of the exact list scan
     DevMem lhi, lscale, lbias, qbuf, cand_s, cand_i;    // the flat store's f16 plane gathered list-major (+ per-row scale, bias); the queries' f16 side
     bool have_hi = false;               // lhi is up to date with ...
     const void* hi_src = nullptr;       // ... this plane of the flat store (pointer, rows and rebuild count at the gather)
@@ -586,7 +753,8 @@ struct radad_ivf_s {
     std::vector<int> loff_host;
     hipEvent_t ev_done = nullptr;       // end of the last search's device work: the next search (any stream) waits for it,
     bool last_hi = false;               // the most recent search went through the certified f16 list scan
-    const int* last_fcount = nullptr;   // ... and this device counter holds how many of its queries the certificate rejected
+    const int* last_fcount = nullptr;   // device counters of the most recent list-scan search: [0] queries its certificate rejected, [1] queries the
+                                        // exact list scan answered
     bool last_exact = false;            // the most recent search was answered by the exact flat scan (k > 26): radad_ivf_last_search_exact
     bool have_last = false;             // since all searches share the workspaces below and nothing synchronises with the host: a search on
     hipStream_t last_stream = nullptr;  // ANOTHER stream than the last records the event behind that stream's work first (knn.hip does the same)
@@ -645,11 +813,13 @@ static int ivf_prepare(radad_ivf_t h, hipStream_t st) {
     if ((rc = h->lnorm.ensure((size_t)n * sizeof(float)))) return rc;
     if ((rc = h->lids.ensure((size_t)n * sizeof(int64_t)))) return rc;
     if ((rc = h->loff.ensure((size_t)(h->nlist + 1) * sizeof(int)))) return rc;
+    if ((rc = h->lmax.ensure((size_t)h->nlist * sizeof(float)))) return rc;
     RADAD_HIP_CHECK(hipMemcpyAsync(h->lids.p, perm.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, st));
     RADAD_HIP_CHECK(hipMemcpyAsync(h->loff.p, h->loff_host.data(), (size_t)(h->nlist + 1) * sizeof(int), hipMemcpyHostToDevice, st));
     if ((rc = radad_knn_reconstruct(h->flat, (const int64_t*)h->lids.p, n, (float*)h->lrows.p, st))) return rc;   // gather by insertion id
     hipLaunchKernelGGL(k_row_sqnorm<float>, dim3((unsigned)ceil_div64(n, 4)), dim3(256), 0, st, (const float*)h->lrows.p, n, h->dim,
                        (float*)h->lnorm.p);
+    hipLaunchKernelGGL(k_ivf_list_maxnorm, dim3((unsigned)h->nlist), dim3(256), 0, st, (const float*)h->lnorm.p, (const int*)h->loff.p, (float*)h->lmax.p);
     RADAD_HIP_CHECK(hipGetLastError());
     RADAD_HIP_CHECK(hipStreamSynchronize(st));     // perm / loff_host are host vectors
     h->dirty = false;
@@ -676,6 +846,19 @@ static bool ivf_ensure_plane(radad_ivf_t h, hipStream_t st) {
     if (hipGetLastError() != hipSuccess) return false;
     h->have_hi = true; h->hi_src = f->hi; h->hi_src_rows = f->hi_rows; h->hi_src_epoch = f->plane_rebuilds;
     return true;
+}
+
+// the counters of the most recent search (zero when the flat store answered it, or the index held no rows); synchronises with it
+static int ivf_last_counts(radad_ivf_t h, int* rejected_out, int* exact_out) {
+    int c[2] = {0, 0};
+    if (!h->last_exact && h->last_fcount) {
+        DeviceGuard g(h->device);
+        ivf_wait_searches(h);
+        RADAD_HIP_CHECK(hipMemcpy(c, h->last_fcount, sizeof(c), hipMemcpyDeviceToHost));
+    }
+    *rejected_out = c[0];
+    if (exact_out) *exact_out = c[1];
+    return RADAD_OK;
 }
 
 extern "C" {
@@ -706,6 +889,7 @@ int radad_ivf_destroy(radad_ivf_t h) {
         if (h->centroids) (void)hipFree(h->centroids);
         h->lrows.release(); h->lnorm.release(); h->lids.release(); h->loff.release(); h->assign_dev.release();
         h->ws_a.release(); h->ws_b.release(); h->ws_c.release(); h->part_s.release(); h->part_i.release(); h->tasks.release();
+        h->lmax.release(); h->xkey.release(); h->xid.release(); h->xarrive.release();
         h->lhi.release(); h->lscale.release(); h->lbias.release(); h->qbuf.release(); h->cand_s.release(); h->cand_i.release();
         if (h->ev_done) { (void)hipDeviceSynchronize(); (void)hipEventDestroy(h->ev_done); }
     }
@@ -825,13 +1009,13 @@ int radad_ivf_last_search_info(radad_ivf_t h, int* kind_out, int* rejected_out) 
     RADAD_REQUIRE(h && kind_out && rejected_out, "radad_ivf_last_search_info: NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
     *kind_out = h->last_exact ? RADAD_IVF_SCAN_EXACT_FLAT : (h->last_hi ? RADAD_IVF_SCAN_HI : RADAD_IVF_SCAN_F32);
-    *rejected_out = 0;
-    if (h->last_hi && !h->last_exact && h->last_fcount) {
-        DeviceGuard g(h->device);
-        ivf_wait_searches(h);
-        RADAD_HIP_CHECK(hipMemcpy(rejected_out, h->last_fcount, sizeof(int), hipMemcpyDeviceToHost));
-    }
-    return RADAD_OK;
+    return ivf_last_counts(h, rejected_out, nullptr);
+}
+
+int radad_ivf_last_search_counts(radad_ivf_t h, int* rejected_out, int* exact_out) {
+    RADAD_REQUIRE(h && rejected_out && exact_out, "radad_ivf_last_search_counts: NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    return ivf_last_counts(h, rejected_out, exact_out);
 }
 
 int radad_ivf_reconstruct(radad_ivf_t h, const int64_t* idx_dev, int64_t n, float* out_dev, void* stream) {
@@ -871,7 +1055,15 @@ int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int n
     }
     if ((rc = ivf_prepare(h, st))) return rc;
     const int64_t n = (int64_t)h->assign.size();
-    const bool use_hi = n > 0 && ivf_ensure_plane(h, st);
+    if (n == 0) {      // a trained index without rows: every slot unfilled (id -1, distance +inf)
+        hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)ceil_div64(nq * k, 256)), dim3(256), 0, st, out_dist_dev, nq * k, INFINITY);
+        RADAD_HIP_CHECK(hipGetLastError());
+        RADAD_HIP_CHECK(hipMemsetAsync(out_idx_dev, 0xff, (size_t)nq * k * sizeof(int64_t), st));
+        h->last_hi = false; h->last_fcount = nullptr;
+        h->last_stream = st; h->have_last = true;
+        return RADAD_OK;
+    }
+    const bool use_hi = ivf_ensure_plane(h, st);
     const int ksel = k + KNN_MARGIN;
     const int64_t npairs = nq * nprobe;
 
@@ -907,23 +1099,26 @@ int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int n
     }
     RADAD_HIP_CHECK(hipGetLastError());
 
-    // 3a) the certified f16 list scan: k_hi_rows on the queries (f16 side, eps), k_ivf_scan_hi (emit mode), k_merge_refine<true> with the
-    //     certificate.  The scatter above has written "empty" partial lists for probes outside [0, nlist): the fp32 pass reads them.
-    const int* d_qflag = nullptr;
-    bool answered = false;
-    if (use_hi && ivf_hi_lds_bytes(qcap, h->dim) <= 160 * 1024) {
+    // per-query scratch of either route: eps, the certificate's list of rejected queries, the search's counters
+    const bool hi_route = use_hi && ivf_hi_lds_bytes(qcap, h->dim) <= 160 * 1024;
+    const size_t b_qh = hi_route ? al256((size_t)nq * h->dim * 2) : 0, b_vec = al256((size_t)nq * sizeof(float));
+    if ((rc = h->qbuf.ensure(b_qh + 6 * b_vec + 256))) return rc;
+    char* qb = (char*)h->qbuf.p;
+    float* eps = (float*)(qb + b_qh + 2 * b_vec);
+    int* fsel = (int*)(qb + b_qh + 5 * b_vec); int* fcount = (int*)(qb + b_qh + 6 * b_vec);      // fcount: [8], [0] rejected, [1] answered by the exact scan
+    const int* xsel = fsel;
+
+    if (hi_route) {
+        // 3a) the certified f16 list scan: k_hi_rows on the queries (f16 side, eps), k_ivf_scan_hi (emit mode), k_merge_refine<true> with the
+        //     certificate
         // (the tasks hold <= qcap queries, sized for the fp32 kernel's query block: the f16 block is half of it and fits beside the score tile)
         radad_knn_t f = h->flat;
-        const size_t b_qh = al256((size_t)nq * h->dim * 2), b_vec = al256((size_t)nq * sizeof(float));
-        if ((rc = h->qbuf.ensure(b_qh + 7 * b_vec + 256))) return rc;
         const int ccap = nq <= SQ_NQ ? IVH_CAND_CAP_SMALLQ : IVH_CAND_CAP;
-        if ((rc = h->cand_s.ensure((size_t)nq * ccap * sizeof(float)))) return rc;      // (not the partial lists' arrays: the scatter has
-        if ((rc = h->cand_i.ensure((size_t)nq * ccap * sizeof(int)))) return rc;        // filled the fp32 pass's lists of unusable probes there)
-        char* qb = (char*)h->qbuf.p;
+        if ((rc = h->cand_s.ensure((size_t)nq * ccap * sizeof(float)))) return rc;
+        if ((rc = h->cand_i.ensure((size_t)nq * ccap * sizeof(int)))) return rc;
         _Float16* qh = (_Float16*)qb;
-        float* qscale = (float*)(qb + b_qh); float* qconst = (float*)(qb + b_qh + b_vec); float* eps = (float*)(qb + b_qh + 2 * b_vec);
+        float* qscale = (float*)(qb + b_qh); float* qconst = (float*)(qb + b_qh + b_vec);
         int* cand_cnt = (int*)(qb + b_qh + 3 * b_vec); unsigned* gbound = (unsigned*)(qb + b_qh + 4 * b_vec);
-        int* qflag = (int*)(qb + b_qh + 5 * b_vec); int* fsel = (int*)(qb + b_qh + 6 * b_vec); int* fcount = (int*)(qb + b_qh + 7 * b_vec);
         HiRowsParams hp;
         hp.in = q_dev; hp.hi = qh; hp.scale_out = qscale; hp.eps_out = eps; hp.ystat = f->stat;
         hp.n = nq; hp.dim = h->dim; hp.fixed_e = HI_E_PER_ROW; hp.l2 = 1;
@@ -949,51 +1144,79 @@ int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int n
         m.cap = std::max(k + KNN_CERT_EXTRA, KNN_CERT_CAP); m.eps = eps; m.part_cnt = cand_cnt;
         m.flag_count = fcount; m.flag_sel = fsel; m.nq = nq;
         m.db = h->lrows.p; m.q = q_dev; m.id_map = (const int64_t*)h->lids.p;
-        m.out_dist = out_dist_dev; m.out_idx = out_idx_dev; m.qflag_out = qflag;
+        m.out_dist = out_dist_dev; m.out_idx = out_idx_dev;
         const size_t rlds = refine_lds_bytes(m.cap) + (size_t)ccap * 8 + 1024;
         if (rlds > 48 * 1024)
             RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge_refine<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
         hipLaunchKernelGGL(k_merge_refine<true>, dim3((unsigned)nq), dim3(RF_THREADS), rlds, st, m);
-        if (h->opt_hi == 2) {       // (tests) every query counts as rejected: the fp32 pass answers them all
-            float one, all;
-            const int i1 = 1, in = (int)nq;
-            memcpy(&one, &i1, 4); memcpy(&all, &in, 4);
-            hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, st, (float*)qflag, nq, one);
+        if (h->opt_hi == 2) {       // (tests) every query counts as rejected: the exact scan answers them all, slot s = query s
+            float all;
+            const int in = (int)nq;
+            memcpy(&all, &in, 4);
             hipLaunchKernelGGL(k_fill_f32, dim3(1), dim3(256), 0, st, (float*)fcount, (int64_t)1, all);
+            xsel = nullptr;
         }
         RADAD_HIP_CHECK(hipGetLastError());
-        d_qflag = qflag;
-        h->last_fcount = fcount;
-        answered = true;
-    }
-    h->last_hi = answered;
-
-    // 3) scan every touched list once
-    IvfScanParams sp;
-    sp.lrows = (const float*)h->lrows.p; sp.lnorm = (const float*)h->lnorm.p; sp.loff = (const int*)h->loff.p; sp.q = q_dev;
-    sp.task_list = d_tl; sp.task_pbeg = d_tp; sp.task_cnt = d_tc; sp.n_tasks_dev = d_nt; sp.pair_q = d_pq; sp.pair_slot = d_ps; sp.dim = h->dim; sp.k = ksel;
-    sp.qcap = qcap;
-    sp.part_score = (float*)h->part_s.p; sp.part_idx = (int*)h->part_i.p; sp.only_flagged = d_qflag; sp.flagged_count = d_qflag ? h->last_fcount : nullptr;
-    const size_t slot_bytes = std::max<size_t>(sizeof(float2) * 4 * SQ_NQ * SQ_SLOTS, sizeof(u64) * 3 * SQ_NQ * 32);
-    const size_t lds = sizeof(float) * qcap * (h->dim + 4) + slot_bytes + sizeof(int) * 4 * SQ_NQ;
-    RADAD_REQUIRE(lds <= 160 * 1024, "radad_ivf_search: dim %d too large for the list-scan kernel", h->dim);
-    if (T > 0 && n > 0) {
+    } else {
+        // 3b) the fp32 list scan (no f16 plane: dim % 64 != 0, RADAD_IVF_OPT_HI_SCAN 0): every touched list once, k + 6 entries per
+        //     (query, list); k_merge_refine re-scores in float64 everything within 2 eps of the k-th best fp32 score and certifies the
+        //     query unless a full list lies entirely inside that band (it may hide more) or the band holds more than `cap` rows
+        hipLaunchKernelGGL(k_ivf_f32_eps, dim3((unsigned)ceil_div64(nq, 4)), dim3(256), 0, st, q_dev, nq, h->dim, (const int64_t*)h->ws_b.p, nprobe, h->nlist,
+                           (const float*)h->lmax.p, eps, fcount);
+        IvfScanParams sp;
+        sp.lrows = (const float*)h->lrows.p; sp.lnorm = (const float*)h->lnorm.p; sp.loff = (const int*)h->loff.p; sp.q = q_dev;
+        sp.task_list = d_tl; sp.task_pbeg = d_tp; sp.task_cnt = d_tc; sp.n_tasks_dev = d_nt; sp.pair_q = d_pq; sp.pair_slot = d_ps; sp.dim = h->dim; sp.k = ksel;
+        sp.qcap = qcap;
+        sp.part_score = (float*)h->part_s.p; sp.part_idx = (int*)h->part_i.p;
+        const size_t slot_bytes = std::max<size_t>(sizeof(float2) * 4 * SQ_NQ * SQ_SLOTS, sizeof(u64) * 3 * SQ_NQ * 32);
+        const size_t lds = sizeof(float) * qcap * (h->dim + 4) + slot_bytes + sizeof(int) * 4 * SQ_NQ;
+        RADAD_REQUIRE(lds <= 160 * 1024, "radad_ivf_search: dim %d too large for the list-scan kernel", h->dim);
         if (ksel <= 16) {
             RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_scan<16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k_ivf_scan<16>, dim3((unsigned)(d_qflag ? std::min<int64_t>(T, 1024) : T)), dim3(SQ_THREADS), lds, st, sp);
+            hipLaunchKernelGGL(k_ivf_scan<16>, dim3((unsigned)T), dim3(SQ_THREADS), lds, st, sp);
         } else {
             RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_scan<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k_ivf_scan<32>, dim3((unsigned)(d_qflag ? std::min<int64_t>(T, 1024) : T)), dim3(SQ_THREADS), lds, st, sp);
+            hipLaunchKernelGGL(k_ivf_scan<32>, dim3((unsigned)T), dim3(SQ_THREADS), lds, st, sp);
+        }
+        RefineParams m;
+        m.score = (const float*)h->part_s.p; m.idx = (const int*)h->part_i.p; m.n_parts = nprobe; m.part_len = ksel; m.k = k; m.dim = h->dim;
+        m.cap = std::max(k + KNN_CERT_EXTRA, (int)std::min<int64_t>((int64_t)nprobe * ksel, KNN_CERT_CAP));
+        m.eps = eps; m.flag_count = fcount; m.flag_sel = fsel;
+        m.l2 = 1; m.nq = nq; m.db = h->lrows.p; m.q = q_dev; m.id_map = (const int64_t*)h->lids.p;
+        m.out_dist = out_dist_dev; m.out_idx = out_idx_dev;
+        hipLaunchKernelGGL(k_merge_refine<false>, dim3((unsigned)nq), dim3(RF_THREADS), refine_lds_bytes(m.cap), st, m);
+        RADAD_HIP_CHECK(hipGetLastError());
+    }
+    h->last_hi = hi_route;
+    h->last_fcount = fcount;
+
+    // 4) the queries the route's certificate rejected: exact float64 scan of their probed lists (leaves at once when there are none)
+    {
+        const size_t xlds = ivf_exact_lds_bytes(h->dim, k, nprobe);
+        RADAD_REQUIRE(xlds <= 160 * 1024, "radad_ivf_search: nprobe %d too large for the exact list scan", nprobe);
+        const int64_t per_q = (int64_t)nprobe * k * 16;
+        const int64_t slots = std::min<int64_t>(nq, std::max<int64_t>(1, (int64_t)IVX_PART_BUDGET / per_q));
+        if ((rc = h->xkey.ensure((size_t)slots * nprobe * k * sizeof(double)))) return rc;
+        if ((rc = h->xid.ensure((size_t)slots * nprobe * k * sizeof(int64_t)))) return rc;
+        {
+            const void* before = h->xarrive.p;
+            if ((rc = h->xarrive.ensure((size_t)slots * sizeof(int)))) return rc;
+            if (h->xarrive.p != before) RADAD_HIP_CHECK(hipMemsetAsync(h->xarrive.p, 0, h->xarrive.bytes, st));
+        }
+        IvfExactParams x;
+        x.lrows = (const float*)h->lrows.p; x.lids = (const int64_t*)h->lids.p; x.loff = (const int*)h->loff.p; x.q = q_dev;
+        x.probes = (const int64_t*)h->ws_b.p; x.sel = xsel; x.count = fcount; x.done = fcount + 1;
+        x.dim = h->dim; x.k = k; x.nprobe = nprobe; x.nlist = h->nlist; x.nslots = (int)slots;
+        x.pkey = (double*)h->xkey.p; x.pid = (int64_t*)h->xid.p; x.arrive = (int*)h->xarrive.p;
+        x.out_dist = out_dist_dev; x.out_idx = out_idx_dev;
+        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_exact), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
+        const unsigned grid = (unsigned)std::min<int64_t>(slots * nprobe, IVX_MAX_GRID);
+        for (int64_t s0 = 0; s0 < nq; s0 += slots) {        // (one launch unless the batch's partial lists exceed IVX_PART_BUDGET)
+            x.slot0 = (int)s0;
+            hipLaunchKernelGGL(k_ivf_exact, dim3(grid), dim3(IVX_THREADS), xlds, st, x);
         }
         RADAD_HIP_CHECK(hipGetLastError());
     }
-    // 4) per query: merge its nprobe lists, float64 re-score, (distance, insertion id) order
-    RefineParams m;
-    m.score = (const float*)h->part_s.p; m.idx = (const int*)h->part_i.p; m.n_parts = nprobe; m.cap = ksel; m.part_len = ksel; m.k = k; m.dim = h->dim;
-    m.l2 = 1; m.nq = nq; m.db = h->lrows.p; m.q = q_dev; m.id_map = (const int64_t*)h->lids.p;
-    m.out_dist = out_dist_dev; m.out_idx = out_idx_dev; m.only_flagged = d_qflag;
-    hipLaunchKernelGGL(k_merge_refine<false>, dim3((unsigned)nq), dim3(RF_THREADS), refine_lds_bytes(ksel), st, m);
-    RADAD_HIP_CHECK(hipGetLastError());
     h->last_stream = st;
     h->have_last = true;
     return RADAD_OK;

@@ -1165,8 +1165,8 @@ struct RefineParams {
     int64_t* out_idx = nullptr;        // [nq, k]
     double* out_key = nullptr;         // optional [nq, k] float64 distances
     int debug = 0;                     // timing experiments only (-DRADAD_DEBUG_HOOKS, RADAD_DEBUG_KNN): 128 no statistics atomics, 256 no re-score, 512 no ranking, 1024 no fp32 funnel
-    int* qflag_out = nullptr;          // optional [nq] (certified mode): the certificate's verdict per query, 0 = certified (IVF: who takes the fp32 pass)
-    const int* only_flagged = nullptr; // optional [nq]: workgroups of queries whose entry is 0 leave at once (IVF: the fp32 pass of the rejected)
+    int* qflag_out = nullptr;          // optional [nq] (certified mode): the certificate's verdict per query, 0 = certified (no caller left: IVF reads flag_sel)
+    const int* only_flagged = nullptr; // optional [nq]: workgroups of queries whose entry is 0 leave at once (no caller left: see k_ivf_exact)
 };
 static_assert(std::is_trivially_copyable_v<RefineParams>, "kernel argument");
 

@@ -334,7 +334,8 @@ class HipIVFFlatIndex:
     search, reconstruct."""
 
     def __init__(self, d: int, nlist: int, device: int = 0, niter: int = 10, hi_scan=None):
-        """hi_scan: 0 keeps the list scans on the fp32 rows (radad_ivf_set_option; None = the library's default, the certified f16 scan)"""
+        """hi_scan: 0 keeps the list scans on the fp32 rows (radad_ivf_set_option; None = the library's default, the certified f16 scan);
+        2 (tests) sends every query through the exact float64 list scan that answers the queries a certificate rejects"""
         self._lib = _lib.load()
         self.d, self.nlist, self.device, self.niter = int(d), int(nlist), int(device), int(niter)
         self.nprobe = 1                      # faiss default; the reference sets it from config.vector_db_nprobe (:177)
@@ -441,11 +442,12 @@ class HipIVFFlatIndex:
         return D.cpu().numpy(), I.cpu().numpy()
 
     def last_search_info(self) -> dict:
-        """{"scan": "f32_lists" | "hi_lists" | "exact_flat", "rejected": queries the f16 scan's certificate handed to the fp32 pass}
-        of the most recent search (synchronises with it)"""
-        kind, rej = C.c_int(), C.c_int()
+        """{"scan": "f32_lists" | "hi_lists" | "exact_flat", "rejected": queries the list scan's certificate could not certify,
+        "exact": queries the exact float64 list scan answered (the rejected ones)} of the most recent search (synchronises with it)"""
+        kind, rej, ex = C.c_int(), C.c_int(), C.c_int()
         _lib.check(self._lib.radad_ivf_last_search_info(self._h, C.byref(kind), C.byref(rej)), "radad_ivf_last_search_info")
-        return {"scan": _lib.IVF_SCAN_KINDS[kind.value], "rejected": rej.value}
+        _lib.check(self._lib.radad_ivf_last_search_counts(self._h, C.byref(rej), C.byref(ex)), "radad_ivf_last_search_counts")
+        return {"scan": _lib.IVF_SCAN_KINDS[kind.value], "rejected": rej.value, "exact": ex.value}
 
     SNAPSHOT_CHUNK = 1 << 18
 
