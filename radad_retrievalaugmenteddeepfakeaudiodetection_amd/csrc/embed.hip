@@ -520,10 +520,12 @@ __device__ __forceinline__ int64_t pp2_scalar_i64(const int64_t* ptr) {         
 #endif
 }
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
 struct PP2Item { int clip, s, s_first, s_end, f0, valid; };      // (plain ints, copied field by field: hipcc otherwise keeps the items in scratch)
 
-template <int NT, int MODE>
+// ONEBIN: levels = [1] (picked on the host): the benchmark's configuration; the package default [1, 2, 4] and every other pyramid
+// run the general bin loop.  With one bin a segment's pooled value never leaves its register: no bin loop, no s_lo / s_hi / spool
+// traffic per tile (pool_tile1 in pass()).  The MFMA loop is the same for both.
+template <int NT, int MODE, bool ONEBIN>
 __global__ __launch_bounds__(PP2_THREADS, 2) void k_proj_pool2(ProjPoolParams p, int n_groups_host) {
     constexpr int FEATS = PP2_WAVES * 32 * NT;
     constexpr int PLANE = PP2_PB * PP_LDH;                   // halfs per plane
@@ -572,6 +574,9 @@ __global__ __launch_bounds__(PP2_THREADS, 2) void k_proj_pool2(ProjPoolParams p,
         bias[nt] = p.bias[feat[nt]];
     }
 
+    float segv[NT];                                          // ONEBIN: the current segment's pooled value (max: before the scale and the bias)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) segv[nt] = 0.f;
     // the walk: (group, segment, pass); a group is a clip, or one segment when clip_seg is null (ragged batches)
     auto first_of = [&](int c, PP2Item& it) {
         it.clip = c; it.f0 = 0; it.valid = c < n_groups ? 1 : 0;
@@ -640,11 +645,16 @@ __global__ __launch_bounds__(PP2_THREADS, 2) void k_proj_pool2(ProjPoolParams p,
     auto pass = [&](const PP2Item& cur, int buf, const PP2Item& nxt, const f32x4 (&rawc)[PP2_RAW], float smaxc) {
         const _Float16* slm_h = planes + (size_t)buf * 2 * PLANE;
         const _Float16* slm_l = slm_h + PLANE;
+        if (ONEBIN && cur.f0 == 0) {
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) segv[nt] = MODE == RADAD_POOL_MAX ? -INFINITY : 0.f;
+        }
         if (cur.f0 == 0 && lh == 0) {                        // (columns are wave-private: no barrier for these)
             const float init = MODE == RADAD_POOL_MAX ? -INFINITY : 0.f;
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
-                for (int b = 0; b < nbins; ++b) spool[b * FEATS + fl[nt]] = init;
+                if (!ONEBIN)
+                    for (int b = 0; b < nbins; ++b) spool[b * FEATS + fl[nt]] = init;
                 if (cur.s == cur.s_first)
                     for (int b = 0; b < nbins; ++b) sclip[b * FEATS + fl[nt]] = 0.f;
             }
@@ -686,6 +696,36 @@ __global__ __launch_bounds__(PP2_THREADS, 2) void k_proj_pool2(ProjPoolParams p,
                 }
             }
         };
+        // ONEBIN: the one bin is [0, T).  The tile's pooled value joins the segment's in a register; for the maximum the two lane halves
+        // meet once per segment (the maximum is order-free), for the sum once per tile, in the order of the general path.
+        auto pool_tile1 = [&](int nt, const f32x16& acc, int tfirst) {
+            if (!active[nt]) return;
+            if (RADAD_DBG(p.debug, 32)) { asm volatile("" : : "v"(acc)); return; }
+            float v = MODE == RADAD_POOL_MAX ? segv[nt] : 0.f;
+            if (tfirst + 32 <= p.T) {                             // whole tile inside the segment (wave-uniform)
+                if (MODE == RADAD_POOL_MAX) {
+#pragma unroll
+                    for (int r = 0; r < 16; r += 2) asm("v_max3_f32 %0, %0, %1, %2" : "+v"(v) : "v"(acc[r]), "v"(acc[r + 1]));
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) v += fmaf(acc[r], wsc[nt], bias[nt]);
+                }
+            } else if (MODE == RADAD_POOL_MAX) {                   // the segment's last tile: rows past T are -inf to the maximum
+                float m[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) m[r] = tfirst + (r & 3) + 8 * (r >> 2) + 4 * lh < p.T ? acc[r] : -INFINITY;
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) asm("v_max3_f32 %0, %0, %1, %2" : "+v"(v) : "v"(m[r]), "v"(m[r + 1]));
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const bool in = tfirst + (r & 3) + 8 * (r >> 2) + 4 * lh < p.T;
+                    v += in ? fmaf(acc[r], wsc[nt], bias[nt]) : 0.f;
+                }
+            }
+            if (MODE == RADAD_POOL_MAX) segv[nt] = v;
+            else segv[nt] += v + __shfl_xor(v, 32, 64);
+        };
 #pragma unroll 1
         for (int tile = 0; tile < 4; ++tile) {
             if (tile < ntile) {
@@ -718,15 +758,25 @@ __global__ __launch_bounds__(PP2_THREADS, 2) void k_proj_pool2(ProjPoolParams p,
                         }
                         if (nt == 1 && st == 1) {
                             __builtin_amdgcn_sched_barrier(0);
-                            pool_tile(0, acc[0], tfirst, tlast);
+                            if (ONEBIN) pool_tile1(0, acc[0], tfirst);
+                            else pool_tile(0, acc[0], tfirst, tlast);
                             __builtin_amdgcn_sched_barrier(0);
                         }
                     }
                 }
-                pool_tile(NT - 1, acc[NT - 1], tfirst, tlast);
+                if (ONEBIN) pool_tile1(NT - 1, acc[NT - 1], tfirst);
+                else pool_tile(NT - 1, acc[NT - 1], tfirst, tlast);
             } else if (nxt.valid) convert_slice(nxt, rawc, smaxc, tile, buf ^ 1);      // a short pass: the slices its missing tiles would have converted
         }
         // segment done: its vector into the clip's running sum; clip done: the mean leaves (pipeline.py:411)
+        float segfin[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {                    // (the two lane halves meet outside the lh == 0 branch below)
+            segfin[nt] = segv[nt];
+            // max: the exact power-of-two un-scale and the bias are monotone, so they commute with the maximum bit for bit
+            if (ONEBIN && MODE == RADAD_POOL_MAX && cur.f0 + PP2_PB >= p.T)
+                segfin[nt] = fmaf(fmaxf(segv[nt], __shfl_xor(segv[nt], 32, 64)), wsc[nt], bias[nt]);
+        }
         if (cur.f0 + PP2_PB >= p.T && lh == 0) {
             const bool last_seg = cur.s + 1 >= cur.s_end;
             const float nseg = (float)(cur.s_end - cur.s_first);
@@ -734,7 +784,7 @@ __global__ __launch_bounds__(PP2_THREADS, 2) void k_proj_pool2(ProjPoolParams p,
             for (int nt = 0; nt < NT; ++nt) {
                 if (!active[nt]) continue;
                 for (int b = 0; b < nbins; ++b) {
-                    float v = spool[b * FEATS + fl[nt]];
+                    float v = ONEBIN ? segfin[nt] : spool[b * FEATS + fl[nt]];
                     if (MODE == RADAD_POOL_AVG) v = v / (float)(s_hi[b] - s_lo[b]);
                     v += sclip[b * FEATS + fl[nt]];
                     if (!last_seg) sclip[b * FEATS + fl[nt]] = v;
@@ -780,6 +830,16 @@ __global__ __launch_bounds__(PP2_THREADS, 2) void k_proj_pool2(ProjPoolParams p,
         __syncthreads();
         copy_item(it0, it2); copy_item(it1, it3); copy_item(it2, it4);
     }
+}
+
+template <int NT, int MODE, bool ONEBIN>
+static hipError_t pp2_set_lds() {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(k_proj_pool2<NT, MODE, ONEBIN>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)projpool2_lds_bytes(NT));
+}
+template <int NT, int MODE, bool ONEBIN>
+static void pp2_launch(dim3 grid, hipStream_t st, const ProjPoolParams& p, int n_groups) {
+    hipLaunchKernelGGL((k_proj_pool2<NT, MODE, ONEBIN>), grid, dim3(PP2_THREADS), projpool2_lds_bytes(NT), st, p, n_groups);
 }
 
 // finalise log-mel for the stage API: out[s][t][m] = (max(x, smax-8)+4)/4, frames >= nf are silence
@@ -1488,14 +1548,10 @@ int radad_embed_create_ex(const radad_embed_cfg* cfg, int flags, const float* me
                                 (int)logmel_h_clip_lds_bytes()) != hipSuccess ||
             hipFuncSetAttribute(reinterpret_cast<const void*>(k_logmel_fft_clip), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)logmel_fft_lds_bytes()) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_proj_pool2<1, RADAD_POOL_MAX>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)projpool2_lds_bytes(1)) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_proj_pool2<1, RADAD_POOL_AVG>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)projpool2_lds_bytes(1)) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_proj_pool2<2, RADAD_POOL_MAX>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)projpool2_lds_bytes(2)) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_proj_pool2<2, RADAD_POOL_AVG>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)projpool2_lds_bytes(2)) != hipSuccess ||
+            pp2_set_lds<1, RADAD_POOL_MAX, false>() != hipSuccess || pp2_set_lds<1, RADAD_POOL_MAX, true>() != hipSuccess ||
+            pp2_set_lds<1, RADAD_POOL_AVG, false>() != hipSuccess || pp2_set_lds<1, RADAD_POOL_AVG, true>() != hipSuccess ||
+            pp2_set_lds<2, RADAD_POOL_MAX, false>() != hipSuccess || pp2_set_lds<2, RADAD_POOL_MAX, true>() != hipSuccess ||
+            pp2_set_lds<2, RADAD_POOL_AVG, false>() != hipSuccess || pp2_set_lds<2, RADAD_POOL_AVG, true>() != hipSuccess ||
             hipFuncSetAttribute(reinterpret_cast<const void*>(k_proj_pool<false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)projpool_lds_bytes(8)) != hipSuccess ||
             hipFuncSetAttribute(reinterpret_cast<const void*>(k_proj_pool<false, 16>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1568,13 +1624,15 @@ static int embed_run(radad_embed_t h, const float* wave_dev, int64_t n_clips, in
     // persistent workgroups (one per CU) walk the groups; the next pass's rows are in flight across the current pass's MFMAs
     const unsigned gx = (unsigned)std::min<int64_t>(n_groups, h->n_cus);
     const bool pmax = h->cfg.pool_mode == RADAD_POOL_MAX;
+    const bool onebin = h->nbins == 1;    // levels = [1]: the pooled value stays in a register (k_proj_pool2, ONEBIN)
     if (h->cfg.feat_dim > 256) {
         const dim3 grid(gx, (unsigned)((h->cfg.feat_dim + 511) / 512));
-        if (pmax) hipLaunchKernelGGL((k_proj_pool2<2, RADAD_POOL_MAX>), grid, dim3(PP2_THREADS), projpool2_lds_bytes(2), st, p, (int)n_groups);
-        else hipLaunchKernelGGL((k_proj_pool2<2, RADAD_POOL_AVG>), grid, dim3(PP2_THREADS), projpool2_lds_bytes(2), st, p, (int)n_groups);
+        if (pmax) onebin ? pp2_launch<2, RADAD_POOL_MAX, true>(grid, st, p, (int)n_groups) : pp2_launch<2, RADAD_POOL_MAX, false>(grid, st, p, (int)n_groups);
+        else onebin ? pp2_launch<2, RADAD_POOL_AVG, true>(grid, st, p, (int)n_groups) : pp2_launch<2, RADAD_POOL_AVG, false>(grid, st, p, (int)n_groups);
     } else {
-        if (pmax) hipLaunchKernelGGL((k_proj_pool2<1, RADAD_POOL_MAX>), dim3(gx, 1), dim3(PP2_THREADS), projpool2_lds_bytes(1), st, p, (int)n_groups);
-        else hipLaunchKernelGGL((k_proj_pool2<1, RADAD_POOL_AVG>), dim3(gx, 1), dim3(PP2_THREADS), projpool2_lds_bytes(1), st, p, (int)n_groups);
+        const dim3 grid(gx, 1);
+        if (pmax) onebin ? pp2_launch<1, RADAD_POOL_MAX, true>(grid, st, p, (int)n_groups) : pp2_launch<1, RADAD_POOL_MAX, false>(grid, st, p, (int)n_groups);
+        else onebin ? pp2_launch<1, RADAD_POOL_AVG, true>(grid, st, p, (int)n_groups) : pp2_launch<1, RADAD_POOL_AVG, false>(grid, st, p, (int)n_groups);
     }
     if (!per_clip)                        // pipeline.py:411: mean over each clip's segment vectors, in segment order
         hipLaunchKernelGGL(k_group_mean, dim3((unsigned)n_clips, (unsigned)((out_dim + 255) / 256)), dim3(256), 0, st,
