@@ -265,14 +265,24 @@ int radad_ivf_destroy(radad_ivf_t h);
 int radad_ivf_is_trained(radad_ivf_t h, int* trained);
 int radad_ivf_ntotal(radad_ivf_t h, int64_t* n);
 int radad_ivf_nlist(radad_ivf_t h, int* nlist);
-/* k-means (Lloyd, `niter` iterations; faiss trains its IVF quantiser with 10) on n training rows; synchronous */
+/* k-means (Lloyd, `niter` iterations; faiss trains its IVF quantiser with 10) on n training rows; synchronous.
+ * Initial centroid c is training row (c * n) / nlist (rows repeat when n < nlist).  Every iteration assigns each row to its nearest
+ * centroid -- the float64 argmin, the lower id on a tie: the assignment is a certified flat search -- and replaces every non-empty
+ * list's centroid by the fp32 mean of its rows, summed in insertion order and divided once: within gamma_(m-1) sum|x| / m + u |mean|
+ * of the exact mean for a list of m rows (u = 2^-24, gamma_k = k u / (1 - k u)); an empty list keeps its centroid.  Deterministic.
+ * NON-FINITE ROWS are refused: a training row with a NaN or an infinity has no nearest centroid, and the call returns RADAD_EINVAL
+ * naming the first such row.  The index is then exactly as it was: untrained, or with its previous centroids and quantiser.  With
+ * niter = 0 only the nlist picked rows are read, so only those are checked.  The same holds for radad_ivf_add: the whole batch is
+ * refused (first bad row named), nothing is appended.  faiss differs: it counts such a row in ntotal and puts it in no list. */
 int radad_ivf_train(radad_ivf_t h, const float* rows_dev, int64_t n, int niter, void* stream);
 /* install centroids computed elsewhere ([nlist, dim] fp32) instead of training; only on an empty index */
 int radad_ivf_set_centroids(radad_ivf_t h, const float* centroids_dev, void* stream);
 int radad_ivf_centroids(radad_ivf_t h, float* out_dev, void* stream);
 /* list of every stored row, in insertion order (host int32 [ntotal]) */
 int radad_ivf_assignments_host(radad_ivf_t h, int32_t* out_host, int64_t cap);
-int radad_ivf_add(radad_ivf_t h, const float* rows_dev, int64_t n, void* stream);               /* synchronous */
+/* synchronous.  Every row goes to the list of its nearest centroid (float64 argmin, the lower id on a tie), whatever the batch it
+ * arrives in.  A batch with a non-finite row is refused as a whole (RADAD_EINVAL, see radad_ivf_train). */
+int radad_ivf_add(radad_ivf_t h, const float* rows_dev, int64_t n, void* stream);
 int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int nprobe, float* out_dist_dev,
                      int64_t* out_idx_dev, void* stream);      /* asynchronous on `stream` (the (query, probe) pairs are grouped by list on
                                                                     the device); only the first search after an add rebuilds the list layout

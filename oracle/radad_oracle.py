@@ -279,6 +279,44 @@ def ivf_search(db, assign, centroids, q, k, nprobe):
     return D, I
 
 
+def kmeans_init(rows, nlist):
+    """Initial centroids of radad_ivf_train: training row (c * n) // nlist for list c (rows repeat when n < nlist)."""
+    rows = np.asarray(rows)
+    n = len(rows)
+    return rows[(np.arange(nlist, dtype=np.int64) * n) // nlist].copy()
+
+
+def kmeans_assign(rows, cent, knn_fn=None):
+    """List of every row: its nearest centroid by squared L2 in float64, the lower id on a tie.  int32 [n].
+    knn_fn(db, q, k) -> (dist, idx): a float64 brute force with (distance, id) order (the tests pass the C oracle, conftest.c_knn);
+    default: knn() above, a few thousand rows at a time (the broadcast form over all rows needs n x nlist x dim float64)."""
+    rows = np.asarray(rows, np.float32)
+    cent = np.asarray(cent, np.float32)
+    if knn_fn is not None:
+        return np.asarray(knn_fn(cent, rows, 1)[1][:, 0], np.int32)
+    out = np.empty(len(rows), np.int32)
+    for s in range(0, len(rows), 2048):
+        out[s:s + 2048] = knn(cent, rows[s:s + 2048], 1, "L2", chunk=1024)[1][:, 0]
+    return out
+
+
+def kmeans_step(rows, cent, knn_fn=None):
+    """One Lloyd step from `cent`: (new centroids float64 [nlist, dim], assignments int32 [n], counts int64 [nlist]).  A list's new
+    centroid is the float64 mean of its rows; an empty list keeps its centroid's value exactly (float32 -> float64 is exact)."""
+    rows = np.asarray(rows, np.float32)
+    cent = np.asarray(cent, np.float32)
+    assign = kmeans_assign(rows, cent, knn_fn)
+    nlist = len(cent)
+    counts = np.bincount(assign, minlength=nlist).astype(np.int64)
+    new = cent.astype(np.float64)
+    order = np.argsort(assign, kind="stable")
+    start = np.concatenate([[0], np.cumsum(counts)])
+    x = rows[order].astype(np.float64)
+    for c in np.flatnonzero(counts):
+        new[c] = x[start[c]:start[c + 1]].sum(0) / counts[c]
+    return new, assign, counts
+
+
 def rank_gaps(dist_sorted):
     """Minimum gap between consecutive ranks per query (used to prove 'bit-exact indices' is testable)."""
     d = np.asarray(dist_sorted, np.float64)

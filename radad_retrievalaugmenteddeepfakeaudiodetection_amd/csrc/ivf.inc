@@ -768,17 +768,38 @@ static void ivf_wait_searches(radad_ivf_t h) {
     h->have_last = false;
 }
 
-// assignment of n rows to their nearest centroid -> host ints
-static int ivf_assign(radad_ivf_t h, const float* rows_dev, int64_t n, std::vector<int>& out, hipStream_t st) {
+// assignment of n rows to their nearest centroid (a flat k = 1 search of `quant`) -> host ints.  *bad_row = -1, or the first row
+// the quantiser found no centroid for: id outside [0, nlist) (a non-finite query comes back with id -1) or a distance that is not
+// finite (the float64 re-score of a row with a NaN or an infinity in it, whatever id the scan gave it).  The callers refuse the
+// whole batch then: such a row has no list.
+static int ivf_assign(radad_ivf_t h, radad_knn_t quant, const float* rows_dev, int64_t n, std::vector<int>& out, int64_t* bad_row, hipStream_t st) {
     int rc;
     if ((rc = h->ws_a.ensure((size_t)n * sizeof(float)))) return rc;
     if ((rc = h->ws_b.ensure((size_t)n * sizeof(int64_t)))) return rc;
-    if ((rc = radad_knn_search(h->quant, rows_dev, n, 1, (float*)h->ws_a.p, (int64_t*)h->ws_b.p, st))) return rc;
+    if ((rc = radad_knn_search(quant, rows_dev, n, 1, (float*)h->ws_a.p, (int64_t*)h->ws_b.p, st))) return rc;
     std::vector<int64_t> ids((size_t)n);
+    std::vector<float> dist((size_t)n);
     RADAD_HIP_CHECK(hipMemcpyAsync(ids.data(), h->ws_b.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    RADAD_HIP_CHECK(hipMemcpyAsync(dist.data(), h->ws_a.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
     RADAD_HIP_CHECK(hipStreamSynchronize(st));
     out.resize((size_t)n);
-    for (int64_t i = 0; i < n; ++i) out[(size_t)i] = (int)ids[(size_t)i];
+    *bad_row = -1;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t id = ids[(size_t)i];
+        if (*bad_row < 0 && (id < 0 || id >= h->nlist || !std::isfinite(dist[(size_t)i]))) *bad_row = i;
+        out[(size_t)i] = (int)id;
+    }
+    return RADAD_OK;
+}
+
+// a flat L2 store over the [nlist, dim] centroids at `cent`
+static int ivf_make_quantizer(radad_ivf_t h, const float* cent, hipStream_t st, radad_knn_t* out) {
+    radad_knn_t q = nullptr;
+    int rc = radad_knn_create(h->dim, RADAD_METRIC_L2, h->device, 0, &q);
+    if (rc) return rc;
+    q->owned_serial = true;      // searched under this index's lock, in the stream order this index keeps: no event of its own per search
+    if ((rc = radad_knn_add(q, cent, h->nlist, st))) { radad_knn_destroy(q); return rc; }
+    *out = q;
     return RADAD_OK;
 }
 
@@ -786,20 +807,20 @@ static int ivf_assign(radad_ivf_t h, const float* rows_dev, int64_t n, std::vect
 static int ivf_load_quantizer(radad_ivf_t h, hipStream_t st) {
     if (h->quant) radad_knn_destroy(h->quant);
     h->quant = nullptr;
-    int rc = radad_knn_create(h->dim, RADAD_METRIC_L2, h->device, 0, &h->quant);
-    if (rc) return rc;
-    h->quant->owned_serial = true;      // searched under this index's lock, in the stream order this index keeps: no event of its own per search
-    return radad_knn_add(h->quant, h->centroids, h->nlist, st);
+    return ivf_make_quantizer(h, h->centroids, st, &h->quant);
 }
 
-// stable counting sort of `assign` -> perm (position -> source index) and offsets
-static void ivf_sort(const std::vector<int>& assign, int nlist, std::vector<int64_t>& perm, std::vector<int>& off) {
+// stable counting sort of `assign` -> perm (position -> source index) and offsets.  false, with nothing indexed, when a list id lies
+// outside [0, nlist): the callers refuse such rows before they get here, and an id that slipped through must not index cur / off.
+static bool ivf_sort(const std::vector<int>& assign, int nlist, std::vector<int64_t>& perm, std::vector<int>& off) {
+    for (int a : assign) if ((unsigned)a >= (unsigned)nlist) return false;
     off.assign((size_t)nlist + 1, 0);
     for (int a : assign) off[(size_t)a + 1]++;
     for (int l = 0; l < nlist; ++l) off[(size_t)l + 1] += off[(size_t)l];
     std::vector<int> cur(off.begin(), off.end() - 1);
     perm.resize(assign.size());
     for (size_t i = 0; i < assign.size(); ++i) perm[(size_t)cur[(size_t)assign[i]]++] = (int64_t)i;
+    return true;
 }
 
 // rebuild the list-major layout after adds
@@ -807,7 +828,7 @@ static int ivf_prepare(radad_ivf_t h, hipStream_t st) {
     if (!h->dirty) return RADAD_OK;
     const int64_t n = (int64_t)h->assign.size();
     std::vector<int64_t> perm;
-    ivf_sort(h->assign, h->nlist, perm, h->loff_host);
+    if (!ivf_sort(h->assign, h->nlist, perm, h->loff_host)) { radad_set_error("the index holds a row without a list"); return RADAD_ESTATE; }
     int rc;
     if ((rc = h->lrows.ensure((size_t)n * h->dim * sizeof(float)))) return rc;
     if ((rc = h->lnorm.ensure((size_t)n * sizeof(float)))) return rc;
@@ -903,13 +924,9 @@ int radad_ivf_nlist(radad_ivf_t h, int* nlist) { RADAD_REQUIRE(h && nlist, "NULL
 
 // Lloyd iterations on the device (assignment = flat L2 scan over the centroids, update = deterministic per-list mean of
 // the list-sorted rows).  Initial centroids: n_train / nlist-strided rows.  Empty clusters keep their centroid.
-int radad_ivf_train(radad_ivf_t h, const float* rows_dev, int64_t n, int niter, void* stream) {
-    RADAD_REQUIRE(h && rows_dev, "radad_ivf_train: NULL argument");
-    RADAD_REQUIRE(n >= 1 && niter >= 0, "radad_ivf_train: need at least one training row");
-    std::lock_guard<std::mutex> lk(h->mu);
-    ivf_wait_searches(h);
-    DeviceGuard g(h->device);
-    hipStream_t st = (hipStream_t)stream;
+// The iterations run on a centroid buffer and a quantiser of their own (`cent`, *quant_out); radad_ivf_train installs them when all
+// of it went well, so a refused training set leaves the index as it was.
+static int ivf_train_into(radad_ivf_t h, const float* rows_dev, int64_t n, int niter, hipStream_t st, float* cent, radad_knn_t* quant_out) {
     int rc;
     // initial centroids: row (c * n) / nlist (repeats when n < nlist, as good as any for a degenerate training set)
     {
@@ -918,16 +935,25 @@ int radad_ivf_train(radad_ivf_t h, const float* rows_dev, int64_t n, int niter, 
         if ((rc = h->ws_b.ensure((size_t)std::max<int64_t>(n, h->nlist) * sizeof(int64_t)))) return rc;
         RADAD_HIP_CHECK(hipMemcpyAsync(h->ws_b.p, pick.data(), pick.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_gather_rows<float>, dim3((unsigned)ceil_div64(h->nlist, 4)), dim3(256), 0, st, rows_dev,
-                           (const int64_t*)h->ws_b.p, (int64_t)h->nlist, n, (int64_t)0, h->dim, h->centroids);
+                           (const int64_t*)h->ws_b.p, (int64_t)h->nlist, n, (int64_t)0, h->dim, cent);
         RADAD_HIP_CHECK(hipGetLastError());
+        // the picked rows must be finite whatever niter is: with niter = 0 they are the centroids, and no assignment looks at them
+        std::vector<float> host((size_t)h->nlist * h->dim);
+        RADAD_HIP_CHECK(hipMemcpyAsync(host.data(), cent, host.size() * sizeof(float), hipMemcpyDeviceToHost, st));
         RADAD_HIP_CHECK(hipStreamSynchronize(st));
+        for (size_t i = 0; i < host.size(); ++i)
+            RADAD_REQUIRE(std::isfinite(host[i]), "radad_ivf_train: training row %lld (the initial centroid of list %lld) is not finite",
+                          (long long)pick[i / (size_t)h->dim], (long long)(i / (size_t)h->dim));
     }
     std::vector<int> assign, off;
     std::vector<int64_t> perm;
     for (int it = 0; it < niter; ++it) {
-        if ((rc = ivf_load_quantizer(h, st))) return rc;
-        if ((rc = ivf_assign(h, rows_dev, n, assign, st))) return rc;
-        ivf_sort(assign, h->nlist, perm, off);
+        if (*quant_out) { radad_knn_destroy(*quant_out); *quant_out = nullptr; }
+        if ((rc = ivf_make_quantizer(h, cent, st, quant_out))) return rc;
+        int64_t bad = -1;
+        if ((rc = ivf_assign(h, *quant_out, rows_dev, n, assign, &bad, st))) return rc;
+        RADAD_REQUIRE(bad < 0, "radad_ivf_train: training row %lld is not finite (no nearest centroid)", (long long)bad);
+        RADAD_REQUIRE(ivf_sort(assign, h->nlist, perm, off), "radad_ivf_train: a training row has no list");
         if ((rc = h->ws_c.ensure((size_t)n * h->dim * sizeof(float)))) return rc;
         if ((rc = h->ws_b.ensure((size_t)n * sizeof(int64_t)))) return rc;
         if ((rc = h->loff.ensure((size_t)(h->nlist + 1) * sizeof(int)))) return rc;
@@ -936,13 +962,41 @@ int radad_ivf_train(radad_ivf_t h, const float* rows_dev, int64_t n, int niter, 
         hipLaunchKernelGGL(k_gather_rows<float>, dim3((unsigned)ceil_div64(n, 4)), dim3(256), 0, st, rows_dev, (const int64_t*)h->ws_b.p,
                            n, n, (int64_t)0, h->dim, (float*)h->ws_c.p);
         hipLaunchKernelGGL(k_centroid_update, dim3((unsigned)h->nlist, (unsigned)((h->dim + 255) / 256)), dim3(256), 0, st,
-                           (const float*)h->ws_c.p, (const int*)h->loff.p, h->dim, h->centroids);
+                           (const float*)h->ws_c.p, (const int*)h->loff.p, h->dim, cent);
         RADAD_HIP_CHECK(hipGetLastError());
         RADAD_HIP_CHECK(hipStreamSynchronize(st));
     }
-    if ((rc = ivf_load_quantizer(h, st))) return rc;
-    h->trained = true;
-    return RADAD_OK;
+    if (*quant_out) { radad_knn_destroy(*quant_out); *quant_out = nullptr; }
+    return ivf_make_quantizer(h, cent, st, quant_out);
+}
+
+int radad_ivf_train(radad_ivf_t h, const float* rows_dev, int64_t n, int niter, void* stream) {
+    RADAD_REQUIRE(h && rows_dev, "radad_ivf_train: NULL argument");
+    RADAD_REQUIRE(n >= 1 && niter >= 0, "radad_ivf_train: need at least one training row");
+    std::lock_guard<std::mutex> lk(h->mu);
+    ivf_wait_searches(h);
+    DeviceGuard g(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t cbytes = (size_t)h->nlist * h->dim * sizeof(float);
+    float* cent = nullptr;
+    if (hipMalloc((void**)&cent, cbytes) != hipSuccess) { (void)hipGetLastError(); radad_set_error("hipMalloc of %zu bytes failed", cbytes); return RADAD_ENOMEM; }
+    radad_knn_t quant = nullptr;
+    int rc = ivf_train_into(h, rows_dev, n, niter, st, cent, &quant);
+    if (!rc && (hipMemcpyAsync(h->centroids, cent, cbytes, hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) {
+        (void)hipGetLastError();
+        radad_set_error("radad_ivf_train: copying the centroids failed");
+        rc = RADAD_EHIP;
+    }
+    if (!rc) {
+        if (h->quant) radad_knn_destroy(h->quant);
+        h->quant = quant;
+        quant = nullptr;
+        h->trained = true;
+    }
+    if (quant) radad_knn_destroy(quant);
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(cent);
+    return rc;
 }
 
 int radad_ivf_set_centroids(radad_ivf_t h, const float* centroids_dev, void* stream) {
@@ -981,9 +1035,12 @@ int radad_ivf_add(radad_ivf_t h, const float* rows_dev, int64_t n, void* stream)
     ivf_wait_searches(h);
     DeviceGuard g(h->device);
     hipStream_t st = (hipStream_t)stream;
+    // the assignment comes first: a batch that is refused has appended nothing
     std::vector<int> a;
-    int rc = ivf_assign(h, rows_dev, n, a, st);
+    int64_t bad = -1;
+    int rc = ivf_assign(h, h->quant, rows_dev, n, a, &bad, st);
     if (rc) return rc;
+    RADAD_REQUIRE(bad < 0, "radad_ivf_add: row %lld of the batch is not finite (no nearest centroid); nothing was added", (long long)bad);
     if ((rc = radad_knn_add(h->flat, rows_dev, n, st))) return rc;
     h->assign.insert(h->assign.end(), a.begin(), a.end());
     h->dirty = true;

@@ -5,6 +5,7 @@ oracle restricted to the probed lists."""
 import numpy as np
 import pytest
 
+from conftest import c_knn
 from oracle import radad_oracle as O
 from oracle import synth
 
@@ -19,7 +20,7 @@ def _clustered(n, dim, n_clusters, seed):
 
 @pytest.mark.parametrize("n,dim,nlist,nq,k,nprobe", [(20000, 64, 64, 100, 5, 8), (30000, 512, 128, 300, 15, 32),
                                                      (5000, 96, 64, 3, 10, 64), (8000, 5376, 64, 20, 15, 4)])
-def test_ivf_search_matches_oracle(gpu, n, dim, nlist, nq, k, nprobe):
+def test_ivf_search_matches_oracle(gpu, knn_oracle_lib, n, dim, nlist, nq, k, nprobe):
     import radad_retrievalaugmenteddeepfakeaudiodetection_amd as R
     db = _clustered(n, dim, 50, 5001)
     q = _clustered(nq, dim, 50, 5003)
@@ -32,11 +33,8 @@ def test_ivf_search_matches_oracle(gpu, n, dim, nlist, nq, k, nprobe):
     assert idx.ntotal == n
     cent, assign = idx.centroids(), idx.assignments()
     assert cent.shape == (nlist, dim) and assign.shape == (n,) and np.isfinite(cent).all()
-    # every row sits in the list of its nearest centroid (ties aside)
-    d2 = ((db[:2000, None, :].astype(np.float64) - cent[None].astype(np.float64)) ** 2).sum(-1) if dim <= 512 else None
-    if d2 is not None:
-        best = d2.min(1)
-        np.testing.assert_allclose(d2[np.arange(2000), assign[:2000]], best, rtol=1e-5, atol=1e-5)
+    # every row sits in the list of its nearest centroid: the float64 argmin (the lower id on a tie), at every dim
+    np.testing.assert_array_equal(assign, O.kmeans_assign(db, cent, lambda c, x, kk: c_knn(knn_oracle_lib, c, x, kk, "L2")))
     idx.nprobe = nprobe
     D, I = idx.search(q, k)
     od, oi = O.ivf_search(db, assign, cent, q, k, nprobe)
