@@ -251,6 +251,37 @@ int radad_filter_topk(const float* in_dist_dev, const int64_t* in_idx_dev, int64
                       const int64_t* row_tags_dev, int64_t ntotal, int64_t id_base, const int64_t* excl_sorted_dev,
                       int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, int device, void* stream);
 
+/* Exclusion-aware search: per query the k nearest rows whose tag is NOT in the exclusion set, however many excluded rows precede
+ * them.  The reference searches K + 10 rows (pipeline.py:478), drops the hits with an excluded basename (:491-509) and pads with zero
+ * vectors / label 0 / NaN when fewer than K survive (:511-515) -- radad_knn_search_ex + radad_filter_topk reproduce exactly that, and
+ * stay the default: a query with more than 10 excluded rows in front of its K-th admissible neighbour (a batch of clips of few
+ * speakers excluding each other, :463; the training_file_ids mode, :500-502, where most of the store is excluded) gets padding
+ * although admissible neighbours exist.  This call returns them, with the contract of radad_knn_search_f64:
+ *   result      the k best admissible rows ordered by (float64 distance, id); out_dist the correctly rounded fp32 distance, out_key
+ *               (may be NULL) the float64 key; slots beyond the number of admissible rows hold id -1, distance NaN and key NaN
+ *               (radad_filter_topk's padding, not the +-inf of the plain searches)
+ *   fast pass   the certified search at k_fetch (clamped to ntotal), every scan path as it is
+ *   certificate per query, on the device: the k_fetch hits hold k admissible rows (any admissible row outside the list ranks behind
+ *               the whole list), or the list is all the store has
+ *   exact pass  float64 brute force over the admissible rows for the queries the certificate cannot prove, driven from the device
+ *               (no host round trip; an excluded row costs one bit of a per-call bitmap).  It streams the admissible rows once per
+ *               group of <= 8 such queries -- far more work per query than the certified search spends on one (its time per listed
+ *               query has not been measured yet, profiles/README.md).
+ *               So choose k_fetch for the crowding you expect: k + (the most excluded rows that can precede a query's k-th
+ *               admissible neighbour), e.g. k + clips per speaker in a batch; up to 128 the fast pass stays on the f16 scans.
+ * row_tags_dev [ntotal] int64 indexed by id - id_base; excl_sorted_dev [n_excl] int64 ASCENDING (the caller's contract, not checked);
+ * both may be NULL only when n_excl == 0.  k in [1, RADAD_KNN_MAX_K], k_fetch in [k, RADAD_KNN_MAX_K]; anything else, or a handle
+ * with a begun search, is RADAD_EINVAL; an empty store RADAD_ESTATE.  Stream-ordered and serialised like every search;
+ * radad_knn_last_launch, _last_certificate, _tuning_info and the like describe the fast pass only. */
+int radad_knn_search_excl(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, int k_fetch,
+                          const int64_t* row_tags_dev /*[ntotal], indexed by id - id_base*/,
+                          const int64_t* excl_sorted_dev /*[n_excl] ascending, NULL when n_excl == 0*/, int64_t n_excl,
+                          float* out_dist_dev /*[nq,k]*/, int64_t* out_idx_dev /*[nq,k]*/, double* out_key_dev /*[nq,k] or NULL*/,
+                          void* stream);
+/* batch size of the most recent radad_knn_search_excl on the handle (n_queries may be NULL) and how many of its queries took the
+ * exact pass; synchronises with that search.  0 / 0 before the first one. */
+int radad_knn_last_excl(radad_knn_t h, int64_t* n_queries, int* n_exact);
+
 /* ------------------------------------------------------------------------------------------------
  * Inverted-file flat index: faiss.IndexIVFFlat(IndexFlatL2 quantiser, d, nlist, METRIC_L2), the reference's optional
  * `vector_db_index_type == "IVF"` (vector_database.py:65-70 create with nlist = max(64, ivf_nlist), :124-128 train on the

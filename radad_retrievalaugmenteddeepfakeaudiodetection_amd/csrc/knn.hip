@@ -1906,6 +1906,13 @@ static int64_t knn_exact_slots(int64_t nq, int k, int group) {
     return std::min<int64_t>(nq, std::max<int64_t>(group, (int64_t)(KX_PART_BUDGET / per_q) / group * group));
 }
 
+// queries per workgroup of the exact kernel: the group's queries (<= 64 KB) and its KX_WAVES lists of k per query share the LDS
+// (the lists shrink it at large k: k = 1024 takes one query per workgroup, 98 KB of lists)
+static int knn_exact_group(int dim, int k) {
+    return (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(8, (size_t)(64 * 1024) / ((size_t)dim * 4)),
+                                                     (KX_LDS_MAX - 16) / ((size_t)dim * 4 + (size_t)KX_WAVES * k * 12)));
+}
+
 struct ExactParams {
     const void* db = nullptr; int db_f16 = 0;
     const float* q = nullptr;  // [nq][dim] fp32 queries (normalised for cosine)
@@ -1922,6 +1929,9 @@ struct ExactParams {
     int stamp = 0;             // ... this value in host_stats[6] (the search's sequence number + 1): the host reads a report only when its stamp is there
     int nq_report = 0;         // the search's batch size (travels with the report: the host may be many searches ahead when it reads it)
     int* arrive = nullptr;     // [query groups] arrival counters of the slices (zero between launches: the last arrival resets its own)
+    // the row-filtered instantiation only (k_exact_scan_excl, radad_knn_search_excl): bit (row & 63) of admit[row >> 6] set = the row
+    // takes part; unfilled result slots are -1 / NaN there (the padding of radad_filter_topk) instead of -1 / +-inf
+    const unsigned long long* admit = nullptr;
 };
 static_assert(std::is_trivially_copyable_v<ExactParams>, "kernel argument");
 
@@ -1932,9 +1942,13 @@ __device__ __forceinline__ void kx_wave_sync() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+template <bool FILTERED>
 __device__ __forceinline__ void exact_merge_slot(const ExactParams& p, int slot, int lane);
 
-__global__ __launch_bounds__(KX_THREADS) void k_exact_scan(ExactParams p) {
+// FILTERED is a compile-time parameter: the unfiltered instantiation (k_exact_scan) is the code it was before the filter existed;
+// k_exact_scan_excl scans the rows a bitmap admits (radad_knn_search_excl): the float64 brute force among the rows not excluded
+template <bool FILTERED>
+__global__ __launch_bounds__(KX_THREADS) void k_exact_scan_any(ExactParams p) {
     const int count = min(*p.count - p.slot0, p.nslots);       // this launch's queries
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && p.host_stats) {
         *reinterpret_cast<volatile int*>(&p.host_stats[6]) = 0;          // the slot is being rewritten: no report until the new stamp is there
@@ -1968,7 +1982,14 @@ __global__ __launch_bounds__(KX_THREADS) void k_exact_scan(ExactParams p) {
         int* wId = sId + (size_t)wave * G * p.k;
         for (int i = lane; i < G * p.k; i += 64) { wKey[i] = -INFINITY; wId[i] = IDX_SENTINEL; }
         __syncthreads();
+        int64_t adm_w = -1;                               // (FILTERED) the bitmap word in hand: one load per 64 rows of the slice
+        unsigned long long adm = 0ull;
         for (int64_t row = r_begin + wave; row < r_end; row += KX_WAVES) {
+            if (FILTERED) {
+                // wave-uniform, before any load of the row: an excluded row costs this bit and nothing else
+                if ((row >> 6) != adm_w) { adm_w = row >> 6; adm = p.admit[adm_w]; }
+                if (!__builtin_amdgcn_readfirstlane((int)((adm >> (row & 63)) & 1ull))) continue;
+            }
             double part[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) part[j] = 0.0;
@@ -2062,12 +2083,16 @@ __global__ __launch_bounds__(KX_THREADS) void k_exact_scan(ExactParams p) {
         __syncthreads();
         if (s_last) {                                    // (workgroup-uniform)
             __threadfence();                             // acquire
-            if (wave < ng) exact_merge_slot(p, g * G + wave, lane);
+            if (wave < ng) exact_merge_slot<FILTERED>(p, g * G + wave, lane);
         }
     }
 }
 
+constexpr auto k_exact_scan = k_exact_scan_any<false>;
+constexpr auto k_exact_scan_excl = k_exact_scan_any<true>;
+
 // one wave: merge the KX_SLICES partial lists of this launch's rejected-query slot `slot`, overwrite the query's output rows
+template <bool FILTERED>
 __device__ __forceinline__ void exact_merge_slot(const ExactParams& p, int slot, int lane) {
     static_assert(KX_SLICES == 64, "one list per lane");
     {
@@ -2088,7 +2113,8 @@ __device__ __forceinline__ void exact_merge_slot(const ExactParams& p, int slot,
         if (bi != IDX_SENTINEL && hi == bi) ++pos;          // ids are unique: exactly one lane advances
         if (lane == 0) {
             const bool none = bi == IDX_SENTINEL;
-            const double d = none ? (p.l2 ? (double)INFINITY : -(double)INFINITY) : (p.l2 ? -bk : bk);
+            const double pad = FILTERED ? (double)__int_as_float(0x7fc00000) : (p.l2 ? (double)INFINITY : -(double)INFINITY);
+            const double d = none ? pad : (p.l2 ? -bk : bk);
             p.out_dist[q * p.k + o] = (float)d;
             p.out_idx[q * p.k + o] = none ? -1 : (int64_t)bi + p.id_base;
             if (p.out_key) p.out_key[q * p.k + o] = d;
@@ -2262,6 +2288,74 @@ __global__ __launch_bounds__(256) void k_filter_topk(const float* __restrict__ i
     }
 }
 
+// ---- exclusion-aware search (radad_knn_search_excl): the exact top-k among the rows whose tag is not excluded ----------------------
+// t in the ascending exclusion set?  (the binary search of k_filter_topk)
+__device__ __forceinline__ bool excl_has(const int64_t* __restrict__ excl, int64_t n_excl, int64_t t) {
+    int64_t lo = 0, hi = n_excl;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (excl[mid] < t) lo = mid + 1; else hi = mid;
+    }
+    return lo < n_excl && excl[lo] == t;
+}
+
+// Certificate + compaction: one wave per query walks the query's k_in exact hits (the certified search at k_fetch: ordered by
+// (float64 distance, id), unfilled slots id -1) in strips of 64 and keeps, in order, the first k_keep whose tag is not excluded;
+// the rest of the row is padded with id -1 / NaN.  The row is PROVED -- the exact top-k_keep among the admissible rows -- when
+// it holds k_keep survivors (an admissible row outside the list ranks behind the whole list), or when the list is all the store
+// has (an unfilled slot, or `whole`: the caller asked for more hits than the store has rows and the list was cut to them).
+// Any other query is appended to sel[] (count[0], device scope) for the row-filtered exact pass, which overwrites its row.
+__global__ __launch_bounds__(256) void k_excl_compact(const float* __restrict__ in_dist, const int64_t* __restrict__ in_idx,
+                                                      const double* __restrict__ in_key, int64_t nq, int k_in, int k_keep, int whole,
+                                                      const int64_t* __restrict__ tags, int64_t ntotal, int64_t id_base,
+                                                      const int64_t* __restrict__ excl, int64_t n_excl, float* __restrict__ out_dist,
+                                                      int64_t* __restrict__ out_idx, double* __restrict__ out_key,
+                                                      int* __restrict__ count, int* __restrict__ sel) {
+    const int lane = threadIdx.x & 63;
+    const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= nq) return;                                        // (wave-uniform)
+    int kept = 0;
+    bool unfilled = false;
+    for (int s0 = 0; s0 < k_in && kept < k_keep; s0 += 64) {
+        const int j = s0 + lane;
+        int64_t id = -1;
+        bool keep = false;
+        if (j < k_in) {
+            id = in_idx[q * k_in + j];
+            const int64_t r = id - id_base;
+            keep = id >= 0 && r >= 0 && r < ntotal;
+            if (keep && n_excl > 0) keep = !excl_has(excl, n_excl, tags[r]);
+        }
+        unfilled |= __ballot(j < k_in && id < 0) != 0ull;
+        const unsigned long long m = __ballot(keep);
+        const int pos = kept + __popcll(m & ((1ull << lane) - 1ull));
+        if (keep && pos < k_keep) {
+            out_idx[q * k_keep + pos] = id;
+            out_dist[q * k_keep + pos] = in_dist[q * k_in + j];
+            if (out_key) out_key[q * k_keep + pos] = in_key[q * k_in + j];
+        }
+        kept += __popcll(m);
+    }
+    kept = min(kept, k_keep);
+    for (int o = kept + lane; o < k_keep; o += 64) {
+        out_idx[q * k_keep + o] = -1;
+        out_dist[q * k_keep + o] = __int_as_float(0x7fc00000);   // NaN, as pipeline.py:515
+        if (out_key) out_key[q * k_keep + o] = (double)__int_as_float(0x7fc00000);
+    }
+    if (lane == 0 && kept < k_keep && !unfilled && !whole) sel[atomicAdd(count, 1)] = (int)q;
+}
+
+// The admission bitmap of the row-filtered exact pass: bit (r & 63) of admit[r >> 6] = row r's tag is not excluded.  One thread per
+// row, one 64-bit word per wave.  Workgroups leave at once when no query was listed (the usual call).
+__global__ __launch_bounds__(256) void k_excl_bitmap(const int64_t* __restrict__ tags, int64_t ntotal, const int64_t* __restrict__ excl,
+                                                     int64_t n_excl, const int* __restrict__ count, unsigned long long* __restrict__ admit) {
+    if (*count == 0) return;
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;          // (ntotal rounded up to whole waves: every lane ballots)
+    const bool ok = r < ntotal && !excl_has(excl, n_excl, tags[r]);
+    const unsigned long long m = __ballot(ok);
+    if ((threadIdx.x & 63) == 0 && (r >> 6) < ((ntotal + 63) >> 6)) admit[r >> 6] = m;
+}
+
 // out[r] = the k-th largest of in[r][0..m) (NaN ranks lowest).  One wave per row, a lane holds up to KTH_PER_LANE values; k - 1 rounds
 // of "wave-wide maximum, its first holder drops it".  The sharded search's bound: m = G k lower bounds per query.
 constexpr int KTH_PER_LANE = 20;         // m <= 1280 (8 shards x k = 128, or 40 x 32)
@@ -2376,6 +2470,11 @@ struct radad_knn_s {
     int64_t kacc_tiles = 0;
     int* xarrive = nullptr;      // exact pass: arrival counters of the query groups (zero between launches)
     int64_t xarrive_cap = 0;
+    // radad_knn_search_excl: a workspace of its own beside `ws` (which the fast pass inside the call may re-allocate): the fast pass's
+    // k_fetch lists | listed-query counter | listed queries | admission bitmap | the filtered exact pass's partial lists
+    void* excl_ws = nullptr;
+    size_t excl_ws_bytes = 0, excl_o_count = 0;
+    int64_t last_excl_nq = 0;    // batch size of the most recent exclusion-aware search (radad_knn_last_excl)
     double* rs_key = nullptr;    // k_refine_small: [SQ_NQ][KNN_CERT_CAP] float64 keys of the candidates, where the query's workgroups meet
     int* rs_count = nullptr;     // ... and [SQ_NQ] arrival counters (zero between launches)
     int uniform_e = HI_E_PER_ROW; // one power-of-two scale 2^e for every row of the plane (rows of one magnitude), or HI_E_PER_ROW
@@ -2775,6 +2874,7 @@ int radad_knn_destroy(radad_knn_t h) {
         if (h->kacc) (void)hipFree(h->kacc);
         if (h->kflag) (void)hipFree(h->kflag);
         if (h->xarrive) (void)hipFree(h->xarrive);
+        if (h->excl_ws) (void)hipFree(h->excl_ws);
         if (h->rs_key) (void)hipFree(h->rs_key);
         if (h->rs_count) (void)hipFree(h->rs_count);
         if (h->host_count) (void)hipHostFree(h->host_count);
@@ -3152,9 +3252,7 @@ static int knn_plan_scan(radad_knn_t h, int64_t nq, int k, int margin, hipStream
     // (a handle that has widened its candidate buffers -- cap_boost: a store whose rows crowd within 2 eps of the k-th best -- also
     // re-ranks four times as many: the fp32 funnel in front of the float64 re-score takes them at ~2 KB of row reads each)
     p.cap = dense ? k + KNN_CERT_EXTRA : std::max(k + KNN_CERT_EXTRA, KNN_CERT_CAP * (use_hi ? h->cap_boost : 1));
-    // (the group's lists shrink it at large k: k = 1024 takes one query per workgroup, 98 KB of lists)
-    p.xgroup = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(8, (size_t)(64 * 1024) / ((size_t)h->dim * 4)),
-                                                         (KX_LDS_MAX - 16) / ((size_t)h->dim * 4 + (size_t)KX_WAVES * k * 12)));
+    p.xgroup = knn_exact_group(h->dim, k);
     p.hi_q = use_hi || smallq_hi;
     p.mu = (p.hi_q && !h->f16) ? h->cmu : nullptr;
     p.biased = p.hi_q && (p.l2 || p.mu);
@@ -3635,6 +3733,21 @@ static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* glo
     return RADAD_OK;
 }
 
+// one search on a handle whose mutex the caller holds; *ctx_out (optional): what the search that ran prepared (its queries)
+static int knn_search_locked(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int margin, float* out_dist_dev,
+                             int64_t* out_idx_dev, double* out_key_dev, hipStream_t st, SearchCtx* ctx_out) {
+    for (int attempt = 0;; ++attempt) {       // (at most: plane re-decided, buffers widened, fp32 kernels)
+        SearchCtx c;
+        int rc = knn_search_phase1(h, q_in, q_dtype, nq, k, margin, nullptr, st, &c);
+        if (rc) return rc;
+        rc = knn_search_phase2(h, c, nullptr, attempt < 3, out_dist_dev, out_idx_dev, out_key_dev, st);
+        if (rc != RADAD_RETRY_INTERNAL) {
+            if (ctx_out) *ctx_out = c;
+            return rc;
+        }
+    }
+}
+
 static int knn_search_core(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int margin, float* out_dist_dev,
                            int64_t* out_idx_dev, double* out_key_dev, void* stream) {
     RADAD_REQUIRE(h, "NULL handle");
@@ -3645,13 +3758,77 @@ static int knn_search_core(radad_knn_t h, const void* q_in, int q_dtype, int64_t
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
     RADAD_REQUIRE(!h->pending.valid, "radad_knn_search: a radad_knn_search_begin on this handle has not been finished");
-    for (int attempt = 0;; ++attempt) {       // (at most: plane re-decided, buffers widened, fp32 kernels)
-        SearchCtx c;
-        int rc = knn_search_phase1(h, q_in, q_dtype, nq, k, margin, nullptr, (hipStream_t)stream, &c);
-        if (rc) return rc;
-        rc = knn_search_phase2(h, c, nullptr, attempt < 3, out_dist_dev, out_idx_dev, out_key_dev, (hipStream_t)stream);
-        if (rc != RADAD_RETRY_INTERNAL) return rc;
+    return knn_search_locked(h, q_in, q_dtype, nq, k, margin, out_dist_dev, out_idx_dev, out_key_dev, (hipStream_t)stream, nullptr);
+}
+
+// ---- exclusion-aware search ---------------------------------------------------------------------------------------------------------
+// fast pass = the certified search at k_fetch (every scan path, float64 keys) -> k_excl_compact: certificate per query, results of the
+// proved ones -> k_exact_scan_excl for the listed ones, sized and driven by the device-side count like the exact pass of any search.
+static int knn_search_excl_locked(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* tags,
+                                  const int64_t* excl, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
+                                  hipStream_t st) {
+    const int kf = (int)std::min<int64_t>(k_fetch, h->ntotal);
+    const int whole = k_fetch > h->ntotal ? 1 : 0;          // the list was cut to the store: it is all there is (an unfilled slot, had it not been cut)
+    const int xgroup = knn_exact_group(h->dim, k);
+    const int64_t xslots = knn_exact_slots(nq, k, xgroup);
+    const int64_t n_words = ceil_div64(h->ntotal, 64);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += al256(bytes); return o; };
+    const size_t o_fd = take((size_t)nq * kf * sizeof(float)), o_fi = take((size_t)nq * kf * sizeof(int64_t));
+    const size_t o_fk = take((size_t)nq * kf * sizeof(double));
+    const size_t o_count = take(256), o_sel = take((size_t)nq * sizeof(int));
+    const size_t o_admit = take(n_excl > 0 ? (size_t)n_words * sizeof(unsigned long long) : 0);
+    const size_t o_xk = take(n_excl > 0 ? (size_t)xslots * KX_SLICES * k * sizeof(double) : 0);
+    const size_t o_xi = take(n_excl > 0 ? (size_t)xslots * KX_SLICES * k * sizeof(int) : 0);
+    if (off > h->excl_ws_bytes) {
+        RADAD_HIP_CHECK(hipDeviceSynchronize());              // an earlier search of this kind may still read the old one
+        if (h->excl_ws) (void)hipFree(h->excl_ws);
+        h->excl_ws = nullptr; h->excl_ws_bytes = 0;
+        if (hipMalloc(&h->excl_ws, off) != hipSuccess) {
+            (void)hipGetLastError();
+            radad_set_error("hipMalloc of %zu bytes for the exclusion-aware search failed", off);
+            return RADAD_ENOMEM;
+        }
+        h->excl_ws_bytes = off;
     }
+    auto at = [&](size_t o) { return (char*)h->excl_ws + o; };
+    SearchCtx c;
+    int rc = knn_search_locked(h, q_in, q_dtype, nq, kf, KNN_MARGIN, (float*)at(o_fd), (int64_t*)at(o_fi), (double*)at(o_fk), st, &c);
+    if (rc) return rc;
+    int* count = (int*)at(o_count);
+    int* sel = (int*)at(o_sel);
+    RADAD_HIP_CHECK(hipMemsetAsync(count, 0, 256, st));
+    hipLaunchKernelGGL(k_excl_compact, dim3((unsigned)ceil_div64(nq, 4)), dim3(256), 0, st, (const float*)at(o_fd), (const int64_t*)at(o_fi),
+                       (const double*)at(o_fk), nq, kf, k, whole, tags, h->ntotal, h->id_base, excl, n_excl, out_dist_dev, out_idx_dev,
+                       out_key_dev, count, sel);
+    RADAD_HIP_CHECK(hipGetLastError());
+    h->excl_o_count = o_count;
+    h->last_excl_nq = nq;
+    if (n_excl == 0) return RADAD_OK;                          // nothing excluded: every query is proved by its own list
+    unsigned long long* admit = (unsigned long long*)at(o_admit);
+    hipLaunchKernelGGL(k_excl_bitmap, dim3((unsigned)ceil_div64(n_words * 64, 256)), dim3(256), 0, st, tags, h->ntotal, excl, n_excl,
+                       (const int*)count, admit);
+    RADAD_HIP_CHECK(hipGetLastError());
+    ExactParams x;
+    x.db = h->rows; x.db_f16 = h->f16; x.q = c.q_use; x.sel = sel; x.count = count;
+    x.n = h->ntotal; x.dim = h->dim; x.k = k; x.l2 = c.l2; x.group = xgroup;
+    x.slice_rows = ceil_div64(h->ntotal, KX_SLICES);
+    x.pkey = (double*)at(o_xk); x.pidx = (int*)at(o_xi); x.id_base = h->id_base;
+    x.out_dist = out_dist_dev; x.out_idx = out_idx_dev; x.out_key = out_key_dev;
+    x.host_stats = nullptr;                                    // the handle's certificate report and its tuning belong to the fast pass
+    x.arrive = h->xarrive;                                     // (the fast pass made room for nq groups; zero between launches)
+    x.admit = admit;
+    const size_t xlds = (size_t)xgroup * h->dim * 4 + (size_t)KX_WAVES * xgroup * k * 12 + 16;
+    RADAD_REQUIRE(xlds <= KX_LDS_MAX && h->xarrive && nq <= h->xarrive_cap, "radad_knn_search_excl: dim %d x k %d too large for the exact kernel", h->dim, k);
+    RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_exact_scan_excl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
+    const unsigned gy = k <= KNN_F16_MAX_K ? KX_GROUPS_Y : 8 * KX_GROUPS_Y;
+    x.nslots = (int)xslots;
+    for (int64_t s0 = 0; s0 < nq; s0 += x.nslots) {            // (launches past the device-side count leave at once)
+        x.slot0 = (int)s0;
+        hipLaunchKernelGGL(k_exact_scan_excl, dim3(KX_SLICES, gy), dim3(KX_THREADS), xlds, st, x);
+    }
+    RADAD_HIP_CHECK(hipGetLastError());
+    return RADAD_OK;
 }
 
 extern "C" {
@@ -3691,6 +3868,38 @@ int radad_knn_search_finish(radad_knn_t h, const float* global_lower_bound_dev, 
     h->pending.valid = false;
     RADAD_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, h->ev_begun, 0));       // the scan of _begin (no-op on the same stream)
     return knn_search_phase2(h, c, global_lower_bound_dev, false, out_dist_dev, out_idx_dev, out_key_dev, (hipStream_t)stream);
+}
+
+int radad_knn_search_excl(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* row_tags_dev,
+                          const int64_t* excl_sorted_dev, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
+                          void* stream) {
+    RADAD_REQUIRE(h, "NULL handle");
+    RADAD_REQUIRE(q_dtype == RADAD_Q_F32 || q_dtype == RADAD_Q_BF16, "radad_knn_search_excl: unsupported query dtype %d", q_dtype);
+    RADAD_REQUIRE(k >= 1 && k <= RADAD_KNN_MAX_K, "radad_knn_search_excl: k=%d outside [1,%d]", k, RADAD_KNN_MAX_K);
+    RADAD_REQUIRE(k_fetch >= k && k_fetch <= RADAD_KNN_MAX_K, "radad_knn_search_excl: k_fetch=%d outside [k=%d,%d]", k_fetch, k, RADAD_KNN_MAX_K);
+    RADAD_REQUIRE(nq >= 0 && nq < (1ll << 31) - KT_N, "radad_knn_search_excl: bad nq");
+    RADAD_REQUIRE(n_excl >= 0 && (n_excl == 0 || (excl_sorted_dev && row_tags_dev)),
+                  "radad_knn_search_excl: %lld excluded tags need the exclusion set and the row tags", (long long)n_excl);
+    if (nq == 0) return RADAD_OK;
+    RADAD_REQUIRE(q_dev && out_dist_dev && out_idx_dev, "radad_knn_search_excl: NULL buffer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    RADAD_REQUIRE(!h->pending.valid, "radad_knn_search_excl: a radad_knn_search_begin on this handle has not been finished");
+    if (h->ntotal == 0) { radad_set_error("radad_knn_search_excl: the store is empty"); return RADAD_ESTATE; }
+    return knn_search_excl_locked(h, q_dev, q_dtype, nq, k, k_fetch, row_tags_dev, excl_sorted_dev, n_excl, out_dist_dev, out_idx_dev,
+                                  out_key_dev, (hipStream_t)stream);
+}
+
+int radad_knn_last_excl(radad_knn_t h, int64_t* n_queries, int* n_exact) {
+    RADAD_REQUIRE(h && n_exact, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    RADAD_HIP_CHECK(knn_wait_last_search(h));
+    *n_exact = 0;
+    if (h->last_excl_nq > 0 && h->excl_ws)
+        RADAD_HIP_CHECK(hipMemcpy(n_exact, (const char*)h->excl_ws + h->excl_o_count, sizeof(int), hipMemcpyDeviceToHost));
+    if (n_queries) *n_queries = h->last_excl_nq;
+    return RADAD_OK;
 }
 
 }  // extern "C"

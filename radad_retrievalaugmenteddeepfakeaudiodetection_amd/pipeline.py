@@ -120,23 +120,38 @@ class HotPathPipeline:
             exclude_ids = {os.path.basename(p) for p in query_paths}            # pipeline.py:463
         k_search = K + (10 if exclude_self else 0)                              # pipeline.py:478
         q = query_vectors.detach().to(self.device, torch.float32)
-        try:
-            dists_t, idxs_t = self.vector_db.search_batch(q, k=k_search)
-        except Exception:                                                       # pipeline.py:481-483: swallow, return padding
-            dists_t = idxs_t = None
+        # config.exact_exclusion (opt-in, this build's): the K nearest rows that are NOT excluded, however many excluded rows sit in
+        # front of them (VectorDatabase.search_excluding), instead of the reference's "search K + 10, drop, pad" below
+        from .vector_database import HipFlatIndex, path_tag
+        exact_excl = bool(getattr(self.config, "exact_exclusion", False)) and exclude_self
+        if exact_excl and not isinstance(index, HipFlatIndex):
+            raise ValueError("config.exact_exclusion: exclusion-aware search is flat and single-handle only (vector_db_index_type 'L2' or 'IP')")
+        dists_t = idxs_t = None
+        if not exact_excl:
+            try:
+                dists_t, idxs_t = self.vector_db.search_batch(q, k=k_search)
+            except Exception:                                                   # pipeline.py:481-483: swallow, return padding
+                dists_t = idxs_t = None
 
         # exclusion + compaction + gathers on the device (csrc/knn.hip k_filter_topk, k_gather_rows): basenames are
         # compared through their 63-bit tags, so the only per-row host work left is building the optional path lists
-        from .vector_database import path_tag
         excl = None
         if exclude_self:
             names = exclude_ids if query_paths is not None else getattr(self, "training_file_ids", set())
             if names:
                 excl = torch.tensor(sorted({path_tag(n) for n in names}), dtype=torch.int64, device=self.device)
-        if idxs_t is None:
-            idxs_t = torch.zeros((B, 0), dtype=torch.int64, device=self.device)
-            dists_t = torch.zeros((B, 0), dtype=torch.float32, device=self.device)
-        dist_t, chosen_t = self.vector_db.filter_hits(dists_t, idxs_t, K, excl)
+        if exact_excl:
+            k_fetch = getattr(self.config, "exclusion_k_fetch", K + 10)
+            dist_t, chosen_t = self.vector_db.search_excluding(q, K, excl, k_fetch=K + 10 if k_fetch is None else int(k_fetch))
+            if chosen_t.shape[1] < K:                                           # (a store of fewer than K rows: k was clamped to it)
+                pad = K - chosen_t.shape[1]
+                chosen_t = torch.cat([chosen_t, torch.full((B, pad), -1, dtype=torch.int64, device=self.device)], dim=1)
+                dist_t = torch.cat([dist_t, torch.full((B, pad), float("nan"), device=self.device)], dim=1)
+        else:
+            if idxs_t is None:
+                idxs_t = torch.zeros((B, 0), dtype=torch.int64, device=self.device)
+                dists_t = torch.zeros((B, 0), dtype=torch.float32, device=self.device)
+            dist_t, chosen_t = self.vector_db.filter_hits(dists_t, idxs_t, K, excl)
         valid = chosen_t >= 0
         rows_t = (chosen_t - index.id_base).clamp(min=0)
         lbl_t = torch.where(valid, self.vector_db.labels_device()[rows_t], torch.zeros((), device=self.device))   # 0.0 pad (:513)

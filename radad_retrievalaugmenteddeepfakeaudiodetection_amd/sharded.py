@@ -146,6 +146,10 @@ class ShardedSearch:
     def gather_queries(self, q_local):
         return q_local if self.world == 1 else self._all_gather(q_local)
 
+    def search_excluding(self, *args, **kwargs):
+        raise ValueError("exclusion-aware search is flat and single-handle only (HipFlatIndex.search_excluding): a row-sharded search "
+                         "cannot certify a query from one shard's hits")
+
     def search(self, q_local, k: int, return_all: bool = False):
         """q_local [Q_r, D] -> this rank's rows of the merged result ([Q_r,k] distances, [Q_r,k] global ids);
         `return_all` returns the rows of all ranks' queries instead (rank-major; with uneven=True: padded blocks removed)."""
@@ -247,6 +251,9 @@ class ReplicatedSearch:
 
     def timings(self):
         return []
+
+    def search_excluding(self, *args, **kwargs):
+        raise ValueError("exclusion-aware search is flat and single-handle only: call HipFlatIndex.search_excluding on the rank's own store")
 
     def search(self, q_local, k: int, return_all: bool = False):
         d, i = self.local_search(q_local, k)

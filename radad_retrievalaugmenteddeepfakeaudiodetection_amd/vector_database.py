@@ -179,6 +179,46 @@ class HipFlatIndex:
                                                      _lib.stream_ptr(q.device)), "radad_knn_search")
         return (D, I, K64) if return_f64 else (D, I)
 
+    def search_excluding(self, q, k: int, row_tags, exclude_tags, k_fetch=None, return_f64: bool = False):
+        """The k nearest rows whose tag is not excluded, exactly (radad_knn_search_excl): q [nq, d] CUDA tensor (float32 or bfloat16),
+        row_tags int64 CUDA tensor [ntotal] (indexed by id - id_base), exclude_tags int64 CUDA tensor sorted ascending, or None /
+        empty -> (D f32 [nq,k], I i64 [nq,k][, K64 f64 [nq,k]]) on the device; slots beyond the admissible rows hold -1 / NaN.
+        k_fetch (None = k + 10, the reference's over-fetch) is the size of the certified search in front: a query that does not find
+        k admissible rows among its k_fetch hits is answered by the float64 scan of the admissible rows (last_excl()["exact"])."""
+        import torch
+        _lib.require_cuda(q, "q")
+        bf16 = q.dtype == torch.bfloat16
+        q = q.contiguous() if bf16 else q.contiguous().float()
+        if q.dim() != 2 or q.shape[1] != self.d:
+            raise ValueError(f"search expects [nq, {self.d}], got {tuple(q.shape)}")
+        k = int(k)
+        k_fetch = min(k + 10, _lib.KNN_MAX_K) if k_fetch is None else int(k_fetch)
+        n_excl = 0 if exclude_tags is None else int(exclude_tags.numel())
+        if n_excl:
+            _lib.require_cuda(exclude_tags, "exclude_tags")
+            _lib.require_cuda(row_tags, "row_tags")
+            exclude_tags = exclude_tags.contiguous().to(torch.int64).reshape(-1)
+            row_tags = row_tags.contiguous().to(torch.int64).reshape(-1)
+            if row_tags.numel() != self.ntotal:
+                raise ValueError(f"row_tags must hold one tag per stored row ({self.ntotal}), got {row_tags.numel()}")
+        D = torch.empty((q.shape[0], max(k, 0)), device=q.device, dtype=torch.float32)
+        I = torch.empty((q.shape[0], max(k, 0)), device=q.device, dtype=torch.int64)
+        K64 = torch.empty((q.shape[0], max(k, 0)), device=q.device, dtype=torch.float64) if return_f64 else None
+        with torch.cuda.device(q.device):
+            _lib.check(self._lib.radad_knn_search_excl(self._h, q.data_ptr(), _lib.Q_BF16 if bf16 else _lib.Q_F32, q.shape[0], k, k_fetch,
+                                                       row_tags.data_ptr() if n_excl else None,
+                                                       exclude_tags.data_ptr() if n_excl else None, n_excl, D.data_ptr(), I.data_ptr(),
+                                                       K64.data_ptr() if return_f64 else None, _lib.stream_ptr(q.device)),
+                       "radad_knn_search_excl")
+        return (D, I, K64) if return_f64 else (D, I)
+
+    def last_excl(self):
+        """{"queries", "exact"} of the most recent search_excluding: its batch size and how many of its queries the exact float64 pass
+        answered (radad_knn_last_excl; synchronises with that search)"""
+        nq, ex = C.c_int64(), C.c_int()
+        _lib.check(self._lib.radad_knn_last_excl(self._h, C.byref(nq), C.byref(ex)), "radad_knn_last_excl")
+        return {"queries": nq.value, "exact": ex.value}
+
     def search_begin(self, q, k: int):
         """first half of a search over a row shard (sharded.py): prepares the queries and scans this shard; returns a float32 CUDA
         tensor [nq, k] -- per query lower bounds of the exact scores of this shard's k best rows (q.y / -|q - y|^2; -inf where
@@ -441,6 +481,9 @@ class HipIVFFlatIndex:
         D, I = self.search_device(x, k)
         return D.cpu().numpy(), I.cpu().numpy()
 
+    def search_excluding(self, *args, **kwargs):
+        raise ValueError("exclusion-aware search is flat and single-handle only: an IVF search sees the probed lists, not the store")
+
     def last_search_info(self) -> dict:
         """{"scan": "f32_lists" | "hi_lists" | "exact_flat", "rejected": queries the list scan's certificate could not certify,
         "exact": queries the exact float64 list scan answered (the rejected ones)} of the most recent search (synchronises with it)"""
@@ -619,6 +662,35 @@ class VectorDatabase:
         if is_dev:
             return self.index.search_device(query_vectors, k)
         return self.index.search(query_vectors.astype(np.float32, copy=False), k)
+
+    def search_excluding(self, query_vectors, k: int = None, exclude_tags=None, k_fetch=None):
+        """The k nearest rows whose basename tag (path_tag) is not in `exclude_tags`, exactly, however many excluded rows precede them
+        (HipFlatIndex.search_excluding; the reference's K + 10 over-fetch, pipeline.py:478,491-515, pads instead).  query_vectors: CUDA
+        tensor [B, d]; exclude_tags: int64 tensor / sequence of tags, or None / empty -> (D f32 [B,k], I i64 [B,k]) on the device, -1 / NaN
+        where fewer than k admissible rows exist.  k is clamped to ntotal as in search_batch.  Flat stores only."""
+        import torch
+        if self.index is None:
+            raise ValueError("Vector database is empty. Build the database first.")
+        if not isinstance(self.index, HipFlatIndex):
+            raise ValueError("exclusion-aware search is flat and single-handle only (vector_db_index_type 'L2' or 'IP')")
+        _lib.require_cuda(query_vectors, "query_vectors")
+        if query_vectors.dim() == 1:
+            query_vectors = query_vectors.reshape(1, -1)
+        k = int(k if k is not None else getattr(self.config, "top_k", 5))
+        k_fetch = k + 10 if k_fetch is None else int(k_fetch)
+        if k_fetch < k:
+            raise ValueError(f"k_fetch={k_fetch} must be at least k={k}")
+        k = min(k, self.index.ntotal)
+        if k <= 0:
+            logging.warning("No vectors available for search")
+            return (torch.zeros((len(query_vectors), 0), dtype=torch.float32, device=query_vectors.device),
+                    torch.zeros((len(query_vectors), 0), dtype=torch.int64, device=query_vectors.device))
+        k_fetch = min(k_fetch, _lib.KNN_MAX_K)
+        excl = None
+        if exclude_tags is not None and len(exclude_tags) > 0:
+            excl = torch.as_tensor(exclude_tags, dtype=torch.int64).to(query_vectors.device).reshape(-1)
+            excl = torch.unique(excl)                       # ascending, as the kernel's binary search needs
+        return self.index.search_excluding(query_vectors, k, self.row_tags_device() if excl is not None else None, excl, k_fetch=k_fetch)
 
     # ---- device-side columns for retrieve_similar_vectors ------------------------------------------------------
     def row_tags_device(self):
