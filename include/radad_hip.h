@@ -282,6 +282,53 @@ int radad_knn_search_excl(radad_knn_t h, const void* q_dev, int q_dtype, int64_t
  * exact pass; synchronises with that search.  0 / 0 before the first one. */
 int radad_knn_last_excl(radad_knn_t h, int64_t* n_queries, int* n_exact);
 
+/* The exclusion-aware search over a ROW-SHARDED store, in two halves around one certificate across the shards (the reference's
+ * over-fetch and exclusion loop: pipeline.py:478,491-515; it is single-GPU, vector_database.py:23 -- the sharding is this build's).
+ * A shard cannot prove a query from its own hits, the shards together can (DESIGN, "exclusion over row shards"):
+ *   _begin   on every shard: the certified search at k_fetch (clamped to the shard's rows) and the compaction.  Per query it writes
+ *            the first <= k admissible hits (float64 key, global id; -1 / NaN padded) and a FRONTIER (key, id): every admissible row
+ *            of the shard that is not in the list ranks strictly behind it, in the order (float64 key in the metric's order, lower
+ *            id) of radad_knn_search_f64.  The frontier is the k-th survivor when the list holds k; else the last of the k_fetch hits,
+ *            admissible or not; else -- the hits are all the shard has -- id -1, key NaN: nothing is unseen.
+ *   certify  radad_excl_merge_certify merges the G lists of a query and proves it iff, for every shard whose frontier id is >= 0, the
+ *            merged list M holds k entries and M[k-1] is that frontier entry or ranks ahead of it.
+ *   _finish  on every shard, given the [nq] flags of the queries NO shard combination proved: the row-filtered float64 exact pass of
+ *            radad_knn_search_excl for those of them whose list on this shard is short although rows are unseen (a full list, or one
+ *            that is all the shard has, already is the shard's exact admissible top k); every other row comes through as _begin left
+ *            it.  After it each shard's rows of the flagged queries are its exact admissible top k: a plain radad_topk_merge_f64 of
+ *            the G lists is exact.
+ * So the exact pass -- far more work per query than the fast pass -- runs only for queries that nobody can prove: a shard most of
+ * whose rows are excluded (the training_file_ids mode, pipeline.py:500-502) does not enter it while another shard holds k admissible
+ * rows in front of its frontier.
+ * radad_knn_search_excl_begin: arguments, their rules and RADAD_ESTATE on an empty store as radad_knn_search_excl, except nq >= 1;
+ * out_key_dev [nq,k] double, out_idx_dev [nq,k], frontier_key_dev [nq] double, frontier_idx_dev [nq] are all required.  The handle
+ * then holds a begun search; it holds at most one, of either kind (radad_knn_search_begin or this): every other search, add, reserve
+ * or load on it fails with RADAD_EINVAL until the search is finished or given up (radad_knn_search_abort covers both kinds).  The
+ * queries, the row tags and the exclusion set must stay alive until _finish.
+ * radad_knn_search_excl_finish: unproved_dev [nq] int32, non-zero = flagged (NULL = none flagged).  out_dist is the correctly
+ * rounded key, out_key_dev (may be NULL) the key; padding -1 / NaN / NaN.  It may run on another stream than _begin (it waits for
+ * _begin's device work through an event); device-driven, no certificate report, the admission bitmap is built only when a query is
+ * listed.  RADAD_EINVAL when no exclusion-aware search was begun.  _begin + _finish with the shard's OWN flags (list short and
+ * frontier id >= 0) is radad_knn_search_excl, bit for bit.
+ * radad_knn_last_excl after _begin reports its batch size and 0; after _finish, the flagged queries this shard answered exactly.
+ * Not offered for the IVF index, and not combined with the cross-shard lower bound of radad_knn_search_begin / _finish: every
+ * shard certifies its own k_fetch here, G times the re-rank work of one GPU. */
+int radad_knn_search_excl_begin(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, int k_fetch,
+                                const int64_t* row_tags_dev, const int64_t* excl_sorted_dev, int64_t n_excl,
+                                double* out_key_dev /*[nq,k]*/, int64_t* out_idx_dev /*[nq,k]*/, double* frontier_key_dev /*[nq]*/,
+                                int64_t* frontier_idx_dev /*[nq]*/, void* stream);
+int radad_knn_search_excl_finish(radad_knn_t h, const int* unproved_dev /*[nq] int32, NULL = none*/, float* out_dist_dev /*[nq,k]*/,
+                                 int64_t* out_idx_dev /*[nq,k]*/, double* out_key_dev /*[nq,k] or NULL*/, void* stream);
+/* Merge + certificate of the sharded exclusion-aware search (pipeline.py:478,491-515 over this build's row shards): in_key_dev /
+ * in_idx_dev [n_parts, nq, k] and frontier_key_dev / frontier_idx_dev [n_parts, nq] as the shards' _begin wrote them, in one order of
+ * the shards.  One wave per query merges by (key in the metric's order, lower id), id -1 last, as radad_topk_merge_f64 does, and
+ * writes out_dist (the rounded key), out_idx, out_key (may be NULL) with padding -1 / NaN / NaN, and unproved_out_dev [nq] int32: 0 =
+ * proved by the rule above, 1 = not.  Limits as radad_topk_merge_f64: 1 <= n_parts <= 4096 (4 bytes of LDS per part and wave),
+ * 1 <= k <= RADAD_KNN_MAX_K; k merge rounds of ceil(n_parts / 64) reads per lane. */
+int radad_excl_merge_certify(int metric, const double* in_key_dev, const int64_t* in_idx_dev, const double* frontier_key_dev,
+                             const int64_t* frontier_idx_dev, int n_parts, int64_t nq, int k, float* out_dist_dev,
+                             int64_t* out_idx_dev, double* out_key_dev, int* unproved_out_dev, int device, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Inverted-file flat index: faiss.IndexIVFFlat(IndexFlatL2 quantiser, d, nlist, METRIC_L2), the reference's optional
  * `vector_db_index_type == "IVF"` (vector_database.py:65-70 create with nlist = max(64, ivf_nlist), :124-128 train on the

@@ -2356,6 +2356,138 @@ __global__ __launch_bounds__(256) void k_excl_bitmap(const int64_t* __restrict__
     if ((threadIdx.x & 63) == 0 && (r >> 6) < ((ntotal + 63) >> 6)) admit[r >> 6] = m;
 }
 
+// ---- the same over ROW SHARDS (radad_knn_search_excl_begin / _finish, radad_excl_merge_certify) -------------------------------------
+// Compaction with frontier: k_excl_compact's walk for one shard of a row-sharded store.  A shard cannot prove a query alone, so
+// nothing is listed here; instead the query gets a FRONTIER (key, id): every admissible row of the shard that is not among the
+// survivors written ranks strictly behind it.  It is the k_keep-th survivor when there are k_keep; else the last hit of the
+// fast-pass list (admissible or not: the list is a prefix of the shard's ranking); else, when the list is all the shard has (an
+// unfilled slot, or `whole`), id -1 / key NaN: nothing is unseen.  own[q] = 1 where the shard's list is short although rows are
+// unseen -- the query k_excl_compact would have listed, and the only kind whose list the exact pass can still change.
+__global__ __launch_bounds__(256) void k_excl_compact_frontier(const float* __restrict__ in_dist, const int64_t* __restrict__ in_idx,
+                                                               const double* __restrict__ in_key, int64_t nq, int k_in, int k_keep,
+                                                               int whole, const int64_t* __restrict__ tags, int64_t ntotal,
+                                                               int64_t id_base, const int64_t* __restrict__ excl, int64_t n_excl,
+                                                               float* __restrict__ out_dist, int64_t* __restrict__ out_idx,
+                                                               double* __restrict__ out_key, double* __restrict__ fr_key,
+                                                               int64_t* __restrict__ fr_idx, int* __restrict__ own) {
+    const int lane = threadIdx.x & 63;
+    const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= nq) return;                                        // (wave-uniform)
+    int kept = 0;
+    bool unfilled = false;
+    for (int s0 = 0; s0 < k_in && kept < k_keep; s0 += 64) {
+        const int j = s0 + lane;
+        int64_t id = -1;
+        bool keep = false;
+        if (j < k_in) {
+            id = in_idx[q * k_in + j];
+            const int64_t r = id - id_base;
+            keep = id >= 0 && r >= 0 && r < ntotal;
+            if (keep && n_excl > 0) keep = !excl_has(excl, n_excl, tags[r]);
+        }
+        unfilled |= __ballot(j < k_in && id < 0) != 0ull;
+        const unsigned long long m = __ballot(keep);
+        const int pos = kept + __popcll(m & ((1ull << lane) - 1ull));
+        if (keep && pos < k_keep) {
+            out_idx[q * k_keep + pos] = id;
+            out_dist[q * k_keep + pos] = in_dist[q * k_in + j];
+            out_key[q * k_keep + pos] = in_key[q * k_in + j];
+            if (pos == k_keep - 1) { fr_key[q] = in_key[q * k_in + j]; fr_idx[q] = id; }
+        }
+        kept += __popcll(m);
+    }
+    kept = min(kept, k_keep);
+    for (int o = kept + lane; o < k_keep; o += 64) {
+        out_idx[q * k_keep + o] = -1;
+        out_dist[q * k_keep + o] = __int_as_float(0x7fc00000);   // NaN, as pipeline.py:515
+        out_key[q * k_keep + o] = (double)__int_as_float(0x7fc00000);
+    }
+    if (lane == 0) {
+        const bool unseen = kept < k_keep && !unfilled && !whole;          // (k_in >= 1: the store is not empty)
+        if (kept < k_keep) {
+            fr_key[q] = unseen ? in_key[q * k_in + k_in - 1] : (double)__int_as_float(0x7fc00000);
+            fr_idx[q] = unseen ? in_idx[q * k_in + k_in - 1] : -1;
+        }
+        own[q] = unseen ? 1 : 0;
+    }
+}
+
+// Flags to list: the queries the shards could not prove together (unproved[q] != 0) and whose list on THIS shard the exact pass can
+// change (own[q]) become the sel[] / count pair the row-filtered exact pass reads.  A flagged query whose shard list is full, or is
+// all the shard has, already holds the shard's exact admissible top k.
+__global__ __launch_bounds__(256) void k_excl_flags_to_list(const int* __restrict__ unproved, const int* __restrict__ own, int64_t nq,
+                                                            int* __restrict__ count, int* __restrict__ sel) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q < nq && unproved[q] != 0 && own[q] != 0) sel[atomicAdd(count, 1)] = (int)q;
+}
+
+struct ExclMergeParams {
+    const double* key = nullptr;      // [n_parts, nq, k] float64 keys of each shard's survivors
+    const int64_t* idx = nullptr;     // [n_parts, nq, k] global ids, -1 = padding
+    const double* fr_key = nullptr;   // [n_parts, nq] frontiers
+    const int64_t* fr_idx = nullptr;  // [n_parts, nq], -1 = the shard has nothing unseen
+    int n_parts = 0, k = 0, l2 = 0;
+    int64_t nq = 0;
+    float* out_dist = nullptr;
+    int64_t* out_idx = nullptr;
+    double* out_key = nullptr;        // optional
+    int* unproved = nullptr;          // [nq]
+};
+static_assert(std::is_trivially_copyable_v<ExclMergeParams>, "kernel argument");
+
+// k_merge_lists<double>'s merge (one wave per query, (key, id) order, id -1 last) with the exclusion family's padding (-1 / NaN / NaN)
+// and the certificate ACROSS shards: the query is proved iff for every shard with a frontier (id >= 0) the merged list holds k
+// entries and its last one is the frontier entry or ranks ahead of it -- an admissible row in no list ranks behind its shard's
+// frontier, hence behind M[k-1].
+__global__ __launch_bounds__(256) void k_excl_merge_certify(ExclMergeParams p) {
+    extern __shared__ int s_pos_all[];   // [4 waves][n_parts]
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int64_t q = (int64_t)blockIdx.x * 4 + wave;
+    if (q >= p.nq) return;
+    int* s_pos = s_pos_all + wave * p.n_parts;
+    for (int i = lane; i < p.n_parts; i += 64) s_pos[i] = 0;
+    double bs = 0;               // "larger is better" key of the entry merged last
+    int64_t bi = INT64_MAX;
+    int bp = -1;
+    for (int o = 0; o < p.k; ++o) {
+        bs = 0; bi = INT64_MAX; bp = -1;
+        for (int part = lane; part < p.n_parts; part += 64) {
+            const int pos = s_pos[part];
+            if (pos >= p.k) continue;
+            const int64_t off = ((int64_t)part * p.nq + q) * p.k + pos;
+            const int64_t id = p.idx[off];
+            if (id < 0) continue;
+            const double key = p.l2 ? -p.key[off] : p.key[off];
+            if (bp < 0 || key > bs || (key == bs && id < bi)) { bs = key; bi = id; bp = part; }
+        }
+#pragma unroll
+        for (int ofs = 32; ofs > 0; ofs >>= 1) {
+            const double os = __shfl_xor(bs, ofs, 64);
+            const int64_t oi = __shfl_xor(bi, ofs, 64);
+            const int op = __shfl_xor(bp, ofs, 64);
+            if (op >= 0 && (bp < 0 || os > bs || (os == bs && oi < bi))) { bs = os; bi = oi; bp = op; }
+        }
+        if (bp >= 0 && (bp & 63) == lane) s_pos[bp] += 1;
+        if (lane == 0) {
+            const double d = bp < 0 ? (double)__int_as_float(0x7fc00000) : (p.l2 ? -bs : bs);
+            p.out_dist[q * p.k + o] = (float)d;
+            p.out_idx[q * p.k + o] = bp < 0 ? -1 : bi;
+            if (p.out_key) p.out_key[q * p.k + o] = d;
+        }
+    }
+    // (bs, bi, bp) is M[k-1] on every lane, bp < 0 when the merged list is short
+    bool bad = false;
+    for (int part = lane; part < p.n_parts; part += 64) {
+        const int64_t fi = p.fr_idx[(int64_t)part * p.nq + q];
+        if (fi < 0) continue;
+        const double fk = p.l2 ? -p.fr_key[(int64_t)part * p.nq + q] : p.fr_key[(int64_t)part * p.nq + q];
+        bad |= !(bp >= 0 && (bs > fk || (bs == fk && bi <= fi)));
+    }
+    const unsigned long long any_bad = __ballot(bad);
+    if (lane == 0) p.unproved[q] = any_bad != 0ull ? 1 : 0;
+}
+
 // out[r] = the k-th largest of in[r][0..m) (NaN ranks lowest).  One wave per row, a lane holds up to KTH_PER_LANE values; k - 1 rounds
 // of "wave-wide maximum, its first holder drops it".  The sharded search's bound: m = G k lower bounds per query.
 constexpr int KTH_PER_LANE = 20;         // m <= 1280 (8 shards x k = 128, or 40 x 32)
@@ -2436,6 +2568,27 @@ struct SearchCtx {
     bool have_ak = false;              // k_kth_floor left a_k in the workspace (ws.ak)
     bool hi_tile = false;              // the certified f16 tile scan took this search
     SearchLayout ws;
+};
+
+// byte offsets in the handle's exclusion workspace
+struct ExclLayout {
+    size_t fd = 0, fi = 0, fk = 0;          // the fast pass's k_fetch lists (dist, id, key)
+    size_t count = 0, sel = 0;              // listed-query counter, listed queries
+    size_t admit = 0, xk = 0, xi = 0;       // admission bitmap, the filtered exact pass's partial lists
+    size_t bd = 0, bi = 0, bk = 0, own = 0; // begun form only: the shard's lists as _begin left them, and its own short-list flags
+    size_t bytes = 0;
+    int kf = 0, whole = 0, xgroup = 1;
+    int64_t xslots = 0, n_words = 0;
+};
+
+// an exclusion-aware search begun on a row shard (radad_knn_search_excl_begin) without its _finish yet
+struct ExclCtx {
+    bool valid = false;
+    int64_t nq = 0, n_excl = 0;
+    int k = 0, l2 = 0;
+    const float* q_use = nullptr;
+    const int64_t *tags = nullptr, *excl = nullptr;
+    ExclLayout L;
 };
 
 // ---- handle -------------------------------------------------------------------------------------------
@@ -2531,6 +2684,7 @@ struct radad_knn_s {
     int last_scan_launches = 1;            // ... in how many launches
     EventRing prof;
     SearchCtx pending;           // radad_knn_search_begin without its _finish yet
+    ExclCtx pending_excl;        // radad_knn_search_excl_begin without its _finish yet (at most one begun search, of either kind)
     std::mutex mu;
 };
 
@@ -2926,7 +3080,7 @@ int radad_knn_reserve(radad_knn_t h, int64_t capacity) {
     RADAD_REQUIRE(h, "NULL handle");
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
-    RADAD_REQUIRE(!h->pending.valid, "radad_knn_reserve: a begun search (radad_knn_search_begin) must be finished or aborted before the store changes");
+    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_reserve: a begun search (radad_knn_search_begin) must be finished or aborted before the store changes");
     if (capacity <= h->capacity) return RADAD_OK;
     RADAD_HIP_CHECK(hipDeviceSynchronize());
     return knn_realloc(h, capacity);
@@ -2941,7 +3095,7 @@ int radad_knn_add(radad_knn_t h, const float* rows_dev, int64_t n, void* stream)
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
     // (the second half of a begun search reads rows / ntotal live while its candidate ids date from the first half)
-    RADAD_REQUIRE(!h->pending.valid, "radad_knn_add: a begun search (radad_knn_search_begin) must be finished or aborted before the store changes");
+    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_add: a begun search (radad_knn_search_begin) must be finished or aborted before the store changes");
     hipStream_t st = (hipStream_t)stream;
     if (h->ntotal + n > h->capacity) {
         RADAD_HIP_CHECK(hipStreamSynchronize(st));   // the old buffers may still be in use on `st`
@@ -3757,77 +3911,129 @@ static int knn_search_core(radad_knn_t h, const void* q_in, int q_dtype, int64_t
     RADAD_REQUIRE(q_in && out_dist_dev && out_idx_dev, "radad_knn_search: NULL buffer");
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
-    RADAD_REQUIRE(!h->pending.valid, "radad_knn_search: a radad_knn_search_begin on this handle has not been finished");
+    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_search: a radad_knn_search_begin on this handle has not been finished");
     return knn_search_locked(h, q_in, q_dtype, nq, k, margin, out_dist_dev, out_idx_dev, out_key_dev, (hipStream_t)stream, nullptr);
 }
 
 // ---- exclusion-aware search ---------------------------------------------------------------------------------------------------------
 // fast pass = the certified search at k_fetch (every scan path, float64 keys) -> k_excl_compact: certificate per query, results of the
 // proved ones -> k_exact_scan_excl for the listed ones, sized and driven by the device-side count like the exact pass of any search.
-static int knn_search_excl_locked(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* tags,
-                                  const int64_t* excl, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
-                                  hipStream_t st) {
-    const int kf = (int)std::min<int64_t>(k_fetch, h->ntotal);
-    const int whole = k_fetch > h->ntotal ? 1 : 0;          // the list was cut to the store: it is all there is (an unfilled slot, had it not been cut)
-    const int xgroup = knn_exact_group(h->dim, k);
-    const int64_t xslots = knn_exact_slots(nq, k, xgroup);
-    const int64_t n_words = ceil_div64(h->ntotal, 64);
+static ExclLayout knn_excl_layout(radad_knn_t h, int64_t nq, int k, int k_fetch, int64_t n_excl, bool begun) {
+    ExclLayout L;
+    L.kf = (int)std::min<int64_t>(k_fetch, h->ntotal);
+    L.whole = k_fetch > h->ntotal ? 1 : 0;          // the list was cut to the store: it is all there is (an unfilled slot, had it not been cut)
+    L.xgroup = knn_exact_group(h->dim, k);
+    L.xslots = knn_exact_slots(nq, k, L.xgroup);
+    L.n_words = ceil_div64(h->ntotal, 64);
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off += al256(bytes); return o; };
-    const size_t o_fd = take((size_t)nq * kf * sizeof(float)), o_fi = take((size_t)nq * kf * sizeof(int64_t));
-    const size_t o_fk = take((size_t)nq * kf * sizeof(double));
-    const size_t o_count = take(256), o_sel = take((size_t)nq * sizeof(int));
-    const size_t o_admit = take(n_excl > 0 ? (size_t)n_words * sizeof(unsigned long long) : 0);
-    const size_t o_xk = take(n_excl > 0 ? (size_t)xslots * KX_SLICES * k * sizeof(double) : 0);
-    const size_t o_xi = take(n_excl > 0 ? (size_t)xslots * KX_SLICES * k * sizeof(int) : 0);
-    if (off > h->excl_ws_bytes) {
-        RADAD_HIP_CHECK(hipDeviceSynchronize());              // an earlier search of this kind may still read the old one
-        if (h->excl_ws) (void)hipFree(h->excl_ws);
-        h->excl_ws = nullptr; h->excl_ws_bytes = 0;
-        if (hipMalloc(&h->excl_ws, off) != hipSuccess) {
-            (void)hipGetLastError();
-            radad_set_error("hipMalloc of %zu bytes for the exclusion-aware search failed", off);
-            return RADAD_ENOMEM;
-        }
-        h->excl_ws_bytes = off;
+    L.fd = take((size_t)nq * L.kf * sizeof(float)); L.fi = take((size_t)nq * L.kf * sizeof(int64_t));
+    L.fk = take((size_t)nq * L.kf * sizeof(double));
+    L.count = take(256); L.sel = take((size_t)nq * sizeof(int));
+    L.admit = take(n_excl > 0 ? (size_t)L.n_words * sizeof(unsigned long long) : 0);
+    L.xk = take(n_excl > 0 ? (size_t)L.xslots * KX_SLICES * k * sizeof(double) : 0);
+    L.xi = take(n_excl > 0 ? (size_t)L.xslots * KX_SLICES * k * sizeof(int) : 0);
+    if (begun) {
+        L.bd = take((size_t)nq * k * sizeof(float)); L.bi = take((size_t)nq * k * sizeof(int64_t));
+        L.bk = take((size_t)nq * k * sizeof(double)); L.own = take((size_t)nq * sizeof(int));
     }
+    L.bytes = off;
+    return L;
+}
+
+static int knn_excl_reserve(radad_knn_t h, size_t bytes) {
+    if (bytes <= h->excl_ws_bytes) return RADAD_OK;
+    RADAD_HIP_CHECK(hipDeviceSynchronize());              // an earlier search of this kind may still read the old one
+    if (h->excl_ws) (void)hipFree(h->excl_ws);
+    h->excl_ws = nullptr; h->excl_ws_bytes = 0;
+    if (hipMalloc(&h->excl_ws, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        radad_set_error("hipMalloc of %zu bytes for the exclusion-aware search failed", bytes);
+        return RADAD_ENOMEM;
+    }
+    h->excl_ws_bytes = bytes;
+    return RADAD_OK;
+}
+
+// the row-filtered exact pass for the queries in sel[0, *count): bitmap (built only when *count > 0), then k_exact_scan_excl sized and
+// driven by the device-side count like the exact pass of any search; it overwrites those queries' rows of out_*
+static int knn_excl_exact_pass(radad_knn_t h, const ExclLayout& L, int64_t nq, int k, int l2, const float* q_use, const int64_t* tags,
+                               const int64_t* excl, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
+                               hipStream_t st) {
     auto at = [&](size_t o) { return (char*)h->excl_ws + o; };
-    SearchCtx c;
-    int rc = knn_search_locked(h, q_in, q_dtype, nq, kf, KNN_MARGIN, (float*)at(o_fd), (int64_t*)at(o_fi), (double*)at(o_fk), st, &c);
-    if (rc) return rc;
-    int* count = (int*)at(o_count);
-    int* sel = (int*)at(o_sel);
-    RADAD_HIP_CHECK(hipMemsetAsync(count, 0, 256, st));
-    hipLaunchKernelGGL(k_excl_compact, dim3((unsigned)ceil_div64(nq, 4)), dim3(256), 0, st, (const float*)at(o_fd), (const int64_t*)at(o_fi),
-                       (const double*)at(o_fk), nq, kf, k, whole, tags, h->ntotal, h->id_base, excl, n_excl, out_dist_dev, out_idx_dev,
-                       out_key_dev, count, sel);
-    RADAD_HIP_CHECK(hipGetLastError());
-    h->excl_o_count = o_count;
-    h->last_excl_nq = nq;
-    if (n_excl == 0) return RADAD_OK;                          // nothing excluded: every query is proved by its own list
-    unsigned long long* admit = (unsigned long long*)at(o_admit);
-    hipLaunchKernelGGL(k_excl_bitmap, dim3((unsigned)ceil_div64(n_words * 64, 256)), dim3(256), 0, st, tags, h->ntotal, excl, n_excl,
+    int* count = (int*)at(L.count);
+    unsigned long long* admit = (unsigned long long*)at(L.admit);
+    hipLaunchKernelGGL(k_excl_bitmap, dim3((unsigned)ceil_div64(L.n_words * 64, 256)), dim3(256), 0, st, tags, h->ntotal, excl, n_excl,
                        (const int*)count, admit);
     RADAD_HIP_CHECK(hipGetLastError());
     ExactParams x;
-    x.db = h->rows; x.db_f16 = h->f16; x.q = c.q_use; x.sel = sel; x.count = count;
-    x.n = h->ntotal; x.dim = h->dim; x.k = k; x.l2 = c.l2; x.group = xgroup;
+    x.db = h->rows; x.db_f16 = h->f16; x.q = q_use; x.sel = (int*)at(L.sel); x.count = count;
+    x.n = h->ntotal; x.dim = h->dim; x.k = k; x.l2 = l2; x.group = L.xgroup;
     x.slice_rows = ceil_div64(h->ntotal, KX_SLICES);
-    x.pkey = (double*)at(o_xk); x.pidx = (int*)at(o_xi); x.id_base = h->id_base;
+    x.pkey = (double*)at(L.xk); x.pidx = (int*)at(L.xi); x.id_base = h->id_base;
     x.out_dist = out_dist_dev; x.out_idx = out_idx_dev; x.out_key = out_key_dev;
     x.host_stats = nullptr;                                    // the handle's certificate report and its tuning belong to the fast pass
     x.arrive = h->xarrive;                                     // (the fast pass made room for nq groups; zero between launches)
     x.admit = admit;
-    const size_t xlds = (size_t)xgroup * h->dim * 4 + (size_t)KX_WAVES * xgroup * k * 12 + 16;
+    const size_t xlds = (size_t)L.xgroup * h->dim * 4 + (size_t)KX_WAVES * L.xgroup * k * 12 + 16;
     RADAD_REQUIRE(xlds <= KX_LDS_MAX && h->xarrive && nq <= h->xarrive_cap, "radad_knn_search_excl: dim %d x k %d too large for the exact kernel", h->dim, k);
     RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_exact_scan_excl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
     const unsigned gy = k <= KNN_F16_MAX_K ? KX_GROUPS_Y : 8 * KX_GROUPS_Y;
-    x.nslots = (int)xslots;
+    x.nslots = (int)L.xslots;
     for (int64_t s0 = 0; s0 < nq; s0 += x.nslots) {            // (launches past the device-side count leave at once)
         x.slot0 = (int)s0;
         hipLaunchKernelGGL(k_exact_scan_excl, dim3(KX_SLICES, gy), dim3(KX_THREADS), xlds, st, x);
     }
     RADAD_HIP_CHECK(hipGetLastError());
+    return RADAD_OK;
+}
+
+static int knn_search_excl_locked(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* tags,
+                                  const int64_t* excl, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
+                                  hipStream_t st) {
+    const ExclLayout L = knn_excl_layout(h, nq, k, k_fetch, n_excl, false);
+    int rc = knn_excl_reserve(h, L.bytes);
+    if (rc) return rc;
+    auto at = [&](size_t o) { return (char*)h->excl_ws + o; };
+    SearchCtx c;
+    rc = knn_search_locked(h, q_in, q_dtype, nq, L.kf, KNN_MARGIN, (float*)at(L.fd), (int64_t*)at(L.fi), (double*)at(L.fk), st, &c);
+    if (rc) return rc;
+    int* count = (int*)at(L.count);
+    int* sel = (int*)at(L.sel);
+    RADAD_HIP_CHECK(hipMemsetAsync(count, 0, 256, st));
+    hipLaunchKernelGGL(k_excl_compact, dim3((unsigned)ceil_div64(nq, 4)), dim3(256), 0, st, (const float*)at(L.fd), (const int64_t*)at(L.fi),
+                       (const double*)at(L.fk), nq, L.kf, k, L.whole, tags, h->ntotal, h->id_base, excl, n_excl, out_dist_dev, out_idx_dev,
+                       out_key_dev, count, sel);
+    RADAD_HIP_CHECK(hipGetLastError());
+    h->excl_o_count = L.count;
+    h->last_excl_nq = nq;
+    if (n_excl == 0) return RADAD_OK;                          // nothing excluded: every query is proved by its own list
+    return knn_excl_exact_pass(h, L, nq, k, c.l2, c.q_use, tags, excl, n_excl, out_dist_dev, out_idx_dev, out_key_dev, st);
+}
+
+// first half over a row shard: the fast pass at k_fetch, then the compaction with frontier into the workspace; the caller gets copies
+static int knn_search_excl_begin_locked(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* tags,
+                                        const int64_t* excl, int64_t n_excl, double* out_key_dev, int64_t* out_idx_dev,
+                                        double* fr_key_dev, int64_t* fr_idx_dev, hipStream_t st) {
+    const ExclLayout L = knn_excl_layout(h, nq, k, k_fetch, n_excl, true);
+    int rc = knn_excl_reserve(h, L.bytes);
+    if (rc) return rc;
+    auto at = [&](size_t o) { return (char*)h->excl_ws + o; };
+    SearchCtx c;
+    rc = knn_search_locked(h, q_in, q_dtype, nq, L.kf, KNN_MARGIN, (float*)at(L.fd), (int64_t*)at(L.fi), (double*)at(L.fk), st, &c);
+    if (rc) return rc;
+    RADAD_HIP_CHECK(hipMemsetAsync(at(L.count), 0, 256, st));
+    hipLaunchKernelGGL(k_excl_compact_frontier, dim3((unsigned)ceil_div64(nq, 4)), dim3(256), 0, st, (const float*)at(L.fd),
+                       (const int64_t*)at(L.fi), (const double*)at(L.fk), nq, L.kf, k, L.whole, tags, h->ntotal, h->id_base, excl, n_excl,
+                       (float*)at(L.bd), (int64_t*)at(L.bi), (double*)at(L.bk), fr_key_dev, fr_idx_dev, (int*)at(L.own));
+    RADAD_HIP_CHECK(hipGetLastError());
+    RADAD_HIP_CHECK(hipMemcpyAsync(out_key_dev, at(L.bk), (size_t)nq * k * sizeof(double), hipMemcpyDeviceToDevice, st));
+    RADAD_HIP_CHECK(hipMemcpyAsync(out_idx_dev, at(L.bi), (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    RADAD_HIP_CHECK(hipEventRecord(h->ev_begun, st));
+    h->excl_o_count = L.count;
+    h->last_excl_nq = nq;
+    ExclCtx& e = h->pending_excl;
+    e.valid = true; e.nq = nq; e.n_excl = n_excl; e.k = k; e.l2 = c.l2; e.q_use = c.q_use; e.tags = tags; e.excl = excl; e.L = L;
     return RADAD_OK;
 }
 
@@ -3841,7 +4047,7 @@ int radad_knn_search_begin(radad_knn_t h, const void* q_dev, int q_dtype, int64_
     RADAD_REQUIRE(q_dev && kth_lower_bound_dev, "radad_knn_search_begin: NULL buffer");
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
-    RADAD_REQUIRE(!h->pending.valid, "radad_knn_search_begin: the previous begin on this handle has not been finished");
+    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_search_begin: the previous begin on this handle has not been finished");
     SearchCtx c;
     int rc = knn_search_phase1(h, q_dev, q_dtype, nq, k, KNN_MARGIN, kth_lower_bound_dev, (hipStream_t)stream, &c);
     if (rc) return rc;
@@ -3854,6 +4060,7 @@ int radad_knn_search_abort(radad_knn_t h) {
     RADAD_REQUIRE(h, "NULL handle");
     std::lock_guard<std::mutex> lk(h->mu);
     h->pending.valid = false;                 // (the workspace of the abandoned first half is simply reused by the next search)
+    h->pending_excl.valid = false;
     return RADAD_OK;
 }
 
@@ -3884,7 +4091,7 @@ int radad_knn_search_excl(radad_knn_t h, const void* q_dev, int q_dtype, int64_t
     RADAD_REQUIRE(q_dev && out_dist_dev && out_idx_dev, "radad_knn_search_excl: NULL buffer");
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
-    RADAD_REQUIRE(!h->pending.valid, "radad_knn_search_excl: a radad_knn_search_begin on this handle has not been finished");
+    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_search_excl: a radad_knn_search_begin on this handle has not been finished");
     if (h->ntotal == 0) { radad_set_error("radad_knn_search_excl: the store is empty"); return RADAD_ESTATE; }
     return knn_search_excl_locked(h, q_dev, q_dtype, nq, k, k_fetch, row_tags_dev, excl_sorted_dev, n_excl, out_dist_dev, out_idx_dev,
                                   out_key_dev, (hipStream_t)stream);
@@ -3899,6 +4106,68 @@ int radad_knn_last_excl(radad_knn_t h, int64_t* n_queries, int* n_exact) {
     if (h->last_excl_nq > 0 && h->excl_ws)
         RADAD_HIP_CHECK(hipMemcpy(n_exact, (const char*)h->excl_ws + h->excl_o_count, sizeof(int), hipMemcpyDeviceToHost));
     if (n_queries) *n_queries = h->last_excl_nq;
+    return RADAD_OK;
+}
+
+int radad_knn_search_excl_begin(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* row_tags_dev,
+                                const int64_t* excl_sorted_dev, int64_t n_excl, double* out_key_dev, int64_t* out_idx_dev,
+                                double* frontier_key_dev, int64_t* frontier_idx_dev, void* stream) {
+    RADAD_REQUIRE(h, "NULL handle");
+    RADAD_REQUIRE(q_dtype == RADAD_Q_F32 || q_dtype == RADAD_Q_BF16, "radad_knn_search_excl_begin: unsupported query dtype %d", q_dtype);
+    RADAD_REQUIRE(k >= 1 && k <= RADAD_KNN_MAX_K, "radad_knn_search_excl_begin: k=%d outside [1,%d]", k, RADAD_KNN_MAX_K);
+    RADAD_REQUIRE(k_fetch >= k && k_fetch <= RADAD_KNN_MAX_K, "radad_knn_search_excl_begin: k_fetch=%d outside [k=%d,%d]", k_fetch, k, RADAD_KNN_MAX_K);
+    RADAD_REQUIRE(nq > 0 && nq < (1ll << 31) - KT_N, "radad_knn_search_excl_begin: bad nq");
+    RADAD_REQUIRE(n_excl >= 0 && (n_excl == 0 || (excl_sorted_dev && row_tags_dev)),
+                  "radad_knn_search_excl_begin: %lld excluded tags need the exclusion set and the row tags", (long long)n_excl);
+    RADAD_REQUIRE(q_dev && out_key_dev && out_idx_dev && frontier_key_dev && frontier_idx_dev, "radad_knn_search_excl_begin: NULL buffer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_search_excl_begin: the previous begin on this handle has not been finished");
+    if (h->ntotal == 0) { radad_set_error("radad_knn_search_excl_begin: the store is empty"); return RADAD_ESTATE; }
+    return knn_search_excl_begin_locked(h, q_dev, q_dtype, nq, k, k_fetch, row_tags_dev, excl_sorted_dev, n_excl, out_key_dev, out_idx_dev,
+                                        frontier_key_dev, frontier_idx_dev, (hipStream_t)stream);
+}
+
+int radad_knn_search_excl_finish(radad_knn_t h, const int* unproved_dev, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
+                                 void* stream) {
+    RADAD_REQUIRE(h, "NULL handle");
+    RADAD_REQUIRE(out_dist_dev && out_idx_dev, "radad_knn_search_excl_finish: NULL buffer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    RADAD_REQUIRE(h->pending_excl.valid, "radad_knn_search_excl_finish: no exclusion-aware search was begun on this handle");
+    const ExclCtx e = h->pending_excl;
+    h->pending_excl.valid = false;
+    hipStream_t st = (hipStream_t)stream;
+    RADAD_HIP_CHECK(hipStreamWaitEvent(st, h->ev_begun, 0));       // the device work of _begin (no-op on the same stream)
+    h->last_stream = st;                                            // whatever comes next on the handle orders itself behind this
+    h->have_last = true;
+    auto at = [&](size_t o) { return (char*)h->excl_ws + o; };
+    const size_t n = (size_t)e.nq * e.k;
+    RADAD_HIP_CHECK(hipMemcpyAsync(out_dist_dev, at(e.L.bd), n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    RADAD_HIP_CHECK(hipMemcpyAsync(out_idx_dev, at(e.L.bi), n * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    if (out_key_dev) RADAD_HIP_CHECK(hipMemcpyAsync(out_key_dev, at(e.L.bk), n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (!unproved_dev || e.n_excl == 0) return RADAD_OK;           // nothing excluded: every shard list is the shard's exact top k
+    hipLaunchKernelGGL(k_excl_flags_to_list, dim3((unsigned)ceil_div64(e.nq, 256)), dim3(256), 0, st, unproved_dev, (const int*)at(e.L.own),
+                       e.nq, (int*)at(e.L.count), (int*)at(e.L.sel));
+    RADAD_HIP_CHECK(hipGetLastError());
+    return knn_excl_exact_pass(h, e.L, e.nq, e.k, e.l2, e.q_use, e.tags, e.excl, e.n_excl, out_dist_dev, out_idx_dev, out_key_dev, st);
+}
+
+int radad_excl_merge_certify(int metric, const double* in_key_dev, const int64_t* in_idx_dev, const double* frontier_key_dev,
+                             const int64_t* frontier_idx_dev, int n_parts, int64_t nq, int k, float* out_dist_dev, int64_t* out_idx_dev,
+                             double* out_key_dev, int* unproved_out_dev, int device, void* stream) {
+    RADAD_REQUIRE(metric >= 0 && metric <= 2, "radad_excl_merge_certify: bad metric");
+    RADAD_REQUIRE(n_parts >= 1 && n_parts <= 4096 && k >= 1 && k <= RADAD_KNN_MAX_K && nq >= 0, "radad_excl_merge_certify: bad shape");
+    if (nq == 0) return RADAD_OK;
+    RADAD_REQUIRE(in_key_dev && in_idx_dev && frontier_key_dev && frontier_idx_dev && out_dist_dev && out_idx_dev && unproved_out_dev,
+                  "radad_excl_merge_certify: NULL buffer");
+    DeviceGuard g(device);
+    ExclMergeParams m;
+    m.key = in_key_dev; m.idx = in_idx_dev; m.fr_key = frontier_key_dev; m.fr_idx = frontier_idx_dev;
+    m.n_parts = n_parts; m.k = k; m.l2 = metric == RADAD_METRIC_L2; m.nq = nq;
+    m.out_dist = out_dist_dev; m.out_idx = out_idx_dev; m.out_key = out_key_dev; m.unproved = unproved_out_dev;
+    hipLaunchKernelGGL(k_excl_merge_certify, dim3((unsigned)ceil_div64(nq, 4)), dim3(256), 4 * n_parts * sizeof(int), (hipStream_t)stream, m);
+    RADAD_HIP_CHECK(hipGetLastError());
     return RADAD_OK;
 }
 
@@ -4173,7 +4442,7 @@ int snap_load_range(radad_knn_t h, const char* path, int64_t row0, int64_t n_row
     RADAD_REQUIRE(row0 >= 0 && n_rows >= 0 && row0 + n_rows <= hd.ntotal, "radad_knn_load_range: rows outside the snapshot");
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
-    RADAD_REQUIRE(!h->pending.valid, "radad_knn_load: a begun search (radad_knn_search_begin) must be finished or aborted before the store changes");
+    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_load: a begun search (radad_knn_search_begin) must be finished or aborted before the store changes");
     RADAD_HIP_CHECK(hipDeviceSynchronize());
     h->ntotal = 0;
     h->hi_rows = 0; h->stat_rows = 0;      // the hi plane and the statistics describe the old contents

@@ -53,6 +53,11 @@ def hip_merge(metric: int, dists, idxs, k: int):
     return out_d, out_i
 
 
+def _hip_certify(metric, keys, ids, fkeys, fids):
+    from .vector_database import HipFlatIndex
+    return HipFlatIndex.excl_merge_certify(metric, keys, ids, fkeys, fids)
+
+
 class ShardedSearch:
     """Collective search over per-rank shards.
 
@@ -69,7 +74,8 @@ class ShardedSearch:
     """
 
     def __init__(self, local_search: Callable, metric: int, group=None, merge: Optional[Callable] = None,
-                 uneven: bool = False, exchange: str = "all_to_all", bounded=None, timing: bool = False):
+                 uneven: bool = False, exchange: str = "all_to_all", bounded=None, timing: bool = False, excluding=None,
+                 certify: Optional[Callable] = None, local_search_excluding: Optional[Callable] = None):
         import torch.distributed as dist
         if exchange not in ("all_to_all", "all_gather"):
             raise ValueError("exchange must be 'all_to_all' or 'all_gather'")
@@ -84,6 +90,14 @@ class ShardedSearch:
         # k are -1 filled; abort() gives the begun search up when the exchange fails (without it finish(None) is called).  Same on
         # every rank.
         self.bounded = bounded
+        # excluding = (begin, finish[, abort]) of search_excluding (HipFlatIndex.sharded_excluding): begin(q [Q,D], k, exclude_tags
+        # sorted int64 [n], k_fetch) -> (key f64 [Q,k], gid [Q,k], frontier key f64 [Q], frontier gid [Q]); finish(unproved int32 [Q] or
+        # None) -> (key f64 [Q,k], gid [Q,k]); abort() gives the begun search up (without it finish(None) is called).  certify(metric,
+        # keys [G,q,k], gids [G,q,k], fkeys [G,q], fgids [G,q]) -> (dist, gid, key, unproved [q]) defaults to
+        # HipFlatIndex.excl_merge_certify; local_search_excluding(q, k, exclude_tags, k_fetch) -> (dist, gid) serves a world of one.
+        self.excluding = excluding
+        self.certify = certify or _hip_certify
+        self.local_search_excluding = local_search_excluding
         self.timing = bool(timing)       # record (collective_ms, rerank_ms) of every search (CUDA events; read with timings())
         self._events = []
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -146,9 +160,92 @@ class ShardedSearch:
     def gather_queries(self, q_local):
         return q_local if self.world == 1 else self._all_gather(q_local)
 
-    def search_excluding(self, *args, **kwargs):
-        raise ValueError("exclusion-aware search is flat and single-handle only (HipFlatIndex.search_excluding): a row-sharded search "
-                         "cannot certify a query from one shard's hits")
+    def _gather_exclusion(self, excl_local, device):
+        """the ranks' exclusion tags -> their sorted union [n] int64 on `device` (counts first, then blocks padded to the largest)"""
+        import torch
+        e = torch.empty(0, dtype=torch.int64, device=device) if excl_local is None else excl_local.to(device=device, dtype=torch.int64).reshape(-1)
+        counts = self._all_gather(torch.tensor([e.numel()], dtype=torch.int64, device=device)).cpu().tolist()
+        emax = max(counts)
+        if emax == 0:
+            return e
+        block = torch.zeros(emax, dtype=torch.int64, device=device)
+        block[:e.numel()] = e
+        blocks = self._all_gather(block).view(self.world, emax)
+        return torch.unique(torch.cat([blocks[r, :c] for r, c in enumerate(counts)]))         # (sorted ascending)
+
+    def search_excluding(self, q_local, k: int, exclude_tags_local=None, k_fetch=None, return_all: bool = False):
+        """The exclusion-aware search (HipFlatIndex.search_excluding) over the row shards: q_local [Q_r, D], exclude_tags_local int64
+        tensor (any order, may be None / empty) -> this rank's rows ([Q_r,k] float32 distances, [Q_r,k] global ids): per query the k
+        nearest rows of the WHOLE store whose tag no rank excluded, -1 / NaN where fewer exist.  Needs excluding=(begin, finish[,
+        abort]); every rank passes the same k and k_fetch (None = k + 10, per shard).
+          1. the ranks' exclusion tags are all-gathered (counts, then padded blocks) and unioned: the excluded set is that of the
+             batch all ranks form together ("no clip of the batch retrieves a clip of the batch", pipeline.py:491-509)
+          2. the queries are all-gathered as in search
+          3. begin on the shard: certified search at k_fetch, admissible hits + frontier per query
+          4. lists and frontiers travel by the configured primitive: each rank holds every shard's lists for its own queries
+          5. certify (radad_excl_merge_certify): merged rows + one flag per query the shards together cannot prove
+          6. the flags are all-gathered: every rank holds the same [Q] vector
+          7. no flag set: the merged rows are the result and the begun search is given up.  Otherwise finish(flags) runs the
+             row-filtered exact pass for the flagged queries on every shard, the lists travel a second time and are merged
+             (radad_topk_merge_f64).
+        The "any flag set?" test of step 7 is one 4-byte host read of the all-gathered vector.  It is the ONLY host synchronisation
+        this search adds (beyond the count exchanges of step 1 and of uneven=True), and its value is identical on every rank, so
+        every rank takes the same sequence of collectives.  A failure between begin and finish gives the begun search up.
+        return_all is refused: each rank certifies its own queries only."""
+        import torch
+        if return_all:
+            raise ValueError("search_excluding returns a rank's own rows only (return_all is not supported: each rank certifies its own queries)")
+        if self.world == 1:
+            if self.local_search_excluding is None:
+                raise ValueError("search_excluding on one rank needs local_search_excluding (HipFlatIndex.search_excluding)")
+            d_loc, i_loc = self.local_search_excluding(q_local, k, exclude_tags_local, k_fetch)[:2]
+            return d_loc.float(), i_loc
+        if self.excluding is None:
+            raise ValueError("search_excluding needs excluding=(begin, finish[, abort]) (HipFlatIndex.sharded_excluding)")
+        begin, finish = self.excluding[0], self.excluding[1]
+        abort = self.excluding[2] if len(self.excluding) > 2 else None
+        k = int(k)
+        excl = self._gather_exclusion(exclude_tags_local, q_local.device)
+        qr = q_local.shape[0]
+        qr_pad = qr
+        if self.uneven:
+            c = torch.tensor([qr], dtype=torch.int64, device=q_local.device)
+            qr_pad = max(max(int(x) for x in self._all_gather(c).cpu().tolist()), 1)
+            if qr < qr_pad:                                 # pad with copies of a zero query: results are dropped below
+                pad = torch.zeros((qr_pad - qr,) + tuple(q_local.shape[1:]), device=q_local.device, dtype=q_local.dtype)
+                q_local = torch.cat([q_local, pad])
+        q_all = self._all_gather(q_local)
+        key, gid, fkey, fgid = begin(q_all, k, excl, k_fetch)
+        done = False
+
+        def give_up():
+            if abort is not None:
+                abort()
+            else:
+                finish(None)
+
+        try:
+            # frontiers ride as column k of the lists: two exchanges instead of four
+            xk = self._exchange(torch.cat([key, fkey.view(-1, 1)], dim=1), qr_pad)
+            xi = self._exchange(torch.cat([gid, fgid.view(-1, 1)], dim=1), qr_pad)
+            md, mi, _, flags = self.certify(self.metric, xk[:, :, :k].contiguous(), xi[:, :, :k].contiguous(),
+                                            xk[:, :, k].contiguous(), xi[:, :, k].contiguous())
+            flags = flags.to(torch.int32)
+            flags[qr:] = 0                                  # (padding queries need no proof)
+            flags_all = self._all_gather(flags)
+            if int(flags_all.max().item()) == 0:            # the one host read; the same value on every rank
+                give_up()
+                done = True
+                return md[:qr].float(), mi[:qr]
+            done = True
+            key2, gid2 = finish(flags_all)
+        except BaseException:
+            if not done:
+                give_up()
+            raise
+        md, mi = self.merge(self.metric, self._exchange(key2, qr_pad), self._exchange(gid2, qr_pad), k)
+        md = md.float().masked_fill(mi < 0, float("nan"))   # the exclusion family's padding (the plain merge pads with +-inf)
+        return md[:qr], mi[:qr]
 
     def search(self, q_local, k: int, return_all: bool = False):
         """q_local [Q_r, D] -> this rank's rows of the merged result ([Q_r,k] distances, [Q_r,k] global ids);
@@ -240,9 +337,10 @@ class ReplicatedSearch:
     Same call surface as ShardedSearch: search(q_local, k) -> this rank's rows; return_all=True gathers every rank's rows (rank-major;
     the only collective, and not part of a search)."""
 
-    def __init__(self, local_search: Callable, group=None):
+    def __init__(self, local_search: Callable, group=None, local_search_excluding: Optional[Callable] = None):
         import torch.distributed as dist
         self.local_search = local_search
+        self.local_search_excluding = local_search_excluding
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -252,8 +350,13 @@ class ReplicatedSearch:
     def timings(self):
         return []
 
-    def search_excluding(self, *args, **kwargs):
-        raise ValueError("exclusion-aware search is flat and single-handle only: call HipFlatIndex.search_excluding on the rank's own store")
+    def search_excluding(self, q_local, k: int, exclude_tags_local=None, k_fetch=None):
+        """local_search_excluding(q_local, k, exclude_tags_local, k_fetch) on the rank's own queries with the rank's OWN exclusion set
+        (HipFlatIndex.search_excluding): every rank holds the whole store, so there is nothing to certify across ranks."""
+        if self.local_search_excluding is None:
+            raise ValueError("search_excluding needs local_search_excluding (HipFlatIndex.search_excluding on the rank's store)")
+        d, i = self.local_search_excluding(q_local, k, exclude_tags_local, k_fetch)[:2]
+        return d.float(), i
 
     def search(self, q_local, k: int, return_all: bool = False):
         d, i = self.local_search(q_local, k)

@@ -219,6 +219,101 @@ class HipFlatIndex:
         _lib.check(self._lib.radad_knn_last_excl(self._h, C.byref(nq), C.byref(ex)), "radad_knn_last_excl")
         return {"queries": nq.value, "exact": ex.value}
 
+    def search_excluding_begin(self, q, k: int, row_tags, exclude_tags, k_fetch=None):
+        """first half of search_excluding over a ROW SHARD (radad_knn_search_excl_begin; sharded.ShardedSearch.search_excluding): the
+        certified search at k_fetch on this shard and the compaction -> (K64 f64 [nq,k], I i64 [nq,k], FK f64 [nq], FI i64 [nq]): the
+        first <= k admissible hits (-1 / NaN padded) and per query the frontier (key, id) behind which every admissible row of the
+        shard that is not listed ranks; FI -1 (FK NaN) = the list is all the shard has.  Arguments as search_excluding.  The index
+        then holds a begun search until search_excluding_finish or search_abort; q, row_tags and exclude_tags are kept alive."""
+        import torch
+        _lib.require_cuda(q, "q")
+        bf16 = q.dtype == torch.bfloat16
+        q = q.contiguous() if bf16 else q.contiguous().float()
+        if q.dim() != 2 or q.shape[1] != self.d:
+            raise ValueError(f"search expects [nq, {self.d}], got {tuple(q.shape)}")
+        if q.shape[0] == 0:
+            raise ValueError("search_excluding_begin needs at least one query")
+        k = int(k)
+        k_fetch = min(k + 10, _lib.KNN_MAX_K) if k_fetch is None else int(k_fetch)
+        n_excl = 0 if exclude_tags is None else int(exclude_tags.numel())
+        if n_excl:
+            _lib.require_cuda(exclude_tags, "exclude_tags")
+            _lib.require_cuda(row_tags, "row_tags")
+            exclude_tags = exclude_tags.contiguous().to(torch.int64).reshape(-1)
+            row_tags = row_tags.contiguous().to(torch.int64).reshape(-1)
+            if row_tags.numel() != self.ntotal:
+                raise ValueError(f"row_tags must hold one tag per stored row ({self.ntotal}), got {row_tags.numel()}")
+        nq = q.shape[0]
+        K64 = torch.empty((nq, max(k, 0)), device=q.device, dtype=torch.float64)
+        I = torch.empty((nq, max(k, 0)), device=q.device, dtype=torch.int64)
+        FK = torch.empty((nq,), device=q.device, dtype=torch.float64)
+        FI = torch.empty((nq,), device=q.device, dtype=torch.int64)
+        with torch.cuda.device(q.device):
+            _lib.check(self._lib.radad_knn_search_excl_begin(self._h, q.data_ptr(), _lib.Q_BF16 if bf16 else _lib.Q_F32, nq, k, k_fetch,
+                                                             row_tags.data_ptr() if n_excl else None,
+                                                             exclude_tags.data_ptr() if n_excl else None, n_excl, K64.data_ptr(),
+                                                             I.data_ptr(), FK.data_ptr(), FI.data_ptr(), _lib.stream_ptr(q.device)),
+                       "radad_knn_search_excl_begin")
+        self._begun_excl = (q, k, row_tags if n_excl else None, exclude_tags if n_excl else None)
+        return K64, I, FK, FI
+
+    def search_excluding_finish(self, unproved=None, return_f64: bool = False):
+        """second half: unproved int32 CUDA tensor [nq] (non-zero = no combination of the shards proved the query,
+        excl_merge_certify; None = none) -> (D, I[, K64]) as search_excluding: the flagged queries' rows are this shard's exact
+        admissible top k (the row-filtered float64 pass where the shard's list could still change; last_excl()["exact"] counts
+        them), the others as search_excluding_begin left them."""
+        import torch
+        if getattr(self, "_begun_excl", None) is None:
+            raise ValueError("search_excluding_finish: no exclusion-aware search was begun on this index (search_excluding_begin "
+                             "first; a begun search is finished once)")
+        q, k = self._begun_excl[:2]
+        if unproved is not None:
+            _lib.require_cuda(unproved, "unproved")
+            unproved = unproved.contiguous().to(torch.int32).reshape(-1)
+            if unproved.numel() != q.shape[0]:
+                raise ValueError("unproved must hold one flag per query")
+        D = torch.empty((q.shape[0], k), device=q.device, dtype=torch.float32)
+        I = torch.empty((q.shape[0], k), device=q.device, dtype=torch.int64)
+        K64 = torch.empty((q.shape[0], k), device=q.device, dtype=torch.float64) if return_f64 else None
+        keep = self._begun_excl                # (alive until the call below has been enqueued on this stream)
+        self._begun_excl = None
+        with torch.cuda.device(q.device):
+            _lib.check(self._lib.radad_knn_search_excl_finish(self._h, unproved.data_ptr() if unproved is not None else None,
+                                                              D.data_ptr(), I.data_ptr(), K64.data_ptr() if return_f64 else None,
+                                                              _lib.stream_ptr(q.device)), "radad_knn_search_excl_finish")
+        del keep
+        return (D, I, K64) if return_f64 else (D, I)
+
+    @staticmethod
+    def excl_merge_certify(metric: int, keys, ids, fkeys, fids):
+        """keys f64 / ids i64 [G, nq, k] and fkeys f64 / fids i64 [G, nq]: every shard's search_excluding_begin result for the same
+        queries -> (D f32 [nq,k], I i64 [nq,k], K64 f64 [nq,k], unproved i32 [nq]): the merged admissible top k (-1 / NaN padded)
+        and, per query, 1 where the shards together cannot prove it (radad_excl_merge_certify)"""
+        import torch
+        _lib.require_cuda(keys, "keys")
+        G, nq, k = keys.shape
+        if tuple(ids.shape) != (G, nq, k) or tuple(fkeys.shape) != (G, nq) or tuple(fids.shape) != (G, nq):
+            raise ValueError("excl_merge_certify expects keys / ids [G, nq, k] and frontiers [G, nq]")
+        keys, ids = keys.contiguous().to(torch.float64), ids.contiguous().to(torch.int64)
+        fkeys, fids = fkeys.contiguous().to(torch.float64), fids.contiguous().to(torch.int64)
+        D = torch.empty((nq, k), device=keys.device, dtype=torch.float32)
+        I = torch.empty((nq, k), device=keys.device, dtype=torch.int64)
+        K64 = torch.empty((nq, k), device=keys.device, dtype=torch.float64)
+        U = torch.empty((nq,), device=keys.device, dtype=torch.int32)
+        with torch.cuda.device(keys.device):
+            _lib.check(_lib.load().radad_excl_merge_certify(int(metric), keys.data_ptr(), ids.data_ptr(), fkeys.data_ptr(), fids.data_ptr(),
+                                                            G, nq, k, D.data_ptr(), I.data_ptr(), K64.data_ptr(), U.data_ptr(),
+                                                            keys.device.index, _lib.stream_ptr(keys.device)), "radad_excl_merge_certify")
+        return D, I, K64, U
+
+    def sharded_excluding(self, row_tags):
+        """the (begin, finish, abort) triple sharded.ShardedSearch(excluding=...) takes, for this shard and its rows' tags"""
+        def finish(unproved):
+            _, I, K64 = self.search_excluding_finish(unproved, return_f64=True)
+            return K64, I
+        return (lambda q, k, exclude_tags, k_fetch=None: self.search_excluding_begin(q, k, row_tags, exclude_tags, k_fetch)), finish, \
+            self.search_abort
+
     def search_begin(self, q, k: int):
         """first half of a search over a row shard (sharded.py): prepares the queries and scans this shard; returns a float32 CUDA
         tensor [nq, k] -- per query lower bounds of the exact scores of this shard's k best rows (q.y / -|q - y|^2; -inf where
@@ -276,8 +371,10 @@ class HipFlatIndex:
         return (D, I, K64) if return_f64 else (D, I)
 
     def search_abort(self):
-        """gives up a begun search (the exchange between the shards failed): the index accepts searches again"""
+        """gives up a begun search of either kind, search_begin or search_excluding_begin (the exchange between the shards failed, or
+        every query was proved): the index accepts searches again"""
         self._begun = None
+        self._begun_excl = None
         _lib.check(self._lib.radad_knn_search_abort(self._h), "radad_knn_search_abort")
 
     KTH_MAX_VALUES = 1280        # radad_kth_largest: groups x per_group values per query (csrc/knn.hip KTH_PER_LANE x 64)
