@@ -311,8 +311,9 @@ int radad_knn_last_excl(radad_knn_t h, int64_t* n_queries, int* n_exact);
  * listed.  RADAD_EINVAL when no exclusion-aware search was begun.  _begin + _finish with the shard's OWN flags (list short and
  * frontier id >= 0) is radad_knn_search_excl, bit for bit.
  * radad_knn_last_excl after _begin reports its batch size and 0; after _finish, the flagged queries this shard answered exactly.
- * Not offered for the IVF index, and not combined with the cross-shard lower bound of radad_knn_search_begin / _finish: every
- * shard certifies its own k_fetch here, G times the re-rank work of one GPU. */
+ * The IVF index has a search of its own for this, radad_ivf_search_excl below (exclusion inside the list scans, no over-fetch).
+ * Not combined with the cross-shard lower bound of radad_knn_search_begin / _finish: every shard certifies its own k_fetch here,
+ * G times the re-rank work of one GPU. */
 int radad_knn_search_excl_begin(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, int k_fetch,
                                 const int64_t* row_tags_dev, const int64_t* excl_sorted_dev, int64_t n_excl,
                                 double* out_key_dev /*[nq,k]*/, int64_t* out_idx_dev /*[nq,k]*/, double* frontier_key_dev /*[nq]*/,
@@ -365,6 +366,29 @@ int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int n
                      int64_t* out_idx_dev, void* stream);      /* asynchronous on `stream` (the (query, probe) pairs are grouped by list on
                                                                     the device); only the first search after an add rebuilds the list layout
                                                                     synchronously */
+/* The exclusion-aware IVF search: for every query the exact top-k by squared L2 among the rows of its nprobe probed lists
+ * (vector_database.py:174-179) whose tag is NOT in the exclusion set -- the reference's "search K + 10, drop the excluded basenames,
+ * pad" (pipeline.py:478,491-515) without the padding it leaves when more than 10 excluded rows precede a query's K-th admissible
+ * neighbour (a batch of clips of few speakers excluding each other; the training_file_ids mode, :500-502, where most of the store is
+ * excluded).  The admission test sits INSIDE the list scans: a per-call bitmap by list-major position (one bit per stored row, built
+ * on `stream` after the layout is up to date) makes an excluded row no part of the universe -- never emitted, listed or inserted,
+ * never counted towards a bound -- so both list scans' certificates and the exact float64 list scan behind them hold as they stand,
+ * over fewer rows, and the cost does not depend on how many excluded rows crowd a query.  (The flat recipe, over-fetch + certify + exact
+ * pass, does not carry over: the list scans hold k + 6 <= 32 entries per (query, list), so K = 15 could over-fetch 11 rows at most.)
+ *   order    (float64 distance, lower id), as radad_ivf_search
+ *   padding  slots beyond the admissible rows of the probed lists hold id -1 and distance NaN (radad_filter_topk's and
+ *            radad_knn_search_excl's padding, not the +inf of radad_ivf_search)
+ *   n_excl == 0: ids and the distances of filled slots are bit-identical to radad_ivf_search
+ * k in [1, 26], the range the list scans hold; a larger k is RADAD_EINVAL (it is NOT forwarded to the flat store as radad_ivf_search
+ * does: that ignores nprobe and answers another question).  row_tags_dev [ntotal] int64 by insertion id, excl_sorted_dev [n_excl]
+ * int64 ASCENDING (the caller's contract, not checked); both may be NULL only when n_excl == 0.  An untrained index is RADAD_EINVAL;
+ * a trained index without rows returns all -1 / NaN.  Stream-ordered, serialised by the handle's mutex and ordered against searches
+ * on other streams exactly as radad_ivf_search; radad_ivf_last_search_info / _counts describe it when it was the most recent search
+ * on the handle, radad_ivf_last_search_exact reports 0. */
+int radad_ivf_search_excl(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int nprobe,
+                          const int64_t* row_tags_dev /*[ntotal], by insertion id*/,
+                          const int64_t* excl_sorted_dev /*[n_excl] ascending*/, int64_t n_excl,
+                          float* out_dist_dev, int64_t* out_idx_dev, void* stream);
 /* 1 if the most recent radad_ivf_search was answered by the exact scan of the index's flat store (26 < k <= 128): every row an IVF
  * search could return AND the ones its probing would have missed -- a superset of faiss.IndexIVFFlat's answer (which holds only rows
  * of the nprobe lists, vector_database.py:174-179), at the flat scan's cost, nprobe ignored.  0: the nprobe lists were scanned. */

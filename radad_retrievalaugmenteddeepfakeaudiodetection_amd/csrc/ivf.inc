@@ -48,8 +48,41 @@ struct IvfScanParams {
     int dim = 0, k = 0, qcap = 0;       // qcap: query rows that fit in LDS (16 unless dim is very large)
     float* part_score = nullptr;        // [nq * nprobe, k]
     int* part_idx = nullptr;            // [nq * nprobe, k]  positions in lrows
+    const unsigned long long* admit = nullptr;      // FILTERED kernels: the admission bitmap by list-major position (k_ivf_admit_bitmap)
 };
 static_assert(std::is_trivially_copyable_v<IvfScanParams>, "kernel argument");
+
+// ---- exclusion inside the list scans (radad_ivf_search_excl) ---------------------------------------------------------
+// bit (p & 63) of admit[p >> 6] = the tag of the row at list-major position p is not in the ascending exclusion set.  One thread per
+// position, one ballot and one 64-bit word per wave (k_excl_bitmap's shape; the rows are reached through lids: position -> insertion
+// id).  The array ends with one spare zero word, so that a reader may fetch the word behind any valid position's.
+// The FILTERED instantiations of the three list kernels below read it: an excluded row is not part of the universe -- it is never
+// emitted, listed or inserted, and it never counts towards a bound.  Bits are indexed by ABSOLUTE position: a list does not start
+// on a multiple of 64, nor does a workgroup's share of a split list.
+__global__ __launch_bounds__(256) void k_ivf_admit_bitmap(const int64_t* __restrict__ tags, const int64_t* __restrict__ lids, int64_t n,
+                                                          const int64_t* __restrict__ excl, int64_t n_excl, unsigned long long* __restrict__ admit) {
+    const int64_t pos = (int64_t)blockIdx.x * 256 + threadIdx.x;        // (n rounded up to whole waves: every lane ballots)
+    const bool ok = pos < n && !excl_has(excl, n_excl, tags[lids[pos]]);
+    const unsigned long long m = __ballot(ok);
+    if ((threadIdx.x & 63) == 0 && (pos >> 6) <= ((n + 63) >> 6)) admit[pos >> 6] = m;       // (<=: the spare word, all zero)
+}
+__device__ __forceinline__ bool ivf_admitted(const unsigned long long* __restrict__ admit, int64_t pos) {
+    return (admit[pos >> 6] >> (pos & 63)) & 1ull;
+}
+// bits 0 .. n - 1 (n <= 16) = the admission bits of the positions pos .. pos + n - 1, pos a valid position: they lie in one word or
+// in two adjacent ones (the spare word makes the second fetch safe)
+__device__ __forceinline__ unsigned ivf_admit_bits(const unsigned long long* __restrict__ admit, int64_t pos, int n) {
+    const int sh = (int)(pos & 63);
+    unsigned long long w = admit[pos >> 6] >> sh;
+    if (sh > 64 - n) w |= admit[(pos >> 6) + 1] << (64 - sh);
+    return (unsigned)w & ((1u << n) - 1u);
+}
+// the padding of the exclusion-aware searches (radad_filter_topk, radad_knn_search_excl): distance NaN where the id is -1
+// (k_merge_refine and k_ivf_exact write +inf there)
+__global__ __launch_bounds__(256) void k_ivf_pad_nan(float* __restrict__ dist, const int64_t* __restrict__ idx, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n && idx[i] < 0) dist[i] = __int_as_float(0x7fc00000);
+}
 
 // ---- (query, probe) pairs grouped by list, on the device ------------------------------------------------------------
 // k_ivf_count: pairs per list.  k_ivf_tasks (one workgroup): exclusive scan -> first sorted position of every list, the
@@ -107,7 +140,7 @@ __global__ __launch_bounds__(256) void k_ivf_scatter(const int64_t* __restrict__
     }
 }
 
-template <int KSEL>
+template <int KSEL, bool FILTERED>
 __device__ __forceinline__ void ivf_scan_task(const IvfScanParams& p, const int task, char* smem) {
     const int qld = p.dim + 4;
     float* sQ = reinterpret_cast<float*>(smem);                   // [qcap][dim + 4] (rows past the task's count are zero)
@@ -145,6 +178,9 @@ __device__ __forceinline__ void ivf_scan_task(const IvfScanParams& p, const int 
         f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
         const int64_t ra = min(row0 + r16, l_end - 1);
         const float* pa = p.lrows + ra * p.dim + 4 * g;
+        unsigned adm = 0xfu;                                            // FILTERED: bit e = row row0 + 4 g + e is admissible (read ahead of the products;
+        if constexpr (FILTERED)                                         // rows past w_end are not emitted whatever their bit says)
+            adm = row0 + 4 * g < w_end ? ivf_admit_bits(p.admit, row0 + 4 * g, 4) : 0u;
         constexpr int PKB = KSEL <= 16 ? 16 : 8;
         for (int kp = 0; kp < nkb; kp += PKB) {
             const int nb = min(PKB, nkb - kp);
@@ -178,7 +214,9 @@ __device__ __forceinline__ void ivf_scan_task(const IvfScanParams& p, const int 
         for (int e = 0; e < 4; ++e) {
             const int64_t row = row0 + 4 * g + e;
             const float sc = 2.f * (acc0[e] + acc1[e]) - p.lnorm[min(row, l_end - 1)];     // L2: rank by 2 q.y - |y|^2
-            if (row < w_end && r16 < cnt && sc >= thr) {
+            // (FILTERED: admission is tested HERE, where rows enter the lists -- thr is -inf until a list is full, so a score of -inf
+            // would still be inserted; and only listed rows set thr, so an excluded row never counts towards it)
+            if (row < w_end && r16 < cnt && sc >= thr && (!FILTERED || ((adm >> e) & 1u))) {
                 const int sl = atomicAdd(&myCnt[r16], 1);
                 myCand[r16 * SQ_SLOTS + sl] = make_float2(sc, __int_as_float((int)row));
                 any = true;
@@ -216,10 +254,10 @@ __device__ __forceinline__ void ivf_scan_task(const IvfScanParams& p, const int 
 }
 
 // One workgroup per task.
-template <int KSEL>
+template <int KSEL, bool FILTERED>
 __global__ __launch_bounds__(SQ_THREADS, 2) void k_ivf_scan(IvfScanParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if ((int)blockIdx.x < *p.n_tasks_dev) ivf_scan_task<KSEL>(p, blockIdx.x, smem);
+    if ((int)blockIdx.x < *p.n_tasks_dev) ivf_scan_task<KSEL, FILTERED>(p, blockIdx.x, smem);
 }
 
 // ---- grouping of a SMALL batch in one launch (npairs <= IVG_MAX_PAIRS, nlist <= IVG_MAX_LISTS): count, scan, task table and
@@ -307,6 +345,7 @@ struct IvfHiParams {
     int cand_cap = 0;
     float* cand_score = nullptr;   // [nq][cand_cap]
     int* cand_idx = nullptr;       // [nq][cand_cap] positions in the list-major order
+    const unsigned long long* admit = nullptr;      // FILTERED: the admission bitmap by list-major position (k_ivf_admit_bitmap)
 };
 static_assert(std::is_trivially_copyable_v<IvfHiParams>, "kernel argument");
 
@@ -326,6 +365,13 @@ constexpr size_t ivf_hi_lds_bytes(int qcap, int dim) {
 // the list "may hide more".  b = max(the k-th best score of THIS list so far, the largest such value any workgroup of the query has
 // published): both are reached by k rows of the probed lists, so b <= a_k and nothing the certificate needs is left out; a far
 // list emits its own ~k + few best at most, nothing once the home list has published.
+// FILTERED (radad_ivf_search_excl): the rows whose admission bit is clear do not exist.  Two things must hold, and a score of -inf
+// gives neither: an excluded row is never EMITTED (while no bound is published the threshold is -inf and `score >= thr` passes
+// everything; k_merge_refine would re-score the row from lrows and return it whenever fewer than k admissible rows are listed), and
+// it never COUNTS towards a bound (it takes KEY_NONE in the selection, like a row past l_end: the K-th best key, the carry and the
+// published gbound are reached by K admissible rows, so b <= a_k of the admissible rows and the certificate holds as it stands).
+// A NaN score gives both (see the chunk loop).
+template <bool FILTERED>
 __global__ __launch_bounds__(SQ_THREADS, 4) void k_ivf_scan_hi(IvfHiParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int qld = p.dim + 8;
@@ -387,6 +433,11 @@ __global__ __launch_bounds__(SQ_THREADS, 4) void k_ivf_scan_hi(IvfHiParams p) {
                 f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
                 const int64_t ra = min(row0 + r16, l_end - 1);
                 const _Float16* pa = p.lhi + ra * p.dim + 8 * g;
+                // FILTERED: bit r = row row0 + r of the step is admissible.  The 16 bits lie in one or two consecutive words at
+                // wave-uniform addresses (ABSOLUTE positions: neither a list nor a workgroup's share of a split list starts on a multiple
+                // of 64; the bitmap ends with a spare word).  They are fetched ahead of the products and used behind them.
+                unsigned abits = 0xffffu;
+                if constexpr (FILTERED) abits = ivf_admit_bits(p.admit, chunk0 + 16 * (4 * s4 + __builtin_amdgcn_readfirstlane(wave)), 16);
                 float rs[4], yb[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -394,14 +445,20 @@ __global__ __launch_bounds__(SQ_THREADS, 4) void k_ivf_scan_hi(IvfHiParams p) {
                     rs[e] = p.lscale ? p.lscale[row] : p.uscale;
                     yb[e] = qc - p.lbias[row];
                 }
-                for (int kp = 0; kp < nkb; kp += 16) {
-                    const int nb = min(16, nkb - kp);
-                    f16x8 v[16];
+                // (FILTERED: 8 row fragments in flight instead of 16.  The unfiltered kernel uses all of the 128 VGPRs that four
+                // workgroups per CU leave; with the admission bits pending across the products the compiler's resource report for 16
+                // fragments was 128 VGPRs + 4 spilled, 20 bytes of scratch per lane -- whether the bits were read here, behind the
+                // products, or patched into the score tile behind a second barrier.  With 8 it is 104 VGPRs and no scratch.  What the
+                // shallower prefetch costs at dim 512 is for tools/bench_ivf.py's excl_ms leg to say: profiles/README.md.)
+                constexpr int HKB = FILTERED ? 8 : 16;
+                for (int kp = 0; kp < nkb; kp += HKB) {
+                    const int nb = min(HKB, nkb - kp);
+                    f16x8 v[HKB];
 #pragma unroll
-                    for (int kb = 0; kb < 16; ++kb)
+                    for (int kb = 0; kb < HKB; ++kb)
                         if (kb < nb) v[kb] = *reinterpret_cast<const f16x8*>(pa + (kp + kb) * 32);
 #pragma unroll
-                    for (int kb = 0; kb < 16; ++kb)
+                    for (int kb = 0; kb < HKB; ++kb)
                         if (kb < nb) {
                             const f16x8 b = *reinterpret_cast<const f16x8*>(qrow + (kp + kb) * 32);
                             if (kb & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(v[kb], b, acc1, 0, 0, 0);
@@ -410,7 +467,13 @@ __global__ __launch_bounds__(SQ_THREADS, 4) void k_ivf_scan_hi(IvfHiParams p) {
                 }
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (row0 + 4 * g + e < l_end) out[e] = fmaf((acc0[e] + acc1[e]) * rs[e], qs, yb[e]);
+                    if (row0 + 4 * g + e < l_end) {
+                        out[e] = fmaf((acc0[e] + acc1[e]) * rs[e], qs, yb[e]);
+                        // an excluded row's score is NaN, this kernel's "no such row" in both places that matter: the selection gives
+                        // it KEY_NONE (it counts towards no K-th best, carry or gbound), and `score >= thr` is false for it whatever
+                        // thr is, -inf included (it is never emitted)
+                        if constexpr (FILTERED) { if (!((abits >> (4 * g + e)) & 1u)) out[e] = __int_as_float(0x7fc00000); }
+                    }
             }
             *reinterpret_cast<f32x4*>(sS + r16 * IVH_SLD + 16 * (4 * s4 + wave) + 4 * g) = out;      // row 4 g + e of the step, query r16
         }
@@ -603,6 +666,7 @@ struct IvfExactParams {
     int64_t* pid = nullptr;
     int* arrive = nullptr;             // [nslots] arrival counters (zero between launches: the last arrival resets its own)
     float* out_dist = nullptr; int64_t* out_idx = nullptr;
+    const unsigned long long* admit = nullptr;      // FILTERED: the admission bitmap by list-major position (k_ivf_admit_bitmap)
 };
 static_assert(std::is_trivially_copyable_v<IvfExactParams>, "kernel argument");
 
@@ -611,6 +675,8 @@ constexpr size_t ivf_exact_lds_bytes(int dim, int k, int nprobe) {
 }
 __device__ __forceinline__ bool ivx_better(double ka, int64_t ia, double kb, int64_t ib) { return ka > kb || (ka == kb && ia < ib); }
 
+// FILTERED (radad_ivf_search_excl): a row whose admission bit is clear is skipped before the insertion test.
+template <bool FILTERED>
 __global__ __launch_bounds__(IVX_THREADS) void k_ivf_exact(IvfExactParams p) {
     const int count = min(*p.count - p.slot0, p.nslots);
     if (count <= 0) return;
@@ -652,6 +718,7 @@ __global__ __launch_bounds__(IVX_THREADS) void k_ivf_exact(IvfExactParams p) {
 #pragma unroll
             for (int u = 0; u < IVX_ROWS; ++u) {
                 if (row + u >= r1) break;                                            // (wave-uniform)
+                if constexpr (FILTERED) { if (!ivf_admitted(p.admit, row + u)) continue; }      // (wave-uniform)
                 double v = acc[u];
 #pragma unroll
                 for (int ofs = 32; ofs > 0; ofs >>= 1) v += __shfl_xor(v, ofs, 64);
@@ -744,6 +811,7 @@ struct radad_ivf_s {
     std::vector<int> assign;            // list of every stored row (host copy; the device copy is rebuilt with the layout)
     DevMem lrows, lnorm, lids, loff, assign_dev, ws_a, ws_b, ws_c, part_s, part_i, tasks;
     DevMem lmax, xkey, xid, xarrive;    // |y|^2 max of every list (the fp32 scan's error bound); partial lists + arrival counters of the exact list scan
+    DevMem admit;                       // radad_ivf_search_excl: the admission bitmap by list-major position, rebuilt by every call
     DevMem lhi, lscale, lbias, qbuf, cand_s, cand_i;    // the flat store's f16 plane gathered list-major (+ per-row scale, bias); the queries' f16 side
     bool have_hi = false;               // lhi is up to date with ...
     const void* hi_src = nullptr;       // ... this plane of the flat store (pointer, rows and rebuild count at the gather)
@@ -912,6 +980,7 @@ int radad_ivf_destroy(radad_ivf_t h) {
         h->ws_a.release(); h->ws_b.release(); h->ws_c.release(); h->part_s.release(); h->part_i.release(); h->tasks.release();
         h->lmax.release(); h->xkey.release(); h->xid.release(); h->xarrive.release();
         h->lhi.release(); h->lscale.release(); h->lbias.release(); h->qbuf.release(); h->cand_s.release(); h->cand_i.release();
+        h->admit.release();
         if (h->ev_done) { (void)hipDeviceSynchronize(); (void)hipEventDestroy(h->ev_done); }
     }
     delete h;
@@ -1080,25 +1149,12 @@ int radad_ivf_reconstruct(radad_ivf_t h, const int64_t* idx_dev, int64_t n, floa
     return radad_knn_reconstruct(h->flat, idx_dev, n, out_dev, stream);
 }
 
-int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int nprobe, float* out_dist_dev, int64_t* out_idx_dev,
-                     void* stream) {
-    RADAD_REQUIRE(h, "NULL handle");
-    RADAD_REQUIRE(h->trained, "radad_ivf_search: the index is not trained");
-    RADAD_REQUIRE(k >= 1 && k <= IVF_MAX_K, "radad_ivf_search: k=%d outside [1,%d]", k, IVF_MAX_K);
-    RADAD_REQUIRE(nq >= 0 && nq < (1 << 24), "radad_ivf_search: bad nq");
-    if (nq == 0) return RADAD_OK;
-    RADAD_REQUIRE(q_dev && out_dist_dev && out_idx_dev, "radad_ivf_search: NULL buffer");
-    // The list scan keeps k + 6 <= 32 candidates per (query, list) pair in registers.  Larger k (faiss takes up to 2048,
-    // vector_database.py:169-181) is answered by the EXACT search over the same rows in insertion order (the certified f16 scan of
-    // the flat store behind this index): every neighbour an IVF search could return and the ones its probing would miss -- recall
-    // 1.0 instead of the probed lists', at the flat scan's cost (~1 ms per 1024 queries x 1 M x 512).
-    // faiss returns only rows of the nprobe lists (vector_database.py:174-179); this answer is a SUPERSET of that (and ignores nprobe):
-    // the caller can tell from radad_ivf_last_search_exact.
-    RADAD_REQUIRE(nprobe >= 1, "radad_ivf_search: nprobe=%d must be >= 1", nprobe);
-    if (k + KNN_MARGIN > 32) {
-        { std::lock_guard<std::mutex> lk(h->mu); h->last_exact = true; }
-        return radad_knn_search(h->flat, q_dev, nq, k, out_dist_dev, out_idx_dev, stream);
-    }
+// The list-scan search behind radad_ivf_search (filtered = false) and radad_ivf_search_excl (filtered = true).  The caller has
+// checked the arguments (k + KNN_MARGIN <= 32); this takes the handle's lock.  filtered: the exact top-k among the rows of the
+// probed lists whose tag (row_tags, by insertion id) is not in excl_sorted; unfilled slots -1 / NaN.  With n_excl == 0 every row is
+// admissible: the unfiltered kernels run and only the padding differs.
+static int ivf_search_lists(const char* fn, radad_ivf_t h, const float* q_dev, int64_t nq, int k, int nprobe, bool filtered, const int64_t* row_tags,
+                            const int64_t* excl_sorted, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, void* stream) {
     std::lock_guard<std::mutex> lk(h->mu);
     h->last_exact = false;
     DeviceGuard g(h->device);
@@ -1112,8 +1168,9 @@ int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int n
     }
     if ((rc = ivf_prepare(h, st))) return rc;
     const int64_t n = (int64_t)h->assign.size();
-    if (n == 0) {      // a trained index without rows: every slot unfilled (id -1, distance +inf)
-        hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)ceil_div64(nq * k, 256)), dim3(256), 0, st, out_dist_dev, nq * k, INFINITY);
+    if (n == 0) {      // a trained index without rows: every slot unfilled (id -1, distance +inf; NaN for the exclusion-aware search)
+        hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)ceil_div64(nq * k, 256)), dim3(256), 0, st, out_dist_dev, nq * k,
+                           filtered ? __builtin_nanf("") : INFINITY);
         RADAD_HIP_CHECK(hipGetLastError());
         RADAD_HIP_CHECK(hipMemsetAsync(out_idx_dev, 0xff, (size_t)nq * k * sizeof(int64_t), st));
         h->last_hi = false; h->last_fcount = nullptr;
@@ -1121,6 +1178,16 @@ int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int n
         return RADAD_OK;
     }
     const bool use_hi = ivf_ensure_plane(h, st);
+    // the admission bitmap: on the search's stream, behind ivf_prepare (lids changes with every add); the tags and the set are the
+    // caller's, so nothing of it is kept between calls
+    const unsigned long long* admit = nullptr;
+    if (filtered && n_excl > 0) {
+        if ((rc = h->admit.ensure((size_t)(((n + 63) >> 6) + 1) * sizeof(unsigned long long)))) return rc;
+        hipLaunchKernelGGL(k_ivf_admit_bitmap, dim3((unsigned)ceil_div64(n + 64, 256)), dim3(256), 0, st, row_tags, (const int64_t*)h->lids.p, n,
+                           excl_sorted, n_excl, (unsigned long long*)h->admit.p);
+        RADAD_HIP_CHECK(hipGetLastError());
+        admit = (const unsigned long long*)h->admit.p;
+    }
     const int ksel = k + KNN_MARGIN;
     const int64_t npairs = nq * nprobe;
 
@@ -1132,12 +1199,13 @@ int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int n
     // 2) group the (query, probe) pairs by list on the device; <= qcap queries per task (LDS holds qcap query rows)
     const int qcap = (int)std::max<size_t>(1, std::min<size_t>(SQ_NQ, (size_t)(112 * 1024) / ((size_t)(h->dim + 4) * sizeof(float))));
     const int64_t T = std::min<int64_t>(h->nlist, npairs) + npairs / qcap + 1;      // upper bound on the number of tasks
-    RADAD_REQUIRE(npairs < (int64_t)1 << 31 && T < (int64_t)1 << 31, "radad_ivf_search: too many (query, probe) pairs");
+    RADAD_REQUIRE(npairs < (int64_t)1 << 31 && T < (int64_t)1 << 31, "%s: too many (query, probe) pairs", fn);
     const size_t tb = (size_t)(3 * T + 2 * npairs + 2 * h->nlist + 1) * sizeof(int);
     {
-        const void* before = h->tasks.p;
+        // (a buffer that grew is new memory even when hipMalloc hands back the address hipFree just released: compare the sizes)
+        const size_t before = h->tasks.bytes;
         if ((rc = h->tasks.ensure(tb))) return rc;
-        if (h->tasks.p != before) RADAD_HIP_CHECK(hipMemsetAsync(h->tasks.p, 0, h->tasks.bytes, st));      // (the per-list counters start at zero)
+        if (h->tasks.bytes != before) RADAD_HIP_CHECK(hipMemsetAsync(h->tasks.p, 0, h->tasks.bytes, st));      // (the per-list counters start at zero)
     }
     // (the per-list counters FIRST: k_ivf_tasks leaves them zero for the next search, whatever that one's sizes are)
     int* d_cnt = (int*)h->tasks.p; int* d_cur = d_cnt + h->nlist; int* d_nt = d_cur + h->nlist;
@@ -1192,10 +1260,15 @@ int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int n
         // against its own bound, and all of a query's must fit half its buffer
         ip.split = (int)std::max<int64_t>(1, std::min<int64_t>(T <= 64 ? 8 : (T <= 128 ? 4 : (T <= 256 ? 2 : 1)), (ccap / 2) / ((int64_t)nprobe * (k + 8))));
         ip.dim = h->dim; ip.k = k; ip.qcap = qcap; ip.gbound = gbound; ip.cand_cnt = cand_cnt; ip.cand_cap = ccap;
-        ip.cand_score = (float*)h->cand_s.p; ip.cand_idx = (int*)h->cand_i.p;
+        ip.cand_score = (float*)h->cand_s.p; ip.cand_idx = (int*)h->cand_i.p; ip.admit = admit;
         const size_t hlds = ivf_hi_lds_bytes(qcap, h->dim);
-        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_scan_hi), hipFuncAttributeMaxDynamicSharedMemorySize, (int)hlds));
-        hipLaunchKernelGGL(k_ivf_scan_hi, dim3((unsigned)(T * ip.split)), dim3(SQ_THREADS), hlds, st, ip);
+        if (admit) {
+            RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_scan_hi<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)hlds));
+            hipLaunchKernelGGL(k_ivf_scan_hi<true>, dim3((unsigned)(T * ip.split)), dim3(SQ_THREADS), hlds, st, ip);
+        } else {
+            RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_scan_hi<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)hlds));
+            hipLaunchKernelGGL(k_ivf_scan_hi<false>, dim3((unsigned)(T * ip.split)), dim3(SQ_THREADS), hlds, st, ip);
+        }
         RefineParams m;
         m.score = (const float*)h->cand_s.p; m.idx = (const int*)h->cand_i.p; m.n_parts = 1; m.part_len = ccap; m.k = k; m.dim = h->dim; m.l2 = 1;
         m.cap = std::max(k + KNN_CERT_EXTRA, KNN_CERT_CAP); m.eps = eps; m.part_cnt = cand_cnt;
@@ -1224,17 +1297,18 @@ int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int n
         sp.lrows = (const float*)h->lrows.p; sp.lnorm = (const float*)h->lnorm.p; sp.loff = (const int*)h->loff.p; sp.q = q_dev;
         sp.task_list = d_tl; sp.task_pbeg = d_tp; sp.task_cnt = d_tc; sp.n_tasks_dev = d_nt; sp.pair_q = d_pq; sp.pair_slot = d_ps; sp.dim = h->dim; sp.k = ksel;
         sp.qcap = qcap;
-        sp.part_score = (float*)h->part_s.p; sp.part_idx = (int*)h->part_i.p;
+        sp.part_score = (float*)h->part_s.p; sp.part_idx = (int*)h->part_i.p; sp.admit = admit;
         const size_t slot_bytes = std::max<size_t>(sizeof(float2) * 4 * SQ_NQ * SQ_SLOTS, sizeof(u64) * 3 * SQ_NQ * 32);
         const size_t lds = sizeof(float) * qcap * (h->dim + 4) + slot_bytes + sizeof(int) * 4 * SQ_NQ;
-        RADAD_REQUIRE(lds <= 160 * 1024, "radad_ivf_search: dim %d too large for the list-scan kernel", h->dim);
-        if (ksel <= 16) {
-            RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_scan<16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k_ivf_scan<16>, dim3((unsigned)T), dim3(SQ_THREADS), lds, st, sp);
-        } else {
-            RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_scan<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k_ivf_scan<32>, dim3((unsigned)T), dim3(SQ_THREADS), lds, st, sp);
-        }
+        RADAD_REQUIRE(lds <= 160 * 1024, "%s: dim %d too large for the list-scan kernel", fn, h->dim);
+        auto scan = [&](auto kern) -> int {
+            RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(kern, dim3((unsigned)T), dim3(SQ_THREADS), lds, st, sp);
+            return RADAD_OK;
+        };
+        if (ksel <= 16) rc = admit ? scan(k_ivf_scan<16, true>) : scan(k_ivf_scan<16, false>);
+        else rc = admit ? scan(k_ivf_scan<32, true>) : scan(k_ivf_scan<32, false>);
+        if (rc) return rc;
         RefineParams m;
         m.score = (const float*)h->part_s.p; m.idx = (const int*)h->part_i.p; m.n_parts = nprobe; m.part_len = ksel; m.k = k; m.dim = h->dim;
         m.cap = std::max(k + KNN_CERT_EXTRA, (int)std::min<int64_t>((int64_t)nprobe * ksel, KNN_CERT_CAP));
@@ -1250,33 +1324,82 @@ int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int n
     // 4) the queries the route's certificate rejected: exact float64 scan of their probed lists (leaves at once when there are none)
     {
         const size_t xlds = ivf_exact_lds_bytes(h->dim, k, nprobe);
-        RADAD_REQUIRE(xlds <= 160 * 1024, "radad_ivf_search: nprobe %d too large for the exact list scan", nprobe);
+        RADAD_REQUIRE(xlds <= 160 * 1024, "%s: nprobe %d too large for the exact list scan", fn, nprobe);
         const int64_t per_q = (int64_t)nprobe * k * 16;
         const int64_t slots = std::min<int64_t>(nq, std::max<int64_t>(1, (int64_t)IVX_PART_BUDGET / per_q));
         if ((rc = h->xkey.ensure((size_t)slots * nprobe * k * sizeof(double)))) return rc;
         if ((rc = h->xid.ensure((size_t)slots * nprobe * k * sizeof(int64_t)))) return rc;
         {
-            const void* before = h->xarrive.p;
+            // (by size, not by address: a grown buffer may come back at the address just freed, and its new tail is not zero -- the
+            // arrival counters of the slots behind the old size then start anywhere, their queries are merged early or never)
+            const size_t before = h->xarrive.bytes;
             if ((rc = h->xarrive.ensure((size_t)slots * sizeof(int)))) return rc;
-            if (h->xarrive.p != before) RADAD_HIP_CHECK(hipMemsetAsync(h->xarrive.p, 0, h->xarrive.bytes, st));
+            if (h->xarrive.bytes != before) RADAD_HIP_CHECK(hipMemsetAsync(h->xarrive.p, 0, h->xarrive.bytes, st));
         }
         IvfExactParams x;
         x.lrows = (const float*)h->lrows.p; x.lids = (const int64_t*)h->lids.p; x.loff = (const int*)h->loff.p; x.q = q_dev;
         x.probes = (const int64_t*)h->ws_b.p; x.sel = xsel; x.count = fcount; x.done = fcount + 1;
         x.dim = h->dim; x.k = k; x.nprobe = nprobe; x.nlist = h->nlist; x.nslots = (int)slots;
         x.pkey = (double*)h->xkey.p; x.pid = (int64_t*)h->xid.p; x.arrive = (int*)h->xarrive.p;
-        x.out_dist = out_dist_dev; x.out_idx = out_idx_dev;
-        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_exact), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
+        x.out_dist = out_dist_dev; x.out_idx = out_idx_dev; x.admit = admit;
         const unsigned grid = (unsigned)std::min<int64_t>(slots * nprobe, IVX_MAX_GRID);
-        for (int64_t s0 = 0; s0 < nq; s0 += slots) {        // (one launch unless the batch's partial lists exceed IVX_PART_BUDGET)
-            x.slot0 = (int)s0;
-            hipLaunchKernelGGL(k_ivf_exact, dim3(grid), dim3(IVX_THREADS), xlds, st, x);
-        }
+        auto exact = [&](auto kern) -> int {
+            RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
+            for (int64_t s0 = 0; s0 < nq; s0 += slots) {    // (one launch unless the batch's partial lists exceed IVX_PART_BUDGET)
+                x.slot0 = (int)s0;
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(IVX_THREADS), xlds, st, x);
+            }
+            RADAD_HIP_CHECK(hipGetLastError());
+            return RADAD_OK;
+        };
+        if ((rc = admit ? exact(k_ivf_exact<true>) : exact(k_ivf_exact<false>))) return rc;
+    }
+    if (filtered) {    // unfilled slots: -1 / NaN, the padding of radad_filter_topk
+        hipLaunchKernelGGL(k_ivf_pad_nan, dim3((unsigned)ceil_div64(nq * k, 256)), dim3(256), 0, st, out_dist_dev, (const int64_t*)out_idx_dev, nq * k);
         RADAD_HIP_CHECK(hipGetLastError());
     }
     h->last_stream = st;
     h->have_last = true;
     return RADAD_OK;
+}
+
+int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int nprobe, float* out_dist_dev, int64_t* out_idx_dev,
+                     void* stream) {
+    RADAD_REQUIRE(h, "NULL handle");
+    RADAD_REQUIRE(h->trained, "radad_ivf_search: the index is not trained");
+    RADAD_REQUIRE(k >= 1 && k <= IVF_MAX_K, "radad_ivf_search: k=%d outside [1,%d]", k, IVF_MAX_K);
+    RADAD_REQUIRE(nq >= 0 && nq < (1 << 24), "radad_ivf_search: bad nq");
+    if (nq == 0) return RADAD_OK;
+    RADAD_REQUIRE(q_dev && out_dist_dev && out_idx_dev, "radad_ivf_search: NULL buffer");
+    // The list scan keeps k + 6 <= 32 candidates per (query, list) pair in registers.  Larger k (faiss takes up to 2048,
+    // vector_database.py:169-181) is answered by the EXACT search over the same rows in insertion order (the certified f16 scan of
+    // the flat store behind this index): every neighbour an IVF search could return and the ones its probing would miss -- recall
+    // 1.0 instead of the probed lists', at the flat scan's cost (~1 ms per 1024 queries x 1 M x 512).
+    // faiss returns only rows of the nprobe lists (vector_database.py:174-179); this answer is a SUPERSET of that (and ignores nprobe):
+    // the caller can tell from radad_ivf_last_search_exact.
+    RADAD_REQUIRE(nprobe >= 1, "radad_ivf_search: nprobe=%d must be >= 1", nprobe);
+    if (k + KNN_MARGIN > 32) {
+        { std::lock_guard<std::mutex> lk(h->mu); h->last_exact = true; }
+        return radad_knn_search(h->flat, q_dev, nq, k, out_dist_dev, out_idx_dev, stream);
+    }
+    return ivf_search_lists("radad_ivf_search", h, q_dev, nq, k, nprobe, false, nullptr, nullptr, 0, out_dist_dev, out_idx_dev, stream);
+}
+
+// The exclusion-aware search (pipeline.py:478,491-515 on the probed lists of vector_database.py:174-179): see ivf_search_lists and the
+// FILTERED kernels.  k stops at 26, what the list scans hold: forwarding a larger k to the flat store as radad_ivf_search does would
+// ignore nprobe and answer another question than the one specified.
+int radad_ivf_search_excl(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int nprobe, const int64_t* row_tags_dev,
+                          const int64_t* excl_sorted_dev, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, void* stream) {
+    RADAD_REQUIRE(h, "NULL handle");
+    RADAD_REQUIRE(h->trained, "radad_ivf_search_excl: the index is not trained");
+    RADAD_REQUIRE(k >= 1 && k + KNN_MARGIN <= 32, "radad_ivf_search_excl: k=%d outside [1,%d], the range the list scans hold", k, 32 - KNN_MARGIN);
+    RADAD_REQUIRE(nq >= 0 && nq < (1 << 24), "radad_ivf_search_excl: bad nq");
+    RADAD_REQUIRE(nprobe >= 1, "radad_ivf_search_excl: nprobe=%d must be >= 1", nprobe);
+    RADAD_REQUIRE(n_excl >= 0 && (n_excl == 0 || (row_tags_dev && excl_sorted_dev)),
+                  "radad_ivf_search_excl: row_tags_dev / excl_sorted_dev may be NULL only when n_excl == 0");
+    if (nq == 0) return RADAD_OK;
+    RADAD_REQUIRE(q_dev && out_dist_dev && out_idx_dev, "radad_ivf_search_excl: NULL buffer");
+    return ivf_search_lists("radad_ivf_search_excl", h, q_dev, nq, k, nprobe, true, row_tags_dev, excl_sorted_dev, n_excl, out_dist_dev, out_idx_dev, stream);
 }
 
 }  // extern "C"

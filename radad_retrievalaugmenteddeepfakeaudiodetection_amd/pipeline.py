@@ -122,12 +122,15 @@ class HotPathPipeline:
         q = query_vectors.detach().to(self.device, torch.float32)
         # config.exact_exclusion (opt-in, this build's): the K nearest rows that are NOT excluded, however many excluded rows sit in
         # front of them (VectorDatabase.search_excluding), instead of the reference's "search K + 10, drop, pad" below
-        from .vector_database import HipFlatIndex, path_tag
+        from .vector_database import HipFlatIndex, HipIVFFlatIndex, path_tag
         exact_excl = bool(getattr(self.config, "exact_exclusion", False)) and exclude_self
         if exact_excl and not isinstance(index, HipFlatIndex):
             raise ValueError("config.exact_exclusion: exclusion-aware search is flat and single-handle only (vector_db_index_type 'L2' or 'IP')")
+        # config.ivf_exact_exclusion (opt-in): the same for an IVF store, among the rows of the probed lists
+        # (VectorDatabase.search_probed_excluding); a flat store ignores it
+        ivf_excl = bool(getattr(self.config, "ivf_exact_exclusion", False)) and exclude_self and isinstance(index, HipIVFFlatIndex)
         dists_t = idxs_t = None
-        if not exact_excl:
+        if not exact_excl and not ivf_excl:
             try:
                 dists_t, idxs_t = self.vector_db.search_batch(q, k=k_search)
             except Exception:                                                   # pipeline.py:481-483: swallow, return padding
@@ -140,9 +143,12 @@ class HotPathPipeline:
             names = exclude_ids if query_paths is not None else getattr(self, "training_file_ids", set())
             if names:
                 excl = torch.tensor(sorted({path_tag(n) for n in names}), dtype=torch.int64, device=self.device)
-        if exact_excl:
-            k_fetch = getattr(self.config, "exclusion_k_fetch", K + 10)
-            dist_t, chosen_t = self.vector_db.search_excluding(q, K, excl, k_fetch=K + 10 if k_fetch is None else int(k_fetch))
+        if exact_excl or ivf_excl:
+            if ivf_excl:
+                dist_t, chosen_t = self.vector_db.search_probed_excluding(q, K, excl)
+            else:
+                k_fetch = getattr(self.config, "exclusion_k_fetch", K + 10)
+                dist_t, chosen_t = self.vector_db.search_excluding(q, K, excl, k_fetch=K + 10 if k_fetch is None else int(k_fetch))
             if chosen_t.shape[1] < K:                                           # (a store of fewer than K rows: k was clamped to it)
                 pad = K - chosen_t.shape[1]
                 chosen_t = torch.cat([chosen_t, torch.full((B, pad), -1, dtype=torch.int64, device=self.device)], dim=1)

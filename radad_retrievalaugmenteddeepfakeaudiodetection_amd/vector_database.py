@@ -581,6 +581,39 @@ class HipIVFFlatIndex:
     def search_excluding(self, *args, **kwargs):
         raise ValueError("exclusion-aware search is flat and single-handle only: an IVF search sees the probed lists, not the store")
 
+    MAX_K_PROBED = 26   # csrc/ivf.inc: the largest k the list scans hold (k + 6 <= 32 entries per (query, list))
+
+    def search_probed_excluding(self, q, k: int, row_tags, exclude_tags):
+        """The k nearest rows of the nprobe probed lists whose tag is not excluded, exactly (radad_ivf_search_excl: the admission test
+        sits inside the list scans, so the cost does not depend on how many excluded rows crowd a query): q [nq, d] CUDA tensor,
+        row_tags int64 CUDA tensor [ntotal] by insertion id, exclude_tags int64 CUDA tensor sorted ascending, or None / empty
+        -> (D f32 [nq,k], I i64 [nq,k]) on the device, ordered by (float64 distance, lower id); slots beyond the admissible rows of the
+        probed lists hold -1 / NaN.  Uses self.nprobe.  k <= 26: a larger k is NOT forwarded to the flat store as search does."""
+        import torch
+        k = int(k)
+        if k > self.MAX_K_PROBED:
+            raise ValueError(f"search_probed_excluding supports k <= {self.MAX_K_PROBED}, the range the list scans hold (asked for {k})")
+        q = self._to_dev(q)
+        if q.dim() != 2 or q.shape[1] != self.d:
+            raise ValueError(f"search expects [nq, {self.d}], got {tuple(q.shape)}")
+        n_excl = 0 if exclude_tags is None else int(exclude_tags.numel())
+        if n_excl:
+            _lib.require_cuda(exclude_tags, "exclude_tags")
+            _lib.require_cuda(row_tags, "row_tags")
+            exclude_tags = exclude_tags.contiguous().to(torch.int64).reshape(-1)
+            row_tags = row_tags.contiguous().to(torch.int64).reshape(-1)
+            if row_tags.numel() != self.ntotal:
+                raise ValueError(f"row_tags must hold one tag per stored row ({self.ntotal}), got {row_tags.numel()}")
+        D = torch.empty((q.shape[0], max(k, 0)), device=q.device, dtype=torch.float32)
+        I = torch.empty((q.shape[0], max(k, 0)), device=q.device, dtype=torch.int64)
+        with torch.cuda.device(q.device):
+            _lib.check(self._lib.radad_ivf_search_excl(self._h, q.data_ptr(), q.shape[0], k, int(self.nprobe),
+                                                       row_tags.data_ptr() if n_excl else None,
+                                                       exclude_tags.data_ptr() if n_excl else None, n_excl, D.data_ptr(), I.data_ptr(),
+                                                       _lib.stream_ptr(q.device)), "radad_ivf_search_excl")
+        self.last_search_exact = False
+        return D, I
+
     def last_search_info(self) -> dict:
         """{"scan": "f32_lists" | "hi_lists" | "exact_flat", "rejected": queries the list scan's certificate could not certify,
         "exact": queries the exact float64 list scan answered (the rejected ones)} of the most recent search (synchronises with it)"""
@@ -788,6 +821,35 @@ class VectorDatabase:
             excl = torch.as_tensor(exclude_tags, dtype=torch.int64).to(query_vectors.device).reshape(-1)
             excl = torch.unique(excl)                       # ascending, as the kernel's binary search needs
         return self.index.search_excluding(query_vectors, k, self.row_tags_device() if excl is not None else None, excl, k_fetch=k_fetch)
+
+    def search_probed_excluding(self, query_vectors, k: int = None, exclude_tags=None):
+        """IVF stores: the k nearest rows of the probed lists (config.vector_db_nprobe, vector_database.py:174-179) whose basename tag
+        (path_tag) is not in `exclude_tags`, exactly, however many excluded rows precede them
+        (HipIVFFlatIndex.search_probed_excluding; the reference's K + 10 over-fetch, pipeline.py:478,491-515, pads instead).
+        query_vectors: CUDA tensor [B, d]; exclude_tags: int64 tensor / sequence of tags, or None / empty -> (D f32 [B,k], I i64 [B,k])
+        on the device, -1 / NaN where the probed lists hold fewer than k admissible rows.  k is clamped to ntotal as in search_batch."""
+        import torch
+        if self.index is None:
+            raise ValueError("Vector database is empty. Build the database first.")
+        if not isinstance(self.index, HipIVFFlatIndex):
+            raise ValueError("search_probed_excluding is the IVF store's exclusion-aware search (vector_db_index_type 'IVF'); "
+                             "a flat store has search_excluding")
+        _lib.require_cuda(query_vectors, "query_vectors")
+        if query_vectors.dim() == 1:
+            query_vectors = query_vectors.reshape(1, -1)
+        k = int(k if k is not None else getattr(self.config, "top_k", 5))
+        k = min(k, self.index.ntotal)
+        if k <= 0:
+            logging.warning("No vectors available for search")
+            return (torch.zeros((len(query_vectors), 0), dtype=torch.float32, device=query_vectors.device),
+                    torch.zeros((len(query_vectors), 0), dtype=torch.int64, device=query_vectors.device))
+        if hasattr(self.config, "vector_db_nprobe"):        # vector_database.py:174-179
+            self.index.nprobe = int(self.config.vector_db_nprobe)
+        excl = None
+        if exclude_tags is not None and len(exclude_tags) > 0:
+            excl = torch.as_tensor(exclude_tags, dtype=torch.int64).to(query_vectors.device).reshape(-1)
+            excl = torch.unique(excl)                       # ascending, as the kernel's binary search needs
+        return self.index.search_probed_excluding(query_vectors, k, self.row_tags_device() if excl is not None else None, excl)
 
     # ---- device-side columns for retrieve_similar_vectors ------------------------------------------------------
     def row_tags_device(self):

@@ -2,7 +2,9 @@
 """IVF-flat (the reference's optional index type, vector_database.py:65-70,174-181) at the benchmark scale: 1M x 512, nlist 4096,
 nprobe 32 (config.py:76), k = 15.  Prints build times and, per batch size, the search time, recall@15 against the exact flat
 search, the flat search's own time, and a roofline block: the bytes of the lists the batch touches (f16 plane rows + their scale /
-bias, each list once) over the search time against HBM (8 TB/s).  tools/bench_ivf.py [nq,nq,...] [hi_scan 0|1]"""
+bias, each list once) over the search time against HBM (8 TB/s).  "excl_ms": the exclusion-aware search (radad_ivf_search_excl, tags =
+row ids) at the same shape with 0 % (a one-tag set no row carries: the filtered kernels run), 1 % and 95 % of the rows excluded.
+tools/bench_ivf.py [nq,nq,...] [hi_scan 0|1]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -28,6 +30,10 @@ idx.nprobe = NPROBE
 assign = torch.from_numpy(idx.assignments()).to(dev)
 list_rows = torch.bincount(assign.long(), minlength=NLIST)
 centroids = torch.from_numpy(idx.centroids()).to(dev)
+tags = torch.arange(N, device=dev, dtype=torch.int64)
+perm = torch.randperm(N, device=dev, generator=torch.Generator(device=dev).manual_seed(5))
+EXCL = {"0pct": torch.tensor([N + 7], device=dev, dtype=torch.int64), "1pct": torch.sort(perm[:N // 100]).values,
+        "95pct": torch.sort(perm[:N * 95 // 100]).values}
 
 
 def timed(fn, reps=20):
@@ -45,6 +51,14 @@ for nq in NQS:
     ms, (Di, Ii) = timed(lambda: idx.search_device(q, K))
     info = idx.last_search_info()
     ms_flat, (De, Ie) = timed(lambda: flat.search_device(q, K))
+    excl_ms = {}
+    for name, ex in EXCL.items():
+        ms_x, (Dx, Ix) = timed(lambda: idx.search_probed_excluding(q, K, tags, ex))
+        xi = idx.last_search_info()
+        assert not torch.isin(Ix[Ix >= 0], ex).any()
+        if name == "0pct":
+            assert torch.equal(Ix, Ii)
+        excl_ms[name] = {"search_ms": round(ms_x, 4), "over_plain": round(ms_x / ms, 3), "rejected": xi["rejected"], "filled": round(float((Ix >= 0).float().mean()), 4)}
     rec = float(np.mean([len(set(a) & set(b)) / K for a, b in zip(Ii.cpu().tolist(), Ie.cpu().tolist())]))
     # the lists this batch probes (float64 centroid distances, as the oracle's ivf_search): each is streamed once per task of <= 16 queries
     d2 = torch.cdist(q.double(), centroids.double())
@@ -55,7 +69,7 @@ for nq in NQS:
     row_bytes = (2 if info["scan"] == "hi_lists" else 4) * D + 8
     alg = int(list_rows[touched].sum().item()) * row_bytes
     streamed = int((list_rows * ((per_list_q + 15) // 16)).sum().item()) * row_bytes
-    out[f"nq{nq}"] = {"search_ms": round(ms, 4), "flat_search_ms": round(ms_flat, 4), "recall_at_15_vs_flat": round(rec, 4), **info,
+    out[f"nq{nq}"] = {"search_ms": round(ms, 4), "flat_search_ms": round(ms_flat, 4), "recall_at_15_vs_flat": round(rec, 4), **info, "excl_ms": excl_ms,
                       "lists_touched": int(touched.numel()), "tasks": tasks,
                       "roofline": {"bound": "hbm", "algorithmic_bytes": alg, "streamed_bytes": streamed, "achieved": round(alg / (ms * 1e-3) / 1e9, 1),
                                    "peak": 8000.0, "unit": "GB/s", "frac": round(alg / (ms * 1e-3) / 1e9 / 8000.0, 4),
