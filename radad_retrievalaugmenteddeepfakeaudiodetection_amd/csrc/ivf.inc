@@ -48,24 +48,16 @@ struct IvfScanParams {
     int dim = 0, k = 0, qcap = 0;       // qcap: query rows that fit in LDS (16 unless dim is very large)
     float* part_score = nullptr;        // [nq * nprobe, k]
     int* part_idx = nullptr;            // [nq * nprobe, k]  positions in lrows
-    const unsigned long long* admit = nullptr;      // FILTERED kernels: the admission bitmap by list-major position (k_ivf_admit_bitmap)
+    const unsigned long long* admit = nullptr;      // FILTERED kernels: the admission bitmap by list-major position (k_admit_bitmap<true>)
 };
 static_assert(std::is_trivially_copyable_v<IvfScanParams>, "kernel argument");
 
 // ---- exclusion inside the list scans (radad_ivf_search_excl) ---------------------------------------------------------
-// bit (p & 63) of admit[p >> 6] = the tag of the row at list-major position p is not in the ascending exclusion set.  One thread per
-// position, one ballot and one 64-bit word per wave (k_excl_bitmap's shape; the rows are reached through lids: position -> insertion
-// id).  The array ends with one spare zero word, so that a reader may fetch the word behind any valid position's.
+// The admission bitmap by list-major position (k_admit_bitmap<true> in knn.hip; the rows are reached through lids: position ->
+// insertion id).  The array ends with one spare zero word, so that a reader may fetch the word behind any valid position's.
 // The FILTERED instantiations of the three list kernels below read it: an excluded row is not part of the universe -- it is never
 // emitted, listed or inserted, and it never counts towards a bound.  Bits are indexed by ABSOLUTE position: a list does not start
 // on a multiple of 64, nor does a workgroup's share of a split list.
-__global__ __launch_bounds__(256) void k_ivf_admit_bitmap(const int64_t* __restrict__ tags, const int64_t* __restrict__ lids, int64_t n,
-                                                          const int64_t* __restrict__ excl, int64_t n_excl, unsigned long long* __restrict__ admit) {
-    const int64_t pos = (int64_t)blockIdx.x * 256 + threadIdx.x;        // (n rounded up to whole waves: every lane ballots)
-    const bool ok = pos < n && !excl_has(excl, n_excl, tags[lids[pos]]);
-    const unsigned long long m = __ballot(ok);
-    if ((threadIdx.x & 63) == 0 && (pos >> 6) <= ((n + 63) >> 6)) admit[pos >> 6] = m;       // (<=: the spare word, all zero)
-}
 __device__ __forceinline__ bool ivf_admitted(const unsigned long long* __restrict__ admit, int64_t pos) {
     return (admit[pos >> 6] >> (pos & 63)) & 1ull;
 }
@@ -345,7 +337,7 @@ struct IvfHiParams {
     int cand_cap = 0;
     float* cand_score = nullptr;   // [nq][cand_cap]
     int* cand_idx = nullptr;       // [nq][cand_cap] positions in the list-major order
-    const unsigned long long* admit = nullptr;      // FILTERED: the admission bitmap by list-major position (k_ivf_admit_bitmap)
+    const unsigned long long* admit = nullptr;      // FILTERED: the admission bitmap by list-major position (k_admit_bitmap<true>)
 };
 static_assert(std::is_trivially_copyable_v<IvfHiParams>, "kernel argument");
 
@@ -666,7 +658,7 @@ struct IvfExactParams {
     int64_t* pid = nullptr;
     int* arrive = nullptr;             // [nslots] arrival counters (zero between launches: the last arrival resets its own)
     float* out_dist = nullptr; int64_t* out_idx = nullptr;
-    const unsigned long long* admit = nullptr;      // FILTERED: the admission bitmap by list-major position (k_ivf_admit_bitmap)
+    const unsigned long long* admit = nullptr;      // FILTERED: the admission bitmap by list-major position (k_admit_bitmap<true>)
 };
 static_assert(std::is_trivially_copyable_v<IvfExactParams>, "kernel argument");
 
@@ -1182,9 +1174,10 @@ static int ivf_search_lists(const char* fn, radad_ivf_t h, const float* q_dev, i
     // caller's, so nothing of it is kept between calls
     const unsigned long long* admit = nullptr;
     if (filtered && n_excl > 0) {
-        if ((rc = h->admit.ensure((size_t)(((n + 63) >> 6) + 1) * sizeof(unsigned long long)))) return rc;
-        hipLaunchKernelGGL(k_ivf_admit_bitmap, dim3((unsigned)ceil_div64(n + 64, 256)), dim3(256), 0, st, row_tags, (const int64_t*)h->lids.p, n,
-                           excl_sorted, n_excl, (unsigned long long*)h->admit.p);
+        const int64_t n_words = ((n + 63) >> 6) + 1;             // (+ 1: the spare word, all zero)
+        if ((rc = h->admit.ensure((size_t)n_words * sizeof(unsigned long long)))) return rc;
+        hipLaunchKernelGGL(k_admit_bitmap<true>, dim3((unsigned)ceil_div64(n_words * 64, 256)), dim3(256), 0, st, row_tags,
+                           (const int64_t*)h->lids.p, n, excl_sorted, n_excl, (const int*)nullptr, (unsigned long long*)h->admit.p, n_words);
         RADAD_HIP_CHECK(hipGetLastError());
         admit = (const unsigned long long*)h->admit.p;
     }

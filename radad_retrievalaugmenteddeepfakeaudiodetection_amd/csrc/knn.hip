@@ -2299,21 +2299,47 @@ __device__ __forceinline__ bool excl_has(const int64_t* __restrict__ excl, int64
     return lo < n_excl && excl[lo] == t;
 }
 
-// Certificate + compaction: one wave per query walks the query's k_in exact hits (the certified search at k_fetch: ordered by
-// (float64 distance, id), unfilled slots id -1) in strips of 64 and keeps, in order, the first k_keep whose tag is not excluded;
-// the rest of the row is padded with id -1 / NaN.  The row is PROVED -- the exact top-k_keep among the admissible rows -- when
+struct ExclCompactParams {
+    const float* in_dist = nullptr;     // [nq, k_in] the fast pass's hits: the certified search at k_fetch, ordered by (float64 distance, id)
+    const int64_t* in_idx = nullptr;    // [nq, k_in] global ids, -1 = unfilled slot
+    const double* in_key = nullptr;     // [nq, k_in] float64 keys
+    int64_t nq = 0;
+    int k_in = 0, k_keep = 0;
+    int whole = 0;                      // the caller asked for more hits than the store has rows and the list was cut to them
+    const int64_t* tags = nullptr;      // [ntotal] row tags (read only when n_excl > 0)
+    int64_t ntotal = 0, id_base = 0;
+    const int64_t* excl = nullptr;      // [n_excl] ascending exclusion set
+    int64_t n_excl = 0;
+    float* out_dist = nullptr;          // [nq, k_keep]
+    int64_t* out_idx = nullptr;         // [nq, k_keep]
+    double* out_key = nullptr;          // [nq, k_keep]; optional unless FRONTIER
+    int* count = nullptr;               // !FRONTIER: [1] listed-query counter (device scope) ...
+    int* sel = nullptr;                 // ... and [nq] the listed queries
+    double* fr_key = nullptr;           // FRONTIER: [nq] frontier keys ...
+    int64_t* fr_idx = nullptr;          // ... ids, -1 = nothing of the shard is unseen ...
+    int* own = nullptr;                 // ... and [nq] 1 = the shard's list is short although rows are unseen
+};
+static_assert(std::is_trivially_copyable_v<ExclCompactParams>, "kernel argument");
+
+// Certificate + compaction: one wave per query walks the query's k_in exact hits (unfilled slots id -1) in strips of 64 and keeps,
+// in order, the first k_keep whose tag is not excluded; the rest of the row is padded with id -1 / NaN.
+// !FRONTIER (radad_knn_search_excl, the whole store): the row is PROVED -- the exact top-k_keep among the admissible rows -- when
 // it holds k_keep survivors (an admissible row outside the list ranks behind the whole list), or when the list is all the store
-// has (an unfilled slot, or `whole`: the caller asked for more hits than the store has rows and the list was cut to them).
-// Any other query is appended to sel[] (count[0], device scope) for the row-filtered exact pass, which overwrites its row.
-__global__ __launch_bounds__(256) void k_excl_compact(const float* __restrict__ in_dist, const int64_t* __restrict__ in_idx,
-                                                      const double* __restrict__ in_key, int64_t nq, int k_in, int k_keep, int whole,
-                                                      const int64_t* __restrict__ tags, int64_t ntotal, int64_t id_base,
-                                                      const int64_t* __restrict__ excl, int64_t n_excl, float* __restrict__ out_dist,
-                                                      int64_t* __restrict__ out_idx, double* __restrict__ out_key,
-                                                      int* __restrict__ count, int* __restrict__ sel) {
+// has (an unfilled slot, or `whole`).  Any other query is appended to sel[] (count[0]) for the row-filtered exact pass, which
+// overwrites its row.
+// FRONTIER (radad_knn_search_excl_begin, one shard of a row-sharded store): a shard cannot prove a query alone, so nothing is listed
+// here; instead the query gets a frontier (key, id): every admissible row of the shard that is not among the survivors written
+// ranks strictly behind it.  It is the k_keep-th survivor when there are k_keep; else the last hit of the fast-pass list
+// (admissible or not: the list is a prefix of the shard's ranking); else, when the list is all the shard has, id -1 / key NaN:
+// nothing is unseen.  own[q] = 1 for the query the other form would have listed: the only kind whose list the exact pass can
+// still change.
+template <bool FRONTIER>
+__global__ __launch_bounds__(256) void k_excl_compact(ExclCompactParams p) {
     const int lane = threadIdx.x & 63;
     const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (q >= nq) return;                                        // (wave-uniform)
+    if (q >= p.nq) return;                                      // (wave-uniform)
+    const int k_in = p.k_in, k_keep = p.k_keep;
+    const double nan64 = (double)__int_as_float(0x7fc00000);
     int kept = 0;
     bool unfilled = false;
     for (int s0 = 0; s0 < k_in && kept < k_keep; s0 += 64) {
@@ -2321,97 +2347,59 @@ __global__ __launch_bounds__(256) void k_excl_compact(const float* __restrict__ 
         int64_t id = -1;
         bool keep = false;
         if (j < k_in) {
-            id = in_idx[q * k_in + j];
-            const int64_t r = id - id_base;
-            keep = id >= 0 && r >= 0 && r < ntotal;
-            if (keep && n_excl > 0) keep = !excl_has(excl, n_excl, tags[r]);
+            id = p.in_idx[q * k_in + j];
+            const int64_t r = id - p.id_base;
+            keep = id >= 0 && r >= 0 && r < p.ntotal;
+            if (keep && p.n_excl > 0) keep = !excl_has(p.excl, p.n_excl, p.tags[r]);
         }
         unfilled |= __ballot(j < k_in && id < 0) != 0ull;
         const unsigned long long m = __ballot(keep);
         const int pos = kept + __popcll(m & ((1ull << lane) - 1ull));
         if (keep && pos < k_keep) {
-            out_idx[q * k_keep + pos] = id;
-            out_dist[q * k_keep + pos] = in_dist[q * k_in + j];
-            if (out_key) out_key[q * k_keep + pos] = in_key[q * k_in + j];
+            p.out_idx[q * k_keep + pos] = id;
+            p.out_dist[q * k_keep + pos] = p.in_dist[q * k_in + j];
+            if (FRONTIER || p.out_key) p.out_key[q * k_keep + pos] = p.in_key[q * k_in + j];
+            if constexpr (FRONTIER)
+                if (pos == k_keep - 1) { p.fr_key[q] = p.in_key[q * k_in + j]; p.fr_idx[q] = id; }
         }
         kept += __popcll(m);
     }
     kept = min(kept, k_keep);
     for (int o = kept + lane; o < k_keep; o += 64) {
-        out_idx[q * k_keep + o] = -1;
-        out_dist[q * k_keep + o] = __int_as_float(0x7fc00000);   // NaN, as pipeline.py:515
-        if (out_key) out_key[q * k_keep + o] = (double)__int_as_float(0x7fc00000);
+        p.out_idx[q * k_keep + o] = -1;
+        p.out_dist[q * k_keep + o] = __int_as_float(0x7fc00000);   // NaN, as pipeline.py:515
+        if (FRONTIER || p.out_key) p.out_key[q * k_keep + o] = nan64;
     }
-    if (lane == 0 && kept < k_keep && !unfilled && !whole) sel[atomicAdd(count, 1)] = (int)q;
+    if (lane != 0) return;
+    const bool unseen = kept < k_keep && !unfilled && !p.whole;    // (k_in >= 1: the store is not empty)
+    if constexpr (FRONTIER) {
+        if (kept < k_keep) {
+            p.fr_key[q] = unseen ? p.in_key[q * k_in + k_in - 1] : nan64;
+            p.fr_idx[q] = unseen ? p.in_idx[q * k_in + k_in - 1] : -1;
+        }
+        p.own[q] = unseen ? 1 : 0;
+    } else if (unseen) {
+        p.sel[atomicAdd(p.count, 1)] = (int)q;
+    }
 }
 
-// The admission bitmap of the row-filtered exact pass: bit (r & 63) of admit[r >> 6] = row r's tag is not excluded.  One thread per
-// row, one 64-bit word per wave.  Workgroups leave at once when no query was listed (the usual call).
-__global__ __launch_bounds__(256) void k_excl_bitmap(const int64_t* __restrict__ tags, int64_t ntotal, const int64_t* __restrict__ excl,
-                                                     int64_t n_excl, const int* __restrict__ count, unsigned long long* __restrict__ admit) {
-    if (*count == 0) return;
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;          // (ntotal rounded up to whole waves: every lane ballots)
-    const bool ok = r < ntotal && !excl_has(excl, n_excl, tags[r]);
+// The admission bitmap of the filtered passes: bit (i & 63) of admit[i >> 6] = the tag of row i is not in the ascending exclusion
+// set.  One thread per row, one ballot and one 64-bit word per wave; the host says how many words to write (the grid covers them).
+// !VIA_LIDS (the row-filtered exact pass, k_exact_scan_excl): i is the row itself.  VIA_LIDS (the IVF list scans): i is a list-major
+// position and the row is lids[i]; the host asks for one spare word behind the last, all zero.
+// count: workgroups leave at once when *count == 0, no query was listed (the flat search's usual call); NULL = always build.
+template <bool VIA_LIDS>
+__global__ __launch_bounds__(256) void k_admit_bitmap(const int64_t* __restrict__ tags, const int64_t* __restrict__ lids, int64_t n,
+                                                      const int64_t* __restrict__ excl, int64_t n_excl, const int* __restrict__ count,
+                                                      unsigned long long* __restrict__ admit, int64_t n_words) {
+    if (count && *count == 0) return;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;          // (whole waves: every lane ballots)
+    const bool ok = i < n && !excl_has(excl, n_excl, tags[VIA_LIDS ? lids[i] : i]);
     const unsigned long long m = __ballot(ok);
-    if ((threadIdx.x & 63) == 0 && (r >> 6) < ((ntotal + 63) >> 6)) admit[r >> 6] = m;
+    if ((threadIdx.x & 63) == 0 && (i >> 6) < n_words) admit[i >> 6] = m;
 }
 
 // ---- the same over ROW SHARDS (radad_knn_search_excl_begin / _finish, radad_excl_merge_certify) -------------------------------------
-// Compaction with frontier: k_excl_compact's walk for one shard of a row-sharded store.  A shard cannot prove a query alone, so
-// nothing is listed here; instead the query gets a FRONTIER (key, id): every admissible row of the shard that is not among the
-// survivors written ranks strictly behind it.  It is the k_keep-th survivor when there are k_keep; else the last hit of the
-// fast-pass list (admissible or not: the list is a prefix of the shard's ranking); else, when the list is all the shard has (an
-// unfilled slot, or `whole`), id -1 / key NaN: nothing is unseen.  own[q] = 1 where the shard's list is short although rows are
-// unseen -- the query k_excl_compact would have listed, and the only kind whose list the exact pass can still change.
-__global__ __launch_bounds__(256) void k_excl_compact_frontier(const float* __restrict__ in_dist, const int64_t* __restrict__ in_idx,
-                                                               const double* __restrict__ in_key, int64_t nq, int k_in, int k_keep,
-                                                               int whole, const int64_t* __restrict__ tags, int64_t ntotal,
-                                                               int64_t id_base, const int64_t* __restrict__ excl, int64_t n_excl,
-                                                               float* __restrict__ out_dist, int64_t* __restrict__ out_idx,
-                                                               double* __restrict__ out_key, double* __restrict__ fr_key,
-                                                               int64_t* __restrict__ fr_idx, int* __restrict__ own) {
-    const int lane = threadIdx.x & 63;
-    const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (q >= nq) return;                                        // (wave-uniform)
-    int kept = 0;
-    bool unfilled = false;
-    for (int s0 = 0; s0 < k_in && kept < k_keep; s0 += 64) {
-        const int j = s0 + lane;
-        int64_t id = -1;
-        bool keep = false;
-        if (j < k_in) {
-            id = in_idx[q * k_in + j];
-            const int64_t r = id - id_base;
-            keep = id >= 0 && r >= 0 && r < ntotal;
-            if (keep && n_excl > 0) keep = !excl_has(excl, n_excl, tags[r]);
-        }
-        unfilled |= __ballot(j < k_in && id < 0) != 0ull;
-        const unsigned long long m = __ballot(keep);
-        const int pos = kept + __popcll(m & ((1ull << lane) - 1ull));
-        if (keep && pos < k_keep) {
-            out_idx[q * k_keep + pos] = id;
-            out_dist[q * k_keep + pos] = in_dist[q * k_in + j];
-            out_key[q * k_keep + pos] = in_key[q * k_in + j];
-            if (pos == k_keep - 1) { fr_key[q] = in_key[q * k_in + j]; fr_idx[q] = id; }
-        }
-        kept += __popcll(m);
-    }
-    kept = min(kept, k_keep);
-    for (int o = kept + lane; o < k_keep; o += 64) {
-        out_idx[q * k_keep + o] = -1;
-        out_dist[q * k_keep + o] = __int_as_float(0x7fc00000);   // NaN, as pipeline.py:515
-        out_key[q * k_keep + o] = (double)__int_as_float(0x7fc00000);
-    }
-    if (lane == 0) {
-        const bool unseen = kept < k_keep && !unfilled && !whole;          // (k_in >= 1: the store is not empty)
-        if (kept < k_keep) {
-            fr_key[q] = unseen ? in_key[q * k_in + k_in - 1] : (double)__int_as_float(0x7fc00000);
-            fr_idx[q] = unseen ? in_idx[q * k_in + k_in - 1] : -1;
-        }
-        own[q] = unseen ? 1 : 0;
-    }
-}
-
 // Flags to list: the queries the shards could not prove together (unproved[q] != 0) and whose list on THIS shard the exact pass can
 // change (own[q]) become the sel[] / count pair the row-filtered exact pass reads.  A flagged query whose shard list is full, or is
 // all the shard has, already holds the shard's exact admissible top k.
@@ -3916,7 +3904,7 @@ static int knn_search_core(radad_knn_t h, const void* q_in, int q_dtype, int64_t
 }
 
 // ---- exclusion-aware search ---------------------------------------------------------------------------------------------------------
-// fast pass = the certified search at k_fetch (every scan path, float64 keys) -> k_excl_compact: certificate per query, results of the
+// fast pass = the certified search at k_fetch (every scan path, float64 keys) -> k_excl_compact<false>: certificate per query, results of the
 // proved ones -> k_exact_scan_excl for the listed ones, sized and driven by the device-side count like the exact pass of any search.
 static ExclLayout knn_excl_layout(radad_knn_t h, int64_t nq, int k, int k_fetch, int64_t n_excl, bool begun) {
     ExclLayout L;
@@ -3963,8 +3951,8 @@ static int knn_excl_exact_pass(radad_knn_t h, const ExclLayout& L, int64_t nq, i
     auto at = [&](size_t o) { return (char*)h->excl_ws + o; };
     int* count = (int*)at(L.count);
     unsigned long long* admit = (unsigned long long*)at(L.admit);
-    hipLaunchKernelGGL(k_excl_bitmap, dim3((unsigned)ceil_div64(L.n_words * 64, 256)), dim3(256), 0, st, tags, h->ntotal, excl, n_excl,
-                       (const int*)count, admit);
+    hipLaunchKernelGGL(k_admit_bitmap<false>, dim3((unsigned)ceil_div64(L.n_words * 64, 256)), dim3(256), 0, st, tags, (const int64_t*)nullptr,
+                       h->ntotal, excl, n_excl, (const int*)count, admit, L.n_words);
     RADAD_HIP_CHECK(hipGetLastError());
     ExactParams x;
     x.db = h->rows; x.db_f16 = h->f16; x.q = q_use; x.sel = (int*)at(L.sel); x.count = count;
@@ -3988,52 +3976,77 @@ static int knn_excl_exact_pass(radad_knn_t h, const ExclLayout& L, int64_t nq, i
     return RADAD_OK;
 }
 
-static int knn_search_excl_locked(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* tags,
-                                  const int64_t* excl, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
-                                  hipStream_t st) {
-    const ExclLayout L = knn_excl_layout(h, nq, k, k_fetch, n_excl, false);
+// the part the whole-store call and the shard's first half share: layout -> workspace -> the fast pass at kf into fd / fi / fk ->
+// compaction into out_* (begun: into the workspace's bd / bi / bk, with frontier and own flags instead of the listing)
+static int knn_excl_fast_pass(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* tags,
+                              const int64_t* excl, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
+                              double* fr_key_dev, int64_t* fr_idx_dev, hipStream_t st, bool begun, SearchCtx* c, ExclLayout* Lout) {
+    const ExclLayout L = knn_excl_layout(h, nq, k, k_fetch, n_excl, begun);
     int rc = knn_excl_reserve(h, L.bytes);
     if (rc) return rc;
     auto at = [&](size_t o) { return (char*)h->excl_ws + o; };
-    SearchCtx c;
-    rc = knn_search_locked(h, q_in, q_dtype, nq, L.kf, KNN_MARGIN, (float*)at(L.fd), (int64_t*)at(L.fi), (double*)at(L.fk), st, &c);
+    rc = knn_search_locked(h, q_in, q_dtype, nq, L.kf, KNN_MARGIN, (float*)at(L.fd), (int64_t*)at(L.fi), (double*)at(L.fk), st, c);
     if (rc) return rc;
-    int* count = (int*)at(L.count);
-    int* sel = (int*)at(L.sel);
-    RADAD_HIP_CHECK(hipMemsetAsync(count, 0, 256, st));
-    hipLaunchKernelGGL(k_excl_compact, dim3((unsigned)ceil_div64(nq, 4)), dim3(256), 0, st, (const float*)at(L.fd), (const int64_t*)at(L.fi),
-                       (const double*)at(L.fk), nq, L.kf, k, L.whole, tags, h->ntotal, h->id_base, excl, n_excl, out_dist_dev, out_idx_dev,
-                       out_key_dev, count, sel);
+    RADAD_HIP_CHECK(hipMemsetAsync(at(L.count), 0, 256, st));
+    ExclCompactParams p;
+    p.in_dist = (const float*)at(L.fd); p.in_idx = (const int64_t*)at(L.fi); p.in_key = (const double*)at(L.fk);
+    p.nq = nq; p.k_in = L.kf; p.k_keep = k; p.whole = L.whole;
+    p.tags = tags; p.ntotal = h->ntotal; p.id_base = h->id_base; p.excl = excl; p.n_excl = n_excl;
+    p.out_dist = begun ? (float*)at(L.bd) : out_dist_dev;
+    p.out_idx = begun ? (int64_t*)at(L.bi) : out_idx_dev;
+    p.out_key = begun ? (double*)at(L.bk) : out_key_dev;
+    p.count = (int*)at(L.count); p.sel = (int*)at(L.sel);
+    p.fr_key = fr_key_dev; p.fr_idx = fr_idx_dev; p.own = begun ? (int*)at(L.own) : nullptr;
+    const dim3 grid((unsigned)ceil_div64(nq, 4));
+    if (begun) hipLaunchKernelGGL(k_excl_compact<true>, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(k_excl_compact<false>, grid, dim3(256), 0, st, p);
     RADAD_HIP_CHECK(hipGetLastError());
     h->excl_o_count = L.count;
     h->last_excl_nq = nq;
+    *Lout = L;
+    return RADAD_OK;
+}
+
+static int knn_search_excl_locked(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* tags,
+                                  const int64_t* excl, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
+                                  hipStream_t st) {
+    SearchCtx c;
+    ExclLayout L;
+    int rc = knn_excl_fast_pass(h, q_in, q_dtype, nq, k, k_fetch, tags, excl, n_excl, out_dist_dev, out_idx_dev, out_key_dev, nullptr,
+                                nullptr, st, false, &c, &L);
+    if (rc) return rc;
     if (n_excl == 0) return RADAD_OK;                          // nothing excluded: every query is proved by its own list
     return knn_excl_exact_pass(h, L, nq, k, c.l2, c.q_use, tags, excl, n_excl, out_dist_dev, out_idx_dev, out_key_dev, st);
 }
 
-// first half over a row shard: the fast pass at k_fetch, then the compaction with frontier into the workspace; the caller gets copies
+// first half over a row shard: the fast pass with frontier into the workspace; the caller gets copies
 static int knn_search_excl_begin_locked(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* tags,
                                         const int64_t* excl, int64_t n_excl, double* out_key_dev, int64_t* out_idx_dev,
                                         double* fr_key_dev, int64_t* fr_idx_dev, hipStream_t st) {
-    const ExclLayout L = knn_excl_layout(h, nq, k, k_fetch, n_excl, true);
-    int rc = knn_excl_reserve(h, L.bytes);
+    SearchCtx c;
+    ExclLayout L;
+    int rc = knn_excl_fast_pass(h, q_in, q_dtype, nq, k, k_fetch, tags, excl, n_excl, nullptr, nullptr, nullptr, fr_key_dev, fr_idx_dev,
+                                st, true, &c, &L);
     if (rc) return rc;
     auto at = [&](size_t o) { return (char*)h->excl_ws + o; };
-    SearchCtx c;
-    rc = knn_search_locked(h, q_in, q_dtype, nq, L.kf, KNN_MARGIN, (float*)at(L.fd), (int64_t*)at(L.fi), (double*)at(L.fk), st, &c);
-    if (rc) return rc;
-    RADAD_HIP_CHECK(hipMemsetAsync(at(L.count), 0, 256, st));
-    hipLaunchKernelGGL(k_excl_compact_frontier, dim3((unsigned)ceil_div64(nq, 4)), dim3(256), 0, st, (const float*)at(L.fd),
-                       (const int64_t*)at(L.fi), (const double*)at(L.fk), nq, L.kf, k, L.whole, tags, h->ntotal, h->id_base, excl, n_excl,
-                       (float*)at(L.bd), (int64_t*)at(L.bi), (double*)at(L.bk), fr_key_dev, fr_idx_dev, (int*)at(L.own));
-    RADAD_HIP_CHECK(hipGetLastError());
     RADAD_HIP_CHECK(hipMemcpyAsync(out_key_dev, at(L.bk), (size_t)nq * k * sizeof(double), hipMemcpyDeviceToDevice, st));
     RADAD_HIP_CHECK(hipMemcpyAsync(out_idx_dev, at(L.bi), (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     RADAD_HIP_CHECK(hipEventRecord(h->ev_begun, st));
-    h->excl_o_count = L.count;
-    h->last_excl_nq = nq;
     ExclCtx& e = h->pending_excl;
     e.valid = true; e.nq = nq; e.n_excl = n_excl; e.k = k; e.l2 = c.l2; e.q_use = c.q_use; e.tags = tags; e.excl = excl; e.L = L;
+    return RADAD_OK;
+}
+
+// the argument checks radad_knn_search_excl and radad_knn_search_excl_begin share (nq_min: the latter refuses an empty batch)
+static int knn_excl_check_args(const char* fn, radad_knn_t h, int q_dtype, int64_t nq, int64_t nq_min, int k, int k_fetch,
+                               const int64_t* row_tags_dev, const int64_t* excl_sorted_dev, int64_t n_excl) {
+    RADAD_REQUIRE(h, "NULL handle");
+    RADAD_REQUIRE(q_dtype == RADAD_Q_F32 || q_dtype == RADAD_Q_BF16, "%s: unsupported query dtype %d", fn, q_dtype);
+    RADAD_REQUIRE(k >= 1 && k <= RADAD_KNN_MAX_K, "%s: k=%d outside [1,%d]", fn, k, RADAD_KNN_MAX_K);
+    RADAD_REQUIRE(k_fetch >= k && k_fetch <= RADAD_KNN_MAX_K, "%s: k_fetch=%d outside [k=%d,%d]", fn, k_fetch, k, RADAD_KNN_MAX_K);
+    RADAD_REQUIRE(nq >= nq_min && nq < (1ll << 31) - KT_N, "%s: bad nq", fn);
+    RADAD_REQUIRE(n_excl >= 0 && (n_excl == 0 || (excl_sorted_dev && row_tags_dev)),
+                  "%s: %lld excluded tags need the exclusion set and the row tags", fn, (long long)n_excl);
     return RADAD_OK;
 }
 
@@ -4080,13 +4093,8 @@ int radad_knn_search_finish(radad_knn_t h, const float* global_lower_bound_dev, 
 int radad_knn_search_excl(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* row_tags_dev,
                           const int64_t* excl_sorted_dev, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
                           void* stream) {
-    RADAD_REQUIRE(h, "NULL handle");
-    RADAD_REQUIRE(q_dtype == RADAD_Q_F32 || q_dtype == RADAD_Q_BF16, "radad_knn_search_excl: unsupported query dtype %d", q_dtype);
-    RADAD_REQUIRE(k >= 1 && k <= RADAD_KNN_MAX_K, "radad_knn_search_excl: k=%d outside [1,%d]", k, RADAD_KNN_MAX_K);
-    RADAD_REQUIRE(k_fetch >= k && k_fetch <= RADAD_KNN_MAX_K, "radad_knn_search_excl: k_fetch=%d outside [k=%d,%d]", k_fetch, k, RADAD_KNN_MAX_K);
-    RADAD_REQUIRE(nq >= 0 && nq < (1ll << 31) - KT_N, "radad_knn_search_excl: bad nq");
-    RADAD_REQUIRE(n_excl >= 0 && (n_excl == 0 || (excl_sorted_dev && row_tags_dev)),
-                  "radad_knn_search_excl: %lld excluded tags need the exclusion set and the row tags", (long long)n_excl);
+    const int bad = knn_excl_check_args("radad_knn_search_excl", h, q_dtype, nq, 0, k, k_fetch, row_tags_dev, excl_sorted_dev, n_excl);
+    if (bad) return bad;
     if (nq == 0) return RADAD_OK;
     RADAD_REQUIRE(q_dev && out_dist_dev && out_idx_dev, "radad_knn_search_excl: NULL buffer");
     std::lock_guard<std::mutex> lk(h->mu);
@@ -4112,13 +4120,8 @@ int radad_knn_last_excl(radad_knn_t h, int64_t* n_queries, int* n_exact) {
 int radad_knn_search_excl_begin(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* row_tags_dev,
                                 const int64_t* excl_sorted_dev, int64_t n_excl, double* out_key_dev, int64_t* out_idx_dev,
                                 double* frontier_key_dev, int64_t* frontier_idx_dev, void* stream) {
-    RADAD_REQUIRE(h, "NULL handle");
-    RADAD_REQUIRE(q_dtype == RADAD_Q_F32 || q_dtype == RADAD_Q_BF16, "radad_knn_search_excl_begin: unsupported query dtype %d", q_dtype);
-    RADAD_REQUIRE(k >= 1 && k <= RADAD_KNN_MAX_K, "radad_knn_search_excl_begin: k=%d outside [1,%d]", k, RADAD_KNN_MAX_K);
-    RADAD_REQUIRE(k_fetch >= k && k_fetch <= RADAD_KNN_MAX_K, "radad_knn_search_excl_begin: k_fetch=%d outside [k=%d,%d]", k_fetch, k, RADAD_KNN_MAX_K);
-    RADAD_REQUIRE(nq > 0 && nq < (1ll << 31) - KT_N, "radad_knn_search_excl_begin: bad nq");
-    RADAD_REQUIRE(n_excl >= 0 && (n_excl == 0 || (excl_sorted_dev && row_tags_dev)),
-                  "radad_knn_search_excl_begin: %lld excluded tags need the exclusion set and the row tags", (long long)n_excl);
+    const int bad = knn_excl_check_args("radad_knn_search_excl_begin", h, q_dtype, nq, 1, k, k_fetch, row_tags_dev, excl_sorted_dev, n_excl);
+    if (bad) return bad;
     RADAD_REQUIRE(q_dev && out_key_dev && out_idx_dev && frontier_key_dev && frontier_idx_dev, "radad_knn_search_excl_begin: NULL buffer");
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);

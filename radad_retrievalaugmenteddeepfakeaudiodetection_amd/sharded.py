@@ -58,6 +58,22 @@ def _hip_certify(metric, keys, ids, fkeys, fids):
     return HipFlatIndex.excl_merge_certify(metric, keys, ids, fkeys, fids)
 
 
+class _Halves:
+    """a (begin, finish[, abort]) triple.  Between begin and finish the shard holds a begun search: whatever goes wrong in between (a
+    collective that throws, a kernel that refuses its shape), the second half must still run -- or be given up -- or every later
+    search on the index fails with "has not been finished"."""
+
+    def __init__(self, triple):
+        self.begin, self.finish = triple[0], triple[1]
+        self.abort = triple[2] if len(triple) > 2 else None
+
+    def give_up(self):
+        if self.abort is not None:
+            self.abort()
+        else:
+            self.finish(None)              # (the shard's own result: a valid, if unbounded, second half)
+
+
 class ShardedSearch:
     """Collective search over per-rank shards.
 
@@ -160,6 +176,21 @@ class ShardedSearch:
     def gather_queries(self, q_local):
         return q_local if self.world == 1 else self._all_gather(q_local)
 
+    def _pad_uneven(self, q_local):
+        """-> (q_local, rows per rank, counts): with uneven=True one all-gather of the ranks' query counts, and the local block padded
+        to the largest with zero queries (their results are dropped by the caller); else as it came, counts None"""
+        import torch
+        qr = q_local.shape[0]
+        if not self.uneven:
+            return q_local, qr, None
+        c = torch.tensor([qr], dtype=torch.int64, device=q_local.device)
+        counts = [int(x) for x in self._all_gather(c).cpu().tolist()]
+        qmax = max(max(counts), 1)
+        if qr < qmax:
+            pad = torch.zeros((qmax - qr,) + tuple(q_local.shape[1:]), device=q_local.device, dtype=q_local.dtype)
+            q_local = torch.cat([q_local, pad])
+        return q_local, qmax, counts
+
     def _gather_exclusion(self, excl_local, device):
         """the ranks' exclusion tags -> their sorted union [n] int64 on `device` (counts first, then blocks padded to the largest)"""
         import torch
@@ -202,28 +233,14 @@ class ShardedSearch:
             return d_loc.float(), i_loc
         if self.excluding is None:
             raise ValueError("search_excluding needs excluding=(begin, finish[, abort]) (HipFlatIndex.sharded_excluding)")
-        begin, finish = self.excluding[0], self.excluding[1]
-        abort = self.excluding[2] if len(self.excluding) > 2 else None
+        halves = _Halves(self.excluding)
         k = int(k)
         excl = self._gather_exclusion(exclude_tags_local, q_local.device)
         qr = q_local.shape[0]
-        qr_pad = qr
-        if self.uneven:
-            c = torch.tensor([qr], dtype=torch.int64, device=q_local.device)
-            qr_pad = max(max(int(x) for x in self._all_gather(c).cpu().tolist()), 1)
-            if qr < qr_pad:                                 # pad with copies of a zero query: results are dropped below
-                pad = torch.zeros((qr_pad - qr,) + tuple(q_local.shape[1:]), device=q_local.device, dtype=q_local.dtype)
-                q_local = torch.cat([q_local, pad])
+        q_local, qr_pad, _ = self._pad_uneven(q_local)
         q_all = self._all_gather(q_local)
-        key, gid, fkey, fgid = begin(q_all, k, excl, k_fetch)
+        key, gid, fkey, fgid = halves.begin(q_all, k, excl, k_fetch)
         done = False
-
-        def give_up():
-            if abort is not None:
-                abort()
-            else:
-                finish(None)
-
         try:
             # frontiers ride as column k of the lists: two exchanges instead of four
             xk = self._exchange(torch.cat([key, fkey.view(-1, 1)], dim=1), qr_pad)
@@ -234,14 +251,14 @@ class ShardedSearch:
             flags[qr:] = 0                                  # (padding queries need no proof)
             flags_all = self._all_gather(flags)
             if int(flags_all.max().item()) == 0:            # the one host read; the same value on every rank
-                give_up()
+                halves.give_up()
                 done = True
                 return md[:qr].float(), mi[:qr]
             done = True
-            key2, gid2 = finish(flags_all)
+            key2, gid2 = halves.finish(flags_all)
         except BaseException:
             if not done:
-                give_up()
+                halves.give_up()
             raise
         md, mi = self.merge(self.metric, self._exchange(key2, qr_pad), self._exchange(gid2, qr_pad), k)
         md = md.float().masked_fill(mi < 0, float("nan"))   # the exclusion family's padding (the plain merge pads with +-inf)
@@ -255,17 +272,7 @@ class ShardedSearch:
             d_loc, i_loc = self.local_search(q_local, k)
             return d_loc.float(), i_loc
         qr = q_local.shape[0]
-        counts = None
-        if self.uneven:
-            c = torch.tensor([qr], dtype=torch.int64, device=q_local.device)
-            counts = [int(x) for x in self._all_gather(c).cpu().tolist()]
-            qmax = max(max(counts), 1)
-            if qr < qmax:                                   # pad with copies of a zero query: results are dropped below
-                pad = torch.zeros((qmax - qr,) + tuple(q_local.shape[1:]), device=q_local.device, dtype=q_local.dtype)
-                q_local = torch.cat([q_local, pad])
-            qr_pad = qmax
-        else:
-            qr_pad = qr
+        q_local, qr_pad, counts = self._pad_uneven(q_local)
         import contextlib
         rec = self.timing and q_local.is_cuda
         coll_ev, rr_ev = [], None
@@ -288,12 +295,8 @@ class ShardedSearch:
         with timed("c"):
             q_all = self._all_gather(q_local)
         if self.bounded is not None:
-            begin, finish = self.bounded[0], self.bounded[1]
-            abort = self.bounded[2] if len(self.bounded) > 2 else None
-            lb = begin(q_all, k)
-            # Between begin and finish the shard holds a begun search: whatever goes wrong in the exchange (a collective that throws,
-            # a bound kernel that refuses its shape), the second half must still run -- or be given up -- or every later search on
-            # this index fails with "has not been finished".
+            halves = _Halves(self.bounded)
+            lb = halves.begin(q_all, k)
             try:
                 with timed("c"):
                     if lb.dim() == 2:      # the k best of every shard: the k-th largest of the union bounds the global k-th best
@@ -303,13 +306,10 @@ class ShardedSearch:
                     else:
                         lb = self._all_reduce_max(lb)
             except BaseException:
-                if abort is not None:
-                    abort()
-                else:
-                    finish(None)                                      # (this shard's own top k: a valid, if unbounded, second half)
+                halves.give_up()
                 raise
             with timed("r"):
-                d_loc, i_loc = finish(lb)
+                d_loc, i_loc = halves.finish(lb)
         else:
             d_loc, i_loc = self.local_search(q_all, k)
         Q = q_all.shape[0]

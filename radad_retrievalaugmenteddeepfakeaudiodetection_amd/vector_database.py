@@ -85,6 +85,46 @@ def knn_options_from_config(config):
     return {k: v for k, v in opts.items() if v is not None}
 
 
+def _prep_queries(q, d: int):
+    """q -> (q, q_dtype): a contiguous [nq, d] CUDA tensor as the library reads it (bfloat16 as it is, anything else as float32)"""
+    import torch
+    _lib.require_cuda(q, "q")
+    bf16 = q.dtype == torch.bfloat16
+    q = q.contiguous() if bf16 else q.contiguous().float()
+    if q.dim() != 2 or q.shape[1] != d:
+        raise ValueError(f"search expects [nq, {d}], got {tuple(q.shape)}")
+    return q, _lib.Q_BF16 if bf16 else _lib.Q_F32
+
+
+def _prep_tags(row_tags, exclude_tags, ntotal: int):
+    """-> (row_tags, exclude_tags, n_excl): flat contiguous int64 CUDA tensors, one tag per stored row; (None, None, 0) when nothing
+    is excluded (the row tags are not looked at then)"""
+    import torch
+    n_excl = 0 if exclude_tags is None else int(exclude_tags.numel())
+    if not n_excl:
+        return None, None, 0
+    _lib.require_cuda(exclude_tags, "exclude_tags")
+    _lib.require_cuda(row_tags, "row_tags")
+    exclude_tags = exclude_tags.contiguous().to(torch.int64).reshape(-1)
+    row_tags = row_tags.contiguous().to(torch.int64).reshape(-1)
+    if row_tags.numel() != ntotal:
+        raise ValueError(f"row_tags must hold one tag per stored row ({ntotal}), got {row_tags.numel()}")
+    return row_tags, exclude_tags, n_excl
+
+
+def _alloc_out(q, k: int, f64: bool = False):
+    """-> (D f32, I i64, K64 f64 or None), each [nq, k] on q's device"""
+    import torch
+    D = torch.empty((q.shape[0], k), device=q.device, dtype=torch.float32)
+    I = torch.empty((q.shape[0], k), device=q.device, dtype=torch.int64)
+    K64 = torch.empty((q.shape[0], k), device=q.device, dtype=torch.float64) if f64 else None
+    return D, I, K64
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
 class HipFlatIndex:
     """Flat (exhaustive) index living in HBM.  Mirrors the slice of faiss.IndexFlat{L2,IP} the reference uses."""
 
@@ -165,18 +205,11 @@ class HipFlatIndex:
         they are) -> (D f32 [nq,k], I i64 [nq,k]) on the device; with return_f64 also the float64 distances the ranking
         was made on (used by the sharded merge)."""
         import torch
-        _lib.require_cuda(q, "q")
-        bf16 = q.dtype == torch.bfloat16
-        q = q.contiguous() if bf16 else q.contiguous().float()
-        if q.dim() != 2 or q.shape[1] != self.d:
-            raise ValueError(f"search expects [nq, {self.d}], got {tuple(q.shape)}")
-        D = torch.empty((q.shape[0], k), device=q.device, dtype=torch.float32)
-        I = torch.empty((q.shape[0], k), device=q.device, dtype=torch.int64)
-        K64 = torch.empty((q.shape[0], k), device=q.device, dtype=torch.float64) if return_f64 else None
+        q, q_dtype = _prep_queries(q, self.d)
+        D, I, K64 = _alloc_out(q, k, return_f64)
         with torch.cuda.device(q.device):
-            _lib.check(self._lib.radad_knn_search_ex(self._h, q.data_ptr(), _lib.Q_BF16 if bf16 else _lib.Q_F32, q.shape[0], int(k),
-                                                     D.data_ptr(), I.data_ptr(), K64.data_ptr() if return_f64 else None,
-                                                     _lib.stream_ptr(q.device)), "radad_knn_search")
+            _lib.check(self._lib.radad_knn_search_ex(self._h, q.data_ptr(), q_dtype, q.shape[0], int(k), D.data_ptr(), I.data_ptr(),
+                                                     _ptr(K64), _lib.stream_ptr(q.device)), "radad_knn_search")
         return (D, I, K64) if return_f64 else (D, I)
 
     def search_excluding(self, q, k: int, row_tags, exclude_tags, k_fetch=None, return_f64: bool = False):
@@ -186,30 +219,15 @@ class HipFlatIndex:
         k_fetch (None = k + 10, the reference's over-fetch) is the size of the certified search in front: a query that does not find
         k admissible rows among its k_fetch hits is answered by the float64 scan of the admissible rows (last_excl()["exact"])."""
         import torch
-        _lib.require_cuda(q, "q")
-        bf16 = q.dtype == torch.bfloat16
-        q = q.contiguous() if bf16 else q.contiguous().float()
-        if q.dim() != 2 or q.shape[1] != self.d:
-            raise ValueError(f"search expects [nq, {self.d}], got {tuple(q.shape)}")
+        q, q_dtype = _prep_queries(q, self.d)
         k = int(k)
         k_fetch = min(k + 10, _lib.KNN_MAX_K) if k_fetch is None else int(k_fetch)
-        n_excl = 0 if exclude_tags is None else int(exclude_tags.numel())
-        if n_excl:
-            _lib.require_cuda(exclude_tags, "exclude_tags")
-            _lib.require_cuda(row_tags, "row_tags")
-            exclude_tags = exclude_tags.contiguous().to(torch.int64).reshape(-1)
-            row_tags = row_tags.contiguous().to(torch.int64).reshape(-1)
-            if row_tags.numel() != self.ntotal:
-                raise ValueError(f"row_tags must hold one tag per stored row ({self.ntotal}), got {row_tags.numel()}")
-        D = torch.empty((q.shape[0], max(k, 0)), device=q.device, dtype=torch.float32)
-        I = torch.empty((q.shape[0], max(k, 0)), device=q.device, dtype=torch.int64)
-        K64 = torch.empty((q.shape[0], max(k, 0)), device=q.device, dtype=torch.float64) if return_f64 else None
+        row_tags, exclude_tags, n_excl = _prep_tags(row_tags, exclude_tags, self.ntotal)
+        D, I, K64 = _alloc_out(q, max(k, 0), return_f64)
         with torch.cuda.device(q.device):
-            _lib.check(self._lib.radad_knn_search_excl(self._h, q.data_ptr(), _lib.Q_BF16 if bf16 else _lib.Q_F32, q.shape[0], k, k_fetch,
-                                                       row_tags.data_ptr() if n_excl else None,
-                                                       exclude_tags.data_ptr() if n_excl else None, n_excl, D.data_ptr(), I.data_ptr(),
-                                                       K64.data_ptr() if return_f64 else None, _lib.stream_ptr(q.device)),
-                       "radad_knn_search_excl")
+            _lib.check(self._lib.radad_knn_search_excl(self._h, q.data_ptr(), q_dtype, q.shape[0], k, k_fetch, _ptr(row_tags),
+                                                       _ptr(exclude_tags), n_excl, D.data_ptr(), I.data_ptr(), _ptr(K64),
+                                                       _lib.stream_ptr(q.device)), "radad_knn_search_excl")
         return (D, I, K64) if return_f64 else (D, I)
 
     def last_excl(self):
@@ -226,35 +244,22 @@ class HipFlatIndex:
         shard that is not listed ranks; FI -1 (FK NaN) = the list is all the shard has.  Arguments as search_excluding.  The index
         then holds a begun search until search_excluding_finish or search_abort; q, row_tags and exclude_tags are kept alive."""
         import torch
-        _lib.require_cuda(q, "q")
-        bf16 = q.dtype == torch.bfloat16
-        q = q.contiguous() if bf16 else q.contiguous().float()
-        if q.dim() != 2 or q.shape[1] != self.d:
-            raise ValueError(f"search expects [nq, {self.d}], got {tuple(q.shape)}")
+        q, q_dtype = _prep_queries(q, self.d)
         if q.shape[0] == 0:
             raise ValueError("search_excluding_begin needs at least one query")
         k = int(k)
         k_fetch = min(k + 10, _lib.KNN_MAX_K) if k_fetch is None else int(k_fetch)
-        n_excl = 0 if exclude_tags is None else int(exclude_tags.numel())
-        if n_excl:
-            _lib.require_cuda(exclude_tags, "exclude_tags")
-            _lib.require_cuda(row_tags, "row_tags")
-            exclude_tags = exclude_tags.contiguous().to(torch.int64).reshape(-1)
-            row_tags = row_tags.contiguous().to(torch.int64).reshape(-1)
-            if row_tags.numel() != self.ntotal:
-                raise ValueError(f"row_tags must hold one tag per stored row ({self.ntotal}), got {row_tags.numel()}")
+        row_tags, exclude_tags, n_excl = _prep_tags(row_tags, exclude_tags, self.ntotal)
         nq = q.shape[0]
         K64 = torch.empty((nq, max(k, 0)), device=q.device, dtype=torch.float64)
         I = torch.empty((nq, max(k, 0)), device=q.device, dtype=torch.int64)
         FK = torch.empty((nq,), device=q.device, dtype=torch.float64)
         FI = torch.empty((nq,), device=q.device, dtype=torch.int64)
         with torch.cuda.device(q.device):
-            _lib.check(self._lib.radad_knn_search_excl_begin(self._h, q.data_ptr(), _lib.Q_BF16 if bf16 else _lib.Q_F32, nq, k, k_fetch,
-                                                             row_tags.data_ptr() if n_excl else None,
-                                                             exclude_tags.data_ptr() if n_excl else None, n_excl, K64.data_ptr(),
-                                                             I.data_ptr(), FK.data_ptr(), FI.data_ptr(), _lib.stream_ptr(q.device)),
-                       "radad_knn_search_excl_begin")
-        self._begun_excl = (q, k, row_tags if n_excl else None, exclude_tags if n_excl else None)
+            _lib.check(self._lib.radad_knn_search_excl_begin(self._h, q.data_ptr(), q_dtype, nq, k, k_fetch, _ptr(row_tags),
+                                                             _ptr(exclude_tags), n_excl, K64.data_ptr(), I.data_ptr(), FK.data_ptr(),
+                                                             FI.data_ptr(), _lib.stream_ptr(q.device)), "radad_knn_search_excl_begin")
+        self._begun_excl = (q, k, row_tags, exclude_tags)
         return K64, I, FK, FI
 
     def search_excluding_finish(self, unproved=None, return_f64: bool = False):
@@ -272,14 +277,11 @@ class HipFlatIndex:
             unproved = unproved.contiguous().to(torch.int32).reshape(-1)
             if unproved.numel() != q.shape[0]:
                 raise ValueError("unproved must hold one flag per query")
-        D = torch.empty((q.shape[0], k), device=q.device, dtype=torch.float32)
-        I = torch.empty((q.shape[0], k), device=q.device, dtype=torch.int64)
-        K64 = torch.empty((q.shape[0], k), device=q.device, dtype=torch.float64) if return_f64 else None
+        D, I, K64 = _alloc_out(q, k, return_f64)
         keep = self._begun_excl                # (alive until the call below has been enqueued on this stream)
         self._begun_excl = None
         with torch.cuda.device(q.device):
-            _lib.check(self._lib.radad_knn_search_excl_finish(self._h, unproved.data_ptr() if unproved is not None else None,
-                                                              D.data_ptr(), I.data_ptr(), K64.data_ptr() if return_f64 else None,
+            _lib.check(self._lib.radad_knn_search_excl_finish(self._h, _ptr(unproved), D.data_ptr(), I.data_ptr(), _ptr(K64),
                                                               _lib.stream_ptr(q.device)), "radad_knn_search_excl_finish")
         del keep
         return (D, I, K64) if return_f64 else (D, I)
@@ -320,14 +322,10 @@ class HipFlatIndex:
         there is none).  The caller gathers them from all shards; the k-th largest of a query's G k values (global_bound below) is
         what search_finish takes."""
         import torch
-        _lib.require_cuda(q, "q")
-        bf16 = q.dtype == torch.bfloat16
-        q = q.contiguous() if bf16 else q.contiguous().float()
-        if q.dim() != 2 or q.shape[1] != self.d:
-            raise ValueError(f"search expects [nq, {self.d}], got {tuple(q.shape)}")
+        q, q_dtype = _prep_queries(q, self.d)
         lb = torch.empty((q.shape[0], int(k)), device=q.device, dtype=torch.float32)
         with torch.cuda.device(q.device):
-            _lib.check(self._lib.radad_knn_search_begin(self._h, q.data_ptr(), _lib.Q_BF16 if bf16 else _lib.Q_F32, q.shape[0], int(k),
+            _lib.check(self._lib.radad_knn_search_begin(self._h, q.data_ptr(), q_dtype, q.shape[0], int(k),
                                                         lb.data_ptr(), _lib.stream_ptr(q.device)), "radad_knn_search_begin")
         self._begun = (q, int(k))          # (keeps the queries alive until the second half has read them)
         return lb
@@ -356,17 +354,14 @@ class HipFlatIndex:
             raise ValueError("search_finish: no search was begun on this index (search_begin first; a begun search is finished once)")
         q, k = self._begun
         self._begun = None
-        D = torch.empty((q.shape[0], k), device=q.device, dtype=torch.float32)
-        I = torch.empty((q.shape[0], k), device=q.device, dtype=torch.int64)
-        K64 = torch.empty((q.shape[0], k), device=q.device, dtype=torch.float64) if return_f64 else None
+        D, I, K64 = _alloc_out(q, k, return_f64)
         if global_lb is not None:
             _lib.require_cuda(global_lb, "global_lb")
             global_lb = global_lb.contiguous().float()
             if global_lb.numel() != q.shape[0]:
                 raise ValueError("global_lb must hold one bound per query")
         with torch.cuda.device(q.device):
-            _lib.check(self._lib.radad_knn_search_finish(self._h, global_lb.data_ptr() if global_lb is not None else None, D.data_ptr(),
-                                                         I.data_ptr(), K64.data_ptr() if return_f64 else None,
+            _lib.check(self._lib.radad_knn_search_finish(self._h, _ptr(global_lb), D.data_ptr(), I.data_ptr(), _ptr(K64),
                                                          _lib.stream_ptr(q.device)), "radad_knn_search_finish")
         return (D, I, K64) if return_f64 else (D, I)
 
@@ -596,20 +591,11 @@ class HipIVFFlatIndex:
         q = self._to_dev(q)
         if q.dim() != 2 or q.shape[1] != self.d:
             raise ValueError(f"search expects [nq, {self.d}], got {tuple(q.shape)}")
-        n_excl = 0 if exclude_tags is None else int(exclude_tags.numel())
-        if n_excl:
-            _lib.require_cuda(exclude_tags, "exclude_tags")
-            _lib.require_cuda(row_tags, "row_tags")
-            exclude_tags = exclude_tags.contiguous().to(torch.int64).reshape(-1)
-            row_tags = row_tags.contiguous().to(torch.int64).reshape(-1)
-            if row_tags.numel() != self.ntotal:
-                raise ValueError(f"row_tags must hold one tag per stored row ({self.ntotal}), got {row_tags.numel()}")
-        D = torch.empty((q.shape[0], max(k, 0)), device=q.device, dtype=torch.float32)
-        I = torch.empty((q.shape[0], max(k, 0)), device=q.device, dtype=torch.int64)
+        row_tags, exclude_tags, n_excl = _prep_tags(row_tags, exclude_tags, self.ntotal)
+        D, I, _ = _alloc_out(q, max(k, 0))
         with torch.cuda.device(q.device):
-            _lib.check(self._lib.radad_ivf_search_excl(self._h, q.data_ptr(), q.shape[0], k, int(self.nprobe),
-                                                       row_tags.data_ptr() if n_excl else None,
-                                                       exclude_tags.data_ptr() if n_excl else None, n_excl, D.data_ptr(), I.data_ptr(),
+            _lib.check(self._lib.radad_ivf_search_excl(self._h, q.data_ptr(), q.shape[0], k, int(self.nprobe), _ptr(row_tags),
+                                                       _ptr(exclude_tags), n_excl, D.data_ptr(), I.data_ptr(),
                                                        _lib.stream_ptr(q.device)), "radad_ivf_search_excl")
         self.last_search_exact = False
         return D, I
@@ -793,16 +779,15 @@ class VectorDatabase:
             return self.index.search_device(query_vectors, k)
         return self.index.search(query_vectors.astype(np.float32, copy=False), k)
 
-    def search_excluding(self, query_vectors, k: int = None, exclude_tags=None, k_fetch=None):
-        """The k nearest rows whose basename tag (path_tag) is not in `exclude_tags`, exactly, however many excluded rows precede them
-        (HipFlatIndex.search_excluding; the reference's K + 10 over-fetch, pipeline.py:478,491-515, pads instead).  query_vectors: CUDA
-        tensor [B, d]; exclude_tags: int64 tensor / sequence of tags, or None / empty -> (D f32 [B,k], I i64 [B,k]) on the device, -1 / NaN
-        where fewer than k admissible rows exist.  k is clamped to ntotal as in search_batch.  Flat stores only."""
+    def _excluding_args(self, index_cls, wrong_index: str, query_vectors, k, exclude_tags, k_fetch=None):
+        """the front of search_excluding / search_probed_excluding -> (query_vectors [B, d], k clamped to ntotal, k_fetch, row tags,
+        exclusion set sorted and unique, as the kernels' binary search needs; both None when nothing is excluded); k == 0: nothing
+        to search"""
         import torch
         if self.index is None:
             raise ValueError("Vector database is empty. Build the database first.")
-        if not isinstance(self.index, HipFlatIndex):
-            raise ValueError("exclusion-aware search is flat and single-handle only (vector_db_index_type 'L2' or 'IP')")
+        if not isinstance(self.index, index_cls):
+            raise ValueError(wrong_index)
         _lib.require_cuda(query_vectors, "query_vectors")
         if query_vectors.dim() == 1:
             query_vectors = query_vectors.reshape(1, -1)
@@ -813,14 +798,29 @@ class VectorDatabase:
         k = min(k, self.index.ntotal)
         if k <= 0:
             logging.warning("No vectors available for search")
-            return (torch.zeros((len(query_vectors), 0), dtype=torch.float32, device=query_vectors.device),
-                    torch.zeros((len(query_vectors), 0), dtype=torch.int64, device=query_vectors.device))
-        k_fetch = min(k_fetch, _lib.KNN_MAX_K)
-        excl = None
-        if exclude_tags is not None and len(exclude_tags) > 0:
-            excl = torch.as_tensor(exclude_tags, dtype=torch.int64).to(query_vectors.device).reshape(-1)
-            excl = torch.unique(excl)                       # ascending, as the kernel's binary search needs
-        return self.index.search_excluding(query_vectors, k, self.row_tags_device() if excl is not None else None, excl, k_fetch=k_fetch)
+            return query_vectors, 0, k_fetch, None, None
+        if exclude_tags is None or len(exclude_tags) == 0:
+            return query_vectors, k, k_fetch, None, None
+        excl = torch.unique(torch.as_tensor(exclude_tags, dtype=torch.int64).to(query_vectors.device).reshape(-1))
+        return query_vectors, k, k_fetch, self.row_tags_device(), excl
+
+    @staticmethod
+    def _no_hits(query_vectors):
+        import torch
+        return (torch.zeros((len(query_vectors), 0), dtype=torch.float32, device=query_vectors.device),
+                torch.zeros((len(query_vectors), 0), dtype=torch.int64, device=query_vectors.device))
+
+    def search_excluding(self, query_vectors, k: int = None, exclude_tags=None, k_fetch=None):
+        """The k nearest rows whose basename tag (path_tag) is not in `exclude_tags`, exactly, however many excluded rows precede them
+        (HipFlatIndex.search_excluding; the reference's K + 10 over-fetch, pipeline.py:478,491-515, pads instead).  query_vectors: CUDA
+        tensor [B, d]; exclude_tags: int64 tensor / sequence of tags, or None / empty -> (D f32 [B,k], I i64 [B,k]) on the device, -1 / NaN
+        where fewer than k admissible rows exist.  k is clamped to ntotal as in search_batch.  Flat stores only."""
+        q, k, k_fetch, tags, excl = self._excluding_args(
+            HipFlatIndex, "exclusion-aware search is flat and single-handle only (vector_db_index_type 'L2' or 'IP')",
+            query_vectors, k, exclude_tags, k_fetch)
+        if k <= 0:
+            return self._no_hits(q)
+        return self.index.search_excluding(q, k, tags, excl, k_fetch=min(k_fetch, _lib.KNN_MAX_K))
 
     def search_probed_excluding(self, query_vectors, k: int = None, exclude_tags=None):
         """IVF stores: the k nearest rows of the probed lists (config.vector_db_nprobe, vector_database.py:174-179) whose basename tag
@@ -828,28 +828,14 @@ class VectorDatabase:
         (HipIVFFlatIndex.search_probed_excluding; the reference's K + 10 over-fetch, pipeline.py:478,491-515, pads instead).
         query_vectors: CUDA tensor [B, d]; exclude_tags: int64 tensor / sequence of tags, or None / empty -> (D f32 [B,k], I i64 [B,k])
         on the device, -1 / NaN where the probed lists hold fewer than k admissible rows.  k is clamped to ntotal as in search_batch."""
-        import torch
-        if self.index is None:
-            raise ValueError("Vector database is empty. Build the database first.")
-        if not isinstance(self.index, HipIVFFlatIndex):
-            raise ValueError("search_probed_excluding is the IVF store's exclusion-aware search (vector_db_index_type 'IVF'); "
-                             "a flat store has search_excluding")
-        _lib.require_cuda(query_vectors, "query_vectors")
-        if query_vectors.dim() == 1:
-            query_vectors = query_vectors.reshape(1, -1)
-        k = int(k if k is not None else getattr(self.config, "top_k", 5))
-        k = min(k, self.index.ntotal)
+        q, k, _, tags, excl = self._excluding_args(
+            HipIVFFlatIndex, "search_probed_excluding is the IVF store's exclusion-aware search (vector_db_index_type 'IVF'); "
+            "a flat store has search_excluding", query_vectors, k, exclude_tags)
         if k <= 0:
-            logging.warning("No vectors available for search")
-            return (torch.zeros((len(query_vectors), 0), dtype=torch.float32, device=query_vectors.device),
-                    torch.zeros((len(query_vectors), 0), dtype=torch.int64, device=query_vectors.device))
+            return self._no_hits(q)
         if hasattr(self.config, "vector_db_nprobe"):        # vector_database.py:174-179
             self.index.nprobe = int(self.config.vector_db_nprobe)
-        excl = None
-        if exclude_tags is not None and len(exclude_tags) > 0:
-            excl = torch.as_tensor(exclude_tags, dtype=torch.int64).to(query_vectors.device).reshape(-1)
-            excl = torch.unique(excl)                       # ascending, as the kernel's binary search needs
-        return self.index.search_probed_excluding(query_vectors, k, self.row_tags_device() if excl is not None else None, excl)
+        return self.index.search_probed_excluding(q, k, tags, excl)
 
     # ---- device-side columns for retrieve_similar_vectors ------------------------------------------------------
     def row_tags_device(self):

@@ -155,6 +155,52 @@ def test_listed_queries_long_lists(gpu, k, k_fetch):
     assert c.run(k, k_fetch) >= 40
 
 
+# ---- 3b. the two forms of the compaction kernel agree at the strip boundaries of its walk ---------------------------------------------
+@pytest.fixture(scope="module")
+def strip_case(gpu):
+    # 62 excluded near-duplicates in front of each crowded query: its admissible hits start at position 62 of the fast-pass list and
+    # run across the end of the first strip of 64 (k_fetch 64: two of them, 65: three, 200: all five, the fifth in the second strip)
+    db, q, tags, excl, which = crowded(20000, 64, 40, 12, 62, 9351)
+    c = _Case(gpu, "L2", db, q, tags, excl)
+    c.want = expected_excluding(c.stored, c.tags, c.excl, q, 5, "L2")
+    yield c
+
+
+@pytest.mark.parametrize("k_fetch", [5, 15, 64, 65, 200])
+def test_compaction_forms_agree_at_strip_boundaries(gpu, strip_case, k_fetch):
+    """k_excl_compact<false> (search_excluding) and k_excl_compact<true> (search_excluding_begin) share one walk: the rows the shard
+    form leaves (finish without flags) are the whole-store form's bit for bit for every query that form did not list, the full
+    call is the oracle's answer for every query, and the frontier is the model's (tests/sharded_excl_ref.shard_begin).  L2: the
+    float64 keys of the excluded near-duplicates a frontier may be are then apart by far more than their rounding, so the frontier
+    ID is compared exactly; its key and the distances with this file's L2 tolerance (summation order differs from the oracle's)."""
+    import torch
+    from sharded_excl_ref import shard_begin
+    c, k = strip_case, 5
+    qt = _dev(c.q, gpu)
+    listed = expected_exact(c.stored, c.tags, c.excl, c.q, k, k_fetch, "L2")
+    D, I, K64 = c.idx.search_excluding(qt, k, c.tags_t, c.excl_t, k_fetch=k_fetch, return_f64=True)
+    info = c.idx.last_excl()
+    Kb, Ib, FK, FI = c.idx.search_excluding_begin(qt, k, c.tags_t, c.excl_t, k_fetch)
+    Df, If, Kf = c.idx.search_excluding_finish(None, return_f64=True)
+    print(f"k_fetch {k_fetch}: listed {info['exact']} of {info['queries']} (derived {int(listed.sum())})")
+    assert info == {"queries": 40, "exact": int(listed.sum())}, info
+    assert (k_fetch == 200) == (not listed.any())                     # the twelve crowded queries are listed unless all five fit
+    _check(D, I, c.want[0], c.want[1], "L2", K64)
+    keep = torch.from_numpy(~listed).to(gpu)
+    assert torch.equal(If[keep], I[keep])
+    assert torch.equal(Df[keep].view(torch.int32), D[keep].view(torch.int32))
+    assert torch.equal(Kf[keep].view(torch.int64), K64[keep].view(torch.int64))
+    mk, mi, mfk, mfi = shard_begin(c.stored, c.tags, c.excl, c.q, k, k_fetch, "L2")
+    np.testing.assert_array_equal(Ib.cpu().numpy(), mi)
+    np.testing.assert_array_equal(If.cpu().numpy(), mi)
+    fk, fi = FK.cpu().numpy(), FI.cpu().numpy()
+    np.testing.assert_array_equal(fi, mfi)
+    assert np.all(fi >= 0)                                            # 20 000 rows: something is always unseen
+    np.testing.assert_allclose(fk, mfk, rtol=1e-6, atol=1e-6)
+    full = mi[:, -1] >= 0
+    np.testing.assert_array_equal(fk[full].view(np.int64), Kb.cpu().numpy()[full, -1].view(np.int64))   # the k-th survivor itself
+
+
 # ---- 4. few admissible rows ------------------------------------------------------------------------------------------------------------
 def test_few_admissible_rows(gpu):
     db, q, tags, _, _ = crowded(4096, 64, 24, 4, 10, 9401)
