@@ -104,7 +104,9 @@ int radad_knn_ntotal(radad_knn_t h, int64_t* n);
 /* reserve HBM for `capacity` rows up front (optional; add grows geometrically otherwise) */
 int radad_knn_reserve(radad_knn_t h, int64_t capacity);
 /* append n rows [n, dim] fp32 (device pointer).  Cosine: rows are normalised on the way in, so
- * reconstruct returns the normalised row exactly as faiss would return what was added. */
+ * reconstruct returns the normalised row exactly as faiss would return what was added -- in fp32, within a few ulp of
+ * x / (|x| + 1e-12f) and bit for bit what radad_rownorm and a cosine search's query preparation give for the same row
+ * (tests/test_gpu_store_contents.py: test_ingest_holds_what_the_model_says, test_the_query_a_search_uses). */
 int radad_knn_add(radad_knn_t h, const float* rows_dev, int64_t n, void* stream);
 /* same, from a host buffer (what index.add(np.ndarray) does); synchronous */
 int radad_knn_add_host(radad_knn_t h, const float* rows_host, int64_t n);

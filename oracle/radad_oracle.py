@@ -334,6 +334,109 @@ def merge_topk(dists, idxs, k, metric="L2"):
 
 
 # ------------------------------------------------------------------------------------------------
+# a5'  what a store HOLDS for given fp32 input rows (the ingest side: radad_knn_add, radad_rownorm, the query preparation of a
+# search).  A host-only model: nothing here comes from the device, so a search oracle fed with stored_rows() does not inherit
+# a wrong byte that the ingest kernel, the gather kernel and the scan would all read alike.
+# ------------------------------------------------------------------------------------------------
+COS_EPS32 = float(np.float32(1e-12))     # the `+ 1e-12` of vector_database.py:104 as a float32 array sees it (and the kernels' 1e-12f)
+
+
+def cosine_sum_depth(dim):
+    """Depth d of the rounding-error chain of sum x^2 in the row kernels (k_rows_prepare mode 2 = radad_rownorm = cosine add, and the
+    query preparation k_hi_rows / k_hi_rows_wide, csrc/knn.hip, csrc/knn_hi.inc), read off the code and its gfx950 instructions:
+      * one wave per row, lane l takes the float4 groups l, l + 64, ...: at most T = ceil(dim / 256) groups per lane;
+      * a group is ((x0^2 + x1^2) + x2^2) + x3^2: one rounding for the square, then at most 3 additions;
+      * the group's sum is then added to the lane's running sum, one addition per group that follows it: at most T (the first
+        group is added to 0, which is exact; T is kept as the bound);
+      * wave_sum is a 6-level xor butterfly: 6 additions.
+    So a term passes through at most d = 1 + 3 + T + 6 = T + 10 roundings.  (Four-term groups added one after the other into the
+    running sum -- 4 T + 7 -- would be the depth if the group were not summed first; it is, so the chain is shorter for
+    dim > 256 and the same, 11, up to 256.)  The compiler emits multiplies and adds here, no FMA; an FMA would only remove a
+    rounding."""
+    return -(-int(dim) // 256) + 10
+
+
+def _cosine_regime(rows):
+    """per row: 0 = the float64 model applies, 1 = the reference's own fp32 formula decides (an all-zero row, or a row whose
+    squares overflow float32: norm = inf, every element becomes 0)"""
+    rows = np.asarray(rows, np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        nrm = np.linalg.norm(rows, axis=1)                # float32, as vector_database.py:103 on a float32 array
+    return (~np.isfinite(nrm)) | (nrm == 0)
+
+
+def stored_rows_err(rows):
+    """Cosine store / radad_rownorm / a cosine search's prepared query for fp32 rows [n, dim]:
+    (exact float64 [n, dim], bound float64 [n, dim]) with |device fp32 value - exact| <= bound for every element.
+
+    exact = x / (sqrt(sum x^2) + COS_EPS32) in float64 (vector_database.py:100-105 with the constant as float32 holds it).
+    bound = (d / 2 + 4) u |exact|, u = 2^-24, d = cosine_sum_depth(dim): all squares are positive, so the fp32 sum has relative
+    error <= d u (first order); the square root halves that and rounds once (u), adding 1e-12f rounds once (u), the division
+    (correctly rounded: the compiler's div_scale / div_fmas / div_fixup sequence) rounds once (u); the fourth u covers every
+    second-order term (d^2 u^2 < 1e-3 u for d <= 100).  No empirical factor.
+    Valid where the squares and the quotients are normal float32 numbers (|x| from about 2^-60 up; rows whose elements differ by
+    less than 2^100 among themselves).
+    Two regimes follow the reference's own float32 formula instead, with bound 0: an all-zero row stays zero, and a row whose
+    squares overflow float32 (elements around 2^70) becomes all zeros because its norm is inf."""
+    rows = np.asarray(rows, np.float32)
+    x = rows.astype(np.float64)
+    den = np.sqrt((x * x).sum(axis=1, keepdims=True)) + COS_EPS32
+    exact = x / den
+    bound = (cosine_sum_depth(rows.shape[1]) / 2.0 + 4.0) * U32 * np.abs(exact)
+    special = _cosine_regime(rows)
+    exact[special] = 0.0
+    bound[special] = 0.0
+    return exact, bound
+
+
+def stored_rows(rows, metric, f16=False):
+    """What a flat store must hold for fp32 input rows [n, dim], as an array of the store's dtype (float32, or float16 when f16).
+    L2 / IP, fp32 store: the input, bit for bit.  fp16 store: IEEE round-to-nearest-even of it (ties to even, fp16 subnormals,
+    overflow to +-inf above 65504 -- what faiss's useFloat16 holds as well).
+    COSINE: the float32 nearest to stored_rows_err()'s exact value -- the device may differ from it within that function's
+    bound, so cosine contents are compared through stored_rows_err -- and for an fp16 store one further rounding of the fp32
+    value."""
+    rows = np.ascontiguousarray(rows, np.float32)
+    metric = metric.upper()
+    if metric == "COSINE":
+        out = stored_rows_err(rows)[0].astype(np.float32)
+    elif metric in ("L2", "IP"):
+        out = rows.copy()
+    else:
+        raise ValueError(f"unknown metric {metric}")
+    if f16:
+        with np.errstate(over="ignore"):
+            out = out.astype(np.float16)
+    return out
+
+
+def rownorm_kernel_order_f32(rows):
+    """The row kernels' normalisation evaluated in float32 numpy in THEIR order of operations (cosine_sum_depth's reading of the
+    code): per lane the groups ((x0^2 + x1^2) + x2^2) + x3^2 added one after the other, the 6-level xor butterfly over the 64
+    lanes, sqrt, + 1e-12f, one division per element.  Used on the CPU to check that stored_rows_err's bound holds for that
+    order; the device is compared with the float64 model, not with this."""
+    x = np.ascontiguousarray(rows, np.float32)
+    n, dim = x.shape
+    assert dim % 4 == 0
+    nv = dim // 4
+    T = -(-nv // 64)
+    g = np.zeros((n, T * 64, 4), np.float32)
+    g[:, :nv] = x.reshape(n, nv, 4)
+    g = g.reshape(n, T, 64, 4)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        sq = g * g
+        grp = ((sq[..., 0] + sq[..., 1]) + sq[..., 2]) + sq[..., 3]          # [n, T, 64]
+        lane = np.zeros((n, 64), np.float32)
+        for t in range(T):
+            lane = lane + grp[:, t]
+        idx = np.arange(64)
+        for o in (32, 16, 8, 4, 2, 1):
+            lane = lane + lane[:, idx ^ o]
+        den = np.sqrt(lane[:, :1]) + np.float32(1e-12)
+        return (x / den).astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------
 # a7  pipeline.py:449-532 (retrieve_similar_vectors post-processing)
 # ------------------------------------------------------------------------------------------------
 

@@ -641,7 +641,9 @@ __device__ __forceinline__ void hi_rows_body(const HiRowsParams& p) {
             ss = wave_sum(ss);
         } else {
             // |x|^2 in the ONE-wave order whatever the team: the normalised query is part of the contract (radad_rownorm, the rows'
-            // k_rows_prepare and this kernel give the same bits: tests compare float64 keys at 1e-12), the rest below is not
+            // k_rows_prepare and both forms of this kernel give the same bits: tests/test_gpu_store_contents.py,
+            // test_the_query_a_search_uses, reads the query a search used off unit-vector rows and compares it with radad_rownorm
+            // bit for bit at 1, 16, 17 and 300 queries), the rest below is not
             if (threadIdx.x < 64) {
                 for (int i = lane; i < nv; i += 64) {
                     const f32x4 v = src[i];
