@@ -149,7 +149,8 @@ int radad_knn_search_ex(radad_knn_t h, const void* q_dev, int q_dtype, int64_t n
  * G x the work of one GPU on G shards.  With a bound the rows a shard returns are those of its rows that can be in the global
  * top k (fewer than k is normal; the rest is -1 filled); merged over the shards (radad_topk_merge_f64) the result is exactly the
  * unsharded search's.  global_lower_bound_dev == NULL: _finish returns this shard's own top k, i.e. _begin + _finish ==
- * radad_knn_search_ex.  One begun search per handle at a time; other searches on the handle fail until it is finished. */
+ * radad_knn_search_ex.  One begun search per handle at a time; other searches on the handle fail until it is finished.  (Each
+ * claim above is asserted by tests/test_gpu_sharded_bound.py on the designed stores of tests/sharded_bound_ref.py.) */
 int radad_knn_search_begin(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, float* topk_lower_bounds_dev, void* stream);
 int radad_knn_search_finish(radad_knn_t h, const float* global_lower_bound_dev, float* out_dist_dev, int64_t* out_idx_dev,
                             double* out_key_dev, void* stream);

@@ -337,7 +337,10 @@ class HipFlatIndex:
         import torch
         G, nq, kk = lb_all.shape
         if G * kk > HipFlatIndex.KTH_MAX_VALUES or not lb_all.is_cuda:     # beyond the selection kernel's reach (8 ranks x k > 160): torch
-            return torch.topk(lb_all.permute(1, 0, 2).reshape(nq, -1).float(), int(k), dim=1).values[:, int(k) - 1].contiguous()
+            # (NaN ranks lowest, as in the kernel; torch.topk alone ranks it highest)
+            vals = torch.nan_to_num(lb_all.permute(1, 0, 2).reshape(nq, -1).float(), nan=float("-inf"), posinf=float("inf"),
+                                    neginf=float("-inf"))
+            return torch.topk(vals, int(k), dim=1).values[:, int(k) - 1].contiguous()
         flat = lb_all.contiguous().float()                 # [G][nq][k] as gathered: the kernel reads that layout
         out = torch.empty((nq,), device=flat.device, dtype=torch.float32)
         with torch.cuda.device(flat.device):
