@@ -63,7 +63,7 @@ struct DeviceGuard {
     int target = -1;
 };
 
-static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+#include "ceil_div.h"
 
 // wave-wide reductions (wave = 64 lanes on gfx950)
 __device__ __forceinline__ float wave_sum(float v) {

@@ -917,7 +917,7 @@ static bool ivf_ensure_plane(radad_ivf_t h, hipStream_t st) {
         if (!knn_ensure_hi(f, st, true) || !f->hi || f->hi_rows != f->ntotal) return false;
     }
     const int64_t n = (int64_t)h->assign.size();
-    if (h->have_hi && h->hi_src == (const void*)f->hi && h->hi_src_rows == f->hi_rows && h->hi_src_epoch == f->plane_rebuilds) return true;
+    if (h->have_hi && h->hi_src == (const void*)f->hi && h->hi_src_rows == f->hi_rows && h->hi_src_epoch == f->tune.plane_rebuilds) return true;
     h->have_hi = false;
     if (h->lhi.ensure((size_t)n * h->dim * 2) || h->lbias.ensure((size_t)n * sizeof(float)) ||
         (f->rscale && h->lscale.ensure((size_t)n * sizeof(float)))) { (void)hipGetLastError(); return false; }
@@ -925,7 +925,7 @@ static bool ivf_ensure_plane(radad_ivf_t h, hipStream_t st) {
                        (const float*)(f->cmu ? f->rbias : f->ynorm), (const int64_t*)h->lids.p, n, h->dim, (_Float16*)h->lhi.p,
                        f->rscale ? (float*)h->lscale.p : (float*)nullptr, (float*)h->lbias.p);
     if (hipGetLastError() != hipSuccess) return false;
-    h->have_hi = true; h->hi_src = f->hi; h->hi_src_rows = f->hi_rows; h->hi_src_epoch = f->plane_rebuilds;
+    h->have_hi = true; h->hi_src = f->hi; h->hi_src_rows = f->hi_rows; h->hi_src_epoch = f->tune.plane_rebuilds;
     return true;
 }
 

@@ -16,6 +16,7 @@
 // Layout in HBM: rows [capacity, dim] fp32 row-major (insertion order), ynorm [capacity] fp32 (L2 only).
 // Partial results: score [nq, n_splits, k] fp32 + local row index int32, same shape.
 #include "common.h"
+#include "knn_plan.h"
 
 #include <algorithm>
 #include <atomic>
@@ -32,11 +33,9 @@
 
 namespace {
 
-constexpr int KT_M = 128;       // store rows per tile (MFMA A rows)
-constexpr int KT_N = 128;       // queries per tile (MFMA B columns)
+// (KT_M x KT_N = 128 store rows x 128 queries per tile, KNN_THREADS = 256: knn_plan.h)
 constexpr int KT_K = 32;        // K step
 constexpr int KT_LD = KT_K + 4; // padded LDS row (floats): 36-dword stride is conflict-free for ds_read_b128
-constexpr int KNN_THREADS = 256;
 constexpr int KS_LD = KT_M + 4;  // score-tile row (floats): 132-dword stride keeps b128 writes and reads conflict-free
 constexpr int IDX_SENTINEL = 0x7fffffff;
 
@@ -658,10 +657,8 @@ __global__ __launch_bounds__(KNN_THREADS, 2) void k_knn_f32_reg(KnnParams p) {
 // (lane & 15) and 4 rows per group, so the filter threshold is a register.  Each wave keeps private top-k lists
 // (lanes 0-15 own one query each, lists in registers); survivors travel through a per-wave LDS slot buffer that can
 // never overflow (16 slots per query = everything one step can produce).  No workgroup barrier inside the scan.
-constexpr int SQ_THREADS = 256;
-constexpr int SQ_NQ = 16;
-constexpr int SQ_SLOTS = 16;
-constexpr size_t SQ_LDS_BUDGET = 160 * 1024;      // the query block [nq][dim + pad] + slot buffers must fit one CU's LDS
+// (SQ_THREADS, SQ_NQ, SQ_SLOTS, SQ_LDS_BUDGET: knn_plan.h)
+static_assert(sizeof(float2) == 8 && sizeof(u64) == 8 && sizeof(_Float16) == 2, "knn_plan.h sizes the streaming kernels' LDS (SQ_SLOT_BYTES, knn_sq_lds_hi) with these as literals");
 
 struct SmallQParams {
     const float* db = nullptr; const float* ynorm = nullptr; const float* q = nullptr; // fp32 store only
@@ -1131,13 +1128,9 @@ constexpr size_t knn_reg_lds_bytes() { return 4 * KD_TILE_BYTES + sizeof(float2)
 //       candidate buffer (cap) sufficed.  Uncertified queries are appended to flag_sel for the exact kernel below.
 //   eps == nullptr (IVF list scans): legacy behaviour -- the `cap` best candidates are re-scored, no certificate.
 // k_merge_lists<KeyT> (radad_topk_merge / _f64): plain P-way merge of final per-shard lists, no rescoring.
-constexpr int KNN_MARGIN = 6;            // spare entries of a (query, chunk) list on the fp32 tile kernels
-constexpr int KNN_CERT_EXTRA = 32;       // candidates beyond k the certified re-rank can take before it gives up, at least ...
-constexpr int KNN_CERT_CAP = 512;        // ... and this many in all: stores of near-duplicates (the benchmark plants 2048 rows
-                                         // within 2e-2 of every query) put hundreds of rows within 2 eps of the k-th
-constexpr int KNN_F16_MAX_K = 128;       // largest k the certified f16 scans take; beyond it the fp32 tile kernels filter (certified too)
+// (KNN_MARGIN, KNN_CERT_EXTRA, KNN_CERT_CAP, KNN_F16_MAX_K, KW_SAMPLE_SPLITS, RF_STAGE_MAX, RF_STAGE_MAX_SMALLQ: knn_plan.h)
 constexpr int IVF_MAX_K = 128;           // largest k of radad_ivf_search (HipIVFFlatIndex.MAX_K); flat searches take any k <= RADAD_KNN_MAX_K
-constexpr int KW_SAMPLE_SPLITS = 64;     // one-tile splits of the threshold pre-pass (<= 16384 rows)
+
 
 struct RefineParams {
     const float* score = nullptr;      // [nq, n_parts, part_len] fp32 scan scores (larger is better), each list sorted
@@ -1176,8 +1169,6 @@ static_assert(std::is_trivially_copyable_v<RefineParams>, "kernel argument");
 // pass in flight), the ranking is one thread per candidate.
 constexpr int RF_THREADS = 256;
 constexpr int RF_MAXL = 4;               // lists per thread: n_parts <= 1024
-constexpr int RF_STAGE_MAX = 6144;       // list entries per query that k_merge_refine<true> stages in LDS (48 KB + candidates)
-constexpr int RF_STAGE_MAX_SMALLQ = 16384;   // ... for batches of <= 16 queries (128 KB: occupancy does not matter there)
 
 constexpr size_t refine_lds_bytes(int cap) { return (size_t)cap * 20 + 256; }      // candidates + per-wave scratch of k_merge_refine
 
@@ -1891,27 +1882,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_refine_small(RefineParams p, dou
 // and writes one list per (query slot, slice); the slice that arrives last for a query group merges the slices (exact_merge_slot)
 // and overwrites the queries' results.
 // Keys are "larger is better" doubles (inner product, or minus the squared distance); order (key desc, id asc).
-constexpr int KX_THREADS = 512;
-constexpr int KX_WAVES = KX_THREADS / 64;
-constexpr int KX_SLICES = 64;
+// (KX_THREADS, KX_WAVES, KX_SLICES, KX_LDS_MAX, KX_PART_BUDGET and the grouping knn_exact_group / knn_exact_slots: knn_plan.h)
 constexpr int KX_GROUPS_Y = 4;
-constexpr size_t KX_LDS_MAX = 160 * 1024;              // LDS of a CU: the group's queries + KX_WAVES sorted lists of k per query
-constexpr size_t KX_PART_BUDGET = (size_t)128 << 20;   // workspace of one launch's partial lists (KX_SLICES x k x 12 B per query)
-
-// rejected queries one launch of k_exact_scan takes: as many as KX_PART_BUDGET holds partial lists for, a whole group at least.
-// (k = 1024: 170 per launch, 128 MiB -- instead of 64 x 1024 x 12 B = 768 KiB for EVERY query of the batch, 805 MB at nq = 1024;
-// k <= 128 with batches of up to 1365 queries: one launch, as before)
-static int64_t knn_exact_slots(int64_t nq, int k, int group) {
-    const int64_t per_q = (int64_t)KX_SLICES * k * (int64_t)(sizeof(double) + sizeof(int));
-    return std::min<int64_t>(nq, std::max<int64_t>(group, (int64_t)(KX_PART_BUDGET / per_q) / group * group));
-}
-
-// queries per workgroup of the exact kernel: the group's queries (<= 64 KB) and its KX_WAVES lists of k per query share the LDS
-// (the lists shrink it at large k: k = 1024 takes one query per workgroup, 98 KB of lists)
-static int knn_exact_group(int dim, int k) {
-    return (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(8, (size_t)(64 * 1024) / ((size_t)dim * 4)),
-                                                     (KX_LDS_MAX - 16) / ((size_t)dim * 4 + (size_t)KX_WAVES * k * 12)));
-}
 
 struct ExactParams {
     const void* db = nullptr; int db_f16 = 0;
@@ -2536,13 +2508,6 @@ static int merge_lists(int metric, const KeyT* in_key, const int64_t* in_idx, in
     return RADAD_OK;
 }
 
-// byte offsets of a search's buffers in the handle's workspace (knn_search_layout)
-struct SearchLayout {
-    size_t qf = 0, qn = 0, qh = 0, qscale = 0, qconst = 0, eps = 0, thr = 0, ak = 0, cnt = 0, fcount = 0, fsel = 0, ps = 0, pi = 0, xk = 0, xi = 0;
-    size_t cand_elems = 0;     // entries of the candidate buffers / partial lists in ps, pi: the sample pre-pass's lists follow them
-    size_t bytes = 0;
-};
-
 // what phase 2 of a search needs from phase 1 (knn_search_phase1 / _phase2 below)
 struct SearchCtx {
     bool valid = false;
@@ -2556,17 +2521,6 @@ struct SearchCtx {
     bool have_ak = false;              // k_kth_floor left a_k in the workspace (ws.ak)
     bool hi_tile = false;              // the certified f16 tile scan took this search
     SearchLayout ws;
-};
-
-// byte offsets in the handle's exclusion workspace
-struct ExclLayout {
-    size_t fd = 0, fi = 0, fk = 0;          // the fast pass's k_fetch lists (dist, id, key)
-    size_t count = 0, sel = 0;              // listed-query counter, listed queries
-    size_t admit = 0, xk = 0, xi = 0;       // admission bitmap, the filtered exact pass's partial lists
-    size_t bd = 0, bi = 0, bk = 0, own = 0; // begun form only: the shard's lists as _begin left them, and its own short-list flags
-    size_t bytes = 0;
-    int kf = 0, whole = 0, xgroup = 1;
-    int64_t xslots = 0, n_words = 0;
 };
 
 // an exclusion-aware search begun on a row shard (radad_knn_search_excl_begin) without its _finish yet
@@ -2620,26 +2574,12 @@ struct radad_knn_s {
     int* rs_count = nullptr;     // ... and [SQ_NQ] arrival counters (zero between launches)
     int uniform_e = HI_E_PER_ROW; // one power-of-two scale 2^e for every row of the plane (rows of one magnitude), or HI_E_PER_ROW
     // queries the certificate rejected in the most recent search: counted on the device, copied to pinned host memory
-    // behind the search (no synchronisation inside search); feeds the adaptive choice below and radad_knn_last_recheck
-    // The counters of search i land in slot i % 2 of pinned host memory, written by k_exact_scan together with the search's batch size
-    // and, last, its stamp (sequence number + 1).  Every later search looks at BOTH slots without waiting and acts on any report it
-    // has not consumed yet (stamp_seen) that belongs to a search issued since the last tuning change (tuned_at) -- however far the
-    // host runs ahead of the device (round 4 acted only on the report of exactly search_seq - 2: a host more than two searches
-    // ahead, e.g. a queued bench loop, never saw one).  WHEN a report is first seen depends on host / device timing, so
-    // the search at which a handle retunes may differ between runs; what a search returns never does (exact by construction).
+    // behind the search (no synchronisation inside search); feeds the adaptive tuning and radad_knn_last_recheck
     int* host_count = nullptr;   // pinned [2][8]: rejected queries, sum of candidates, rejections by reason x 4, [6] the report's stamp, [7] its batch size
-    int stamp_seen[2] = {0, 0};  // stamp of the last report consumed from each slot
-    // LOOKING before the exact pass.  The exact float64 kernel costs nq x ntotal x dim multiply-adds for a fully rejected batch: 10 s for
-    // 10 240 queries against 10 M x 512 (BASELINE config 4 with a store whose planted rows neighbour EVERY query: 73 % of the batch
-    // overflowed its 1024 candidates), and a host that queues searches gets no report before it has queued them all.  So the first
-    // large tile-scan search after anything that can change the outcome (handle creation, a plane (re)build, a tuning step, the end of
-    // an fp32 fallback) WAITS for its re-rank -- one stream synchronisation -- and, when more than a quarter of the batch was rejected,
-    // retunes and runs again at once instead of entering the exact kernel.  A search that passes clears the flag: steady state never
-    // synchronises.
-    bool verify_next = true;
-    int hi_fail_streak = 0;      // consecutive returns from the fp32 fallback that were rejected again: the fallback doubles (8, 16, ... 512 searches)
-    int64_t verified_retries = 0;
-    int64_t reports_consumed = 0;   // (radad_knn_tuning_info)
+    // what the handle does about batches the certificate mostly rejected -- reports, the look before the exact pass, re-deciding the
+    // plane, wider buffers, the fp32 fallback: ONE policy, described and kept in KnnTuning (knn_plan.h); this file reads the pinned
+    // slots, synchronises, rebuilds the plane and hands plain integers to it
+    KnnTuning tune;
     bool owned_serial = false;   // the handle is private to another object that orders its calls itself (the IVF index's centroid store): no ev_done
     int* host_count_dev = nullptr;   // the same memory as the device sees it
     hipEvent_t ev_done = nullptr;
@@ -2647,21 +2587,6 @@ struct radad_knn_s {
     bool have_last = false;
     hipStream_t last_stream = nullptr;   // where the last search was enqueued (the next one on ANOTHER stream orders itself behind it; the statistics calls synchronise on it)
     int64_t count_nq[2] = {0, 0};    // batch size of the search a slot belongs to
-    uint64_t search_seq = 0;     // certified searches so far
-    int hi_skip = 0;             // searches left on the fp32 kernels after the certified scan rejected too many queries
-    // Re-deciding the plane (its centre mu and its scale are decided from the rows the store holds WHEN IT IS BUILT; add_vectors_batch
-    // appends 10 000 rows at a time, vector_database.py:134-138): it is dropped and rebuilt -- 0.84 ms per million rows, one
-    // synchronisation -- when the store has doubled since the decision, when rows appended since then measure 8x beyond what the
-    // decision saw (max |y'| or the rounding residual: the f16 scale has 8x headroom), or when a batch was mostly rejected and rows
-    // have been appended since (otherwise the same plane would come back: the fp32 fallback stays the remedy)
-    int64_t plane_decided_rows = 0;
-    float plane_stat[2] = {0.f, 0.f};     // max |y'|, max |y' - yh| right after the plane was built
-    bool replan = false;
-    int plane_rebuilds = 0;      // (radad_knn_plane_info: how often the plane was re-decided)
-    uint64_t tuned_at = 0;       // search_seq at the last change of the plane / of cap_boost: reports of EARLIER searches are not acted on
-    int cap_boost = 1;           // candidate buffers of the tile scan are 1024 entries per query x this (1 or 4): raised once when a batch
-                                 // was mostly rejected (a store of several clusters has a large |y - mu|, hence a large eps: more rows
-                                 // pass the floor than 1024) -- before the handle resorts to the fp32 kernels
     size_t esize() const { return f16 ? 2 : 4; }
     size_t row_bytes() const { return (size_t)dim * esize(); }
     // search workspace (grown on demand, reused)
@@ -2834,19 +2759,17 @@ static bool knn_ensure_hi(radad_knn_t h, hipStream_t st, bool want_plane) {
         h->stat_rows = 0;
     }
     const bool plane = want_plane && !h->hi_off && !h->f16 && h->dim % 64 == 0;
-    if (plane && h->hi && h->hi_cap == h->capacity && h->ntotal > h->plane_decided_rows &&
-        (h->replan || h->ntotal >= 2 * h->plane_decided_rows)) {
+    if (plane && h->tune.plane_rebuild_due(h->hi && h->hi_cap == h->capacity, h->ntotal)) {
         (void)hipDeviceSynchronize();
         knn_drop_plane(h);
-        ++h->plane_rebuilds;
-        h->tuned_at = h->search_seq;
+        h->tune.plane_dropped_for_rebuild();
     }
-    if (plane) h->replan = false;
+    if (plane) h->tune.plane_wanted();
     const bool fresh = plane && (h->hi_cap != h->capacity || !h->hi);
     if (fresh) {
         (void)hipDeviceSynchronize();
         knn_drop_plane(h);
-        h->verify_next = true;                           // a new plane: the next large search looks at its certificate before the exact pass
+        h->tune.plane_is_new();                          // the next large search looks at its certificate before the exact pass
         const bool centred = knn_choose_centre(h, st);
         // One scale for the whole plane when the rows are of one magnitude (the largest row maximum within 2^6 of the smallest over
         // the rows the store holds now: clip embeddings are; rows scaled over 2^22, as a test does, are not): the scan then needs
@@ -2911,50 +2834,12 @@ static bool knn_ensure_hi(radad_knn_t h, hipStream_t st, bool want_plane) {
             // what the plane's operands measure now (only searches that follow an append come through here: one small read-back)
             float host[2] = {0.f, 0.f};
             if (hipMemcpyAsync(host, h->stat, sizeof(host), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) {
-                if (fresh) { h->plane_stat[0] = host[0]; h->plane_stat[1] = host[1]; h->plane_decided_rows = h->ntotal; }
-                else if ((h->plane_stat[0] > 0.f && host[0] > 8.f * h->plane_stat[0]) || (h->plane_stat[1] > 0.f && host[1] > 8.f * h->plane_stat[1])) {
-                    h->replan = true;                      // rows beyond what the scale was chosen for: decide again, now
-                    return knn_ensure_hi(h, st, want_plane);
-                }
+                if (fresh) h->tune.plane_decided(host[0], host[1], h->ntotal);
+                else if (h->tune.plane_outgrown(host[0], host[1])) return knn_ensure_hi(h, st, want_plane);      // decide again, now
             } else (void)hipGetLastError();
         }
     }
     return !want_plane || have_plane || h->f16;
-}
-
-// wide kernel: 256-query tiles, one workgroup per CU; two rounds of workgroups keep the tail short.  (The list-based scan of
-// rounds 1-2 also needed >= 64 chunks so that no 16-entry list was used up; the emit-mode scan has no lists: a sharded batch of
-// 32 query tiles now runs 16 chunks of 31 tiles instead of 64 chunks of 8, i.e. a quarter of the per-workgroup start-up cost.)
-static void knn_geometry_wide(int64_t n, int64_t nq, int* n_qtiles, int* n_splits, int64_t* chunk_rows) {
-    const int qt = (int)ceil_div64(nq, KW_N);
-    const int64_t tiles = ceil_div64(n, KW_M);
-    int64_t want = ceil_div64(512, qt);
-    want = std::min<int64_t>(want, tiles);
-    want = std::max<int64_t>(8, ceil_div64(want, 8) * 8);
-    want = std::min<int64_t>(want, 1024);
-    int64_t tiles_per = ceil_div64(tiles, want);
-    // A launch takes (rounds of 256 workgroups) x (tiles per chunk) tile times, and both factors round up.  Round 4 always took
-    // ceil(512 / query tiles) chunks ("two rounds keep the tail short"): right for 4 query tiles x 1 M rows (2 x 31 = 1 x 62), wrong
-    // where the rounding bites -- BASELINE config 2's 100 k rows = 391 tiles x 4 query tiles: 128 chunks of 4 tiles = 392 workgroups =
-    // 2 rounds x 4 = 8 tile times, 64 chunks of 7 = 224 workgroups = ONE round of 7; configs 4 / 5 at full size, 40 query tiles: 16
-    // chunks = 640 workgroups = 2.5 -> 3 rounds x 2442 tiles, 32 chunks = 1280 = exactly 5 rounds x 1221 (-17 %).  So: the cheapest by
-    // that count among one round's worth of chunks and `want`, `want` + 8, ... 4 x `want`, when it saves 3 % or more.
-    if (qt <= 256) {
-        auto cost = [&](int64_t per) { return ceil_div64((int64_t)qt * ceil_div64(tiles, per), 256) * per; };
-        int64_t best = want, best_per = tiles_per, best_cost = cost(tiles_per);
-        auto consider = [&](int64_t splits) {
-            splits = std::min<int64_t>(std::max<int64_t>(8, splits / 8 * 8), std::min<int64_t>(1024, std::max<int64_t>(8, ceil_div64(tiles, 8) * 8)));
-            const int64_t per = ceil_div64(tiles, splits);
-            const int64_t c = cost(per);
-            if (c * 100 < best_cost * 97) { best = splits; best_per = per; best_cost = c; }      // (a gain under 3 % is not worth leaving two rounds)
-        };
-        consider(256 / qt);
-        for (int64_t sp = want + 8; sp <= 4 * want; sp += 8) consider(sp);
-        want = best; tiles_per = best_per;
-    }
-    *n_qtiles = qt;
-    *n_splits = (int)want;
-    *chunk_rows = tiles_per * KW_M;
 }
 
 extern "C" {
@@ -3123,20 +3008,6 @@ int radad_knn_add_host(radad_knn_t h, const float* rows_host, int64_t n) {
     return rc;
 }
 
-// choose the launch geometry: enough equal splits to put >= 2 workgroups on each of the 256 CUs
-static void knn_geometry(int64_t n, int64_t nq, int* n_qtiles, int* n_splits, int64_t* chunk_rows) {
-    const int qt = (int)ceil_div64(nq, KT_N);
-    const int64_t tiles = ceil_div64(n, KT_M);
-    int64_t want = ceil_div64(512, qt);            // splits so that qt*splits ~ 512 workgroups
-    want = std::min<int64_t>(want, tiles);
-    want = std::max<int64_t>(8, ceil_div64(want, 8) * 8);
-    want = std::min<int64_t>(want, 1024);
-    const int64_t tiles_per = ceil_div64(tiles, want);
-    *n_qtiles = qt;
-    *n_splits = (int)want;
-    *chunk_rows = tiles_per * KT_M;
-}
-
 int radad_knn_search(radad_knn_t h, const float* q_dev, int64_t nq, int k, float* out_dist_dev, int64_t* out_idx_dev,
                      void* stream) {
     return radad_knn_search_f64(h, q_dev, nq, k, out_dist_dev, out_idx_dev, nullptr, stream);
@@ -3173,7 +3044,6 @@ __global__ __launch_bounds__(256) void k_bf16_to_f32(const unsigned short* __res
                                                __uint_as_float((unsigned)b[2] << 16), __uint_as_float((unsigned)b[3] << 16)};
 }
 
-static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 template <typename T>
 static inline T* ws_at(radad_knn_t h, size_t off) { return reinterpret_cast<T*>((char*)h->ws + off); }
 
@@ -3220,16 +3090,6 @@ static int knn_tile_ksplit(radad_knn_t h, int qtiles_grid, int n_splits, int64_t
 // and scans, and can report per query a lower bound of the exact k-th best score of THIS store; phase 2 re-ranks -- with the
 // maximum of the shards' bounds, only what can still be among the global k best -- and runs the exact kernel.
 
-// a batch was mostly rejected by the certificate: re-decide the plane if rows were appended since it was decided, else widen the
-// candidate buffers, else leave the f16 kernels for a while (8 searches, doubling while every return is rejected again)
-static void knn_retune_after_mass_rejection(radad_knn_t h) {
-    if (h->hi && h->ntotal > h->plane_decided_rows) h->replan = true;
-    else if (h->cap_boost == 1) h->cap_boost = 4;
-    else { h->hi_skip = 8 << std::min(h->hi_fail_streak, 6); ++h->hi_fail_streak; }
-    h->tuned_at = h->search_seq;
-    h->verify_next = true;
-}
-
 // the most recent search's device work is complete (its statistics are in the pinned host copy)
 static hipError_t knn_wait_last_search(radad_knn_t h) {
     if (!h->have_last) return hipSuccess;
@@ -3238,202 +3098,53 @@ static hipError_t knn_wait_last_search(radad_knn_t h) {
     return hipDeviceSynchronize();
 }
 
-// how the certificates of earlier searches fared: any report that has arrived and was not looked at yet (see the handle); this
-// search takes over slot search_seq & 1
+// how the certificates of earlier searches fared: any report that has arrived and was not looked at yet (KnnTuning decides what
+// follows from it); this search takes over slot tune.slot().  The volatile reads, the fences and the re-check of the stamp are the
+// synchronisation with the device's writes.
 // (until round 4 an event behind every search was waited for here: an event record between dependent kernels costs the stream ~6 us,
 // a tenth of an online search.  The exact kernel stamps its report; one that has not arrived yet is simply not looked at.)
 static void knn_consume_reports(radad_knn_t h) {
     for (int sl = 0; sl < 2; ++sl) {
         volatile int* rep = reinterpret_cast<volatile int*>(h->host_count + 8 * sl);
         const int stamp = rep[6];
-        if (stamp == 0 || stamp == h->stamp_seen[sl]) continue;
+        if (!h->tune.report_is_new(sl, stamp)) continue;
         std::atomic_thread_fence(std::memory_order_acquire);
         const int rejected = rep[0], rep_nq = rep[7];
         std::atomic_thread_fence(std::memory_order_acquire);
         if (rep[6] != stamp) continue;                    // the device is rewriting the slot right now: next search
-        h->stamp_seen[sl] = stamp;
-        ++h->reports_consumed;
-        // the report's own search: the one search at or below search_seq with that stamp's low 30 bits
-        const uint64_t cur30 = h->search_seq & 0x3fffffff, rep30 = (uint64_t)(stamp - 1);
-        const uint64_t rep_seq = h->search_seq - ((cur30 - rep30) & 0x3fffffff);
-        // (a report from before the last change of the plane or of the buffers says nothing about them)
-        if (h->hi_skip == 0 && rep_nq >= 64 && (int64_t)rejected * 4 > rep_nq && rep_seq >= h->tuned_at) knn_retune_after_mass_rejection(h);
+        h->tune.consume_report(sl, stamp, rejected, rep_nq, h->tune.appended_since_plane(h->hi != nullptr, h->ntotal));
     }
 }
 
-// what one search scans with: the kind of scan, its launch layout, its list / buffer sizes and how its queries are prepared
-struct ScanPlan {
-    int kind = RADAD_SCAN_F32_TILE;  // RADAD_SCAN_*
-    int64_t nq = 0;
-    int k = 0, l2 = 0;
-    int n_qtiles = 0, n_splits = 0;  // workgroups: query tiles x row splits (the streaming kernels: 1 x n_splits)
-    int64_t chunk_rows = 0;
-    int ksel = 0;                    // list length of the fp32 tile kernels: k + margin
-    int ksel_sq = 0;                 // ... of the small-batch kernels
-    int s_splits = 0;                // tile scan: tiles of the sample pre-pass
-    int emit_cap = 0;                // tile scan: entries of a query's candidate buffer
-    int cap = 0;                     // candidates the re-rank can take per query
-    int plen = 0, n_parts = 0;       // entries of a partial list / candidate buffer, lists per query
-    int sq_rows_per_wave = 0;        // small batches: rows per wave (per workgroup in the K-split form)
-    bool sq_ksplit = false;          // small batch over a small store of wide rows: k_knn_hi_smallq_ksplit
-    size_t sq_lds = 0;               // small batches: LDS of the streaming kernel
-    int dense_plen = 0;
-    int xgroup = 1;                  // queries per workgroup of the exact kernel
-    bool hi_q = false;               // f16 queries with a per-query scale (the certified f16 kernels)
-    bool biased = false;             // the scale + bias variant of the f16 kernels (RSC 2, 3)
-    const float* mu = nullptr;       // centred plane: the queries are centred the same way
-    bool f16_queries() const { return kind == RADAD_SCAN_HI_TILE || kind == RADAD_SCAN_HI_SMALLQ || kind == RADAD_SCAN_F16_TILE; }
-};
+static StoreFacts knn_store_facts(radad_knn_t h) {
+    StoreFacts s;
+    s.ntotal = h->ntotal; s.dim = h->dim; s.metric = h->metric; s.f16 = h->f16; s.hi_off = h->hi_off;
+    s.opt_centre = h->opt_centre; s.opt_smallq_hi = h->opt_smallq_hi; s.opt_wide_min_q = h->opt_wide_min_q; s.opt_dense = h->opt_dense;
+    s.cap_boost = h->tune.cap_boost;
+    return s;
+}
 
-// The choice of the scan.  Its side effects -- counting hi_skip down, verify_next, building the plane (knn_ensure_hi) -- happen in this
-// order and under these conditions on purpose: the next searches of the handle see them.
+// The choice of the scan: the plan itself is knn_plan.h's (pure); here are its side effects, in this order and under these conditions
+// on purpose -- the tuning state counts a skipped turn, the plane is built (knn_ensure_hi) -- the next searches of the handle see them.
 static int knn_plan_scan(radad_knn_t h, int64_t nq, int k, int margin, hipStream_t st, ScanPlan* out) {
-    ScanPlan p;
-    p.nq = nq; p.k = k; p.l2 = h->metric == RADAD_METRIC_L2 ? 1 : 0;
-    p.ksel = k + margin;
-    knn_geometry(std::max<int64_t>(h->ntotal, 1), nq, &p.n_qtiles, &p.n_splits, &p.chunk_rows);
-    const int ksel = p.ksel;
-    bool use_hi = false, skipped_hi = false;
-    // small batches (<= 16 queries: the online predict() search, pipeline.py:1038-1054, is ONE query of dim 5376 / 3584) stream the
-    // store; the kernels park only the nq queries handed over in LDS, so any dim goes as long as that block fits beside the slots
-    // (16 queries of dim 5376 do not: such a batch takes the tile kernels like a large one)
-    const size_t sq_slot_bytes = std::max<size_t>(sizeof(float2) * 4 * SQ_NQ * SQ_SLOTS, sizeof(u64) * 3 * SQ_NQ * 32) + sizeof(int) * 4 * SQ_NQ;
-    const size_t sq_lds_hi = sizeof(_Float16) * (size_t)nq * (h->dim + 8) + sq_slot_bytes;
-    const size_t sq_lds_f32 = sizeof(float) * (size_t)nq * (h->dim + 4) + sq_slot_bytes;
-    const bool sq_fits = nq <= SQ_NQ && ksel <= 32 &&
-                         ((!h->hi_off && h->dim % 64 == 0 && sq_lds_hi <= SQ_LDS_BUDGET) || (!h->f16 && h->dim % 32 == 0 && sq_lds_f32 <= SQ_LDS_BUDGET));
-    // the certified f16 scans take k <= KNN_F16_MAX_K: their candidate buffers (emit_cap <= RF_STAGE_MAX) and phase sizes are
-    // tuned for ~8 (k + margin) admissions per launch.  Larger k is filtered by the fp32 tile kernels (lists of k + margin per
-    // split), certified the same way.
-    const bool f16_k = k <= KNN_F16_MAX_K;
-    // the certified tile scan: its candidate buffers are sized from k; the floor's rank k + margin must exist in the sample (16
-    // entries per sample tile)
-    if (f16_k && (nq >= h->opt_wide_min_q || !sq_fits) && h->ntotal > 0 && h->dim % 64 == 0 && !h->hi_off) {
-        int wq, ws; int64_t wc;
-        knn_geometry_wide(h->ntotal, nq, &wq, &ws, &wc);
-        // the sample pre-pass: one tile per workgroup, at most KW_SAMPLE_SPLITS tiles and 1/8 of the store (whatever the number of
-        // query tiles: every phase of the scan is sized from the sample, a small sample means more phases)
-        // ... and about 3 % of it: the pre-pass multiplies every query tile with its rows, so on a shard of a row-sharded store -- 1/G of
-        // the rows against G times the queries -- a fixed 16 384-row sample was 12 % of the scan's own work at G = 8 (0.16 of 1.7 ms);
-        // large enough, though, for the floor's rank to exist twice over (16 entries per sample tile)
-        const int64_t tiles = h->ntotal / KW_M;
-        int64_t want = (tiles * 3 / 100 + 4) / 8 * 8;
-        const int64_t need = ((int64_t)(2 * ksel + KW_SAMPLE_LIST - 1) / KW_SAMPLE_LIST + 7) / 8 * 8;
-        want = std::max<int64_t>(std::max<int64_t>(want, need), 8);
-        // ... but never fewer tiles than fill ONE round of the chip: the pre-pass is one tile per workgroup, its time is that one
-        // tile's latency whether 32 or 256 workgroups run it, and a larger sample is a tighter first floor (BASELINE config 2's
-        // 100 k rows took 8 tiles = 2048 rows: every tile of the scan's first layer then admitted ~2 rows per query -- 512 returning
-        // atomics per workgroup and tile; with 48 tiles the whole store is one launch behind the sample's floor alone)
-        want = std::max<int64_t>(want, std::min<int64_t>(KW_SAMPLE_SPLITS, (256 / std::max(1, std::min(wq, 256))) / 8 * 8));
-        p.s_splits = (int)std::min<int64_t>(std::min<int64_t>(KW_SAMPLE_SPLITS, want), tiles / 8 / 8 * 8);
-        if (p.s_splits >= 8 && p.s_splits * KW_SAMPLE_LIST >= 2 * ksel) {
-            if (h->hi_skip > 0) { --h->hi_skip; skipped_hi = true; if (h->hi_skip == 0) h->verify_next = true; }
-            else if (knn_ensure_hi(h, st, true)) { use_hi = true; p.n_qtiles = wq; }
-        }
+    bool use_hi = false, skipped_hi = false, smallq_hi = false;
+    const TileEligibility t = knn_tile_eligibility(knn_store_facts(h), nq, k, margin);
+    if (t.eligible) {
+        if (!h->tune.take_tile_turn()) skipped_hi = true;
+        else use_hi = knn_ensure_hi(h, st, true);
     }
     if (!use_hi && !knn_ensure_hi(h, st, false)) { radad_set_error("store statistics could not be computed"); return RADAD_EHIP; }
-    const bool smallq_geom = !use_hi && nq <= SQ_NQ && ksel <= 32 && h->ntotal > 0;
-    // the small batch over the f16 plane (certified like the tile scan): stores the plane is kept for, or fp16 stores
-    bool smallq_hi = false;
-    if (smallq_geom && f16_k && h->opt_smallq_hi && h->dim % 64 == 0 && h->ntotal >= 16384 && !h->hi_off && !skipped_hi &&
-        sq_lds_hi <= SQ_LDS_BUDGET) {
-        // (every search that would take a certified f16 kernel counts the skip down: a handle that only sees small batches after a
-        // mass rejection used to stay on the fp32 kernel for ever)
-        if (h->hi_skip > 0) --h->hi_skip;
-        else smallq_hi = knn_ensure_hi(h, st, true);
-    }
-    // a small fp32 store (the IVF index's centroids; a database of a few thousand files): every score + select on the staged copy
-    p.dense_plen = (int)((std::max<int64_t>(h->ntotal, 1) + 3) / 4 * 4);
-    const bool dense = !use_hi && !smallq_hi && !h->f16 && h->opt_dense && h->ntotal >= 1 &&
-                       h->ntotal <= (nq <= SQ_NQ ? RF_STAGE_MAX_SMALLQ : RF_STAGE_MAX) && h->dim % 16 == 0 && nq * (int64_t)p.dense_plen <= ((int64_t)1 << 24);
-    const bool smallq = smallq_geom && !dense && !smallq_hi && !h->f16 && h->dim % 32 == 0 && sq_lds_f32 <= SQ_LDS_BUDGET;
-    // a small store of wide rows (the reference's own: 25 423 x 5376) has too few 16-row steps to occupy the chip with one wave per
-    // row slice: the K-split form puts four waves on every step
-    p.sq_ksplit = smallq_hi && h->dim >= 1024 && ceil_div64(h->ntotal, 16) < 4096;
-    // (its lists are 16 entries for k <= 16 -- the reference's k = 15 included -- instead of k + 6 <= 32: half the list registers,
-    // twice the waves per SIMD to hide the HBM latency behind.  A workgroup whose 16-entry list is used up by rows within the
-    // threshold rejects the query; the exact kernel over so small a store costs ~0.3 ms)
-    // (the same 16-entry lists on every f16 small-batch scan since round 4: k_knn_hi_smallq<32> streams the 1 M x 512 store in 0.40 ms,
-    // <16> in 0.20 -- 155 VGPRs against the 32-entry lists' panel of half the loads in flight)
-    p.ksel_sq = (smallq_hi && k <= 16) ? 16 : ksel;
-    if (p.sq_ksplit) {
-        int64_t rpg = 16;
-        while (ceil_div64(h->ntotal, rpg) * p.ksel_sq > RF_STAGE_MAX_SMALLQ) rpg += 16;
-        p.sq_rows_per_wave = (int)rpg;                // (rows per WORKGROUP in this form)
-        p.n_splits = (int)ceil_div64(h->ntotal, rpg);
-        p.n_qtiles = 1;
-    } else if (smallq || smallq_hi) {
-        // a wave streams >= 128 KB (128 rows at dim 512) so that its lists' hand-over stays small beside the stream, but no more
-        // rows than leave 8 waves for every CU; the lists of a query (one per workgroup) should fit the re-rank's staged form
-        // one full round of resident waves: 1024 SIMDs x the waves per SIMD the kernel's registers allow (k_knn_hi_smallq<16>: 155
-        // VGPRs = 3; the 32-entry and fp32 variants: 2).  (Measured: no difference against 2048 waves on the 1 M x 512 store -- 0.2075
-        // vs 0.208 ms, 4.93 TB/s either way: the stream is not limited by the number of waves in flight.)
-        const int64_t waves_wanted = 1024 * ((smallq_hi && p.ksel_sq <= 16) ? 3 : 2);
-        const size_t rb = smallq_hi ? (size_t)h->dim * 2 : (size_t)h->dim * 4;
-        const int64_t rows_min = std::max<int64_t>(16, std::min<int64_t>(128, ceil_div64(ceil_div64(128 * 1024, (int64_t)rb), 16) * 16));
-        int64_t rpw = std::max<int64_t>(ceil_div64(ceil_div64(h->ntotal, waves_wanted), 16) * 16, rows_min);
-        while (rpw < 128 && ceil_div64(ceil_div64(h->ntotal, rpw), 4) * p.ksel_sq > RF_STAGE_MAX_SMALLQ) rpw += 16;
-        p.sq_rows_per_wave = (int)rpw;
-        p.n_splits = (int)ceil_div64(ceil_div64(h->ntotal, rpw), 4);              // workgroups of 4 waves = lists per query
-        p.n_qtiles = 1;
-    }
-    p.sq_lds = smallq_hi ? sq_lds_hi : sq_lds_f32;
-    const bool f16_tile = !use_hi && !smallq_hi && h->f16 && ksel <= 32 && h->dim % 64 == 0;
-    p.kind = use_hi ? RADAD_SCAN_HI_TILE : dense ? RADAD_SCAN_F32_DENSE : smallq_hi ? RADAD_SCAN_HI_SMALLQ : smallq ? RADAD_SCAN_F32_SMALLQ
-           : f16_tile ? RADAD_SCAN_F16_TILE : RADAD_SCAN_F32_TILE;
-    p.emit_cap = use_hi ? std::min(RF_STAGE_MAX, std::max(1024 * h->cap_boost, 32 * ksel)) : 0;
-    h->last_qtiles = p.n_qtiles;                       // (the dense kernel's own query tiles are not reported)
-    if (dense) { p.n_qtiles = (int)ceil_div64(nq, 16); p.n_splits = 1; }
-    h->last_threads = use_hi ? KW_THREADS : ((smallq || smallq_hi || dense) ? SQ_THREADS : KNN_THREADS);
-    h->last_kind = p.kind;
-    p.plen = use_hi ? p.emit_cap : dense ? p.dense_plen : p.ksel_sq;   // entries of a partial list / of the candidate buffer
-    p.n_parts = (use_hi || dense) ? 1 : p.n_splits;
-    // (dense: eps of exact fp32 products is ~1e-6 of |q||y| -- hardly a row beyond the k best is within 2 eps; k + 32 candidates keep
-    // the re-rank's workgroup at 34 KB of LDS for 4096 staged scores, four per CU instead of three: the IVF coarse step's 1024
-    // workgroups in one round.  More near-ties than that reject the query: exact kernel.)
-    // (a handle that has widened its candidate buffers -- cap_boost: a store whose rows crowd within 2 eps of the k-th best -- also
-    // re-ranks four times as many: the fp32 funnel in front of the float64 re-score takes them at ~2 KB of row reads each)
-    p.cap = dense ? k + KNN_CERT_EXTRA : std::max(k + KNN_CERT_EXTRA, KNN_CERT_CAP * (use_hi ? h->cap_boost : 1));
-    p.xgroup = knn_exact_group(h->dim, k);
-    p.hi_q = use_hi || smallq_hi;
+    // (the facts again: a plane that could not be allocated has switched itself off)
+    if (knn_smallq_hi_eligible(knn_store_facts(h), nq, k, margin, use_hi, skipped_hi) && h->tune.take_smallq_turn())
+        smallq_hi = knn_ensure_hi(h, st, true);
+    ScanPlan p = knn_finish_plan(knn_store_facts(h), nq, k, margin, t, use_hi, smallq_hi);
     p.mu = (p.hi_q && !h->f16) ? h->cmu : nullptr;
     p.biased = p.hi_q && (p.l2 || p.mu);
+    h->last_qtiles = p.reported_qtiles;
+    h->last_threads = p.block_threads;
+    h->last_kind = p.kind;
     *out = p;
     return RADAD_OK;
-}
-
-// The search's workspace: qf (decoded bf16) | qn (normalised) | qh (f16 queries) | qscale | qconst | eps | thr_init | a_k | cand_cnt |
-// flag_count + statistics | flag_sel | part_score | part_idx | exact partial keys | ids.  Byte offsets into the handle's workspace.
-static SearchLayout knn_search_layout(radad_knn_t h, const ScanPlan& p, int q_dtype) {
-    const int64_t nq = p.nq;
-    const size_t qrow_f32 = al256((size_t)nq * h->dim * sizeof(float));
-    const size_t b_vec = al256((size_t)nq * sizeof(float));
-    SearchLayout L;
-    // (the sample pre-pass's lists live BEHIND the candidate buffers, not in them: k_floor_from_sample writes a query's floor while
-    // other queries' sample lists are still being read)
-    L.cand_elems = (size_t)nq * (size_t)p.n_parts * p.plen;
-    const size_t part_elems = L.cand_elems + (p.kind == RADAD_SCAN_HI_TILE ? (size_t)nq * KW_SAMPLE_SPLITS * KW_SAMPLE_LIST : 0);
-    const size_t b_part = al256(part_elems * sizeof(float));
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += bytes; return o; };
-    L.qf = take(q_dtype == RADAD_Q_BF16 ? qrow_f32 : 0);
-    L.qn = take(h->metric == RADAD_METRIC_COSINE ? qrow_f32 : 0);
-    L.qh = take(p.f16_queries() ? al256((size_t)nq * h->dim * 2) : 0);
-    L.qscale = take(b_vec);
-    L.qconst = take(b_vec);
-    L.eps = take(b_vec);
-    L.thr = take(b_vec);
-    L.ak = take(b_vec);            // a_k of the candidates (two-half searches: k_kth_floor -> k_merge_refine)
-    L.cnt = take(b_vec);           // cand_cnt [nq] int (zeroed by k_hi_rows with the counters)
-    L.fcount = take(256);          // flag_count + statistics
-    L.fsel = take(b_vec);
-    L.ps = take(b_part);
-    L.pi = take(b_part);
-    const int64_t xslots = knn_exact_slots(nq, p.k, p.xgroup);
-    L.xk = take(al256((size_t)xslots * KX_SLICES * p.k * sizeof(double)));
-    L.xi = take(al256((size_t)xslots * KX_SLICES * p.k * sizeof(int)));
-    L.bytes = off;
-    return L;
 }
 
 // ---- queries: decode, normalise, round (+ scale) to f16, error bound.  Returns the fp32 queries the scan and the re-rank read.
@@ -3469,44 +3180,7 @@ static const float* knn_prepare_queries(radad_knn_t h, const ScanPlan& p, const 
 }
 
 // ---- the certified f16 tile scan (knn_hi.inc) -------------------------------------------------------------------------------------
-// The phases of the scan, as row boundaries 0 = r[0] < r[1] < ... = n: a floor taken from m rows admits ~(rank / m) of what it is
-// applied to, so every launch covers at most 8 x the rows its floor was taken from -- the first 8 x the sample (phase0 rows) with the
-// sample's floor, the next 8 x that with the floor the candidates so far give (k_kth_floor), and so on: 2 launches up to 1.2 M rows,
-// 3 up to 9.5 M.  Each admits ~8 (k + margin) rows per query; the candidate buffer holds 32 (k + margin) (>= 1024): more (stores of
-// near-duplicates) rejects the query.  `one_go`: the sample's floor alone filters the store to a third of the buffer (~(k + margin) N /
-// sample rows): one launch.  (One launch with the floors raised inside it was measured slower and removed: DESIGN §4.1.)
-static std::vector<int64_t> knn_hi_phases(int64_t n, int64_t nq, int64_t phase0, bool one_go) {
-    std::vector<int64_t> r{0};
-    for (int64_t r0 = 0, span = phase0; r0 < n; span *= 8) {
-        // (a last phase of less than a quarter of its predecessor is not worth a launch of its own: it joins it)
-        int64_t r1 = std::min<int64_t>(n, r0 + span);
-        if (n - r1 < span / 4) r1 = n;
-        if (r0 == 0 && one_go) r1 = n;
-        // A launch deals whole tiles to its row splits, ceil(tiles / splits) each: what decides its time is that quotient, and a
-        // remainder of a few tiles costs a whole extra tile per workgroup (64 + 260 tiles over 128 splits = 1 + 3 tile times, the last
-        // round of the second launch nearly empty; 68 + 256 tiles = 1 + 2).  When the LAST launch follows this one, up to a quarter
-        // more tiles move into this one if that lowers the sum of the two quotients.  (BASELINE config 2 -- 100 k rows = 64 + 327
-        // tiles -- gains nothing from it: 1 + 3 either way; its scan stays at 0.27 of the MFMA peak, 1 564 tile tasks over 256 CUs.)
-        if (r1 < n && (n - r1 <= span * 8 || n - r1 - span * 8 < span * 2)) {
-            auto tile_time = [&](int64_t rows) {
-                int gq, gs; int64_t gc;
-                knn_geometry_wide(rows, nq, &gq, &gs, &gc);
-                return gc / KW_M;
-            };
-            const int64_t t_this = ceil_div64(r1 - r0, KW_M), t_rest = ceil_div64(n - r1, KW_M);
-            int64_t best = tile_time(r1 - r0) + tile_time(n - r1), best_s = 0;
-            for (int64_t sft = 1; sft <= std::min<int64_t>(t_this / 4, t_rest - 1); ++sft) {
-                const int64_t c = tile_time(r1 - r0 + sft * KW_M) + tile_time(n - r1 - sft * KW_M);
-                if (c < best) { best = c; best_s = sft; }
-            }
-            r1 += best_s * KW_M;
-        }
-        r.push_back(r1);
-        r0 = r1;
-    }
-    return r;
-}
-
+// (its phases -- row boundaries, one launch each -- are knn_hi_phases, knn_plan.h)
 // the tile scan's kernel for one RSC (knn_hi.inc), the sample pre-pass's or the scan's own
 static auto knn_hi_kernel(int rsc, bool sample) -> void (*)(KnnHiParams) {
     switch (rsc) {
@@ -3562,8 +3236,8 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
         // certificate rejected all 256 queries of a batch (tests/test_gpu_reference_shapes.py::test_a_store_that_drifts...).
         sp.n_splits = p.s_splits; sp.chunk_rows = KW_M;
         sp.part_score = ps + L.cand_elems; sp.part_idx = pi + L.cand_elems;
-        sp.chunk_stride = std::max<int64_t>(1, (h->ntotal / KW_M) / p.s_splits) * KW_M;
-        const int sq_grid = sp.n_qtiles <= 8 ? sp.n_qtiles : (sp.n_qtiles + 7) / 8 * 8;
+        sp.chunk_stride = knn_hi_sample_stride(h->ntotal, p.s_splits);
+        const int sq_grid = knn_hi_qtile_grid(sp.n_qtiles);
         // (the K split's scratch is indexed by row0 / KW_M: the sample's tiles lie anywhere in the store)
         sp.ksplit = knn_tile_ksplit(h, sq_grid, sp.n_splits, KW_M, h->ntotal, st);
         sp.kacc = h->kacc; sp.kflag = h->kflag;
@@ -3573,8 +3247,7 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
                            (const int*)sp.part_idx, n_ent, p.ksel, (const float*)eps, thr_init);
         wp.thr_init = thr_init;
     }
-    const bool one_go = (int64_t)p.ksel * h->ntotal <= (int64_t)(p.emit_cap / 3) * p.s_splits * KW_M;
-    const std::vector<int64_t> r = knn_hi_phases(h->ntotal, nq, (int64_t)8 * p.s_splits * KW_M, one_go);
+    const std::vector<int64_t> r = knn_hi_phases(h->ntotal, nq, (int64_t)8 * p.s_splits * KW_M, knn_hi_one_go(p, h->ntotal));
     h->last_scan_launches = h->last_scan_phases = (int)r.size() - 1;
     for (size_t i = 0; i + 1 < r.size(); ++i) {       // rows [r0, r1) of the store, one full round (or two) of workgroups
         const int64_t r0 = r[i], r1 = r[i + 1];
@@ -3595,7 +3268,7 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
         knn_geometry_wide(rp.n, nq, &gq, &gs, &gc);
         rp.n_splits = gs; rp.chunk_rows = gc; rp.chunk_stride = gc;
         h->last_splits = gs;
-        const int gq_grid = gq <= 8 ? gq : (gq + 7) / 8 * 8;                      // (more than 8 query tiles: whole groups of 8, see the kernel)
+        const int gq_grid = knn_hi_qtile_grid(gq);
         rp.ksplit = knn_tile_ksplit(h, gq_grid, gs, gc, rp.n, st);
         rp.kacc = h->kacc; rp.kflag = h->kflag;
         h->prof.begin(st);      // the event pair brackets a scan launch only (the kernel the roofline is quoted on; the phases of one
@@ -3717,14 +3390,14 @@ static int knn_search_phase1(radad_knn_t h, const void* q_in, int q_dtype, int64
 
     h->prof.next_search();
     knn_consume_reports(h);
-    const int cslot = (int)(h->search_seq & 1);
+    const int cslot = h->tune.slot();
 #ifdef RADAD_DEBUG_HOOKS
-    if (getenv("RADAD_DEBUG_KNN")) h->hi_skip = 0;     // timing ablations (wrong results, every query rejected): stay on the kernel under test
+    if (getenv("RADAD_DEBUG_KNN")) h->tune.clear_skip();    // timing ablations (wrong results, every query rejected): stay on the kernel under test
 #endif
     ScanPlan p;
     int rc = knn_plan_scan(h, nq, k, margin, st, &p);
     if (rc) return rc;
-    const SearchLayout L = knn_search_layout(h, p, q_dtype);
+    const SearchLayout L = knn_search_layout(knn_store_facts(h), p, q_dtype);
     if (L.bytes > h->ws_bytes) {
         RADAD_HIP_CHECK(hipDeviceSynchronize());
         rc = knn_workspace(h, L.bytes);
@@ -3814,17 +3487,12 @@ static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* glo
     }
     RADAD_HIP_CHECK(hipGetLastError());
 
-    // ---- look before the exact pass (see radad_knn_s::verify_next) ---------------------------------------------------------------
-    if (c.hi_tile && h->verify_next && nq >= 64 && (double)nq * (double)h->ntotal * (double)h->dim >= 4e11) {
+    // ---- look before the exact pass (see KnnTuning) ------------------------------------------------------------------------------
+    if (h->tune.looks_before_exact(c.hi_tile, nq, h->ntotal, h->dim)) {
         int* rej = h->host_count + 16;
         RADAD_HIP_CHECK(hipMemcpyAsync(rej, flag_count, sizeof(int), hipMemcpyDeviceToHost, st));
         RADAD_HIP_CHECK(hipStreamSynchronize(st));
-        if ((int64_t)*rej * 4 > nq && may_retry) {
-            knn_retune_after_mass_rejection(h);
-            ++h->verified_retries;
-            return RADAD_RETRY_INTERNAL;
-        }
-        if ((int64_t)*rej * 4 <= nq) { h->verify_next = false; h->hi_fail_streak = 0; }
+        if (h->tune.look_outcome(*rej, nq, may_retry, h->tune.appended_since_plane(h->hi != nullptr, h->ntotal))) return RADAD_RETRY_INTERNAL;
     }
 
     // ---- the queries the certificate rejected: exact float64 search, sized and driven by the device-side count ------
@@ -3835,7 +3503,7 @@ static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* glo
         x.slice_rows = ceil_div64(std::max<int64_t>(h->ntotal, 1), KX_SLICES);
         x.pkey = ws_at<double>(h, c.ws.xk); x.pidx = ws_at<int>(h, c.ws.xi); x.id_base = h->id_base;
         x.out_dist = out_dist_dev; x.out_idx = out_idx_dev; x.out_key = out_key_dev;
-        x.stamp = (int)(h->search_seq & 0x3fffffff) + 1;
+        x.stamp = h->tune.stamp();
         // (a search beyond KNN_F16_MAX_K took no f16 scan: its rejections say nothing about the f16 scans' tuning, which reads
         // batch sizes of >= 64 only -- knn_consume_reports)
         x.nq_report = k <= KNN_F16_MAX_K ? (int)std::min<int64_t>(nq, 0x7fffffff) : 0;
@@ -3868,7 +3536,7 @@ static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* glo
         }
         RADAD_HIP_CHECK(hipGetLastError());
         h->count_nq[c.cslot] = nq;                                     // (k_exact_scan writes the counters and its stamp to the pinned host copy)
-        ++h->search_seq;
+        h->tune.search_issued();
     }
     h->last_stream = st;
     h->have_last = true;
@@ -3906,29 +3574,6 @@ static int knn_search_core(radad_knn_t h, const void* q_in, int q_dtype, int64_t
 // ---- exclusion-aware search ---------------------------------------------------------------------------------------------------------
 // fast pass = the certified search at k_fetch (every scan path, float64 keys) -> k_excl_compact<false>: certificate per query, results of the
 // proved ones -> k_exact_scan_excl for the listed ones, sized and driven by the device-side count like the exact pass of any search.
-static ExclLayout knn_excl_layout(radad_knn_t h, int64_t nq, int k, int k_fetch, int64_t n_excl, bool begun) {
-    ExclLayout L;
-    L.kf = (int)std::min<int64_t>(k_fetch, h->ntotal);
-    L.whole = k_fetch > h->ntotal ? 1 : 0;          // the list was cut to the store: it is all there is (an unfilled slot, had it not been cut)
-    L.xgroup = knn_exact_group(h->dim, k);
-    L.xslots = knn_exact_slots(nq, k, L.xgroup);
-    L.n_words = ceil_div64(h->ntotal, 64);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al256(bytes); return o; };
-    L.fd = take((size_t)nq * L.kf * sizeof(float)); L.fi = take((size_t)nq * L.kf * sizeof(int64_t));
-    L.fk = take((size_t)nq * L.kf * sizeof(double));
-    L.count = take(256); L.sel = take((size_t)nq * sizeof(int));
-    L.admit = take(n_excl > 0 ? (size_t)L.n_words * sizeof(unsigned long long) : 0);
-    L.xk = take(n_excl > 0 ? (size_t)L.xslots * KX_SLICES * k * sizeof(double) : 0);
-    L.xi = take(n_excl > 0 ? (size_t)L.xslots * KX_SLICES * k * sizeof(int) : 0);
-    if (begun) {
-        L.bd = take((size_t)nq * k * sizeof(float)); L.bi = take((size_t)nq * k * sizeof(int64_t));
-        L.bk = take((size_t)nq * k * sizeof(double)); L.own = take((size_t)nq * sizeof(int));
-    }
-    L.bytes = off;
-    return L;
-}
-
 static int knn_excl_reserve(radad_knn_t h, size_t bytes) {
     if (bytes <= h->excl_ws_bytes) return RADAD_OK;
     RADAD_HIP_CHECK(hipDeviceSynchronize());              // an earlier search of this kind may still read the old one
@@ -3981,7 +3626,7 @@ static int knn_excl_exact_pass(radad_knn_t h, const ExclLayout& L, int64_t nq, i
 static int knn_excl_fast_pass(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* tags,
                               const int64_t* excl, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
                               double* fr_key_dev, int64_t* fr_idx_dev, hipStream_t st, bool begun, SearchCtx* c, ExclLayout* Lout) {
-    const ExclLayout L = knn_excl_layout(h, nq, k, k_fetch, n_excl, begun);
+    const ExclLayout L = knn_excl_layout(knn_store_facts(h), nq, k, k_fetch, n_excl, begun);
     int rc = knn_excl_reserve(h, L.bytes);
     if (rc) return rc;
     auto at = [&](size_t o) { return (char*)h->excl_ws + o; };
@@ -4266,9 +3911,9 @@ int radad_knn_last_recheck(radad_knn_t h, int* n_queries) {
     RADAD_REQUIRE(h && n_queries, "NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
-    const int ls = (int)((h->search_seq + 1) & 1);       // slot of the most recent certified search
+    const int ls = h->tune.last_slot();
     RADAD_HIP_CHECK(knn_wait_last_search(h));
-    *n_queries = (h->host_count && h->search_seq) ? h->host_count[8 * ls] : 0;
+    *n_queries = (h->host_count && h->tune.search_seq) ? h->host_count[8 * ls] : 0;
     return RADAD_OK;
 }
 
@@ -4276,10 +3921,10 @@ int radad_knn_last_certificate(radad_knn_t h, int64_t* n_queries, int* stats6) {
     RADAD_REQUIRE(h && stats6, "NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
-    const int ls = (int)((h->search_seq + 1) & 1);       // slot of the most recent certified search
+    const int ls = h->tune.last_slot();
     RADAD_HIP_CHECK(knn_wait_last_search(h));
-    for (int i = 0; i < 6; ++i) stats6[i] = (h->host_count && h->search_seq) ? h->host_count[8 * ls + i] : 0;
-    if (n_queries) *n_queries = h->search_seq ? h->count_nq[ls] : 0;
+    for (int i = 0; i < 6; ++i) stats6[i] = (h->host_count && h->tune.search_seq) ? h->host_count[8 * ls + i] : 0;
+    if (n_queries) *n_queries = h->tune.search_seq ? h->count_nq[ls] : 0;
     return RADAD_OK;
 }
 
@@ -4303,7 +3948,7 @@ int radad_knn_plane_info(radad_knn_t h, int* built, int* centred, int* one_scale
 int radad_knn_plane_rebuilds(radad_knn_t h, int* n_out) {
     RADAD_REQUIRE(h && n_out, "NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    *n_out = h->plane_rebuilds;
+    *n_out = h->tune.plane_rebuilds;
     return RADAD_OK;
 }
 
@@ -4334,9 +3979,9 @@ int radad_knn_last_scan_phases(radad_knn_t h, int* n_phases) {
 int radad_knn_tuning_info(radad_knn_t h, int* cap_boost, int* fp32_searches_left, int64_t* reports_consumed) {
     RADAD_REQUIRE(h && cap_boost && fp32_searches_left && reports_consumed, "NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    *cap_boost = h->cap_boost;
-    *fp32_searches_left = h->hi_skip;
-    *reports_consumed = h->reports_consumed;
+    *cap_boost = h->tune.cap_boost;
+    *fp32_searches_left = h->tune.hi_skip;
+    *reports_consumed = h->tune.reports_consumed;
     return RADAD_OK;
 }
 

@@ -26,13 +26,10 @@
 // Tile: 256 rows x 256 queries per workgroup (8 waves, each 128 rows x 64 queries = 32 accumulator tiles of 16 x 16),
 // one workgroup per CU, K stepped 64 elements (128-byte LDS rows) through two 64 KB stages filled by LDS-DMA; XOR
 // swizzle on the source side and on the reads (16-byte chunk c of row r lives at chunk c ^ ((r >> 1) & 7)).
-constexpr int KW_M = 256;                          // store rows per tile
-constexpr int KW_N = 256;                          // queries per tile
-constexpr int KW_WAVES = 8;
-constexpr int KW_THREADS = KW_WAVES * 64;
+// (KW_M x KW_N = 256 x 256, KW_WAVES = 8, KW_THREADS, KW_SAMPLE_LIST: knn_plan.h)
 constexpr int KW_OP_BYTES = KW_M * 128;            // one operand of one stage: 256 rows x 128 B
 constexpr int KW_STAGE_BYTES = 2 * KW_OP_BYTES;    // A + B
-constexpr int KW_SAMPLE_LIST = 16;                 // sample pre-pass: entries per (query, tile): 8 holders x 2
+
 
 
 struct KnnHiParams {

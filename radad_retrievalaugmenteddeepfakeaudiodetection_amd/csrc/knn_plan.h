@@ -1,0 +1,504 @@
+// knn_plan.h -- the host side of a flat search that needs no GPU: which scan runs, with what geometry, lists, buffers and
+// workspace layout (the PLAN), and when a handle retunes after the certificate rejected most of a batch (KnnTuning).
+//
+// Plain C++17: no HIP header, no handle, no stream.  Everything here is integer arithmetic on what a store is (StoreFacts) and what a
+// search asks for (nq, k, margin); knn.hip supplies the facts, does the device work and launches what the plan says.
+// tests/knn_plan_check.cpp drives this header alone.
+#pragma once
+#include <algorithm>
+#include <stddef.h>
+#include <stdint.h>
+#include <vector>
+
+#include "../../include/radad_hip.h"
+#include "ceil_div.h"
+
+// ---- constants the plan reads (the kernels of knn.hip / knn_hi.inc are written against the same ones) ---------------------------
+// fp32 tile kernels (k_knn_f32, k_knn_f32_reg)
+constexpr int KT_M = 128;       // store rows per tile (MFMA A rows)
+constexpr int KT_N = 128;       // queries per tile (MFMA B columns)
+constexpr int KNN_THREADS = 256;
+// certified f16 tile scan (knn_hi.inc)
+constexpr int KW_M = 256;                          // store rows per tile
+constexpr int KW_N = 256;                          // queries per tile
+constexpr int KW_WAVES = 8;
+constexpr int KW_THREADS = KW_WAVES * 64;
+constexpr int KW_SAMPLE_LIST = 16;                 // sample pre-pass: entries per (query, tile): 8 holders x 2
+constexpr int KW_SAMPLE_SPLITS = 64;     // one-tile splits of the threshold pre-pass (<= 16384 rows)
+// small-batch streaming kernels
+constexpr int SQ_THREADS = 256;
+constexpr int SQ_NQ = 16;
+constexpr int SQ_SLOTS = 16;
+constexpr size_t SQ_LDS_BUDGET = 160 * 1024;      // the query block [nq][dim + pad] + slot buffers must fit one CU's LDS
+// re-rank (k_merge_refine)
+constexpr int KNN_MARGIN = 6;            // spare entries of a (query, chunk) list on the fp32 tile kernels
+constexpr int KNN_CERT_EXTRA = 32;       // candidates beyond k the certified re-rank can take before it gives up, at least ...
+constexpr int KNN_CERT_CAP = 512;        // ... and this many in all: stores of near-duplicates (the benchmark plants 2048 rows
+                                         // within 2e-2 of every query) put hundreds of rows within 2 eps of the k-th
+constexpr int KNN_F16_MAX_K = 128;       // largest k the certified f16 scans take; beyond it the fp32 tile kernels filter (certified too)
+constexpr int RF_STAGE_MAX = 6144;       // list entries per query that k_merge_refine<true> stages in LDS (48 KB + candidates)
+constexpr int RF_STAGE_MAX_SMALLQ = 16384;   // ... for batches of <= 16 queries (128 KB: occupancy does not matter there)
+// exact float64 kernel (k_exact_scan)
+constexpr int KX_THREADS = 512;
+constexpr int KX_WAVES = KX_THREADS / 64;
+constexpr int KX_SLICES = 64;
+constexpr size_t KX_LDS_MAX = 160 * 1024;              // LDS of a CU: the group's queries + KX_WAVES sorted lists of k per query
+constexpr size_t KX_PART_BUDGET = (size_t)128 << 20;   // workspace of one launch's partial lists (KX_SLICES x k x 12 B per query)
+
+static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// what the plan reads of a store and of its handle's options
+struct StoreFacts {
+    int64_t ntotal = 0;
+    int dim = 0, metric = 0, f16 = 0;
+    int hi_off = 0;              // 1: no f16 plane (switched off, or its allocation failed)
+    int opt_centre = -1, opt_smallq_hi = 1, opt_wide_min_q = SQ_NQ + 1, opt_dense = 1;     // radad_knn_set_option
+    int cap_boost = 1;           // KnnTuning::cap_boost
+};
+
+// ---- the exact kernel's grouping --------------------------------------------------------------------------------------------------
+// rejected queries one launch of k_exact_scan takes: as many as KX_PART_BUDGET holds partial lists for, a whole group at least.
+// (k = 1024: 170 per launch, 128 MiB -- instead of 64 x 1024 x 12 B = 768 KiB for EVERY query of the batch, 805 MB at nq = 1024;
+// k <= 128 with batches of up to 1365 queries: one launch, as before)
+static int64_t knn_exact_slots(int64_t nq, int k, int group) {
+    const int64_t per_q = (int64_t)KX_SLICES * k * (int64_t)(sizeof(double) + sizeof(int));
+    return std::min<int64_t>(nq, std::max<int64_t>(group, (int64_t)(KX_PART_BUDGET / per_q) / group * group));
+}
+
+// queries per workgroup of the exact kernel: the group's queries (<= 64 KB) and its KX_WAVES lists of k per query share the LDS
+// (the lists shrink it at large k: k = 1024 takes one query per workgroup, 98 KB of lists)
+static int knn_exact_group(int dim, int k) {
+    return (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(8, (size_t)(64 * 1024) / ((size_t)dim * 4)),
+                                                     (KX_LDS_MAX - 16) / ((size_t)dim * 4 + (size_t)KX_WAVES * k * 12)));
+}
+
+// ---- launch geometry --------------------------------------------------------------------------------------------------------------
+// choose the launch geometry: enough equal splits to put >= 2 workgroups on each of the 256 CUs
+static void knn_geometry(int64_t n, int64_t nq, int* n_qtiles, int* n_splits, int64_t* chunk_rows) {
+    const int qt = (int)ceil_div64(nq, KT_N);
+    const int64_t tiles = ceil_div64(n, KT_M);
+    int64_t want = ceil_div64(512, qt);            // splits so that qt*splits ~ 512 workgroups
+    want = std::min<int64_t>(want, tiles);
+    want = std::max<int64_t>(8, ceil_div64(want, 8) * 8);
+    want = std::min<int64_t>(want, 1024);
+    const int64_t tiles_per = ceil_div64(tiles, want);
+    *n_qtiles = qt;
+    *n_splits = (int)want;
+    *chunk_rows = tiles_per * KT_M;
+}
+
+// wide kernel: 256-query tiles, one workgroup per CU; two rounds of workgroups keep the tail short.  (The list-based scan of
+// rounds 1-2 also needed >= 64 chunks so that no 16-entry list was used up; the emit-mode scan has no lists: a sharded batch of
+// 32 query tiles now runs 16 chunks of 31 tiles instead of 64 chunks of 8, i.e. a quarter of the per-workgroup start-up cost.)
+static void knn_geometry_wide(int64_t n, int64_t nq, int* n_qtiles, int* n_splits, int64_t* chunk_rows) {
+    const int qt = (int)ceil_div64(nq, KW_N);
+    const int64_t tiles = ceil_div64(n, KW_M);
+    int64_t want = ceil_div64(512, qt);
+    want = std::min<int64_t>(want, tiles);
+    want = std::max<int64_t>(8, ceil_div64(want, 8) * 8);
+    want = std::min<int64_t>(want, 1024);
+    int64_t tiles_per = ceil_div64(tiles, want);
+    // A launch takes (rounds of 256 workgroups) x (tiles per chunk) tile times, and both factors round up.  Round 4 always took
+    // ceil(512 / query tiles) chunks ("two rounds keep the tail short"): right for 4 query tiles x 1 M rows (2 x 31 = 1 x 62), wrong
+    // where the rounding bites -- BASELINE config 2's 100 k rows = 391 tiles x 4 query tiles: 128 chunks of 4 tiles = 392 workgroups =
+    // 2 rounds x 4 = 8 tile times, 64 chunks of 7 = 224 workgroups = ONE round of 7; configs 4 / 5 at full size, 40 query tiles: 16
+    // chunks = 640 workgroups = 2.5 -> 3 rounds x 2442 tiles, 32 chunks = 1280 = exactly 5 rounds x 1221 (-17 %).  So: the cheapest by
+    // that count among one round's worth of chunks and `want`, `want` + 8, ... 4 x `want`, when it saves 3 % or more.
+    if (qt <= 256) {
+        auto cost = [&](int64_t per) { return ceil_div64((int64_t)qt * ceil_div64(tiles, per), 256) * per; };
+        int64_t best = want, best_per = tiles_per, best_cost = cost(tiles_per);
+        auto consider = [&](int64_t splits) {
+            splits = std::min<int64_t>(std::max<int64_t>(8, splits / 8 * 8), std::min<int64_t>(1024, std::max<int64_t>(8, ceil_div64(tiles, 8) * 8)));
+            const int64_t per = ceil_div64(tiles, splits);
+            const int64_t c = cost(per);
+            if (c * 100 < best_cost * 97) { best = splits; best_per = per; best_cost = c; }      // (a gain under 3 % is not worth leaving two rounds)
+        };
+        consider(256 / qt);
+        for (int64_t sp = want + 8; sp <= 4 * want; sp += 8) consider(sp);
+        want = best; tiles_per = best_per;
+    }
+    *n_qtiles = qt;
+    *n_splits = (int)want;
+    *chunk_rows = tiles_per * KW_M;
+}
+
+// ---- the plan ---------------------------------------------------------------------------------------------------------------------
+// what one search scans with: the kind of scan, its launch layout, its list / buffer sizes and how its queries are prepared
+struct ScanPlan {
+    int kind = RADAD_SCAN_F32_TILE;  // RADAD_SCAN_*
+    int64_t nq = 0;
+    int k = 0, l2 = 0;
+    int n_qtiles = 0, n_splits = 0;  // workgroups: query tiles x row splits (the streaming kernels: 1 x n_splits)
+    int64_t chunk_rows = 0;
+    int ksel = 0;                    // list length of the fp32 tile kernels: k + margin
+    int ksel_sq = 0;                 // ... of the small-batch kernels
+    int s_splits = 0;                // tile scan: tiles of the sample pre-pass
+    int emit_cap = 0;                // tile scan: entries of a query's candidate buffer
+    int cap = 0;                     // candidates the re-rank can take per query
+    int plen = 0, n_parts = 0;       // entries of a partial list / candidate buffer, lists per query
+    int sq_rows_per_wave = 0;        // small batches: rows per wave (per workgroup in the K-split form)
+    bool sq_ksplit = false;          // small batch over a small store of wide rows: k_knn_hi_smallq_ksplit
+    size_t sq_lds = 0;               // small batches: LDS of the streaming kernel
+    int dense_plen = 0;
+    int xgroup = 1;                  // queries per workgroup of the exact kernel
+    int reported_qtiles = 0;         // radad_knn_last_launch: query tiles (the dense kernel's own are not reported) ...
+    int block_threads = KNN_THREADS; // ... and threads per workgroup of the scan
+    bool hi_q = false;               // f16 queries with a per-query scale (the certified f16 kernels)
+    bool biased = false;             // the scale + bias variant of the f16 kernels (RSC 2, 3)
+    const float* mu = nullptr;       // centred plane: the queries are centred the same way
+    bool f16_queries() const { return kind == RADAD_SCAN_HI_TILE || kind == RADAD_SCAN_HI_SMALLQ || kind == RADAD_SCAN_F16_TILE; }
+};
+
+// small batches (<= 16 queries: the online predict() search, pipeline.py:1038-1054, is ONE query of dim 5376 / 3584) stream the
+// store; the kernels park only the nq queries handed over in LDS, so any dim goes as long as that block fits beside the slots
+// (16 queries of dim 5376 do not: such a batch takes the tile kernels like a large one)
+// (slots: float2 x 4 x SQ_NQ x SQ_SLOTS, or the u64 triples of 32-entry lists, + 4 ints per query.  This header knows no device types:
+// sizeof(float2), sizeof(u64) and sizeof(_Float16) are the literals 8, 8 and 2 here, and knn.hip static_asserts that they are)
+constexpr size_t SQ_SLOT_BYTES = std::max<size_t>((size_t)8 * 4 * SQ_NQ * SQ_SLOTS, (size_t)8 * 3 * SQ_NQ * 32) + sizeof(int) * 4 * SQ_NQ;
+static size_t knn_sq_lds_hi(int64_t nq, int dim) { return 2 * (size_t)nq * (dim + 8) + SQ_SLOT_BYTES; }                  // f16 queries
+static size_t knn_sq_lds_f32(int64_t nq, int dim) { return sizeof(float) * (size_t)nq * (dim + 4) + SQ_SLOT_BYTES; }
+
+// Whether a search may take the certified f16 TILE scan, and the sample pre-pass it would run.
+// the certified f16 scans take k <= KNN_F16_MAX_K: their candidate buffers (emit_cap <= RF_STAGE_MAX) and phase sizes are
+// tuned for ~8 (k + margin) admissions per launch.  Larger k is filtered by the fp32 tile kernels (lists of k + margin per
+// split), certified the same way.
+struct TileEligibility {
+    bool eligible = false;
+    int s_splits = 0;                // tiles of the sample pre-pass (set whenever the store and the batch qualify at all)
+    int n_qtiles = 0;                // query tiles of the tile scan
+};
+static TileEligibility knn_tile_eligibility(const StoreFacts& s, int64_t nq, int k, int margin) {
+    TileEligibility t;
+    const int ksel = k + margin;
+    const size_t sq_lds_hi = knn_sq_lds_hi(nq, s.dim), sq_lds_f32 = knn_sq_lds_f32(nq, s.dim);
+    const bool sq_fits = nq <= SQ_NQ && ksel <= 32 &&
+                         ((!s.hi_off && s.dim % 64 == 0 && sq_lds_hi <= SQ_LDS_BUDGET) || (!s.f16 && s.dim % 32 == 0 && sq_lds_f32 <= SQ_LDS_BUDGET));
+    const bool f16_k = k <= KNN_F16_MAX_K;
+    // the certified tile scan: its candidate buffers are sized from k; the floor's rank k + margin must exist in the sample (16
+    // entries per sample tile)
+    if (f16_k && (nq >= s.opt_wide_min_q || !sq_fits) && s.ntotal > 0 && s.dim % 64 == 0 && !s.hi_off) {
+        int wq, ws; int64_t wc;
+        knn_geometry_wide(s.ntotal, nq, &wq, &ws, &wc);
+        // the sample pre-pass: one tile per workgroup, at most KW_SAMPLE_SPLITS tiles and 1/8 of the store (whatever the number of
+        // query tiles: every phase of the scan is sized from the sample, a small sample means more phases)
+        // ... and about 3 % of it: the pre-pass multiplies every query tile with its rows, so on a shard of a row-sharded store -- 1/G of
+        // the rows against G times the queries -- a fixed 16 384-row sample was 12 % of the scan's own work at G = 8 (0.16 of 1.7 ms);
+        // large enough, though, for the floor's rank to exist twice over (16 entries per sample tile)
+        const int64_t tiles = s.ntotal / KW_M;
+        int64_t want = (tiles * 3 / 100 + 4) / 8 * 8;
+        const int64_t need = ((int64_t)(2 * ksel + KW_SAMPLE_LIST - 1) / KW_SAMPLE_LIST + 7) / 8 * 8;
+        want = std::max<int64_t>(std::max<int64_t>(want, need), 8);
+        // ... but never fewer tiles than fill ONE round of the chip: the pre-pass is one tile per workgroup, its time is that one
+        // tile's latency whether 32 or 256 workgroups run it, and a larger sample is a tighter first floor (BASELINE config 2's
+        // 100 k rows took 8 tiles = 2048 rows: every tile of the scan's first layer then admitted ~2 rows per query -- 512 returning
+        // atomics per workgroup and tile; with 48 tiles the whole store is one launch behind the sample's floor alone)
+        want = std::max<int64_t>(want, std::min<int64_t>(KW_SAMPLE_SPLITS, (256 / std::max(1, std::min(wq, 256))) / 8 * 8));
+        t.s_splits = (int)std::min<int64_t>(std::min<int64_t>(KW_SAMPLE_SPLITS, want), tiles / 8 / 8 * 8);
+        t.n_qtiles = wq;
+        t.eligible = t.s_splits >= 8 && t.s_splits * KW_SAMPLE_LIST >= 2 * ksel;
+    }
+    return t;
+}
+
+// Whether a search that did not take the tile scan (`use_hi`) may stream the f16 plane as a small batch (certified like the tile
+// scan): stores the plane is kept for, or fp16 stores.  A search whose tile scan was skipped by the tuning state does not ask again.
+static bool knn_smallq_hi_eligible(const StoreFacts& s, int64_t nq, int k, int margin, bool use_hi, bool skipped_hi) {
+    const bool smallq_geom = !use_hi && nq <= SQ_NQ && k + margin <= 32 && s.ntotal > 0;
+    return smallq_geom && k <= KNN_F16_MAX_K && s.opt_smallq_hi && s.dim % 64 == 0 && s.ntotal >= 16384 && !s.hi_off && !skipped_hi &&
+           knn_sq_lds_hi(nq, s.dim) <= SQ_LDS_BUDGET;
+}
+
+// The rest of the plan, once it is settled which certified f16 scan (if any) the search takes: `use_hi` the tile scan, `smallq_hi`
+// the small-batch stream of the plane.  (ScanPlan::mu / ::biased depend on the plane's centring: the caller fills them in.)
+static ScanPlan knn_finish_plan(const StoreFacts& s, int64_t nq, int k, int margin, const TileEligibility& t, bool use_hi, bool smallq_hi) {
+    ScanPlan p;
+    p.nq = nq; p.k = k; p.l2 = s.metric == RADAD_METRIC_L2 ? 1 : 0;
+    p.ksel = k + margin;
+    knn_geometry(std::max<int64_t>(s.ntotal, 1), nq, &p.n_qtiles, &p.n_splits, &p.chunk_rows);
+    const int ksel = p.ksel;
+    p.s_splits = t.s_splits;
+    if (use_hi) p.n_qtiles = t.n_qtiles;
+    const size_t sq_lds_hi = knn_sq_lds_hi(nq, s.dim), sq_lds_f32 = knn_sq_lds_f32(nq, s.dim);
+    const bool smallq_geom = !use_hi && nq <= SQ_NQ && ksel <= 32 && s.ntotal > 0;
+    // a small fp32 store (the IVF index's centroids; a database of a few thousand files): every score + select on the staged copy
+    p.dense_plen = (int)((std::max<int64_t>(s.ntotal, 1) + 3) / 4 * 4);
+    const bool dense = !use_hi && !smallq_hi && !s.f16 && s.opt_dense && s.ntotal >= 1 &&
+                       s.ntotal <= (nq <= SQ_NQ ? RF_STAGE_MAX_SMALLQ : RF_STAGE_MAX) && s.dim % 16 == 0 && nq * (int64_t)p.dense_plen <= ((int64_t)1 << 24);
+    const bool smallq = smallq_geom && !dense && !smallq_hi && !s.f16 && s.dim % 32 == 0 && sq_lds_f32 <= SQ_LDS_BUDGET;
+    // a small store of wide rows (the reference's own: 25 423 x 5376) has too few 16-row steps to occupy the chip with one wave per
+    // row slice: the K-split form puts four waves on every step
+    p.sq_ksplit = smallq_hi && s.dim >= 1024 && ceil_div64(s.ntotal, 16) < 4096;
+    // (its lists are 16 entries for k <= 16 -- the reference's k = 15 included -- instead of k + 6 <= 32: half the list registers,
+    // twice the waves per SIMD to hide the HBM latency behind.  A workgroup whose 16-entry list is used up by rows within the
+    // threshold rejects the query; the exact kernel over so small a store costs ~0.3 ms)
+    // (the same 16-entry lists on every f16 small-batch scan since round 4: k_knn_hi_smallq<32> streams the 1 M x 512 store in 0.40 ms,
+    // <16> in 0.20 -- 155 VGPRs against the 32-entry lists' panel of half the loads in flight)
+    p.ksel_sq = (smallq_hi && k <= 16) ? 16 : ksel;
+    if (p.sq_ksplit) {
+        int64_t rpg = 16;
+        while (ceil_div64(s.ntotal, rpg) * p.ksel_sq > RF_STAGE_MAX_SMALLQ) rpg += 16;
+        p.sq_rows_per_wave = (int)rpg;                // (rows per WORKGROUP in this form)
+        p.n_splits = (int)ceil_div64(s.ntotal, rpg);
+        p.n_qtiles = 1;
+    } else if (smallq || smallq_hi) {
+        // a wave streams >= 128 KB (128 rows at dim 512) so that its lists' hand-over stays small beside the stream, but no more
+        // rows than leave 8 waves for every CU; the lists of a query (one per workgroup) should fit the re-rank's staged form
+        // one full round of resident waves: 1024 SIMDs x the waves per SIMD the kernel's registers allow (k_knn_hi_smallq<16>: 155
+        // VGPRs = 3; the 32-entry and fp32 variants: 2).  (Measured: no difference against 2048 waves on the 1 M x 512 store -- 0.2075
+        // vs 0.208 ms, 4.93 TB/s either way: the stream is not limited by the number of waves in flight.)
+        const int64_t waves_wanted = 1024 * ((smallq_hi && p.ksel_sq <= 16) ? 3 : 2);
+        const size_t rb = smallq_hi ? (size_t)s.dim * 2 : (size_t)s.dim * 4;
+        const int64_t rows_min = std::max<int64_t>(16, std::min<int64_t>(128, ceil_div64(ceil_div64(128 * 1024, (int64_t)rb), 16) * 16));
+        int64_t rpw = std::max<int64_t>(ceil_div64(ceil_div64(s.ntotal, waves_wanted), 16) * 16, rows_min);
+        while (rpw < 128 && ceil_div64(ceil_div64(s.ntotal, rpw), 4) * p.ksel_sq > RF_STAGE_MAX_SMALLQ) rpw += 16;
+        p.sq_rows_per_wave = (int)rpw;
+        p.n_splits = (int)ceil_div64(ceil_div64(s.ntotal, rpw), 4);              // workgroups of 4 waves = lists per query
+        p.n_qtiles = 1;
+    }
+    p.sq_lds = smallq_hi ? sq_lds_hi : sq_lds_f32;
+    const bool f16_tile = !use_hi && !smallq_hi && s.f16 && ksel <= 32 && s.dim % 64 == 0;
+    p.kind = use_hi ? RADAD_SCAN_HI_TILE : dense ? RADAD_SCAN_F32_DENSE : smallq_hi ? RADAD_SCAN_HI_SMALLQ : smallq ? RADAD_SCAN_F32_SMALLQ
+           : f16_tile ? RADAD_SCAN_F16_TILE : RADAD_SCAN_F32_TILE;
+    p.emit_cap = use_hi ? std::min(RF_STAGE_MAX, std::max(1024 * s.cap_boost, 32 * ksel)) : 0;
+    p.reported_qtiles = p.n_qtiles;                    // (the dense kernel's own query tiles are not reported)
+    if (dense) { p.n_qtiles = (int)ceil_div64(nq, 16); p.n_splits = 1; }
+    p.block_threads = use_hi ? KW_THREADS : ((smallq || smallq_hi || dense) ? SQ_THREADS : KNN_THREADS);
+    p.plen = use_hi ? p.emit_cap : dense ? p.dense_plen : p.ksel_sq;   // entries of a partial list / of the candidate buffer
+    p.n_parts = (use_hi || dense) ? 1 : p.n_splits;
+    // (dense: eps of exact fp32 products is ~1e-6 of |q||y| -- hardly a row beyond the k best is within 2 eps; k + 32 candidates keep
+    // the re-rank's workgroup at 34 KB of LDS for 4096 staged scores, four per CU instead of three: the IVF coarse step's 1024
+    // workgroups in one round.  More near-ties than that reject the query: exact kernel.)
+    // (a handle that has widened its candidate buffers -- cap_boost: a store whose rows crowd within 2 eps of the k-th best -- also
+    // re-ranks four times as many: the fp32 funnel in front of the float64 re-score takes them at ~2 KB of row reads each)
+    p.cap = dense ? k + KNN_CERT_EXTRA : std::max(k + KNN_CERT_EXTRA, KNN_CERT_CAP * (use_hi ? s.cap_boost : 1));
+    p.xgroup = knn_exact_group(s.dim, k);
+    p.hi_q = use_hi || smallq_hi;
+    return p;
+}
+
+// ---- the certified f16 tile scan's launches ---------------------------------------------------------------------------------------
+// `one_go`: the sample's floor alone filters the store to a third of the buffer (~(k + margin) N / sample rows): one launch
+static bool knn_hi_one_go(const ScanPlan& p, int64_t ntotal) { return (int64_t)p.ksel * ntotal <= (int64_t)(p.emit_cap / 3) * p.s_splits * KW_M; }
+// rows between the sample pre-pass's tiles: every (tiles / s_splits)-th tile of the store
+static int64_t knn_hi_sample_stride(int64_t ntotal, int s_splits) { return std::max<int64_t>(1, (ntotal / KW_M) / s_splits) * KW_M; }
+// query tiles of a launch's grid: more than 8 run as whole groups of 8 (see the kernel)
+static int knn_hi_qtile_grid(int n_qtiles) { return n_qtiles <= 8 ? n_qtiles : (n_qtiles + 7) / 8 * 8; }
+
+// The phases of the scan, as row boundaries 0 = r[0] < r[1] < ... = n: a floor taken from m rows admits ~(rank / m) of what it is
+// applied to, so every launch covers at most 8 x the rows its floor was taken from -- the first 8 x the sample (phase0 rows) with the
+// sample's floor, the next 8 x that with the floor the candidates so far give (k_kth_floor), and so on: 2 launches up to 1.2 M rows,
+// 3 up to 9.5 M.  Each admits ~8 (k + margin) rows per query; the candidate buffer holds 32 (k + margin) (>= 1024): more (stores of
+// near-duplicates) rejects the query.  (One launch with the floors raised inside it was measured slower and removed: DESIGN §4.1.)
+static std::vector<int64_t> knn_hi_phases(int64_t n, int64_t nq, int64_t phase0, bool one_go) {
+    std::vector<int64_t> r{0};
+    for (int64_t r0 = 0, span = phase0; r0 < n; span *= 8) {
+        // (a last phase of less than a quarter of its predecessor is not worth a launch of its own: it joins it.  The quarter is taken
+        // HERE, before the balancing below: that may then move up to a quarter of this phase's tiles out of the last one, which can
+        // end up shorter)
+        int64_t r1 = std::min<int64_t>(n, r0 + span);
+        if (n - r1 < span / 4) r1 = n;
+        if (r0 == 0 && one_go) r1 = n;
+        // A launch deals whole tiles to its row splits, ceil(tiles / splits) each: what decides its time is that quotient, and a
+        // remainder of a few tiles costs a whole extra tile per workgroup (64 + 260 tiles over 128 splits = 1 + 3 tile times, the last
+        // round of the second launch nearly empty; 68 + 256 tiles = 1 + 2).  When the LAST launch follows this one, up to a quarter
+        // more tiles move into this one if that lowers the sum of the two quotients.  (BASELINE config 2 -- 100 k rows = 64 + 327
+        // tiles -- gains nothing from it: 1 + 3 either way; its scan stays at 0.27 of the MFMA peak, 1 564 tile tasks over 256 CUs.)
+        if (r1 < n && (n - r1 <= span * 8 || n - r1 - span * 8 < span * 2)) {
+            auto tile_time = [&](int64_t rows) {
+                int gq, gs; int64_t gc;
+                knn_geometry_wide(rows, nq, &gq, &gs, &gc);
+                return gc / KW_M;
+            };
+            const int64_t t_this = ceil_div64(r1 - r0, KW_M), t_rest = ceil_div64(n - r1, KW_M);
+            int64_t best = tile_time(r1 - r0) + tile_time(n - r1), best_s = 0;
+            for (int64_t sft = 1; sft <= std::min<int64_t>(t_this / 4, t_rest - 1); ++sft) {
+                const int64_t c = tile_time(r1 - r0 + sft * KW_M) + tile_time(n - r1 - sft * KW_M);
+                if (c < best) { best = c; best_s = sft; }
+            }
+            r1 += best_s * KW_M;
+        }
+        r.push_back(r1);
+        r0 = r1;
+    }
+    return r;
+}
+
+// ---- workspace layouts ------------------------------------------------------------------------------------------------------------
+// byte offsets of a search's buffers in the handle's workspace (knn_search_layout)
+struct SearchLayout {
+    size_t qf = 0, qn = 0, qh = 0, qscale = 0, qconst = 0, eps = 0, thr = 0, ak = 0, cnt = 0, fcount = 0, fsel = 0, ps = 0, pi = 0, xk = 0, xi = 0;
+    size_t cand_elems = 0;     // entries of the candidate buffers / partial lists in ps, pi: the sample pre-pass's lists follow them
+    size_t bytes = 0;
+};
+
+// The search's workspace: qf (decoded bf16) | qn (normalised) | qh (f16 queries) | qscale | qconst | eps | thr_init | a_k | cand_cnt |
+// flag_count + statistics | flag_sel | part_score | part_idx | exact partial keys | ids.  Byte offsets into the handle's workspace.
+static SearchLayout knn_search_layout(const StoreFacts& s, const ScanPlan& p, int q_dtype) {
+    const int64_t nq = p.nq;
+    const size_t qrow_f32 = al256((size_t)nq * s.dim * sizeof(float));
+    const size_t b_vec = al256((size_t)nq * sizeof(float));
+    SearchLayout L;
+    // (the sample pre-pass's lists live BEHIND the candidate buffers, not in them: k_floor_from_sample writes a query's floor while
+    // other queries' sample lists are still being read)
+    L.cand_elems = (size_t)nq * (size_t)p.n_parts * p.plen;
+    const size_t part_elems = L.cand_elems + (p.kind == RADAD_SCAN_HI_TILE ? (size_t)nq * KW_SAMPLE_SPLITS * KW_SAMPLE_LIST : 0);
+    const size_t b_part = al256(part_elems * sizeof(float));
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += bytes; return o; };
+    L.qf = take(q_dtype == RADAD_Q_BF16 ? qrow_f32 : 0);
+    L.qn = take(s.metric == RADAD_METRIC_COSINE ? qrow_f32 : 0);
+    L.qh = take(p.f16_queries() ? al256((size_t)nq * s.dim * 2) : 0);
+    L.qscale = take(b_vec);
+    L.qconst = take(b_vec);
+    L.eps = take(b_vec);
+    L.thr = take(b_vec);
+    L.ak = take(b_vec);            // a_k of the candidates (two-half searches: k_kth_floor -> k_merge_refine)
+    L.cnt = take(b_vec);           // cand_cnt [nq] int (zeroed by k_hi_rows with the counters)
+    L.fcount = take(256);          // flag_count + statistics
+    L.fsel = take(b_vec);
+    L.ps = take(b_part);
+    L.pi = take(b_part);
+    const int64_t xslots = knn_exact_slots(nq, p.k, p.xgroup);
+    L.xk = take(al256((size_t)xslots * KX_SLICES * p.k * sizeof(double)));
+    L.xi = take(al256((size_t)xslots * KX_SLICES * p.k * sizeof(int)));
+    L.bytes = off;
+    return L;
+}
+
+// byte offsets in the handle's exclusion workspace
+struct ExclLayout {
+    size_t fd = 0, fi = 0, fk = 0;          // the fast pass's k_fetch lists (dist, id, key)
+    size_t count = 0, sel = 0;              // listed-query counter, listed queries
+    size_t admit = 0, xk = 0, xi = 0;       // admission bitmap, the filtered exact pass's partial lists
+    size_t bd = 0, bi = 0, bk = 0, own = 0; // begun form only: the shard's lists as _begin left them, and its own short-list flags
+    size_t bytes = 0;
+    int kf = 0, whole = 0, xgroup = 1;
+    int64_t xslots = 0, n_words = 0;
+};
+
+static ExclLayout knn_excl_layout(const StoreFacts& s, int64_t nq, int k, int k_fetch, int64_t n_excl, bool begun) {
+    ExclLayout L;
+    L.kf = (int)std::min<int64_t>(k_fetch, s.ntotal);
+    L.whole = k_fetch > s.ntotal ? 1 : 0;          // the list was cut to the store: it is all there is (an unfilled slot, had it not been cut)
+    L.xgroup = knn_exact_group(s.dim, k);
+    L.xslots = knn_exact_slots(nq, k, L.xgroup);
+    L.n_words = ceil_div64(s.ntotal, 64);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += al256(bytes); return o; };
+    L.fd = take((size_t)nq * L.kf * sizeof(float)); L.fi = take((size_t)nq * L.kf * sizeof(int64_t));
+    L.fk = take((size_t)nq * L.kf * sizeof(double));
+    L.count = take(256); L.sel = take((size_t)nq * sizeof(int));
+    L.admit = take(n_excl > 0 ? (size_t)L.n_words * sizeof(unsigned long long) : 0);
+    L.xk = take(n_excl > 0 ? (size_t)L.xslots * KX_SLICES * k * sizeof(double) : 0);
+    L.xi = take(n_excl > 0 ? (size_t)L.xslots * KX_SLICES * k * sizeof(int) : 0);
+    if (begun) {
+        L.bd = take((size_t)nq * k * sizeof(float)); L.bi = take((size_t)nq * k * sizeof(int64_t));
+        L.bk = take((size_t)nq * k * sizeof(double)); L.own = take((size_t)nq * sizeof(int));
+    }
+    L.bytes = off;
+    return L;
+}
+
+// ---- adaptive tuning --------------------------------------------------------------------------------------------------------------
+// What a handle does when the certificate rejects more than a quarter of a batch of >= 64 queries: re-decide the plane if rows were
+// appended since it was decided, else widen the candidate buffers once (cap_boost 1 -> 4), else leave the certified f16 kernels for
+// hi_skip searches (8, doubling to 512).  It learns of a rejection from the reports k_exact_scan stamps into two pinned slots, or by
+// looking at a large tile-scan search's certificate before its exact pass (verify_next).  Why, with the measurements: DESIGN.md §4.1,
+// "Adaptive tuning"; the rules themselves are the methods below, and tests/knn_plan_check.cpp states each with its numbers.
+struct KnnTuning {
+    int stamp_seen[2] = {0, 0};      // stamp of the last report consumed from each slot
+    bool verify_next = true;         // the next large tile-scan search looks at its certificate before the exact pass
+    int hi_fail_streak = 0;          // consecutive returns from the fp32 kernels that were rejected again
+    int64_t verified_retries = 0;    // searches run again after a look
+    int64_t reports_consumed = 0;    // (radad_knn_tuning_info)
+    uint64_t search_seq = 0;         // certified searches so far
+    int hi_skip = 0;                 // searches left on the fp32 kernels
+    int64_t plane_decided_rows = 0;  // rows the store held when the plane's centre and scale were decided
+    float plane_stat[2] = {0.f, 0.f};     // max |y'|, max |y' - yh| right after the plane was built
+    bool replan = false;             // decide the plane again at the next search that wants it
+    int plane_rebuilds = 0;          // (radad_knn_plane_rebuilds)
+    uint64_t tuned_at = 0;           // search_seq at the last change of the plane / of cap_boost / of hi_skip
+    int cap_boost = 1;               // candidate buffers of the tile scan: 1024 entries per query x this (1 or 4)
+
+    // -- the sequence of certified searches: search i reports into slot i % 2 under stamp (i mod 2^30) + 1
+    int slot() const { return (int)(search_seq & 1); }
+    int last_slot() const { return (int)((search_seq + 1) & 1); }       // slot of the most recent certified search
+    int stamp() const { return (int)(search_seq & 0x3fffffff) + 1; }
+    void search_issued() { ++search_seq; }
+
+    bool appended_since_plane(bool have_plane, int64_t ntotal) const { return have_plane && ntotal > plane_decided_rows; }
+
+    // a batch was mostly rejected by the certificate: re-decide the plane if rows were appended since it was decided, else widen the
+    // candidate buffers, else leave the f16 kernels for a while (8 searches, doubling while every return is rejected again)
+    void mass_rejection(bool appended) {
+        if (appended) replan = true;
+        else if (cap_boost == 1) cap_boost = 4;
+        else { hi_skip = 8 << std::min(hi_fail_streak, 6); ++hi_fail_streak; }
+        tuned_at = search_seq;
+        verify_next = true;
+    }
+
+    // A search eligible for the certified tile scan: true = take it, false = this search was counted off the skip (the search after
+    // the last skipped one looks before its exact pass).
+    bool take_tile_turn() {
+        if (hi_skip == 0) return true;
+        if (--hi_skip == 0) verify_next = true;
+        return false;
+    }
+    // ... for the small-batch stream of the plane (every search that would take a certified f16 kernel counts the skip down: a handle
+    // that only sees small batches after a mass rejection used to stay on the fp32 kernel for ever)
+    bool take_smallq_turn() {
+        if (hi_skip == 0) return true;
+        --hi_skip;
+        return false;
+    }
+    void clear_skip() { hi_skip = 0; }
+
+    // a slot holds a report (stamp != 0) that was not consumed yet
+    bool report_is_new(int slot, int stamp) const { return stamp != 0 && stamp != stamp_seen[slot]; }
+    // One report (slot, stamp, rejected queries, batch size), read consistently by the caller.  Returns whether it retuned: only
+    // off a skip, for batches of >= 64 with more than a quarter rejected, and only for a search issued since the last tuning change
+    // (a report from before the last change of the plane or of the buffers says nothing about them).
+    bool consume_report(int slot, int stamp, int rejected, int batch, bool appended) {
+        if (!report_is_new(slot, stamp)) return false;
+        stamp_seen[slot] = stamp;
+        ++reports_consumed;
+        // the report's own search: the one search at or below search_seq with that stamp's low 30 bits
+        const uint64_t rep_seq = report_search(stamp);
+        if (hi_skip == 0 && batch >= 64 && (int64_t)rejected * 4 > batch && rep_seq >= tuned_at) { mass_rejection(appended); return true; }
+        return false;
+    }
+    uint64_t report_search(int stamp) const {
+        const uint64_t cur30 = search_seq & 0x3fffffff, rep30 = (uint64_t)(stamp - 1);
+        return search_seq - ((cur30 - rep30) & 0x3fffffff);
+    }
+
+    // looking before the exact pass: only the tile scan, only when something changed, only where the exact pass would be expensive
+    bool looks_before_exact(bool hi_tile, int64_t nq, int64_t ntotal, int dim) const {
+        return hi_tile && verify_next && nq >= 64 && (double)nq * (double)ntotal * (double)dim >= 4e11;
+    }
+    // what the look saw.  true: retuned, run the search again (`may_retry`: not the last attempt)
+    bool look_outcome(int rejected, int64_t nq, bool may_retry, bool appended) {
+        if ((int64_t)rejected * 4 > nq && may_retry) {
+            mass_rejection(appended);
+            ++verified_retries;
+            return true;
+        }
+        if ((int64_t)rejected * 4 <= nq) { verify_next = false; hi_fail_streak = 0; }
+        return false;
+    }
+
+    // -- the plane.  `current`: a plane exists and was built for the store's present capacity (another capacity rebuilds it anyway)
+    bool plane_rebuild_due(bool current, int64_t ntotal) const {
+        return current && ntotal > plane_decided_rows && (replan || ntotal >= 2 * plane_decided_rows);
+    }
+    void plane_dropped_for_rebuild() { ++plane_rebuilds; tuned_at = search_seq; }
+    void plane_wanted() { replan = false; }          // whatever asked for a new decision is being served now
+    void plane_is_new() { verify_next = true; }
+    void plane_decided(float max_abs, float max_residual, int64_t ntotal) { plane_stat[0] = max_abs; plane_stat[1] = max_residual; plane_decided_rows = ntotal; }
+    // what the plane's operands measure after an append.  true: rows beyond what the scale was chosen for -- decide again, now
+    bool plane_outgrown(float max_abs, float max_residual) {
+        if ((plane_stat[0] > 0.f && max_abs > 8.f * plane_stat[0]) || (plane_stat[1] > 0.f && max_residual > 8.f * plane_stat[1])) { replan = true; return true; }
+        return false;
+    }
+};
