@@ -32,6 +32,8 @@
 //      hide more: rejected)
 //   5. rejected queries only: k_ivf_exact -- launched always, its workgroups leave at once when nobody was rejected
 // Without a plane (dim % 64 != 0, RADAD_IVF_OPT_HI_SCAN 0): k_ivf_f32_eps, k_ivf_scan, k_merge_refine<false> with that eps, k_ivf_exact.
+// What a search launches and allocates is decided by ivf_plan.h (host-only: tests/ivf_plan_check.cpp); ivf_search_lists is its glue.
+#include "ivf_plan.h"
 namespace {
 
 struct IvfScanParams {
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(256) void k_ivf_count(const int64_t* __restrict__ p
     if (i < npairs && (uint64_t)probes[i] < (uint64_t)nlist) atomicAdd(&cnt[(int)probes[i]], 1);
 }
 
-constexpr int IVF_TASK_THREADS = 1024;
+// (IVF_TASK_THREADS: ivf_plan.h)
 __global__ __launch_bounds__(IVF_TASK_THREADS) void k_ivf_tasks(int* __restrict__ cnt, int nlist, int qcap, int* __restrict__ cursor,
                                                                  int* __restrict__ task_list, int* __restrict__ task_pbeg,
                                                                  int* __restrict__ task_cnt, int* __restrict__ n_tasks) {
@@ -255,8 +257,7 @@ __global__ __launch_bounds__(SQ_THREADS, 2) void k_ivf_scan(IvfScanParams p) {
 // ---- grouping of a SMALL batch in one launch (npairs <= IVG_MAX_PAIRS, nlist <= IVG_MAX_LISTS): count, scan, task table and
 // scatter by one workgroup with the per-list counters in LDS (memset + k_ivf_count + k_ivf_tasks + k_ivf_scatter are four
 // dependent launches of ~5 us each, most of a one-query search)
-constexpr int IVG_MAX_PAIRS = 4096;
-constexpr int IVG_MAX_LISTS = 8192;
+// (IVG_MAX_PAIRS, IVG_MAX_LISTS: ivf_plan.h)
 __global__ __launch_bounds__(IVF_TASK_THREADS) void k_ivf_group_small(const int64_t* __restrict__ probes, int npairs, int nprobe, int nlist, int qcap,
                                                                      int* __restrict__ task_list, int* __restrict__ task_pbeg, int* __restrict__ task_cnt,
                                                                      int* __restrict__ n_tasks, int* __restrict__ pair_q, int* __restrict__ pair_slot,
@@ -341,14 +342,8 @@ struct IvfHiParams {
 };
 static_assert(std::is_trivially_copyable_v<IvfHiParams>, "kernel argument");
 
-constexpr int IVH_CHUNK = 256;                 // rows per chunk: 4 waves x 4 steps of 16
-constexpr int IVH_SLD = IVH_CHUNK + 4;         // score row (floats)
-constexpr int IVH_CAND_CAP = 2048;             // candidate buffer per query ...
-constexpr int IVH_CAND_CAP_SMALLQ = 8192;      // ... of a batch of <= 16 queries (its lists are split over several workgroups, each
-                                               // of which emits against the k-th best of its own few rows)
-constexpr size_t ivf_hi_lds_bytes(int qcap, int dim) {
-    return (size_t)qcap * (dim + 8) * 2 + (size_t)SQ_NQ * IVH_SLD * 4 + (size_t)SQ_NQ * 32 * 8;
-}
+// (IVH_CHUNK, IVH_SLD, IVH_CAND_CAP, IVH_CAND_CAP_SMALLQ, ivf_hi_lds_bytes: ivf_plan.h)
+static_assert(sizeof(_Float16) == 2, "ivf_plan.h sizes the f16 queries (ivf_hi_lds_bytes, the qbuf layout) with this as a literal");
 
 // EMIT mode, as the certified tile scan of the flat store: what leaves the kernel is, per query, every row of its probed lists whose
 // score is >= b - 2 eps for some lower bound b of a_k.  A per-(query, list) top-(k + 6) list -- the first version -- was rejected for
@@ -591,10 +586,6 @@ __global__ __launch_bounds__(256) void k_centroid_update(const float* __restrict
     centroids[(int64_t)c * dim + col] = v / (float)(b - a);
 }
 
-__global__ void k_i64_to_i32(const int64_t* in, int* out, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = (int)in[i];
-}
-
 // ---- the certificate of the fp32 list scan ---------------------------------------------------------------------------------------
 // k_ivf_scan ranks by a = fl(2 fl(q.y) - fl(|y|^2)).  With S = sum |q_i y_i| <= |q||y|: the two MFMA accumulators sum dim products in
 // dim / 8 steps of four each and are added once; |y|^2 is an fp32 sum of dim squares; one subtraction forms a.  Charging EVERY product
@@ -636,11 +627,8 @@ __global__ __launch_bounds__(256) void k_ivf_f32_eps(const float* __restrict__ q
 // sorted list ACROSS the wave's lanes (lane e holds entry e: k <= 26); the waves' lists are ranked into the pair's partial list, and
 // the workgroup that arrives last for a query (device-scope counter) merges the nprobe partial lists and overwrites the query's
 // output rows.  Keys are minus the squared distance: larger is better.
-constexpr int IVX_THREADS = 512;
-constexpr int IVX_WAVES = IVX_THREADS / 64;
+// (IVX_THREADS, IVX_WAVES, IVX_MAX_GRID, IVX_PART_BUDGET, ivf_exact_lds_bytes: ivf_plan.h)
 constexpr int IVX_ROWS = 4;                              // rows of a wave in flight
-constexpr int IVX_MAX_GRID = 4096;
-constexpr size_t IVX_PART_BUDGET = (size_t)128 << 20;    // partial lists of one launch (nprobe x k x 16 B per query)
 constexpr int64_t IVX_NO_ID = INT64_MAX;
 
 struct IvfExactParams {
@@ -662,9 +650,6 @@ struct IvfExactParams {
 };
 static_assert(std::is_trivially_copyable_v<IvfExactParams>, "kernel argument");
 
-constexpr size_t ivf_exact_lds_bytes(int dim, int k, int nprobe) {
-    return (size_t)dim * 4 + (size_t)IVX_WAVES * k * 16 + (size_t)nprobe * 4;
-}
 __device__ __forceinline__ bool ivx_better(double ka, int64_t ia, double kb, int64_t ib) { return ka > kb || (ka == kb && ia < ib); }
 
 // FILTERED (radad_ivf_search_excl): a row whose admission bit is clear is skipped before the insertion test.
@@ -800,8 +785,8 @@ struct radad_ivf_s {
     radad_knn_t quant = nullptr;        // flat L2 store over the centroids
     float* centroids = nullptr;         // [nlist, dim]
     radad_knn_t flat = nullptr;         // rows in insertion order (IP metric = plain copy; used for storage + reconstruct)
-    std::vector<int> assign;            // list of every stored row (host copy; the device copy is rebuilt with the layout)
-    DevMem lrows, lnorm, lids, loff, assign_dev, ws_a, ws_b, ws_c, part_s, part_i, tasks;
+    std::vector<int> assign;            // list of every stored row (host)
+    DevMem lrows, lnorm, lids, loff, ws_a, ws_b, ws_c, part_s, part_i, tasks;
     DevMem lmax, xkey, xid, xarrive;    // |y|^2 max of every list (the fp32 scan's error bound); partial lists + arrival counters of the exact list scan
     DevMem admit;                       // radad_ivf_search_excl: the admission bitmap by list-major position, rebuilt by every call
     DevMem lhi, lscale, lbias, qbuf, cand_s, cand_i;    // the flat store's f16 plane gathered list-major (+ per-row scale, bias); the queries' f16 side
@@ -942,6 +927,270 @@ static int ivf_last_counts(radad_ivf_t h, int* rejected_out, int* exact_out) {
     return RADAD_OK;
 }
 
+// ---- the list-scan search: ivf_plan.h decides, the functions below size the buffers and launch, one job each -------------------------
+template <typename T>
+static inline T* ivf_at(const DevMem& m, size_t off) { return reinterpret_cast<T*>((char*)m.p + off); }
+
+// what the launches of one search share
+struct IvfSearch {
+    radad_ivf_t h;
+    const IvfPlan& p;
+    const float* q;                      // [nq, dim]
+    float* out_dist; int64_t* out_idx;   // [nq, k]
+    hipStream_t st;
+    const unsigned long long* admit;     // the admission bitmap, or nullptr: every row is admissible (the unfiltered kernels run)
+    int* tasks(size_t off) const { return ivf_at<int>(h->tasks, off); }                            // a sub-array of `tasks` (p.tasks.*)
+    template <typename T> T* qbuf(size_t off) const { return ivf_at<T>(h->qbuf, off); }            // ... of `qbuf` (p.qbuf.*)
+    int* fcount() const { return qbuf<int>(p.qbuf.fcount); }
+    const int64_t* probes() const { return (const int64_t*)h->ws_b.p; }
+};
+
+// the plan's three refusals, with the error code and messages they have always had
+static int ivf_plan_refused(const char* fn, radad_ivf_t h, const IvfPlan& p) {
+    RADAD_REQUIRE(p.status != IVF_PLAN_TOO_MANY_PAIRS, "%s: too many (query, probe) pairs", fn);
+    RADAD_REQUIRE(p.status != IVF_PLAN_DIM_TOO_LARGE, "%s: dim %d too large for the list-scan kernel", fn, h->dim);
+    RADAD_REQUIRE(p.status != IVF_PLAN_NPROBE_TOO_LARGE, "%s: nprobe %d too large for the exact list scan", fn, p.nprobe);
+    return RADAD_OK;
+}
+
+// every buffer of the search at the plan's size.  `tasks` (its per-list counters start at zero) and `xarrive` (the arrival counters)
+// are cleared when, and only when, they are new memory.
+static int ivf_ensure_buffers(radad_ivf_t h, const IvfPlan& p, hipStream_t st) {
+    int rc;
+    if ((rc = h->admit.ensure(p.admit))) return rc;
+    if ((rc = h->ws_a.ensure(p.ws_a))) return rc;
+    if ((rc = h->ws_b.ensure(p.ws_b))) return rc;
+    if ((rc = h->part_s.ensure(p.part_s))) return rc;
+    if ((rc = h->part_i.ensure(p.part_i))) return rc;
+    if ((rc = h->qbuf.ensure(p.qbuf.bytes))) return rc;
+    if ((rc = h->cand_s.ensure(p.cand_s))) return rc;
+    if ((rc = h->cand_i.ensure(p.cand_i))) return rc;
+    if ((rc = h->xkey.ensure(p.xkey))) return rc;
+    if ((rc = h->xid.ensure(p.xid))) return rc;
+    // (a buffer that grew is new memory even when hipMalloc hands back the address hipFree just released: compare the sizes.  A grown
+    // xarrive's new tail is not zero -- the arrival counters of the slots behind the old size would start anywhere, their queries be
+    // merged early or never)
+    const size_t tasks_before = h->tasks.bytes, xarrive_before = h->xarrive.bytes;
+    if ((rc = h->tasks.ensure(p.tasks.bytes))) return rc;
+    if (h->tasks.bytes != tasks_before) RADAD_HIP_CHECK(hipMemsetAsync(h->tasks.p, 0, h->tasks.bytes, st));
+    if ((rc = h->xarrive.ensure(p.xarrive))) return rc;
+    if (h->xarrive.bytes != xarrive_before) RADAD_HIP_CHECK(hipMemsetAsync(h->xarrive.p, 0, h->xarrive.bytes, st));
+    return RADAD_OK;
+}
+
+// a trained index without rows: every slot unfilled (id -1, distance +inf; NaN for the exclusion-aware search)
+static int ivf_answer_empty(int64_t nq, int k, bool filtered, float* out_dist_dev, int64_t* out_idx_dev, hipStream_t st) {
+    hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)ceil_div64(nq * k, 256)), dim3(256), 0, st, out_dist_dev, nq * k,
+                       filtered ? __builtin_nanf("") : INFINITY);
+    RADAD_HIP_CHECK(hipGetLastError());
+    RADAD_HIP_CHECK(hipMemsetAsync(out_idx_dev, 0xff, (size_t)nq * k * sizeof(int64_t), st));
+    return RADAD_OK;
+}
+
+// the admission bitmap: on the search's stream, behind ivf_prepare (lids changes with every add); the tags and the set are the
+// caller's, so nothing of it is kept between calls
+static int ivf_launch_admit(const IvfSearch& s, const int64_t* row_tags, const int64_t* excl_sorted, int64_t n_excl) {
+    radad_ivf_t h = s.h;
+    const int64_t n = (int64_t)h->assign.size(), n_words = s.p.admit_words;
+    hipLaunchKernelGGL(k_admit_bitmap<true>, dim3((unsigned)ceil_div64(n_words * 64, 256)), dim3(256), 0, s.st, row_tags,
+                       (const int64_t*)h->lids.p, n, excl_sorted, n_excl, (const int*)nullptr, (unsigned long long*)h->admit.p, n_words);
+    RADAD_HIP_CHECK(hipGetLastError());
+    return RADAD_OK;
+}
+
+// 1) coarse quantiser: the nprobe nearest centroids of every query; 2) the (query, probe) pairs grouped by list on the device,
+// <= qcap queries per task (LDS holds qcap query rows)
+static int ivf_launch_coarse_group(const IvfSearch& s) {
+    radad_ivf_t h = s.h;
+    const IvfPlan& p = s.p;
+    const hipStream_t st = s.st;
+    int rc;
+    if ((rc = knn_search_core(h->quant, s.q, RADAD_Q_F32, p.nq, p.nprobe, p.cmargin, (float*)h->ws_a.p, (int64_t*)h->ws_b.p, nullptr, st))) return rc;
+    int* d_cnt = s.tasks(p.tasks.cnt); int* d_cur = s.tasks(p.tasks.cur); int* d_nt = s.tasks(p.tasks.nt);
+    int* d_tl = s.tasks(p.tasks.tl); int* d_tp = s.tasks(p.tasks.tp); int* d_tc = s.tasks(p.tasks.tc);
+    int* d_pq = s.tasks(p.tasks.pq); int* d_ps = s.tasks(p.tasks.ps);
+    if (p.group_small) {
+        hipLaunchKernelGGL(k_ivf_group_small, dim3(1), dim3(IVF_TASK_THREADS), p.group_lds, st, s.probes(), (int)p.npairs,
+                           p.nprobe, h->nlist, p.qcap, d_tl, d_tp, d_tc, d_nt, d_pq, d_ps, (float*)h->part_s.p, (int*)h->part_i.p, p.ksel);
+    } else {
+        const unsigned pair_blocks = (unsigned)((p.npairs + 255) / 256);
+        hipLaunchKernelGGL(k_ivf_count, dim3(pair_blocks), dim3(256), 0, st, s.probes(), p.npairs, h->nlist, d_cnt);
+        hipLaunchKernelGGL(k_ivf_tasks, dim3(1), dim3(IVF_TASK_THREADS), 0, st, d_cnt, h->nlist, p.qcap, d_cur, d_tl, d_tp, d_tc, d_nt);
+        hipLaunchKernelGGL(k_ivf_scatter, dim3(pair_blocks), dim3(256), 0, st, s.probes(), p.npairs, p.nprobe, h->nlist, d_cur, d_pq, d_ps,
+                           (float*)h->part_s.p, (int*)h->part_i.p, p.ksel);
+    }
+    RADAD_HIP_CHECK(hipGetLastError());
+    return RADAD_OK;
+}
+
+// what both routes' re-rank shares: the certificate's outputs, the float64 side, the search's outputs
+static RefineParams ivf_refine_params(const IvfSearch& s) {
+    radad_ivf_t h = s.h;
+    const IvfPlan& p = s.p;
+    RefineParams m;
+    m.k = p.k; m.dim = h->dim; m.l2 = 1; m.cap = p.cap; m.eps = s.qbuf<float>(p.qbuf.eps);
+    m.flag_count = s.fcount(); m.flag_sel = s.qbuf<int>(p.qbuf.fsel); m.nq = p.nq;
+    m.db = h->lrows.p; m.q = s.q; m.id_map = (const int64_t*)h->lids.p;
+    m.out_dist = s.out_dist; m.out_idx = s.out_idx;
+    return m;
+}
+
+// 3a) the certified f16 list scan: k_hi_rows on the queries (f16 side, eps; it zeroes cand_cnt, gbound and the counters),
+//     k_ivf_scan_hi (emit mode), k_merge_refine<true> with the certificate
+static int ivf_launch_hi_route(const IvfSearch& s) {
+    radad_ivf_t h = s.h;
+    const IvfPlan& p = s.p;
+    const hipStream_t st = s.st;
+    radad_knn_t f = h->flat;
+    _Float16* qh = s.qbuf<_Float16>(p.qbuf.qh);
+    float* qscale = s.qbuf<float>(p.qbuf.qscale); float* qconst = s.qbuf<float>(p.qbuf.qconst);
+    float* eps = s.qbuf<float>(p.qbuf.eps);
+    int* cand_cnt = s.qbuf<int>(p.qbuf.cand_cnt); unsigned* gbound = s.qbuf<unsigned>(p.qbuf.gbound);
+    HiRowsParams hp;
+    hp.in = s.q; hp.hi = qh; hp.scale_out = qscale; hp.eps_out = eps; hp.ystat = f->stat;
+    hp.n = p.nq; hp.dim = h->dim; hp.fixed_e = HI_E_PER_ROW; hp.l2 = 1;
+    hp.zero_flags = cand_cnt; hp.zero_flags2 = (int*)gbound; hp.zero_counters = s.fcount();
+    hp.mu = f->cmu; hp.mu_norm = f->cmu ? f->mu_norm : 0.f; hp.mu_sq = f->cmu ? f->mu_sq : 0.f; hp.biased = 1;
+    hp.qconst_out = qconst;
+    launch_hi_rows(hp, st);
+    IvfHiParams ip;
+    ip.lhi = (const _Float16*)h->lhi.p; ip.lscale = f->rscale ? (const float*)h->lscale.p : nullptr;
+    ip.uscale = f->uniform_e != HI_E_PER_ROW ? ldexpf(1.0f, -f->uniform_e) : 1.0f;
+    ip.lbias = (const float*)h->lbias.p; ip.loff = (const int*)h->loff.p; ip.qh = qh; ip.qscale = qscale; ip.qconst = qconst; ip.eps = eps;
+    ip.task_list = s.tasks(p.tasks.tl); ip.task_pbeg = s.tasks(p.tasks.tp); ip.task_cnt = s.tasks(p.tasks.tc);
+    ip.n_tasks_dev = s.tasks(p.tasks.nt); ip.pair_q = s.tasks(p.tasks.pq);
+    ip.split = p.split;
+    ip.dim = h->dim; ip.k = p.k; ip.qcap = p.qcap; ip.gbound = gbound; ip.cand_cnt = cand_cnt; ip.cand_cap = p.ccap;
+    ip.cand_score = (float*)h->cand_s.p; ip.cand_idx = (int*)h->cand_i.p; ip.admit = s.admit;
+    if (s.admit) {
+        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_scan_hi<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.scan_lds));
+        hipLaunchKernelGGL(k_ivf_scan_hi<true>, dim3((unsigned)p.scan_grid), dim3(SQ_THREADS), p.scan_lds, st, ip);
+    } else {
+        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_scan_hi<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.scan_lds));
+        hipLaunchKernelGGL(k_ivf_scan_hi<false>, dim3((unsigned)p.scan_grid), dim3(SQ_THREADS), p.scan_lds, st, ip);
+    }
+    RefineParams m = ivf_refine_params(s);
+    m.score = (const float*)h->cand_s.p; m.idx = (const int*)h->cand_i.p; m.n_parts = 1; m.part_len = p.ccap; m.part_cnt = cand_cnt;
+    if (p.refine_lds > 48 * 1024)
+        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge_refine<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.refine_lds));
+    hipLaunchKernelGGL(k_merge_refine<true>, dim3((unsigned)p.nq), dim3(RF_THREADS), p.refine_lds, st, m);
+    if (h->opt_hi == 2) {       // (tests) every query counts as rejected: the exact scan answers them all (ivf_launch_exact: slot s = query s)
+        float all;
+        const int in = (int)p.nq;
+        memcpy(&all, &in, 4);
+        hipLaunchKernelGGL(k_fill_f32, dim3(1), dim3(256), 0, st, (float*)s.fcount(), (int64_t)1, all);
+    }
+    RADAD_HIP_CHECK(hipGetLastError());
+    return RADAD_OK;
+}
+
+// 3b) the fp32 list scan (no f16 plane: dim % 64 != 0, RADAD_IVF_OPT_HI_SCAN 0): k_ivf_f32_eps (it zeroes the counters), then every
+//     touched list once, k + 6 entries per (query, list); k_merge_refine re-scores in float64 everything within 2 eps of the k-th best
+//     fp32 score and certifies the query unless a full list lies entirely inside that band (it may hide more) or the band holds more
+//     than `cap` rows
+static int ivf_launch_f32_route(const IvfSearch& s) {
+    radad_ivf_t h = s.h;
+    const IvfPlan& p = s.p;
+    const hipStream_t st = s.st;
+    hipLaunchKernelGGL(k_ivf_f32_eps, dim3((unsigned)ceil_div64(p.nq, 4)), dim3(256), 0, st, s.q, p.nq, h->dim, s.probes(), p.nprobe, h->nlist,
+                       (const float*)h->lmax.p, s.qbuf<float>(p.qbuf.eps), s.fcount());
+    IvfScanParams sp;
+    sp.lrows = (const float*)h->lrows.p; sp.lnorm = (const float*)h->lnorm.p; sp.loff = (const int*)h->loff.p; sp.q = s.q;
+    sp.task_list = s.tasks(p.tasks.tl); sp.task_pbeg = s.tasks(p.tasks.tp); sp.task_cnt = s.tasks(p.tasks.tc);
+    sp.n_tasks_dev = s.tasks(p.tasks.nt); sp.pair_q = s.tasks(p.tasks.pq); sp.pair_slot = s.tasks(p.tasks.ps);
+    sp.dim = h->dim; sp.k = p.ksel; sp.qcap = p.qcap;
+    sp.part_score = (float*)h->part_s.p; sp.part_idx = (int*)h->part_i.p; sp.admit = s.admit;
+    auto scan = [&](auto kern) -> int {
+        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.scan_lds));
+        hipLaunchKernelGGL(kern, dim3((unsigned)p.scan_grid), dim3(SQ_THREADS), p.scan_lds, st, sp);
+        return RADAD_OK;
+    };
+    int rc;
+    if (p.ksel <= 16) rc = s.admit ? scan(k_ivf_scan<16, true>) : scan(k_ivf_scan<16, false>);
+    else rc = s.admit ? scan(k_ivf_scan<32, true>) : scan(k_ivf_scan<32, false>);
+    if (rc) return rc;
+    RefineParams m = ivf_refine_params(s);
+    m.score = (const float*)h->part_s.p; m.idx = (const int*)h->part_i.p; m.n_parts = p.nprobe; m.part_len = p.ksel;
+    hipLaunchKernelGGL(k_merge_refine<false>, dim3((unsigned)p.nq), dim3(RF_THREADS), p.refine_lds, st, m);
+    RADAD_HIP_CHECK(hipGetLastError());
+    return RADAD_OK;
+}
+
+// 4) the queries the route's certificate rejected: exact float64 scan of their probed lists (leaves at once when there are none);
+//    one launch unless the batch's partial lists exceed IVX_PART_BUDGET
+static int ivf_launch_exact(const IvfSearch& s) {
+    radad_ivf_t h = s.h;
+    const IvfPlan& p = s.p;
+    IvfExactParams x;
+    x.lrows = (const float*)h->lrows.p; x.lids = (const int64_t*)h->lids.p; x.loff = (const int*)h->loff.p; x.q = s.q;
+    // the rejected queries: the certificate's list -- or, where the f16 route declared every query rejected (hi_scan 2), slot s = query s
+    x.sel = p.hi_route && h->opt_hi == 2 ? nullptr : s.qbuf<int>(p.qbuf.fsel);
+    x.probes = s.probes(); x.count = s.fcount(); x.done = s.fcount() + 1;
+    x.dim = h->dim; x.k = p.k; x.nprobe = p.nprobe; x.nlist = h->nlist; x.nslots = (int)p.nslots;
+    x.pkey = (double*)h->xkey.p; x.pid = (int64_t*)h->xid.p; x.arrive = (int*)h->xarrive.p;
+    x.out_dist = s.out_dist; x.out_idx = s.out_idx; x.admit = s.admit;
+    auto exact = [&](auto kern) -> int {
+        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.xlds));
+        for (int64_t i = 0; i < p.xlaunches; ++i) {
+            x.slot0 = (int)(i * p.nslots);
+            hipLaunchKernelGGL(kern, dim3((unsigned)p.xgrid), dim3(IVX_THREADS), p.xlds, s.st, x);
+        }
+        RADAD_HIP_CHECK(hipGetLastError());
+        return RADAD_OK;
+    };
+    return s.admit ? exact(k_ivf_exact<true>) : exact(k_ivf_exact<false>);
+}
+
+// unfilled slots of the exclusion-aware search: -1 / NaN, the padding of radad_filter_topk
+static int ivf_launch_pad_nan(const IvfSearch& s) {
+    hipLaunchKernelGGL(k_ivf_pad_nan, dim3((unsigned)ceil_div64(s.p.nq * s.p.k, 256)), dim3(256), 0, s.st, s.out_dist, (const int64_t*)s.out_idx, s.p.nq * s.p.k);
+    RADAD_HIP_CHECK(hipGetLastError());
+    return RADAD_OK;
+}
+
+// The list-scan search behind radad_ivf_search (filtered = false) and radad_ivf_search_excl (filtered = true).  The caller has
+// checked the arguments (k + KNN_MARGIN <= 32); this takes the handle's lock.  filtered: the exact top-k among the rows of the
+// probed lists whose tag (row_tags, by insertion id) is not in excl_sorted; unfilled slots -1 / NaN.  With n_excl == 0 every row is
+// admissible: the unfiltered kernels run and only the padding differs.
+static int ivf_search_lists(const char* fn, radad_ivf_t h, const float* q_dev, int64_t nq, int k, int nprobe, bool filtered, const int64_t* row_tags,
+                            const int64_t* excl_sorted, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, void* stream) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->last_exact = false;
+    DeviceGuard g(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if (!h->ev_done) RADAD_HIP_CHECK(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
+    if (h->have_last && st != h->last_stream) {
+        if (hipEventRecord(h->ev_done, h->last_stream) == hipSuccess) RADAD_HIP_CHECK(hipStreamWaitEvent(st, h->ev_done, 0));
+        else { (void)hipGetLastError(); RADAD_HIP_CHECK(hipDeviceSynchronize()); }
+    }
+    if ((rc = ivf_prepare(h, st))) return rc;
+    IvfFacts facts;
+    facts.dim = h->dim; facts.nlist = h->nlist; facts.rows = (int64_t)h->assign.size();
+    if (facts.rows == 0) {
+        if ((rc = ivf_answer_empty(nq, k, filtered, out_dist_dev, out_idx_dev, st))) return rc;
+        h->last_hi = false; h->last_fcount = nullptr;
+        h->last_stream = st; h->have_last = true;
+        return RADAD_OK;
+    }
+    facts.plane = ivf_ensure_plane(h, st);
+    const IvfPlan p = ivf_plan_search(facts, nq, k, nprobe, filtered && n_excl > 0);
+    if ((rc = ivf_plan_refused(fn, h, p))) return rc;
+    if ((rc = ivf_ensure_buffers(h, p, st))) return rc;
+
+    const IvfSearch s{h, p, q_dev, out_dist_dev, out_idx_dev, st, p.admit_words ? (const unsigned long long*)h->admit.p : nullptr};
+    if (p.admit_words && (rc = ivf_launch_admit(s, row_tags, excl_sorted, n_excl))) return rc;
+    if ((rc = ivf_launch_coarse_group(s))) return rc;
+    if ((rc = p.hi_route ? ivf_launch_hi_route(s) : ivf_launch_f32_route(s))) return rc;
+    h->last_hi = p.hi_route;
+    h->last_fcount = s.fcount();
+    if ((rc = ivf_launch_exact(s))) return rc;
+    if (filtered && (rc = ivf_launch_pad_nan(s))) return rc;
+    h->last_stream = st;
+    h->have_last = true;
+    return RADAD_OK;
+}
+
 extern "C" {
 
 int radad_ivf_create(int dim, int nlist, int device, radad_ivf_t* out) {
@@ -968,7 +1217,7 @@ int radad_ivf_destroy(radad_ivf_t h) {
     {
         DeviceGuard g(h->device);
         if (h->centroids) (void)hipFree(h->centroids);
-        h->lrows.release(); h->lnorm.release(); h->lids.release(); h->loff.release(); h->assign_dev.release();
+        h->lrows.release(); h->lnorm.release(); h->lids.release(); h->loff.release();
         h->ws_a.release(); h->ws_b.release(); h->ws_c.release(); h->part_s.release(); h->part_i.release(); h->tasks.release();
         h->lmax.release(); h->xkey.release(); h->xid.release(); h->xarrive.release();
         h->lhi.release(); h->lscale.release(); h->lbias.release(); h->qbuf.release(); h->cand_s.release(); h->cand_i.release();
@@ -1139,221 +1388,6 @@ int radad_ivf_last_search_counts(radad_ivf_t h, int* rejected_out, int* exact_ou
 int radad_ivf_reconstruct(radad_ivf_t h, const int64_t* idx_dev, int64_t n, float* out_dev, void* stream) {
     RADAD_REQUIRE(h, "NULL handle");
     return radad_knn_reconstruct(h->flat, idx_dev, n, out_dev, stream);
-}
-
-// The list-scan search behind radad_ivf_search (filtered = false) and radad_ivf_search_excl (filtered = true).  The caller has
-// checked the arguments (k + KNN_MARGIN <= 32); this takes the handle's lock.  filtered: the exact top-k among the rows of the
-// probed lists whose tag (row_tags, by insertion id) is not in excl_sorted; unfilled slots -1 / NaN.  With n_excl == 0 every row is
-// admissible: the unfiltered kernels run and only the padding differs.
-static int ivf_search_lists(const char* fn, radad_ivf_t h, const float* q_dev, int64_t nq, int k, int nprobe, bool filtered, const int64_t* row_tags,
-                            const int64_t* excl_sorted, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, void* stream) {
-    std::lock_guard<std::mutex> lk(h->mu);
-    h->last_exact = false;
-    DeviceGuard g(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    nprobe = std::max(1, std::min(nprobe, h->nlist));
-    int rc;
-    if (!h->ev_done) RADAD_HIP_CHECK(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
-    if (h->have_last && st != h->last_stream) {
-        if (hipEventRecord(h->ev_done, h->last_stream) == hipSuccess) RADAD_HIP_CHECK(hipStreamWaitEvent(st, h->ev_done, 0));
-        else { (void)hipGetLastError(); RADAD_HIP_CHECK(hipDeviceSynchronize()); }
-    }
-    if ((rc = ivf_prepare(h, st))) return rc;
-    const int64_t n = (int64_t)h->assign.size();
-    if (n == 0) {      // a trained index without rows: every slot unfilled (id -1, distance +inf; NaN for the exclusion-aware search)
-        hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)ceil_div64(nq * k, 256)), dim3(256), 0, st, out_dist_dev, nq * k,
-                           filtered ? __builtin_nanf("") : INFINITY);
-        RADAD_HIP_CHECK(hipGetLastError());
-        RADAD_HIP_CHECK(hipMemsetAsync(out_idx_dev, 0xff, (size_t)nq * k * sizeof(int64_t), st));
-        h->last_hi = false; h->last_fcount = nullptr;
-        h->last_stream = st; h->have_last = true;
-        return RADAD_OK;
-    }
-    const bool use_hi = ivf_ensure_plane(h, st);
-    // the admission bitmap: on the search's stream, behind ivf_prepare (lids changes with every add); the tags and the set are the
-    // caller's, so nothing of it is kept between calls
-    const unsigned long long* admit = nullptr;
-    if (filtered && n_excl > 0) {
-        const int64_t n_words = ((n + 63) >> 6) + 1;             // (+ 1: the spare word, all zero)
-        if ((rc = h->admit.ensure((size_t)n_words * sizeof(unsigned long long)))) return rc;
-        hipLaunchKernelGGL(k_admit_bitmap<true>, dim3((unsigned)ceil_div64(n_words * 64, 256)), dim3(256), 0, st, row_tags,
-                           (const int64_t*)h->lids.p, n, excl_sorted, n_excl, (const int*)nullptr, (unsigned long long*)h->admit.p, n_words);
-        RADAD_HIP_CHECK(hipGetLastError());
-        admit = (const unsigned long long*)h->admit.p;
-    }
-    const int ksel = k + KNN_MARGIN;
-    const int64_t npairs = nq * nprobe;
-
-    // 1) coarse quantiser: the nprobe nearest centroids of every query
-    if ((rc = h->ws_a.ensure((size_t)npairs * sizeof(float)))) return rc;
-    if ((rc = h->ws_b.ensure((size_t)npairs * sizeof(int64_t)))) return rc;
-    const int cmargin = nprobe + KNN_MARGIN <= 32 ? KNN_MARGIN : std::max(0, 32 - nprobe);   // keep the register-list kernels
-    if ((rc = knn_search_core(h->quant, q_dev, RADAD_Q_F32, nq, nprobe, cmargin, (float*)h->ws_a.p, (int64_t*)h->ws_b.p, nullptr, st))) return rc;
-    // 2) group the (query, probe) pairs by list on the device; <= qcap queries per task (LDS holds qcap query rows)
-    const int qcap = (int)std::max<size_t>(1, std::min<size_t>(SQ_NQ, (size_t)(112 * 1024) / ((size_t)(h->dim + 4) * sizeof(float))));
-    const int64_t T = std::min<int64_t>(h->nlist, npairs) + npairs / qcap + 1;      // upper bound on the number of tasks
-    RADAD_REQUIRE(npairs < (int64_t)1 << 31 && T < (int64_t)1 << 31, "%s: too many (query, probe) pairs", fn);
-    const size_t tb = (size_t)(3 * T + 2 * npairs + 2 * h->nlist + 1) * sizeof(int);
-    {
-        // (a buffer that grew is new memory even when hipMalloc hands back the address hipFree just released: compare the sizes)
-        const size_t before = h->tasks.bytes;
-        if ((rc = h->tasks.ensure(tb))) return rc;
-        if (h->tasks.bytes != before) RADAD_HIP_CHECK(hipMemsetAsync(h->tasks.p, 0, h->tasks.bytes, st));      // (the per-list counters start at zero)
-    }
-    // (the per-list counters FIRST: k_ivf_tasks leaves them zero for the next search, whatever that one's sizes are)
-    int* d_cnt = (int*)h->tasks.p; int* d_cur = d_cnt + h->nlist; int* d_nt = d_cur + h->nlist;
-    int* d_tl = d_nt + 1; int* d_tp = d_tl + T; int* d_tc = d_tp + T; int* d_pq = d_tc + T; int* d_ps = d_pq + npairs;
-    if ((rc = h->part_s.ensure((size_t)npairs * ksel * sizeof(float)))) return rc;
-    if ((rc = h->part_i.ensure((size_t)npairs * ksel * sizeof(int)))) return rc;
-    if (npairs <= IVG_MAX_PAIRS && h->nlist <= IVG_MAX_LISTS) {
-        hipLaunchKernelGGL(k_ivf_group_small, dim3(1), dim3(IVF_TASK_THREADS), (size_t)h->nlist * sizeof(int), st, (const int64_t*)h->ws_b.p, (int)npairs,
-                           nprobe, h->nlist, qcap, d_tl, d_tp, d_tc, d_nt, d_pq, d_ps, (float*)h->part_s.p, (int*)h->part_i.p, ksel);
-    } else {
-        const unsigned pair_blocks = (unsigned)((npairs + 255) / 256);
-        hipLaunchKernelGGL(k_ivf_count, dim3(pair_blocks), dim3(256), 0, st, (const int64_t*)h->ws_b.p, npairs, h->nlist, d_cnt);
-        hipLaunchKernelGGL(k_ivf_tasks, dim3(1), dim3(IVF_TASK_THREADS), 0, st, d_cnt, h->nlist, qcap, d_cur, d_tl, d_tp, d_tc, d_nt);
-        hipLaunchKernelGGL(k_ivf_scatter, dim3(pair_blocks), dim3(256), 0, st, (const int64_t*)h->ws_b.p, npairs, nprobe, h->nlist, d_cur, d_pq, d_ps,
-                           (float*)h->part_s.p, (int*)h->part_i.p, ksel);
-    }
-    RADAD_HIP_CHECK(hipGetLastError());
-
-    // per-query scratch of either route: eps, the certificate's list of rejected queries, the search's counters
-    const bool hi_route = use_hi && ivf_hi_lds_bytes(qcap, h->dim) <= 160 * 1024;
-    const size_t b_qh = hi_route ? al256((size_t)nq * h->dim * 2) : 0, b_vec = al256((size_t)nq * sizeof(float));
-    if ((rc = h->qbuf.ensure(b_qh + 6 * b_vec + 256))) return rc;
-    char* qb = (char*)h->qbuf.p;
-    float* eps = (float*)(qb + b_qh + 2 * b_vec);
-    int* fsel = (int*)(qb + b_qh + 5 * b_vec); int* fcount = (int*)(qb + b_qh + 6 * b_vec);      // fcount: [8], [0] rejected, [1] answered by the exact scan
-    const int* xsel = fsel;
-
-    if (hi_route) {
-        // 3a) the certified f16 list scan: k_hi_rows on the queries (f16 side, eps), k_ivf_scan_hi (emit mode), k_merge_refine<true> with the
-        //     certificate
-        // (the tasks hold <= qcap queries, sized for the fp32 kernel's query block: the f16 block is half of it and fits beside the score tile)
-        radad_knn_t f = h->flat;
-        const int ccap = nq <= SQ_NQ ? IVH_CAND_CAP_SMALLQ : IVH_CAND_CAP;
-        if ((rc = h->cand_s.ensure((size_t)nq * ccap * sizeof(float)))) return rc;
-        if ((rc = h->cand_i.ensure((size_t)nq * ccap * sizeof(int)))) return rc;
-        _Float16* qh = (_Float16*)qb;
-        float* qscale = (float*)(qb + b_qh); float* qconst = (float*)(qb + b_qh + b_vec);
-        int* cand_cnt = (int*)(qb + b_qh + 3 * b_vec); unsigned* gbound = (unsigned*)(qb + b_qh + 4 * b_vec);
-        HiRowsParams hp;
-        hp.in = q_dev; hp.hi = qh; hp.scale_out = qscale; hp.eps_out = eps; hp.ystat = f->stat;
-        hp.n = nq; hp.dim = h->dim; hp.fixed_e = HI_E_PER_ROW; hp.l2 = 1;
-        hp.zero_flags = cand_cnt; hp.zero_flags2 = (int*)gbound; hp.zero_counters = fcount;
-        hp.mu = f->cmu; hp.mu_norm = f->cmu ? f->mu_norm : 0.f; hp.mu_sq = f->cmu ? f->mu_sq : 0.f; hp.biased = 1;
-        hp.qconst_out = qconst;
-        launch_hi_rows(hp, st);
-        IvfHiParams ip;
-        ip.lhi = (const _Float16*)h->lhi.p; ip.lscale = f->rscale ? (const float*)h->lscale.p : nullptr;
-        ip.uscale = f->uniform_e != HI_E_PER_ROW ? ldexpf(1.0f, -f->uniform_e) : 1.0f;
-        ip.lbias = (const float*)h->lbias.p; ip.loff = (const int*)h->loff.p; ip.qh = qh; ip.qscale = qscale; ip.qconst = qconst; ip.eps = eps;
-        ip.task_list = d_tl; ip.task_pbeg = d_tp; ip.task_cnt = d_tc; ip.n_tasks_dev = d_nt; ip.pair_q = d_pq;
-        // few tasks (a one-query search has nprobe): several workgroups per list, as many as fill the chip -- but each emits ~k + 8 rows
-        // against its own bound, and all of a query's must fit half its buffer
-        ip.split = (int)std::max<int64_t>(1, std::min<int64_t>(T <= 64 ? 8 : (T <= 128 ? 4 : (T <= 256 ? 2 : 1)), (ccap / 2) / ((int64_t)nprobe * (k + 8))));
-        ip.dim = h->dim; ip.k = k; ip.qcap = qcap; ip.gbound = gbound; ip.cand_cnt = cand_cnt; ip.cand_cap = ccap;
-        ip.cand_score = (float*)h->cand_s.p; ip.cand_idx = (int*)h->cand_i.p; ip.admit = admit;
-        const size_t hlds = ivf_hi_lds_bytes(qcap, h->dim);
-        if (admit) {
-            RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_scan_hi<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)hlds));
-            hipLaunchKernelGGL(k_ivf_scan_hi<true>, dim3((unsigned)(T * ip.split)), dim3(SQ_THREADS), hlds, st, ip);
-        } else {
-            RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_scan_hi<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)hlds));
-            hipLaunchKernelGGL(k_ivf_scan_hi<false>, dim3((unsigned)(T * ip.split)), dim3(SQ_THREADS), hlds, st, ip);
-        }
-        RefineParams m;
-        m.score = (const float*)h->cand_s.p; m.idx = (const int*)h->cand_i.p; m.n_parts = 1; m.part_len = ccap; m.k = k; m.dim = h->dim; m.l2 = 1;
-        m.cap = std::max(k + KNN_CERT_EXTRA, KNN_CERT_CAP); m.eps = eps; m.part_cnt = cand_cnt;
-        m.flag_count = fcount; m.flag_sel = fsel; m.nq = nq;
-        m.db = h->lrows.p; m.q = q_dev; m.id_map = (const int64_t*)h->lids.p;
-        m.out_dist = out_dist_dev; m.out_idx = out_idx_dev;
-        const size_t rlds = refine_lds_bytes(m.cap) + (size_t)ccap * 8 + 1024;
-        if (rlds > 48 * 1024)
-            RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge_refine<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
-        hipLaunchKernelGGL(k_merge_refine<true>, dim3((unsigned)nq), dim3(RF_THREADS), rlds, st, m);
-        if (h->opt_hi == 2) {       // (tests) every query counts as rejected: the exact scan answers them all, slot s = query s
-            float all;
-            const int in = (int)nq;
-            memcpy(&all, &in, 4);
-            hipLaunchKernelGGL(k_fill_f32, dim3(1), dim3(256), 0, st, (float*)fcount, (int64_t)1, all);
-            xsel = nullptr;
-        }
-        RADAD_HIP_CHECK(hipGetLastError());
-    } else {
-        // 3b) the fp32 list scan (no f16 plane: dim % 64 != 0, RADAD_IVF_OPT_HI_SCAN 0): every touched list once, k + 6 entries per
-        //     (query, list); k_merge_refine re-scores in float64 everything within 2 eps of the k-th best fp32 score and certifies the
-        //     query unless a full list lies entirely inside that band (it may hide more) or the band holds more than `cap` rows
-        hipLaunchKernelGGL(k_ivf_f32_eps, dim3((unsigned)ceil_div64(nq, 4)), dim3(256), 0, st, q_dev, nq, h->dim, (const int64_t*)h->ws_b.p, nprobe, h->nlist,
-                           (const float*)h->lmax.p, eps, fcount);
-        IvfScanParams sp;
-        sp.lrows = (const float*)h->lrows.p; sp.lnorm = (const float*)h->lnorm.p; sp.loff = (const int*)h->loff.p; sp.q = q_dev;
-        sp.task_list = d_tl; sp.task_pbeg = d_tp; sp.task_cnt = d_tc; sp.n_tasks_dev = d_nt; sp.pair_q = d_pq; sp.pair_slot = d_ps; sp.dim = h->dim; sp.k = ksel;
-        sp.qcap = qcap;
-        sp.part_score = (float*)h->part_s.p; sp.part_idx = (int*)h->part_i.p; sp.admit = admit;
-        const size_t slot_bytes = std::max<size_t>(sizeof(float2) * 4 * SQ_NQ * SQ_SLOTS, sizeof(u64) * 3 * SQ_NQ * 32);
-        const size_t lds = sizeof(float) * qcap * (h->dim + 4) + slot_bytes + sizeof(int) * 4 * SQ_NQ;
-        RADAD_REQUIRE(lds <= 160 * 1024, "%s: dim %d too large for the list-scan kernel", fn, h->dim);
-        auto scan = [&](auto kern) -> int {
-            RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kern, dim3((unsigned)T), dim3(SQ_THREADS), lds, st, sp);
-            return RADAD_OK;
-        };
-        if (ksel <= 16) rc = admit ? scan(k_ivf_scan<16, true>) : scan(k_ivf_scan<16, false>);
-        else rc = admit ? scan(k_ivf_scan<32, true>) : scan(k_ivf_scan<32, false>);
-        if (rc) return rc;
-        RefineParams m;
-        m.score = (const float*)h->part_s.p; m.idx = (const int*)h->part_i.p; m.n_parts = nprobe; m.part_len = ksel; m.k = k; m.dim = h->dim;
-        m.cap = std::max(k + KNN_CERT_EXTRA, (int)std::min<int64_t>((int64_t)nprobe * ksel, KNN_CERT_CAP));
-        m.eps = eps; m.flag_count = fcount; m.flag_sel = fsel;
-        m.l2 = 1; m.nq = nq; m.db = h->lrows.p; m.q = q_dev; m.id_map = (const int64_t*)h->lids.p;
-        m.out_dist = out_dist_dev; m.out_idx = out_idx_dev;
-        hipLaunchKernelGGL(k_merge_refine<false>, dim3((unsigned)nq), dim3(RF_THREADS), refine_lds_bytes(m.cap), st, m);
-        RADAD_HIP_CHECK(hipGetLastError());
-    }
-    h->last_hi = hi_route;
-    h->last_fcount = fcount;
-
-    // 4) the queries the route's certificate rejected: exact float64 scan of their probed lists (leaves at once when there are none)
-    {
-        const size_t xlds = ivf_exact_lds_bytes(h->dim, k, nprobe);
-        RADAD_REQUIRE(xlds <= 160 * 1024, "%s: nprobe %d too large for the exact list scan", fn, nprobe);
-        const int64_t per_q = (int64_t)nprobe * k * 16;
-        const int64_t slots = std::min<int64_t>(nq, std::max<int64_t>(1, (int64_t)IVX_PART_BUDGET / per_q));
-        if ((rc = h->xkey.ensure((size_t)slots * nprobe * k * sizeof(double)))) return rc;
-        if ((rc = h->xid.ensure((size_t)slots * nprobe * k * sizeof(int64_t)))) return rc;
-        {
-            // (by size, not by address: a grown buffer may come back at the address just freed, and its new tail is not zero -- the
-            // arrival counters of the slots behind the old size then start anywhere, their queries are merged early or never)
-            const size_t before = h->xarrive.bytes;
-            if ((rc = h->xarrive.ensure((size_t)slots * sizeof(int)))) return rc;
-            if (h->xarrive.bytes != before) RADAD_HIP_CHECK(hipMemsetAsync(h->xarrive.p, 0, h->xarrive.bytes, st));
-        }
-        IvfExactParams x;
-        x.lrows = (const float*)h->lrows.p; x.lids = (const int64_t*)h->lids.p; x.loff = (const int*)h->loff.p; x.q = q_dev;
-        x.probes = (const int64_t*)h->ws_b.p; x.sel = xsel; x.count = fcount; x.done = fcount + 1;
-        x.dim = h->dim; x.k = k; x.nprobe = nprobe; x.nlist = h->nlist; x.nslots = (int)slots;
-        x.pkey = (double*)h->xkey.p; x.pid = (int64_t*)h->xid.p; x.arrive = (int*)h->xarrive.p;
-        x.out_dist = out_dist_dev; x.out_idx = out_idx_dev; x.admit = admit;
-        const unsigned grid = (unsigned)std::min<int64_t>(slots * nprobe, IVX_MAX_GRID);
-        auto exact = [&](auto kern) -> int {
-            RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
-            for (int64_t s0 = 0; s0 < nq; s0 += slots) {    // (one launch unless the batch's partial lists exceed IVX_PART_BUDGET)
-                x.slot0 = (int)s0;
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(IVX_THREADS), xlds, st, x);
-            }
-            RADAD_HIP_CHECK(hipGetLastError());
-            return RADAD_OK;
-        };
-        if ((rc = admit ? exact(k_ivf_exact<true>) : exact(k_ivf_exact<false>))) return rc;
-    }
-    if (filtered) {    // unfilled slots: -1 / NaN, the padding of radad_filter_topk
-        hipLaunchKernelGGL(k_ivf_pad_nan, dim3((unsigned)ceil_div64(nq * k, 256)), dim3(256), 0, st, out_dist_dev, (const int64_t*)out_idx_dev, nq * k);
-        RADAD_HIP_CHECK(hipGetLastError());
-    }
-    h->last_stream = st;
-    h->have_last = true;
-    return RADAD_OK;
 }
 
 int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int nprobe, float* out_dist_dev, int64_t* out_idx_dev,

@@ -1129,7 +1129,7 @@ constexpr size_t knn_reg_lds_bytes() { return 4 * KD_TILE_BYTES + sizeof(float2)
 //   eps == nullptr (IVF list scans): legacy behaviour -- the `cap` best candidates are re-scored, no certificate.
 // k_merge_lists<KeyT> (radad_topk_merge / _f64): plain P-way merge of final per-shard lists, no rescoring.
 // (KNN_MARGIN, KNN_CERT_EXTRA, KNN_CERT_CAP, KNN_F16_MAX_K, KW_SAMPLE_SPLITS, RF_STAGE_MAX, RF_STAGE_MAX_SMALLQ: knn_plan.h)
-constexpr int IVF_MAX_K = 128;           // largest k of radad_ivf_search (HipIVFFlatIndex.MAX_K); flat searches take any k <= RADAD_KNN_MAX_K
+// (IVF_MAX_K: ivf_plan.h)
 
 
 struct RefineParams {
@@ -1170,7 +1170,7 @@ static_assert(std::is_trivially_copyable_v<RefineParams>, "kernel argument");
 constexpr int RF_THREADS = 256;
 constexpr int RF_MAXL = 4;               // lists per thread: n_parts <= 1024
 
-constexpr size_t refine_lds_bytes(int cap) { return (size_t)cap * 20 + 256; }      // candidates + per-wave scratch of k_merge_refine
+// (refine_lds_bytes: knn_plan.h)
 
 // STAGED (certified mode, n_parts * part_len <= RF_STAGE_MAX): all of the query's list entries are first copied to LDS in ONE
 // round of independent loads, and the k selection rounds, the gathering of everything >= tau and the used-up test run on that

@@ -38,6 +38,7 @@ constexpr int KNN_CERT_CAP = 512;        // ... and this many in all: stores of 
 constexpr int KNN_F16_MAX_K = 128;       // largest k the certified f16 scans take; beyond it the fp32 tile kernels filter (certified too)
 constexpr int RF_STAGE_MAX = 6144;       // list entries per query that k_merge_refine<true> stages in LDS (48 KB + candidates)
 constexpr int RF_STAGE_MAX_SMALLQ = 16384;   // ... for batches of <= 16 queries (128 KB: occupancy does not matter there)
+constexpr size_t refine_lds_bytes(int cap) { return (size_t)cap * 20 + 256; }      // candidates + per-wave scratch of k_merge_refine
 // exact float64 kernel (k_exact_scan)
 constexpr int KX_THREADS = 512;
 constexpr int KX_WAVES = KX_THREADS / 64;

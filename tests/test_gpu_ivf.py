@@ -196,3 +196,43 @@ def test_ivf_fuzz_against_the_oracle(gpu, seed):
         np.testing.assert_array_equal(I, oi, err_msg=str(what))
         fin = np.isfinite(od)
         np.testing.assert_allclose(D[fin], od[fin], rtol=1e-6, atol=1e-5, err_msg=str(what))
+
+
+@pytest.fixture(scope="module")
+def exact_launches_case(gpu):
+    """4096 rows of dim 64 under 256 centroids that are rows of the store, every list probed at k = 26 with every query declared
+    rejected (hi_scan 2): k_ivf_exact answers the batch, 1260 queries per launch (256 x 26 x 16 B of partial lists each, 128 MiB per
+    launch).  The store, the queries, the index and the float64 oracle over the whole store, made once and released with the module."""
+    import radad_retrievalaugmenteddeepfakeaudiodetection_amd as R
+    n, dim, nlist, k = 4096, 64, 256, 26
+    db, q = synth.rows(0, n, dim, 5401), synth.rows(0, 1300, dim, 5403)
+    idx = R.HipIVFFlatIndex(dim, nlist, gpu.index or 0, hi_scan=2)
+    idx.set_centroids(db[:: n // nlist])
+    idx.add(db)
+    idx.nprobe = nlist
+    tags = np.arange(n, dtype=np.int64)
+    excl = np.sort(np.random.default_rng(5405).choice(n, n // 100, replace=False)).astype(np.int64)
+    keep = np.flatnonzero(~np.isin(tags, excl))
+    fd, fi = O.knn(db[keep], q, k, "L2")
+    yield dict(idx=idx, q=q, k=k, plain=O.knn(db, q, k, "L2"), tags=tags, excl=excl, filtered=(fd, keep[fi]))
+
+
+@pytest.mark.parametrize("nq,filtered", [(1260, False), (1261, False), (1300, False), (1300, True)])
+def test_ivf_exact_list_scan_in_more_than_one_launch(gpu, exact_launches_case, nq, filtered):
+    """the rejected queries' partial lists exceed the budget of one launch of k_ivf_exact from 1261 queries on: 1260 is one launch,
+    1261 and 1300 are two, the second with 1 and 40 live slots; unfiltered, and with 1 % of the rows excluded"""
+    import torch
+    c = exact_launches_case
+    idx, q, k = c["idx"], c["q"][:nq], c["k"]
+    if filtered:
+        qd, td, ed = (torch.from_numpy(a).to(gpu) for a in (q, c["tags"], c["excl"]))
+        D, I = (t.cpu().numpy() for t in idx.search_probed_excluding(qd, k, td, ed))
+        od, oi = c["filtered"]
+        assert not np.isin(I, c["excl"]).any()
+    else:
+        D, I = idx.search(q, k)
+        od, oi = c["plain"]
+    info = idx.last_search_info()
+    assert info["scan"] == "hi_lists" and info["rejected"] == nq and info["exact"] == nq, info
+    np.testing.assert_array_equal(I, oi[:nq])
+    np.testing.assert_allclose(D, od[:nq], rtol=1e-6, atol=1e-5)
