@@ -488,7 +488,11 @@ int radad_embed_forward_ex(radad_embed_t h, const float* wave_dev, const int64_t
 /* clip offsets resident on the DEVICE (int64 [n_clips + 1]): the segment plan (segmenter.py:25-39: n_seg per clip,
  * exclusive scan, start / valid samples of every segment) is built by a kernel, nothing synchronises with the host.
  * n_samples_total (= clip_offsets[n_clips], known to the caller from the wave buffer's size) only bounds the number of
- * segments for buffer and grid sizes. */
+ * segments for buffer and grid sizes.
+ * Offsets the plan kernel had to repair (radad_embed_plan_flags below): a clip whose own two offsets were valid and whose segments
+ * all fit under the cap embeds exactly as in a clean batch (tests/test_gpu_embed_plan.py); the output rows of every other clip of
+ * such a batch -- clamped, emptied, cut at the segment cap or behind the cut -- are written from inside the buffers but otherwise
+ * UNSPECIFIED (today: the mean over whatever segments the clip kept, not a number for a clip that kept none). */
 int radad_embed_forward_dev(radad_embed_t h, const float* wave_dev, const int64_t* clip_offsets_dev, int64_t n_clips,
                             int64_t n_samples_total, void* out_dev, int out_dtype, void* stream);
 /* 16-bit PCM (what audio files hold) -> the float32 samples the reference's loader produces (pipeline.py / dataset.py: librosa.load,
@@ -508,6 +512,32 @@ int radad_embed_plan_flags(radad_embed_t h, int* flags_out);
  * back to back polls before each one (it never blocks behind the previous batch) and calls radad_embed_plan_flags once after the
  * last. */
 int radad_embed_plan_flags_poll(radad_embed_t h, int* flags_out, int* batches_pending_out);
+/* Diagnostic (tests/test_gpu_embed_plan.py compares it with the host model tests/embed_plan_ref.py): the segment and chunk plan that
+ * the handle's most recent radad_embed_forward* or stage call (radad_embed_normalize / _logmel / _frame_features) built, copied to the
+ * host.  Waits for `stream` (the one that call was enqueued on); launches nothing, changes no plan and leaves the report ring of
+ * radad_embed_plan_flags[_poll] alone -- the flags here are read from the plan itself, those calls report exactly as before.
+ *   info8 = { n_clips, n_seg, n_chunks (0 when the call took no chunk plan), the repair flags of THIS plan (bits as above),
+ *             seg_cap and chunk_cap the plan was built under (host offsets: the exact counts; device offsets: the bounds
+ *             n_samples_total / hop + n_clips and the chunk bound derived from it; explicit segments: their number and 0),
+ *             RADAD_PLAN_* (which entry built it), RADAD_PLAN_CHUNKS_* (the chunk geometry) }
+ *   clip_seg_host  [n_clips + 1] first segment of every clip (explicit segments: one "clip" per segment); clip_capacity entries
+ *   seg_start_host, seg_valid_host [n_seg] absolute first sample and real samples of every segment; seg_capacity entries each
+ *   chunk_beg_host [n_chunks] int64 and chunk_fields_host [n_chunks][4] int32 = { seg0, n_seg, cidx, avail }: the work list of
+ *             k_logmel_h_clip / k_logmel_fft_clip (first sample of the chunk's clip, the clip's first segment and the segments it
+ *             kept, the chunk's index inside the clip, samples of the clip those segments cover); chunk_capacity entries
+ * NULL array pointers: that array is not wanted (all NULL: info only, e.g. to size the arrays for a second call).  info8 is written
+ * before the capacities are checked; an array that is too small is RADAD_EINVAL and nothing is copied.  RADAD_ESTATE before the first
+ * plan. */
+#define RADAD_PLAN_NONE 0
+#define RADAD_PLAN_HOST_OFFSETS 1
+#define RADAD_PLAN_DEVICE_OFFSETS 2
+#define RADAD_PLAN_SEGMENTS 3
+#define RADAD_PLAN_CHUNKS_NONE 0
+#define RADAD_PLAN_CHUNKS_GEMM 1   /* k_logmel_h_clip: 104 interior frames per chunk   */
+#define RADAD_PLAN_CHUNKS_FFT 2    /* k_logmel_fft_clip: 64 frame slots per chunk      */
+int radad_embed_last_plan(radad_embed_t h, int64_t* info8, int64_t* clip_seg_host, int64_t clip_capacity, int64_t* seg_start_host,
+                          int32_t* seg_valid_host, int64_t seg_capacity, int64_t* chunk_beg_host, int32_t* chunk_fields_host,
+                          int64_t chunk_capacity, void* stream);
 /* Which log-mel kernel the most recent embedding call took: 0 = one transform per (segment, frame) (k_logmel_h, or k_logmel under
  * RADAD_LOGMEL_F32); 1, 2 = the frames overlapping segments share were transformed once per CLIP (chosen by the configuration --
  * segment hop a multiple of 160 samples and smaller than the segment, Slaney filter bank -- for calls that hand over clips;

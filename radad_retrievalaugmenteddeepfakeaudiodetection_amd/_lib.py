@@ -23,6 +23,8 @@ KNN_OPT_HI_PLANE, KNN_OPT_CENTRE, KNN_OPT_SMALLQ_HI, KNN_OPT_WIDE_MIN_Q, KNN_OPT
 IVF_OPT_HI_SCAN = 0
 IVF_SCAN_KINDS = ("f32_lists", "hi_lists", "exact_flat")
 EMBED_NO_SHARED_FRAMES, EMBED_LOGMEL_F32, EMBED_LOGMEL_DFT_GEMM = 1, 2, 4
+PLAN_KINDS = ("none", "host_offsets", "device_offsets", "segments")      # RADAD_PLAN_*
+PLAN_CHUNKS = ("none", "gemm_104", "fft_64")                             # RADAD_PLAN_CHUNKS_*
 
 c_i64p = C.POINTER(C.c_int64)
 c_i32p = C.POINTER(C.c_int32)
@@ -145,6 +147,8 @@ SIGNATURES = {
     "radad_pcm16_to_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "radad_embed_plan_flags": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "radad_embed_plan_flags_poll": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "radad_embed_last_plan": (C.c_int, [C.c_void_p, c_i64p, c_i64p, C.c_int64, c_i64p, c_i32p, C.c_int64, c_i64p, c_i32p, C.c_int64,
+                                        C.c_void_p]),
     "radad_embed_last_logmel_kind": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "radad_embed_clip_chunks": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "radad_embed_fft_clip_chunks": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),

@@ -1166,6 +1166,11 @@ struct radad_embed_s {
     bool plan_uniform = true;            // every clip of the cached plan has the same number of segments
     DevBuf seg_start, seg_valid, clip_seg, seg_pool, logmel, seg_max, misc, clip_off, n_seg_dev;
     bool plan_on_device = false;         // the cached plan came from device-resident offsets: segment count only known there
+    // what the plan held by the handle was built from and under (radad_embed_last_plan reads these; nothing else does)
+    int plan_kind = RADAD_PLAN_NONE;     // RADAD_PLAN_*: which entry point built it
+    int64_t plan_nclips = 0;             // clips of the plan (explicit segments: one "clip" per segment)
+    int64_t plan_seg_cap = 0;            // segments k_build_plan was allowed to write (explicit segments: their number)
+    int64_t plan_chunk_cap = 0;          // chunk records it was allowed to write (0: no chunk plan)
     // two pinned staging buffers for clip offsets handed over in host memory (no stream synchronisation on the way)
     int64_t* pin[2] = {nullptr, nullptr};
     size_t pin_cap[2] = {0, 0};
@@ -1214,6 +1219,9 @@ static int plan_on_device(radad_embed_t h, const int64_t* clip_off_dev, int64_t 
     RADAD_HIP_CHECK(hipGetLastError());
     h->plan_has_chunks = chunk_cap > 0;
     h->plan_nchunks = chunk_cap;
+    h->plan_nclips = n_clips;
+    h->plan_seg_cap = seg_cap;
+    h->plan_chunk_cap = chunk_cap;
     return RADAD_OK;
 }
 static int64_t clip_chunks(const radad_embed_s* h, int64_t n_segments_of_clip) {       // chunks of one clip
@@ -1259,6 +1267,7 @@ static int build_plan(radad_embed_t h, const int64_t* clip_offsets, int64_t n_cl
     if ((rc = plan_on_device(h, (const int64_t*)h->clip_off.p, n_clips, std::max<int64_t>(n_seg, 1), -1, st, n_chunks))) return rc;
     h->plan_uniform = uniform;
     h->plan_on_device = false;
+    h->plan_kind = RADAD_PLAN_HOST_OFFSETS;
     h->plan_key.assign(clip_offsets, clip_offsets + n_clips + 1);
     h->plan_nseg = n_seg;
     return RADAD_OK;
@@ -1280,6 +1289,10 @@ static int upload_plan_explicit(radad_embed_t h, const int64_t* seg_start, const
     if ((rc = upload(h->clip_seg, cs.data(), cs.size() * sizeof(int64_t), st))) return rc;
     RADAD_HIP_CHECK(hipStreamSynchronize(st));
     h->plan_nseg = n_seg;
+    h->plan_kind = RADAD_PLAN_SEGMENTS;
+    h->plan_nclips = n_seg;
+    h->plan_seg_cap = n_seg;
+    h->plan_chunk_cap = 0;
     return RADAD_OK;
 }
 
@@ -1689,6 +1702,9 @@ int radad_pcm16_to_f32(const int16_t* pcm_dev, float* out_dev, int64_t n, int de
     return RADAD_OK;
 }
 
+// Offsets k_build_plan had to repair: clips whose own offsets were valid and whose segments all fit under seg_cap embed as in a clean
+// batch (pooled per segment, a clip's row does not depend on its neighbours); the rows of the other clips -- clamped, emptied, cut at
+// the cap or behind it -- are unspecified (k_group_mean averages whatever segments the clip kept: 0 / 0 for none).
 int radad_embed_forward_dev(radad_embed_t h, const float* wave_dev, const int64_t* clip_offsets_dev, int64_t n_clips,
                             int64_t n_samples_total, void* out_dev, int out_dtype, void* stream) {
     RADAD_REQUIRE(h, "NULL handle");
@@ -1703,7 +1719,9 @@ int radad_embed_forward_dev(radad_embed_t h, const float* wave_dev, const int64_
     // bound, the kernels read the true count from the device
     const int64_t seg_cap = n_samples_total / h->cfg.hop_length + n_clips;
     RADAD_REQUIRE(seg_cap < (1ll << 31), "radad_embed_forward_dev: too many segments in one batch");
-    // chunks: a clip of S segments has <= ((S - 1) H + T) / 96 + 1 + 3 S / 32 + 1 of them
+    // chunks: a clip of S segments has <= ((S - 1) H + T) / C + 1 + 3 S / E + 1 of them, C = LH_CLIP_FRAMES (104) and E = LH_EDGE_CHUNK
+    // (32) for k_logmel_h_clip, FC_SLOTS (64) and FC_EDGE_CHUNK (26) for k_logmel_fft_clip; summed over the clips with
+    // sum S <= seg_cap (tests/test_embed_plan_model.py checks the bound against the chunk arithmetic itself)
     const int64_t chunk_cap = !h->share_frames ? 0
                               : h->logmel_fft ? (seg_cap * h->share_H + n_clips * h->nf) / FC_SLOTS + (3 * seg_cap) / FC_EDGE_CHUNK + 2 * n_clips + 1
                                               : (seg_cap * h->share_H + n_clips * h->nf) / LH_CLIP_FRAMES + (3 * seg_cap) / LH_EDGE_CHUNK + 2 * n_clips + 1;
@@ -1712,6 +1730,7 @@ int radad_embed_forward_dev(radad_embed_t h, const float* wave_dev, const int64_
     if (rc) return rc;
     h->plan_key.clear();
     h->plan_on_device = true;
+    h->plan_kind = RADAD_PLAN_DEVICE_OFFSETS;
     h->plan_nseg = seg_cap;
     if ((rc = embed_run(h, wave_dev, n_clips, seg_cap, false, out_dev, out_dtype, (const int*)h->n_seg_dev.p, st))) return rc;
     // what k_build_plan had to repair travels to pinned host memory behind the batch (radad_embed_plan_flags[_poll] read it)
@@ -1759,6 +1778,61 @@ int radad_embed_plan_flags_poll(radad_embed_t h, int* flags_out, int* batches_pe
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
     return plan_flags_collect(h, false, flags_out, batches_pending_out);
+}
+
+// Diagnostic: the plan the most recent forward / stage call left in the handle, copied to the host.  Reads only: no launch, no change
+// to the plan, its cache or the report ring of radad_embed_plan_flags[_poll] (the flags here come from the plan's own n_seg_out[1]).
+int radad_embed_last_plan(radad_embed_t h, int64_t* info8, int64_t* clip_seg_host, int64_t clip_capacity, int64_t* seg_start_host,
+                          int32_t* seg_valid_host, int64_t seg_capacity, int64_t* chunk_beg_host, int32_t* chunk_fields_host,
+                          int64_t chunk_capacity, void* stream) {
+    RADAD_REQUIRE(h && info8, "radad_embed_last_plan: NULL argument");
+    RADAD_REQUIRE(clip_capacity >= 0 && seg_capacity >= 0 && chunk_capacity >= 0, "radad_embed_last_plan: negative capacity");
+    RADAD_REQUIRE((seg_start_host == nullptr) == (seg_valid_host == nullptr) && (chunk_beg_host == nullptr) == (chunk_fields_host == nullptr),
+                  "radad_embed_last_plan: seg_start / seg_valid and chunk_beg / chunk_fields come in pairs");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->plan_kind == RADAD_PLAN_NONE) { radad_set_error("radad_embed_last_plan: the handle has built no plan yet"); return RADAD_ESTATE; }
+    DeviceGuard g(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    RADAD_HIP_CHECK(hipStreamSynchronize(st));
+    int64_t n_seg = h->plan_nseg, n_chunks = 0;
+    int flags = 0;
+    if (h->plan_kind != RADAD_PLAN_SEGMENTS) {             // k_build_plan's own counts: n_seg_out[0..2]
+        int counts[3] = {0, 0, 0};
+        RADAD_HIP_CHECK(hipMemcpyAsync(counts, h->n_seg_dev.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+        RADAD_HIP_CHECK(hipStreamSynchronize(st));
+        n_seg = counts[0];
+        flags = counts[1];
+        if (h->plan_has_chunks) n_chunks = counts[2];
+        if (n_seg < 0 || n_seg > h->plan_seg_cap || n_chunks < 0 || n_chunks > h->plan_chunk_cap) {
+            radad_set_error("radad_embed_last_plan: the plan's counts (%lld segments, %lld chunks) exceed its caps (%lld, %lld)",
+                            (long long)n_seg, (long long)n_chunks, (long long)h->plan_seg_cap, (long long)h->plan_chunk_cap);
+            return RADAD_ESTATE;
+        }
+    }
+    info8[0] = h->plan_nclips; info8[1] = n_seg; info8[2] = n_chunks; info8[3] = flags;
+    info8[4] = h->plan_seg_cap; info8[5] = h->plan_chunk_cap; info8[6] = h->plan_kind;
+    info8[7] = !h->plan_has_chunks ? RADAD_PLAN_CHUNKS_NONE : h->logmel_fft ? RADAD_PLAN_CHUNKS_FFT : RADAD_PLAN_CHUNKS_GEMM;
+    RADAD_REQUIRE(!clip_seg_host || clip_capacity >= h->plan_nclips + 1, "radad_embed_last_plan: clip_seg needs room for %lld entries, has %lld",
+                  (long long)(h->plan_nclips + 1), (long long)clip_capacity);
+    RADAD_REQUIRE(!seg_start_host || seg_capacity >= n_seg, "radad_embed_last_plan: the segment arrays need room for %lld entries, have %lld",
+                  (long long)n_seg, (long long)seg_capacity);
+    RADAD_REQUIRE(!chunk_beg_host || chunk_capacity >= n_chunks, "radad_embed_last_plan: the chunk arrays need room for %lld entries, have %lld",
+                  (long long)n_chunks, (long long)chunk_capacity);
+    if (clip_seg_host)
+        RADAD_HIP_CHECK(hipMemcpyAsync(clip_seg_host, h->clip_seg.p, (size_t)(h->plan_nclips + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (seg_start_host && n_seg > 0) {
+        RADAD_HIP_CHECK(hipMemcpyAsync(seg_start_host, h->seg_start.p, (size_t)n_seg * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        RADAD_HIP_CHECK(hipMemcpyAsync(seg_valid_host, h->seg_valid.p, (size_t)n_seg * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    std::vector<ChunkRec> recs(chunk_beg_host ? (size_t)n_chunks : 0);
+    if (!recs.empty()) RADAD_HIP_CHECK(hipMemcpyAsync(recs.data(), h->chunk_rec.p, recs.size() * sizeof(ChunkRec), hipMemcpyDeviceToHost, st));
+    RADAD_HIP_CHECK(hipStreamSynchronize(st));
+    for (size_t i = 0; i < recs.size(); ++i) {
+        chunk_beg_host[i] = recs[i].beg;
+        chunk_fields_host[4 * i] = recs[i].seg0; chunk_fields_host[4 * i + 1] = recs[i].n_seg;
+        chunk_fields_host[4 * i + 2] = recs[i].cidx; chunk_fields_host[4 * i + 3] = recs[i].avail;
+    }
+    return RADAD_OK;
 }
 
 int radad_embed_clip_chunks(int n_segments, int frames_per_segment, int hop_frames, int32_t* out5) {

@@ -66,14 +66,14 @@ __device__ __forceinline__ float block_max4(float v, float* scratch) {   // LH_W
 // and log10 of it is log10 mel' - 2 log10 sd_s for the other 78 bands.  c is the mean of the segment the chunk starts in (no correction
 // at all for that owner; for its neighbours d is the difference of two overlapping segments' means -- a DC offset cancels).  What is
 // NOT shared: a segment's frames 0, 1 and T - 1, whose windows reach past the segment and see its reflection.  So the work list is
-//     per clip:    its INTERIOR clip frames j in [2, (S - 1) H + T - 2], in chunks of 96 consecutive frames (one workgroup each: the
-//                  planes hold the 15 600 samples the chunk touches), every frame written to each segment s that owns it
+//     per clip:    its INTERIOR clip frames j in [2, (S - 1) H + T - 2], in chunks of LH_CLIP_FRAMES = 104 consecutive frames (one workgroup
+//                  each: the planes hold the 16 880 samples the chunk touches), every frame written to each segment s that owns it
 //                  (2 <= j - s H <= T - 2) with that segment's scale and correction;
 //                  plus the clip's 3 S EDGE frames in the clip's last, partly filled chunk(s) (clip_chunking below): every one staged as
 //                  its own reflected 400-sample window of x - c behind the chunk's samples and written to its one owner like any other
 //                  frame (the affine argument does not care which samples a window holds).
 // k_seg_stats supplies mean and 1 / sd of every segment.  At the benchmark's shape (T = 200, H = 100, 3 segments per clip) a clip is
-// 4 chunks of 96 frames + one of 12 + 9 edge frames: 13 wave tiles instead of the 21 of three segments; segment samples are read once
+// 3 chunks of 104 frames + one of 85 + 9 edge frames (397 interior frames in all) instead of the 600 frames of three segments; segment samples are read once
 // by k_seg_stats and once here instead of twice here.
 constexpr int LH_CLIP_FRAMES = 104;              // interior frames of a full chunk: what the planes of two workgroups per CU hold
 constexpr int LH_EDGE_STRIDE = 424;              // halfs between edge windows in LDS (>= 416 = lh_pos(399) + 1; same bank residue as 168)
@@ -84,10 +84,9 @@ static_assert(2 * logmel_h_clip_lds_bytes() <= 160 * 1024, "two chunk workgroups
 static_assert(lh_plane_halfs(LH_CLIP_FRAMES) <= LH_CLIP_PLANE_HALFS && LH_EDGE_CHUNK * LH_EDGE_STRIDE <= LH_CLIP_PLANE_HALFS, "planes fit");
 
 // How a clip of S segments (T frames each, hop H frames) is cut into chunks: its ni = (S - 1) H + T - 3 interior frames in FULL chunks of
-// 96 (three full tiles, no edge frames), then ONE tail chunk with the remaining r < 96 interior frames and as many of the clip's 3 S
-// edge frames as its lanes (128) and its planes hold, then edge-only chunks of 32.  (Balanced chunks -- 4 x 99 + edges at the
-// benchmark's shape -- leave every fourth wave with 3-6 live lanes of 32: the kernel's time follows the number of wave tiles, 16 per
-// clip that way against 13 this way.)
+// LH_CLIP_FRAMES = 104 (no edge frames), then ONE tail chunk with the remaining r < 104 interior frames and as many of the clip's 3 S
+// edge frames as its lanes (128) and its planes hold, then edge-only chunks of 32.  (Balanced chunks leave a wave of every workgroup with a few live lanes
+// of 32, and the kernel's time follows the number of wave tiles: hence full chunks first, one partly filled chunk per clip.)
 struct ClipChunks { int n_full, r, e_tail, n_edge_chunks; };
 __host__ __device__ inline ClipChunks clip_chunking(int S, int T, int H) {
     ClipChunks c{0, 0, 0, 0};
@@ -368,8 +367,8 @@ __device__ __forceinline__ void logmel_h_body(const LogmelParams& p) {
     }   // !CLIP
 
     // ---- DFT + mel: wave w owns the workgroup's frame tile w; frames are local to the workgroup from here on ----------------
-    // which frame tile this wave takes: rotated by the workgroup index, so that the idle waves of partly filled workgroups (a 96-frame
-    // chunk has three tiles) are not always the same wave slot
+    // which frame tile this wave takes: rotated by the workgroup index, so that the idle waves of partly filled workgroups (a 104-frame
+    // chunk has three full tiles and one of 8 frames) are not always the same wave slot
     const int wtile = CLIP ? ((wave + (int)blockIdx.x) & (LH_WAVES - 1)) : wave;
     if (32 * wtile >= nfr) return;                     // wave-uniform (no barrier below this line)
     f32x16 zacc[NMT];

@@ -155,22 +155,32 @@ class MelProjectionFeatureExtractor:
             if n_clips < 0:
                 raise ValueError("clip_offsets must hold at least one entry")
             # device offsets cannot be checked here without a synchronisation: the plan kernel clamps them (no out-of-bounds
-            # read whatever the tensor holds) and flags what it repaired.  THIS batch is enqueued first; then earlier batches that have
-            # COMPLETED are reported without waiting (a caller may queue batches back to back) -- the exception names them as earlier
-            # ones and carries this call's output (`.result`), so a valid batch is never lost to another batch's offsets;
-            # check_device_plan() after the last batch waits for the rest
-            out = torch.empty((n_clips, self.output_dim), device=wave.device, dtype=out_dtype)
-            with torch.cuda.device(wave.device):
-                _lib.check(self._lib.radad_embed_forward_dev(self._h, wave.data_ptr(), offs.data_ptr(), n_clips, wave.numel(),
-                                                             out.data_ptr(), code, _lib.stream_ptr(wave.device)),
-                           "radad_embed_forward_dev")
+            # read whatever the tensor holds) and flags what it repaired.  Earlier batches that have COMPLETED are collected without
+            # waiting (a caller may queue batches back to back) BEFORE this one is enqueued -- polled afterwards, a small batch of
+            # this call could finish first and be reported as an earlier one, its clamped output handed back as a valid `.result`.
+            # THIS batch is enqueued whatever the poll found; then the exception names the earlier ones and carries this call's
+            # output (`.result`), so a valid batch is never lost to another batch's offsets;
+            # check_device_plan() after the last batch waits for the rest, this one included
             self._dev_batches = getattr(self, "_dev_batches", 0) + 1
+            earlier = None
             try:
                 self.check_device_plan(what=f"an earlier device-offset batch (before batch #{self._dev_batches} of this extractor, which HAS "
                                             "been enqueued: its output is this exception's .result)", wait=False)
             except ValueError as e:
-                e.result = out
+                earlier = e
+            out = torch.empty((n_clips, self.output_dim), device=wave.device, dtype=out_dtype)
+            try:
+                with torch.cuda.device(wave.device):
+                    _lib.check(self._lib.radad_embed_forward_dev(self._h, wave.data_ptr(), offs.data_ptr(), n_clips, wave.numel(),
+                                                                 out.data_ptr(), code, _lib.stream_ptr(wave.device)),
+                               "radad_embed_forward_dev")
+            except Exception as e:
+                if earlier is not None:                                    # (the report was consumed: it travels with this failure)
+                    raise e from earlier
                 raise
+            if earlier is not None:
+                earlier.result = out
+                raise earlier
             return out
         offs = np.ascontiguousarray(np.asarray(clip_offsets, np.int64))
         n_clips = len(offs) - 1
@@ -197,6 +207,30 @@ class MelProjectionFeatureExtractor:
             why = [m for b, m in ((1, "offsets outside the wave buffer"), (2, "offsets not non-decreasing"),
                                   (4, "more segments than the wave buffer can hold")) if f.value & b]
             raise ValueError(f"clip_offsets of {what} were invalid ({', '.join(why)}); its embeddings are not those of the intended clips")
+
+    def last_plan(self) -> dict:
+        """Diagnostic: the segment and chunk plan the most recent embed_clips / stage call of this extractor built, read back from the
+        handle (radad_embed_last_plan; waits for the current stream, changes nothing, does not consume check_device_plan's report).
+        Counts and caps as ints, `flags` (the repair bits of that plan), `kind` (_lib.PLAN_KINDS), `geometry` (_lib.PLAN_CHUNKS),
+        clip_seg [n_clips + 1], seg_start / seg_valid [n_seg] and the chunk records chunk_beg / chunk_seg0 / chunk_n_seg / chunk_cidx /
+        chunk_avail [n_chunks] as numpy arrays."""
+        import torch
+        info = (C.c_int64 * 8)()
+        with torch.cuda.device(self.device):
+            st = _lib.stream_ptr(self.device)
+            _lib.check(self._lib.radad_embed_last_plan(self._h, info, None, 0, None, None, 0, None, None, 0, st), "radad_embed_last_plan")
+            n_clips, n_seg, n_chunks = int(info[0]), int(info[1]), int(info[2])
+            clip_seg, seg_start, seg_valid = np.empty(n_clips + 1, np.int64), np.empty(n_seg, np.int64), np.empty(n_seg, np.int32)
+            beg, fields = np.empty(n_chunks, np.int64), np.empty((n_chunks, 4), np.int32)
+            _lib.check(self._lib.radad_embed_last_plan(self._h, info, clip_seg.ctypes.data_as(_lib.c_i64p), n_clips + 1,
+                                                       seg_start.ctypes.data_as(_lib.c_i64p), seg_valid.ctypes.data_as(_lib.c_i32p), n_seg,
+                                                       beg.ctypes.data_as(_lib.c_i64p), fields.ctypes.data_as(_lib.c_i32p), n_chunks, st),
+                       "radad_embed_last_plan")
+        return {"n_clips": n_clips, "n_seg": n_seg, "n_chunks": n_chunks, "flags": int(info[3]), "seg_cap": int(info[4]),
+                "chunk_cap": int(info[5]), "kind": _lib.PLAN_KINDS[int(info[6])], "geometry": _lib.PLAN_CHUNKS[int(info[7])],
+                "clip_seg": clip_seg, "seg_start": seg_start, "seg_valid": seg_valid, "chunk_beg": beg,
+                "chunk_seg0": fields[:, 0].copy(), "chunk_n_seg": fields[:, 1].copy(), "chunk_cidx": fields[:, 2].copy(),
+                "chunk_avail": fields[:, 3].copy()}
 
     def last_logmel_kind(self) -> str:
         """"per_segment" (k_logmel_h: one transform per segment and frame), "clip_frames" (k_logmel_h_clip: the frames overlapping
