@@ -333,6 +333,40 @@ int radad_excl_merge_certify(int metric, const double* in_key_dev, const int64_t
                              const int64_t* frontier_idx_dev, int n_parts, int64_t nq, int k, float* out_dist_dev,
                              int64_t* out_idx_dev, double* out_key_dev, int* unproved_out_dev, int device, void* stream);
 
+/* The exclusion-aware search with one exclusion set PER QUERY (leave-one-out: a query excludes its own file, or its own speaker's
+ * files, and nothing else).  The reference excludes the union of the batch's basenames (pipeline.py:463,498), so what a clip retrieves
+ * there depends on which clips share its batch; here the result of a query is a function of the query alone.  Opt-in: the batch-wide
+ * calls above stay as they are.
+ * Contract: that of radad_knn_search_excl with one change -- row r is admissible for query j iff row_tags[r] is not among the first
+ * cnt_j entries of q_tags[j, :], cnt_j = q_tag_counts[j] clamped on the device to [0, m] (NULL = m for every query).  The tags of a
+ * query may come in any order and repeat.  Order (float64 key, lower id); out_dist the key rounded once; padding -1 / NaN / NaN;
+ * stream-ordered and serialised like every search.  Fast pass, certificate and exact pass as there: the certificate counts the hits
+ * the QUERY admits; the exact pass streams the store once per group of <= 8 listed queries, reads one row tag per row and compares it
+ * with the tags of the group's queries held in registers, one ballot per query (no bitmap: one per listed query would cost ntotal / 8
+ * bytes each); a row none of the group admits is not loaded (its time per listed query has not been measured either,
+ * profiles/README.md).  If no tag is carried by more than c rows, k_fetch >= k + m * c proves
+ * every query in the fast pass.
+ * 0 <= m <= RADAD_EXCL_PQ_MAX_TAGS: one wave compares a row's tag with a query's set in one ballot (and an all-gather carries the sets
+ * at that fixed width).  m == 0: nothing is excluded, the result is the certified search at k with this family's padding.  A larger
+ * m, or m > 0 with NULL q_tags_dev or row_tags_dev, is RADAD_EINVAL; the other argument rules, RADAD_ESTATE on an empty store and
+ * RADAD_EINVAL on a handle with a begun search as radad_knn_search_excl.  radad_knn_last_excl covers it.
+ * radad_knn_search_excl_pq_begin is the first half over a ROW SHARD, as radad_knn_search_excl_begin (nq >= 1, all four outputs
+ * required).  Its second half is radad_knn_search_excl_finish: the begun search remembers the admission rule it was begun with.
+ * radad_excl_merge_certify and radad_knn_search_abort cover it unchanged; the queries, the row tags, the query tags and the counts
+ * must stay alive until _finish.  _pq_begin + _finish with the shard's own flags is radad_knn_search_excl_pq, bit for bit.
+ * Not offered: a batch-wide set combined with per-query sets in one call; the IVF index (its admission bitmap is per call and sits
+ * inside the list scans); the cross-shard lower bound. */
+#define RADAD_EXCL_PQ_MAX_TAGS 64
+int radad_knn_search_excl_pq(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, int k_fetch,
+                             const int64_t* row_tags_dev /*[ntotal], by id - id_base*/,
+                             const int64_t* q_tags_dev /*[nq, m] row-major; any order, duplicates allowed*/, int m,
+                             const int32_t* q_tag_counts_dev /*[nq] or NULL = m for every query*/, float* out_dist_dev /*[nq,k]*/,
+                             int64_t* out_idx_dev /*[nq,k]*/, double* out_key_dev /*[nq,k] or NULL*/, void* stream);
+int radad_knn_search_excl_pq_begin(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, int k_fetch,
+                                   const int64_t* row_tags_dev, const int64_t* q_tags_dev, int m, const int32_t* q_tag_counts_dev,
+                                   double* out_key_dev /*[nq,k]*/, int64_t* out_idx_dev /*[nq,k]*/, double* frontier_key_dev /*[nq]*/,
+                                   int64_t* frontier_idx_dev /*[nq]*/, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Inverted-file flat index: faiss.IndexIVFFlat(IndexFlatL2 quantiser, d, nlist, METRIC_L2), the reference's optional
  * `vector_db_index_type == "IVF"` (vector_database.py:65-70 create with nlist = max(64, ivf_nlist), :124-128 train on the

@@ -1904,6 +1904,12 @@ struct ExactParams {
     // the row-filtered instantiation only (k_exact_scan_excl, radad_knn_search_excl): bit (row & 63) of admit[row >> 6] set = the row
     // takes part; unfilled result slots are -1 / NaN there (the padding of radad_filter_topk) instead of -1 / +-inf
     const unsigned long long* admit = nullptr;
+    // the per-query instantiation only (k_exact_scan_excl_pq, radad_knn_search_excl_pq): no bitmap; row r takes part for query j iff
+    // row_tags[r] is not among the first clamp(q_cnt[j], 0, m) entries of q_tags[j, :] (q_cnt NULL = m for every query); 1 <= m <= 64
+    const int64_t* row_tags = nullptr;
+    const int64_t* q_tags = nullptr;
+    const int* q_cnt = nullptr;
+    int m = 0;
 };
 static_assert(std::is_trivially_copyable_v<ExactParams>, "kernel argument");
 
@@ -1918,9 +1924,13 @@ template <bool FILTERED>
 __device__ __forceinline__ void exact_merge_slot(const ExactParams& p, int slot, int lane);
 
 // FILTERED is a compile-time parameter: the unfiltered instantiation (k_exact_scan) is the code it was before the filter existed;
-// k_exact_scan_excl scans the rows a bitmap admits (radad_knn_search_excl): the float64 brute force among the rows not excluded
-template <bool FILTERED>
+// k_exact_scan_excl scans the rows a bitmap admits (radad_knn_search_excl): the float64 brute force among the rows not excluded.
+// PER_QUERY (with FILTERED, k_exact_scan_excl_pq, radad_knn_search_excl_pq): every query of a group has an admissible set of its
+// own, <= 64 excluded tags each.  Lane l holds tag l of each of the group's queries; per row one load of the row's tag and one
+// ballot per query say which of the group's lists the row may enter.  A row nobody of the group admits is not loaded.
+template <bool FILTERED, bool PER_QUERY = false>
 __global__ __launch_bounds__(KX_THREADS) void k_exact_scan_any(ExactParams p) {
+    static_assert(FILTERED || !PER_QUERY, "the per-query form is a filtered form");
     const int count = min(*p.count - p.slot0, p.nslots);       // this launch's queries
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && p.host_stats) {
         *reinterpret_cast<volatile int*>(&p.host_stats[6]) = 0;          // the slot is being rewritten: no report until the new stamp is there
@@ -1953,14 +1963,36 @@ __global__ __launch_bounds__(KX_THREADS) void k_exact_scan_any(ExactParams p) {
         double* wKey = sKey + (size_t)wave * G * p.k;
         int* wId = sId + (size_t)wave * G * p.k;
         for (int i = lane; i < G * p.k; i += 64) { wKey[i] = -INFINITY; wId[i] = IDX_SENTINEL; }
+        int64_t qt[8];                                    // (PER_QUERY) tag `lane` of the group's query j ...
+        bool qv[8];                                       // ... and whether the query's clamped count reaches it
+        if constexpr (PER_QUERY) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                qt[j] = 0; qv[j] = false;
+                if (j < ng) {
+                    const int64_t qq = p.sel[p.slot0 + g * G + j];
+                    const int cnt = min(max(p.q_cnt ? p.q_cnt[qq] : p.m, 0), p.m);
+                    qv[j] = lane < cnt;
+                    if (qv[j]) qt[j] = p.q_tags[qq * p.m + lane];
+                }
+            }
+        }
         __syncthreads();
         int64_t adm_w = -1;                               // (FILTERED) the bitmap word in hand: one load per 64 rows of the slice
         unsigned long long adm = 0ull;
         for (int64_t row = r_begin + wave; row < r_end; row += KX_WAVES) {
-            if (FILTERED) {
+            if (FILTERED && !PER_QUERY) {
                 // wave-uniform, before any load of the row: an excluded row costs this bit and nothing else
                 if ((row >> 6) != adm_w) { adm_w = row >> 6; adm = p.admit[adm_w]; }
                 if (!__builtin_amdgcn_readfirstlane((int)((adm >> (row & 63)) & 1ull))) continue;
+            }
+            unsigned adm_q = 0u;                          // (PER_QUERY) bit j: query j of the group admits the row (wave-uniform)
+            if constexpr (PER_QUERY) {
+                const int64_t t = p.row_tags[row];        // one address for the wave
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (j < ng && __ballot(qv[j] && qt[j] == t) == 0ull) adm_q |= 1u << j;
+                if (adm_q == 0u) continue;                // before any load of the row
             }
             double part[8];
 #pragma unroll
@@ -1987,7 +2019,7 @@ __global__ __launch_bounds__(KX_THREADS) void k_exact_scan_any(ExactParams p) {
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                if (j < ng) {
+                if (j < ng && (!PER_QUERY || ((adm_q >> j) & 1u))) {
                     double v = part[j];
 #pragma unroll
                     for (int ofs = 32; ofs > 0; ofs >>= 1) v += __shfl_xor(v, ofs, 64);
@@ -2062,6 +2094,7 @@ __global__ __launch_bounds__(KX_THREADS) void k_exact_scan_any(ExactParams p) {
 
 constexpr auto k_exact_scan = k_exact_scan_any<false>;
 constexpr auto k_exact_scan_excl = k_exact_scan_any<true>;
+constexpr auto k_exact_scan_excl_pq = k_exact_scan_any<true, true>;
 
 // one wave: merge the KX_SLICES partial lists of this launch's rejected-query slot `slot`, overwrite the query's output rows
 template <bool FILTERED>
@@ -2290,6 +2323,11 @@ struct ExclCompactParams {
     double* fr_key = nullptr;           // FRONTIER: [nq] frontier keys ...
     int64_t* fr_idx = nullptr;          // ... ids, -1 = nothing of the shard is unseen ...
     int* own = nullptr;                 // ... and [nq] 1 = the shard's list is short although rows are unseen
+    // PER_QUERY (radad_knn_search_excl_pq / _pq_begin) instead of excl / n_excl: query q excludes the first clamp(q_cnt[q], 0, m)
+    // tags of q_tags[q, :] (q_cnt NULL = m for every query); 0 <= m <= 64
+    const int64_t* q_tags = nullptr;
+    const int* q_cnt = nullptr;
+    int m = 0;
 };
 static_assert(std::is_trivially_copyable_v<ExclCompactParams>, "kernel argument");
 
@@ -2305,11 +2343,20 @@ static_assert(std::is_trivially_copyable_v<ExclCompactParams>, "kernel argument"
 // (admissible or not: the list is a prefix of the shard's ranking); else, when the list is all the shard has, id -1 / key NaN:
 // nothing is unseen.  own[q] = 1 for the query the other form would have listed: the only kind whose list the exact pass can
 // still change.
-template <bool FRONTIER>
+// PER_QUERY: the same with the admission test of radad_knn_search_excl_pq -- lane l holds tag l of the wave's query; a hit's tag is
+// compared with the query's tags one lane at a time (<= 64 register reads per strip, no memory).  A compile-time parameter: the
+// batch-wide instantiations are the code they were.
+template <bool FRONTIER, bool PER_QUERY = false>
 __global__ __launch_bounds__(256) void k_excl_compact(ExclCompactParams p) {
     const int lane = threadIdx.x & 63;
     const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= p.nq) return;                                      // (wave-uniform)
+    int64_t my_tag = 0;                                         // (PER_QUERY) tag `lane` of this query, lanes [0, cnt)
+    int cnt = 0;
+    if constexpr (PER_QUERY) {
+        cnt = p.m > 0 ? min(max(p.q_cnt ? p.q_cnt[q] : p.m, 0), p.m) : 0;
+        if (lane < cnt) my_tag = p.q_tags[q * p.m + lane];
+    }
     const int k_in = p.k_in, k_keep = p.k_keep;
     const double nan64 = (double)__int_as_float(0x7fc00000);
     int kept = 0;
@@ -2322,7 +2369,18 @@ __global__ __launch_bounds__(256) void k_excl_compact(ExclCompactParams p) {
             id = p.in_idx[q * k_in + j];
             const int64_t r = id - p.id_base;
             keep = id >= 0 && r >= 0 && r < p.ntotal;
-            if (keep && p.n_excl > 0) keep = !excl_has(p.excl, p.n_excl, p.tags[r]);
+            if constexpr (!PER_QUERY) {
+                if (keep && p.n_excl > 0) keep = !excl_has(p.excl, p.n_excl, p.tags[r]);
+            }
+        }
+        if constexpr (PER_QUERY) {
+            if (cnt > 0) {                                      // (wave-uniform; every lane takes part in the shuffles)
+                const int64_t t = keep ? p.tags[id - p.id_base] : 0;
+                for (int e = 0; e < cnt; ++e) {
+                    const int64_t o = __shfl(my_tag, e, 64);    // (outside the condition: all lanes shuffle)
+                    keep = keep && o != t;
+                }
+            }
         }
         unfilled |= __ballot(j < k_in && id < 0) != 0ull;
         const unsigned long long m = __ballot(keep);
@@ -2523,13 +2581,25 @@ struct SearchCtx {
     SearchLayout ws;
 };
 
-// an exclusion-aware search begun on a row shard (radad_knn_search_excl_begin) without its _finish yet
+// the admission rule of an exclusion-aware search: one ascending set for the batch (radad_knn_search_excl), or <= 64 tags per query
+// (radad_knn_search_excl_pq).  n_excl is the size of the set, or m: 0 = nothing is excluded, in either mode.
+struct ExclRule {
+    const int64_t* tags = nullptr;      // [ntotal] row tags
+    const int64_t* excl = nullptr;      // batch-wide: [n_excl] ascending
+    int64_t n_excl = 0;
+    bool per_query = false;
+    const int64_t* q_tags = nullptr;    // per query: [nq, m]
+    const int* q_cnt = nullptr;         // [nq] or NULL = m for every query
+    int m() const { return (int)n_excl; }
+};
+
+// an exclusion-aware search begun on a row shard (radad_knn_search_excl_begin / _pq_begin) without its _finish yet
 struct ExclCtx {
     bool valid = false;
-    int64_t nq = 0, n_excl = 0;
+    int64_t nq = 0;
     int k = 0, l2 = 0;
     const float* q_use = nullptr;
-    const int64_t *tags = nullptr, *excl = nullptr;
+    ExclRule rule;                      // (which admission rule it was begun with: _finish runs the exact pass of that rule)
     ExclLayout L;
 };
 
@@ -3590,15 +3660,17 @@ static int knn_excl_reserve(radad_knn_t h, size_t bytes) {
 
 // the row-filtered exact pass for the queries in sel[0, *count): bitmap (built only when *count > 0), then k_exact_scan_excl sized and
 // driven by the device-side count like the exact pass of any search; it overwrites those queries' rows of out_*
-static int knn_excl_exact_pass(radad_knn_t h, const ExclLayout& L, int64_t nq, int k, int l2, const float* q_use, const int64_t* tags,
-                               const int64_t* excl, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
-                               hipStream_t st) {
+// (per-query rule: no bitmap; k_exact_scan_excl_pq compares the row's tag with the group's query tags)
+static int knn_excl_exact_pass(radad_knn_t h, const ExclLayout& L, int64_t nq, int k, int l2, const float* q_use, const ExclRule& r,
+                               float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, hipStream_t st) {
     auto at = [&](size_t o) { return (char*)h->excl_ws + o; };
     int* count = (int*)at(L.count);
-    unsigned long long* admit = (unsigned long long*)at(L.admit);
-    hipLaunchKernelGGL(k_admit_bitmap<false>, dim3((unsigned)ceil_div64(L.n_words * 64, 256)), dim3(256), 0, st, tags, (const int64_t*)nullptr,
-                       h->ntotal, excl, n_excl, (const int*)count, admit, L.n_words);
-    RADAD_HIP_CHECK(hipGetLastError());
+    unsigned long long* admit = r.per_query ? nullptr : (unsigned long long*)at(L.admit);
+    if (!r.per_query) {
+        hipLaunchKernelGGL(k_admit_bitmap<false>, dim3((unsigned)ceil_div64(L.n_words * 64, 256)), dim3(256), 0, st, r.tags,
+                           (const int64_t*)nullptr, h->ntotal, r.excl, r.n_excl, (const int*)count, admit, L.n_words);
+        RADAD_HIP_CHECK(hipGetLastError());
+    }
     ExactParams x;
     x.db = h->rows; x.db_f16 = h->f16; x.q = q_use; x.sel = (int*)at(L.sel); x.count = count;
     x.n = h->ntotal; x.dim = h->dim; x.k = k; x.l2 = l2; x.group = L.xgroup;
@@ -3608,14 +3680,16 @@ static int knn_excl_exact_pass(radad_knn_t h, const ExclLayout& L, int64_t nq, i
     x.host_stats = nullptr;                                    // the handle's certificate report and its tuning belong to the fast pass
     x.arrive = h->xarrive;                                     // (the fast pass made room for nq groups; zero between launches)
     x.admit = admit;
+    if (r.per_query) { x.row_tags = r.tags; x.q_tags = r.q_tags; x.q_cnt = r.q_cnt; x.m = r.m(); }
+    const auto kern = r.per_query ? k_exact_scan_excl_pq : k_exact_scan_excl;
     const size_t xlds = (size_t)L.xgroup * h->dim * 4 + (size_t)KX_WAVES * L.xgroup * k * 12 + 16;
     RADAD_REQUIRE(xlds <= KX_LDS_MAX && h->xarrive && nq <= h->xarrive_cap, "radad_knn_search_excl: dim %d x k %d too large for the exact kernel", h->dim, k);
-    RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_exact_scan_excl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
+    RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
     const unsigned gy = k <= KNN_F16_MAX_K ? KX_GROUPS_Y : 8 * KX_GROUPS_Y;
     x.nslots = (int)L.xslots;
     for (int64_t s0 = 0; s0 < nq; s0 += x.nslots) {            // (launches past the device-side count leave at once)
         x.slot0 = (int)s0;
-        hipLaunchKernelGGL(k_exact_scan_excl, dim3(KX_SLICES, gy), dim3(KX_THREADS), xlds, st, x);
+        hipLaunchKernelGGL(kern, dim3(KX_SLICES, gy), dim3(KX_THREADS), xlds, st, x);
     }
     RADAD_HIP_CHECK(hipGetLastError());
     return RADAD_OK;
@@ -3623,10 +3697,10 @@ static int knn_excl_exact_pass(radad_knn_t h, const ExclLayout& L, int64_t nq, i
 
 // the part the whole-store call and the shard's first half share: layout -> workspace -> the fast pass at kf into fd / fi / fk ->
 // compaction into out_* (begun: into the workspace's bd / bi / bk, with frontier and own flags instead of the listing)
-static int knn_excl_fast_pass(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* tags,
-                              const int64_t* excl, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
+static int knn_excl_fast_pass(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int k_fetch, const ExclRule& r,
+                              float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
                               double* fr_key_dev, int64_t* fr_idx_dev, hipStream_t st, bool begun, SearchCtx* c, ExclLayout* Lout) {
-    const ExclLayout L = knn_excl_layout(knn_store_facts(h), nq, k, k_fetch, n_excl, begun);
+    const ExclLayout L = knn_excl_layout(knn_store_facts(h), nq, k, k_fetch, r.n_excl, begun, r.per_query);
     int rc = knn_excl_reserve(h, L.bytes);
     if (rc) return rc;
     auto at = [&](size_t o) { return (char*)h->excl_ws + o; };
@@ -3636,14 +3710,19 @@ static int knn_excl_fast_pass(radad_knn_t h, const void* q_in, int q_dtype, int6
     ExclCompactParams p;
     p.in_dist = (const float*)at(L.fd); p.in_idx = (const int64_t*)at(L.fi); p.in_key = (const double*)at(L.fk);
     p.nq = nq; p.k_in = L.kf; p.k_keep = k; p.whole = L.whole;
-    p.tags = tags; p.ntotal = h->ntotal; p.id_base = h->id_base; p.excl = excl; p.n_excl = n_excl;
+    p.tags = r.tags; p.ntotal = h->ntotal; p.id_base = h->id_base;
+    if (r.per_query) { p.q_tags = r.q_tags; p.q_cnt = r.q_cnt; p.m = r.m(); }
+    else { p.excl = r.excl; p.n_excl = r.n_excl; }
     p.out_dist = begun ? (float*)at(L.bd) : out_dist_dev;
     p.out_idx = begun ? (int64_t*)at(L.bi) : out_idx_dev;
     p.out_key = begun ? (double*)at(L.bk) : out_key_dev;
     p.count = (int*)at(L.count); p.sel = (int*)at(L.sel);
     p.fr_key = fr_key_dev; p.fr_idx = fr_idx_dev; p.own = begun ? (int*)at(L.own) : nullptr;
     const dim3 grid((unsigned)ceil_div64(nq, 4));
-    if (begun) hipLaunchKernelGGL(k_excl_compact<true>, grid, dim3(256), 0, st, p);
+    if (r.per_query) {
+        if (begun) hipLaunchKernelGGL((k_excl_compact<true, true>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((k_excl_compact<false, true>), grid, dim3(256), 0, st, p);
+    } else if (begun) hipLaunchKernelGGL(k_excl_compact<true>, grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL(k_excl_compact<false>, grid, dim3(256), 0, st, p);
     RADAD_HIP_CHECK(hipGetLastError());
     h->excl_o_count = L.count;
@@ -3652,25 +3731,24 @@ static int knn_excl_fast_pass(radad_knn_t h, const void* q_in, int q_dtype, int6
     return RADAD_OK;
 }
 
-static int knn_search_excl_locked(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* tags,
-                                  const int64_t* excl, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
-                                  hipStream_t st) {
+static int knn_search_excl_locked(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int k_fetch, const ExclRule& r,
+                                  float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, hipStream_t st) {
     SearchCtx c;
     ExclLayout L;
-    int rc = knn_excl_fast_pass(h, q_in, q_dtype, nq, k, k_fetch, tags, excl, n_excl, out_dist_dev, out_idx_dev, out_key_dev, nullptr,
+    int rc = knn_excl_fast_pass(h, q_in, q_dtype, nq, k, k_fetch, r, out_dist_dev, out_idx_dev, out_key_dev, nullptr,
                                 nullptr, st, false, &c, &L);
     if (rc) return rc;
-    if (n_excl == 0) return RADAD_OK;                          // nothing excluded: every query is proved by its own list
-    return knn_excl_exact_pass(h, L, nq, k, c.l2, c.q_use, tags, excl, n_excl, out_dist_dev, out_idx_dev, out_key_dev, st);
+    if (r.n_excl == 0) return RADAD_OK;                        // nothing excluded: every query is proved by its own list
+    return knn_excl_exact_pass(h, L, nq, k, c.l2, c.q_use, r, out_dist_dev, out_idx_dev, out_key_dev, st);
 }
 
 // first half over a row shard: the fast pass with frontier into the workspace; the caller gets copies
-static int knn_search_excl_begin_locked(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* tags,
-                                        const int64_t* excl, int64_t n_excl, double* out_key_dev, int64_t* out_idx_dev,
+static int knn_search_excl_begin_locked(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int k_fetch, const ExclRule& r,
+                                        double* out_key_dev, int64_t* out_idx_dev,
                                         double* fr_key_dev, int64_t* fr_idx_dev, hipStream_t st) {
     SearchCtx c;
     ExclLayout L;
-    int rc = knn_excl_fast_pass(h, q_in, q_dtype, nq, k, k_fetch, tags, excl, n_excl, nullptr, nullptr, nullptr, fr_key_dev, fr_idx_dev,
+    int rc = knn_excl_fast_pass(h, q_in, q_dtype, nq, k, k_fetch, r, nullptr, nullptr, nullptr, fr_key_dev, fr_idx_dev,
                                 st, true, &c, &L);
     if (rc) return rc;
     auto at = [&](size_t o) { return (char*)h->excl_ws + o; };
@@ -3678,7 +3756,7 @@ static int knn_search_excl_begin_locked(radad_knn_t h, const void* q_in, int q_d
     RADAD_HIP_CHECK(hipMemcpyAsync(out_idx_dev, at(L.bi), (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     RADAD_HIP_CHECK(hipEventRecord(h->ev_begun, st));
     ExclCtx& e = h->pending_excl;
-    e.valid = true; e.nq = nq; e.n_excl = n_excl; e.k = k; e.l2 = c.l2; e.q_use = c.q_use; e.tags = tags; e.excl = excl; e.L = L;
+    e.valid = true; e.nq = nq; e.k = k; e.l2 = c.l2; e.q_use = c.q_use; e.rule = r; e.L = L;
     return RADAD_OK;
 }
 
@@ -3692,6 +3770,22 @@ static int knn_excl_check_args(const char* fn, radad_knn_t h, int q_dtype, int64
     RADAD_REQUIRE(nq >= nq_min && nq < (1ll << 31) - KT_N, "%s: bad nq", fn);
     RADAD_REQUIRE(n_excl >= 0 && (n_excl == 0 || (excl_sorted_dev && row_tags_dev)),
                   "%s: %lld excluded tags need the exclusion set and the row tags", fn, (long long)n_excl);
+    return RADAD_OK;
+}
+
+static ExclRule knn_excl_rule_batch(const int64_t* row_tags_dev, const int64_t* excl_sorted_dev, int64_t n_excl) {
+    ExclRule r;
+    r.tags = row_tags_dev; r.excl = excl_sorted_dev; r.n_excl = n_excl;
+    return r;
+}
+
+// the argument checks of the per-query forms beyond knn_excl_check_args (called with n_excl = 0), and their rule
+static int knn_excl_pq_rule(const char* fn, const int64_t* row_tags_dev, const int64_t* q_tags_dev, int m, const int32_t* q_tag_counts_dev,
+                            ExclRule* r) {
+    RADAD_REQUIRE(m >= 0 && m <= RADAD_EXCL_PQ_MAX_TAGS, "%s: m=%d tags per query outside [0,%d] (one wave compares them: RADAD_EXCL_PQ_MAX_TAGS)",
+                  fn, m, RADAD_EXCL_PQ_MAX_TAGS);
+    RADAD_REQUIRE(m == 0 || (q_tags_dev && row_tags_dev), "%s: %d tags per query need the query tags and the row tags", fn, m);
+    r->tags = row_tags_dev; r->n_excl = m; r->per_query = true; r->q_tags = q_tags_dev; r->q_cnt = m > 0 ? q_tag_counts_dev : nullptr;
     return RADAD_OK;
 }
 
@@ -3746,8 +3840,25 @@ int radad_knn_search_excl(radad_knn_t h, const void* q_dev, int q_dtype, int64_t
     DeviceGuard g(h->device);
     RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_search_excl: a radad_knn_search_begin on this handle has not been finished");
     if (h->ntotal == 0) { radad_set_error("radad_knn_search_excl: the store is empty"); return RADAD_ESTATE; }
-    return knn_search_excl_locked(h, q_dev, q_dtype, nq, k, k_fetch, row_tags_dev, excl_sorted_dev, n_excl, out_dist_dev, out_idx_dev,
-                                  out_key_dev, (hipStream_t)stream);
+    return knn_search_excl_locked(h, q_dev, q_dtype, nq, k, k_fetch, knn_excl_rule_batch(row_tags_dev, excl_sorted_dev, n_excl), out_dist_dev,
+                                  out_idx_dev, out_key_dev, (hipStream_t)stream);
+}
+
+int radad_knn_search_excl_pq(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* row_tags_dev,
+                             const int64_t* q_tags_dev, int m, const int32_t* q_tag_counts_dev, float* out_dist_dev, int64_t* out_idx_dev,
+                             double* out_key_dev, void* stream) {
+    int bad = knn_excl_check_args("radad_knn_search_excl_pq", h, q_dtype, nq, 0, k, k_fetch, nullptr, nullptr, 0);
+    if (bad) return bad;
+    ExclRule r;
+    bad = knn_excl_pq_rule("radad_knn_search_excl_pq", row_tags_dev, q_tags_dev, m, q_tag_counts_dev, &r);
+    if (bad) return bad;
+    if (nq == 0) return RADAD_OK;
+    RADAD_REQUIRE(q_dev && out_dist_dev && out_idx_dev, "radad_knn_search_excl_pq: NULL buffer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_search_excl_pq: a radad_knn_search_begin on this handle has not been finished");
+    if (h->ntotal == 0) { radad_set_error("radad_knn_search_excl_pq: the store is empty"); return RADAD_ESTATE; }
+    return knn_search_excl_locked(h, q_dev, q_dtype, nq, k, k_fetch, r, out_dist_dev, out_idx_dev, out_key_dev, (hipStream_t)stream);
 }
 
 int radad_knn_last_excl(radad_knn_t h, int64_t* n_queries, int* n_exact) {
@@ -3772,8 +3883,25 @@ int radad_knn_search_excl_begin(radad_knn_t h, const void* q_dev, int q_dtype, i
     DeviceGuard g(h->device);
     RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_search_excl_begin: the previous begin on this handle has not been finished");
     if (h->ntotal == 0) { radad_set_error("radad_knn_search_excl_begin: the store is empty"); return RADAD_ESTATE; }
-    return knn_search_excl_begin_locked(h, q_dev, q_dtype, nq, k, k_fetch, row_tags_dev, excl_sorted_dev, n_excl, out_key_dev, out_idx_dev,
-                                        frontier_key_dev, frontier_idx_dev, (hipStream_t)stream);
+    return knn_search_excl_begin_locked(h, q_dev, q_dtype, nq, k, k_fetch, knn_excl_rule_batch(row_tags_dev, excl_sorted_dev, n_excl),
+                                        out_key_dev, out_idx_dev, frontier_key_dev, frontier_idx_dev, (hipStream_t)stream);
+}
+
+int radad_knn_search_excl_pq_begin(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* row_tags_dev,
+                                   const int64_t* q_tags_dev, int m, const int32_t* q_tag_counts_dev, double* out_key_dev,
+                                   int64_t* out_idx_dev, double* frontier_key_dev, int64_t* frontier_idx_dev, void* stream) {
+    int bad = knn_excl_check_args("radad_knn_search_excl_pq_begin", h, q_dtype, nq, 1, k, k_fetch, nullptr, nullptr, 0);
+    if (bad) return bad;
+    ExclRule r;
+    bad = knn_excl_pq_rule("radad_knn_search_excl_pq_begin", row_tags_dev, q_tags_dev, m, q_tag_counts_dev, &r);
+    if (bad) return bad;
+    RADAD_REQUIRE(q_dev && out_key_dev && out_idx_dev && frontier_key_dev && frontier_idx_dev, "radad_knn_search_excl_pq_begin: NULL buffer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_search_excl_pq_begin: the previous begin on this handle has not been finished");
+    if (h->ntotal == 0) { radad_set_error("radad_knn_search_excl_pq_begin: the store is empty"); return RADAD_ESTATE; }
+    return knn_search_excl_begin_locked(h, q_dev, q_dtype, nq, k, k_fetch, r, out_key_dev, out_idx_dev, frontier_key_dev, frontier_idx_dev,
+                                        (hipStream_t)stream);
 }
 
 int radad_knn_search_excl_finish(radad_knn_t h, const int* unproved_dev, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
@@ -3794,11 +3922,11 @@ int radad_knn_search_excl_finish(radad_knn_t h, const int* unproved_dev, float* 
     RADAD_HIP_CHECK(hipMemcpyAsync(out_dist_dev, at(e.L.bd), n * sizeof(float), hipMemcpyDeviceToDevice, st));
     RADAD_HIP_CHECK(hipMemcpyAsync(out_idx_dev, at(e.L.bi), n * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     if (out_key_dev) RADAD_HIP_CHECK(hipMemcpyAsync(out_key_dev, at(e.L.bk), n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    if (!unproved_dev || e.n_excl == 0) return RADAD_OK;           // nothing excluded: every shard list is the shard's exact top k
+    if (!unproved_dev || e.rule.n_excl == 0) return RADAD_OK;           // nothing excluded: every shard list is the shard's exact top k
     hipLaunchKernelGGL(k_excl_flags_to_list, dim3((unsigned)ceil_div64(e.nq, 256)), dim3(256), 0, st, unproved_dev, (const int*)at(e.L.own),
                        e.nq, (int*)at(e.L.count), (int*)at(e.L.sel));
     RADAD_HIP_CHECK(hipGetLastError());
-    return knn_excl_exact_pass(h, e.L, e.nq, e.k, e.l2, e.q_use, e.tags, e.excl, e.n_excl, out_dist_dev, out_idx_dev, out_key_dev, st);
+    return knn_excl_exact_pass(h, e.L, e.nq, e.k, e.l2, e.q_use, e.rule, out_dist_dev, out_idx_dev, out_key_dev, st);
 }
 
 int radad_excl_merge_certify(int metric, const double* in_key_dev, const int64_t* in_idx_dev, const double* frontier_key_dev,

@@ -377,7 +377,8 @@ struct ExclLayout {
     int64_t xslots = 0, n_words = 0;
 };
 
-static ExclLayout knn_excl_layout(const StoreFacts& s, int64_t nq, int k, int k_fetch, int64_t n_excl, bool begun) {
+// per_query (radad_knn_search_excl_pq): n_excl is the tags per query, m; the exact pass of that rule reads no bitmap
+static ExclLayout knn_excl_layout(const StoreFacts& s, int64_t nq, int k, int k_fetch, int64_t n_excl, bool begun, bool per_query = false) {
     ExclLayout L;
     L.kf = (int)std::min<int64_t>(k_fetch, s.ntotal);
     L.whole = k_fetch > s.ntotal ? 1 : 0;          // the list was cut to the store: it is all there is (an unfilled slot, had it not been cut)
@@ -389,7 +390,7 @@ static ExclLayout knn_excl_layout(const StoreFacts& s, int64_t nq, int k, int k_
     L.fd = take((size_t)nq * L.kf * sizeof(float)); L.fi = take((size_t)nq * L.kf * sizeof(int64_t));
     L.fk = take((size_t)nq * L.kf * sizeof(double));
     L.count = take(256); L.sel = take((size_t)nq * sizeof(int));
-    L.admit = take(n_excl > 0 ? (size_t)L.n_words * sizeof(unsigned long long) : 0);
+    L.admit = take(n_excl > 0 && !per_query ? (size_t)L.n_words * sizeof(unsigned long long) : 0);
     L.xk = take(n_excl > 0 ? (size_t)L.xslots * KX_SLICES * k * sizeof(double) : 0);
     L.xi = take(n_excl > 0 ? (size_t)L.xslots * KX_SLICES * k * sizeof(int) : 0);
     if (begun) {

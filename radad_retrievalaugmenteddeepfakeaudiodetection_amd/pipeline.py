@@ -124,6 +124,19 @@ class HotPathPipeline:
         # front of them (VectorDatabase.search_excluding), instead of the reference's "search K + 10, drop, pad" below
         from .vector_database import HipFlatIndex, HipIVFFlatIndex, path_tag
         exact_excl = bool(getattr(self.config, "exact_exclusion", False)) and exclude_self
+        # config.exclusion_scope "query" (opt-in): clip i excludes its OWN basename and nothing else (VectorDatabase.
+        # search_excluding_per_query), so what a clip retrieves does not depend on its batch; "batch" is the reference's union (:463)
+        scope = getattr(self.config, "exclusion_scope", "batch")
+        if scope not in ("batch", "query"):
+            raise ValueError(f"config.exclusion_scope must be 'batch' or 'query', got {scope!r}")
+        per_query = scope == "query" and exclude_self
+        if per_query and not exact_excl:
+            raise ValueError("config.exclusion_scope 'query' needs config.exact_exclusion: the over-fetch-and-drop path excludes the batch's union")
+        if per_query and query_paths is None:
+            raise ValueError("config.exclusion_scope 'query' needs query_paths: a query excludes its own basename")
+        if per_query and not isinstance(index, HipFlatIndex):
+            raise ValueError("config.exclusion_scope 'query': per-query exclusion sets are flat and single-handle only "
+                             "(vector_db_index_type 'L2' or 'IP')")
         if exact_excl and not isinstance(index, HipFlatIndex):
             raise ValueError("config.exact_exclusion: exclusion-aware search is flat and single-handle only (vector_db_index_type 'L2' or 'IP')")
         # config.ivf_exact_exclusion (opt-in): the same for an IVF store, among the rows of the probed lists
@@ -146,6 +159,12 @@ class HotPathPipeline:
         if exact_excl or ivf_excl:
             if ivf_excl:
                 dist_t, chosen_t = self.vector_db.search_probed_excluding(q, K, excl)
+            elif per_query:
+                if len(query_paths) != B:
+                    raise ValueError(f"config.exclusion_scope 'query' needs one path per query ({B}), got {len(query_paths)}")
+                own = torch.tensor([[path_tag(os.path.basename(p))] for p in query_paths], dtype=torch.int64, device=self.device)
+                k_fetch = getattr(self.config, "exclusion_k_fetch", K + 10)
+                dist_t, chosen_t = self.vector_db.search_excluding_per_query(q, K, own, k_fetch=K + 10 if k_fetch is None else int(k_fetch))
             else:
                 k_fetch = getattr(self.config, "exclusion_k_fetch", K + 10)
                 dist_t, chosen_t = self.vector_db.search_excluding(q, K, excl, k_fetch=K + 10 if k_fetch is None else int(k_fetch))

@@ -91,7 +91,8 @@ class ShardedSearch:
 
     def __init__(self, local_search: Callable, metric: int, group=None, merge: Optional[Callable] = None,
                  uneven: bool = False, exchange: str = "all_to_all", bounded=None, timing: bool = False, excluding=None,
-                 certify: Optional[Callable] = None, local_search_excluding: Optional[Callable] = None):
+                 certify: Optional[Callable] = None, local_search_excluding: Optional[Callable] = None,
+                 excluding_per_query=None, local_search_excluding_per_query: Optional[Callable] = None):
         import torch.distributed as dist
         if exchange not in ("all_to_all", "all_gather"):
             raise ValueError("exchange must be 'all_to_all' or 'all_gather'")
@@ -114,6 +115,12 @@ class ShardedSearch:
         self.excluding = excluding
         self.certify = certify or _hip_certify
         self.local_search_excluding = local_search_excluding
+        # excluding_per_query = (begin, finish[, abort]) of search_excluding(query_tags_local=...) (HipFlatIndex.
+        # sharded_excluding_per_query): begin(q [Q,D], k, query_tags int64 [Q,m], query_tag_counts int32 [Q], k_fetch) -> as above;
+        # finish / abort as above.  local_search_excluding_per_query(q, k, query_tags, query_tag_counts, k_fetch) -> (dist, gid)
+        # serves a world of one (HipFlatIndex.search_excluding_per_query bound to the store's row tags).
+        self.excluding_per_query = excluding_per_query
+        self.local_search_excluding_per_query = local_search_excluding_per_query
         self.timing = bool(timing)       # record (collective_ms, rerank_ms) of every search (CUDA events; read with timings())
         self._events = []
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -204,7 +211,31 @@ class ShardedSearch:
         blocks = self._all_gather(block).view(self.world, emax)
         return torch.unique(torch.cat([blocks[r, :c] for r, c in enumerate(counts)]))         # (sorted ascending)
 
-    def search_excluding(self, q_local, k: int, exclude_tags_local=None, k_fetch=None, return_all: bool = False):
+    def _gather_query_tags(self, qtags_local, qcnt_local, qr: int, qr_pad: int, device):
+        """the rank's per-query tags [qr, m] (or [qr]) and counts [qr] / None -> (tags int64 [world * qr_pad, m], counts int32
+        [world * qr_pad]) in the order of the gathered queries.  They travel as ONE block of fixed width m + 1 (the count rides as
+        the last column), so m must be the same on every rank; padding queries get count 0."""
+        import torch
+        t = torch.as_tensor(qtags_local, dtype=torch.int64).to(device)
+        if t.dim() == 1:
+            t = t.reshape(-1, 1)
+        if t.dim() != 2 or t.shape[0] != qr:
+            raise ValueError(f"query_tags_local must be [Q_r, m] (or [Q_r]) with Q_r = {qr}, got {tuple(t.shape)}")
+        m = t.shape[1]
+        if m > 64:
+            raise ValueError(f"query_tags_local lists {m} tags per query; a per-query exclusion set holds at most 64")
+        c = torch.full((qr,), m, dtype=torch.int64, device=device) if qcnt_local is None else \
+            torch.as_tensor(qcnt_local).to(device=device, dtype=torch.int64).reshape(-1).clamp(0, m)
+        if c.numel() != qr:
+            raise ValueError("query_tag_counts_local must hold one count per local query")
+        block = torch.zeros((qr_pad, m + 1), dtype=torch.int64, device=device)
+        block[:qr, :m] = t
+        block[:qr, m] = c
+        allb = self._all_gather(block)
+        return allb[:, :m].contiguous(), allb[:, m].to(torch.int32).contiguous()
+
+    def search_excluding(self, q_local, k: int, exclude_tags_local=None, k_fetch=None, return_all: bool = False,
+                         query_tags_local=None, query_tag_counts_local=None):
         """The exclusion-aware search (HipFlatIndex.search_excluding) over the row shards: q_local [Q_r, D], exclude_tags_local int64
         tensor (any order, may be None / empty) -> this rank's rows ([Q_r,k] float32 distances, [Q_r,k] global ids): per query the k
         nearest rows of the WHOLE store whose tag no rank excluded, -1 / NaN where fewer exist.  Needs excluding=(begin, finish[,
@@ -222,24 +253,48 @@ class ShardedSearch:
         The "any flag set?" test of step 7 is one 4-byte host read of the all-gathered vector.  It is the ONLY host synchronisation
         this search adds (beyond the count exchanges of step 1 and of uneven=True), and its value is identical on every rank, so
         every rank takes the same sequence of collectives.  A failure between begin and finish gives the begun search up.
-        return_all is refused: each rank certifies its own queries only."""
+        return_all is refused: each rank certifies its own queries only.
+        query_tags_local int64 [Q_r, m] (or [Q_r]; m <= 64, the same on every rank) with query_tag_counts_local [Q_r] or None selects
+        the PER-QUERY form instead (HipFlatIndex.search_excluding_per_query): query j excludes the first count_j of its own tags and
+        nothing else.  The tags travel with the queries, all-gathered at the fixed width m; step 1 is skipped, no union is formed, and
+        the result of a query depends neither on the batch nor on the world size.  Steps 2 - 7 are the same sequence.  Needs
+        excluding_per_query=(begin, finish[, abort]); passing both kinds of set is refused (one call takes one admission rule)."""
         import torch
         if return_all:
             raise ValueError("search_excluding returns a rank's own rows only (return_all is not supported: each rank certifies its own queries)")
+        per_query = query_tags_local is not None
+        if per_query and exclude_tags_local is not None:
+            raise ValueError("search_excluding takes exclude_tags_local (one set for the batch) or query_tags_local (one set per query), "
+                             "not both: a batch-wide set cannot be combined with per-query sets in one call")
+        if query_tag_counts_local is not None and not per_query:
+            raise ValueError("query_tag_counts_local needs query_tags_local")
+        if self.world == 1 and per_query:
+            if self.local_search_excluding_per_query is None:
+                raise ValueError("search_excluding(query_tags_local=...) on one rank needs local_search_excluding_per_query "
+                                 "(HipFlatIndex.search_excluding_per_query)")
+            d_loc, i_loc = self.local_search_excluding_per_query(q_local, k, query_tags_local, query_tag_counts_local, k_fetch)[:2]
+            return d_loc.float(), i_loc
         if self.world == 1:
             if self.local_search_excluding is None:
                 raise ValueError("search_excluding on one rank needs local_search_excluding (HipFlatIndex.search_excluding)")
             d_loc, i_loc = self.local_search_excluding(q_local, k, exclude_tags_local, k_fetch)[:2]
             return d_loc.float(), i_loc
-        if self.excluding is None:
+        if per_query and self.excluding_per_query is None:
+            raise ValueError("search_excluding(query_tags_local=...) needs excluding_per_query=(begin, finish[, abort]) "
+                             "(HipFlatIndex.sharded_excluding_per_query)")
+        if not per_query and self.excluding is None:
             raise ValueError("search_excluding needs excluding=(begin, finish[, abort]) (HipFlatIndex.sharded_excluding)")
-        halves = _Halves(self.excluding)
+        halves = _Halves(self.excluding_per_query if per_query else self.excluding)
         k = int(k)
-        excl = self._gather_exclusion(exclude_tags_local, q_local.device)
+        excl = None if per_query else self._gather_exclusion(exclude_tags_local, q_local.device)
         qr = q_local.shape[0]
         q_local, qr_pad, _ = self._pad_uneven(q_local)
         q_all = self._all_gather(q_local)
-        key, gid, fkey, fgid = halves.begin(q_all, k, excl, k_fetch)
+        if per_query:
+            qtags_all, qcnt_all = self._gather_query_tags(query_tags_local, query_tag_counts_local, qr, qr_pad, q_local.device)
+            key, gid, fkey, fgid = halves.begin(q_all, k, qtags_all, qcnt_all, k_fetch)
+        else:
+            key, gid, fkey, fgid = halves.begin(q_all, k, excl, k_fetch)
         done = False
         try:
             # frontiers ride as column k of the lists: two exchanges instead of four

@@ -112,6 +112,40 @@ def _prep_tags(row_tags, exclude_tags, ntotal: int):
     return row_tags, exclude_tags, n_excl
 
 
+def _prep_query_tags(row_tags, query_tags, query_tag_counts, nq: int, ntotal: int):
+    """-> (row_tags [ntotal], query_tags [nq, m], counts int32 [nq] or None, m): contiguous CUDA tensors of the per-query exclusion
+    (radad_knn_search_excl_pq); a 1-D [nq] query_tags is m = 1; (None, None, None, 0) when no query lists a tag.  A tensor on the CPU,
+    a wrong shape or m above the limit is a ValueError here: the library would only see a pointer."""
+    import torch
+    if query_tags is None:
+        return None, None, None, 0
+    if not isinstance(query_tags, torch.Tensor) or not query_tags.is_cuda:
+        raise ValueError("query_tags must be an int64 CUDA (ROCm) tensor [nq, m]: the HIP path has no CPU fallback")
+    if query_tags.dim() == 1:
+        query_tags = query_tags.reshape(-1, 1)
+    if query_tags.dim() != 2 or query_tags.shape[0] != nq:
+        raise ValueError(f"query_tags must be [nq, m] (or [nq] for one tag per query) with nq = {nq}, got {tuple(query_tags.shape)}")
+    m = int(query_tags.shape[1])
+    if m > _lib.EXCL_PQ_MAX_TAGS:
+        raise ValueError(f"query_tags lists {m} tags per query; a per-query exclusion set holds at most {_lib.EXCL_PQ_MAX_TAGS} "
+                         "(one wave compares them)")
+    if m == 0:
+        return None, None, None, 0
+    if not isinstance(row_tags, torch.Tensor) or not row_tags.is_cuda:
+        raise ValueError("row_tags must be an int64 CUDA (ROCm) tensor [ntotal]: the HIP path has no CPU fallback")
+    query_tags = query_tags.contiguous().to(torch.int64)
+    row_tags = row_tags.contiguous().to(torch.int64).reshape(-1)
+    if row_tags.numel() != ntotal:
+        raise ValueError(f"row_tags must hold one tag per stored row ({ntotal}), got {row_tags.numel()}")
+    if query_tag_counts is not None:
+        if not isinstance(query_tag_counts, torch.Tensor) or not query_tag_counts.is_cuda:
+            raise ValueError("query_tag_counts must be a CUDA (ROCm) tensor [nq]: the HIP path has no CPU fallback")
+        query_tag_counts = query_tag_counts.contiguous().to(torch.int32).reshape(-1)
+        if query_tag_counts.numel() != nq:
+            raise ValueError(f"query_tag_counts must hold one count per query ({nq}), got {query_tag_counts.numel()}")
+    return row_tags, query_tags, query_tag_counts, m
+
+
 def _alloc_out(q, k: int, f64: bool = False):
     """-> (D f32, I i64, K64 f64 or None), each [nq, k] on q's device"""
     import torch
@@ -230,6 +264,25 @@ class HipFlatIndex:
                                                        _lib.stream_ptr(q.device)), "radad_knn_search_excl")
         return (D, I, K64) if return_f64 else (D, I)
 
+    def search_excluding_per_query(self, q, k: int, row_tags, query_tags, query_tag_counts=None, k_fetch=None, return_f64: bool = False):
+        """search_excluding with one exclusion set PER QUERY (radad_knn_search_excl_pq; leave-one-out): row r is admissible for query
+        j iff row_tags[r] is not among the first query_tag_counts[j] entries of query_tags[j].  query_tags int64 CUDA tensor [nq, m],
+        m <= 64, any order, duplicates allowed ([nq] = one tag per query; None or m = 0 = nothing excluded); query_tag_counts int32
+        CUDA tensor [nq], clamped to [0, m] on the device, None = m for every query.  Everything else as search_excluding: the result
+        of a query does not depend on what the other queries of the batch exclude.  If no tag is carried by more than c rows,
+        k_fetch >= k + m * c proves every query in the fast pass (last_excl()["exact"] == 0)."""
+        import torch
+        q, q_dtype = _prep_queries(q, self.d)
+        k = int(k)
+        k_fetch = min(k + 10, _lib.KNN_MAX_K) if k_fetch is None else int(k_fetch)
+        row_tags, query_tags, counts, m = _prep_query_tags(row_tags, query_tags, query_tag_counts, q.shape[0], self.ntotal)
+        D, I, K64 = _alloc_out(q, max(k, 0), return_f64)
+        with torch.cuda.device(q.device):
+            _lib.check(self._lib.radad_knn_search_excl_pq(self._h, q.data_ptr(), q_dtype, q.shape[0], k, k_fetch, _ptr(row_tags),
+                                                          _ptr(query_tags), m, _ptr(counts), D.data_ptr(), I.data_ptr(), _ptr(K64),
+                                                          _lib.stream_ptr(q.device)), "radad_knn_search_excl_pq")
+        return (D, I, K64) if return_f64 else (D, I)
+
     def last_excl(self):
         """{"queries", "exact"} of the most recent search_excluding: its batch size and how many of its queries the exact float64 pass
         answered (radad_knn_last_excl; synchronises with that search)"""
@@ -260,6 +313,30 @@ class HipFlatIndex:
                                                              _ptr(exclude_tags), n_excl, K64.data_ptr(), I.data_ptr(), FK.data_ptr(),
                                                              FI.data_ptr(), _lib.stream_ptr(q.device)), "radad_knn_search_excl_begin")
         self._begun_excl = (q, k, row_tags, exclude_tags)
+        return K64, I, FK, FI
+
+    def search_excluding_per_query_begin(self, q, k: int, row_tags, query_tags, query_tag_counts=None, k_fetch=None):
+        """first half of search_excluding_per_query over a ROW SHARD (radad_knn_search_excl_pq_begin) -> (K64, I, FK, FI) as
+        search_excluding_begin, with the per-query admission test.  It is finished by search_excluding_finish (the begun search
+        remembers its rule) or given up by search_abort; q, the tags and the counts are kept alive until then."""
+        import torch
+        q, q_dtype = _prep_queries(q, self.d)
+        if q.shape[0] == 0:
+            raise ValueError("search_excluding_per_query_begin needs at least one query")
+        k = int(k)
+        k_fetch = min(k + 10, _lib.KNN_MAX_K) if k_fetch is None else int(k_fetch)
+        nq = q.shape[0]
+        row_tags, query_tags, counts, m = _prep_query_tags(row_tags, query_tags, query_tag_counts, nq, self.ntotal)
+        K64 = torch.empty((nq, max(k, 0)), device=q.device, dtype=torch.float64)
+        I = torch.empty((nq, max(k, 0)), device=q.device, dtype=torch.int64)
+        FK = torch.empty((nq,), device=q.device, dtype=torch.float64)
+        FI = torch.empty((nq,), device=q.device, dtype=torch.int64)
+        with torch.cuda.device(q.device):
+            _lib.check(self._lib.radad_knn_search_excl_pq_begin(self._h, q.data_ptr(), q_dtype, nq, k, k_fetch, _ptr(row_tags),
+                                                                _ptr(query_tags), m, _ptr(counts), K64.data_ptr(), I.data_ptr(),
+                                                                FK.data_ptr(), FI.data_ptr(), _lib.stream_ptr(q.device)),
+                       "radad_knn_search_excl_pq_begin")
+        self._begun_excl = (q, k, row_tags, query_tags, counts)
         return K64, I, FK, FI
 
     def search_excluding_finish(self, unproved=None, return_f64: bool = False):
@@ -315,6 +392,15 @@ class HipFlatIndex:
             return K64, I
         return (lambda q, k, exclude_tags, k_fetch=None: self.search_excluding_begin(q, k, row_tags, exclude_tags, k_fetch)), finish, \
             self.search_abort
+
+    def sharded_excluding_per_query(self, row_tags):
+        """the (begin, finish, abort) triple sharded.ShardedSearch(excluding_per_query=...) takes, for this shard and its rows' tags:
+        begin(q, k, query_tags [Q, m], query_tag_counts [Q] or None, k_fetch)"""
+        def finish(unproved):
+            _, I, K64 = self.search_excluding_finish(unproved, return_f64=True)
+            return K64, I
+        return (lambda q, k, query_tags, query_tag_counts=None, k_fetch=None:
+                self.search_excluding_per_query_begin(q, k, row_tags, query_tags, query_tag_counts, k_fetch)), finish, self.search_abort
 
     def search_begin(self, q, k: int):
         """first half of a search over a row shard (sharded.py): prepares the queries and scans this shard; returns a float32 CUDA
@@ -579,6 +665,10 @@ class HipIVFFlatIndex:
     def search_excluding(self, *args, **kwargs):
         raise ValueError("exclusion-aware search is flat and single-handle only: an IVF search sees the probed lists, not the store")
 
+    def search_excluding_per_query(self, *args, **kwargs):
+        raise ValueError("per-query exclusion sets are flat and single-handle only: the IVF search's admission bitmap is one per call "
+                         "and sits inside the list scans (search_probed_excluding takes one set for the batch)")
+
     MAX_K_PROBED = 26   # csrc/ivf.inc: the largest k the list scans hold (k + 6 <= 32 entries per (query, list))
 
     def search_probed_excluding(self, q, k: int, row_tags, exclude_tags):
@@ -824,6 +914,26 @@ class VectorDatabase:
         if k <= 0:
             return self._no_hits(q)
         return self.index.search_excluding(q, k, tags, excl, k_fetch=min(k_fetch, _lib.KNN_MAX_K))
+
+    def search_excluding_per_query(self, query_vectors, k: int = None, query_tags=None, query_tag_counts=None, k_fetch=None):
+        """search_excluding with one exclusion set PER QUERY (HipFlatIndex.search_excluding_per_query; leave-one-out): query i excludes
+        the rows whose basename tag (path_tag) is among the first query_tag_counts[i] entries of query_tags[i] and nothing else, so its
+        result does not depend on the rest of the batch.  query_vectors: CUDA tensor [B, d]; query_tags: int64 tensor / nested sequence
+        [B, m] (or [B]: one tag per query), m <= 64, None = nothing excluded; query_tag_counts: [B] or None = m for every query
+        -> (D f32 [B,k], I i64 [B,k]) on the device, -1 / NaN where fewer than k admissible rows exist.  Flat stores only; a
+        batch-wide set cannot be combined with it in one call."""
+        import torch
+        q, k, k_fetch, _, _ = self._excluding_args(
+            HipFlatIndex, "per-query exclusion sets are flat and single-handle only (vector_db_index_type 'L2' or 'IP'): the IVF "
+            "search's admission bitmap is one per call", query_vectors, k, None, k_fetch)
+        if k <= 0:
+            return self._no_hits(q)
+        if query_tags is not None:
+            query_tags = torch.as_tensor(query_tags, dtype=torch.int64).to(q.device)
+        if query_tag_counts is not None:
+            query_tag_counts = torch.as_tensor(query_tag_counts, dtype=torch.int32).to(q.device)
+        return self.index.search_excluding_per_query(q, k, self.row_tags_device(), query_tags, query_tag_counts,
+                                                     k_fetch=min(k_fetch, _lib.KNN_MAX_K))
 
     def search_probed_excluding(self, query_vectors, k: int = None, exclude_tags=None):
         """IVF stores: the k nearest rows of the probed lists (config.vector_db_nprobe, vector_database.py:174-179) whose basename tag
