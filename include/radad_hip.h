@@ -354,8 +354,8 @@ int radad_excl_merge_certify(int metric, const double* in_key_dev, const int64_t
  * required).  Its second half is radad_knn_search_excl_finish: the begun search remembers the admission rule it was begun with.
  * radad_excl_merge_certify and radad_knn_search_abort cover it unchanged; the queries, the row tags, the query tags and the counts
  * must stay alive until _finish.  _pq_begin + _finish with the shard's own flags is radad_knn_search_excl_pq, bit for bit.
- * Not offered: a batch-wide set combined with per-query sets in one call; the IVF index (its admission bitmap is per call and sits
- * inside the list scans); the cross-shard lower bound. */
+ * Not offered: a batch-wide set combined with per-query sets in one call; the cross-shard lower bound.  The IVF index has its own
+ * call for this, radad_ivf_search_excl_pq below. */
 #define RADAD_EXCL_PQ_MAX_TAGS 64
 int radad_knn_search_excl_pq(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, int k_fetch,
                              const int64_t* row_tags_dev /*[ntotal], by id - id_base*/,
@@ -426,6 +426,31 @@ int radad_ivf_search_excl(radad_ivf_t h, const float* q_dev, int64_t nq, int k, 
                           const int64_t* row_tags_dev /*[ntotal], by insertion id*/,
                           const int64_t* excl_sorted_dev /*[n_excl] ascending*/, int64_t n_excl,
                           float* out_dist_dev, int64_t* out_idx_dev, void* stream);
+/* radad_ivf_search_excl with one exclusion set PER QUERY, the rule of radad_knn_search_excl_pq: row r is admissible for query j iff
+ * row_tags[r] is not among the first cnt_j entries of q_tags[j, :], cnt_j = q_tag_counts[j] clamped on the device to [0, m] (NULL = m
+ * for every query); the tags of a query may come in any order and repeat.  The result of a query is a function of the query alone:
+ * the exact top-k by squared L2 among the admissible rows of ITS nprobe probed lists, ordered by (float64 distance, lower id), padding
+ * -1 / NaN; k in [1, 26], 0 <= m <= RADAD_EXCL_PQ_MAX_TAGS.
+ *   m == 0, or no query excludes a stored row: ids and the distances of filled slots are bit-identical to radad_ivf_search
+ *   every query carries the same set S:        bit for bit radad_ivf_search_excl with S sorted
+ * How: the list kernels keep ONE bit per list-major position in their inner loops, as radad_ivf_search_excl does, with a weaker
+ * meaning -- set = no query of the batch excludes the row.  A pre-pass on `stream` hashes every live tag of the batch into a bitset
+ * (two hashes, sized from nq * m so that under 1 % of the rows nobody excludes look suspect) and tests every position's tag against
+ * it; a row whose bit is clear is decided exactly per (row, query) in a branch of the kernels, against the query's tags held in LDS
+ * (in registers across a wave in the exact float64 list scan).  For every query an excluded row is never emitted, listed or inserted
+ * and never counts towards a bound of THAT query, so both certificates hold per query as they stand.  A batch in which no stored row
+ * is suspect costs the pre-pass and radad_ivf_search_excl's scan.  The frequent-suspect case -- a tag carried by many rows, e.g. a
+ * speaker's, so that most steps take the branch -- costs more; what both cost on an MI355X is measured by tools/bench_ivf.py's
+ * excl_pq_ms leg and written down in profiles/README.md.
+ * RADAD_EINVAL: m outside its range, k > 26, NULL q_tags_dev or row_tags_dev with m > 0, an untrained index.  A trained index
+ * without rows returns all -1 / NaN.  Stream-ordered and serialised like every IVF search; the tag arrays must stay alive until the
+ * call's device work ends.  radad_ivf_last_search_info / _counts describe it, radad_ivf_last_search_exact reports 0.
+ * Not offered: k > 26, m > 64, a batch-wide set combined with per-query sets in one call, sharded IVF. */
+int radad_ivf_search_excl_pq(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int nprobe,
+                             const int64_t* row_tags_dev /*[ntotal], by insertion id*/,
+                             const int64_t* q_tags_dev /*[nq, m] row-major; any order, duplicates allowed*/, int m,
+                             const int32_t* q_tag_counts_dev /*[nq] or NULL = m for every query*/,
+                             float* out_dist_dev, int64_t* out_idx_dev, void* stream);
 /* 1 if the most recent radad_ivf_search was answered by the exact scan of the index's flat store (26 < k <= 128): every row an IVF
  * search could return AND the ones its probing would have missed -- a superset of faiss.IndexIVFFlat's answer (which holds only rows
  * of the nprobe lists, vector_database.py:174-179), at the flat scan's cost, nprobe ignored.  0: the nprobe lists were scanned. */
@@ -448,6 +473,9 @@ int radad_ivf_last_search_counts(radad_ivf_t h, int* rejected_out, int* exact_ou
 /* RADAD_IVF_OPT_HI_SCAN 1 (default) / 0: list scans over the f16 plane / over the fp32 rows (A/B measurements; same results);
  * 2 (tests): the f16 scan runs and every query is then treated as rejected by its certificate, i.e. answered by the exact list scan */
 #define RADAD_IVF_OPT_HI_SCAN 0
+/* RADAD_IVF_OPT_PQ_FILTER 1 (default) / 0 (tests): radad_ivf_search_excl_pq's pre-pass marks the rows some query may exclude / is
+ * skipped and every row counts as suspect, so the per-(row, query) test decides every row.  Same results, bit for bit. */
+#define RADAD_IVF_OPT_PQ_FILTER 1
 int radad_ivf_set_option(radad_ivf_t h, int option, int value);
 int radad_ivf_reconstruct(radad_ivf_t h, const int64_t* idx_dev, int64_t n, float* out_dev, void* stream);
 

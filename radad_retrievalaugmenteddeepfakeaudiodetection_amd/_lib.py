@@ -22,6 +22,7 @@ KNN_MAX_K = 1024
 EXCL_PQ_MAX_TAGS = 64     # RADAD_EXCL_PQ_MAX_TAGS
 KNN_OPT_HI_PLANE, KNN_OPT_CENTRE, KNN_OPT_SMALLQ_HI, KNN_OPT_WIDE_MIN_Q, KNN_OPT_DENSE = 0, 1, 2, 3, 4
 IVF_OPT_HI_SCAN = 0
+IVF_OPT_PQ_FILTER = 1      # RADAD_IVF_OPT_PQ_FILTER
 IVF_SCAN_KINDS = ("f32_lists", "hi_lists", "exact_flat")
 EMBED_NO_SHARED_FRAMES, EMBED_LOGMEL_F32, EMBED_LOGMEL_DFT_GEMM = 1, 2, 4
 PLAN_KINDS = ("none", "host_offsets", "device_offsets", "segments")      # RADAD_PLAN_*
@@ -132,6 +133,8 @@ SIGNATURES = {
     "radad_ivf_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "radad_ivf_search_excl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    "radad_ivf_search_excl_pq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "radad_ivf_last_search_exact": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "radad_ivf_last_search_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "radad_ivf_last_search_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -32,9 +32,29 @@
 //      hide more: rejected)
 //   5. rejected queries only: k_ivf_exact -- launched always, its workgroups leave at once when nobody was rejected
 // Without a plane (dim % 64 != 0, RADAD_IVF_OPT_HI_SCAN 0): k_ivf_f32_eps, k_ivf_scan, k_merge_refine<false> with that eps, k_ivf_exact.
+// Exclusion-aware searches (radad_ivf_search_excl: one set for the batch; radad_ivf_search_excl_pq: one per query) run the same launches
+// with the ADM instantiations of the three list kernels behind a bitmap pre-pass: "exclusion inside the list scans", below.
 // What a search launches and allocates is decided by ivf_plan.h (host-only: tests/ivf_plan_check.cpp); ivf_search_lists is its glue.
 #include "ivf_plan.h"
 namespace {
+
+// The admission test of a list kernel (the template parameter ADM):
+//   IVF_ADM_NONE    every row is admissible (radad_ivf_search)
+//   IVF_ADM_BITMAP  one set for the batch: bit = the row is admissible (radad_ivf_search_excl)
+//   IVF_ADM_PQ      one set per query: bit = NO query of the batch excludes the row; a clear bit is decided per (row, query) against
+//                   the query's tags (radad_ivf_search_excl_pq, below)
+constexpr int IVF_ADM_NONE = 0, IVF_ADM_BITMAP = 1, IVF_ADM_PQ = 2;
+
+// what the IVF_ADM_PQ kernels read beside the suspect bitmap: row r is admissible for query j iff row_tags[r] is not among the first
+// clamp(q_cnt[j], 0, m) entries of q_tags[j, :] (q_cnt nullptr = m for every query)
+struct IvfPqRule {
+    const int64_t* row_tags = nullptr;  // [ntotal] by insertion id
+    const int64_t* lids = nullptr;      // [N] insertion id of every list-major position
+    const int64_t* q_tags = nullptr;    // [nq, m]
+    const int* q_cnt = nullptr;         // [nq] or nullptr
+    int m = 0;
+    int tag_off = 0;                    // list scans: byte offset of the tag block in LDS (IvfPlan: scan_lds - pq_lds)
+};
 
 struct IvfScanParams {
     const float* lrows = nullptr;       // [N, dim] list-major
@@ -51,6 +71,7 @@ struct IvfScanParams {
     float* part_score = nullptr;        // [nq * nprobe, k]
     int* part_idx = nullptr;            // [nq * nprobe, k]  positions in lrows
     const unsigned long long* admit = nullptr;      // FILTERED kernels: the admission bitmap by list-major position (k_admit_bitmap<true>)
+    IvfPqRule pq;                                   // IVF_ADM_PQ: the per-query rule (admit is then the suspect bitmap)
 };
 static_assert(std::is_trivially_copyable_v<IvfScanParams>, "kernel argument");
 
@@ -76,6 +97,74 @@ __device__ __forceinline__ unsigned ivf_admit_bits(const unsigned long long* __r
 __global__ __launch_bounds__(256) void k_ivf_pad_nan(float* __restrict__ dist, const int64_t* __restrict__ idx, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n && idx[i] < 0) dist[i] = __int_as_float(0x7fc00000);
+}
+
+// ---- one exclusion set PER QUERY inside the list scans (radad_ivf_search_excl_pq) ----------------------------------------------------
+// The list kernels keep ONE bit per list-major position in their inner loops, fetched where the admission bits are, with a weaker
+// meaning: set = no query of the batch excludes the row, clear = SUSPECT, some query may.  A suspect row is decided exactly, per (row,
+// query), in a branch: the row's tag (through lids) against the query's tags, staged in LDS per task (ivf_pq_stage) or held across a
+// wave's lanes (k_ivf_exact).  Any superset of the truly excluded rows is a correct suspect set, so the pre-pass may err on that side:
+//   k_ivf_pq_hash     every live tag (j, t < cnt_j) sets two bits of a power-of-two bitset (ivf_pq_bitset_bits: the size and why)
+//   k_ivf_pq_suspect  shaped like k_admit_bitmap<true>: one position per thread, one ballot and one word per wave, the spare word kept;
+//                     a position is suspect when both bits of its row's tag are set (positions past the last row come out clear:
+//                     the kernels look only at positions inside their list)
+// RADAD_IVF_OPT_PQ_FILTER 0 (tests) skips both and clears the bitmap: every position is suspect, every (row, query) decided exactly.
+__device__ __forceinline__ unsigned long long ivf_pq_mix(int64_t tag) {      // splitmix64's finaliser: the two halves are the two hashes
+    unsigned long long x = (unsigned long long)tag + 0x9e3779b97f4a7c15ull;
+    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
+    x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
+    return x ^ (x >> 31);
+}
+__global__ __launch_bounds__(256) void k_ivf_pq_hash(const int64_t* __restrict__ q_tags, const int* __restrict__ q_cnt, int64_t nq, int m,
+                                                     unsigned* __restrict__ bits, unsigned mask) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nq * m) return;
+    const int64_t j = i / m;
+    const int cnt = min(max(q_cnt ? q_cnt[j] : m, 0), m);
+    if ((int)(i - j * m) >= cnt) return;
+    const unsigned long long h = ivf_pq_mix(q_tags[i]);
+    const unsigned a = (unsigned)h & mask, b = (unsigned)(h >> 32) & mask;
+    atomicOr(&bits[a >> 5], 1u << (a & 31));
+    atomicOr(&bits[b >> 5], 1u << (b & 31));
+}
+__global__ __launch_bounds__(256) void k_ivf_pq_suspect(const int64_t* __restrict__ tags, const int64_t* __restrict__ lids, int64_t n,
+                                                        const unsigned* __restrict__ bits, unsigned mask,
+                                                        unsigned long long* __restrict__ admit, int64_t n_words) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;          // (whole waves: every lane ballots)
+    bool clean = false;
+    if (i < n) {
+        const unsigned long long h = ivf_pq_mix(tags[lids[i]]);
+        const unsigned a = (unsigned)h & mask, b = (unsigned)(h >> 32) & mask;
+        clean = !(((bits[a >> 5] >> (a & 31)) & 1u) && ((bits[b >> 5] >> (b & 31)) & 1u));
+    }
+    const unsigned long long w = __ballot(clean);
+    if ((threadIdx.x & 63) == 0 && (i >> 6) < n_words) admit[i >> 6] = w;
+}
+// the tag block of a list-scan task: [qcap][m] tags of the task's queries (pair_q[pbeg + qq]) and their clamped counts, 0 for the rows
+// of the block past the task's count; the caller's __syncthreads makes it visible
+__device__ __forceinline__ void ivf_pq_stage(const IvfPqRule& r, char* smem, int qcap, const int* __restrict__ pair_q, int pbeg, int cnt,
+                                             int tid, int nthreads) {
+    int64_t* sTag = reinterpret_cast<int64_t*>(smem + r.tag_off);
+    int* sTc = reinterpret_cast<int*>(sTag + qcap * r.m);
+    for (int i = tid; i < qcap * r.m; i += nthreads) {
+        const int qq = i / r.m;
+        sTag[i] = qq < cnt ? r.q_tags[(int64_t)pair_q[pbeg + qq] * r.m + (i - qq * r.m)] : 0;
+    }
+    for (int qq = tid; qq < qcap; qq += nthreads) {
+        int c = 0;
+        if (qq < cnt) { const int pq = pair_q[pbeg + qq]; c = min(max(r.q_cnt ? r.q_cnt[pq] : r.m, 0), r.m); }
+        sTc[qq] = c;
+    }
+}
+// a suspect row (list-major position pos, inside the list) against the tags of the task's query qq: true = the query excludes it
+__device__ __forceinline__ bool ivf_pq_excludes(const IvfPqRule& r, const char* smem, int qcap, int qq, int64_t pos) {
+    const int64_t* sTag = reinterpret_cast<const int64_t*>(smem + r.tag_off);
+    const int* sTc = reinterpret_cast<const int*>(sTag + qcap * r.m);
+    const int64_t tag = r.row_tags[r.lids[pos]];
+    const int c = sTc[qq];
+    bool hit = false;
+    for (int t = 0; t < c; ++t) hit |= sTag[qq * r.m + t] == tag;
+    return hit;
 }
 
 // ---- (query, probe) pairs grouped by list, on the device ------------------------------------------------------------
@@ -134,8 +223,13 @@ __global__ __launch_bounds__(256) void k_ivf_scatter(const int64_t* __restrict__
     }
 }
 
-template <int KSEL, bool FILTERED>
+// ADM == IVF_ADM_PQ: the same four bits are fetched at the same place; a row that passed `sc >= thr` with its bit clear is decided
+// there, lazily, by its lane against the tags of the lane's query (r16) -- where IVF_ADM_BITMAP tests the bit.  Only rows the query
+// admits are listed and only listed rows set thr, so the per-(query, list) lists hold the best k + 6 rows the QUERY admits, and
+// k_merge_refine's certificate (eps over all rows of the probed lists is an upper bound for the admitted ones) holds as it stands.
+template <int KSEL, int ADM>
 __device__ __forceinline__ void ivf_scan_task(const IvfScanParams& p, const int task, char* smem) {
+    constexpr bool FILTERED = ADM != IVF_ADM_NONE;
     const int qld = p.dim + 4;
     float* sQ = reinterpret_cast<float*>(smem);                   // [qcap][dim + 4] (rows past the task's count are zero)
     float2* sCand = reinterpret_cast<float2*>(sQ + p.qcap * qld); // [4 waves][16][SQ_SLOTS]; later 3 x 16 x KSEL keys
@@ -151,6 +245,7 @@ __device__ __forceinline__ void ivf_scan_task(const IvfScanParams& p, const int 
         *reinterpret_cast<f32x4*>(sQ + qq * qld + c4 * 4) = v;
     }
     if (tid < 4 * SQ_NQ) sCnt[tid] = 0;
+    if constexpr (ADM == IVF_ADM_PQ) ivf_pq_stage(p.pq, smem, p.qcap, p.pair_q, pbeg, cnt, tid, SQ_THREADS);
     __syncthreads();
 
     const int64_t l_begin = p.loff[list], l_end = p.loff[list + 1];
@@ -210,7 +305,9 @@ __device__ __forceinline__ void ivf_scan_task(const IvfScanParams& p, const int 
             const float sc = 2.f * (acc0[e] + acc1[e]) - p.lnorm[min(row, l_end - 1)];     // L2: rank by 2 q.y - |y|^2
             // (FILTERED: admission is tested HERE, where rows enter the lists -- thr is -inf until a list is full, so a score of -inf
             // would still be inserted; and only listed rows set thr, so an excluded row never counts towards it)
-            if (row < w_end && r16 < cnt && sc >= thr && (!FILTERED || ((adm >> e) & 1u))) {
+            // (IVF_ADM_PQ: a clear bit is a suspect row -- decided here, for this lane's query, only when the row would enter its list)
+            if (row < w_end && r16 < cnt && sc >= thr &&
+                (!FILTERED || ((adm >> e) & 1u) || (ADM == IVF_ADM_PQ && !ivf_pq_excludes(p.pq, smem, p.qcap, r16, row)))) {
                 const int sl = atomicAdd(&myCnt[r16], 1);
                 myCand[r16 * SQ_SLOTS + sl] = make_float2(sc, __int_as_float((int)row));
                 any = true;
@@ -248,10 +345,10 @@ __device__ __forceinline__ void ivf_scan_task(const IvfScanParams& p, const int 
 }
 
 // One workgroup per task.
-template <int KSEL, bool FILTERED>
+template <int KSEL, int ADM>
 __global__ __launch_bounds__(SQ_THREADS, 2) void k_ivf_scan(IvfScanParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if ((int)blockIdx.x < *p.n_tasks_dev) ivf_scan_task<KSEL, FILTERED>(p, blockIdx.x, smem);
+    if ((int)blockIdx.x < *p.n_tasks_dev) ivf_scan_task<KSEL, ADM>(p, blockIdx.x, smem);
 }
 
 // ---- grouping of a SMALL batch in one launch (npairs <= IVG_MAX_PAIRS, nlist <= IVG_MAX_LISTS): count, scan, task table and
@@ -339,6 +436,7 @@ struct IvfHiParams {
     float* cand_score = nullptr;   // [nq][cand_cap]
     int* cand_idx = nullptr;       // [nq][cand_cap] positions in the list-major order
     const unsigned long long* admit = nullptr;      // FILTERED: the admission bitmap by list-major position (k_admit_bitmap<true>)
+    IvfPqRule pq;                                   // IVF_ADM_PQ: the per-query rule (admit is then the suspect bitmap)
 };
 static_assert(std::is_trivially_copyable_v<IvfHiParams>, "kernel argument");
 
@@ -358,8 +456,15 @@ static_assert(sizeof(_Float16) == 2, "ivf_plan.h sizes the f16 queries (ivf_hi_l
 // it never COUNTS towards a bound (it takes KEY_NONE in the selection, like a row past l_end: the K-th best key, the carry and the
 // published gbound are reached by K admissible rows, so b <= a_k of the admissible rows and the certificate holds as it stands).
 // A NaN score gives both (see the chunk loop).
-template <bool FILTERED>
+// IVF_ADM_PQ (radad_ivf_search_excl_pq): both arguments hold PER QUERY.  The score tile is [query][row]; the NaN goes to the entries
+// (row, query) whose query excludes the row and to no other, so for every query a row it excludes is never emitted and never counts
+// towards its K-th best, its carry or gbound[q] -- each is reached by K rows that query q admits, b <= a_k of q's admissible rows.
+// The 16 bits are fetched as before; when all are set nothing else happens, otherwise (wave-uniform branch) the lane speaking for
+// (query r16, row 4 g + e) decides its suspect rows against the query's tags in LDS.  k_merge_refine needs no change: every emitted
+// row is admissible for its query, and eps over all rows of the probed lists is an upper bound for the admitted ones.
+template <int ADM>
 __global__ __launch_bounds__(SQ_THREADS, 4) void k_ivf_scan_hi(IvfHiParams p) {
+    constexpr bool FILTERED = ADM != IVF_ADM_NONE;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int qld = p.dim + 8;
     _Float16* sQ = reinterpret_cast<_Float16*>(smem);                          // [qcap][dim + 8]
@@ -392,6 +497,7 @@ __global__ __launch_bounds__(SQ_THREADS, 4) void k_ivf_scan_hi(IvfHiParams p) {
         *reinterpret_cast<f16x8*>(sQ + qq * qld + c8 * 8) = v;
     }
     for (int i = tid; i < SQ_NQ * 32; i += SQ_THREADS) { sCs[i] = -INFINITY; sCi[i] = IDX_SENTINEL; }
+    if constexpr (ADM == IVF_ADM_PQ) ivf_pq_stage(p.pq, smem, p.qcap, p.pair_q, pbeg, cnt, tid, SQ_THREADS);
     const int pq = r16 < cnt ? p.pair_q[pbeg + r16] : 0;
     const float qs = r16 < cnt ? p.qscale[pq] * 2.f : 0.f;
     const float qc = r16 < cnt ? p.qconst[pq] : 0.f;
@@ -459,8 +565,20 @@ __global__ __launch_bounds__(SQ_THREADS, 4) void k_ivf_scan_hi(IvfHiParams p) {
                         // an excluded row's score is NaN, this kernel's "no such row" in both places that matter: the selection gives
                         // it KEY_NONE (it counts towards no K-th best, carry or gbound), and `score >= thr` is false for it whatever
                         // thr is, -inf included (it is never emitted)
-                        if constexpr (FILTERED) { if (!((abits >> (4 * g + e)) & 1u)) out[e] = __int_as_float(0x7fc00000); }
+                        if constexpr (ADM == IVF_ADM_BITMAP) { if (!((abits >> (4 * g + e)) & 1u)) out[e] = __int_as_float(0x7fc00000); }
                     }
+                // IVF_ADM_PQ: a step without a suspect row is done.  Otherwise the same NaN, per (row, query): this lane's query
+                // (r16; a query row past the task's count has no tags) against its suspect rows of the step.  The bits behind l_end
+                // belong to the next list or to no row: they are not looked at.
+                if constexpr (ADM == IVF_ADM_PQ) {
+                    if (abits != 0xffffu) {                                       // (wave-uniform)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (row0 + 4 * g + e < l_end && !((abits >> (4 * g + e)) & 1u) &&
+                                ivf_pq_excludes(p.pq, smem, p.qcap, min(r16, p.qcap - 1), row0 + 4 * g + e))
+                                out[e] = __int_as_float(0x7fc00000);
+                    }
+                }
             }
             *reinterpret_cast<f32x4*>(sS + r16 * IVH_SLD + 16 * (4 * s4 + wave) + 4 * g) = out;      // row 4 g + e of the step, query r16
         }
@@ -647,13 +765,16 @@ struct IvfExactParams {
     int* arrive = nullptr;             // [nslots] arrival counters (zero between launches: the last arrival resets its own)
     float* out_dist = nullptr; int64_t* out_idx = nullptr;
     const unsigned long long* admit = nullptr;      // FILTERED: the admission bitmap by list-major position (k_admit_bitmap<true>)
+    IvfPqRule pq;                                   // IVF_ADM_PQ: the per-query rule (admit is then the suspect bitmap)
 };
 static_assert(std::is_trivially_copyable_v<IvfExactParams>, "kernel argument");
 
 __device__ __forceinline__ bool ivx_better(double ka, int64_t ia, double kb, int64_t ib) { return ka > kb || (ka == kb && ia < ib); }
 
 // FILTERED (radad_ivf_search_excl): a row whose admission bit is clear is skipped before the insertion test.
-template <bool FILTERED>
+// IVF_ADM_PQ (radad_ivf_search_excl_pq): a pair has ONE query; lane t of every wave holds tag t of it (t < its clamped count), and a
+// row whose bit is clear -- a suspect -- is skipped iff one ballot finds its tag among them: the rule of k_exact_scan_any<true, true>.
+template <int ADM>
 __global__ __launch_bounds__(IVX_THREADS) void k_ivf_exact(IvfExactParams p) {
     const int count = min(*p.count - p.slot0, p.nslots);
     if (count <= 0) return;
@@ -678,6 +799,12 @@ __global__ __launch_bounds__(IVX_THREADS) void k_ivf_exact(IvfExactParams p) {
         __syncthreads();
         double ek = -INFINITY;                                                       // lane e: entry e of the wave's sorted list
         long long ei = IVX_NO_ID;
+        int64_t my_tag = 0;                                                          // (IVF_ADM_PQ) tag `lane` of the pair's query ...
+        bool my_tag_on = false;                                                      // ... when the query's clamped count reaches it
+        if constexpr (ADM == IVF_ADM_PQ) {
+            my_tag_on = lane < min(max(p.pq.q_cnt ? p.pq.q_cnt[qi] : p.pq.m, 0), p.pq.m);
+            if (my_tag_on) my_tag = p.pq.q_tags[qi * p.pq.m + lane];
+        }
         for (int64_t row = r0 + wave * IVX_ROWS; row < r1; row += IVX_WAVES * IVX_ROWS) {
             double acc[IVX_ROWS];
 #pragma unroll
@@ -695,7 +822,13 @@ __global__ __launch_bounds__(IVX_THREADS) void k_ivf_exact(IvfExactParams p) {
 #pragma unroll
             for (int u = 0; u < IVX_ROWS; ++u) {
                 if (row + u >= r1) break;                                            // (wave-uniform)
-                if constexpr (FILTERED) { if (!ivf_admitted(p.admit, row + u)) continue; }      // (wave-uniform)
+                if constexpr (ADM == IVF_ADM_BITMAP) { if (!ivf_admitted(p.admit, row + u)) continue; }      // (wave-uniform)
+                if constexpr (ADM == IVF_ADM_PQ) {                                   // (wave-uniform: one row, one query)
+                    if (!ivf_admitted(p.admit, row + u)) {
+                        const int64_t t = p.pq.row_tags[p.pq.lids[row + u]];
+                        if (__ballot(my_tag_on && my_tag == t) != 0ull) continue;
+                    }
+                }
                 double v = acc[u];
 #pragma unroll
                 for (int ofs = 32; ofs > 0; ofs >>= 1) v += __shfl_xor(v, ofs, 64);
@@ -789,12 +922,14 @@ struct radad_ivf_s {
     DevMem lrows, lnorm, lids, loff, ws_a, ws_b, ws_c, part_s, part_i, tasks;
     DevMem lmax, xkey, xid, xarrive;    // |y|^2 max of every list (the fp32 scan's error bound); partial lists + arrival counters of the exact list scan
     DevMem admit;                       // radad_ivf_search_excl: the admission bitmap by list-major position, rebuilt by every call
+    DevMem pqset;                       // radad_ivf_search_excl_pq: the hash bitset of the suspect pre-pass (`admit` is the suspect bitmap)
     DevMem lhi, lscale, lbias, qbuf, cand_s, cand_i;    // the flat store's f16 plane gathered list-major (+ per-row scale, bias); the queries' f16 side
     bool have_hi = false;               // lhi is up to date with ...
     const void* hi_src = nullptr;       // ... this plane of the flat store (pointer, rows and rebuild count at the gather)
     int64_t hi_src_rows = 0;
     int hi_src_epoch = -1;
     int opt_hi = 1;                     // 0: every search on the fp32 list scan (A/B measurements; radad_ivf_set_option)
+    int opt_pq_filter = 1;              // 0 (tests): the per-query search marks every position suspect (RADAD_IVF_OPT_PQ_FILTER)
     std::vector<int> loff_host;
     hipEvent_t ev_done = nullptr;       // end of the last search's device work: the next search (any stream) waits for it,
     bool last_hi = false;               // the most recent search went through the certified f16 list scan
@@ -939,6 +1074,8 @@ struct IvfSearch {
     float* out_dist; int64_t* out_idx;   // [nq, k]
     hipStream_t st;
     const unsigned long long* admit;     // the admission bitmap, or nullptr: every row is admissible (the unfiltered kernels run)
+    IvfPqRule pq;                        // pq.m > 0: one set per query, `admit` is the suspect bitmap (the IVF_ADM_PQ kernels run)
+    int adm() const { return !admit ? IVF_ADM_NONE : (pq.m > 0 ? IVF_ADM_PQ : IVF_ADM_BITMAP); }
     int* tasks(size_t off) const { return ivf_at<int>(h->tasks, off); }                            // a sub-array of `tasks` (p.tasks.*)
     template <typename T> T* qbuf(size_t off) const { return ivf_at<T>(h->qbuf, off); }            // ... of `qbuf` (p.qbuf.*)
     int* fcount() const { return qbuf<int>(p.qbuf.fcount); }
@@ -958,6 +1095,7 @@ static int ivf_plan_refused(const char* fn, radad_ivf_t h, const IvfPlan& p) {
 static int ivf_ensure_buffers(radad_ivf_t h, const IvfPlan& p, hipStream_t st) {
     int rc;
     if ((rc = h->admit.ensure(p.admit))) return rc;
+    if ((rc = h->pqset.ensure(p.pq_bitset))) return rc;
     if ((rc = h->ws_a.ensure(p.ws_a))) return rc;
     if ((rc = h->ws_b.ensure(p.ws_b))) return rc;
     if ((rc = h->part_s.ensure(p.part_s))) return rc;
@@ -994,6 +1132,27 @@ static int ivf_launch_admit(const IvfSearch& s, const int64_t* row_tags, const i
     const int64_t n = (int64_t)h->assign.size(), n_words = s.p.admit_words;
     hipLaunchKernelGGL(k_admit_bitmap<true>, dim3((unsigned)ceil_div64(n_words * 64, 256)), dim3(256), 0, s.st, row_tags,
                        (const int64_t*)h->lids.p, n, excl_sorted, n_excl, (const int*)nullptr, (unsigned long long*)h->admit.p, n_words);
+    RADAD_HIP_CHECK(hipGetLastError());
+    return RADAD_OK;
+}
+
+// the suspect bitmap of the per-query search, where ivf_launch_admit sits for the batch-wide one: clear the hash bitset, hash the
+// batch's live tags into it, test every position's tag (the kernels' comment, above).  RADAD_IVF_OPT_PQ_FILTER 0: no pre-pass, the
+// bitmap all clear -- every position suspect.
+static int ivf_launch_suspect(const IvfSearch& s) {
+    radad_ivf_t h = s.h;
+    const IvfPlan& p = s.p;
+    const int64_t n = (int64_t)h->assign.size(), n_words = p.admit_words;
+    if (!h->opt_pq_filter) {
+        RADAD_HIP_CHECK(hipMemsetAsync(h->admit.p, 0, p.admit, s.st));
+        return RADAD_OK;
+    }
+    const unsigned mask = (unsigned)(p.pq_bits - 1);
+    RADAD_HIP_CHECK(hipMemsetAsync(h->pqset.p, 0, p.pq_bitset, s.st));
+    hipLaunchKernelGGL(k_ivf_pq_hash, dim3((unsigned)ceil_div64(p.nq * p.pq_m, 256)), dim3(256), 0, s.st, s.pq.q_tags, s.pq.q_cnt, p.nq, p.pq_m,
+                       (unsigned*)h->pqset.p, mask);
+    hipLaunchKernelGGL(k_ivf_pq_suspect, dim3((unsigned)ceil_div64(n_words * 64, 256)), dim3(256), 0, s.st, s.pq.row_tags,
+                       (const int64_t*)h->lids.p, n, (const unsigned*)h->pqset.p, mask, (unsigned long long*)h->admit.p, n_words);
     RADAD_HIP_CHECK(hipGetLastError());
     return RADAD_OK;
 }
@@ -1061,14 +1220,19 @@ static int ivf_launch_hi_route(const IvfSearch& s) {
     ip.n_tasks_dev = s.tasks(p.tasks.nt); ip.pair_q = s.tasks(p.tasks.pq);
     ip.split = p.split;
     ip.dim = h->dim; ip.k = p.k; ip.qcap = p.qcap; ip.gbound = gbound; ip.cand_cnt = cand_cnt; ip.cand_cap = p.ccap;
-    ip.cand_score = (float*)h->cand_s.p; ip.cand_idx = (int*)h->cand_i.p; ip.admit = s.admit;
-    if (s.admit) {
-        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_scan_hi<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.scan_lds));
-        hipLaunchKernelGGL(k_ivf_scan_hi<true>, dim3((unsigned)p.scan_grid), dim3(SQ_THREADS), p.scan_lds, st, ip);
-    } else {
-        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_scan_hi<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.scan_lds));
-        hipLaunchKernelGGL(k_ivf_scan_hi<false>, dim3((unsigned)p.scan_grid), dim3(SQ_THREADS), p.scan_lds, st, ip);
+    ip.cand_score = (float*)h->cand_s.p; ip.cand_idx = (int*)h->cand_i.p; ip.admit = s.admit; ip.pq = s.pq;
+    auto scan = [&](auto kern) -> int {
+        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.scan_lds));
+        hipLaunchKernelGGL(kern, dim3((unsigned)p.scan_grid), dim3(SQ_THREADS), p.scan_lds, st, ip);
+        return RADAD_OK;
+    };
+    int rc;
+    switch (s.adm()) {
+        case IVF_ADM_PQ: rc = scan(k_ivf_scan_hi<IVF_ADM_PQ>); break;
+        case IVF_ADM_BITMAP: rc = scan(k_ivf_scan_hi<IVF_ADM_BITMAP>); break;
+        default: rc = scan(k_ivf_scan_hi<IVF_ADM_NONE>);
     }
+    if (rc) return rc;
     RefineParams m = ivf_refine_params(s);
     m.score = (const float*)h->cand_s.p; m.idx = (const int*)h->cand_i.p; m.n_parts = 1; m.part_len = p.ccap; m.part_cnt = cand_cnt;
     if (p.refine_lds > 48 * 1024)
@@ -1099,15 +1263,16 @@ static int ivf_launch_f32_route(const IvfSearch& s) {
     sp.task_list = s.tasks(p.tasks.tl); sp.task_pbeg = s.tasks(p.tasks.tp); sp.task_cnt = s.tasks(p.tasks.tc);
     sp.n_tasks_dev = s.tasks(p.tasks.nt); sp.pair_q = s.tasks(p.tasks.pq); sp.pair_slot = s.tasks(p.tasks.ps);
     sp.dim = h->dim; sp.k = p.ksel; sp.qcap = p.qcap;
-    sp.part_score = (float*)h->part_s.p; sp.part_idx = (int*)h->part_i.p; sp.admit = s.admit;
+    sp.part_score = (float*)h->part_s.p; sp.part_idx = (int*)h->part_i.p; sp.admit = s.admit; sp.pq = s.pq;
     auto scan = [&](auto kern) -> int {
         RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.scan_lds));
         hipLaunchKernelGGL(kern, dim3((unsigned)p.scan_grid), dim3(SQ_THREADS), p.scan_lds, st, sp);
         return RADAD_OK;
     };
     int rc;
-    if (p.ksel <= 16) rc = s.admit ? scan(k_ivf_scan<16, true>) : scan(k_ivf_scan<16, false>);
-    else rc = s.admit ? scan(k_ivf_scan<32, true>) : scan(k_ivf_scan<32, false>);
+    const int adm = s.adm();
+    if (p.ksel <= 16) rc = adm == IVF_ADM_PQ ? scan(k_ivf_scan<16, IVF_ADM_PQ>) : (adm ? scan(k_ivf_scan<16, IVF_ADM_BITMAP>) : scan(k_ivf_scan<16, IVF_ADM_NONE>));
+    else rc = adm == IVF_ADM_PQ ? scan(k_ivf_scan<32, IVF_ADM_PQ>) : (adm ? scan(k_ivf_scan<32, IVF_ADM_BITMAP>) : scan(k_ivf_scan<32, IVF_ADM_NONE>));
     if (rc) return rc;
     RefineParams m = ivf_refine_params(s);
     m.score = (const float*)h->part_s.p; m.idx = (const int*)h->part_i.p; m.n_parts = p.nprobe; m.part_len = p.ksel;
@@ -1128,7 +1293,7 @@ static int ivf_launch_exact(const IvfSearch& s) {
     x.probes = s.probes(); x.count = s.fcount(); x.done = s.fcount() + 1;
     x.dim = h->dim; x.k = p.k; x.nprobe = p.nprobe; x.nlist = h->nlist; x.nslots = (int)p.nslots;
     x.pkey = (double*)h->xkey.p; x.pid = (int64_t*)h->xid.p; x.arrive = (int*)h->xarrive.p;
-    x.out_dist = s.out_dist; x.out_idx = s.out_idx; x.admit = s.admit;
+    x.out_dist = s.out_dist; x.out_idx = s.out_idx; x.admit = s.admit; x.pq = s.pq;
     auto exact = [&](auto kern) -> int {
         RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.xlds));
         for (int64_t i = 0; i < p.xlaunches; ++i) {
@@ -1138,7 +1303,11 @@ static int ivf_launch_exact(const IvfSearch& s) {
         RADAD_HIP_CHECK(hipGetLastError());
         return RADAD_OK;
     };
-    return s.admit ? exact(k_ivf_exact<true>) : exact(k_ivf_exact<false>);
+    switch (s.adm()) {
+        case IVF_ADM_PQ: return exact(k_ivf_exact<IVF_ADM_PQ>);
+        case IVF_ADM_BITMAP: return exact(k_ivf_exact<IVF_ADM_BITMAP>);
+        default: return exact(k_ivf_exact<IVF_ADM_NONE>);
+    }
 }
 
 // unfilled slots of the exclusion-aware search: -1 / NaN, the padding of radad_filter_topk
@@ -1152,8 +1321,11 @@ static int ivf_launch_pad_nan(const IvfSearch& s) {
 // checked the arguments (k + KNN_MARGIN <= 32); this takes the handle's lock.  filtered: the exact top-k among the rows of the
 // probed lists whose tag (row_tags, by insertion id) is not in excl_sorted; unfilled slots -1 / NaN.  With n_excl == 0 every row is
 // admissible: the unfiltered kernels run and only the padding differs.
+// pq (radad_ivf_search_excl_pq; with filtered, instead of excl_sorted / n_excl): one set per query, pq->m > 0 tags wide (its row_tags,
+// q_tags, q_cnt and m are the caller's; lids and tag_off are filled in here).
 static int ivf_search_lists(const char* fn, radad_ivf_t h, const float* q_dev, int64_t nq, int k, int nprobe, bool filtered, const int64_t* row_tags,
-                            const int64_t* excl_sorted, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, void* stream) {
+                            const int64_t* excl_sorted, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, void* stream,
+                            const IvfPqRule* pq = nullptr) {
     std::lock_guard<std::mutex> lk(h->mu);
     h->last_exact = false;
     DeviceGuard g(h->device);
@@ -1174,12 +1346,15 @@ static int ivf_search_lists(const char* fn, radad_ivf_t h, const float* q_dev, i
         return RADAD_OK;
     }
     facts.plane = ivf_ensure_plane(h, st);
-    const IvfPlan p = ivf_plan_search(facts, nq, k, nprobe, filtered && n_excl > 0);
+    const int pq_m = filtered && pq ? pq->m : 0;
+    const IvfPlan p = ivf_plan_search(facts, nq, k, nprobe, filtered && (n_excl > 0 || pq_m > 0), pq_m);
     if ((rc = ivf_plan_refused(fn, h, p))) return rc;
     if ((rc = ivf_ensure_buffers(h, p, st))) return rc;
 
-    const IvfSearch s{h, p, q_dev, out_dist_dev, out_idx_dev, st, p.admit_words ? (const unsigned long long*)h->admit.p : nullptr};
-    if (p.admit_words && (rc = ivf_launch_admit(s, row_tags, excl_sorted, n_excl))) return rc;
+    IvfPqRule rule;
+    if (p.pq_m > 0) { rule = *pq; rule.lids = (const int64_t*)h->lids.p; rule.tag_off = (int)(p.scan_lds - p.pq_lds); }
+    const IvfSearch s{h, p, q_dev, out_dist_dev, out_idx_dev, st, p.admit_words ? (const unsigned long long*)h->admit.p : nullptr, rule};
+    if (p.admit_words && (rc = p.pq_m > 0 ? ivf_launch_suspect(s) : ivf_launch_admit(s, row_tags, excl_sorted, n_excl))) return rc;
     if ((rc = ivf_launch_coarse_group(s))) return rc;
     if ((rc = p.hi_route ? ivf_launch_hi_route(s) : ivf_launch_f32_route(s))) return rc;
     h->last_hi = p.hi_route;
@@ -1221,7 +1396,7 @@ int radad_ivf_destroy(radad_ivf_t h) {
         h->ws_a.release(); h->ws_b.release(); h->ws_c.release(); h->part_s.release(); h->part_i.release(); h->tasks.release();
         h->lmax.release(); h->xkey.release(); h->xid.release(); h->xarrive.release();
         h->lhi.release(); h->lscale.release(); h->lbias.release(); h->qbuf.release(); h->cand_s.release(); h->cand_i.release();
-        h->admit.release();
+        h->admit.release(); h->pqset.release();
         if (h->ev_done) { (void)hipDeviceSynchronize(); (void)hipEventDestroy(h->ev_done); }
     }
     delete h;
@@ -1367,8 +1542,10 @@ int radad_ivf_last_search_exact(radad_ivf_t h, int* exact_out) {
 int radad_ivf_set_option(radad_ivf_t h, int option, int value) {
     RADAD_REQUIRE(h, "radad_ivf_set_option: NULL handle");
     std::lock_guard<std::mutex> lk(h->mu);
-    RADAD_REQUIRE(option == RADAD_IVF_OPT_HI_SCAN && value >= 0 && value <= 2, "radad_ivf_set_option: unknown option %d or bad value %d", option, value);
-    h->opt_hi = value;
+    RADAD_REQUIRE((option == RADAD_IVF_OPT_HI_SCAN && value >= 0 && value <= 2) || (option == RADAD_IVF_OPT_PQ_FILTER && value >= 0 && value <= 1),
+                  "radad_ivf_set_option: unknown option %d or bad value %d", option, value);
+    if (option == RADAD_IVF_OPT_HI_SCAN) h->opt_hi = value;
+    else h->opt_pq_filter = value;
     return RADAD_OK;
 }
 
@@ -1427,6 +1604,27 @@ int radad_ivf_search_excl(radad_ivf_t h, const float* q_dev, int64_t nq, int k, 
     if (nq == 0) return RADAD_OK;
     RADAD_REQUIRE(q_dev && out_dist_dev && out_idx_dev, "radad_ivf_search_excl: NULL buffer");
     return ivf_search_lists("radad_ivf_search_excl", h, q_dev, nq, k, nprobe, true, row_tags_dev, excl_sorted_dev, n_excl, out_dist_dev, out_idx_dev, stream);
+}
+
+// One exclusion set per query (the header's contract): ivf_search_lists with the per-query rule -- the suspect pre-pass where the
+// admission bitmap is built, the IVF_ADM_PQ list kernels.  m == 0: nothing is excluded, the unfiltered kernels run.
+int radad_ivf_search_excl_pq(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int nprobe, const int64_t* row_tags_dev,
+                             const int64_t* q_tags_dev, int m, const int32_t* q_tag_counts_dev, float* out_dist_dev, int64_t* out_idx_dev,
+                             void* stream) {
+    static_assert(RADAD_EXCL_PQ_MAX_TAGS == IVF_PQ_MAX_TAGS && RADAD_EXCL_PQ_MAX_TAGS <= 64, "lane t of a wave holds tag t (k_ivf_exact)");
+    RADAD_REQUIRE(h, "NULL handle");
+    RADAD_REQUIRE(h->trained, "radad_ivf_search_excl_pq: the index is not trained");
+    RADAD_REQUIRE(k >= 1 && k + KNN_MARGIN <= 32, "radad_ivf_search_excl_pq: k=%d outside [1,%d], the range the list scans hold", k, 32 - KNN_MARGIN);
+    RADAD_REQUIRE(nq >= 0 && nq < (1 << 24), "radad_ivf_search_excl_pq: bad nq");
+    RADAD_REQUIRE(nprobe >= 1, "radad_ivf_search_excl_pq: nprobe=%d must be >= 1", nprobe);
+    RADAD_REQUIRE(m >= 0 && m <= RADAD_EXCL_PQ_MAX_TAGS, "radad_ivf_search_excl_pq: m=%d tags per query outside [0,%d] (RADAD_EXCL_PQ_MAX_TAGS)", m,
+                  RADAD_EXCL_PQ_MAX_TAGS);
+    RADAD_REQUIRE(m == 0 || (q_tags_dev && row_tags_dev), "radad_ivf_search_excl_pq: %d tags per query need the query tags and the row tags", m);
+    if (nq == 0) return RADAD_OK;
+    RADAD_REQUIRE(q_dev && out_dist_dev && out_idx_dev, "radad_ivf_search_excl_pq: NULL buffer");
+    IvfPqRule rule;
+    rule.row_tags = row_tags_dev; rule.q_tags = q_tags_dev; rule.q_cnt = m > 0 ? (const int*)q_tag_counts_dev : nullptr; rule.m = m;
+    return ivf_search_lists("radad_ivf_search_excl_pq", h, q_dev, nq, k, nprobe, true, row_tags_dev, nullptr, 0, out_dist_dev, out_idx_dev, stream, &rule);
 }
 
 }  // extern "C"

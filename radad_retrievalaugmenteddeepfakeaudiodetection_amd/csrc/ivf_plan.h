@@ -30,6 +30,24 @@ constexpr size_t IVX_PART_BUDGET = (size_t)128 << 20;    // partial lists of one
 constexpr size_t ivf_exact_lds_bytes(int dim, int k, int nprobe) {
     return (size_t)dim * 4 + (size_t)IVX_WAVES * k * 16 + (size_t)nprobe * 4;
 }
+// per-query exclusion sets (radad_ivf_search_excl_pq), m tags per query
+constexpr int IVF_PQ_MAX_TAGS = 64;            // RADAD_EXCL_PQ_MAX_TAGS: one wave compares a row's tag with a query's set in one ballot
+// the tag block both list scans append to their LDS: [qcap][m] int64 tags of the task's queries, then [qcap] clamped counts, whole
+// 16-byte units (k_ivf_exact has one query per pair and holds its tags in registers, lane t tag t: no LDS)
+constexpr size_t ivf_pq_lds_bytes(int qcap, int m) {
+    return m > 0 ? (((size_t)qcap * m * 8 + (size_t)qcap * 4 + 15) & ~(size_t)15) : 0;
+}
+// The hash bitset of the pre-pass (k_ivf_pq_hash, k_ivf_pq_suspect): every live tag of the batch sets two bits of a bitset of B bits; a
+// stored row is SUSPECT when both bits of its tag are set.  With n = nq m tags (an upper bound on the live ones) a row no query excludes
+// is suspect with probability (1 - exp(-2 n / B))^2; B = the power of two >= 32 n gives 2 n / B <= 1/16 and a share below
+// (1 - exp(-1/16))^2 = 0.37 % -- under 1 % with room for the hash not being ideal.  At least 2^12 bits (one 512-byte clear), at most
+// 2^30 (128 MB, reached by 2^25 tags: beyond that the share of false suspects grows, the result stays exact -- the list kernels decide).
+constexpr int64_t IVF_PQ_MIN_BITS = (int64_t)1 << 12, IVF_PQ_MAX_BITS = (int64_t)1 << 30;
+constexpr int64_t ivf_pq_bitset_bits(int64_t nq, int m) {
+    int64_t b = IVF_PQ_MIN_BITS;
+    while (b < IVF_PQ_MAX_BITS && b < 32 * nq * m) b <<= 1;
+    return b;
+}
 
 // what the plan reads of an index
 struct IvfFacts {
@@ -73,11 +91,18 @@ struct IvfPlan {
     // bytes of every other buffer the search sizes (0: not used by this search)
     size_t ws_a = 0, ws_b = 0, part_s = 0, part_i = 0, cand_s = 0, cand_i = 0, xkey = 0, xid = 0, xarrive = 0, admit = 0;
     int64_t admit_words = 0;         // words of the admission bitmap, the spare one included
+    // per-query exclusion sets (pq_m > 0): `admit` is then the SUSPECT bitmap (same size, same spare word)
+    int pq_m = 0;                    // tags per query
+    size_t pq_lds = 0;               // the tag block, part of scan_lds on both routes (at offset scan_lds - pq_lds)
+    int64_t pq_bits = 0;             // bits of the pre-pass's hash bitset (a power of two)
+    size_t pq_bitset = 0;            // its bytes
 };
 
-// The plan of radad_ivf_search / radad_ivf_search_excl on the probed lists (k + KNN_MARGIN <= 32).  has_admit: the search reads an
-// admission bitmap (exclusion-aware with a set that is not empty).
-static IvfPlan ivf_plan_search(const IvfFacts& s, int64_t nq, int k, int nprobe, bool has_admit) {
+// The plan of radad_ivf_search / radad_ivf_search_excl / radad_ivf_search_excl_pq on the probed lists (k + KNN_MARGIN <= 32).
+// has_admit: the search reads an admission bitmap (exclusion-aware with a set that is not empty).  pq_m > 0 (with has_admit): one set
+// of pq_m tags per query -- the bitmap is the suspect bitmap, the pre-pass needs its hash bitset and both list scans the tag block in
+// LDS; with pq_m == 0 the plan is field for field what it was (tests/ivf_plan_pq_check.cpp).
+static IvfPlan ivf_plan_search(const IvfFacts& s, int64_t nq, int k, int nprobe, bool has_admit, int pq_m = 0) {
     IvfPlan p;
     nprobe = std::max(1, std::min(nprobe, s.nlist));
     const int64_t n = s.rows;
@@ -88,6 +113,12 @@ static IvfPlan ivf_plan_search(const IvfFacts& s, int64_t nq, int k, int nprobe,
         const int64_t n_words = ((n + 63) >> 6) + 1;             // (+ 1: the spare word, all zero)
         p.admit_words = n_words;
         p.admit = (size_t)n_words * sizeof(unsigned long long);
+    }
+    if (!has_admit) pq_m = 0;
+    p.pq_m = pq_m;
+    if (pq_m > 0) {
+        p.pq_bits = ivf_pq_bitset_bits(nq, pq_m);
+        p.pq_bitset = (size_t)(p.pq_bits >> 3);
     }
 
     // 1) coarse quantiser: the nprobe nearest centroids of every query
@@ -112,7 +143,9 @@ static IvfPlan ivf_plan_search(const IvfFacts& s, int64_t nq, int k, int nprobe,
     p.group_lds = p.group_small ? (size_t)s.nlist * sizeof(int) : 0;
 
     // per-query scratch of either route: eps, the certificate's list of rejected queries, the search's counters
-    const bool hi_route = s.plane && ivf_hi_lds_bytes(qcap, s.dim) <= 160 * 1024;
+    const size_t pq_lds = ivf_pq_lds_bytes(qcap, pq_m);
+    p.pq_lds = pq_lds;
+    const bool hi_route = s.plane && ivf_hi_lds_bytes(qcap, s.dim) + pq_lds <= 160 * 1024;
     const size_t b_qh = hi_route ? al256((size_t)nq * s.dim * 2) : 0, b_vec = al256((size_t)nq * sizeof(float));
     p.hi_route = hi_route;
     {   // qh | qscale | qconst | eps | cand_cnt | gbound | fsel | fcount [8]: [0] rejected, [1] answered by the exact scan
@@ -134,13 +167,13 @@ static IvfPlan ivf_plan_search(const IvfFacts& s, int64_t nq, int k, int nprobe,
         // against its own bound, and all of a query's must fit half its buffer
         p.split = (int)std::max<int64_t>(1, std::min<int64_t>(T <= 64 ? 8 : (T <= 128 ? 4 : (T <= 256 ? 2 : 1)), (ccap / 2) / ((int64_t)nprobe * (k + 8))));
         p.scan_grid = T * p.split;
-        p.scan_lds = ivf_hi_lds_bytes(qcap, s.dim);
+        p.scan_lds = ivf_hi_lds_bytes(qcap, s.dim) + pq_lds;
         p.cap = std::max(k + KNN_CERT_EXTRA, KNN_CERT_CAP);
         p.refine_lds = refine_lds_bytes(p.cap) + (size_t)ccap * 8 + 1024;
     } else {
         // 3b) the fp32 list scan (no f16 plane: dim % 64 != 0, RADAD_IVF_OPT_HI_SCAN 0)
         p.scan_grid = T;
-        const size_t lds = knn_sq_lds_f32(qcap, s.dim);
+        const size_t lds = knn_sq_lds_f32(qcap, s.dim) + pq_lds;
         p.scan_lds = lds;
         if (!(lds <= 160 * 1024)) { p.status = IVF_PLAN_DIM_TOO_LARGE; return p; }
         p.cap = std::max(k + KNN_CERT_EXTRA, (int)std::min<int64_t>((int64_t)nprobe * ksel, KNN_CERT_CAP));

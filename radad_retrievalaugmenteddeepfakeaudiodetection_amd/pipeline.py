@@ -130,18 +130,19 @@ class HotPathPipeline:
         if scope not in ("batch", "query"):
             raise ValueError(f"config.exclusion_scope must be 'batch' or 'query', got {scope!r}")
         per_query = scope == "query" and exclude_self
-        if per_query and not exact_excl:
-            raise ValueError("config.exclusion_scope 'query' needs config.exact_exclusion: the over-fetch-and-drop path excludes the batch's union")
+        # config.ivf_exact_exclusion (opt-in): the same for an IVF store, among the rows of the probed lists
+        # (VectorDatabase.search_probed_excluding, with scope "query" search_probed_excluding_per_query); a flat store ignores it
+        ivf_excl = bool(getattr(self.config, "ivf_exact_exclusion", False)) and exclude_self and isinstance(index, HipIVFFlatIndex)
+        if exact_excl and not isinstance(index, HipFlatIndex):
+            raise ValueError("config.exact_exclusion: exclusion-aware search is flat and single-handle only (vector_db_index_type 'L2' or 'IP'); "
+                             "an IVF store takes config.ivf_exact_exclusion")
+        if per_query and not exact_excl and not ivf_excl:
+            raise ValueError("config.exclusion_scope 'query' needs config.exact_exclusion (flat stores) or config.ivf_exact_exclusion (IVF "
+                             "stores): the over-fetch-and-drop path excludes the batch's union")
         if per_query and query_paths is None:
             raise ValueError("config.exclusion_scope 'query' needs query_paths: a query excludes its own basename")
-        if per_query and not isinstance(index, HipFlatIndex):
-            raise ValueError("config.exclusion_scope 'query': per-query exclusion sets are flat and single-handle only "
-                             "(vector_db_index_type 'L2' or 'IP')")
-        if exact_excl and not isinstance(index, HipFlatIndex):
-            raise ValueError("config.exact_exclusion: exclusion-aware search is flat and single-handle only (vector_db_index_type 'L2' or 'IP')")
-        # config.ivf_exact_exclusion (opt-in): the same for an IVF store, among the rows of the probed lists
-        # (VectorDatabase.search_probed_excluding); a flat store ignores it
-        ivf_excl = bool(getattr(self.config, "ivf_exact_exclusion", False)) and exclude_self and isinstance(index, HipIVFFlatIndex)
+        if per_query and len(query_paths) != B:
+            raise ValueError(f"config.exclusion_scope 'query' needs one path per query ({B}), got {len(query_paths)}")
         dists_t = idxs_t = None
         if not exact_excl and not ivf_excl:
             try:
@@ -157,12 +158,15 @@ class HotPathPipeline:
             if names:
                 excl = torch.tensor(sorted({path_tag(n) for n in names}), dtype=torch.int64, device=self.device)
         if exact_excl or ivf_excl:
-            if ivf_excl:
-                dist_t, chosen_t = self.vector_db.search_probed_excluding(q, K, excl)
-            elif per_query:
-                if len(query_paths) != B:
-                    raise ValueError(f"config.exclusion_scope 'query' needs one path per query ({B}), got {len(query_paths)}")
+            own = None
+            if per_query:
                 own = torch.tensor([[path_tag(os.path.basename(p))] for p in query_paths], dtype=torch.int64, device=self.device)
+            if ivf_excl:
+                if per_query:
+                    dist_t, chosen_t = self.vector_db.search_probed_excluding_per_query(q, K, own)
+                else:
+                    dist_t, chosen_t = self.vector_db.search_probed_excluding(q, K, excl)
+            elif per_query:
                 k_fetch = getattr(self.config, "exclusion_k_fetch", K + 10)
                 dist_t, chosen_t = self.vector_db.search_excluding_per_query(q, K, own, k_fetch=K + 10 if k_fetch is None else int(k_fetch))
             else:

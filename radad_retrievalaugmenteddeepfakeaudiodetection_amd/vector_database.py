@@ -554,9 +554,10 @@ class HipIVFFlatIndex:
     (vector_database.py:65-70,124-128,138,174-181; pipeline.py:503): d, nlist, nprobe, is_trained, ntotal, train, add,
     search, reconstruct."""
 
-    def __init__(self, d: int, nlist: int, device: int = 0, niter: int = 10, hi_scan=None):
+    def __init__(self, d: int, nlist: int, device: int = 0, niter: int = 10, hi_scan=None, pq_filter=None):
         """hi_scan: 0 keeps the list scans on the fp32 rows (radad_ivf_set_option; None = the library's default, the certified f16 scan);
-        2 (tests) sends every query through the exact float64 list scan that answers the queries a certificate rejects"""
+        2 (tests) sends every query through the exact float64 list scan that answers the queries a certificate rejects.
+        pq_filter: 0 (tests) makes search_probed_excluding_per_query treat every row as suspect (RADAD_IVF_OPT_PQ_FILTER; same results)"""
         self._lib = _lib.load()
         self.d, self.nlist, self.device, self.niter = int(d), int(nlist), int(device), int(niter)
         self.nprobe = 1                      # faiss default; the reference sets it from config.vector_db_nprobe (:177)
@@ -568,6 +569,12 @@ class HipIVFFlatIndex:
         self._h = h
         if hi_scan is not None:
             _lib.check(self._lib.radad_ivf_set_option(self._h, _lib.IVF_OPT_HI_SCAN, int(hi_scan)), "radad_ivf_set_option")
+        if pq_filter is not None:
+            self.set_pq_filter(pq_filter)
+
+    def set_pq_filter(self, value):
+        """RADAD_IVF_OPT_PQ_FILTER: 1 = the suspect pre-pass of search_probed_excluding_per_query (default), 0 (tests) = every row suspect"""
+        _lib.check(self._lib.radad_ivf_set_option(self._h, _lib.IVF_OPT_PQ_FILTER, int(value)), "radad_ivf_set_option")
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -666,8 +673,8 @@ class HipIVFFlatIndex:
         raise ValueError("exclusion-aware search is flat and single-handle only: an IVF search sees the probed lists, not the store")
 
     def search_excluding_per_query(self, *args, **kwargs):
-        raise ValueError("per-query exclusion sets are flat and single-handle only: the IVF search's admission bitmap is one per call "
-                         "and sits inside the list scans (search_probed_excluding takes one set for the batch)")
+        raise ValueError("search_excluding_per_query is the flat store's search: an IVF search sees the probed lists, not the store "
+                         "(search_probed_excluding_per_query takes one set per query, search_probed_excluding one for the batch)")
 
     MAX_K_PROBED = 26   # csrc/ivf.inc: the largest k the list scans hold (k + 6 <= 32 entries per (query, list))
 
@@ -690,6 +697,28 @@ class HipIVFFlatIndex:
             _lib.check(self._lib.radad_ivf_search_excl(self._h, q.data_ptr(), q.shape[0], k, int(self.nprobe), _ptr(row_tags),
                                                        _ptr(exclude_tags), n_excl, D.data_ptr(), I.data_ptr(),
                                                        _lib.stream_ptr(q.device)), "radad_ivf_search_excl")
+        self.last_search_exact = False
+        return D, I
+
+    def search_probed_excluding_per_query(self, q, k: int, row_tags, query_tags, query_tag_counts=None):
+        """search_probed_excluding with one exclusion set PER QUERY (radad_ivf_search_excl_pq; leave-one-out): row r is admissible for
+        query j iff row_tags[r] is not among the first query_tag_counts[j] entries of query_tags[j].  query_tags int64 CUDA tensor
+        [nq, m], m <= 64, any order, duplicates allowed ([nq] = one tag per query; None or m = 0 = nothing excluded); query_tag_counts
+        int32 CUDA tensor [nq], clamped to [0, m] on the device, None = m for every query.  Everything else as search_probed_excluding;
+        the result of a query does not depend on what the other queries of the batch exclude."""
+        import torch
+        k = int(k)
+        if k > self.MAX_K_PROBED:
+            raise ValueError(f"search_probed_excluding_per_query supports k <= {self.MAX_K_PROBED}, the range the list scans hold (asked for {k})")
+        q = self._to_dev(q)
+        if q.dim() != 2 or q.shape[1] != self.d:
+            raise ValueError(f"search expects [nq, {self.d}], got {tuple(q.shape)}")
+        row_tags, query_tags, counts, m = _prep_query_tags(row_tags, query_tags, query_tag_counts, q.shape[0], self.ntotal)
+        D, I, _ = _alloc_out(q, max(k, 0))
+        with torch.cuda.device(q.device):
+            _lib.check(self._lib.radad_ivf_search_excl_pq(self._h, q.data_ptr(), q.shape[0], k, int(self.nprobe), _ptr(row_tags),
+                                                          _ptr(query_tags), m, _ptr(counts), D.data_ptr(), I.data_ptr(),
+                                                          _lib.stream_ptr(q.device)), "radad_ivf_search_excl_pq")
         self.last_search_exact = False
         return D, I
 
@@ -924,8 +953,8 @@ class VectorDatabase:
         batch-wide set cannot be combined with it in one call."""
         import torch
         q, k, k_fetch, _, _ = self._excluding_args(
-            HipFlatIndex, "per-query exclusion sets are flat and single-handle only (vector_db_index_type 'L2' or 'IP'): the IVF "
-            "search's admission bitmap is one per call", query_vectors, k, None, k_fetch)
+            HipFlatIndex, "search_excluding_per_query is flat and single-handle only (vector_db_index_type 'L2' or 'IP'); an IVF store has "
+            "search_probed_excluding_per_query", query_vectors, k, None, k_fetch)
         if k <= 0:
             return self._no_hits(q)
         if query_tags is not None:
@@ -949,6 +978,25 @@ class VectorDatabase:
         if hasattr(self.config, "vector_db_nprobe"):        # vector_database.py:174-179
             self.index.nprobe = int(self.config.vector_db_nprobe)
         return self.index.search_probed_excluding(q, k, tags, excl)
+
+    def search_probed_excluding_per_query(self, query_vectors, k: int = None, query_tags=None, query_tag_counts=None):
+        """IVF stores: search_probed_excluding with one exclusion set PER QUERY (HipIVFFlatIndex.search_probed_excluding_per_query;
+        leave-one-out): query i excludes the rows whose basename tag (path_tag) is among the first query_tag_counts[i] entries of
+        query_tags[i] and nothing else, so its result does not depend on the rest of the batch.  Arguments and result as
+        search_excluding_per_query, among the rows of the probed lists (config.vector_db_nprobe)."""
+        import torch
+        q, k, _, _, _ = self._excluding_args(
+            HipIVFFlatIndex, "search_probed_excluding_per_query is the IVF store's per-query exclusion-aware search (vector_db_index_type "
+            "'IVF'); a flat store has search_excluding_per_query", query_vectors, k, None)
+        if k <= 0:
+            return self._no_hits(q)
+        if query_tags is not None:
+            query_tags = torch.as_tensor(query_tags, dtype=torch.int64).to(q.device)
+        if query_tag_counts is not None:
+            query_tag_counts = torch.as_tensor(query_tag_counts, dtype=torch.int32).to(q.device)
+        if hasattr(self.config, "vector_db_nprobe"):        # vector_database.py:174-179
+            self.index.nprobe = int(self.config.vector_db_nprobe)
+        return self.index.search_probed_excluding_per_query(q, k, self.row_tags_device(), query_tags, query_tag_counts)
 
     # ---- device-side columns for retrieve_similar_vectors ------------------------------------------------------
     def row_tags_device(self):

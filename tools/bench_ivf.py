@@ -4,6 +4,10 @@ nprobe 32 (config.py:76), k = 15.  Prints build times and, per batch size, the s
 search, the flat search's own time, and a roofline block: the bytes of the lists the batch touches (f16 plane rows + their scale /
 bias, each list once) over the search time against HBM (8 TB/s).  "excl_ms": the exclusion-aware search (radad_ivf_search_excl, tags =
 row ids) at the same shape with 0 % (a one-tag set no row carries: the filtered kernels run), 1 % and 95 % of the rows excluded.
+"excl_pq_ms": one exclusion set per query (radad_ivf_search_excl_pq) in three cases -- "loo_m1": every query excludes the one stored row
+it was drawn from (tags = row ids); "none_m64": 64 tags per query that no row carries; "speaker_m1": tags = row id % 100, every query
+excludes the tag of its source row, carried by 1 % of the rows (the per-(row, query) branch runs often) -- each beside "union_ms", the
+batch-wide radad_ivf_search_excl with the UNION of the batch's sets: another question, the same rows streamed.
 tools/bench_ivf.py [nq,nq,...] [hi_scan 0|1]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -59,6 +63,22 @@ for nq in NQS:
         if name == "0pct":
             assert torch.equal(Ix, Ii)
         excl_ms[name] = {"search_ms": round(ms_x, 4), "over_plain": round(ms_x / ms, 3), "rejected": xi["rejected"], "filled": round(float((Ix >= 0).float().mean()), 4)}
+    src = (torch.arange(nq, device=dev) * 977 + 5) % N           # the row every query was drawn from
+    spk = tags % 100
+    PQ = {"loo_m1": (tags, src.reshape(-1, 1)), "none_m64": (tags, N + 1 + torch.arange(nq * 64, device=dev).reshape(nq, 64)),
+          "speaker_m1": (spk, spk[src].reshape(-1, 1))}
+    excl_pq_ms = {}
+    for name, (rt, qt) in PQ.items():
+        ms_p, (Dp, Ip) = timed(lambda: idx.search_probed_excluding_per_query(q, K, rt, qt))
+        pi = idx.last_search_info()
+        union = torch.unique(qt)
+        ms_u, _ = timed(lambda: idx.search_probed_excluding(q, K, rt, union))
+        hit = (rt[Ip.clamp(min=0)].unsqueeze(2) == qt.unsqueeze(1)).any(2) & (Ip >= 0)
+        assert not hit.any()
+        if name == "none_m64":
+            assert torch.equal(Ip, Ii)
+        excl_pq_ms[name] = {"search_ms": round(ms_p, 4), "union_ms": round(ms_u, 4), "over_union": round(ms_p / ms_u, 3), "over_plain": round(ms_p / ms, 3),
+                            "rejected": pi["rejected"], "filled": round(float((Ip >= 0).float().mean()), 4)}
     rec = float(np.mean([len(set(a) & set(b)) / K for a, b in zip(Ii.cpu().tolist(), Ie.cpu().tolist())]))
     # the lists this batch probes (float64 centroid distances, as the oracle's ivf_search): each is streamed once per task of <= 16 queries
     d2 = torch.cdist(q.double(), centroids.double())
@@ -69,7 +89,7 @@ for nq in NQS:
     row_bytes = (2 if info["scan"] == "hi_lists" else 4) * D + 8
     alg = int(list_rows[touched].sum().item()) * row_bytes
     streamed = int((list_rows * ((per_list_q + 15) // 16)).sum().item()) * row_bytes
-    out[f"nq{nq}"] = {"search_ms": round(ms, 4), "flat_search_ms": round(ms_flat, 4), "recall_at_15_vs_flat": round(rec, 4), **info, "excl_ms": excl_ms,
+    out[f"nq{nq}"] = {"search_ms": round(ms, 4), "flat_search_ms": round(ms_flat, 4), "recall_at_15_vs_flat": round(rec, 4), **info, "excl_ms": excl_ms, "excl_pq_ms": excl_pq_ms,
                       "lists_touched": int(touched.numel()), "tasks": tasks,
                       "roofline": {"bound": "hbm", "algorithmic_bytes": alg, "streamed_bytes": streamed, "achieved": round(alg / (ms * 1e-3) / 1e9, 1),
                                    "peak": 8000.0, "unit": "GB/s", "frac": round(alg / (ms * 1e-3) / 1e9 / 8000.0, 4),
