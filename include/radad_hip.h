@@ -69,7 +69,13 @@ int radad_device_count(void);
 typedef struct radad_knn_s* radad_knn_t;
 
 /* dim must be a positive multiple of 4.  id_base is added to every returned index (row-shard offset;
- * 0 for an unsharded store).  Rows are stored as fp32 in HBM in insertion order. */
+ * 0 for an unsharded store).  Rows are stored as fp32 in HBM in insertion order.
+ * The width x k limit: a store of any such dim can be created and filled, but a search of it at k needs
+ *     dim * 4 + 96 * k + 16 <= 163840
+ * (one fp32 query and the eight k-entry lists of the exact float64 kernel in the 160 KB LDS of a compute unit): dim <= 16380 at
+ * k = RADAD_KNN_MAX_K = 1024, dim <= 40932 at k = 1.  Every search entry point (radad_knn_search*, _search_begin, _search_excl* -- there
+ * with k_fetch for k) returns RADAD_EINVAL beyond it BEFORE anything is enqueued: the output buffers are untouched and the handle
+ * stays usable, whether or not the search would have needed the exact kernel. */
 int radad_knn_create(int dim, int metric, int device, int64_t id_base, radad_knn_t* out);
 /* same with a choice of storage type.  RADAD_STORE_F16 is the reference's `use_float16` knob (faiss
  * GpuIndexFlatConfig.useFloat16, vector_database.py:80): rows are rounded to IEEE fp16 on the way in (after the cosine
@@ -115,7 +121,7 @@ int radad_knn_add_host(radad_knn_t h, const float* rows_host, int64_t n);
  *   out_dist_dev [nq, k] fp32  L2: squared distances ascending; IP/cosine: inner products descending
  *   out_idx_dev  [nq, k] int64 id_base + row; ties are broken towards the LOWER index, always
  *   slots beyond ntotal are filled with index -1 and distance +inf (L2) / -inf (IP), as faiss does.
- * k must be in [1, RADAD_KNN_MAX_K]. */
+ * k must be in [1, RADAD_KNN_MAX_K], and dim * 4 + 96 * k + 16 <= 163840 (the width x k limit, radad_knn_create). */
 #define RADAD_KNN_MAX_K 1024
 int radad_knn_search(radad_knn_t h, const float* q_dev, int64_t nq, int k, float* out_dist_dev,
                      int64_t* out_idx_dev, void* stream);
@@ -124,7 +130,9 @@ int radad_knn_search(radad_knn_t h, const float* q_dev, int64_t nq, int k, float
  * row whose scan score is within 2 eps of the k-th best is re-scored in float64 from the stored rows (L2 as sum (q-y)^2)
  * and ordered by (float64 distance, id); a per-query certificate checks that no unlisted row can reach that threshold, and
  * the queries it rejects are searched again by an exact float64 kernel (driven from the device, no host round trip).  For
- * every k in [1, RADAD_KNN_MAX_K] ids and order are therefore those of an exact float64 brute force, ties to the lower id, and
+ * every k in [1, RADAD_KNN_MAX_K] within the width x k limit (radad_knn_create: dim * 4 + 96 * k + 16 <= 163840, i.e. dim <= 16380
+ * at k = 1024; refused with RADAD_EINVAL before anything is enqueued otherwise) ids and order are therefore those of an exact
+ * float64 brute force, ties to the lower id, and
  * out_dist is the correctly rounded distance (k <= 128 takes the f16 MFMA scans where they apply; larger k the fp32 tile
  * kernels, certified the same way).  Sharded
  * searches merge on these keys (radad_topk_merge_f64) so that no cross-shard pair is decided by fp32 rounding.

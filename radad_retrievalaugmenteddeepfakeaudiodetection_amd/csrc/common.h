@@ -15,6 +15,7 @@ void radad_set_error(const char* fmt, ...);
         hipError_t e__ = (expr);                                                                      \
         if (e__ != hipSuccess) {                                                                      \
             radad_set_error("%s: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__);    \
+            (void)hipGetLastError(); /* reported here: the next call's hipGetLastError() must not find it */ \
             return RADAD_EHIP;                                                                        \
         }                                                                                             \
     } while (0)

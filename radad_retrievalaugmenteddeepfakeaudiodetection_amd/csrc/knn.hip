@@ -3577,8 +3577,10 @@ static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* glo
         // (a search beyond KNN_F16_MAX_K took no f16 scan: its rejections say nothing about the f16 scans' tuning, which reads
         // batch sizes of >= 64 only -- knn_consume_reports)
         x.nq_report = k <= KNN_F16_MAX_K ? (int)std::min<int64_t>(nq, 0x7fffffff) : 0;
-        const size_t xlds = (size_t)c.xgroup * h->dim * 4 + (size_t)KX_WAVES * c.xgroup * k * 12 + 16;
-        RADAD_REQUIRE(xlds <= KX_LDS_MAX, "radad_knn_search: dim %d x k %d too large for the exact kernel", h->dim, k);
+        // (with the kernel's static arrival flag <= KX_LDS_MAX: every entry point checked knn_exact_fits.  Until the width tests
+        // searched 16380 x 1024 the launch asked for 16 bytes more than the kernel indexes, and the widest rows the limit admits
+        // were refused by hipFuncSetAttribute: 160 KB of dynamic LDS plus the static flag)
+        const size_t xlds = knn_exact_dyn_lds_bytes(h->dim, k);
         RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_exact_scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
         if (nq > h->xarrive_cap) {                       // arrival counters of the query groups (zero between launches)
             RADAD_HIP_CHECK(hipStreamSynchronize(st));
@@ -3633,6 +3635,8 @@ static int knn_search_core(radad_knn_t h, const void* q_in, int q_dtype, int64_t
     RADAD_REQUIRE(h, "NULL handle");
     RADAD_REQUIRE(k >= 1 && k <= RADAD_KNN_MAX_K, "radad_knn_search: k=%d outside [1,%d]", k, RADAD_KNN_MAX_K);
     RADAD_REQUIRE(nq >= 0 && nq < (1ll << 31) - KT_N, "radad_knn_search: bad nq");
+    // (before anything is enqueued: the outputs stay untouched and the handle usable -- knn_exact_fits, knn_plan.h)
+    RADAD_REQUIRE(knn_exact_fits(h->dim, k), "radad_knn_search: dim %d x k %d too large for the exact kernel (dim * 4 + 96 k + 16 <= %zu)", h->dim, k, KX_LDS_MAX);
     if (nq == 0) return RADAD_OK;
     RADAD_REQUIRE(q_in && out_dist_dev && out_idx_dev, "radad_knn_search: NULL buffer");
     std::lock_guard<std::mutex> lk(h->mu);
@@ -3682,8 +3686,8 @@ static int knn_excl_exact_pass(radad_knn_t h, const ExclLayout& L, int64_t nq, i
     x.admit = admit;
     if (r.per_query) { x.row_tags = r.tags; x.q_tags = r.q_tags; x.q_cnt = r.q_cnt; x.m = r.m(); }
     const auto kern = r.per_query ? k_exact_scan_excl_pq : k_exact_scan_excl;
-    const size_t xlds = (size_t)L.xgroup * h->dim * 4 + (size_t)KX_WAVES * L.xgroup * k * 12 + 16;
-    RADAD_REQUIRE(xlds <= KX_LDS_MAX && h->xarrive && nq <= h->xarrive_cap, "radad_knn_search_excl: dim %d x k %d too large for the exact kernel", h->dim, k);
+    const size_t xlds = knn_exact_dyn_lds_bytes(h->dim, k);      // (with the static arrival flag <= KX_LDS_MAX: knn_excl_check_args)
+    RADAD_REQUIRE(h->xarrive && nq <= h->xarrive_cap, "radad_knn_search_excl: the fast pass left no arrival counters for %lld queries", (long long)nq);
     RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
     const unsigned gy = k <= KNN_F16_MAX_K ? KX_GROUPS_Y : 8 * KX_GROUPS_Y;
     x.nslots = (int)L.xslots;
@@ -3767,6 +3771,8 @@ static int knn_excl_check_args(const char* fn, radad_knn_t h, int q_dtype, int64
     RADAD_REQUIRE(q_dtype == RADAD_Q_F32 || q_dtype == RADAD_Q_BF16, "%s: unsupported query dtype %d", fn, q_dtype);
     RADAD_REQUIRE(k >= 1 && k <= RADAD_KNN_MAX_K, "%s: k=%d outside [1,%d]", fn, k, RADAD_KNN_MAX_K);
     RADAD_REQUIRE(k_fetch >= k && k_fetch <= RADAD_KNN_MAX_K, "%s: k_fetch=%d outside [k=%d,%d]", fn, k_fetch, k, RADAD_KNN_MAX_K);
+    // (the fast pass searches at k_fetch >= k, the row-filtered exact pass at k: refused here, before either is enqueued)
+    RADAD_REQUIRE(knn_exact_fits(h->dim, k_fetch), "%s: dim %d x k_fetch %d too large for the exact kernel (dim * 4 + 96 k + 16 <= %zu)", fn, h->dim, k_fetch, KX_LDS_MAX);
     RADAD_REQUIRE(nq >= nq_min && nq < (1ll << 31) - KT_N, "%s: bad nq", fn);
     RADAD_REQUIRE(n_excl >= 0 && (n_excl == 0 || (excl_sorted_dev && row_tags_dev)),
                   "%s: %lld excluded tags need the exclusion set and the row tags", fn, (long long)n_excl);
@@ -3796,6 +3802,7 @@ int radad_knn_search_begin(radad_knn_t h, const void* q_dev, int q_dtype, int64_
     RADAD_REQUIRE(q_dtype == RADAD_Q_F32 || q_dtype == RADAD_Q_BF16, "radad_knn_search_begin: unsupported query dtype %d", q_dtype);
     RADAD_REQUIRE(k >= 1 && k <= RADAD_KNN_MAX_K, "radad_knn_search_begin: k=%d outside [1,%d]", k, RADAD_KNN_MAX_K);
     RADAD_REQUIRE(nq > 0 && nq < (1ll << 31) - KT_N, "radad_knn_search_begin: bad nq");
+    RADAD_REQUIRE(knn_exact_fits(h->dim, k), "radad_knn_search_begin: dim %d x k %d too large for the exact kernel (dim * 4 + 96 k + 16 <= %zu)", h->dim, k, KX_LDS_MAX);
     RADAD_REQUIRE(q_dev && kth_lower_bound_dev, "radad_knn_search_begin: NULL buffer");
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);

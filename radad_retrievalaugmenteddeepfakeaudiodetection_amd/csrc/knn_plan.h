@@ -73,6 +73,19 @@ static int knn_exact_group(int dim, int k) {
                                                      (KX_LDS_MAX - 16) / ((size_t)dim * 4 + (size_t)KX_WAVES * k * 12)));
 }
 
+// LDS of one workgroup of the exact kernel.  Dynamic: the group's fp32 queries and KX_WAVES sorted lists of k (key, id) per query --
+// what the kernel indexes and what a launch asks for.  Static: the kernel's arrival flag, 16 bytes with its alignment.  HIP adds
+// the two and refuses a launch (and hipFuncSetAttribute) whose sum exceeds the 160 KB of a CU.
+static size_t knn_exact_dyn_lds_bytes(int dim, int k) {
+    const size_t group = (size_t)knn_exact_group(dim, k);
+    return group * (size_t)dim * 4 + (size_t)KX_WAVES * group * (size_t)k * 12;
+}
+static size_t knn_exact_lds_bytes(int dim, int k) { return knn_exact_dyn_lds_bytes(dim, k) + 16; }
+// The width x k limit of every flat search (radad_hip.h, radad_knn_create): one query and its lists must fit the LDS of a CU,
+// dim * 4 + 96 k + 16 <= 160 KB -- dim <= 16380 at k = 1024, dim <= 40932 at k = 1.  Any search may need the exact kernel (whether a
+// query is rejected is only known on the device), so the entry points refuse (dim, k) beyond it before anything is enqueued.
+static bool knn_exact_fits(int dim, int k) { return knn_exact_lds_bytes(dim, k) <= KX_LDS_MAX; }
+
 // ---- launch geometry --------------------------------------------------------------------------------------------------------------
 // choose the launch geometry: enough equal splits to put >= 2 workgroups on each of the 256 CUs
 static void knn_geometry(int64_t n, int64_t nq, int* n_qtiles, int* n_splits, int64_t* chunk_rows) {

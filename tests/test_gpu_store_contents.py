@@ -18,7 +18,8 @@ from oracle import synth
 pytestmark = pytest.mark.gpu
 
 BASE = 10 ** 10                     # id_base of the ingest tests: ids beyond 2^32
-DIMS = [4, 12, 64, 100, 252, 256, 260, 1024, 5376]     # nv = dim / 4 below, at and above 64 lanes; 1 to 21 trips of the lane loop
+DIMS = [4, 8, 12, 28, 48, 64, 100, 252, 256, 260, 1024, 5376, 16380]  # nv = dim / 4 below, at and above 64 lanes; 1 to 64 trips of the lane
+                                                                       # loop; 16380: the widest rows a search at k = 1024 takes
 COUNTS = [1, 3, 4, 5, 1025]         # four rows per workgroup: part of one, exactly one, one and a bit, many and a bit
 HEADER = struct.Struct("<8sIiiiq")  # "RADADKNN" | u32 version | i32 dim | i32 metric | i32 store dtype | i64 ntotal
 
