@@ -276,8 +276,9 @@ int radad_filter_topk(const float* in_dist_dev, const int64_t* in_idx_dev, int64
  *               the whole list), or the list is all the store has
  *   exact pass  float64 brute force over the admissible rows for the queries the certificate cannot prove, driven from the device
  *               (no host round trip; an excluded row costs one bit of a per-call bitmap).  It streams the admissible rows once per
- *               group of <= 8 such queries -- far more work per query than the certified search spends on one (its time per listed
- *               query has not been measured yet, profiles/README.md).
+ *               group of <= 8 such queries -- far more work per query than the certified search spends on one (measured where most
+ *               of the store is excluded: 0.051 ms per listed query over 100 000 admissible rows x 512, 3.3 ms for 64 listed
+ *               queries, profiles/README.md; when most of the store is excluded use radad_knn_search_excl_scan below).
  *               So choose k_fetch for the crowding you expect: k + (the most excluded rows that can precede a query's k-th
  *               admissible neighbour), e.g. k + clips per speaker in a batch; up to 128 the fast pass stays on the f16 scans.
  * row_tags_dev [ntotal] int64 indexed by id - id_base; excl_sorted_dev [n_excl] int64 ASCENDING (the caller's contract, not checked);
@@ -374,6 +375,44 @@ int radad_knn_search_excl_pq_begin(radad_knn_t h, const void* q_dev, int q_dtype
                                    const int64_t* row_tags_dev, const int64_t* q_tags_dev, int m, const int32_t* q_tag_counts_dev,
                                    double* out_key_dev /*[nq,k]*/, int64_t* out_idx_dev /*[nq,k]*/, double* frontier_key_dev /*[nq]*/,
                                    int64_t* frontier_idx_dev /*[nq]*/, void* stream);
+
+/* The exclusion-aware search with the admission test INSIDE the certified tile scan: the call for exclusion sets that cover much of the
+ * store (the training_file_ids mode, pipeline.py:500-502), where no k_fetch <= 1024 proves a query and radad_knn_search_excl sends
+ * the whole batch through its exact pass.  The result contract is radad_knn_search_excl's without k_fetch: the k best admissible rows
+ * ordered by (float64 key, lower id), out_dist the key rounded once, id -1 / NaN / NaN where the store has fewer admissible rows.
+ * Two routes, chosen on the host (knn_excl_scan_route, knn_plan.h):
+ *   RADAD_EXCL_SCAN_TILE   exactly when the plain search of this batch would take RADAD_SCAN_HI_TILE (17 or more queries, dim % 64
+ *                 == 0, k <= 128, the plane on, a store large enough for the sample pre-pass -- 16 384 rows at small k --, and the
+ *                 handle not on its fp32 fallback).  A pre-pass on `stream` builds the admission bitmap and a per-call bias array
+ *                 (the plane's bias, or 0, where a row is admitted; NaN where it is not: 12 bytes read and 4 written per row); the
+ *                 scan runs its biased instantiation (RSC 2 / 3; an un-centred IP / cosine store with a zero query constant) with
+ *                 that array.  A NaN score passes no compare of the scan (DESIGN, "exclusion inside the tile scan", names each), so
+ *                 an excluded row is never emitted and never counts towards a floor: the scan costs what the plain scan costs,
+ *                 however much of the store is excluded.  Sample pre-pass, floors, phases, K split and the float64 re-rank are the
+ *                 plain search's; the queries its certificate rejects go, driven from the device, to the ROW-FILTERED float64 exact
+ *                 kernel with the same bitmap.  The handle's own bias arrays are not written.
+ *   RADAD_EXCL_SCAN_EXACT  every other shape (16 or fewer queries, small stores, k > 128, dim % 64 != 0, plane off, fp32 fallback
+ *                 active): the row-filtered float64 exact pass for every query.  Correct everywhere; about two fp32 passes over
+ *                 the store per group of <= 8 queries, so slow for large batches (k > 128 with hundreds of queries: prefer
+ *                 radad_knn_search_excl there when few excluded rows crowd a query).
+ * The call posts no certificate report and leaves radad_knn_tuning_info's three values and the plane's re-decision inputs as it
+ * found them (a batch with few admissible rows overflows its candidate buffers by design and must not push later plain searches to
+ * fp32); it may build the plane, as any first large-batch search does.  radad_knn_last_recheck / _last_certificate keep describing
+ * the last plain search.  Arguments and errors as radad_knn_search_excl: row_tags_dev / excl_sorted_dev (ascending) may be NULL only
+ * when n_excl == 0; RADAD_ESTATE on an empty store; RADAD_EINVAL on a handle with a begun search or beyond the width x k limit,
+ * before anything is enqueued.  Stream-ordered and serialised like every search.
+ * Not offered: per-query sets (a bias is per row, not per (row, query): radad_knn_search_excl_pq); a begin / finish pair (a shard's
+ * result here IS its exact admissible top k: radad_topk_merge_f64 of the shards' lists is exact).
+ * radad_knn_last_excl_scan synchronises with the most recent such call: its batch size (may be NULL), route and the number of
+ * queries the exact kernel answered (all of them on the exact route).  0 / RADAD_EXCL_SCAN_EXACT / 0 before the first one. */
+#define RADAD_EXCL_SCAN_TILE 0
+#define RADAD_EXCL_SCAN_EXACT 1
+int radad_knn_search_excl_scan(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k,
+                               const int64_t* row_tags_dev /*[ntotal], by id - id_base*/,
+                               const int64_t* excl_sorted_dev /*[n_excl] ascending, NULL when n_excl == 0*/, int64_t n_excl,
+                               float* out_dist_dev /*[nq,k]*/, int64_t* out_idx_dev /*[nq,k]*/, double* out_key_dev /*[nq,k] or NULL*/,
+                               void* stream);
+int radad_knn_last_excl_scan(radad_knn_t h, int64_t* n_queries, int* route, int* n_exact);
 
 /* ------------------------------------------------------------------------------------------------
  * Inverted-file flat index: faiss.IndexIVFFlat(IndexFlatL2 quantiser, d, nlist, METRIC_L2), the reference's optional

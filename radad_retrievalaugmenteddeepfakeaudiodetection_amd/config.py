@@ -70,6 +70,7 @@ class Config:
         # retrieval with exclusions (retrieve_similar_vectors): False = the reference's search K + 10, drop, pad (pipeline.py:478,491-515)
         self.exact_exclusion = False        # True: the K nearest rows that are not excluded, exactly (flat stores)
         self.exclusion_k_fetch = None       # ... size of the certified search in front of the exact pass (None = top_k + 10)
+        self.exclusion_in_scan = False      # True (with exact_exclusion, scope "batch", flat stores): the admission test inside the certified tile scan -- for exclusion sets that cover most of the store (training_file_ids); no k_fetch
         self.exclusion_scope = "batch"      # "query" (needs exact_exclusion, or ivf_exact_exclusion on an IVF store): clip i excludes its OWN basename only, so what it retrieves does not depend on its batch
         self.ivf_exact_exclusion = False    # True, IVF stores: the same among the rows of the probed lists (exclusion inside the list scans; top_k <= 26)
 

@@ -2640,6 +2640,8 @@ struct radad_knn_s {
     void* excl_ws = nullptr;
     size_t excl_ws_bytes = 0, excl_o_count = 0;
     int64_t last_excl_nq = 0;    // batch size of the most recent exclusion-aware search (radad_knn_last_excl)
+    int64_t last_xs_nq = 0;      // radad_knn_search_excl_scan: batch size and route of the most recent one (radad_knn_last_excl_scan; its
+    int last_xs_route = RADAD_EXCL_SCAN_EXACT;      // count of exactly answered queries is copied to host_count[17] behind it)
     double* rs_key = nullptr;    // k_refine_small: [SQ_NQ][KNN_CERT_CAP] float64 keys of the candidates, where the query's workgroups meet
     int* rs_count = nullptr;     // ... and [SQ_NQ] arrival counters (zero between launches)
     int uniform_e = HI_E_PER_ROW; // one power-of-two scale 2^e for every row of the plane (rows of one magnitude), or HI_E_PER_ROW
@@ -3261,7 +3263,9 @@ static auto knn_hi_kernel(int rsc, bool sample) -> void (*)(KnnHiParams) {
     }
 }
 
-static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, hipStream_t st) {
+// row_bias: the bias array of a biased plan (p.biased), or NULL = the handle's own (radad_knn_search_excl_scan hands in its per-call
+// array: NaN for the rows it excludes)
+static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, hipStream_t st, const float* row_bias = nullptr) {
     const int64_t nq = p.nq;
     float* ps = ws_at<float>(h, L.ps);
     int* pi = ws_at<int>(h, L.pi);
@@ -3272,7 +3276,7 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
     wp.rscale = h->f16 ? nullptr : h->rscale;
     wp.uscale = h->f16 ? 1.0f : (h->uniform_e != HI_E_PER_ROW ? ldexpf(1.0f, -h->uniform_e) : (h->metric == RADAD_METRIC_COSINE ? 0x1p-14f : 1.0f));
     // bias of the scale + bias variant: a centred plane has its own (|y - mu|^2 or mu.y); un-centred L2 uses |y|^2 as stored
-    wp.rbias = p.mu ? h->rbias : h->ynorm; wp.bias_sign = p.l2 ? -1.f : 1.f; wp.mult = p.l2 ? 2.f : 1.f;
+    wp.rbias = row_bias ? row_bias : (p.mu ? h->rbias : h->ynorm); wp.bias_sign = p.l2 ? -1.f : 1.f; wp.mult = p.l2 ? 2.f : 1.f;
     wp.qconst = p.biased ? ws_at<float>(h, L.qconst) : nullptr;
     wp.q = ws_at<_Float16>(h, L.qh); wp.qscale = ws_at<float>(h, L.qscale);
     wp.n = h->ntotal; wp.nq = (int)nq; wp.row_bytes = h->dim * 2; wp.l2 = p.l2;
@@ -3441,13 +3445,8 @@ static void knn_report_lower_bounds(radad_knn_t h, const ScanPlan& p, const Sear
     }
 }
 
-static int knn_search_phase1(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int margin, float* lb_out, hipStream_t st,
-                             SearchCtx* ctx) {
-    // one workspace per handle: a search on another stream waits for the previous one (threads are serialised by h->mu,
-    // the device work by this event)
-    // (searches share the handle's workspace.  On ONE stream they are ordered anyway; a search on another stream than the last one
-    // first records an event behind whatever that stream holds and waits for it -- recording one behind EVERY search, as until round 4,
-    // held the kernel after each search back ~6 us, 5 % of an online search)
+// a search on another stream than the last one waits for it; from here on `st` is where the handle's workspace is in use
+static int knn_order_behind_last(radad_knn_t h, hipStream_t st) {
     if (h->have_last && !h->owned_serial && st != h->last_stream) {
         if (hipEventRecord(h->ev_done, h->last_stream) == hipSuccess) RADAD_HIP_CHECK(hipStreamWaitEvent(st, h->ev_done, 0));
         else { (void)hipGetLastError(); RADAD_HIP_CHECK(hipDeviceSynchronize()); }      // (that stream no longer exists)
@@ -3457,6 +3456,18 @@ static int knn_search_phase1(radad_knn_t h, const void* q_in, int q_dtype, int64
     // of phase 2: a search on another stream after an aborted one shared the workspace with kernels still running)
     h->last_stream = st;
     h->have_last = true;
+    return RADAD_OK;
+}
+
+static int knn_search_phase1(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, int margin, float* lb_out, hipStream_t st,
+                             SearchCtx* ctx) {
+    // one workspace per handle: a search on another stream waits for the previous one (threads are serialised by h->mu,
+    // the device work by this event)
+    // (searches share the handle's workspace.  On ONE stream they are ordered anyway; a search on another stream than the last one
+    // first records an event behind whatever that stream holds and waits for it -- recording one behind EVERY search, as until round 4,
+    // held the kernel after each search back ~6 us, 5 % of an online search)
+    int rc = knn_order_behind_last(h, st);
+    if (rc) return rc;
 
     h->prof.next_search();
     knn_consume_reports(h);
@@ -3465,7 +3476,7 @@ static int knn_search_phase1(radad_knn_t h, const void* q_in, int q_dtype, int64
     if (getenv("RADAD_DEBUG_KNN")) h->tune.clear_skip();    // timing ablations (wrong results, every query rejected): stay on the kernel under test
 #endif
     ScanPlan p;
-    int rc = knn_plan_scan(h, nq, k, margin, st, &p);
+    rc = knn_plan_scan(h, nq, k, margin, st, &p);
     if (rc) return rc;
     const SearchLayout L = knn_search_layout(knn_store_facts(h), p, q_dtype);
     if (L.bytes > h->ws_bytes) {
@@ -3503,14 +3514,13 @@ static int knn_search_phase1(radad_knn_t h, const void* q_in, int q_dtype, int64
     return RADAD_OK;
 }
 
-constexpr int RADAD_RETRY_INTERNAL = 1;      // knn_search_phase2 -> knn_search_core: retuned after a mass rejection, run the search again
-static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* global_lb, bool may_retry, float* out_dist_dev, int64_t* out_idx_dev,
-                             double* out_key_dev, hipStream_t st) {
+// ---- float64 re-rank + certificate of what phase 1 listed: results of every query, the rejected ones in flag_sel[0, *flag_count) ----
+static int knn_rerank(radad_knn_t h, const SearchCtx& c, const float* global_lb, float* out_dist_dev, int64_t* out_idx_dev,
+                      double* out_key_dev, hipStream_t st) {
     int* flag_count = ws_at<int>(h, c.ws.fcount);
     int* flag_sel = ws_at<int>(h, c.ws.fsel);
     const int64_t nq = c.nq;
     const int k = c.k;
-    // ---- float64 re-rank + certificate ----------------------------------------------------------------------------
     RefineParams m;
     m.score = ws_at<const float>(h, c.ws.ps); m.idx = ws_at<const int>(h, c.ws.pi); m.n_parts = c.n_parts; m.k = k; m.dim = h->dim; m.l2 = c.l2; m.nq = nq;
     m.part_len = c.plen; m.cap = c.cap;
@@ -3556,6 +3566,36 @@ static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* glo
             hipLaunchKernelGGL(k_merge_refine<false>, dim3((unsigned)nq), dim3(RF_THREADS), refine_lds_bytes(c.cap), st, m);
     }
     RADAD_HIP_CHECK(hipGetLastError());
+    return RADAD_OK;
+}
+
+// arrival counters of the exact kernels' query groups (zero between launches), room for nq of them
+static int knn_ensure_xarrive(radad_knn_t h, int64_t nq, hipStream_t st) {
+    if (nq <= h->xarrive_cap) return RADAD_OK;
+    RADAD_HIP_CHECK(hipStreamSynchronize(st));
+    if (h->xarrive) (void)hipFree(h->xarrive);
+    h->xarrive = nullptr; h->xarrive_cap = 0;
+    const int64_t cap = nq + nq / 2 + 64;
+    if (hipMalloc((void**)&h->xarrive, (size_t)cap * sizeof(int)) != hipSuccess || hipMemset(h->xarrive, 0, (size_t)cap * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError();
+        if (h->xarrive) (void)hipFree(h->xarrive);
+        h->xarrive = nullptr;
+        radad_set_error("hipMalloc of the exact pass's arrival counters failed");
+        return RADAD_ENOMEM;
+    }
+    h->xarrive_cap = cap;
+    return RADAD_OK;
+}
+
+constexpr int RADAD_RETRY_INTERNAL = 1;      // knn_search_phase2 -> knn_search_core: retuned after a mass rejection, run the search again
+static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* global_lb, bool may_retry, float* out_dist_dev, int64_t* out_idx_dev,
+                             double* out_key_dev, hipStream_t st) {
+    int* flag_count = ws_at<int>(h, c.ws.fcount);
+    int* flag_sel = ws_at<int>(h, c.ws.fsel);
+    const int64_t nq = c.nq;
+    const int k = c.k;
+    int rc = knn_rerank(h, c, global_lb, out_dist_dev, out_idx_dev, out_key_dev, st);
+    if (rc) return rc;
 
     // ---- look before the exact pass (see KnnTuning) ------------------------------------------------------------------------------
     if (h->tune.looks_before_exact(c.hi_tile, nq, h->ntotal, h->dim)) {
@@ -3582,20 +3622,8 @@ static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* glo
         // were refused by hipFuncSetAttribute: 160 KB of dynamic LDS plus the static flag)
         const size_t xlds = knn_exact_dyn_lds_bytes(h->dim, k);
         RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_exact_scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
-        if (nq > h->xarrive_cap) {                       // arrival counters of the query groups (zero between launches)
-            RADAD_HIP_CHECK(hipStreamSynchronize(st));
-            if (h->xarrive) (void)hipFree(h->xarrive);
-            h->xarrive = nullptr; h->xarrive_cap = 0;
-            const int64_t cap = nq + nq / 2 + 64;
-            if (hipMalloc((void**)&h->xarrive, (size_t)cap * sizeof(int)) != hipSuccess || hipMemset(h->xarrive, 0, (size_t)cap * sizeof(int)) != hipSuccess) {
-                (void)hipGetLastError();
-                if (h->xarrive) (void)hipFree(h->xarrive);
-                h->xarrive = nullptr;
-                radad_set_error("hipMalloc of the exact pass's arrival counters failed");
-                return RADAD_ENOMEM;
-            }
-            h->xarrive_cap = cap;
-        }
+        rc = knn_ensure_xarrive(h, nq, st);
+        if (rc) return rc;
         x.arrive = h->xarrive;
         // (k beyond KNN_F16_MAX_K: groups of one or two queries, each a long insert and merge -- more of them in flight; the
         // geometry of k <= 128 is the measured one)
@@ -3795,6 +3823,126 @@ static int knn_excl_pq_rule(const char* fn, const int64_t* row_tags_dev, const i
     return RADAD_OK;
 }
 
+// ---- exclusion inside the certified tile scan (radad_knn_search_excl_scan) ----------------------------------------------------------
+// The per-call bias array of the tile route: the plane's bias (NULL = none: an un-centred IP / cosine plane, an fp16 store) where the
+// bitmap admits the row, NaN where it does not.  The scan starts a row's accumulators at its bias: a NaN start makes every score of
+// the row NaN, and no compare of the scan passes a NaN (DESIGN, "exclusion inside the tile scan", names each of them).
+__global__ __launch_bounds__(256) void k_excl_scan_bias(const unsigned long long* __restrict__ admit, const float* __restrict__ bias,
+                                                        int64_t n, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const bool ok = (admit[i >> 6] >> (i & 63)) & 1ull;
+    out[i] = ok ? (bias ? bias[i] : 0.f) : __int_as_float(0x7fc00000);
+}
+// the exact route: every query of the batch is listed for the row-filtered exact kernel
+__global__ __launch_bounds__(256) void k_excl_scan_list_all(int* __restrict__ sel, int* __restrict__ count, int64_t nq) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < nq) sel[i] = (int)i;
+    if (i == 0) *count = (int)nq;
+}
+// this family's padding where the re-rank left id -1 with +-inf (fewer admissible rows than k, all of them listed): NaN / NaN
+__global__ __launch_bounds__(256) void k_excl_scan_pad(float* __restrict__ dist, const int64_t* __restrict__ idx, double* __restrict__ key, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n && idx[i] < 0) {
+        dist[i] = __int_as_float(0x7fc00000);
+        if (key) key[i] = (double)__int_as_float(0x7fc00000);
+    }
+}
+
+// One call, two routes (knn_excl_scan_route).  Neither consumes a certificate report, takes a turn off the tuning state, looks before
+// its exact pass or posts a report: KnnTuning is read (hi_skip) and otherwise left as it was found.
+static int knn_search_excl_scan_locked(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, const ExclRule& r,
+                                       float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, hipStream_t st) {
+    int rc = knn_order_behind_last(h, st);
+    if (rc) return rc;
+    const TileEligibility t = knn_tile_eligibility(knn_store_facts(h), nq, k, KNN_MARGIN);
+    bool tile = knn_excl_scan_route(knn_store_facts(h), nq, k, h->tune.hi_skip) == RADAD_EXCL_SCAN_TILE;
+    if (tile) tile = knn_ensure_hi(h, st, true);                   // (a plane that cannot be allocated switches itself off: exact route)
+    if (!tile && !knn_ensure_hi(h, st, false)) { radad_set_error("store statistics could not be computed"); return RADAD_EHIP; }
+    // the plan of the plain search, with the biased instantiation whatever the plane: RSC 0 / 1 run as RSC 3 / 2 with a zero bias for
+    // the admitted rows and a zero query constant (k_hi_rows writes mu.q' + |mu|^2 = 0 without a centre)
+    ScanPlan p = knn_finish_plan(knn_store_facts(h), nq, k, KNN_MARGIN, t, tile, false);
+    p.mu = (p.hi_q && !h->f16) ? h->cmu : nullptr;
+    p.biased = p.hi_q;
+    const SearchLayout L = knn_search_layout(knn_store_facts(h), p, q_dtype);
+    if (L.bytes > h->ws_bytes) {
+        RADAD_HIP_CHECK(hipDeviceSynchronize());
+        rc = knn_workspace(h, L.bytes);
+        if (rc) return rc;
+    }
+    const int route = tile ? RADAD_EXCL_SCAN_TILE : RADAD_EXCL_SCAN_EXACT;
+    const ExclScanLayout X = knn_excl_scan_layout(knn_store_facts(h), route);
+    rc = knn_excl_reserve(h, X.bytes);
+    if (rc) return rc;
+    rc = knn_ensure_xarrive(h, nq, st);
+    if (rc) return rc;
+    h->last_emit_nq = 0;                                           // (the workspace no longer holds the last plain tile scan's counters)
+    h->last_xs_nq = 0;
+
+    // ---- pre-pass: admission bitmap (all ones when nothing is excluded: the tags may be NULL then) -----------------------------------
+    unsigned long long* admit = reinterpret_cast<unsigned long long*>((char*)h->excl_ws + X.admit);
+    if (r.n_excl > 0)
+        hipLaunchKernelGGL(k_admit_bitmap<false>, dim3((unsigned)ceil_div64(X.n_words * 64, 256)), dim3(256), 0, st, r.tags,
+                           (const int64_t*)nullptr, h->ntotal, r.excl, r.n_excl, (const int*)nullptr, admit, X.n_words);
+    else
+        RADAD_HIP_CHECK(hipMemsetAsync(admit, 0xff, (size_t)X.n_words * sizeof(unsigned long long), st));
+    const float* q_use = knn_prepare_queries(h, p, L, q_in, q_dtype, st);      // (clears the listed-query counter and the candidate counters)
+    RADAD_HIP_CHECK(hipGetLastError());
+    int* flag_count = ws_at<int>(h, L.fcount);
+    int* flag_sel = ws_at<int>(h, L.fsel);
+
+    if (tile) {
+        // ... and the bias array; then the plain search's scan, re-rank and certificate over the admitted rows
+        float* bias = reinterpret_cast<float*>((char*)h->excl_ws + X.bias);
+        hipLaunchKernelGGL(k_excl_scan_bias, dim3((unsigned)ceil_div64(h->ntotal, 256)), dim3(256), 0, st, (const unsigned long long*)admit,
+                           (const float*)(p.mu ? h->rbias : (p.l2 ? h->ynorm : nullptr)), h->ntotal, bias);
+        RADAD_HIP_CHECK(hipGetLastError());
+        h->prof.next_search();
+        rc = knn_scan_hi_tile(h, p, L, st, bias);
+        if (rc) return rc;
+        RADAD_HIP_CHECK(hipGetLastError());
+        SearchCtx c;
+        c.valid = true;
+        c.nq = nq; c.k = k; c.l2 = p.l2; c.n_parts = p.n_parts; c.plen = p.plen; c.cap = p.cap; c.xgroup = p.xgroup;
+        c.emit = true; c.use_floor = true; c.hi_tile = true; c.canonical = true; c.q_use = q_use; c.ws = L;
+        h->last_o_cnt = L.cnt; h->last_o_thr = L.thr; h->last_emit_nq = nq;
+        rc = knn_rerank(h, c, nullptr, out_dist_dev, out_idx_dev, out_key_dev, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_excl_scan_pad, dim3((unsigned)ceil_div64(nq * k, 256)), dim3(256), 0, st, out_dist_dev, (const int64_t*)out_idx_dev,
+                           out_key_dev, nq * k);
+    } else {
+        hipLaunchKernelGGL(k_excl_scan_list_all, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, st, flag_sel, flag_count, nq);
+    }
+    RADAD_HIP_CHECK(hipGetLastError());
+
+    // ---- the listed queries (tile route: the ones the certificate rejected): the ROW-FILTERED float64 exact kernel, sized and driven
+    // by the device-side count.  No report: host_stats stays NULL.
+    {
+        ExactParams x;
+        x.db = h->rows; x.db_f16 = h->f16; x.q = q_use; x.sel = flag_sel; x.count = flag_count;
+        x.n = h->ntotal; x.dim = h->dim; x.k = k; x.l2 = p.l2; x.group = p.xgroup;
+        x.slice_rows = ceil_div64(h->ntotal, KX_SLICES);
+        x.pkey = ws_at<double>(h, L.xk); x.pidx = ws_at<int>(h, L.xi); x.id_base = h->id_base;
+        x.out_dist = out_dist_dev; x.out_idx = out_idx_dev; x.out_key = out_key_dev;
+        x.host_stats = nullptr;
+        x.arrive = h->xarrive;
+        x.admit = admit;
+        const size_t xlds = knn_exact_dyn_lds_bytes(h->dim, k);
+        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_exact_scan_excl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
+        const unsigned gy = k <= KNN_F16_MAX_K ? KX_GROUPS_Y : 8 * KX_GROUPS_Y;
+        x.nslots = (int)knn_exact_slots(nq, k, p.xgroup);
+        for (int64_t s0 = 0; s0 < nq; s0 += x.nslots) {            // (launches past the device-side count leave at once)
+            x.slot0 = (int)s0;
+            hipLaunchKernelGGL(k_exact_scan_excl, dim3(KX_SLICES, gy), dim3(KX_THREADS), xlds, st, x);
+        }
+        RADAD_HIP_CHECK(hipGetLastError());
+    }
+    // how many queries the exact kernel answered, for radad_knn_last_excl_scan (pinned memory: no synchronisation here)
+    RADAD_HIP_CHECK(hipMemcpyAsync(h->host_count + 17, flag_count, sizeof(int), hipMemcpyDeviceToHost, st));
+    h->last_xs_nq = nq; h->last_xs_route = route;
+    return RADAD_OK;
+}
+
 extern "C" {
 
 int radad_knn_search_begin(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, float* kth_lower_bound_dev, void* stream) {
@@ -3866,6 +4014,32 @@ int radad_knn_search_excl_pq(radad_knn_t h, const void* q_dev, int q_dtype, int6
     RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_search_excl_pq: a radad_knn_search_begin on this handle has not been finished");
     if (h->ntotal == 0) { radad_set_error("radad_knn_search_excl_pq: the store is empty"); return RADAD_ESTATE; }
     return knn_search_excl_locked(h, q_dev, q_dtype, nq, k, k_fetch, r, out_dist_dev, out_idx_dev, out_key_dev, (hipStream_t)stream);
+}
+
+int radad_knn_search_excl_scan(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, const int64_t* row_tags_dev,
+                               const int64_t* excl_sorted_dev, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
+                               void* stream) {
+    const int bad = knn_excl_check_args("radad_knn_search_excl_scan", h, q_dtype, nq, 0, k, k, row_tags_dev, excl_sorted_dev, n_excl);
+    if (bad) return bad;
+    if (nq == 0) return RADAD_OK;
+    RADAD_REQUIRE(q_dev && out_dist_dev && out_idx_dev, "radad_knn_search_excl_scan: NULL buffer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_search_excl_scan: a radad_knn_search_begin on this handle has not been finished");
+    if (h->ntotal == 0) { radad_set_error("radad_knn_search_excl_scan: the store is empty"); return RADAD_ESTATE; }
+    return knn_search_excl_scan_locked(h, q_dev, q_dtype, nq, k, knn_excl_rule_batch(row_tags_dev, excl_sorted_dev, n_excl), out_dist_dev,
+                                       out_idx_dev, out_key_dev, (hipStream_t)stream);
+}
+
+int radad_knn_last_excl_scan(radad_knn_t h, int64_t* n_queries, int* route, int* n_exact) {
+    RADAD_REQUIRE(h && route && n_exact, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    RADAD_HIP_CHECK(knn_wait_last_search(h));
+    *n_exact = h->last_xs_nq > 0 ? *reinterpret_cast<volatile int*>(h->host_count + 17) : 0;
+    *route = h->last_xs_route;
+    if (n_queries) *n_queries = h->last_xs_nq;
+    return RADAD_OK;
 }
 
 int radad_knn_last_excl(radad_knn_t h, int64_t* n_queries, int* n_exact) {

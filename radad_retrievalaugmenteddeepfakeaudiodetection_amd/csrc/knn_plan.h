@@ -414,6 +414,30 @@ static ExclLayout knn_excl_layout(const StoreFacts& s, int64_t nq, int k, int k_
     return L;
 }
 
+// ---- exclusion inside the certified tile scan (radad_knn_search_excl_scan) --------------------------------------------------------
+// Which route a batch takes: the tile scan with the per-call bias array exactly when the plain search of this batch would take
+// RADAD_SCAN_HI_TILE -- knn_tile_eligibility at the user searches' margin, and the tuning state not on its fp32 fallback
+// (`fp32_searches_left`, KnnTuning::hi_skip: read, never counted down here) -- else the row-filtered float64 exact pass for every
+// query.  (A plane that cannot be allocated sends the batch to the exact route as well: knn.hip.)
+static int knn_excl_scan_route(const StoreFacts& s, int64_t nq, int k, int fp32_searches_left) {
+    return (fp32_searches_left == 0 && knn_tile_eligibility(s, nq, k, KNN_MARGIN).eligible) ? RADAD_EXCL_SCAN_TILE : RADAD_EXCL_SCAN_EXACT;
+}
+
+// byte offsets in the handle's exclusion workspace: the admission bitmap (one bit per row), and on the tile route the per-call bias
+// array (one float per row: the plane's bias or 0 where the row is admitted, NaN where it is not)
+struct ExclScanLayout {
+    size_t admit = 0, bias = 0, bytes = 0;
+    int64_t n_words = 0;
+};
+static ExclScanLayout knn_excl_scan_layout(const StoreFacts& s, int route) {
+    ExclScanLayout L;
+    L.n_words = ceil_div64(s.ntotal, 64);
+    L.admit = 0;
+    L.bias = al256((size_t)L.n_words * sizeof(unsigned long long));
+    L.bytes = L.bias + (route == RADAD_EXCL_SCAN_TILE ? al256((size_t)s.ntotal * sizeof(float)) : 0);
+    return L;
+}
+
 // ---- adaptive tuning --------------------------------------------------------------------------------------------------------------
 // What a handle does when the certificate rejects more than a quarter of a batch of >= 64 queries: re-decide the plane if rows were
 // appended since it was decided, else widen the candidate buffers once (cap_boost 1 -> 4), else leave the certified f16 kernels for

@@ -139,6 +139,13 @@ class HotPathPipeline:
         if per_query and not exact_excl and not ivf_excl:
             raise ValueError("config.exclusion_scope 'query' needs config.exact_exclusion (flat stores) or config.ivf_exact_exclusion (IVF "
                              "stores): the over-fetch-and-drop path excludes the batch's union")
+        # config.exclusion_in_scan (opt-in, with exact_exclusion, scope "batch", a flat store): the admission test inside the certified
+        # tile scan (VectorDatabase.search_excluding_in_scan) -- for exclusion sets that cover most of the store (training_file_ids,
+        # pipeline.py:500-502), where no over-fetch proves a query
+        in_scan = bool(getattr(self.config, "exclusion_in_scan", False)) and exact_excl
+        if in_scan and per_query:
+            raise ValueError("config.exclusion_in_scan excludes one set for the batch (a bias is per row, not per (row, query)): "
+                             "config.exclusion_scope 'query' takes search_excluding_per_query, without exclusion_in_scan")
         if per_query and query_paths is None:
             raise ValueError("config.exclusion_scope 'query' needs query_paths: a query excludes its own basename")
         if per_query and len(query_paths) != B:
@@ -169,6 +176,8 @@ class HotPathPipeline:
             elif per_query:
                 k_fetch = getattr(self.config, "exclusion_k_fetch", K + 10)
                 dist_t, chosen_t = self.vector_db.search_excluding_per_query(q, K, own, k_fetch=K + 10 if k_fetch is None else int(k_fetch))
+            elif in_scan:
+                dist_t, chosen_t = self.vector_db.search_excluding_in_scan(q, K, excl)
             else:
                 k_fetch = getattr(self.config, "exclusion_k_fetch", K + 10)
                 dist_t, chosen_t = self.vector_db.search_excluding(q, K, excl, k_fetch=K + 10 if k_fetch is None else int(k_fetch))

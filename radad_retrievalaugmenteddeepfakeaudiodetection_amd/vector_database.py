@@ -290,6 +290,30 @@ class HipFlatIndex:
         _lib.check(self._lib.radad_knn_last_excl(self._h, C.byref(nq), C.byref(ex)), "radad_knn_last_excl")
         return {"queries": nq.value, "exact": ex.value}
 
+    def search_excluding_in_scan(self, q, k: int, row_tags, exclude_tags, return_f64: bool = False):
+        """search_excluding's result without a k_fetch (radad_knn_search_excl_scan): the admission test sits inside the certified tile
+        scan, so the cost does not depend on how much of the store is excluded -- the call for exclusion sets that cover most of it
+        (the reference's training_file_ids mode, pipeline.py:500-502).  Arguments and outputs as search_excluding.  Batches the
+        plain search would not give to the tile scan (<= 16 queries, small stores, k > 128, dim % 64 != 0) take the row-filtered
+        float64 pass for every query: last_excl_scan()["route"]."""
+        import torch
+        q, q_dtype = _prep_queries(q, self.d)
+        k = int(k)
+        row_tags, exclude_tags, n_excl = _prep_tags(row_tags, exclude_tags, self.ntotal)
+        D, I, K64 = _alloc_out(q, max(k, 0), return_f64)
+        with torch.cuda.device(q.device):
+            _lib.check(self._lib.radad_knn_search_excl_scan(self._h, q.data_ptr(), q_dtype, q.shape[0], k, _ptr(row_tags),
+                                                            _ptr(exclude_tags), n_excl, D.data_ptr(), I.data_ptr(), _ptr(K64),
+                                                            _lib.stream_ptr(q.device)), "radad_knn_search_excl_scan")
+        return (D, I, K64) if return_f64 else (D, I)
+
+    def last_excl_scan(self):
+        """{"queries", "route", "exact"} of the most recent search_excluding_in_scan: its batch size, "tile" or "exact", and how many
+        of its queries the exact float64 kernel answered (radad_knn_last_excl_scan; synchronises with that search)"""
+        nq, route, ex = C.c_int64(), C.c_int(), C.c_int()
+        _lib.check(self._lib.radad_knn_last_excl_scan(self._h, C.byref(nq), C.byref(route), C.byref(ex)), "radad_knn_last_excl_scan")
+        return {"queries": nq.value, "route": "tile" if route.value == _lib.EXCL_SCAN_TILE else "exact", "exact": ex.value}
+
     def search_excluding_begin(self, q, k: int, row_tags, exclude_tags, k_fetch=None):
         """first half of search_excluding over a ROW SHARD (radad_knn_search_excl_begin; sharded.ShardedSearch.search_excluding): the
         certified search at k_fetch on this shard and the compaction -> (K64 f64 [nq,k], I i64 [nq,k], FK f64 [nq], FI i64 [nq]): the
@@ -676,7 +700,11 @@ class HipIVFFlatIndex:
         raise ValueError("search_excluding_per_query is the flat store's search: an IVF search sees the probed lists, not the store "
                          "(search_probed_excluding_per_query takes one set per query, search_probed_excluding one for the batch)")
 
-    MAX_K_PROBED = 26   # csrc/ivf.inc: the largest k the list scans hold (k + 6 <= 32 entries per (query, list))
+    def search_excluding_in_scan(self, *args, **kwargs):
+        raise ValueError("search_excluding_in_scan is the flat store's search: an IVF index has the admission test inside its own list "
+                         "scans (search_probed_excluding)")
+
+    MAX_K_PROBED = 26  # csrc/ivf.inc: the largest k the list scans hold (k + 6 <= 32 entries per (query, list))
 
     def search_probed_excluding(self, q, k: int, row_tags, exclude_tags):
         """The k nearest rows of the nprobe probed lists whose tag is not excluded, exactly (radad_ivf_search_excl: the admission test
@@ -943,6 +971,18 @@ class VectorDatabase:
         if k <= 0:
             return self._no_hits(q)
         return self.index.search_excluding(q, k, tags, excl, k_fetch=min(k_fetch, _lib.KNN_MAX_K))
+
+    def search_excluding_in_scan(self, query_vectors, k: int = None, exclude_tags=None):
+        """search_excluding's result with the admission test inside the certified tile scan (HipFlatIndex.search_excluding_in_scan): no
+        k_fetch, and a cost that does not depend on how much of the store is excluded -- the call when `exclude_tags` covers most of
+        it (training_file_ids, pipeline.py:500-502).  Arguments and outputs as search_excluding.  Flat stores only: an IVF store has
+        search_probed_excluding, a row-sharded one merges its shards' results."""
+        q, k, _, tags, excl = self._excluding_args(
+            HipFlatIndex, "search_excluding_in_scan is flat and single-handle only (vector_db_index_type 'L2' or 'IP'); an IVF store has "
+            "search_probed_excluding", query_vectors, k, exclude_tags)
+        if k <= 0:
+            return self._no_hits(q)
+        return self.index.search_excluding_in_scan(q, k, tags, excl)
 
     def search_excluding_per_query(self, query_vectors, k: int = None, query_tags=None, query_tag_counts=None, k_fetch=None):
         """search_excluding with one exclusion set PER QUERY (HipFlatIndex.search_excluding_per_query; leave-one-out): query i excludes
