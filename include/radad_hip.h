@@ -95,6 +95,9 @@ int radad_knn_create_ex(int dim, int metric, int store_dtype, int device, int64_
  *   RADAD_KNN_OPT_WIDE_MIN_Q smallest batch that takes the 256-query tile scan instead of the streaming kernels (default 17)
  *   RADAD_KNN_OPT_DENSE      1 (default) / 0: an fp32 store of <= 6144 rows (<= 16384 for <= 16 queries) is searched by writing out every
  *                            score and selecting on them / by the register-list kernels
+ *   RADAD_KNN_OPT_ABANDON    1 (default) / 0: the certified tile scan leaves a 256 x 256 tile after its first K stages when no score
+ *                            of it can still reach its query's admission floor (it pays on stores whose k-th neighbour stands clear
+ *                            of the bulk of the rows; where it cannot, a scalar gate keeps the test from running) / it never does
  * The environment variables RADAD_KNN_HI, RADAD_KNN_CENTRE, RADAD_KNN_SMALLQ_HI, RADAD_WIDE_MIN_Q override the DEFAULTS of handles
  * created while they are set (announced once per process on stderr); the product path never needs them. */
 #define RADAD_KNN_OPT_HI_PLANE 0
@@ -102,6 +105,7 @@ int radad_knn_create_ex(int dim, int metric, int store_dtype, int device, int64_
 #define RADAD_KNN_OPT_SMALLQ_HI 2
 #define RADAD_KNN_OPT_WIDE_MIN_Q 3
 #define RADAD_KNN_OPT_DENSE 4
+#define RADAD_KNN_OPT_ABANDON 5
 int radad_knn_set_option(radad_knn_t h, int option, int value);
 int radad_knn_destroy(radad_knn_t h);
 int radad_knn_dim(radad_knn_t h, int* dim);
@@ -209,6 +213,10 @@ int radad_knn_last_scan_phases(radad_knn_t h, int* n_phases);
  * candidates the scan emitted (more than the candidate buffer holds -- 1024, 4096 after the handle widened them -- rejects the query)
  * and, optionally, the admission floor the scan ended with.  Host pointers. */
 int radad_knn_last_emitted(radad_knn_t h, int* counts_host, float* floors_host, int64_t nq);
+/* Early abandon of the last search (synchronises with it): of the `tasks` (query tile, row tile) pairs its abandoning scan launches
+ * covered, how many ran the test (`checked`: the gate let them) and how many were left after it (`skipped`).  All three are 0 when
+ * no launch of the last search took the abandoning scan. */
+int radad_knn_last_abandon(radad_knn_t h, int64_t* checked, int64_t* skipped, int64_t* tasks);
 /* the f16 plane the certified scans read, once a search has built it: built (0/1); centred = the common component (column mean)
  * of the rows is subtracted before rounding (stores of embeddings that share most of their mean); one_scale = one power-of-two
  * scale for all rows (rows of one magnitude: the scan applies no per-score arithmetic) */

@@ -2645,6 +2645,19 @@ struct radad_knn_s {
     double* rs_key = nullptr;    // k_refine_small: [SQ_NQ][KNN_CERT_CAP] float64 keys of the candidates, where the query's workgroups meet
     int* rs_count = nullptr;     // ... and [SQ_NQ] arrival counters (zero between launches)
     int uniform_e = HI_E_PER_ROW; // one power-of-two scale 2^e for every row of the plane (rows of one magnitude), or HI_E_PER_ROW
+    // early abandon of scan tiles (knn_hi.inc, ABANDON; knn_plan.h): the store's suffix norms per aligned KW_M-row tile, kept with the
+    // rows the statistics kernel has seen -- built with the plane, extended by appends (only the tiles touched: an atomic max, which an
+    // append can only raise), started over whenever the statistics start over (a new plane, a loaded snapshot)
+    int opt_abandon = 1;         // RADAD_KNN_OPT_ABANDON
+    float* tile_ry = nullptr;    // [2][tile_ry_cap]: per tile the largest suffix norm, then the largest accumulator start (bias_sign x bias)
+    int64_t tile_ry_cap = 0;     // tiles
+    int64_t ab_rows = 0;         // rows [0, ab_rows) are in tile_ry ...
+    int ab_from = 0;             // ... as norms from this element on
+    void* ab_ws = nullptr;       // a search's per-query terms (AbandonLayout)
+    size_t ab_ws_bytes = 0;
+    bool ab_search_ready = false;// this search's per-query terms are written (knn_prepare_queries decides, once; the scan reads it)
+    size_t last_o_ab = 0;        // the last search's abandon counters in the workspace, and the tile tasks of its abandoning launches
+    int64_t last_ab_tasks = -1;  // (-1: no search yet)
     // queries the certificate rejected in the most recent search: counted on the device, copied to pinned host memory
     // behind the search (no synchronisation inside search); feeds the adaptive tuning and radad_knn_last_recheck
     int* host_count = nullptr;   // pinned [2][8]: rejected queries, sum of candidates, rejections by reason x 4, [6] the report's stamp, [7] its batch size
@@ -2786,6 +2799,7 @@ static void knn_drop_plane(radad_knn_t h) {
     if (h->rbias) (void)hipFree(h->rbias);
     h->hi = nullptr; h->rscale = nullptr; h->cmu = nullptr; h->rbias = nullptr; h->mu_norm = 0.f; h->mu_sq = 0.f;
     h->hi_rows = 0; h->hi_cap = 0; h->uniform_e = HI_E_PER_ROW;
+    h->ab_rows = 0;
 }
 
 // Decide whether the plane is CENTRED and compute mu (one-off, when the plane is built; synchronises).  Centred when the common
@@ -2820,6 +2834,34 @@ static bool knn_choose_centre(radad_knn_t h, hipStream_t st) {
     h->mu_norm = sqrtf(host2[0]) * (1.0f + 0x1p-10f);
     h->mu_sq = host2[0];
     return true;
+}
+
+// The early abandon's per-tile terms (knn_plan.h), read off the values the scan multiplies -- the plane, or an fp16 store's own rows --
+// once those are current: k_tile_terms recomputes every aligned KW_M-row tile from the first one an append touched, so the arrays are
+// consistent wherever the plane is built, extended, rebuilt or reloaded.  Stores with per-row scales (RSC 1 / 2) keep none.
+static void knn_ensure_tile_terms(radad_knn_t h, hipStream_t st, bool have_plane) {
+    const int suf_from = knn_abandon_suffix_from(h->dim);
+    const bool current = have_plane ? h->hi_rows == h->ntotal : (h->f16 != 0 && h->stat_rows == h->ntotal);
+    if (!h->opt_abandon || suf_from <= 0 || h->rscale || !current || h->ntotal <= 0) return;
+    const int64_t cap = knn_abandon_tiles(h->capacity);
+    if (h->tile_ry_cap < cap) {
+        float* grown = nullptr;
+        if (hipMalloc(&grown, (size_t)cap * 2 * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return; }
+        if (h->tile_ry) { (void)hipStreamSynchronize(st); (void)hipFree(h->tile_ry); }
+        h->tile_ry = grown; h->tile_ry_cap = cap; h->ab_rows = 0;
+    }
+    if (h->ab_from != suf_from) { h->ab_rows = 0; h->ab_from = suf_from; }
+    if (h->ab_rows >= h->ntotal) return;
+    TileTermsParams tp;
+    tp.plane = h->f16 ? reinterpret_cast<const _Float16*>(h->rows) : h->hi;
+    tp.dim = h->dim; tp.suf_from = suf_from; tp.n = h->ntotal;
+    tp.tile0 = h->ab_rows / KW_M;
+    const bool biased = h->metric == RADAD_METRIC_L2 || h->cmu;
+    tp.rbias = biased ? (h->cmu ? h->rbias : h->ynorm) : nullptr;
+    tp.bias_sign = h->metric == RADAD_METRIC_L2 ? -1.f : 1.f;
+    tp.ry = h->tile_ry; tp.bmax = h->tile_ry + h->tile_ry_cap;
+    hipLaunchKernelGGL(k_tile_terms, dim3((unsigned)(knn_abandon_tiles(h->ntotal) - tp.tile0)), dim3(256), 0, st, tp);
+    if (hipGetLastError() == hipSuccess) h->ab_rows = h->ntotal;
 }
 
 // store statistics (max |y|, max |y - yh|) and, when wanted, the f16 hi plane, brought up to date with the rows
@@ -2911,6 +2953,7 @@ static bool knn_ensure_hi(radad_knn_t h, hipStream_t st, bool want_plane) {
             } else (void)hipGetLastError();
         }
     }
+    knn_ensure_tile_terms(h, st, have_plane);
     return !want_plane || have_plane || h->f16;
 }
 
@@ -2976,6 +3019,8 @@ int radad_knn_destroy(radad_knn_t h) {
         if (h->excl_ws) (void)hipFree(h->excl_ws);
         if (h->rs_key) (void)hipFree(h->rs_key);
         if (h->rs_count) (void)hipFree(h->rs_count);
+        if (h->tile_ry) (void)hipFree(h->tile_ry);
+        if (h->ab_ws) (void)hipFree(h->ab_ws);
         if (h->host_count) (void)hipHostFree(h->host_count);
         if (h->ev_done) (void)hipEventDestroy(h->ev_done);
         if (h->ev_begun) (void)hipEventDestroy(h->ev_begun);
@@ -3014,6 +3059,10 @@ int radad_knn_set_option(radad_knn_t h, int option, int value) {
         case RADAD_KNN_OPT_DENSE:
             RADAD_REQUIRE(value == 0 || value == 1, "radad_knn_set_option: DENSE takes 0 or 1");
             h->opt_dense = value;
+            return RADAD_OK;
+        case RADAD_KNN_OPT_ABANDON:
+            RADAD_REQUIRE(value == 0 || value == 1, "radad_knn_set_option: ABANDON takes 0 or 1");
+            h->opt_abandon = value;
             return RADAD_OK;
         default:
             radad_set_error("radad_knn_set_option: unknown option %d", option);
@@ -3219,6 +3268,21 @@ static int knn_plan_scan(radad_knn_t h, int64_t nq, int k, int margin, hipStream
     return RADAD_OK;
 }
 
+// the store's per-tile suffix norms are current and the handle's buffer holds the per-query terms of nq queries (grown here: a
+// synchronising allocation the first time a batch size is seen); false = this search's launches run the plain scan
+static bool knn_abandon_terms_ready(radad_knn_t h, int64_t nq) {
+    if (!h->opt_abandon || !h->tile_ry || h->ab_rows != h->ntotal || h->ab_from <= 0 || h->ab_from != knn_abandon_suffix_from(h->dim)) return false;
+    const AbandonLayout A = knn_abandon_layout(nq);
+    if (A.bytes > h->ab_ws_bytes) {
+        if (hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); return false; }
+        if (h->ab_ws) (void)hipFree(h->ab_ws);
+        h->ab_ws = nullptr; h->ab_ws_bytes = 0;
+        if (hipMalloc(&h->ab_ws, A.bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
+        h->ab_ws_bytes = A.bytes;
+    }
+    return true;
+}
+
 // ---- queries: decode, normalise, round (+ scale) to f16, error bound.  Returns the fp32 queries the scan and the re-rank read.
 static const float* knn_prepare_queries(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, const void* q_in, int q_dtype, hipStream_t st) {
     const int64_t nq = p.nq;
@@ -3246,6 +3310,14 @@ static const float* knn_prepare_queries(radad_knn_t h, const ScanPlan& p, const 
         hp.zero_flags = ws_at<int>(h, L.cnt); hp.zero_counters = ws_at<int>(h, L.fcount);
         hp.mu = p.mu; hp.mu_norm = p.mu ? h->mu_norm : 0.f; hp.mu_sq = p.mu ? h->mu_sq : 0.f; hp.biased = (p.biased || (f16_tile && p.l2)) ? 1 : 0;
         hp.qconst_out = p.biased ? ws_at<float>(h, L.qconst) : nullptr;
+        hp.zero_ab = ws_at<int>(h, L.fcount) + KNN_AB_COUNTER0;
+        h->ab_search_ready = p.kind == RADAD_SCAN_HI_TILE && knn_abandon_terms_ready(h, nq);
+        if (h->ab_search_ready) {       // the abandon's per-query terms
+            const AbandonLayout A = knn_abandon_layout(nq);
+            hp.suf_from = h->ab_from;
+            hp.suf_out = reinterpret_cast<float*>(static_cast<char*>(h->ab_ws) + A.rq);
+            hp.ab_slack_out = reinterpret_cast<float*>(static_cast<char*>(h->ab_ws) + A.slack);
+        }
         launch_hi_rows(hp, st);
     }
     return cosine ? ws_at<const float>(h, L.qn) : q_use;
@@ -3254,7 +3326,8 @@ static const float* knn_prepare_queries(radad_knn_t h, const ScanPlan& p, const 
 // ---- the certified f16 tile scan (knn_hi.inc) -------------------------------------------------------------------------------------
 // (its phases -- row boundaries, one launch each -- are knn_hi_phases, knn_plan.h)
 // the tile scan's kernel for one RSC (knn_hi.inc), the sample pre-pass's or the scan's own
-static auto knn_hi_kernel(int rsc, bool sample) -> void (*)(KnnHiParams) {
+static auto knn_hi_kernel(int rsc, bool sample, bool abandon = false) -> void (*)(KnnHiParams) {
+    if (abandon) return rsc == 0 ? k_knn_hi_abandon<0> : k_knn_hi_abandon<3>;       // (knn_abandon_launch: RSC 0 and 3, never the sample)
     switch (rsc) {
         case 0: return sample ? k_knn_hi_sample<0> : k_knn_hi<0>;
         case 1: return sample ? k_knn_hi_sample<1> : k_knn_hi<1>;
@@ -3296,6 +3369,13 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
     const int rsc = p.biased ? (wp.rscale ? 2 : 3) : (wp.rscale ? 1 : 0);
     const auto scan = knn_hi_kernel(rsc, false), sample = knn_hi_kernel(rsc, true);
     const size_t lds = knn_hi_lds_bytes();
+    // early abandon: the launches that qualify (knn_abandon_launch) take the ABANDON instantiation, with the store's per-tile and the
+    // search's per-query suffix norms (knn_prepare_queries wrote the latter and says so: ab_search_ready)
+    AbandonFacts af;
+    af.opt_abandon = h->opt_abandon; af.rsc = rsc; af.floors = true; af.per_call_bias = row_bias != nullptr; af.dim = h->dim;
+    af.terms_current = h->ab_search_ready;
+    const AbandonLayout AL = knn_abandon_layout(nq);
+    h->last_ab_tasks = 0; h->last_o_ab = L.fcount + KNN_AB_COUNTER0 * sizeof(int);
     RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(sample), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // sample pre-pass: the (k + margin)-th best score over the first rows of the store is a score at least k rows reach, so the
@@ -3345,9 +3425,25 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
         const int gq_grid = knn_hi_qtile_grid(gq);
         rp.ksplit = knn_tile_ksplit(h, gq_grid, gs, gc, rp.n, st);
         rp.kacc = h->kacc; rp.kflag = h->kflag;
+        af.ksplit = rp.ksplit;
+        const int ab_ck = knn_abandon_launch(af);
+        auto launch_fn = scan;
+        size_t launch_lds = lds;
+        if (ab_ck > 0) {
+            rp.ab_ck = ab_ck;
+            rp.ab_rq = reinterpret_cast<const float*>(static_cast<const char*>(h->ab_ws) + AL.rq);
+            rp.ab_slack = reinterpret_cast<const float*>(static_cast<const char*>(h->ab_ws) + AL.slack);
+            rp.ab_ry = h->tile_ry + r0 / KW_M;          // (phases begin on tile boundaries: knn_hi_phases)
+            rp.ab_b = h->tile_ry + h->tile_ry_cap + r0 / KW_M;
+            rp.ab_count = ws_at<int>(h, L.fcount) + KNN_AB_COUNTER0;
+            launch_fn = knn_hi_kernel(rsc, false, true);
+            launch_lds = knn_hi_lds_bytes(true);
+            RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(launch_fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)launch_lds));
+            h->last_ab_tasks += (int64_t)gq * ceil_div64(rp.n, KW_M);
+        }
         h->prof.begin(st);      // the event pair brackets a scan launch only (the kernel the roofline is quoted on; the phases of one
                                 // search are two entries)
-        hipLaunchKernelGGL(scan, dim3((unsigned)(gq_grid * gs * rp.ksplit)), dim3(KW_THREADS), lds, st, rp);
+        hipLaunchKernelGGL(launch_fn, dim3((unsigned)(gq_grid * gs * rp.ksplit)), dim3(KW_THREADS), launch_lds, st, rp);
         h->prof.end(st);
     }
 #ifdef RADAD_DEBUG_HOOKS
@@ -3496,7 +3592,7 @@ static int knn_search_phase1(radad_knn_t h, const void* q_in, int q_dtype, int64
     }
     if (rc) return rc;
     const bool hi_tile = p.kind == RADAD_SCAN_HI_TILE;
-    if (!hi_tile) { h->last_splits = p.n_splits; h->last_scan_launches = 1; }
+    if (!hi_tile) { h->last_splits = p.n_splits; h->last_scan_launches = 1; h->last_ab_tasks = 0; }
     RADAD_HIP_CHECK(hipGetLastError());
     if (lb_out) {
         knn_report_lower_bounds(h, p, L, lb_out, st);
@@ -4272,6 +4368,19 @@ int radad_knn_last_emitted(radad_knn_t h, int* counts_host, float* floors_host, 
     return RADAD_OK;
 }
 
+int radad_knn_last_abandon(radad_knn_t h, int64_t* checked, int64_t* skipped, int64_t* tasks) {
+    RADAD_REQUIRE(h && checked && skipped && tasks, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    *checked = *skipped = *tasks = 0;
+    if (h->last_ab_tasks <= 0 || !h->ws) return RADAD_OK;       // the last search launched no abandoning scan
+    RADAD_HIP_CHECK(knn_wait_last_search(h));
+    int c2[2] = {0, 0};
+    RADAD_HIP_CHECK(hipMemcpy(c2, (const char*)h->ws + h->last_o_ab, sizeof(c2), hipMemcpyDeviceToHost));
+    *checked = c2[0]; *skipped = c2[1]; *tasks = h->last_ab_tasks;
+    return RADAD_OK;
+}
+
 int radad_knn_scan_geometry(int64_t n_rows, int64_t n_queries, int* query_tiles, int* chunks, int64_t* rows_per_chunk) {
     RADAD_REQUIRE(n_rows >= 1 && n_queries >= 1 && query_tiles && chunks && rows_per_chunk, "radad_knn_scan_geometry: bad argument");
     knn_geometry_wide(n_rows, n_queries, query_tiles, chunks, rows_per_chunk);
@@ -4402,7 +4511,7 @@ int snap_load_range(radad_knn_t h, const char* path, int64_t row0, int64_t n_row
     RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_load: a begun search (radad_knn_search_begin) must be finished or aborted before the store changes");
     RADAD_HIP_CHECK(hipDeviceSynchronize());
     h->ntotal = 0;
-    h->hi_rows = 0; h->stat_rows = 0;      // the hi plane and the statistics describe the old contents
+    h->hi_rows = 0; h->stat_rows = 0; h->ab_rows = 0;      // the hi plane, the statistics and the per-tile terms describe the old contents
     if (h->stat) RADAD_HIP_CHECK(hipMemset(h->stat, 0, 4 * sizeof(unsigned)));
     if ((rc = knn_grow(h, n_rows))) return rc;
     const unsigned char* src = map.base + hd.payload_off + (size_t)row0 * rb;

@@ -68,11 +68,20 @@ struct KnnHiParams {
                                           // 2 skip the DMA issue
     unsigned long long* stamps = nullptr; // -DRADAD_DEBUG_HOOKS only: [2][4096] (tag << 56 | s_memtime) of waves 0 and 4 of workgroup 0
     // (floors raised inside one launch over the whole store were measured slower and removed: DESIGN §4.1)
+    // EARLY ABANDON (the ABANDON instantiations only; which launches take them: knn_abandon_launch, knn_plan.h).  All norms are
+    // those of the RAW f16 values, i.e. in the accumulators' units, inflated as hi_rows_body inflates its norms.
+    int ab_ck = 0;                        // K stages multiplied before the test
+    const float* ab_rq = nullptr;         // [nq] |qh_j[64 ck:]|
+    const float* ab_slack = nullptr;      // [nq] 2 dim 2^-23 (|qh_j| max |yh| + |c0|max) in true units (x 1 / (2^-eq uscale) in the kernel)
+    const float* ab_ry = nullptr;         // [tiles of this launch] max over the tile's rows of |yh_i[64 ck:]|
+    const float* ab_b = nullptr;          // RSC 3: [tiles of this launch] max over the tile's rows of bias_sign x bias (what the accumulators start from, x s_qs)
+    int* ab_count = nullptr;              // [2] tile tasks tested, tile tasks abandoned (one atomic each per workgroup)
 };
 static_assert(std::is_trivially_copyable_v<KnnHiParams>, "kernel argument");
 
-constexpr size_t knn_hi_lds_bytes() {
-    return 2 * KW_STAGE_BYTES + sizeof(float) * KW_N * 4 + sizeof(float) * 2 * KW_M * 2 + 16;
+constexpr size_t knn_hi_lds_bytes(bool abandon = false) {
+    // (ABANDON: + three per-query arrays and the two veto words)
+    return 2 * KW_STAGE_BYTES + sizeof(float) * KW_N * 4 + sizeof(float) * 2 * KW_M * 2 + 16 + (abandon ? sizeof(float) * KW_N * 3 + 16 : 0);
 }
 
 // RSC: 0 = IP with one scale for all rows (un-centred cosine stores, fp16 stores): no per-score arithmetic at all;
@@ -99,8 +108,47 @@ constexpr size_t knn_hi_lds_bytes() {
 #define KH_STAMP(tag) do { } while (0)
 #endif
 
-template <int RSC, bool SAMPLE>
-__device__ __forceinline__ void knn_hi_body(const KnnHiParams& p) {
+// workgroup -> (query tile, chunk of the store); false: a workgroup of the grid's padding (block-uniform)
+__device__ __forceinline__ bool knn_hi_task(const KnnHiParams& p, int bid, int& qt, int& split) {
+    const int xcd = bid & 7;
+    const int slot_b = bid >> 3;
+    if (p.n_qtiles <= 8) {
+        qt = slot_b % p.n_qtiles;
+        split = (slot_b / p.n_qtiles) * 8 + xcd;
+        return true;
+    }
+    const int per_group = p.n_splits;            // slots of one query group on this XCD: 8 query tiles x n_splits / 8 chunks
+    const int r = slot_b % per_group;
+    qt = (slot_b / per_group) * 8 + (r & 7);
+    split = (r >> 3) * 8 + xcd;
+    return qt < p.n_qtiles;                      // (the grid covers whole groups)
+}
+
+// The abandon's terms of one live query, in the accumulators' units (RSC 0, 3): `at` exactly the value the epilogue compares against
+// ((s_thr - s_qc) s_qs, the same operations on the same values), rq = |qh_j[64 ck:]|, sl the accumulation slack; qi = 1 / s_qs.
+template <int RSC>
+__device__ __forceinline__ void knn_hi_ab_query(const KnnHiParams& p, int q, float& at, float& rq, float& sl, float& qi) {
+    qi = p.qscale[q] * p.uscale;
+    if (RSC == 3) qi *= p.mult;
+    const float qs = 1.0f / qi;                  // powers of two: exact
+    const float qc = (RSC >= 2 && p.qconst) ? p.qconst[q] : 0.f;
+    at = (p.thr_init[q] - qc) * qs;
+    rq = p.ab_rq[q];
+    sl = p.ab_slack[q] * qs * (RSC == 3 ? p.mult : 1.f);
+}
+// THE GATE (scalars only; a heuristic: it decides whether the test RUNS, never what the test finds).  A tile can only be skipped if
+// for every live query   at_j - sl_j - start_ij - RQ_j RY > 0   leaves room for the partial products; with the accumulators' start
+// start_ij = b_i / qi_j (RSC 3: b = bias_sign x bias; RSC 0: 0) and everything multiplied by qi_j > 0:
+//     amin - rmax RY - B > 0,    amin = min_j (at_j - sl_j) qi_j,  rmax = max_j RQ_j qi_j,  B = the tile's largest b
+// (sufficient for none of the per-query conditions to fail on the suffix product alone; a NaN anywhere closes it).
+__device__ __forceinline__ bool knn_hi_gate(float amin, float rmax, float ry, float b) { return amin - rmax * (ry * (1.0f + 0x1p-10f)) - b > 0.f; }
+
+// ABANDON: after p.ab_ck K stages a tile whose partial scores provably cannot reach any query's floor is left (the test, its gate and
+// the proof are at the checkpoint below).  Instantiations without it compile to the code they had before it existed.
+// (ab_amin, ab_rmax: the gate's query side, from knn_hi_gate_open)
+template <int RSC, bool SAMPLE, bool ABANDON = false>
+__device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab_amin = 0.f, const float ab_rmax = 0.f) {
+    static_assert(!ABANDON || (!SAMPLE && (RSC == 0 || RSC == 3)), "the abandon covers the one-scale scans");
     int stamp_n = 0;
     (void)stamp_n;
     // acc[mt][nt][r] = row wm*128 + mt*16 + 4*lq + r, query wn*64 + nt*16 + l15   (l15 = lane & 15, lq = lane >> 4)
@@ -113,6 +161,11 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p) {
     float* s_qc = s_qi + KW_N;                                               // [KW_N] per-query constant of the score (RSC 2, 3)
     float* s_rs = s_qc + KW_N;                                               // [2][KW_M] row scale (x mult)
     float* s_rb = s_rs + 2 * KW_M;                                           // [2][KW_M] accumulator start of the row: bias / (mult scale)
+    // ABANDON (behind the K split's flag, which such a launch never uses):
+    float* s_at = s_rb + 2 * KW_M + 4;                                       // [KW_N] the epilogue's threshold of each query, +inf past nq
+    float* s_arq = s_at + KW_N;                                              // [KW_N] |qh_j[64 ck:]|
+    float* s_asl = s_arq + KW_N;                                             // [KW_N] accumulation slack, accumulator units
+    int* s_veto = reinterpret_cast<int*>(s_asl + KW_N);                      // [2] by tile parity: the tile (row0 / KW_M) a wave vetoed last
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -125,28 +178,17 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p) {
     // search: every rank scores ALL ranks' queries, 32-40 tiles): 32 query tiles of 256 KB each would evict each other from a 4 MB
     // L2 and every stage would refetch its query tile from the Infinity Cache -- instead GROUPS of 8 query tiles (2 MB) stay on
     // an XCD while its share of the chunks passes, 4 chunks at a time (the 32 concurrent workgroups = 8 query tiles x 4 chunks).
-    const int part = p.ksplit == 2 ? (int)(blockIdx.x & 1) : 0;
-    const int bid = p.ksplit == 2 ? (int)(blockIdx.x >> 1) : (int)blockIdx.x;
-    const int xcd = bid & 7;
-    const int slot_b = bid >> 3;
+    const int part = (!ABANDON && p.ksplit == 2) ? (int)(blockIdx.x & 1) : 0;
+    const int bid = (!ABANDON && p.ksplit == 2) ? (int)(blockIdx.x >> 1) : (int)blockIdx.x;
     int qt, split;
-    if (p.n_qtiles <= 8) {
-        qt = slot_b % p.n_qtiles;
-        split = (slot_b / p.n_qtiles) * 8 + xcd;
-    } else {
-        const int per_group = p.n_splits;            // slots of one query group on this XCD: 8 query tiles x n_splits / 8 chunks
-        const int r = slot_b % per_group;
-        qt = (slot_b / per_group) * 8 + (r & 7);
-        split = (r >> 3) * 8 + xcd;
-        if (qt >= p.n_qtiles) return;                // (the grid covers whole groups; block-uniform, before any barrier)
-    }
+    if (!knn_hi_task(p, bid, qt, split)) return;     // (block-uniform, before any barrier)
     const int q0 = qt * KW_N;
     const int64_t chunk_begin = (int64_t)split * p.chunk_stride;
     const int64_t chunk_end = min(chunk_begin + p.chunk_rows, p.n);
     const bool owner = tid < KW_N && q0 + tid < p.nq;
     const int nk_all = p.row_bytes >> 7;             // 128-byte K steps per row
     const int k_lo = part * (nk_all >> 1);           // this workgroup's K steps [k_lo, k_lo + nk)
-    const int nk = p.ksplit == 2 ? (part == 0 ? (nk_all >> 1) : nk_all - (nk_all >> 1)) : nk_all;
+    const int nk = (!ABANDON && p.ksplit == 2) ? (part == 0 ? (nk_all >> 1) : nk_all - (nk_all >> 1)) : nk_all;
 
     if (tid < KW_N) {
         s_thr[tid] = (owner && p.thr_init) ? p.thr_init[q0 + tid] : -INFINITY;
@@ -157,7 +199,15 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p) {
         s_qi[tid] = qi;
         s_qs[tid] = 1.0f / qi;                       // powers of two: exact
         s_qc[tid] = (RSC >= 2 && owner && p.qconst) ? p.qconst[q0 + tid] : 0.f;
+        if constexpr (ABANDON) {
+            // a slot past nq counts as +inf (the epilogue's -inf would veto every skip of a partly filled query tile); a real query
+            // whose floor is -inf vetoes
+            float at = INFINITY, rq = 0.f, sl = 0.f, qi_ab;
+            if (owner) knn_hi_ab_query<RSC>(p, q0 + tid, at, rq, sl, qi_ab);
+            s_at[tid] = at; s_arq[tid] = rq; s_asl[tid] = sl;
+        }
     }
+    if constexpr (ABANDON) { if (tid < 2) s_veto[tid] = -1; }
 
     // DMA plan.  One LDS-DMA instruction fills an 8-row group (1 KB, lane-linear) of an operand tile; 32 groups per operand
     // and stage.  Waves 0-3 fetch the A (store) tile, 8 groups each, right after the stage's barrier (it comes from HBM: the
@@ -249,7 +299,9 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p) {
     constexpr bool HOLD = true;
     f32x4 acc[MT][NT];
     f16x8 bfr[2][NT], afr[2][2];
-    auto stage_body = [&](const char* a_row, const char* b_row, auto first_c, const bool hold_out, const float* rb_t, auto&& dma_a, auto&& dma_b) {
+    // (ABANDON: the checkpoint stage holds nothing back -- the test needs the finished partial sums -- so the stage after it has no
+    // held-back pair to finish: hold_in, wave-uniform; without ABANDON it is the constant true)
+    auto stage_body = [&](const char* a_row, const char* b_row, auto first_c, const bool hold_out, const bool hold_in, const float* rb_t, auto&& dma_a, auto&& dma_b) {
         constexpr bool ZERO = decltype(first_c)::value;         // a tile's first stage: C = 0, or (RSC 2, 3) C = the row bias in the
                                                                 // accumulator's units, bias_row 2^eq / (mult 2^-ey): exact (powers of two)
         constexpr bool HOLD_IN = HOLD && !ZERO;   // every stage but a tile's first finishes the previous stage's last pair first;
@@ -270,11 +322,13 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p) {
         afr[0][1] = *reinterpret_cast<const f16x8*>(a_row + 2048 + rd_x);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (HOLD_IN) {
+            if (!ABANDON || hold_in) {
 #pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2)
+                for (int h2 = 0; h2 < 2; ++h2)
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    acc[6 + h2][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[1][h2], bfr[1][nt], acc[6 + h2][nt], 0, 0, 0);
+                    for (int nt = 0; nt < NT; ++nt)
+                        acc[6 + h2][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[1][h2], bfr[1][nt], acc[6 + h2][nt], 0, 0, 0);
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
         KH_STAMP(1);
@@ -319,9 +373,31 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p) {
     };
     static_assert(MT == 8, "the hold-back names row tiles 6 and 7");
 
+    // ---- EARLY ABANDON ----------------------------------------------------------------------------------------------------------
+    // After ck stages the accumulators hold acc_c = (bias start) + sum over the first 64 ck elements, and for every pair (row i, query j)
+    //     acc_full <= acc_c + RQ_j RY (1 + 2^-10) + slack_j,    RQ_j = |qh_j[64 ck:]|, RY = max_i |yh_i[64 ck:]| over the tile's rows
+    // (Cauchy-Schwarz on the exact rest of the dot product; both norms are fp32 sums of squares of the raw f16 values inflated by 2^-10
+    // as hi_rows_body inflates its norms; slack_j = 2 dim 2^-23 (|qh_j| max |yh| + |c0|max) covers the fp32 accumulation error of any
+    // summation order, of the part done and of the part to come).  The epilogue emits a pair iff acc_full >= at_j; so when
+    //     acc_c + RQ_j RY (1 + 2^-10) + slack_j < at_j      for all 256 x 256 pairs (every comparison TRUE: a NaN vetoes),
+    // the tile emits nothing and its remaining stages and its epilogue are left out.  The set of emitted candidates is the parent's.
+    // Every lane takes the maximum of its 32 partial scores per query (4 queries); a wave that cannot agree writes the tile's number
+    // into s_veto[parity]; the stage's own barrier publishes it; everyone reads it: the decision is workgroup-uniform, no spinning, no
+    // communication between workgroups.  (The word holds a tile NUMBER and is never reset; the next write to the same parity is two
+    // tiles on, behind at least two more barriers.)
+    int ab_ck = 0, ab_checked = 0, ab_skipped = 0;
+    if constexpr (ABANDON) ab_ck = p.ab_ck;
     int tile_par = 0;
     for (int64_t row0 = chunk_begin; row0 < chunk_end; row0 += KW_M, tile_par ^= 1) {
         const bool has_next = row0 + KW_M < chunk_end;
+        // THE GATE, tile side (scalars only): the test runs iff it can succeed
+        float ab_ry = 0.f;
+        bool ab_check = false, ab_skip = false;
+        if constexpr (ABANDON) {
+            ab_ry = p.ab_ry[row0 >> 8] * (1.0f + 0x1p-10f);
+            ab_check = knn_hi_gate(ab_amin, ab_rmax, p.ab_ry[row0 >> 8], RSC == 3 ? p.ab_b[row0 >> 8] : 0.f);
+        }
+        static_assert(KW_M == 256, "row0 >> 8 is the tile's number");
         const int rowlimit = (int)min((int64_t)KW_M, chunk_end - row0);
         const __amdgpu_buffer_rsrc_t cur_desc = tile_desc(row0);
         const __amdgpu_buffer_rsrc_t next_desc = tile_desc(row0 + KW_M);
@@ -335,8 +411,28 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p) {
             const char* a_row = smem + stage * KW_STAGE_BYTES + rd_a;
             const char* b_row = smem + stage * KW_STAGE_BYTES + rd_b;
             const float* rb_t = s_rb + tile_par * KW_M + wm * 128 + 4 * lq;
-            if (kc == 0) stage_body(a_row, b_row, std::true_type{}, more_k, rb_t, dma_a, dma_b);      // first stage of a tile: C = 0 / the bias
-            else stage_body(a_row, b_row, std::false_type{}, more_k, rb_t, dma_a, dma_b);            // (the last stage leaves nothing over)
+            const bool at_ck = ABANDON && ab_check && kc + 1 == ab_ck;      // the checkpoint stage (wave-uniform)
+            const bool after_ck = ABANDON && ab_check && kc == ab_ck;
+            if (kc == 0) stage_body(a_row, b_row, std::true_type{}, more_k && !at_ck, true, rb_t, dma_a, dma_b);      // first stage of a tile: C = 0 / the bias
+            else stage_body(a_row, b_row, std::false_type{}, more_k && !at_ck, !after_ck, rb_t, dma_a, dma_b);       // (the last stage leaves nothing over)
+            if constexpr (ABANDON) {
+                if (at_ck) {
+                    int lane_t = lane;
+                    asm volatile("" : "+v"(lane_t));         // (opaque, as in the epilogue: no address of this block lives across the K loop)
+                    bool ok = true;
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) {
+                        const int ql = wn * 64 + nt * 16 + (lane_t & 15);
+                        float gm = -INFINITY;
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt)
+                            gm = fmaxf(gm, fmaxf(fmaxf(acc[mt][nt][0], acc[mt][nt][1]), fmaxf(acc[mt][nt][2], acc[mt][nt][3])));
+                        // (fmaxf drops a NaN score: a NaN score is never emitted either.  Rows past the tile's end read as zero rows.)
+                        ok = ok && (gm + fmaf(s_arq[ql], ab_ry, s_asl[ql]) < s_at[ql]);
+                    }
+                    if (!__all(ok) && (lane_t & 63) == 0) s_veto[tile_par] = (int)(row0 >> 8);
+                }
+            }
 #ifdef RADAD_DEBUG_HOOKS
             if (p.stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); KH_STAMP(10); }   // own DMA landed (stamps only)
 #endif
@@ -344,9 +440,28 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p) {
             KH_STAMP(6);
             ++gbuf;
             if (kc == 0 && has_next) park_row_terms(row0 + KW_M, tile_par ^ 1);
+            if constexpr (ABANDON) {
+                if (at_ck) {
+                    ++ab_checked;
+                    if (__builtin_amdgcn_readfirstlane(s_veto[tile_par]) != (int)(row0 >> 8)) { ab_skip = true; break; }
+                }
+            }
+        }
+        if constexpr (ABANDON) {
+            if (ab_skip) {
+                // the stage fetched during the checkpoint stage (this tile's stage ck) has landed behind the barrier and is not read:
+                // the next tile's stage 0 goes over it, and one barrier waits for it (the skip's DMA bubble)
+                ++ab_skipped;
+                if (has_next) {
+                    if (grp_half == 0) dma_half(next_desc, gbuf & 1, 0, 0);
+                    else dma_half(q_desc, gbuf & 1, 0, 1);
+                    __syncthreads();
+                }
+                continue;
+            }
         }
         KH_STAMP(8);
-        if (p.ksplit == 2) {
+        if (!ABANDON && p.ksplit == 2) {
             // publish this half's partial sums, lane-linear (vector v of thread t at [v][t]); the second arrival adds the other half's
             int* s_flag = reinterpret_cast<int*>(s_rb + 2 * KW_M);
             // (K split: one tile per workgroup pair -- the pair's index is the tile's.  Taken from blockIdx here: `split * n_qtiles + qt`
@@ -537,15 +652,115 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p) {
         KH_STAMP(9);
         if (nk < 2 && has_next) __syncthreads();     // one K step per tile: the next tile's only barrier comes after park_row_terms' reader
     }
+    if constexpr (ABANDON) {
+        if (tid == 0 && ab_checked > 0) {
+            atomicAdd(p.ab_count, ab_checked);
+            if (ab_skipped > 0) atomicAdd(p.ab_count + 1, ab_skipped);
+        }
+    }
 }
 
 template <int RSC>
 __global__ __launch_bounds__(KW_THREADS, 1) void k_knn_hi(KnnHiParams p) { knn_hi_body<RSC, false>(p); }
 
+// Whether the gate can open for ANY tile of this workgroup's chunk, and its query side (amin, rmax: knn_hi_gate).  Decided once, in front
+// of the body, so that a workgroup that can never test runs the plain body: the abandoning one carries a wave-uniform branch around
+// every stage's held-back MFMAs, measured at 2.5 % of the scan on unstructured queries.
+template <int RSC>
+__device__ __forceinline__ bool knn_hi_gate_open(const KnnHiParams& p, float& amin, float& rmax) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* s_pre = reinterpret_cast<float*>(smem);           // [16]: the stage buffers are not in use yet
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int qt, split;
+    if (!knn_hi_task(p, (int)blockIdx.x, qt, split)) return false;       // (the plain body returns at the same test)
+    const int q = qt * KW_N + tid;
+    float a = INFINITY, r = 0.f;
+    if (tid < KW_N && q < p.nq) {
+        float at, rq, sl, qi;
+        knn_hi_ab_query<RSC>(p, q, at, rq, sl, qi);
+        a = (at - sl) * qi;
+        r = rq * qi;
+        if (!(a == a) || !(r == r)) a = -INFINITY;            // NaN: shut
+    }
+    a = -wave_max(-a); r = wave_max(r);
+    if (lane == 0) { s_pre[wave] = a; s_pre[8 + wave] = r; }
+    __syncthreads();
+    amin = fminf(fminf(s_pre[0], s_pre[1]), fminf(s_pre[2], s_pre[3]));
+    rmax = fmaxf(fmaxf(s_pre[8], s_pre[9]), fmaxf(s_pre[10], s_pre[11]));
+    const int64_t chunk_begin = (int64_t)split * p.chunk_stride;
+    const int64_t chunk_end = min(chunk_begin + p.chunk_rows, p.n);
+    int open = 0;
+    for (int64_t r0 = chunk_begin + (int64_t)tid * KW_M; r0 < chunk_end; r0 += (int64_t)KW_THREADS * KW_M)
+        open |= knn_hi_gate(amin, rmax, p.ab_ry[r0 >> 8], RSC == 3 ? p.ab_b[r0 >> 8] : 0.f) ? 1 : 0;
+    __syncthreads();                                         // (everyone has read s_pre)
+    if (__any(open) && lane == 0) s_pre[wave] = 1.f;
+    else if (lane == 0) s_pre[wave] = 0.f;
+    __syncthreads();
+    float any = 0.f;
+#pragma unroll
+    for (int w = 0; w < KW_WAVES; ++w) any += s_pre[w];
+    __syncthreads();                                         // (the body's first DMA overwrites s_pre)
+    amin = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(amin)));
+    rmax = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(rmax)));
+    return __builtin_amdgcn_readfirstlane(any > 0.f ? 1 : 0) != 0;
+}
+
+// the same scan with the early abandon: own symbol (profiles keep the two apart)
+template <int RSC>
+__global__ __launch_bounds__(KW_THREADS, 1) void k_knn_hi_abandon(KnnHiParams p) {
+    float amin, rmax;
+    if (knn_hi_gate_open<RSC>(p, amin, rmax)) knn_hi_body<RSC, false, true>(p, amin, rmax);
+    else knn_hi_body<RSC, false, false>(p);
+}
+
 // the threshold pre-pass over the first rows of the store: same K loop, own symbol (profiles keep the two apart);
 // one tile per workgroup
 template <int RSC>
 __global__ __launch_bounds__(KW_THREADS, 1) void k_knn_hi_sample(KnnHiParams p) { knn_hi_body<RSC, true>(p); }
+
+// The abandon's per-tile terms, read off the values the scan multiplies: one workgroup per aligned KW_M-row tile, a wave per row.
+struct TileTermsParams {
+    const _Float16* plane = nullptr; // [n][dim] the f16 plane, or the rows of an fp16 store
+    int dim = 0, suf_from = 0;
+    int64_t n = 0, tile0 = 0;        // rows of the store; first tile to compute (the grid covers tile0 ... the last)
+    const float* rbias = nullptr;    // [n] per-row bias of a biased scan (RSC 3), or nullptr
+    float bias_sign = 1.f;
+    float* ry = nullptr;             // [tiles] max_i |yh_i[suf_from:]|, fp32 sum of squares inflated like hi_rows_body's norms
+    float* bmax = nullptr;           // [tiles] max_i bias_sign x bias_i (0 without a bias)
+};
+static_assert(std::is_trivially_copyable_v<TileTermsParams>, "kernel argument");
+
+__global__ __launch_bounds__(256) void k_tile_terms(TileTermsParams p) {
+    __shared__ float s_m[8];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t tile = p.tile0 + blockIdx.x;
+    const int64_t row_end = min((tile + 1) * (int64_t)KW_M, p.n);
+    const int nv = (p.dim - p.suf_from) >> 3;                // f16x8 chunks of the suffix
+    float m = 0.f;
+    for (int64_t row = tile * KW_M + wave; row < row_end; row += 4) {
+        const f16x8* src = reinterpret_cast<const f16x8*>(p.plane + row * p.dim + p.suf_from);
+        float ss = 0.f;
+        for (int i = lane; i < nv; i += 64) {
+            const f16x8 v = src[i];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) ss = fmaf((float)v[j], (float)v[j], ss);
+        }
+        const float nrm = sqrtf(wave_sum(ss)) * (1.0f + 0x1p-10f);
+        m = (nrm == nrm) ? fmaxf(m, nrm) : INFINITY;         // (a NaN row can never let its tile be skipped)
+    }
+    float b = -INFINITY;
+    if (p.rbias) {
+        const int64_t row = tile * KW_M + threadIdx.x;
+        if (row < row_end) { const float v = p.bias_sign * p.rbias[row]; b = (v == v) ? v : INFINITY; }
+        b = wave_max(b);
+    }
+    if (lane == 0) { s_m[wave] = m; s_m[4 + wave] = b; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        p.ry[tile] = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
+        p.bmax[tile] = p.rbias ? fmaxf(fmaxf(s_m[4], s_m[5]), fmaxf(s_m[6], s_m[7])) : 0.f;
+    }
+}
 
 // ---- operand preparation ---------------------------------------------------------------------------------------
 // one wave per row: hi[row][:] = f16(in[row][:] * 2^e), scale_out[row] = 2^-e.
@@ -584,6 +799,11 @@ struct HiRowsParams {
     // orthogonal to their mean), the large |mu|^2 goes with the query's constant, so the accumulators never carry it
     float* bias_out = nullptr;       // store side, optional [n]: |x'|^2 (L2) or mu.x' (IP / cosine)
     float* qconst_out = nullptr;     // query side, optional [n]: -|x'|^2 (L2) or x'.mu + |mu|^2 (IP / cosine)
+    // the tile scan's early abandon: norms of the RAW f16 values xh 2^e (the accumulators' units) from element suf_from on
+    int suf_from = 0;                // a multiple of 64 (knn_abandon_suffix_from), 0 = none wanted
+    float* suf_out = nullptr;        // query side, [n]: |xh[suf_from:]|, inflated like the other norms
+    float* ab_slack_out = nullptr;   // query side, [n] (with eps_out): 2 dim 2^-23 (|qh| max |yh| + |c0|max), true units
+    int* zero_ab = nullptr;          // optional [2]: the abandon's counters, cleared with zero_counters
 };
 static_assert(std::is_trivially_copyable_v<HiRowsParams>, "kernel argument");
 constexpr int HI_E_PER_ROW = -0x7fffffff - 1;
@@ -625,6 +845,7 @@ __device__ __forceinline__ void hi_rows_body(const HiRowsParams& p) {
         if (p.zero_flags) p.zero_flags[row] = 0;
         if (p.zero_flags2) p.zero_flags2[row] = 0;
         if (p.zero_counters && row == 0) { for (int i = 0; i < 8; ++i) p.zero_counters[i] = 0; }
+        if (p.zero_ab && row == 0) { p.zero_ab[0] = 0; p.zero_ab[1] = 0; }
     }
     float den = 1.f;
     if (p.norm_out) {                        // same arithmetic as k_rows_prepare<float> mode 2 (bit for bit)
@@ -689,7 +910,8 @@ __device__ __forceinline__ void hi_rows_body(const HiRowsParams& p) {
         }
     }
     const float up = ldexpf(1.0f, e), down = ldexpf(1.0f, -e);
-    float sx = 0.f, sd = 0.f, sh = 0.f, sm = 0.f, so = 0.f;
+    float sx = 0.f, sd = 0.f, sh = 0.f, sm = 0.f, so = 0.f, ssuf = 0.f;
+    const int suf_v = p.suf_from > 0 ? (p.suf_from >> 2) : nv;      // first 4-vector of the suffix
     for (int i = lane; i < nv; i += TEAM) {
         const f32x4 v = load4(i);
         f16x4 hi;
@@ -702,6 +924,8 @@ __device__ __forceinline__ void hi_rows_body(const HiRowsParams& p) {
             sx = fmaf(v[j], v[j], sx);
             sd = fmaf(d, d, sd);
             sh = fmaf(back, back, sh);
+            const float raw = (float)hi[j];
+            if (i >= suf_v) ssuf = fmaf(raw, raw, ssuf);
         }
         if (p.mu) {                                           // mu.x'
             const f32x4 m = reinterpret_cast<const f32x4*>(p.mu)[i];
@@ -715,6 +939,7 @@ __device__ __forceinline__ void hi_rows_body(const HiRowsParams& p) {
     }
     sx = hi_rows_sum<WPR>(sx, scratch); sd = hi_rows_sum<WPR>(sd, scratch); sh = hi_rows_sum<WPR>(sh, scratch);
     sm = hi_rows_sum<WPR>(sm, scratch); so = hi_rows_sum<WPR>(so, scratch);
+    if (p.suf_from > 0) ssuf = hi_rows_sum<WPR>(ssuf, scratch);       // (uniform: a kernel argument)
     if (lane != 0) return;
     if (p.bias_out) p.bias_out[row] = p.l2 ? sx : sm;
     if (p.qconst_out) p.qconst_out[row] = p.l2 ? -sx : sm + p.mu_sq;
@@ -734,6 +959,7 @@ __device__ __forceinline__ void hi_rows_body(const HiRowsParams& p) {
         raise(&p.stat_max[2], p.mu ? sqrtf(so) * infl * infl : nx);
         raise(&p.stat_max[3], fabsf(sm) * infl);       // |mu.x'|: what an IP row's accumulator starts from
     }
+    if (p.suf_out) p.suf_out[row] = sqrtf(ssuf) * infl;     // (ssuf <= 16380 x 65504^2 = 7e13: finite)
     if (p.eps_out) {
         // (all norms are those of the CENTRED operands when the plane is centred: q' = fl(q - mu), y' = fl(y - mu))
         // (exact_ops: the fp32 kernels multiply the un-centred fp32 operands themselves: |y| is the un-centred maximum)
@@ -746,6 +972,8 @@ __device__ __forceinline__ void hi_rows_body(const HiRowsParams& p) {
         const float yorig = ymax + p.mu_norm;                          // |y| <= |y'| + |mu|
         const float c0 = !p.biased ? 0.f : (p.l2 ? 0.5f * ymax * ymax : __uint_as_float(p.ystat[3]));
         float eps = nd * ymax + nh * dymax + gamma * (nh * (ymax + dymax) + c0);
+        // the abandon's slack: the same accumulation term twice (the part of the sum done at the checkpoint and the part to come)
+        if (p.ab_slack_out) p.ab_slack_out[row] = 2.f * gamma * (nh * (ymax + dymax) + c0) * infl;
         if (p.l2) {
             // the score 2 a - |y'|^2 - |q'|^2 estimates -|q - y|^2: |y'|^2 and |q'|^2 are fp32 wave sums, and the start value, the
             // epilogue's multiply and the constant's add each round once on a magnitude <= 2 |q'||y'| + |y'|^2 + |q'|^2

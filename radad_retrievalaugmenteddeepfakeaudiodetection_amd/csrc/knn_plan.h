@@ -337,6 +337,55 @@ static std::vector<int64_t> knn_hi_phases(int64_t n, int64_t nq, int64_t phase0,
     return r;
 }
 
+// ---- early abandon of scan tiles (knn_hi.inc, ABANDON) ----------------------------------------------------------------------------
+// After `c` of a tile's K stages (64 elements each) the rest of every dot product is at most |qh[64c:]| |yh[64c:]| (Cauchy-Schwarz):
+// a tile none of whose 256 x 256 partial scores can still reach its query's admission floor is left there.  The checkpoint c per
+// row width, 0 = the scan never tests: an eighth of the stages, at least one, and none on rows of a single stage.  An early
+// checkpoint saves more of a skipped tile and succeeds less often: with flat energy the suffix norms have shrunk to
+// (1 - c / stages) of |q||y|, so the test can succeed only against floors above that -- 0.875 |q||y| at an eighth.
+// (dim 512: c = 1 of 8.  Measured against c = 2 on the benchmark, three alternations on one box: 1.197-1.201 against 1.242-1.246 ms
+// per step, the skipped fraction 0.488 either way: profiles/abandon_ab.txt.)
+static int knn_abandon_checkpoint(int dim) {
+    if (dim < 128 || dim % 64 != 0) return 0;
+    return std::max(1, dim / 64 / 8);
+}
+// first element of the suffix whose norms the store keeps per row tile and a search keeps per query
+static int knn_abandon_suffix_from(int dim) { return 64 * knn_abandon_checkpoint(dim); }
+
+// What one launch of the tile scan needs to take the ABANDON instantiation; everything else launches the parent's kernel.
+struct AbandonFacts {
+    int opt_abandon = 1;         // RADAD_KNN_OPT_ABANDON
+    int rsc = 0;                 // the launch's RSC (knn_hi.inc): one scale for all rows (0, 3) is covered, per-row scales (1, 2) are not
+    bool sample = false;         // the threshold pre-pass: it has no floor to test against
+    int ksplit = 1;              // K split over two workgroups: neither holds a whole partial score
+    bool floors = false;         // the launch admits from per-query floors (thr_init)
+    bool per_call_bias = false;  // radad_knn_search_excl_scan's bias array (NaN rows): not covered
+    bool terms_current = false;  // the store's per-tile suffix norms cover every row and were taken at this dim's checkpoint
+    int dim = 0;
+};
+// -> the checkpoint the launch runs with, 0 = the plain instantiation
+static int knn_abandon_launch(const AbandonFacts& f) {
+    if (!f.opt_abandon || f.sample || f.ksplit != 1 || !f.floors || f.per_call_bias || !f.terms_current) return 0;
+    if (f.rsc != 0 && f.rsc != 3) return 0;
+    return knn_abandon_checkpoint(f.dim);
+}
+
+// The abandon's per-query terms live in a small buffer of the handle's own beside the search workspace (SearchLayout and its byte
+// counts stay what every other scan was planned and pinned with): rq [nq] suffix norms | slack [nq] accumulation slack.
+struct AbandonLayout {
+    size_t rq = 0, slack = 0, bytes = 0;
+};
+static AbandonLayout knn_abandon_layout(int64_t nq) {
+    AbandonLayout L;
+    const size_t b_vec = al256((size_t)nq * sizeof(float));
+    L.rq = 0; L.slack = b_vec; L.bytes = 2 * b_vec;
+    return L;
+}
+// the store's per-tile terms (largest suffix norm, largest accumulator start): two floats per aligned KW_M-row tile of the capacity
+static int64_t knn_abandon_tiles(int64_t rows) { return ceil_div64(rows, KW_M); }
+// ints of the search's counter block (SearchLayout::fcount, 64 ints: flag_count + 6 statistics first) the abandon counts in
+constexpr int KNN_AB_COUNTER0 = 8;       // [8] tile tasks tested, [9] tile tasks abandoned
+
 // ---- workspace layouts ------------------------------------------------------------------------------------------------------------
 // byte offsets of a search's buffers in the handle's workspace (knn_search_layout)
 struct SearchLayout {

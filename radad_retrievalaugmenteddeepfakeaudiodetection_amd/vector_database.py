@@ -74,14 +74,14 @@ def write_faiss_flat(path: str, rows: np.ndarray, metric: str):
 
 def knn_options_from_config(config):
     """the optional scan knobs, read the way the reference reads its own optional ones (getattr with a default,
-    vector_database.py:43,67,80): knn_hi_plane, knn_centre, knn_smallq_hi, knn_wide_min_q, knn_dense; absent / None = the library's default.
+    vector_database.py:43,67,80): knn_hi_plane, knn_centre, knn_smallq_hi, knn_wide_min_q, knn_dense, knn_abandon; absent / None = the library's default.
     knn_live_floor is still recognised, but only None / 0 (the default): the one-launch scan form it selected was removed"""
     if getattr(config, "knn_live_floor", None) not in (None, 0):
         raise ValueError("knn_live_floor: the one-launch scan form was measured slower and removed (DESIGN §4.1); "
                          "leave it None / 0 for the default, one launch per phase")
     opts = dict(hi_plane=getattr(config, "knn_hi_plane", None), centre=getattr(config, "knn_centre", None),
                 smallq_hi=getattr(config, "knn_smallq_hi", None), wide_min_q=getattr(config, "knn_wide_min_q", None),
-                dense=getattr(config, "knn_dense", None))
+                dense=getattr(config, "knn_dense", None), abandon=getattr(config, "knn_abandon", None))
     return {k: v for k, v in opts.items() if v is not None}
 
 
@@ -165,8 +165,8 @@ class HipFlatIndex:
     is_trained = True   # flat indexes need no training (vector_database.py:124)
 
     def __init__(self, d: int, metric: int, device: int = 0, id_base: int = 0, store_f16: bool = False, hi_plane=None, centre=None,
-                 smallq_hi=None, wide_min_q=None, dense=None):
-        """hi_plane / centre / smallq_hi / wide_min_q / dense: kernel choices of the handle (radad_knn_set_option; None = the library's
+                 smallq_hi=None, wide_min_q=None, dense=None, abandon=None):
+        """hi_plane / centre / smallq_hi / wide_min_q / dense / abandon: kernel choices of the handle (radad_knn_set_option; None = the library's
         default).  They change speed, never results: A/B measurements and the parity tests select kernels through them."""
         self._lib = _lib.load()
         self.d = int(d)
@@ -178,9 +178,9 @@ class HipFlatIndex:
         _lib.check(self._lib.radad_knn_create_ex(self.d, self.metric, _lib.STORE_F16 if self.store_f16 else _lib.STORE_F32,
                                                  self.device, self.id_base, C.byref(h)), "radad_knn_create")
         self._h = h
-        self.options = dict(hi_plane=hi_plane, centre=centre, smallq_hi=smallq_hi, wide_min_q=wide_min_q, dense=dense)
+        self.options = dict(hi_plane=hi_plane, centre=centre, smallq_hi=smallq_hi, wide_min_q=wide_min_q, dense=dense, abandon=abandon)
         for opt, val in ((_lib.KNN_OPT_HI_PLANE, hi_plane), (_lib.KNN_OPT_CENTRE, centre), (_lib.KNN_OPT_SMALLQ_HI, smallq_hi),
-                         (_lib.KNN_OPT_WIDE_MIN_Q, wide_min_q), (_lib.KNN_OPT_DENSE, dense)):
+                         (_lib.KNN_OPT_WIDE_MIN_Q, wide_min_q), (_lib.KNN_OPT_DENSE, dense), (_lib.KNN_OPT_ABANDON, abandon)):
             if val is not None:
                 _lib.check(self._lib.radad_knn_set_option(self._h, opt, int(val)), "radad_knn_set_option")
 
@@ -512,6 +512,19 @@ class HipFlatIndex:
         _lib.check(self._lib.radad_knn_last_emitted(self._h, c.ctypes.data, f.ctypes.data, int(nq)), "radad_knn_last_emitted")
         return c, f
 
+    def set_abandon(self, value):
+        """RADAD_KNN_OPT_ABANDON at any time: 1 = the tile scan leaves tiles that cannot reach the admission floor (default), 0 = never
+        (same results; A/B measurements and the parity tests)"""
+        _lib.check(self._lib.radad_knn_set_option(self._h, _lib.KNN_OPT_ABANDON, int(value)), "radad_knn_set_option")
+        self.options["abandon"] = int(value)
+
+    def last_abandon(self):
+        """{"checked", "skipped", "tasks"}: of the (query tile, row tile) tasks the last search's abandoning scan launches covered, how
+        many ran the abandon test and how many were left after it (radad_knn_last_abandon; all 0 when no launch abandoned)"""
+        c, s, t = C.c_int64(), C.c_int64(), C.c_int64()
+        _lib.check(self._lib.radad_knn_last_abandon(self._h, C.byref(c), C.byref(s), C.byref(t)), "radad_knn_last_abandon")
+        return {"checked": c.value, "skipped": s.value, "tasks": t.value}
+
     def tuning_info(self):
         """{"cap_boost", "fp32_searches_left", "reports_consumed"} (radad_knn_tuning_info): read without synchronising"""
         a, b, n = C.c_int(), C.c_int(), C.c_int64()
@@ -528,7 +541,7 @@ class HipFlatIndex:
         _lib.check(self._lib.radad_knn_last_scan_launches(self._h, C.byref(nl)))
         _lib.check(self._lib.radad_knn_last_scan_phases(self._h, C.byref(nph)))
         return {"query_tiles": a.value, "db_splits": b.value, "block_threads": c.value, "rechecked_queries": st[0],
-                "scan_launches": nl.value, "scan_phases": nph.value,
+                "scan_launches": nl.value, "scan_phases": nph.value, "early_abandon": self.last_abandon(),
                 "scan_kind": ("f32_tile", "hi_tile", "f32_smallq", "hi_smallq", "f16_tile", "f32_dense")[kind.value],
                 "certificate": {"queries": nq.value, "rejected": st[0], "candidates_rescored": st[1],
                                 "rejected_buffer_full": st[2], "rejected_list_used_up": st[3],
