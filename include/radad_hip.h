@@ -409,10 +409,12 @@ int radad_knn_search_excl_pq_begin(radad_knn_t h, const void* q_dev, int q_dtype
  * the last plain search.  Arguments and errors as radad_knn_search_excl: row_tags_dev / excl_sorted_dev (ascending) may be NULL only
  * when n_excl == 0; RADAD_ESTATE on an empty store; RADAD_EINVAL on a handle with a begun search or beyond the width x k limit,
  * before anything is enqueued.  Stream-ordered and serialised like every search.
- * Not offered: per-query sets (a bias is per row, not per (row, query): radad_knn_search_excl_pq); a begin / finish pair (a shard's
- * result here IS its exact admissible top k: radad_topk_merge_f64 of the shards' lists is exact).
- * radad_knn_last_excl_scan synchronises with the most recent such call: its batch size (may be NULL), route and the number of
- * queries the exact kernel answered (all of them on the exact route).  0 / RADAD_EXCL_SCAN_EXACT / 0 before the first one. */
+ * Per-query sets: radad_knn_search_excl_scan_pq below (a bias is per row, not per (row, query), so that call filters what the scan
+ * emitted instead).  Not offered: a begin / finish pair (a shard's result here IS its exact admissible top k: radad_topk_merge_f64 of
+ * the shards' lists is exact).
+ * radad_knn_last_excl_scan synchronises with the most recent such call -- this one or radad_knn_search_excl_scan_pq, whichever ran
+ * last: its batch size (may be NULL), route and the number of queries the exact kernel answered (all of them on the exact route).
+ * 0 / RADAD_EXCL_SCAN_EXACT / 0 before the first one. */
 #define RADAD_EXCL_SCAN_TILE 0
 #define RADAD_EXCL_SCAN_EXACT 1
 int radad_knn_search_excl_scan(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k,
@@ -421,6 +423,46 @@ int radad_knn_search_excl_scan(radad_knn_t h, const void* q_dev, int q_dtype, in
                                float* out_dist_dev /*[nq,k]*/, int64_t* out_idx_dev /*[nq,k]*/, double* out_key_dev /*[nq,k] or NULL*/,
                                void* stream);
 int radad_knn_last_excl_scan(radad_knn_t h, int64_t* n_queries, int* route, int* n_exact);
+
+/* One exclusion set PER QUERY on the certified tile scan: leave-one-speaker-out over a flat store, where one tag is carried by
+ * hundreds or thousands of rows and no k_fetch <= 1024 lets radad_knn_search_excl_pq prove a query (k_fetch >= k + m * c).
+ * Contract: radad_knn_search_excl_pq's without k_fetch -- row r is admissible for query j iff row_tags[r] is not among the first cnt_j
+ * entries of q_tags[j, :], cnt_j = q_tag_counts[j] clamped on the device to [0, m] (NULL = m for every query), any order, repeats
+ * allowed; per query the k best admissible rows ordered by (float64 key, lower id), out_dist the key rounded once, id -1 / NaN / NaN
+ * where the query has fewer admissible rows; the result of a query is a function of that query alone.
+ * Routes: knn_excl_scan_route's, as radad_knn_search_excl_scan, reported by radad_knn_last_excl_scan:
+ *   RADAD_EXCL_SCAN_TILE   the PLAIN search's plan and launches -- its RSC, no per-call bias, sample pre-pass, phases, K split, early
+ *                 abandon -- over candidate buffers of 4096 entries per query (the handle's widened form, whatever its tuning state).
+ *                 The scan emits excluded rows like any other; k_excl_pq_scrub (one workgroup per query, the query's tags in LDS)
+ *                 clears a query's excluded entries (row -> no entry, score -> -inf) out of the sample's lists before the first
+ *                 floor is taken from them, out of the candidate buffers before every floor between two phases, and before the
+ *                 float64 re-rank: phases + 1 launches (none when m == 0; a query whose count is 0 leaves at once).  So an excluded
+ *                 row never counts towards a floor and never reaches the re-rank; the floors stay lower bounds for admissible rows,
+ *                 which is all the abandon needs.  A query whose emitted rows -- excluded ones included -- exceed its buffer is
+ *                 rejected by the certificate like any overflow; rejected queries go, driven from the device, to the per-query
+ *                 float64 exact kernel (k_exact_scan_any<true, true>) with the query tags (m == 0: the bitmap form, every bit set).
+ *   RADAD_EXCL_SCAN_EXACT  every other shape: that exact kernel for every query.  Correct everywhere; it streams the store once per
+ *                 group of <= 8 queries, so it is slow for large batches.
+ * m == 0, or every count 0: ids and float64 keys of filled slots are those of radad_knn_search_f64 on the same handle, bit for bit;
+ * the padding is this family's.
+ * Like radad_knn_search_excl_scan the call posts no certificate report, takes no turn off the tuning state and leaves
+ * radad_knn_tuning_info as it found it; radad_knn_last_recheck / _last_certificate keep describing the last plain search; it may
+ * build the plane.  After it radad_knn_last_emitted counts the rows the scan EMITTED per query, the ones the scrub cleared included.
+ * Errors: RADAD_EINVAL before anything is enqueued for m outside [0, RADAD_EXCL_PQ_MAX_TAGS], for m > 0 with NULL q_tags_dev or
+ * row_tags_dev, on a handle with a begun search, or beyond the width x k limit; RADAD_ESTATE on an empty store; nq == 0 returns
+ * RADAD_OK.  Stream-ordered and serialised like every search.
+ * Measured (tools/bench_excl_scan_pq.py, profiles/README.md; 1 M x 512 cosine, 1024 queries, k = 10, every query excluding its own
+ * speaker of c rows): 1.19 / 1.26 / 1.58 ms at c = 0 / 200 / 1500 against 0.97 / 1.04 / 1.07 ms for the plain search of the same
+ * handle (+22 / +21 / +48 %), all queries certified in the scan; radad_knn_search_excl_pq at k_fetch = min(1024, k + c) takes 469 ms
+ * at c = 200 (fp32 tile kernels at k_fetch = 210) and 4.6 s at c = 1500 (every query in the exact pass).  The +22 % at c = 0 is the
+ * 4096-entry buffers, not the scrub: they let the 1 M-row store through in ONE scan launch behind the sample's floor (knn_hi_one_go)
+ * where the plain search's 1024-entry buffers take two, and that launch emits ~1070 rows per query.
+ * Not offered: a begin / finish pair; a batch-wide set combined with per-query sets; a certified route for <= 16 queries. */
+int radad_knn_search_excl_scan_pq(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k,
+                                  const int64_t* row_tags_dev /*[ntotal], by id - id_base*/,
+                                  const int64_t* q_tags_dev /*[nq, m] row-major; any order, duplicates allowed*/, int m,
+                                  const int32_t* q_tag_counts_dev /*[nq] or NULL = m for every query*/, float* out_dist_dev /*[nq,k]*/,
+                                  int64_t* out_idx_dev /*[nq,k]*/, double* out_key_dev /*[nq,k] or NULL*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Inverted-file flat index: faiss.IndexIVFFlat(IndexFlatL2 quantiser, d, nlist, METRIC_L2), the reference's optional

@@ -92,6 +92,8 @@ SIGNATURES = {
     "radad_knn_search_excl_scan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "radad_knn_last_excl_scan": (C.c_int, [C.c_void_p, c_i64p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "radad_knn_search_excl_scan_pq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "radad_excl_merge_certify": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "radad_knn_scan_geometry": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),

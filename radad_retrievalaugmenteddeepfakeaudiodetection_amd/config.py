@@ -73,7 +73,8 @@ class Config:
         self.exclusion_k_fetch = None       # ... size of the certified search in front of the exact pass (None = top_k + 10)
         self.exclusion_in_scan = False      # True (with exact_exclusion, scope "batch", flat stores): the admission test inside the certified tile scan -- for exclusion sets that cover most of the store (training_file_ids); no k_fetch
         self.exclusion_scope = "batch"      # "query" (needs exact_exclusion, or ivf_exact_exclusion on an IVF store): clip i excludes its OWN basename only, so what it retrieves does not depend on its batch
-        self.ivf_exact_exclusion = False    # True, IVF stores: the same among the rows of the probed lists (exclusion inside the list scans; top_k <= 26)
+        self.exclusion_per_query_in_scan = False   # True (with exact_exclusion, scope "query", flat stores): the per-query search on the certified tile scan -- for basenames carried by hundreds of rows; no k_fetch
+        self.ivf_exact_exclusion = False   # True, IVF stores: the same among the rows of the probed lists (exclusion inside the list scans; top_k <= 26)
 
     def update(self, **kwargs):
         """config.py:109-115."""

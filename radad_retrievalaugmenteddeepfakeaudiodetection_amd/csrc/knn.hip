@@ -3336,9 +3336,68 @@ static auto knn_hi_kernel(int rsc, bool sample, bool abandon = false) -> void (*
     }
 }
 
+// ---- per-query exclusion sets on the tile scan (radad_knn_search_excl_scan_pq): the scrub ---------------------------------------------
+// The scan cannot test a per-(row, query) rule, and does not have to: every floor it runs with is computed BETWEEN its launches by
+// k_floor_from_sample / k_kth_floor from (score, row) entries in buffers, and the result by k_merge_refine<true> from the same
+// buffers.  This kernel clears a query's excluded entries out of such a buffer in front of each of those readers: row = IDX_SENTINEL
+// AND score = -inf (k_kth_floor reads scores only).  One workgroup per query; the query's <= 64 live tags sit in LDS; every thread
+// walks entries i, i + 256, ... of the first min(count, cap) (cnt NULL: all cap -- the sample's lists), loads the tag of each entry
+// that is not a hole already and compares it with the tags.  Idempotent: a cleared entry is a hole the next launch skips.  The
+// counters are not touched: overflow stays "the scan emitted more than the buffer holds", excluded rows included.  A query with no
+// live tag leaves at once.  Plain C++ stores.
+struct ExclScrubParams {
+    float* score = nullptr;             // [nq][cap]
+    int* idx = nullptr;                 // [nq][cap] rows of the store, IDX_SENTINEL = no entry
+    const int* cnt = nullptr;           // [nq] entries emitted (may exceed cap), or NULL = every buffer holds cap entries
+    int cap = 0;
+    const int64_t* tags = nullptr;      // [ntotal] row tags
+    int64_t ntotal = 0;
+    const int64_t* q_tags = nullptr;    // [nq, m]
+    const int* q_cnt = nullptr;         // [nq] or NULL = m
+    int m = 0;
+};
+static_assert(std::is_trivially_copyable_v<ExclScrubParams>, "kernel argument");
+__global__ __launch_bounds__(256) void k_excl_pq_scrub(ExclScrubParams p) {
+    __shared__ int64_t s_tag[RADAD_EXCL_PQ_MAX_TAGS];
+    const int64_t q = blockIdx.x;
+    const int cnt = min(max(p.q_cnt ? p.q_cnt[q] : p.m, 0), min(p.m, RADAD_EXCL_PQ_MAX_TAGS));
+    if (cnt == 0) return;                                       // (workgroup-uniform)
+    if ((int)threadIdx.x < cnt) s_tag[threadIdx.x] = p.q_tags[q * p.m + threadIdx.x];
+    __syncthreads();
+    const int ne = p.cnt ? min(max(p.cnt[q], 0), p.cap) : p.cap;
+    float* sc = p.score + q * p.cap;
+    int* id = p.idx + q * p.cap;
+    for (int i = threadIdx.x; i < ne; i += 256) {
+        const int row = id[i];
+        if (row == IDX_SENTINEL || row < 0 || row >= p.ntotal) continue;
+        const int64_t t = p.tags[row];
+        bool excluded = false;
+        for (int e = 0; e < cnt; ++e) excluded |= s_tag[e] == t;
+        if (excluded) { id[i] = IDX_SENTINEL; sc[i] = -INFINITY; }
+    }
+}
+
+// what radad_knn_search_excl_scan_pq hands to the tile scan: the rule to scrub with, the grid its planner gave, and (out) the launches made
+struct ScanScrub {
+    const ExclRule* rule = nullptr;
+    int64_t grid = 0;
+    int launched = 0;
+};
+static void knn_launch_scrub(radad_knn_t h, ScanScrub* s, float* score, int* idx, const int* cnt, int cap, hipStream_t st) {
+    ExclScrubParams x;
+    x.score = score; x.idx = idx; x.cnt = cnt; x.cap = cap;
+    x.tags = s->rule->tags; x.ntotal = h->ntotal; x.q_tags = s->rule->q_tags; x.q_cnt = s->rule->q_cnt; x.m = s->rule->m();
+    hipLaunchKernelGGL(k_excl_pq_scrub, dim3((unsigned)s->grid), dim3(256), 0, st, x);
+    ++s->launched;
+}
+
 // row_bias: the bias array of a biased plan (p.biased), or NULL = the handle's own (radad_knn_search_excl_scan hands in its per-call
 // array: NaN for the rows it excludes)
-static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, hipStream_t st, const float* row_bias = nullptr) {
+// scrub: NULL (every search but radad_knn_search_excl_scan_pq: nothing below changes), or the per-query rule -- k_excl_pq_scrub then
+// runs on the sample's entries before k_floor_from_sample, on the candidate buffers before every k_kth_floor, and once more behind
+// the last launch, so that whoever reads the buffers next (the re-rank) finds them scrubbed
+static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, hipStream_t st, const float* row_bias = nullptr,
+                            ScanScrub* scrub = nullptr) {
     const int64_t nq = p.nq;
     float* ps = ws_at<float>(h, L.ps);
     int* pi = ws_at<int>(h, L.pi);
@@ -3397,6 +3456,7 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
         sp.kacc = h->kacc; sp.kflag = h->kflag;
         hipLaunchKernelGGL(sample, dim3((unsigned)(sq_grid * sp.n_splits * sp.ksplit)), dim3(KW_THREADS), lds, st, sp);
         const int n_ent = sp.n_splits * KW_SAMPLE_LIST;
+        if (scrub) knn_launch_scrub(h, scrub, sp.part_score, sp.part_idx, nullptr, n_ent, st);
         hipLaunchKernelGGL(k_floor_from_sample, dim3((unsigned)nq), dim3(RF_THREADS), (size_t)n_ent * 4 + 1040, st, (const float*)sp.part_score,
                            (const int*)sp.part_idx, n_ent, p.ksel, (const float*)eps, thr_init);
         wp.thr_init = thr_init;
@@ -3406,6 +3466,7 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
     for (size_t i = 0; i + 1 < r.size(); ++i) {       // rows [r0, r1) of the store, one full round (or two) of workgroups
         const int64_t r0 = r[i], r1 = r[i + 1];
         if (r0 > 0) {
+            if (scrub) knn_launch_scrub(h, scrub, ps, pi, wp.cand_cnt, p.emit_cap, st);
             KthParams kp;
             kp.score = ps; kp.cnt = wp.cand_cnt; kp.cap = p.emit_cap; kp.k = p.k; kp.eps = eps; kp.floor_io = thr_init;
             hipLaunchKernelGGL(k_kth_floor, dim3((unsigned)nq), dim3(RF_THREADS), (size_t)p.emit_cap * 4 + 1040, st, kp);
@@ -3446,6 +3507,7 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
         hipLaunchKernelGGL(launch_fn, dim3((unsigned)(gq_grid * gs * rp.ksplit)), dim3(KW_THREADS), launch_lds, st, rp);
         h->prof.end(st);
     }
+    if (scrub) knn_launch_scrub(h, scrub, ps, pi, wp.cand_cnt, p.emit_cap, st);     // (for the re-rank)
 #ifdef RADAD_DEBUG_HOOKS
     if (wp.stamps) {
         std::vector<unsigned long long> hs(8 * 4096);
@@ -4039,6 +4101,104 @@ static int knn_search_excl_scan_locked(radad_knn_t h, const void* q_in, int q_dt
     return RADAD_OK;
 }
 
+// ---- per-query exclusion sets on the certified tile scan (radad_knn_search_excl_scan_pq) ----------------------------------------------
+// Routes, facts, plan and scrub launches are knn_excl_scan_pq_plan's (knn_plan.h).  Tile route: the PLAIN search's preparation, scan
+// launches (early abandon included) and re-rank over widened candidate buffers, with k_excl_pq_scrub in front of every reader of the
+// sample's entries and of the candidate buffers (knn_scan_hi_tile); the queries the certificate rejects -- overflow of a buffer by a
+// large crowd among them -- go to the per-query exact kernel with the query tags.  Like the sibling above: KnnTuning is read (hi_skip)
+// and never written, no report is posted, no turn is taken.
+static int knn_search_excl_scan_pq_locked(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, const ExclRule& r,
+                                          float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, hipStream_t st) {
+    int rc = knn_order_behind_last(h, st);
+    if (rc) return rc;
+    ExclScanPqPlan X = knn_excl_scan_pq_plan(knn_store_facts(h), nq, k, r.m(), h->tune.hi_skip);
+    bool tile = X.route == RADAD_EXCL_SCAN_TILE;
+    if (tile && !knn_ensure_hi(h, st, true)) {                     // (a plane that cannot be allocated switches itself off: exact route)
+        tile = false;
+        X = knn_excl_scan_pq_plan(knn_store_facts(h), nq, k, r.m(), h->tune.hi_skip);
+        RADAD_REQUIRE(X.route == RADAD_EXCL_SCAN_EXACT, "radad_knn_search_excl_scan_pq: a store without a plane planned the tile route");
+    }
+    if (!tile && !knn_ensure_hi(h, st, false)) { radad_set_error("store statistics could not be computed"); return RADAD_EHIP; }
+    ScanPlan p = X.plan;
+    p.mu = (p.hi_q && !h->f16) ? h->cmu : nullptr;                 // the plain search's instantiation (knn_plan_scan)
+    p.biased = p.hi_q && (p.l2 || p.mu);
+    const SearchLayout L = knn_search_layout(X.facts, p, q_dtype);
+    if (L.bytes > h->ws_bytes) {
+        RADAD_HIP_CHECK(hipDeviceSynchronize());
+        rc = knn_workspace(h, L.bytes);
+        if (rc) return rc;
+    }
+    // m == 0: nothing is excluded and the tags may be NULL -- the per-query exact kernel reads a tag per row, so the rejected queries of
+    // such a call take the bitmap form with every bit set
+    const bool no_rule = r.m() == 0;
+    const ExclScanLayout B = knn_excl_scan_layout(X.facts, RADAD_EXCL_SCAN_EXACT);
+    if (no_rule) {
+        rc = knn_excl_reserve(h, B.bytes);
+        if (rc) return rc;
+    }
+    rc = knn_ensure_xarrive(h, nq, st);
+    if (rc) return rc;
+    h->last_emit_nq = 0;                                           // (the workspace no longer holds the last plain tile scan's counters)
+    h->last_xs_nq = 0;
+    unsigned long long* admit = no_rule ? reinterpret_cast<unsigned long long*>((char*)h->excl_ws + B.admit) : nullptr;
+    if (no_rule) RADAD_HIP_CHECK(hipMemsetAsync(admit, 0xff, (size_t)B.n_words * sizeof(unsigned long long), st));
+    const float* q_use = knn_prepare_queries(h, p, L, q_in, q_dtype, st);      // (clears the listed-query counter and the candidate counters)
+    RADAD_HIP_CHECK(hipGetLastError());
+    int* flag_count = ws_at<int>(h, L.fcount);
+    int* flag_sel = ws_at<int>(h, L.fsel);
+
+    if (tile) {
+        ScanScrub scrub;
+        scrub.rule = &r; scrub.grid = X.scrub_grid;
+        h->prof.next_search();
+        rc = knn_scan_hi_tile(h, p, L, st, nullptr, X.scrub_launches > 0 ? &scrub : nullptr);
+        if (rc) return rc;
+        RADAD_HIP_CHECK(hipGetLastError());
+        RADAD_REQUIRE(scrub.launched == X.scrub_launches && h->last_scan_phases == X.phases,
+                      "radad_knn_search_excl_scan_pq: %d scrub launches over %d phases, planned %d over %d", scrub.launched, h->last_scan_phases,
+                      X.scrub_launches, X.phases);
+        SearchCtx c;
+        c.valid = true;
+        c.nq = nq; c.k = k; c.l2 = p.l2; c.n_parts = p.n_parts; c.plen = p.plen; c.cap = p.cap; c.xgroup = p.xgroup;
+        c.emit = true; c.use_floor = true; c.hi_tile = true; c.canonical = true; c.q_use = q_use; c.ws = L;
+        h->last_o_cnt = L.cnt; h->last_o_thr = L.thr; h->last_emit_nq = nq;
+        rc = knn_rerank(h, c, nullptr, out_dist_dev, out_idx_dev, out_key_dev, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_excl_scan_pad, dim3((unsigned)ceil_div64(nq * k, 256)), dim3(256), 0, st, out_dist_dev, (const int64_t*)out_idx_dev,
+                           out_key_dev, nq * k);
+    } else {
+        hipLaunchKernelGGL(k_excl_scan_list_all, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, st, flag_sel, flag_count, nq);
+    }
+    RADAD_HIP_CHECK(hipGetLastError());
+
+    // ---- the listed queries: the float64 exact kernel with each query's own tags, sized and driven by the device-side count; no report
+    {
+        ExactParams x;
+        x.db = h->rows; x.db_f16 = h->f16; x.q = q_use; x.sel = flag_sel; x.count = flag_count;
+        x.n = h->ntotal; x.dim = h->dim; x.k = k; x.l2 = p.l2; x.group = p.xgroup;
+        x.slice_rows = ceil_div64(h->ntotal, KX_SLICES);
+        x.pkey = ws_at<double>(h, L.xk); x.pidx = ws_at<int>(h, L.xi); x.id_base = h->id_base;
+        x.out_dist = out_dist_dev; x.out_idx = out_idx_dev; x.out_key = out_key_dev;
+        x.host_stats = nullptr;
+        x.arrive = h->xarrive;
+        if (no_rule) x.admit = admit;
+        else { x.row_tags = r.tags; x.q_tags = r.q_tags; x.q_cnt = r.q_cnt; x.m = r.m(); }
+        const auto kern = no_rule ? k_exact_scan_excl : k_exact_scan_excl_pq;
+        const size_t xlds = knn_exact_dyn_lds_bytes(h->dim, k);
+        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
+        const unsigned gy = k <= KNN_F16_MAX_K ? KX_GROUPS_Y : 8 * KX_GROUPS_Y;
+        x.nslots = (int)knn_exact_slots(nq, k, p.xgroup);
+        for (int64_t s0 = 0; s0 < nq; s0 += x.nslots) {            // (launches past the device-side count leave at once)
+            x.slot0 = (int)s0;
+            hipLaunchKernelGGL(kern, dim3(KX_SLICES, gy), dim3(KX_THREADS), xlds, st, x);
+        }
+        RADAD_HIP_CHECK(hipGetLastError());
+    }
+    RADAD_HIP_CHECK(hipMemcpyAsync(h->host_count + 17, flag_count, sizeof(int), hipMemcpyDeviceToHost, st));
+    h->last_xs_nq = nq; h->last_xs_route = tile ? RADAD_EXCL_SCAN_TILE : RADAD_EXCL_SCAN_EXACT;
+    return RADAD_OK;
+}
+
 extern "C" {
 
 int radad_knn_search_begin(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, float* kth_lower_bound_dev, void* stream) {
@@ -4125,6 +4285,23 @@ int radad_knn_search_excl_scan(radad_knn_t h, const void* q_dev, int q_dtype, in
     if (h->ntotal == 0) { radad_set_error("radad_knn_search_excl_scan: the store is empty"); return RADAD_ESTATE; }
     return knn_search_excl_scan_locked(h, q_dev, q_dtype, nq, k, knn_excl_rule_batch(row_tags_dev, excl_sorted_dev, n_excl), out_dist_dev,
                                        out_idx_dev, out_key_dev, (hipStream_t)stream);
+}
+
+int radad_knn_search_excl_scan_pq(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, const int64_t* row_tags_dev,
+                                  const int64_t* q_tags_dev, int m, const int32_t* q_tag_counts_dev, float* out_dist_dev, int64_t* out_idx_dev,
+                                  double* out_key_dev, void* stream) {
+    int bad = knn_excl_check_args("radad_knn_search_excl_scan_pq", h, q_dtype, nq, 0, k, k, nullptr, nullptr, 0);
+    if (bad) return bad;
+    ExclRule r;
+    bad = knn_excl_pq_rule("radad_knn_search_excl_scan_pq", row_tags_dev, q_tags_dev, m, q_tag_counts_dev, &r);
+    if (bad) return bad;
+    if (nq == 0) return RADAD_OK;
+    RADAD_REQUIRE(q_dev && out_dist_dev && out_idx_dev, "radad_knn_search_excl_scan_pq: NULL buffer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_search_excl_scan_pq: a radad_knn_search_begin on this handle has not been finished");
+    if (h->ntotal == 0) { radad_set_error("radad_knn_search_excl_scan_pq: the store is empty"); return RADAD_ESTATE; }
+    return knn_search_excl_scan_pq_locked(h, q_dev, q_dtype, nq, k, r, out_dist_dev, out_idx_dev, out_key_dev, (hipStream_t)stream);
 }
 
 int radad_knn_last_excl_scan(radad_knn_t h, int64_t* n_queries, int* route, int* n_exact) {

@@ -487,6 +487,38 @@ static ExclScanLayout knn_excl_scan_layout(const StoreFacts& s, int route) {
     return L;
 }
 
+// ---- per-query exclusion sets on the certified tile scan (radad_knn_search_excl_scan_pq) ------------------------------------------
+// The routes are knn_excl_scan_route's.  The tile route runs the PLAIN plan -- no per-call bias, the plain search's RSC -- from a copy
+// of the store's facts with the candidate buffers widened (cap_boost 4 whatever the handle's tuning state says: the scan emits a
+// query's excluded rows too, they occupy slots until the scrub clears them, and a speaker of 1500 rows must fit), and between the
+// scan's launches k_excl_pq_scrub clears every query's excluded entries out of the buffers the floors and the re-rank read:
+//   1 launch on the sample pre-pass's entries (before k_floor_from_sample), 1 before each k_kth_floor between two phases, 1 before
+//   the re-rank: 1 + (phases - 1) + 1; none on the exact route, none when m == 0.  One workgroup per query.
+constexpr int KNN_EXCL_SCAN_PQ_CAP_BOOST = 4;
+struct ExclScanPqPlan {
+    int route = RADAD_EXCL_SCAN_EXACT;
+    StoreFacts facts;            // what `plan` and the workspace layout are made from: the caller's with the forced cap_boost
+    ScanPlan plan;               // tile route: the plain search's plan over `facts` (mu / biased: the caller's, as for any plan);
+                                 // exact route: the plan the queries are prepared and the workspace laid out with
+    int phases = 0;              // tile route: launches of the scan proper (knn_hi_phases)
+    int scrub_launches = 0;
+    int64_t scrub_grid = 0;      // workgroups of each scrub launch
+};
+static ExclScanPqPlan knn_excl_scan_pq_plan(const StoreFacts& s, int64_t nq, int k, int m, int fp32_searches_left) {
+    ExclScanPqPlan x;
+    x.route = knn_excl_scan_route(s, nq, k, fp32_searches_left);
+    x.facts = s;
+    x.facts.cap_boost = KNN_EXCL_SCAN_PQ_CAP_BOOST;
+    const bool tile = x.route == RADAD_EXCL_SCAN_TILE;
+    const TileEligibility t = knn_tile_eligibility(x.facts, nq, k, KNN_MARGIN);
+    x.plan = knn_finish_plan(x.facts, nq, k, KNN_MARGIN, t, tile, false);
+    if (tile) {
+        x.phases = (int)knn_hi_phases(s.ntotal, nq, (int64_t)8 * x.plan.s_splits * KW_M, knn_hi_one_go(x.plan, s.ntotal)).size() - 1;
+        if (m > 0) { x.scrub_launches = 1 + (x.phases - 1) + 1; x.scrub_grid = nq; }
+    }
+    return x;
+}
+
 // ---- adaptive tuning --------------------------------------------------------------------------------------------------------------
 // What a handle does when the certificate rejects more than a quarter of a batch of >= 64 queries: re-decide the plane if rows were
 // appended since it was decided, else widen the candidate buffers once (cap_boost 1 -> 4), else leave the certified f16 kernels for

@@ -146,6 +146,13 @@ class HotPathPipeline:
         if in_scan and per_query:
             raise ValueError("config.exclusion_in_scan excludes one set for the batch (a bias is per row, not per (row, query)): "
                              "config.exclusion_scope 'query' takes search_excluding_per_query, without exclusion_in_scan")
+        # config.exclusion_per_query_in_scan (opt-in, with exact_exclusion, scope "query", a flat store): the per-query search on the
+        # certified tile scan (VectorDatabase.search_excluding_per_query_in_scan) -- for basenames carried by so many rows that no
+        # k_fetch proves a query
+        pq_in_scan = bool(getattr(self.config, "exclusion_per_query_in_scan", False))
+        if pq_in_scan and exclude_self and not (exact_excl and per_query):
+            raise ValueError("config.exclusion_per_query_in_scan needs config.exact_exclusion and config.exclusion_scope 'query' on a flat "
+                             "store (one set for the batch inside the scan is config.exclusion_in_scan)")
         if per_query and query_paths is None:
             raise ValueError("config.exclusion_scope 'query' needs query_paths: a query excludes its own basename")
         if per_query and len(query_paths) != B:
@@ -173,6 +180,8 @@ class HotPathPipeline:
                     dist_t, chosen_t = self.vector_db.search_probed_excluding_per_query(q, K, own)
                 else:
                     dist_t, chosen_t = self.vector_db.search_probed_excluding(q, K, excl)
+            elif per_query and pq_in_scan:
+                dist_t, chosen_t = self.vector_db.search_excluding_per_query_in_scan(q, K, own)
             elif per_query:
                 k_fetch = getattr(self.config, "exclusion_k_fetch", K + 10)
                 dist_t, chosen_t = self.vector_db.search_excluding_per_query(q, K, own, k_fetch=K + 10 if k_fetch is None else int(k_fetch))

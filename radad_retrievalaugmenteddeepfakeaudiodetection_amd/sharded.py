@@ -239,6 +239,12 @@ class ShardedSearch:
                          "is already its exact admissible top k, so ShardedSearch(local_search=<that call with return_f64>).search(q, k) "
                          "merges the shards' lists exactly (INTEGRATION.md); search_excluding is the certified over-fetch over shards")
 
+    def search_excluding_per_query_in_scan(self, *args, **kwargs):
+        raise ValueError("search_excluding_per_query_in_scan has no sharded form of its own: a shard's result of "
+                         "HipFlatIndex.search_excluding_per_query_in_scan is already its exact admissible top k, so "
+                         "ShardedSearch(local_search=<that call with return_f64>).search(q, k) merges the shards' lists exactly "
+                         "(INTEGRATION.md); search_excluding with query_tags_local is the certified over-fetch over shards")
+
     def search_excluding(self, q_local, k: int, exclude_tags_local=None, k_fetch=None, return_all: bool = False,
                          query_tags_local=None, query_tag_counts_local=None):
         """The exclusion-aware search (HipFlatIndex.search_excluding) over the row shards: q_local [Q_r, D], exclude_tags_local int64

@@ -307,9 +307,27 @@ class HipFlatIndex:
                                                             _lib.stream_ptr(q.device)), "radad_knn_search_excl_scan")
         return (D, I, K64) if return_f64 else (D, I)
 
+    def search_excluding_per_query_in_scan(self, q, k: int, row_tags, query_tags, query_tag_counts=None, return_f64: bool = False):
+        """search_excluding_per_query's result without a k_fetch (radad_knn_search_excl_scan_pq): the plain certified tile scan, with
+        each query's excluded rows cleared out of the scan's buffers before every floor and before the re-rank -- the call for tags
+        carried by hundreds or thousands of rows (leave-one-speaker-out), where no k_fetch proves a query.  Arguments and outputs as
+        search_excluding_per_query.  Batches the plain search would not give to the tile scan (<= 16 queries, small stores, k > 128,
+        dim % 64 != 0) take the per-query float64 pass for every query: last_excl_scan()["route"]."""
+        import torch
+        q, q_dtype = _prep_queries(q, self.d)
+        k = int(k)
+        row_tags, query_tags, counts, m = _prep_query_tags(row_tags, query_tags, query_tag_counts, q.shape[0], self.ntotal)
+        D, I, K64 = _alloc_out(q, max(k, 0), return_f64)
+        with torch.cuda.device(q.device):
+            _lib.check(self._lib.radad_knn_search_excl_scan_pq(self._h, q.data_ptr(), q_dtype, q.shape[0], k, _ptr(row_tags),
+                                                               _ptr(query_tags), m, _ptr(counts), D.data_ptr(), I.data_ptr(), _ptr(K64),
+                                                               _lib.stream_ptr(q.device)), "radad_knn_search_excl_scan_pq")
+        return (D, I, K64) if return_f64 else (D, I)
+
     def last_excl_scan(self):
-        """{"queries", "route", "exact"} of the most recent search_excluding_in_scan: its batch size, "tile" or "exact", and how many
-        of its queries the exact float64 kernel answered (radad_knn_last_excl_scan; synchronises with that search)"""
+        """{"queries", "route", "exact"} of the most recent search_excluding_in_scan or search_excluding_per_query_in_scan: its batch
+        size, "tile" or "exact", and how many of its queries the exact float64 kernel answered (radad_knn_last_excl_scan; synchronises
+        with that search)"""
         nq, route, ex = C.c_int64(), C.c_int(), C.c_int()
         _lib.check(self._lib.radad_knn_last_excl_scan(self._h, C.byref(nq), C.byref(route), C.byref(ex)), "radad_knn_last_excl_scan")
         return {"queries": nq.value, "route": "tile" if route.value == _lib.EXCL_SCAN_TILE else "exact", "exact": ex.value}
@@ -717,6 +735,10 @@ class HipIVFFlatIndex:
         raise ValueError("search_excluding_in_scan is the flat store's search: an IVF index has the admission test inside its own list "
                          "scans (search_probed_excluding)")
 
+    def search_excluding_per_query_in_scan(self, *args, **kwargs):
+        raise ValueError("search_excluding_per_query_in_scan is the flat store's search: an IVF index has the per-(row, query) test "
+                         "inside its own list scans (search_probed_excluding_per_query)")
+
     MAX_K_PROBED = 26  # csrc/ivf.inc: the largest k the list scans hold (k + 6 <= 32 entries per (query, list))
 
     def search_probed_excluding(self, q, k: int, row_tags, exclude_tags):
@@ -1016,6 +1038,23 @@ class VectorDatabase:
             query_tag_counts = torch.as_tensor(query_tag_counts, dtype=torch.int32).to(q.device)
         return self.index.search_excluding_per_query(q, k, self.row_tags_device(), query_tags, query_tag_counts,
                                                      k_fetch=min(k_fetch, _lib.KNN_MAX_K))
+
+    def search_excluding_per_query_in_scan(self, query_vectors, k: int = None, query_tags=None, query_tag_counts=None):
+        """search_excluding_per_query's result on the certified tile scan (HipFlatIndex.search_excluding_per_query_in_scan): no k_fetch
+        -- the call when one basename tag is carried by hundreds or thousands of rows (a query excluding its own speaker's files).
+        Arguments and outputs as search_excluding_per_query.  Flat stores only: an IVF store has search_probed_excluding_per_query, a
+        row-sharded one merges its shards' results."""
+        import torch
+        q, k, _, _, _ = self._excluding_args(
+            HipFlatIndex, "search_excluding_per_query_in_scan is flat and single-handle only (vector_db_index_type 'L2' or 'IP'); an IVF "
+            "store has search_probed_excluding_per_query", query_vectors, k, None)
+        if k <= 0:
+            return self._no_hits(q)
+        if query_tags is not None:
+            query_tags = torch.as_tensor(query_tags, dtype=torch.int64).to(q.device)
+        if query_tag_counts is not None:
+            query_tag_counts = torch.as_tensor(query_tag_counts, dtype=torch.int32).to(q.device)
+        return self.index.search_excluding_per_query_in_scan(q, k, self.row_tags_device(), query_tags, query_tag_counts)
 
     def search_probed_excluding(self, query_vectors, k: int = None, exclude_tags=None):
         """IVF stores: the k nearest rows of the probed lists (config.vector_db_nprobe, vector_database.py:174-179) whose basename tag
