@@ -464,6 +464,56 @@ int radad_knn_search_excl_scan_pq(radad_knn_t h, const void* q_dev, int q_dtype,
                                   const int32_t* q_tag_counts_dev /*[nq] or NULL = m for every query*/, float* out_dist_dev /*[nq,k]*/,
                                   int64_t* out_idx_dev /*[nq,k]*/, double* out_key_dev /*[nq,k] or NULL*/, void* stream);
 
+/* Certified range search: EVERY row within a radius of each query, exactly -- faiss's index.range_search on the flat store.  The
+ * reference has only the top-k call (vector_database.py:181) and audits leakage and self-retrieval by file BASENAME
+ * (validate_no_leakage, pipeline.py:1105-1110; the exclude_self path of retrieve_similar_vectors, pipeline.py:478-515): a re-encoded
+ * or renamed copy of a clip passes both.  "Which stored rows have cosine > 0.98 with this clip" is a range search; over-fetching a
+ * guessed k and cutting afterwards is wrong whenever more than k copies exist.
+ * Membership: row r is within the radius of query j iff its float64 key passes the threshold STRICTLY, as faiss does --
+ *   L2: sum (q - y)^2 < (double)radius;   IP / cosine: q.y > (double)radius
+ * -- the key being the value radad_knn_search_f64 reports in out_key, same sign convention; cosine normalises the query in fp32 as
+ * every search does; the stored rows are what radad_knn_reconstruct returns.  An infinite radius is legal and means every row (+inf
+ * for L2, -inf for IP).
+ * Outputs, M = max_per_query: out_count[j] is the EXACT number of rows within the radius, also when it exceeds M; slots
+ * 0 .. min(count, M) - 1 hold the best rows ordered by (key, lower id), id = id_base + row, out_dist the key rounded once; the
+ * remaining slots hold -1 / NaN / NaN (the padding of the _excl family, not +-inf).
+ * Routes, chosen on the host (knn_range_plan, knn_plan.h), reported by radad_knn_last_range:
+ *   RADAD_RANGE_TILE   exactly when knn_excl_scan_route says tile at k = 1, whatever M is: 17 or more queries, dim % 64 == 0, the
+ *                 plane on, at least 16 384 rows, the handle not on its fp32 fallback.  The plain search's query preparation, RSC
+ *                 and bias; k_range_floor writes the admission floor T - eps(q), two ulps lower (T = radius for IP / cosine,
+ *                 -radius for L2; eps(q) the scan's measured error bound): exact score >= T implies scan score >= T - eps, so every
+ *                 row within the radius is emitted.  No floor is derived from rows: no sample pre-pass, no floor kernels, ONE scan
+ *                 launch over 4096-entry candidate buffers, early abandon included (it compares the scan's partial sums with the
+ *                 floor the emit uses, whatever the floor came from).  k_range_refine, one workgroup per query, re-scores ALL
+ *                 emitted rows in float64 from the stored rows, applies the strict test, counts, sorts the rows that pass by
+ *                 (key, id) in LDS (48 KB) and writes the best M.  A query that emitted more than 4096 rows proves nothing: it goes,
+ *                 driven from the device, to the exact range kernel.
+ *   RADAD_RANGE_EXACT  every other shape: k_exact_scan_any<false, false, true> for every query -- the float64 key of every row, the
+ *                 strict test before the list insertion, one count per wave and slice added to out_count, top-M lists merged as in
+ *                 any exact pass.  Correct everywhere; it streams the store once per group of <= 8 queries.
+ * The call posts no certificate report, takes no turn off the tuning state and leaves radad_knn_tuning_info, radad_knn_last_recheck
+ * and radad_knn_last_certificate as it found them; it may build the plane.  After a tile-route call radad_knn_last_emitted reports
+ * the rows emitted per query and the floors T - eps, and radad_knn_last_abandon the one launch's tile tasks.
+ * Errors, before anything is enqueued (outputs untouched, the handle usable): RADAD_EINVAL for M outside [1, RADAD_KNN_MAX_K], beyond
+ * the width x k limit with M for k, for a NaN radius, NULL out_count / out_dist / out_idx, or a handle with a begun search;
+ * RADAD_ESTATE on an empty store; nq == 0 returns RADAD_OK.  Stream-ordered and serialised like every search.
+ * radad_knn_last_range synchronises with the most recent range call: its batch size (may be NULL), route and the number of queries
+ * the exact kernel answered (all of them on the exact route); 0 / RADAD_RANGE_EXACT / 0 before the first one.
+ * Measured (tools/bench_range.py, profiles/README.md, "Range search"; 1 M x 512 cosine, 1024 queries, threshold 0.9, M = 128, one
+ * run on one MI355X): 0.86 / 0.88 / 1.42 ms with 0 / 10 / 1000 rows above the threshold per query against 0.98 / 0.99 / 1.04 ms for
+ * the plain k = 10 search of the same handle -- cheaper than the plain search while few rows pass (no sample pre-pass, one launch),
+ * +37 % at 1000 hits (the re-score reads ~2 KB of row per emitted row: 0.36 ms; the scan's emits: +0.25 ms).  The scan's eps on that
+ * store: 5.5e-4.  Not measured: the exact route's time per query, and stores on which the early abandon skips tiles.
+ * Not offered: a begin / finish pair and sharded range search (a shard's answer is exact: concatenating the shards' lists is the
+ * merge); the IVF index; a certified route for 16 or fewer queries; exclusion sets combined with a radius; results beyond
+ * RADAD_KNN_MAX_K per query (the count is exact: the caller can narrow the radius). */
+#define RADAD_RANGE_TILE 0
+#define RADAD_RANGE_EXACT 1
+int radad_knn_range_search(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, float radius, int max_per_query,
+                           int32_t* out_count_dev /*[nq]*/, float* out_dist_dev /*[nq,M]*/, int64_t* out_idx_dev /*[nq,M]*/,
+                           double* out_key_dev /*[nq,M] or NULL*/, void* stream);
+int radad_knn_last_range(radad_knn_t h, int64_t* n_queries, int* route, int* n_exact);
+
 /* ------------------------------------------------------------------------------------------------
  * Inverted-file flat index: faiss.IndexIVFFlat(IndexFlatL2 quantiser, d, nlist, METRIC_L2), the reference's optional
  * `vector_db_index_type == "IVF"` (vector_database.py:65-70 create with nlist = max(64, ivf_nlist), :124-128 train on the

@@ -21,6 +21,7 @@ MAX_LEVELS = 8
 KNN_MAX_K = 1024
 EXCL_PQ_MAX_TAGS = 64     # RADAD_EXCL_PQ_MAX_TAGS
 EXCL_SCAN_TILE, EXCL_SCAN_EXACT = 0, 1      # RADAD_EXCL_SCAN_*
+RANGE_TILE, RANGE_EXACT = 0, 1                # RADAD_RANGE_*
 KNN_OPT_HI_PLANE, KNN_OPT_CENTRE, KNN_OPT_SMALLQ_HI, KNN_OPT_WIDE_MIN_Q, KNN_OPT_DENSE, KNN_OPT_ABANDON = 0, 1, 2, 3, 4, 5
 IVF_OPT_HI_SCAN = 0
 IVF_OPT_PQ_FILTER = 1      # RADAD_IVF_OPT_PQ_FILTER
@@ -94,6 +95,9 @@ SIGNATURES = {
     "radad_knn_last_excl_scan": (C.c_int, [C.c_void_p, c_i64p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "radad_knn_search_excl_scan_pq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "radad_knn_range_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "radad_knn_last_range": (C.c_int, [C.c_void_p, c_i64p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "radad_excl_merge_certify": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "radad_knn_scan_geometry": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),

@@ -1293,6 +1293,65 @@ __global__ __launch_bounds__(RF_THREADS) void k_floor_from_sample(const float* _
 // ballot counts, no LDS -- was built in round 5 and measured at 15.0 us against this kernel's 11.6 for 1024 queries: one wave walks
 // its dependent chain of loads and 32 search steps alone, where this one puts four waves on a query.  Removed.)
 
+// The float64 re-score of k_merge_refine and k_range_refine: the candidates c_id[0, nsel) of one query (LDS, rows of the store) -> c_key.
+// 16 lanes per candidate, 32 candidates per pass (two per 16-lane group), all row loads of a pass issued before the first multiply
+// (the stored rows are random 2 KB reads: latency-bound unless many are in flight).  L2 as sum (q - y)^2: no cancellation.  Called by all
+// RF_THREADS threads; a candidate's key depends on its row and the query alone, not on its place in c_id.
+__device__ __forceinline__ void refine_rescore_f64(const void* db, int db_f16, const float* qrow, int dim, int l2, const int* c_id,
+                                                   double* c_key, int nsel) {
+    const int tid = threadIdx.x, sub = tid >> 4, l16 = tid & 15;
+    for (int c0 = 0; c0 < nsel; c0 += 32) {
+        int cc[2];
+        bool on[2];
+        int64_t rid[2];
+        double acc[2] = {0.0, 0.0};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            cc[h] = c0 + 16 * h + sub;
+            on[h] = cc[h] < nsel;
+            rid[h] = on[h] ? (int64_t)c_id[cc[h]] : 0;
+        }
+        for (int i0 = 0; i0 < dim; i0 += 512) {                 // 16 lanes x 8 x 4 elements per sweep
+            f32x4 b[2][8];
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int i = i0 + (u * 16 + l16) * 4;
+                    b[h][u] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (on[h] && i < dim) {
+                        if (db_f16) {
+                            const f16x4 h4 = *reinterpret_cast<const f16x4*>(reinterpret_cast<const _Float16*>(db) + rid[h] * dim + i);
+                            b[h][u] = f32x4{(float)h4[0], (float)h4[1], (float)h4[2], (float)h4[3]};
+                        } else {
+                            b[h][u] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(db) + rid[h] * dim + i);
+                        }
+                    }
+                }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = i0 + (u * 16 + l16) * 4;
+                if (i < dim) {
+                    const f32x4 a = *reinterpret_cast<const f32x4*>(qrow + i);
+#pragma unroll
+                    for (int h = 0; h < 2; ++h)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            if (l2) { const double d = (double)a[e] - (double)b[h][u][e]; acc[h] += d * d; }
+                            else acc[h] += (double)a[e] * (double)b[h][u][e];
+                        }
+                }
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+#pragma unroll
+            for (int ofs = 8; ofs > 0; ofs >>= 1) acc[h] += __shfl_xor(acc[h], ofs, 64);
+            if (on[h] && l16 == 0) c_key[cc[h]] = acc[h];
+        }
+    }
+}
+
 template <bool STAGED>
 __global__ __launch_bounds__(RF_THREADS) void k_merge_refine(RefineParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem_m[];
@@ -1595,62 +1654,8 @@ __global__ __launch_bounds__(RF_THREADS) void k_merge_refine(RefineParams p) {
         nsel = n_keep;
         __syncthreads();
     }
-    // 2) float64 re-score: 16 lanes per candidate, 32 candidates per pass (two per 16-lane group), all row loads of a pass
-    //    issued before the first multiply (the stored rows are random 2 KB reads: latency-bound unless many are in flight)
-    {
-        const float* qrow = p.q + q * p.dim;
-        const int sub = tid >> 4, l16 = tid & 15;
-        for (int c0 = 0; c0 < (RADAD_DBG(p.debug, 256) ? 0 : nsel); c0 += 32) {
-            int cc[2];
-            bool on[2];
-            int64_t rid[2];
-            double acc[2] = {0.0, 0.0};
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                cc[h] = c0 + 16 * h + sub;
-                on[h] = cc[h] < nsel;
-                rid[h] = on[h] ? (int64_t)c_id[cc[h]] : 0;
-            }
-            for (int i0 = 0; i0 < p.dim; i0 += 512) {                 // 16 lanes x 8 x 4 elements per sweep
-                f32x4 b[2][8];
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int i = i0 + (u * 16 + l16) * 4;
-                        b[h][u] = f32x4{0.f, 0.f, 0.f, 0.f};
-                        if (on[h] && i < p.dim) {
-                            if (p.db_f16) {
-                                const f16x4 h4 = *reinterpret_cast<const f16x4*>(reinterpret_cast<const _Float16*>(p.db) + rid[h] * p.dim + i);
-                                b[h][u] = f32x4{(float)h4[0], (float)h4[1], (float)h4[2], (float)h4[3]};
-                            } else {
-                                b[h][u] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p.db) + rid[h] * p.dim + i);
-                            }
-                        }
-                    }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int i = i0 + (u * 16 + l16) * 4;
-                    if (i < p.dim) {
-                        const f32x4 a = *reinterpret_cast<const f32x4*>(qrow + i);
-#pragma unroll
-                        for (int h = 0; h < 2; ++h)
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                if (p.l2) { const double d = (double)a[e] - (double)b[h][u][e]; acc[h] += d * d; }
-                                else acc[h] += (double)a[e] * (double)b[h][u][e];
-                            }
-                    }
-                }
-            }
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-#pragma unroll
-                for (int ofs = 8; ofs > 0; ofs >>= 1) acc[h] += __shfl_xor(acc[h], ofs, 64);
-                if (on[h] && l16 == 0) c_key[cc[h]] = acc[h];
-            }
-        }
-    }
+    // 2) float64 re-score (refine_rescore_f64)
+    refine_rescore_f64(p.db, p.db_f16, p.q + q * p.dim, p.dim, p.l2, c_id, c_key, RADAD_DBG(p.debug, 256) ? 0 : nsel);
     __syncthreads();
     // 3) rank by (distance, id): L2 ascending, IP descending; ids are unique so ranks are a permutation.  Rank = number of
     //    candidates that come first, counted branch-free over "larger is better" keys by 1, 2 or 4 threads per candidate
@@ -1695,6 +1700,126 @@ __global__ __launch_bounds__(RF_THREADS) void k_merge_refine(RefineParams p) {
         p.out_idx[q * p.k + o] = -1;
         if (p.out_key) p.out_key[q * p.k + o] = p.l2 ? (double)INFINITY : -(double)INFINITY;
     }
+}
+
+// ---- the re-rank of a range search (radad_knn_range_search, tile route) ------------------------------------------------------------
+// The scan ran with the floor T - eps(q) (k_range_floor), so a query's candidate buffer holds EVERY row whose exact score reaches T
+// unless it overflowed.  One workgroup per query:
+//   * cnt > cap: the buffer proves nothing -- the query is appended to flag_sel for the exact range pass, its count zeroed for it;
+//   * else ALL cnt emitted rows (holes skipped) are re-scored in float64 from the stored rows (refine_rescore_f64: the keys of
+//     radad_knn_search_f64, bit for bit), the strict test decides membership (L2: key < radius, IP / cosine: key > radius; a NaN key
+//     passes neither), out_count = the number that pass;
+//   * the passing rows are ranked by (key, lower row) with a bitonic sort over the next power of two >= cnt entries in LDS (rows that
+//     fail and the padding carry the worst key and the largest row: they sort last), and the best min(count, m) are written;
+//     the other slots get -1 / NaN / NaN.
+// LDS: 12 bytes per buffer entry (float64 key + row), 48 KB at the 4096 entries the range plan runs with.
+constexpr int RG_MAX_CAP = 4096;         // entries the sort is sized for (a power of two)
+struct RangeRefineParams {
+    const int* idx = nullptr;           // [nq][cap] rows the scan emitted, IDX_SENTINEL = no entry
+    const int* cnt = nullptr;           // [nq] entries emitted (> cap: overflow)
+    int cap = 0, dim = 0, l2 = 0, db_f16 = 0, m = 0;
+    const void* db = nullptr;           // stored rows (normalised for cosine)
+    const float* q = nullptr;           // the fp32 queries (normalised for cosine)
+    double radius = 0.0;
+    int64_t id_base = 0, ntotal = 0;
+    int* flag_count = nullptr;          // [1] queries left to the exact range pass ...
+    int* flag_sel = nullptr;            // ... and their indices
+    int* out_count = nullptr;           // [nq]
+    float* out_dist = nullptr;          // [nq, m]
+    int64_t* out_idx = nullptr;         // [nq, m]
+    double* out_key = nullptr;          // optional [nq, m]
+};
+static_assert(std::is_trivially_copyable_v<RangeRefineParams>, "kernel argument");
+constexpr size_t range_refine_lds_bytes() { return (size_t)RG_MAX_CAP * 12 + 64; }
+
+__global__ __launch_bounds__(RF_THREADS) void k_range_refine(RangeRefineParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem_g[];
+    double* c_key = reinterpret_cast<double*>(smem_g);                   // [RG_MAX_CAP]
+    int* c_id = reinterpret_cast<int*>(c_key + RG_MAX_CAP);              // [RG_MAX_CAP]
+    int* w_cnt = c_id + RG_MAX_CAP;                                      // [4]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t q = blockIdx.x;
+    const int filled = p.cnt[q];
+    if (filled > p.cap) {                                                // (workgroup-uniform)
+        if (tid == 0) { p.flag_sel[atomicAdd(p.flag_count, 1)] = (int)q; p.out_count[q] = 0; }
+        return;
+    }
+    // the emitted rows, holes and rows outside the store left out (slots by a prefix sum over the block, as k_merge_refine's)
+    const int NE = max(filled, 0);
+    const int* ebuf = p.idx + q * p.cap;
+    int mine = 0;
+    for (int i = tid; i < NE; i += RF_THREADS) { const int id = ebuf[i]; mine += (id != IDX_SENTINEL && id >= 0 && id < p.ntotal) ? 1 : 0; }
+    int incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) w_cnt[wave] = incl;
+    __syncthreads();
+    int slot = incl - mine, nsel = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { if (w < wave) slot += w_cnt[w]; nsel += w_cnt[w]; }
+    for (int i = tid; i < NE; i += RF_THREADS) { const int id = ebuf[i]; if (id != IDX_SENTINEL && id >= 0 && id < p.ntotal) c_id[slot++] = id; }
+    __syncthreads();
+    refine_rescore_f64(p.db, p.db_f16, p.q + q * p.dim, p.dim, p.l2, c_id, c_key, nsel);
+    __syncthreads();
+    // membership, and "larger is better" keys for the ranking
+    int P = 1;
+    while (P < nsel) P <<= 1;                                            // <= RG_MAX_CAP: nsel <= cap <= RG_MAX_CAP (the host checks)
+    int n_pass = 0;
+    for (int i0 = 0; i0 < P; i0 += RF_THREADS) {
+        const int i = i0 + tid;
+        bool pass = false;
+        if (i < nsel) {
+            const double key = c_key[i];
+            pass = p.l2 ? key < p.radius : key > p.radius;
+            c_key[i] = pass ? (p.l2 ? -key : key) : -(double)INFINITY;
+            if (!pass) c_id[i] = IDX_SENTINEL;
+        } else if (i < P) {
+            c_key[i] = -(double)INFINITY;
+            c_id[i] = IDX_SENTINEL;
+        }
+        n_pass += __syncthreads_count(pass);
+    }
+    // (a passing key is never the worst key: -inf passes no strict test, +inf squared distance neither -- the n_pass best entries are
+    // exactly the passing rows)
+    for (int k2 = 2; k2 <= P; k2 <<= 1)
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < P; i += RF_THREADS) {
+                const int o = i ^ j;
+                if (o > i) {
+                    const double ka = c_key[i], kb = c_key[o];
+                    const int ia = c_id[i], ib = c_id[o];
+                    const bool b_first = kb > ka || (kb == ka && ib < ia);
+                    const bool a_first = ka > kb || (ka == kb && ia < ib);
+                    if ((i & k2) == 0 ? b_first : a_first) { c_key[i] = kb; c_id[i] = ib; c_key[o] = ka; c_id[o] = ia; }
+                }
+            }
+            __syncthreads();
+        }
+    if (tid == 0) p.out_count[q] = n_pass;
+    const int n_out = min(n_pass, p.m);
+    const float nan_f = __int_as_float(0x7fc00000);
+    for (int o = tid; o < p.m; o += RF_THREADS) {
+        const bool have = o < n_out;
+        const double kd = have ? (p.l2 ? -c_key[o] : c_key[o]) : (double)nan_f;
+        p.out_dist[q * p.m + o] = have ? (float)kd : nan_f;
+        p.out_idx[q * p.m + o] = have ? (int64_t)c_id[o] + p.id_base : -1;
+        if (p.out_key) p.out_key[q * p.m + o] = kd;
+    }
+}
+
+// the admission floor of a range search: thr[q] = T - eps[q], lowered two more ulps (the subtraction rounds to nearest: one ulp makes
+// it a lower bound of T - eps, the second covers the rounding of the scan's own compare (thr - qc) qs); T = -inf stays -inf.  A query
+// whose eps is not a number >= 0 (non-finite operands) gets -inf: its buffer overflows and the exact pass answers it.
+__global__ __launch_bounds__(256) void k_range_floor(const float* __restrict__ eps, float T, float* __restrict__ thr, int64_t nq) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nq) return;
+    const float e = eps[i];
+    float f = -INFINITY;
+    if (e >= 0.f && e < INFINITY) f = nextafterf(nextafterf(T - e, -INFINITY), -INFINITY);
+    thr[i] = f;
 }
 
 // ---- the re-rank of a SMALL batch (<= 16 queries: the online predict() search, pipeline.py:1038-1054) -------------------------
@@ -1910,6 +2035,11 @@ struct ExactParams {
     const int64_t* q_tags = nullptr;
     const int* q_cnt = nullptr;
     int m = 0;
+    // the range instantiation only (k_exact_scan_range, radad_knn_range_search): a row enters a query's list only when its key passes
+    // the strict test key > range_t (inner product: the radius; L2: minus the radius, the keys here being minus the squared distance),
+    // and every row that passes is counted into out_count[query] (zeroed by the caller); padding -1 / NaN / NaN
+    int* out_count = nullptr;
+    double range_t = 0.0;
 };
 static_assert(std::is_trivially_copyable_v<ExactParams>, "kernel argument");
 
@@ -1928,9 +2058,13 @@ __device__ __forceinline__ void exact_merge_slot(const ExactParams& p, int slot,
 // PER_QUERY (with FILTERED, k_exact_scan_excl_pq, radad_knn_search_excl_pq): every query of a group has an admissible set of its
 // own, <= 64 excluded tags each.  Lane l holds tag l of each of the group's queries; per row one load of the row's tag and one
 // ballot per query say which of the group's lists the row may enter.  A row nobody of the group admits is not loaded.
-template <bool FILTERED, bool PER_QUERY = false>
+// RANGE (alone, k_exact_scan_range, radad_knn_range_search): every row is read; the strict threshold test stands in front of the list
+// insertion, and each wave counts the rows that pass per query of its group -- one atomicAdd per wave, slice and query into
+// out_count.  The lists, the slice merge and the last-arrival merge are the other forms', with k = max_per_query.
+template <bool FILTERED, bool PER_QUERY = false, bool RANGE = false>
 __global__ __launch_bounds__(KX_THREADS) void k_exact_scan_any(ExactParams p) {
     static_assert(FILTERED || !PER_QUERY, "the per-query form is a filtered form");
+    static_assert(!RANGE || !FILTERED, "the range form reads every row");
     const int count = min(*p.count - p.slot0, p.nslots);       // this launch's queries
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && p.host_stats) {
         *reinterpret_cast<volatile int*>(&p.host_stats[6]) = 0;          // the slot is being rewritten: no report until the new stamp is there
@@ -1978,6 +2112,11 @@ __global__ __launch_bounds__(KX_THREADS) void k_exact_scan_any(ExactParams p) {
             }
         }
         __syncthreads();
+        int n_in[8];                                      // (RANGE) rows of this wave that passed the threshold, per query of the group
+        if constexpr (RANGE) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) n_in[j] = 0;
+        }
         int64_t adm_w = -1;                               // (FILTERED) the bitmap word in hand: one load per 64 rows of the slice
         unsigned long long adm = 0ull;
         for (int64_t row = r_begin + wave; row < r_end; row += KX_WAVES) {
@@ -2026,7 +2165,9 @@ __global__ __launch_bounds__(KX_THREADS) void k_exact_scan_any(ExactParams p) {
                     // wave-uniform from here: insert (v, row) into the sorted list of query j when it beats the k-th entry
                     double* lk = wKey + (size_t)j * p.k;
                     int* li = wId + (size_t)j * p.k;
-                    if (kx_better(v, (int)row, lk[p.k - 1], li[p.k - 1])) {
+                    bool within = true;                      // (RANGE) strict, before the insertion; a NaN key passes nothing
+                    if constexpr (RANGE) { within = v > p.range_t; n_in[j] += within ? 1 : 0; }
+                    if (within && kx_better(v, (int)row, lk[p.k - 1], li[p.k - 1])) {
                         // strips of 64 entries (lane l <-> entry 64 s + l), the LAST strip first: a strip reads its entries, counts
                         // the better ones and moves the others one place down -- onto the next strip's first entry, which that
                         // strip has already read.  The better entries are a prefix of the sorted list: a strip of nothing but
@@ -2049,6 +2190,11 @@ __global__ __launch_bounds__(KX_THREADS) void k_exact_scan_any(ExactParams p) {
                     }
                 }
             }
+        }
+        if constexpr (RANGE) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (j < ng && lane == 0 && n_in[j] > 0) atomicAdd(p.out_count + p.sel[p.slot0 + g * G + j], n_in[j]);
         }
         __syncthreads();
         // wave j merges the KX_WAVES lists of query j (lane 0, serial: k * 8 comparisons) into the slice's partial list
@@ -2087,7 +2233,7 @@ __global__ __launch_bounds__(KX_THREADS) void k_exact_scan_any(ExactParams p) {
         __syncthreads();
         if (s_last) {                                    // (workgroup-uniform)
             __threadfence();                             // acquire
-            if (wave < ng) exact_merge_slot<FILTERED>(p, g * G + wave, lane);
+            if (wave < ng) exact_merge_slot<FILTERED || RANGE>(p, g * G + wave, lane);
         }
     }
 }
@@ -2095,6 +2241,7 @@ __global__ __launch_bounds__(KX_THREADS) void k_exact_scan_any(ExactParams p) {
 constexpr auto k_exact_scan = k_exact_scan_any<false>;
 constexpr auto k_exact_scan_excl = k_exact_scan_any<true>;
 constexpr auto k_exact_scan_excl_pq = k_exact_scan_any<true, true>;
+constexpr auto k_exact_scan_range = k_exact_scan_any<false, false, true>;
 
 // one wave: merge the KX_SLICES partial lists of this launch's rejected-query slot `slot`, overwrite the query's output rows
 template <bool FILTERED>
@@ -2637,11 +2784,14 @@ struct radad_knn_s {
     int64_t xarrive_cap = 0;
     // radad_knn_search_excl: a workspace of its own beside `ws` (which the fast pass inside the call may re-allocate): the fast pass's
     // k_fetch lists | listed-query counter | listed queries | admission bitmap | the filtered exact pass's partial lists
+    // (radad_knn_range_search keeps the partial lists of its exact pass here as well: RangeLayout, knn_plan.h)
     void* excl_ws = nullptr;
     size_t excl_ws_bytes = 0, excl_o_count = 0;
     int64_t last_excl_nq = 0;    // batch size of the most recent exclusion-aware search (radad_knn_last_excl)
     int64_t last_xs_nq = 0;      // radad_knn_search_excl_scan: batch size and route of the most recent one (radad_knn_last_excl_scan; its
     int last_xs_route = RADAD_EXCL_SCAN_EXACT;      // count of exactly answered queries is copied to host_count[17] behind it)
+    int64_t last_rg_nq = 0;      // radad_knn_range_search: batch size and route of the most recent one (radad_knn_last_range; its count
+    int last_rg_route = RADAD_RANGE_EXACT;          // of exactly answered queries is copied to host_count[18] behind it)
     double* rs_key = nullptr;    // k_refine_small: [SQ_NQ][KNN_CERT_CAP] float64 keys of the candidates, where the query's workgroups meet
     int* rs_count = nullptr;     // ... and [SQ_NQ] arrival counters (zero between launches)
     int uniform_e = HI_E_PER_ROW; // one power-of-two scale 2^e for every row of the plane (rows of one magnitude), or HI_E_PER_ROW
@@ -3396,8 +3546,13 @@ static void knn_launch_scrub(radad_knn_t h, ScanScrub* s, float* score, int* idx
 // scrub: NULL (every search but radad_knn_search_excl_scan_pq: nothing below changes), or the per-query rule -- k_excl_pq_scrub then
 // runs on the sample's entries before k_floor_from_sample, on the candidate buffers before every k_kth_floor, and once more behind
 // the last launch, so that whoever reads the buffers next (the re-rank) finds them scrubbed
+// floors: NULL (every search but radad_knn_range_search: nothing below changes), or [nq] admission floors the caller has computed
+// (k_range_floor; the search's own floor array, L.thr, so that radad_knn_last_emitted reports them): no floor is derived from rows
+// then -- no sample pre-pass, no k_floor_from_sample, no k_kth_floor -- and the store is ONE launch (nothing changes between
+// launches, so there is nothing to phase).  The launch takes the ABANDON instantiation by the same rule (knn_abandon_launch): the
+// abandon compares the scan's own partial sums with the floor the emit uses, whatever that floor was derived from.
 static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, hipStream_t st, const float* row_bias = nullptr,
-                            ScanScrub* scrub = nullptr) {
+                            ScanScrub* scrub = nullptr, const float* floors = nullptr) {
     const int64_t nq = p.nq;
     float* ps = ws_at<float>(h, L.ps);
     int* pi = ws_at<int>(h, L.pi);
@@ -3440,7 +3595,8 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
     // sample pre-pass: the (k + margin)-th best score over the first rows of the store is a score at least k rows reach, so the
     // scan admits from it (minus 2 eps) instead of -inf (the score of a (row, query) pair does not depend on the tiling).
     // Its lists live behind the candidate buffers.
-    {
+    if (floors) wp.thr_init = floors;
+    else {
         KnnHiParams sp = wp;
         // The sample's tiles are SPREAD over the store (every (tiles / s_splits)-th one).  The first s_splits tiles, as until round 4,
         // are a sample of the store only while its rows are in random order: on a store whose rows arrive cluster by cluster
@@ -3461,7 +3617,7 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
                            (const int*)sp.part_idx, n_ent, p.ksel, (const float*)eps, thr_init);
         wp.thr_init = thr_init;
     }
-    const std::vector<int64_t> r = knn_hi_phases(h->ntotal, nq, (int64_t)8 * p.s_splits * KW_M, knn_hi_one_go(p, h->ntotal));
+    const std::vector<int64_t> r = knn_hi_phases(h->ntotal, nq, (int64_t)8 * p.s_splits * KW_M, floors ? true : knn_hi_one_go(p, h->ntotal));
     h->last_scan_launches = h->last_scan_phases = (int)r.size() - 1;
     for (size_t i = 0; i + 1 < r.size(); ++i) {       // rows [r0, r1) of the store, one full round (or two) of workgroups
         const int64_t r0 = r[i], r1 = r[i + 1];
@@ -4199,6 +4355,104 @@ static int knn_search_excl_scan_pq_locked(radad_knn_t h, const void* q_in, int q
     return RADAD_OK;
 }
 
+// ---- certified range search (radad_knn_range_search) ------------------------------------------------------------------------------
+// Route, facts, plan and the one scan launch are knn_range_plan's (knn_plan.h).  Tile route: the PLAIN search's preparation, RSC and
+// bias (as knn_search_excl_scan_pq_locked), k_range_floor into the search's floor array, one scan launch from those floors (early
+// abandon included), k_range_refine; the queries whose buffer overflowed go, driven from the device, to the exact range kernel.
+// Exact route: that kernel for every query.  Like the siblings above: KnnTuning is read (hi_skip) and never written, no report is
+// posted, no turn is taken.
+static int knn_range_search_locked(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, float radius, int m, int32_t* out_count_dev,
+                                   float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, hipStream_t st) {
+    int rc = knn_order_behind_last(h, st);
+    if (rc) return rc;
+    RangePlan X = knn_range_plan(knn_store_facts(h), nq, m, h->tune.hi_skip);
+    bool tile = X.route == RADAD_RANGE_TILE;
+    if (tile && !knn_ensure_hi(h, st, true)) {                     // (a plane that cannot be allocated switches itself off: exact route)
+        tile = false;
+        X = knn_range_plan(knn_store_facts(h), nq, m, h->tune.hi_skip);
+        RADAD_REQUIRE(X.route == RADAD_RANGE_EXACT, "radad_knn_range_search: a store without a plane planned the tile route");
+    }
+    if (!tile && !knn_ensure_hi(h, st, false)) { radad_set_error("store statistics could not be computed"); return RADAD_EHIP; }
+    ScanPlan p = X.plan;
+    p.mu = (p.hi_q && !h->f16) ? h->cmu : nullptr;                 // the plain search's instantiation (knn_plan_scan)
+    p.biased = p.hi_q && (p.l2 || p.mu);
+    RADAD_REQUIRE(!tile || p.emit_cap <= RG_MAX_CAP, "radad_knn_range_search: %d-entry candidate buffers exceed the re-rank's %d", p.emit_cap, RG_MAX_CAP);
+    const SearchLayout L = knn_search_layout(X.facts, p, q_dtype);
+    if (L.bytes > h->ws_bytes) {
+        RADAD_HIP_CHECK(hipDeviceSynchronize());
+        rc = knn_workspace(h, L.bytes);
+        if (rc) return rc;
+    }
+    const RangeLayout B = knn_range_layout(X.facts, nq, m);        // the exact pass's partial lists, k = m
+    rc = knn_excl_reserve(h, B.bytes);
+    if (rc) return rc;
+    rc = knn_ensure_xarrive(h, nq, st);
+    if (rc) return rc;
+    h->last_emit_nq = 0;                                           // (the workspace no longer holds the last plain tile scan's counters)
+    h->last_xs_nq = 0;
+    h->last_rg_nq = 0;
+    const float* q_use = knn_prepare_queries(h, p, L, q_in, q_dtype, st);      // (clears the listed-query counter and the candidate counters)
+    RADAD_HIP_CHECK(hipGetLastError());
+    int* flag_count = ws_at<int>(h, L.fcount);
+    int* flag_sel = ws_at<int>(h, L.fsel);
+
+    if (tile) {
+        // scan scores estimate q.y (IP / cosine) or -|q - y|^2 (L2): the threshold in their units
+        float* floors = ws_at<float>(h, L.thr);
+        hipLaunchKernelGGL(k_range_floor, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, st, ws_at<const float>(h, L.eps),
+                           p.l2 ? -radius : radius, floors, nq);
+        RADAD_HIP_CHECK(hipGetLastError());
+        h->prof.next_search();
+        rc = knn_scan_hi_tile(h, p, L, st, nullptr, nullptr, floors);
+        if (rc) return rc;
+        RADAD_HIP_CHECK(hipGetLastError());
+        RADAD_REQUIRE(h->last_scan_launches == X.launches, "radad_knn_range_search: %d scan launches, planned %d", h->last_scan_launches, X.launches);
+        h->last_o_cnt = L.cnt; h->last_o_thr = L.thr; h->last_emit_nq = nq;
+        RangeRefineParams g;
+        g.idx = ws_at<const int>(h, L.pi); g.cnt = ws_at<const int>(h, L.cnt); g.cap = p.emit_cap; g.dim = h->dim; g.l2 = p.l2;
+        g.db_f16 = h->f16; g.m = m; g.db = h->rows; g.q = q_use; g.radius = (double)radius; g.id_base = h->id_base; g.ntotal = h->ntotal;
+        g.flag_count = flag_count; g.flag_sel = flag_sel;
+        g.out_count = out_count_dev; g.out_dist = out_dist_dev; g.out_idx = out_idx_dev; g.out_key = out_key_dev;
+        const size_t glds = range_refine_lds_bytes();
+        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_range_refine), hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds));
+        h->prof.begin(st);                                         // (the call's second profile entry: its re-rank)
+        hipLaunchKernelGGL(k_range_refine, dim3((unsigned)nq), dim3(RF_THREADS), glds, st, g);
+        h->prof.end(st);
+    } else {
+        RADAD_HIP_CHECK(hipMemsetAsync(out_count_dev, 0, (size_t)nq * sizeof(int32_t), st));
+        hipLaunchKernelGGL(k_excl_scan_list_all, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, st, flag_sel, flag_count, nq);
+    }
+    RADAD_HIP_CHECK(hipGetLastError());
+
+    // ---- the listed queries (tile route: k_range_refine zeroed their counts): the float64 exact range kernel, sized and driven by the
+    // device-side count; no report
+    {
+        ExactParams x;
+        x.db = h->rows; x.db_f16 = h->f16; x.q = q_use; x.sel = flag_sel; x.count = flag_count;
+        x.n = h->ntotal; x.dim = h->dim; x.k = m; x.l2 = p.l2; x.group = B.xgroup;
+        x.slice_rows = ceil_div64(h->ntotal, KX_SLICES);
+        x.pkey = reinterpret_cast<double*>((char*)h->excl_ws + B.xk); x.pidx = reinterpret_cast<int*>((char*)h->excl_ws + B.xi);
+        x.id_base = h->id_base;
+        x.out_dist = out_dist_dev; x.out_idx = out_idx_dev; x.out_key = out_key_dev;
+        x.host_stats = nullptr;
+        x.arrive = h->xarrive;
+        x.out_count = out_count_dev;
+        x.range_t = p.l2 ? -(double)radius : (double)radius;
+        const size_t xlds = knn_exact_dyn_lds_bytes(h->dim, m);      // (with the static arrival flag <= KX_LDS_MAX: the entry point checked)
+        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_exact_scan_range), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
+        const unsigned gy = m <= KNN_F16_MAX_K ? KX_GROUPS_Y : 8 * KX_GROUPS_Y;
+        x.nslots = (int)B.xslots;
+        for (int64_t s0 = 0; s0 < nq; s0 += x.nslots) {            // (launches past the device-side count leave at once)
+            x.slot0 = (int)s0;
+            hipLaunchKernelGGL(k_exact_scan_range, dim3(KX_SLICES, gy), dim3(KX_THREADS), xlds, st, x);
+        }
+        RADAD_HIP_CHECK(hipGetLastError());
+    }
+    RADAD_HIP_CHECK(hipMemcpyAsync(h->host_count + 18, flag_count, sizeof(int), hipMemcpyDeviceToHost, st));
+    h->last_rg_nq = nq; h->last_rg_route = tile ? RADAD_RANGE_TILE : RADAD_RANGE_EXACT;
+    return RADAD_OK;
+}
+
 extern "C" {
 
 int radad_knn_search_begin(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, float* kth_lower_bound_dev, void* stream) {
@@ -4302,6 +4556,38 @@ int radad_knn_search_excl_scan_pq(radad_knn_t h, const void* q_dev, int q_dtype,
     RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_search_excl_scan_pq: a radad_knn_search_begin on this handle has not been finished");
     if (h->ntotal == 0) { radad_set_error("radad_knn_search_excl_scan_pq: the store is empty"); return RADAD_ESTATE; }
     return knn_search_excl_scan_pq_locked(h, q_dev, q_dtype, nq, k, r, out_dist_dev, out_idx_dev, out_key_dev, (hipStream_t)stream);
+}
+
+int radad_knn_range_search(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, float radius, int max_per_query,
+                           int32_t* out_count_dev, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, void* stream) {
+    RADAD_REQUIRE(h, "NULL handle");
+    RADAD_REQUIRE(q_dtype == RADAD_Q_F32 || q_dtype == RADAD_Q_BF16, "radad_knn_range_search: unsupported query dtype %d", q_dtype);
+    RADAD_REQUIRE(max_per_query >= 1 && max_per_query <= RADAD_KNN_MAX_K, "radad_knn_range_search: max_per_query=%d outside [1,%d]",
+                  max_per_query, RADAD_KNN_MAX_K);
+    RADAD_REQUIRE(knn_exact_fits(h->dim, max_per_query),
+                  "radad_knn_range_search: dim %d x max_per_query %d too large for the exact kernel (dim * 4 + 96 k + 16 <= %zu)", h->dim,
+                  max_per_query, KX_LDS_MAX);
+    RADAD_REQUIRE(radius == radius, "radad_knn_range_search: the radius is not a number");
+    RADAD_REQUIRE(nq >= 0 && nq < (1ll << 31) - KT_N, "radad_knn_range_search: bad nq");
+    if (nq == 0) return RADAD_OK;
+    RADAD_REQUIRE(q_dev && out_count_dev && out_dist_dev && out_idx_dev, "radad_knn_range_search: NULL buffer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_range_search: a radad_knn_search_begin on this handle has not been finished");
+    if (h->ntotal == 0) { radad_set_error("radad_knn_range_search: the store is empty"); return RADAD_ESTATE; }
+    return knn_range_search_locked(h, q_dev, q_dtype, nq, radius, max_per_query, out_count_dev, out_dist_dev, out_idx_dev, out_key_dev,
+                                   (hipStream_t)stream);
+}
+
+int radad_knn_last_range(radad_knn_t h, int64_t* n_queries, int* route, int* n_exact) {
+    RADAD_REQUIRE(h && route && n_exact, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    RADAD_HIP_CHECK(knn_wait_last_search(h));
+    *n_exact = h->last_rg_nq > 0 ? *reinterpret_cast<volatile int*>(h->host_count + 18) : 0;
+    *route = h->last_rg_route;
+    if (n_queries) *n_queries = h->last_rg_nq;
+    return RADAD_OK;
 }
 
 int radad_knn_last_excl_scan(radad_knn_t h, int64_t* n_queries, int* route, int* n_exact) {

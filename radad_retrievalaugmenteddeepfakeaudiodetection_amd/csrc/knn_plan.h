@@ -519,6 +519,51 @@ static ExclScanPqPlan knn_excl_scan_pq_plan(const StoreFacts& s, int64_t nq, int
     return x;
 }
 
+// ---- certified range search (radad_knn_range_search) ------------------------------------------------------------------------------
+// Every row within a radius instead of the k nearest.  The tile scan is a threshold filter already; a range search hands it the
+// floor (threshold - eps(q), k_range_floor) instead of deriving one from rows, so there is no sample pre-pass, no floor kernel and
+// nothing to phase: ONE scan launch over the whole store (knn_hi_phases, one_go).
+// Route: the tile scan exactly when knn_excl_scan_route says so at k = 1, whatever max_per_query is -- the candidate buffers hold
+// what the scan emits, not what the caller wants back.  That keeps the plain search's store-size precondition (a store large enough
+// for a sample pre-pass that never runs) on purpose: every kernel precondition the tile scan has been tested under stays in force.
+// Facts: the caller's with the widened candidate buffers (cap_boost 4: 4096 entries per query, whatever the handle's tuning state).
+// The plan is the plain search's at k = 1 (mu / biased: the caller's, as for any plan); on the exact route it is the plan the queries
+// are prepared and the workspace laid out with.
+struct RangePlan {
+    int route = RADAD_RANGE_EXACT;
+    StoreFacts facts;
+    ScanPlan plan;
+    int launches = 0;            // tile route: launches of the scan (1); exact route: 0
+};
+static RangePlan knn_range_plan(const StoreFacts& s, int64_t nq, int max_per_query, int fp32_searches_left) {
+    (void)max_per_query;
+    RangePlan x;
+    const bool tile = knn_excl_scan_route(s, nq, 1, fp32_searches_left) == RADAD_EXCL_SCAN_TILE;
+    x.route = tile ? RADAD_RANGE_TILE : RADAD_RANGE_EXACT;
+    x.facts = s;
+    x.facts.cap_boost = KNN_EXCL_SCAN_PQ_CAP_BOOST;
+    const TileEligibility t = knn_tile_eligibility(x.facts, nq, 1, KNN_MARGIN);
+    x.plan = knn_finish_plan(x.facts, nq, 1, KNN_MARGIN, t, tile, false);
+    if (tile) x.launches = (int)knn_hi_phases(s.ntotal, nq, (int64_t)8 * x.plan.s_splits * KW_M, true).size() - 1;
+    return x;
+}
+// The exact range pass keeps lists of max_per_query entries, not of the plan's k = 1: its partial lists live in the handle's exclusion
+// workspace (xk | xi), grouped and sized as any exact pass at k = max_per_query.
+struct RangeLayout {
+    size_t xk = 0, xi = 0, bytes = 0;
+    int xgroup = 1;
+    int64_t xslots = 0;
+};
+static RangeLayout knn_range_layout(const StoreFacts& s, int64_t nq, int max_per_query) {
+    RangeLayout L;
+    L.xgroup = knn_exact_group(s.dim, max_per_query);
+    L.xslots = knn_exact_slots(nq, max_per_query, L.xgroup);
+    L.xk = 0;
+    L.xi = al256((size_t)L.xslots * KX_SLICES * max_per_query * sizeof(double));
+    L.bytes = L.xi + al256((size_t)L.xslots * KX_SLICES * max_per_query * sizeof(int));
+    return L;
+}
+
 // ---- adaptive tuning --------------------------------------------------------------------------------------------------------------
 // What a handle does when the certificate rejects more than a quarter of a batch of >= 64 queries: re-decide the plane if rows were
 // appended since it was decided, else widen the candidate buffers once (cap_boost 1 -> 4), else leave the certified f16 kernels for

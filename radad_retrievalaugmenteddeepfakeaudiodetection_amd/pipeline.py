@@ -89,6 +89,29 @@ class HotPathPipeline:
             return [m.get("speaker_id", "unknown") if isinstance(m, dict) else "unknown" for m in metas]
         return ["unknown"] * batch_size
 
+    # ---- audit by content ---------------------------------------------------------------------------------
+    def near_duplicates(self, query_vectors, thresh: float, max_per_query: int = 128, query_paths: Optional[List[str]] = None):
+        """Per query the stored rows within `thresh` of it (VectorDatabase.range_search_batch: cosine / inner product > thresh, or
+        squared L2 < thresh, exactly), as a list of (path, label, score), best first, at most max_per_query.  The content
+        counterpart of validate_no_leakage (pipeline.py:1105-1110), which compares basenames and so passes a re-encoded or renamed
+        copy of a training clip.  With `query_paths`, entries whose basename equals the query's own are dropped (the file itself),
+        a copy under another name stays."""
+        lims, dist, idx = self.vector_db.range_search_batch(query_vectors, thresh, max_per_query=max_per_query)[:3]
+        if hasattr(lims, "cpu"):
+            lims, dist, idx = lims.cpu().numpy(), dist.cpu().numpy(), idx.cpu().numpy()
+        base = self.vector_db.index.id_base if hasattr(self.vector_db.index, "id_base") else 0
+        out = []
+        for j in range(len(lims) - 1):
+            own = os.path.basename(query_paths[j]) if query_paths is not None else None
+            hits = []
+            for d, i in zip(dist[lims[j]:lims[j + 1]], idx[lims[j]:lims[j + 1]]):
+                path = self.vector_db.vector_paths[int(i) - base]
+                if own is not None and os.path.basename(path) == own:
+                    continue
+                hits.append((path, self.vector_db.vector_labels[int(i) - base], float(d)))
+            out.append(hits)
+        return out
+
     # ---- retrieve -----------------------------------------------------------------------------------------
     def retrieve_similar_vectors(self, query_vectors, query_paths: Optional[List[str]] = None, exclude_self: bool = True,
                                  return_info: bool = False, return_distances: bool = False):

@@ -245,6 +245,11 @@ class ShardedSearch:
                          "ShardedSearch(local_search=<that call with return_f64>).search(q, k) merges the shards' lists exactly "
                          "(INTEGRATION.md); search_excluding with query_tags_local is the certified over-fetch over shards")
 
+    def range_search(self, *args, **kwargs):
+        raise ValueError("range_search has no sharded form of its own: a shard's result of HipFlatIndex.range_search is already every "
+                         "row of that shard within the radius, so concatenating the shards' lists per query (and adding their counts) "
+                         "is the merge")
+
     def search_excluding(self, q_local, k: int, exclude_tags_local=None, k_fetch=None, return_all: bool = False,
                          query_tags_local=None, query_tag_counts_local=None):
         """The exclusion-aware search (HipFlatIndex.search_excluding) over the row shards: q_local [Q_r, D], exclude_tags_local int64
@@ -415,6 +420,10 @@ class ReplicatedSearch:
 
     def timings(self):
         return []
+
+    def range_search(self, *args, **kwargs):
+        raise ValueError("range_search has no replicated form of its own: every rank holds the whole store, so "
+                         "HipFlatIndex.range_search on the rank's store with the rank's own queries is the answer")
 
     def search_excluding(self, q_local, k: int, exclude_tags_local=None, k_fetch=None):
         """local_search_excluding(q_local, k, exclude_tags_local, k_fetch) on the rank's own queries with the rank's OWN exclusion set

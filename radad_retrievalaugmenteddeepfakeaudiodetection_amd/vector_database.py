@@ -332,6 +332,50 @@ class HipFlatIndex:
         _lib.check(self._lib.radad_knn_last_excl_scan(self._h, C.byref(nq), C.byref(route), C.byref(ex)), "radad_knn_last_excl_scan")
         return {"queries": nq.value, "route": "tile" if route.value == _lib.EXCL_SCAN_TILE else "exact", "exact": ex.value}
 
+    def range_search_device(self, q, thresh: float, max_per_query: int = 128, return_f64: bool = False):
+        """Every stored row within `thresh` of each query, exactly (radad_knn_range_search): squared L2 < thresh, or inner product /
+        cosine > thresh, strictly, decided on the float64 key.  q [nq, d] CUDA tensor (float32 or bfloat16) ->
+        (counts i32 [nq], D f32 [nq, M], I i64 [nq, M]) on the device, M = max_per_query: counts are the EXACT numbers of rows within
+        the radius, also beyond M; each query's first min(count, M) slots hold its best rows in (key, lower id) order, the rest
+        -1 / NaN.  With return_f64 also the float64 keys."""
+        import torch
+        q, q_dtype = _prep_queries(q, self.d)
+        m = int(max_per_query)
+        counts = torch.empty((q.shape[0],), device=q.device, dtype=torch.int32)
+        D, I, K64 = _alloc_out(q, max(m, 0), return_f64)
+        with torch.cuda.device(q.device):
+            _lib.check(self._lib.radad_knn_range_search(self._h, q.data_ptr(), q_dtype, q.shape[0], float(thresh), m, counts.data_ptr(),
+                                                        D.data_ptr(), I.data_ptr(), _ptr(K64), _lib.stream_ptr(q.device)),
+                       "radad_knn_range_search")
+        return (counts, D, I, K64) if return_f64 else (counts, D, I)
+
+    def range_search(self, x, thresh: float, max_per_query: int = 128, return_counts: bool = False):
+        """faiss's index.range_search: -> (lims int64 [nq + 1], D float32 [lims[-1]], I int64 [lims[-1]]), query i's rows at
+        lims[i]:lims[i + 1], best first.  Unlike faiss a query's list is cut to its `max_per_query` (<= 1024) best rows; a warning is
+        logged once per call when any query was cut, and with return_counts the exact int32 counts (cut or not) come back as a fourth
+        value.  numpy in -> numpy out; a CUDA tensor in -> CUDA tensors out."""
+        import torch
+        is_dev = hasattr(x, "is_cuda") and x.is_cuda
+        q = x if is_dev else torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(torch.device("cuda", self.device))
+        counts, D, I = self.range_search_device(q, thresh, max_per_query)
+        kept = counts.to(torch.int64).clamp(max=int(max_per_query))
+        lims = torch.zeros((q.shape[0] + 1,), dtype=torch.int64, device=q.device)
+        lims[1:] = torch.cumsum(kept, 0)
+        n_cut = int((counts.to(torch.int64) > kept).sum().item())
+        if n_cut:
+            logging.warning(f"range_search: {n_cut} of {q.shape[0]} queries have more than max_per_query={int(max_per_query)} rows "
+                            "within the radius; their lists were cut to the best (the counts are exact)")
+        mask = torch.arange(D.shape[1], device=q.device).unsqueeze(0) < kept.unsqueeze(1)
+        out = (lims, D[mask], I[mask]) + ((counts,) if return_counts else ())
+        return out if is_dev else tuple(t.cpu().numpy() for t in out)
+
+    def last_range(self):
+        """{"queries", "route", "exact"} of the most recent range search: its batch size, "tile" or "exact", and how many of its queries
+        the exact float64 kernel answered (radad_knn_last_range; synchronises with that search)"""
+        nq, route, ex = C.c_int64(), C.c_int(), C.c_int()
+        _lib.check(self._lib.radad_knn_last_range(self._h, C.byref(nq), C.byref(route), C.byref(ex)), "radad_knn_last_range")
+        return {"queries": nq.value, "route": "tile" if route.value == _lib.RANGE_TILE else "exact", "exact": ex.value}
+
     def search_excluding_begin(self, q, k: int, row_tags, exclude_tags, k_fetch=None):
         """first half of search_excluding over a ROW SHARD (radad_knn_search_excl_begin; sharded.ShardedSearch.search_excluding): the
         certified search at k_fetch on this shard and the compaction -> (K64 f64 [nq,k], I i64 [nq,k], FK f64 [nq], FI i64 [nq]): the
@@ -739,6 +783,10 @@ class HipIVFFlatIndex:
         raise ValueError("search_excluding_per_query_in_scan is the flat store's search: an IVF index has the per-(row, query) test "
                          "inside its own list scans (search_probed_excluding_per_query)")
 
+    def range_search(self, *args, **kwargs):
+        raise ValueError("range_search is the flat store's search: an IVF search sees the probed lists, not the store, so it cannot "
+                         "say that no other row is within the radius")
+
     MAX_K_PROBED = 26  # csrc/ivf.inc: the largest k the list scans hold (k + 6 <= 32 entries per (query, list))
 
     def search_probed_excluding(self, q, k: int, row_tags, exclude_tags):
@@ -963,6 +1011,33 @@ class VectorDatabase:
         if is_dev:
             return self.index.search_device(query_vectors, k)
         return self.index.search(query_vectors.astype(np.float32, copy=False), k)
+
+    def range_search_batch(self, query_vectors, thresh: float, max_per_query: int = 128, return_counts: bool = False):
+        """Every stored row within `thresh` of each query, exactly, in faiss's CSR form (HipFlatIndex.range_search): -> (lims int64
+        [B + 1], D, I), with return_counts also the exact int32 counts.  Inputs as search_batch: numpy in -> numpy out, a CUDA tensor
+        in -> CUDA tensors out, a 1-d query is one query; an empty store returns empty results.  Flat stores only."""
+        if self.index is None:
+            raise ValueError("Vector database is empty. Build the database first.")
+        if not isinstance(self.index, HipFlatIndex):
+            raise ValueError("range_search_batch is flat and single-handle only (vector_db_index_type 'L2' or 'IP'): an IVF search "
+                             "sees the probed lists, not the store")
+        is_dev = hasattr(query_vectors, "is_cuda") and query_vectors.is_cuda
+        if not is_dev:
+            query_vectors = np.asarray(query_vectors)
+        if query_vectors.ndim == 1:
+            query_vectors = query_vectors.reshape(1, -1)
+        if self.index.ntotal <= 0:
+            logging.warning("No vectors available for search")
+            nq = len(query_vectors)
+            if is_dev:
+                import torch
+                dev = query_vectors.device
+                out = (torch.zeros((nq + 1,), dtype=torch.int64, device=dev), torch.zeros((0,), dtype=torch.float32, device=dev),
+                       torch.zeros((0,), dtype=torch.int64, device=dev))
+                return out + ((torch.zeros((nq,), dtype=torch.int32, device=dev),) if return_counts else ())
+            out = (np.zeros((nq + 1,), np.int64), np.zeros((0,), np.float32), np.zeros((0,), np.int64))
+            return out + ((np.zeros((nq,), np.int32),) if return_counts else ())
+        return self.index.range_search(query_vectors, thresh, max_per_query=max_per_query, return_counts=return_counts)
 
     def _excluding_args(self, index_cls, wrong_index: str, query_vectors, k, exclude_tags, k_fetch=None):
         """the front of search_excluding / search_probed_excluding -> (query_vectors [B, d], k clamped to ntotal, k_fetch, row tags,
