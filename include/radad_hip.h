@@ -505,14 +505,70 @@ int radad_knn_search_excl_scan_pq(radad_knn_t h, const void* q_dev, int q_dtype,
  * +37 % at 1000 hits (the re-score reads ~2 KB of row per emitted row: 0.36 ms; the scan's emits: +0.25 ms).  The scan's eps on that
  * store: 5.5e-4.  Not measured: the exact route's time per query, and stores on which the early abandon skips tiles.
  * Not offered: a begin / finish pair and sharded range search (a shard's answer is exact: concatenating the shards' lists is the
- * merge); the IVF index; a certified route for 16 or fewer queries; exclusion sets combined with a radius; results beyond
- * RADAD_KNN_MAX_K per query (the count is exact: the caller can narrow the radius). */
+ * merge); the IVF index; a certified route for 16 or fewer queries; results beyond RADAD_KNN_MAX_K per query (the count is exact:
+ * the caller can narrow the radius).  Exclusion sets combined with a radius: the two calls below. */
 #define RADAD_RANGE_TILE 0
 #define RADAD_RANGE_EXACT 1
 int radad_knn_range_search(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, float radius, int max_per_query,
                            int32_t* out_count_dev /*[nq]*/, float* out_dist_dev /*[nq,M]*/, int64_t* out_idx_dev /*[nq,M]*/,
                            double* out_key_dev /*[nq,M] or NULL*/, void* stream);
 int radad_knn_last_range(radad_knn_t h, int64_t* n_queries, int* route, int* n_exact);
+
+/* Certified range search among the rows a query does not exclude: every ADMISSIBLE row within the radius, exactly.  The audit of a
+ * store by file or by speaker ("which rows of ANOTHER speaker lie within cosine 0.98 of this clip") is this call: filtering the plain
+ * range search's lists afterwards leaves the count of the unfiltered set and lets a clip's own copies or a speaker's 1500 rows take
+ * every one of the M slots.
+ * Outputs: radad_knn_range_search's, word for word, over the admissible rows -- out_count[j] is the EXACT number of admissible rows
+ * within the radius (strict float64 membership), also beyond M = max_per_query; slots 0 .. min(count, M) - 1 hold the best admissible
+ * rows ordered by (key, lower id); -1 / NaN / NaN behind them.  An excluded row is never counted and never takes a slot.
+ *   radad_knn_range_search_excl     ONE set for the batch; arguments and NULL rules of radad_knn_search_excl_scan (row_tags_dev and
+ *                 excl_sorted_dev, ascending, may be NULL only when n_excl == 0).
+ *   radad_knn_range_search_excl_pq  one set of at most RADAD_EXCL_PQ_MAX_TAGS tags PER QUERY; the admissibility rule of
+ *                 radad_knn_search_excl_scan_pq (counts clamped on the device to [0, m], NULL counts = m, any order, repeats allowed).
+ * Tags are indexed by id - id_base.  With n_excl == 0, m == 0 or every count 0 the counts, ids and float64 keys are those of
+ * radad_knn_range_search on the same handle, bit for bit.
+ * Routes: radad_knn_range_search's (knn_range_excl_plan, knn_plan.h: knn_excl_scan_route at k = 1, 4096-entry buffers, one scan
+ * launch), reported by radad_knn_last_range, which describes whichever of the three range calls ran last.
+ *   RADAD_RANGE_TILE, one set for the batch: the bitmap and per-call bias pre-pass of radad_knn_search_excl_scan (NaN for excluded
+ *                 rows; 12 bytes read and 4 written per row), the queries prepared for the biased instantiation (RSC 2 / 3, a zero
+ *                 query constant without a centre) so that eps is that instantiation's own, k_range_floor, one scan launch with the
+ *                 bias.  A NaN score passes no compare: excluded rows are never emitted, k_range_refine runs unchanged, and the
+ *                 buffers hold admissible rows only.  Early abandon: as for any per-call bias (knn_abandon_launch: not taken).  A
+ *                 query that still overflows goes, driven from the device, to k_exact_scan_any<true, false, true> with the bitmap.
+ *   RADAD_RANGE_TILE, one set per query: the plain range search's launch -- its floors, RSC and early abandon; the scan emits excluded
+ *                 rows like any others.  No k_excl_pq_scrub (it serves k_kth_floor, which a range search never runs): the re-rank's
+ *                 per-query form stages the query's live tags in LDS and drops an emitted row whose tag is among them while it
+ *                 compacts the buffer, so excluded rows are never re-scored, counted or sorted.  Overflow stays "emitted more than
+ *                 the buffer holds, excluded rows included": such a query goes to k_exact_scan_any<true, true, true> with the query
+ *                 tags.  m == 0 takes the plain range path outright.  radad_knn_last_emitted counts the emitted rows, excluded ones
+ *                 included.
+ *   RADAD_RANGE_EXACT: those exact kernels for every query.  With both a radius and a filter the strict test, the count and the list
+ *                 insertion happen only for the queries that admit the row; a row nobody admits is not loaded.
+ * State: as the sibling calls -- KnnTuning is read (hi_skip), never written; no certificate report, no turn off the tuning state;
+ * radad_knn_tuning_info, radad_knn_last_recheck and radad_knn_last_certificate are left as found; the call may build the plane.
+ * Errors, before anything is enqueued (outputs untouched, the handle usable): RADAD_EINVAL for everything radad_knn_range_search
+ * refuses, for m outside [0, RADAD_EXCL_PQ_MAX_TAGS], for m > 0 or n_excl > 0 with NULL tag arrays (n_excl < 0 too); RADAD_ESTATE on
+ * an empty store; nq == 0 returns RADAD_OK.  Stream-ordered and serialised like every search.
+ * Measured (tools/bench_range_excl.py, profiles/README.md, "Range search with exclusion"; 1 M x 512 cosine, 1024 queries, threshold
+ * 0.9, M = 128, 10 admissible rows above the threshold per query, one run on one MI355X, each call alternated with
+ * radad_knn_range_search on the same handle).  Per query, every query excluding its own speaker of c rows above the threshold:
+ * 0.87 / 0.93 / 1.22 ms at c = 0 / 200 / 1500 against 0.87 / 0.97 / 1.79 ms for the plain range search (which counts and re-scores
+ * the speaker's rows): equal at c = 0, cheaper with a crowd, because the re-rank drops it before the float64 re-score.  One set for
+ * the batch with 0 / 50 / 90 % of the rows excluded: 0.90 / 0.88 / 0.85 ms against 0.87: at 0 % the biased instantiation's scan
+ * launch is 0.03 ms slower than the plain one (RSC 3 instead of RSC 0 on an un-centred cosine store) and the two pre-pass launches
+ * come on top; excluded rows emit nothing, so the cost falls as the set grows.
+ * Not offered: a begin / finish pair; a batch-wide set combined with per-query sets; the IVF index. */
+int radad_knn_range_search_excl(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, float radius, int max_per_query,
+                                const int64_t* row_tags_dev /*[ntotal], by id - id_base*/,
+                                const int64_t* excl_sorted_dev /*[n_excl] ascending, NULL when n_excl == 0*/, int64_t n_excl,
+                                int32_t* out_count_dev /*[nq]*/, float* out_dist_dev /*[nq,M]*/, int64_t* out_idx_dev /*[nq,M]*/,
+                                double* out_key_dev /*[nq,M] or NULL*/, void* stream);
+int radad_knn_range_search_excl_pq(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, float radius, int max_per_query,
+                                   const int64_t* row_tags_dev /*[ntotal], by id - id_base*/,
+                                   const int64_t* q_tags_dev /*[nq, m] row-major; any order, duplicates allowed*/, int m,
+                                   const int32_t* q_tag_counts_dev /*[nq] or NULL = m for every query*/, int32_t* out_count_dev /*[nq]*/,
+                                   float* out_dist_dev /*[nq,M]*/, int64_t* out_idx_dev /*[nq,M]*/, double* out_key_dev /*[nq,M] or NULL*/,
+                                   void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Inverted-file flat index: faiss.IndexIVFFlat(IndexFlatL2 quantiser, d, nlist, METRIC_L2), the reference's optional

@@ -1731,8 +1731,22 @@ struct RangeRefineParams {
 };
 static_assert(std::is_trivially_copyable_v<RangeRefineParams>, "kernel argument");
 constexpr size_t range_refine_lds_bytes() { return (size_t)RG_MAX_CAP * 12 + 64; }
+// PER_QUERY (k_range_refine<true>, radad_knn_range_search_excl_pq): the scan emitted a query's excluded rows like any others; the
+// query's live tags are staged in LDS (as k_excl_pq_scrub does) and both passes of the compaction below treat an emitted row whose tag
+// is among them as one more hole -- such a row is never re-scored, never counted, never sorted.  Overflow is decided on the emitted
+// count, excluded rows included.  The plain instantiation takes RangeRefineParams and is the code it was.
+struct RangeRefinePqParams : RangeRefineParams {
+    const int64_t* tags = nullptr;      // [ntotal] row tags
+    const int64_t* q_tags = nullptr;    // [nq, n_tags]
+    const int* q_cnt = nullptr;         // [nq] or NULL = n_tags for every query (clamped to [0, n_tags] here)
+    int n_tags = 0;
+};
+static_assert(std::is_trivially_copyable_v<RangeRefinePqParams>, "kernel argument");
+constexpr size_t range_refine_pq_lds_bytes() { return range_refine_lds_bytes() + (size_t)RADAD_EXCL_PQ_MAX_TAGS * sizeof(int64_t); }
+static_assert(range_refine_lds_bytes() % 8 == 0, "the tags behind the plain form's LDS are 8-byte entries");
 
-__global__ __launch_bounds__(RF_THREADS) void k_range_refine(RangeRefineParams p) {
+template <bool PER_QUERY = false>
+__global__ __launch_bounds__(RF_THREADS) void k_range_refine(std::conditional_t<PER_QUERY, RangeRefinePqParams, RangeRefineParams> p) {
     extern __shared__ __attribute__((aligned(16))) char smem_g[];
     double* c_key = reinterpret_cast<double*>(smem_g);                   // [RG_MAX_CAP]
     int* c_id = reinterpret_cast<int*>(c_key + RG_MAX_CAP);              // [RG_MAX_CAP]
@@ -1747,8 +1761,28 @@ __global__ __launch_bounds__(RF_THREADS) void k_range_refine(RangeRefineParams p
     // the emitted rows, holes and rows outside the store left out (slots by a prefix sum over the block, as k_merge_refine's)
     const int NE = max(filled, 0);
     const int* ebuf = p.idx + q * p.cap;
+    int64_t* s_tag = reinterpret_cast<int64_t*>(smem_g + range_refine_lds_bytes());     // (PER_QUERY) [RADAD_EXCL_PQ_MAX_TAGS], behind the plain form's LDS
+    int n_tag = 0;
+    if constexpr (PER_QUERY) {
+        n_tag = min(max(p.q_cnt ? p.q_cnt[q] : p.n_tags, 0), min(p.n_tags, RADAD_EXCL_PQ_MAX_TAGS));
+        if (tid < n_tag) s_tag[tid] = p.q_tags[q * p.n_tags + tid];
+        __syncthreads();
+    }
+    // an entry the re-score takes: a row of the store that (PER_QUERY) the query does not exclude
+    auto taken = [&](int id) -> bool {
+        if (id == IDX_SENTINEL || id < 0 || id >= p.ntotal) return false;
+        if constexpr (PER_QUERY) {
+            if (n_tag > 0) {
+                const int64_t t = p.tags[id];
+                bool excluded = false;
+                for (int e = 0; e < n_tag; ++e) excluded |= s_tag[e] == t;
+                return !excluded;
+            }
+        }
+        return true;
+    };
     int mine = 0;
-    for (int i = tid; i < NE; i += RF_THREADS) { const int id = ebuf[i]; mine += (id != IDX_SENTINEL && id >= 0 && id < p.ntotal) ? 1 : 0; }
+    for (int i = tid; i < NE; i += RF_THREADS) mine += taken(ebuf[i]) ? 1 : 0;
     int incl = mine;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -1760,7 +1794,7 @@ __global__ __launch_bounds__(RF_THREADS) void k_range_refine(RangeRefineParams p
     int slot = incl - mine, nsel = 0;
 #pragma unroll
     for (int w = 0; w < 4; ++w) { if (w < wave) slot += w_cnt[w]; nsel += w_cnt[w]; }
-    for (int i = tid; i < NE; i += RF_THREADS) { const int id = ebuf[i]; if (id != IDX_SENTINEL && id >= 0 && id < p.ntotal) c_id[slot++] = id; }
+    for (int i = tid; i < NE; i += RF_THREADS) { const int id = ebuf[i]; if (taken(id)) c_id[slot++] = id; }
     __syncthreads();
     refine_rescore_f64(p.db, p.db_f16, p.q + q * p.dim, p.dim, p.l2, c_id, c_key, nsel);
     __syncthreads();
@@ -2035,9 +2069,10 @@ struct ExactParams {
     const int64_t* q_tags = nullptr;
     const int* q_cnt = nullptr;
     int m = 0;
-    // the range instantiation only (k_exact_scan_range, radad_knn_range_search): a row enters a query's list only when its key passes
-    // the strict test key > range_t (inner product: the radius; L2: minus the radius, the keys here being minus the squared distance),
-    // and every row that passes is counted into out_count[query] (zeroed by the caller); padding -1 / NaN / NaN
+    // the range instantiations only (k_exact_scan_range, radad_knn_range_search; with `admit` or the tags above: k_exact_scan_range_excl
+    // / _range_excl_pq, among the rows the query admits): a row enters a query's list only when its key passes the strict test
+    // key > range_t (inner product: the radius; L2: minus the radius, the keys here being minus the squared distance), and every row
+    // that passes is counted into out_count[query] (zeroed by the caller); padding -1 / NaN / NaN
     int* out_count = nullptr;
     double range_t = 0.0;
 };
@@ -2061,10 +2096,12 @@ __device__ __forceinline__ void exact_merge_slot(const ExactParams& p, int slot,
 // RANGE (alone, k_exact_scan_range, radad_knn_range_search): every row is read; the strict threshold test stands in front of the list
 // insertion, and each wave counts the rows that pass per query of its group -- one atomicAdd per wave, slice and query into
 // out_count.  The lists, the slice merge and the last-arrival merge are the other forms', with k = max_per_query.
+// RANGE with FILTERED (k_exact_scan_range_excl / _excl_pq, radad_knn_range_search_excl / _excl_pq): the strict test, the count and the
+// insertion happen only for the queries that admit the row -- the bitmap bit (the row is skipped before it is loaded, as in the
+// filtered form), or bit j of adm_q (a row nobody of the group admits is not loaded either).  An excluded row is never counted.
 template <bool FILTERED, bool PER_QUERY = false, bool RANGE = false>
 __global__ __launch_bounds__(KX_THREADS) void k_exact_scan_any(ExactParams p) {
     static_assert(FILTERED || !PER_QUERY, "the per-query form is a filtered form");
-    static_assert(!RANGE || !FILTERED, "the range form reads every row");
     const int count = min(*p.count - p.slot0, p.nslots);       // this launch's queries
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && p.host_stats) {
         *reinterpret_cast<volatile int*>(&p.host_stats[6]) = 0;          // the slot is being rewritten: no report until the new stamp is there
@@ -2242,6 +2279,8 @@ constexpr auto k_exact_scan = k_exact_scan_any<false>;
 constexpr auto k_exact_scan_excl = k_exact_scan_any<true>;
 constexpr auto k_exact_scan_excl_pq = k_exact_scan_any<true, true>;
 constexpr auto k_exact_scan_range = k_exact_scan_any<false, false, true>;
+constexpr auto k_exact_scan_range_excl = k_exact_scan_any<true, false, true>;
+constexpr auto k_exact_scan_range_excl_pq = k_exact_scan_any<true, true, true>;
 
 // one wave: merge the KX_SLICES partial lists of this launch's rejected-query slot `slot`, overwrite the query's output rows
 template <bool FILTERED>
@@ -4361,62 +4400,102 @@ static int knn_search_excl_scan_pq_locked(radad_knn_t h, const void* q_in, int q
 // abandon included), k_range_refine; the queries whose buffer overflowed go, driven from the device, to the exact range kernel.
 // Exact route: that kernel for every query.  Like the siblings above: KnnTuning is read (hi_skip) and never written, no report is
 // posted, no turn is taken.
-static int knn_range_search_locked(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, float radius, int m, int32_t* out_count_dev,
-                                   float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, hipStream_t st) {
+// rule: NULL (radad_knn_range_search), or what the queries exclude (radad_knn_range_search_excl / _excl_pq; knn_range_excl_plan):
+//   one set for the batch   the bitmap and the NaN bias of radad_knn_search_excl_scan in front of the scan, which then runs the biased
+//                           instantiation with this eps and never emits an excluded row; the plain k_range_refine; overflow and the
+//                           exact route go to k_exact_scan_range_excl with the same bitmap;
+//   a set per query (m > 0; m == 0 arrives here as NULL)   the plain range search's scan, k_range_refine<true>, which drops a query's
+//                           excluded rows while it compacts; overflow and the exact route go to k_exact_scan_range_excl_pq.
+static int knn_range_search_locked(const char* fn, radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, float radius, int m,
+                                   const ExclRule* rule, int32_t* out_count_dev, float* out_dist_dev, int64_t* out_idx_dev,
+                                   double* out_key_dev, hipStream_t st) {
     int rc = knn_order_behind_last(h, st);
     if (rc) return rc;
-    RangePlan X = knn_range_plan(knn_store_facts(h), nq, m, h->tune.hi_skip);
+    const bool batch = rule && !rule->per_query, pq = rule && rule->per_query;
+    struct { int route; StoreFacts facts; ScanPlan plan; int launches; } X;
+    auto make_plan = [&] {
+        if (rule) {
+            const RangeExclPlan e = knn_range_excl_plan(knn_store_facts(h), nq, m, pq ? KNN_RANGE_EXCL_PER_QUERY : KNN_RANGE_EXCL_BATCH,
+                                                        rule->m(), h->tune.hi_skip);
+            X.route = e.route; X.facts = e.facts; X.plan = e.plan; X.launches = e.launches;
+        } else {
+            const RangePlan e = knn_range_plan(knn_store_facts(h), nq, m, h->tune.hi_skip);
+            X.route = e.route; X.facts = e.facts; X.plan = e.plan; X.launches = e.launches;
+        }
+    };
+    make_plan();
     bool tile = X.route == RADAD_RANGE_TILE;
     if (tile && !knn_ensure_hi(h, st, true)) {                     // (a plane that cannot be allocated switches itself off: exact route)
         tile = false;
-        X = knn_range_plan(knn_store_facts(h), nq, m, h->tune.hi_skip);
-        RADAD_REQUIRE(X.route == RADAD_RANGE_EXACT, "radad_knn_range_search: a store without a plane planned the tile route");
+        make_plan();
+        RADAD_REQUIRE(X.route == RADAD_RANGE_EXACT, "%s: a store without a plane planned the tile route", fn);
     }
     if (!tile && !knn_ensure_hi(h, st, false)) { radad_set_error("store statistics could not be computed"); return RADAD_EHIP; }
     ScanPlan p = X.plan;
-    p.mu = (p.hi_q && !h->f16) ? h->cmu : nullptr;                 // the plain search's instantiation (knn_plan_scan)
-    p.biased = p.hi_q && (p.l2 || p.mu);
-    RADAD_REQUIRE(!tile || p.emit_cap <= RG_MAX_CAP, "radad_knn_range_search: %d-entry candidate buffers exceed the re-rank's %d", p.emit_cap, RG_MAX_CAP);
+    p.mu = (p.hi_q && !h->f16) ? h->cmu : nullptr;                 // the plain search's instantiation (knn_plan_scan) ...
+    if (!batch) p.biased = p.hi_q && (p.l2 || p.mu);               // ... (one set for the batch: the biased one whatever the plane, the plan's)
+    RADAD_REQUIRE(!tile || p.emit_cap <= RG_MAX_CAP, "%s: %d-entry candidate buffers exceed the re-rank's %d", fn, p.emit_cap, RG_MAX_CAP);
     const SearchLayout L = knn_search_layout(X.facts, p, q_dtype);
     if (L.bytes > h->ws_bytes) {
         RADAD_HIP_CHECK(hipDeviceSynchronize());
         rc = knn_workspace(h, L.bytes);
         if (rc) return rc;
     }
-    const RangeLayout B = knn_range_layout(X.facts, nq, m);        // the exact pass's partial lists, k = m
-    rc = knn_excl_reserve(h, B.bytes);
+    // the exact pass's partial lists, k = m; one set for the batch: the bitmap and the bias array behind them
+    const RangeExclLayout E = knn_range_excl_layout(X.facts, nq, m, tile ? RADAD_RANGE_TILE : RADAD_RANGE_EXACT);
+    const RangeLayout B = E.lists;
+    rc = knn_excl_reserve(h, batch ? E.bytes : B.bytes);
     if (rc) return rc;
     rc = knn_ensure_xarrive(h, nq, st);
     if (rc) return rc;
     h->last_emit_nq = 0;                                           // (the workspace no longer holds the last plain tile scan's counters)
     h->last_xs_nq = 0;
     h->last_rg_nq = 0;
+    // one set for the batch: the admission bitmap (all ones when nothing is excluded: the tags may be NULL then)
+    unsigned long long* admit = batch ? reinterpret_cast<unsigned long long*>((char*)h->excl_ws + E.admit) : nullptr;
+    if (batch) {
+        if (rule->n_excl > 0)
+            hipLaunchKernelGGL(k_admit_bitmap<false>, dim3((unsigned)ceil_div64(E.n_words * 64, 256)), dim3(256), 0, st, rule->tags,
+                               (const int64_t*)nullptr, h->ntotal, rule->excl, rule->n_excl, (const int*)nullptr, admit, E.n_words);
+        else
+            RADAD_HIP_CHECK(hipMemsetAsync(admit, 0xff, (size_t)E.n_words * sizeof(unsigned long long), st));
+    }
     const float* q_use = knn_prepare_queries(h, p, L, q_in, q_dtype, st);      // (clears the listed-query counter and the candidate counters)
     RADAD_HIP_CHECK(hipGetLastError());
     int* flag_count = ws_at<int>(h, L.fcount);
     int* flag_sel = ws_at<int>(h, L.fsel);
 
     if (tile) {
+        // one set for the batch: the per-call bias, NaN for the rows the bitmap does not admit (no compare of the scan passes a NaN)
+        float* bias = nullptr;
+        if (batch) {
+            bias = reinterpret_cast<float*>((char*)h->excl_ws + E.bias);
+            hipLaunchKernelGGL(k_excl_scan_bias, dim3((unsigned)ceil_div64(h->ntotal, 256)), dim3(256), 0, st, (const unsigned long long*)admit,
+                               (const float*)(p.mu ? h->rbias : (p.l2 ? h->ynorm : nullptr)), h->ntotal, bias);
+        }
         // scan scores estimate q.y (IP / cosine) or -|q - y|^2 (L2): the threshold in their units
         float* floors = ws_at<float>(h, L.thr);
         hipLaunchKernelGGL(k_range_floor, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, st, ws_at<const float>(h, L.eps),
                            p.l2 ? -radius : radius, floors, nq);
         RADAD_HIP_CHECK(hipGetLastError());
         h->prof.next_search();
-        rc = knn_scan_hi_tile(h, p, L, st, nullptr, nullptr, floors);
+        rc = knn_scan_hi_tile(h, p, L, st, bias, nullptr, floors);
         if (rc) return rc;
         RADAD_HIP_CHECK(hipGetLastError());
-        RADAD_REQUIRE(h->last_scan_launches == X.launches, "radad_knn_range_search: %d scan launches, planned %d", h->last_scan_launches, X.launches);
+        RADAD_REQUIRE(h->last_scan_launches == X.launches, "%s: %d scan launches, planned %d", fn, h->last_scan_launches, X.launches);
         h->last_o_cnt = L.cnt; h->last_o_thr = L.thr; h->last_emit_nq = nq;
-        RangeRefineParams g;
+        RangeRefinePqParams g;
         g.idx = ws_at<const int>(h, L.pi); g.cnt = ws_at<const int>(h, L.cnt); g.cap = p.emit_cap; g.dim = h->dim; g.l2 = p.l2;
         g.db_f16 = h->f16; g.m = m; g.db = h->rows; g.q = q_use; g.radius = (double)radius; g.id_base = h->id_base; g.ntotal = h->ntotal;
         g.flag_count = flag_count; g.flag_sel = flag_sel;
         g.out_count = out_count_dev; g.out_dist = out_dist_dev; g.out_idx = out_idx_dev; g.out_key = out_key_dev;
-        const size_t glds = range_refine_lds_bytes();
-        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_range_refine), hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds));
+        if (pq) { g.tags = rule->tags; g.q_tags = rule->q_tags; g.q_cnt = rule->q_cnt; g.n_tags = rule->m(); }
+        const size_t glds = pq ? range_refine_pq_lds_bytes() : range_refine_lds_bytes();
+        const void* refine = pq ? reinterpret_cast<const void*>(k_range_refine<true>) : reinterpret_cast<const void*>(k_range_refine<false>);
+        RADAD_HIP_CHECK(hipFuncSetAttribute(refine, hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds));
         h->prof.begin(st);                                         // (the call's second profile entry: its re-rank)
-        hipLaunchKernelGGL(k_range_refine, dim3((unsigned)nq), dim3(RF_THREADS), glds, st, g);
+        if (pq) hipLaunchKernelGGL(k_range_refine<true>, dim3((unsigned)nq), dim3(RF_THREADS), glds, st, g);
+        else hipLaunchKernelGGL(k_range_refine<false>, dim3((unsigned)nq), dim3(RF_THREADS), glds, st, static_cast<const RangeRefineParams&>(g));
         h->prof.end(st);
     } else {
         RADAD_HIP_CHECK(hipMemsetAsync(out_count_dev, 0, (size_t)nq * sizeof(int32_t), st));
@@ -4438,13 +4517,16 @@ static int knn_range_search_locked(radad_knn_t h, const void* q_in, int q_dtype,
         x.arrive = h->xarrive;
         x.out_count = out_count_dev;
         x.range_t = p.l2 ? -(double)radius : (double)radius;
+        if (batch) x.admit = admit;
+        if (pq) { x.row_tags = rule->tags; x.q_tags = rule->q_tags; x.q_cnt = rule->q_cnt; x.m = rule->m(); }
+        const auto kern = batch ? k_exact_scan_range_excl : pq ? k_exact_scan_range_excl_pq : k_exact_scan_range;
         const size_t xlds = knn_exact_dyn_lds_bytes(h->dim, m);      // (with the static arrival flag <= KX_LDS_MAX: the entry point checked)
-        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_exact_scan_range), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
+        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
         const unsigned gy = m <= KNN_F16_MAX_K ? KX_GROUPS_Y : 8 * KX_GROUPS_Y;
         x.nslots = (int)B.xslots;
         for (int64_t s0 = 0; s0 < nq; s0 += x.nslots) {            // (launches past the device-side count leave at once)
             x.slot0 = (int)s0;
-            hipLaunchKernelGGL(k_exact_scan_range, dim3(KX_SLICES, gy), dim3(KX_THREADS), xlds, st, x);
+            hipLaunchKernelGGL(kern, dim3(KX_SLICES, gy), dim3(KX_THREADS), xlds, st, x);
         }
         RADAD_HIP_CHECK(hipGetLastError());
     }
@@ -4558,25 +4640,64 @@ int radad_knn_search_excl_scan_pq(radad_knn_t h, const void* q_dev, int q_dtype,
     return knn_search_excl_scan_pq_locked(h, q_dev, q_dtype, nq, k, r, out_dist_dev, out_idx_dev, out_key_dev, (hipStream_t)stream);
 }
 
-int radad_knn_range_search(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, float radius, int max_per_query,
-                           int32_t* out_count_dev, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, void* stream) {
-    RADAD_REQUIRE(h, "NULL handle");
-    RADAD_REQUIRE(q_dtype == RADAD_Q_F32 || q_dtype == RADAD_Q_BF16, "radad_knn_range_search: unsupported query dtype %d", q_dtype);
-    RADAD_REQUIRE(max_per_query >= 1 && max_per_query <= RADAD_KNN_MAX_K, "radad_knn_range_search: max_per_query=%d outside [1,%d]",
-                  max_per_query, RADAD_KNN_MAX_K);
-    RADAD_REQUIRE(knn_exact_fits(h->dim, max_per_query),
-                  "radad_knn_range_search: dim %d x max_per_query %d too large for the exact kernel (dim * 4 + 96 k + 16 <= %zu)", h->dim,
-                  max_per_query, KX_LDS_MAX);
-    RADAD_REQUIRE(radius == radius, "radad_knn_range_search: the radius is not a number");
-    RADAD_REQUIRE(nq >= 0 && nq < (1ll << 31) - KT_N, "radad_knn_range_search: bad nq");
+// the three range calls behind their own argument checks: rule NULL = nothing is excluded
+static int knn_range_search_entry(const char* fn, radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, float radius, int max_per_query,
+                                  const ExclRule* rule, int32_t* out_count_dev, float* out_dist_dev, int64_t* out_idx_dev,
+                                  double* out_key_dev, void* stream) {
     if (nq == 0) return RADAD_OK;
-    RADAD_REQUIRE(q_dev && out_count_dev && out_dist_dev && out_idx_dev, "radad_knn_range_search: NULL buffer");
+    RADAD_REQUIRE(q_dev && out_count_dev && out_dist_dev && out_idx_dev, "%s: NULL buffer", fn);
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
-    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_range_search: a radad_knn_search_begin on this handle has not been finished");
-    if (h->ntotal == 0) { radad_set_error("radad_knn_range_search: the store is empty"); return RADAD_ESTATE; }
-    return knn_range_search_locked(h, q_dev, q_dtype, nq, radius, max_per_query, out_count_dev, out_dist_dev, out_idx_dev, out_key_dev,
-                                   (hipStream_t)stream);
+    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "%s: a radad_knn_search_begin on this handle has not been finished", fn);
+    if (h->ntotal == 0) { radad_set_error("%s: the store is empty", fn); return RADAD_ESTATE; }
+    return knn_range_search_locked(fn, h, q_dev, q_dtype, nq, radius, max_per_query, rule, out_count_dev, out_dist_dev, out_idx_dev,
+                                   out_key_dev, (hipStream_t)stream);
+}
+// what every range call refuses, before anything else
+static int knn_range_check_args(const char* fn, radad_knn_t h, int q_dtype, int64_t nq, float radius, int max_per_query) {
+    RADAD_REQUIRE(h, "NULL handle");
+    RADAD_REQUIRE(q_dtype == RADAD_Q_F32 || q_dtype == RADAD_Q_BF16, "%s: unsupported query dtype %d", fn, q_dtype);
+    RADAD_REQUIRE(max_per_query >= 1 && max_per_query <= RADAD_KNN_MAX_K, "%s: max_per_query=%d outside [1,%d]", fn, max_per_query,
+                  RADAD_KNN_MAX_K);
+    RADAD_REQUIRE(knn_exact_fits(h->dim, max_per_query), "%s: dim %d x max_per_query %d too large for the exact kernel (dim * 4 + 96 k + 16 <= %zu)",
+                  fn, h->dim, max_per_query, KX_LDS_MAX);
+    RADAD_REQUIRE(radius == radius, "%s: the radius is not a number", fn);
+    RADAD_REQUIRE(nq >= 0 && nq < (1ll << 31) - KT_N, "%s: bad nq", fn);
+    return RADAD_OK;
+}
+
+int radad_knn_range_search(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, float radius, int max_per_query,
+                           int32_t* out_count_dev, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, void* stream) {
+    const int bad = knn_range_check_args("radad_knn_range_search", h, q_dtype, nq, radius, max_per_query);
+    if (bad) return bad;
+    return knn_range_search_entry("radad_knn_range_search", h, q_dev, q_dtype, nq, radius, max_per_query, nullptr, out_count_dev, out_dist_dev,
+                                  out_idx_dev, out_key_dev, stream);
+}
+
+int radad_knn_range_search_excl(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, float radius, int max_per_query,
+                                const int64_t* row_tags_dev, const int64_t* excl_sorted_dev, int64_t n_excl, int32_t* out_count_dev,
+                                float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, void* stream) {
+    const char* fn = "radad_knn_range_search_excl";
+    const int bad = knn_range_check_args(fn, h, q_dtype, nq, radius, max_per_query);
+    if (bad) return bad;
+    RADAD_REQUIRE(n_excl >= 0 && (n_excl == 0 || (excl_sorted_dev && row_tags_dev)), "%s: %lld excluded tags need the exclusion set and the row tags",
+                  fn, (long long)n_excl);
+    const ExclRule r = knn_excl_rule_batch(row_tags_dev, excl_sorted_dev, n_excl);
+    return knn_range_search_entry(fn, h, q_dev, q_dtype, nq, radius, max_per_query, &r, out_count_dev, out_dist_dev, out_idx_dev, out_key_dev, stream);
+}
+
+int radad_knn_range_search_excl_pq(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, float radius, int max_per_query,
+                                   const int64_t* row_tags_dev, const int64_t* q_tags_dev, int m, const int32_t* q_tag_counts_dev,
+                                   int32_t* out_count_dev, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, void* stream) {
+    const char* fn = "radad_knn_range_search_excl_pq";
+    int bad = knn_range_check_args(fn, h, q_dtype, nq, radius, max_per_query);
+    if (bad) return bad;
+    ExclRule r;
+    bad = knn_excl_pq_rule(fn, row_tags_dev, q_tags_dev, m, q_tag_counts_dev, &r);
+    if (bad) return bad;
+    // m == 0: nothing is excluded -- the plain range search outright
+    return knn_range_search_entry(fn, h, q_dev, q_dtype, nq, radius, max_per_query, m > 0 ? &r : nullptr, out_count_dev, out_dist_dev, out_idx_dev,
+                                  out_key_dev, stream);
 }
 
 int radad_knn_last_range(radad_knn_t h, int64_t* n_queries, int* route, int* n_exact) {

@@ -564,6 +564,55 @@ static RangeLayout knn_range_layout(const StoreFacts& s, int64_t nq, int max_per
     return L;
 }
 
+// ---- certified range search among the rows a query does not exclude (radad_knn_range_search_excl / _excl_pq) ----------------------
+// Route, facts (4096-entry buffers) and the ONE scan launch are knn_range_plan's, whatever the mode and whatever is excluded.
+//   KNN_RANGE_EXCL_BATCH      one set for the batch: the pre-pass (k_excl_scan_bias, 1 launch on the tile route) writes a per-call bias
+//                             that is NaN for the excluded rows, so the plan carries the BIASED instantiation whatever the plane, as
+//                             radad_knn_search_excl_scan's does (RSC 2 / 3; mu is the caller's: without a centre the query constant is 0);
+//   KNN_RANGE_EXCL_PER_QUERY  <= 64 tags per query: the plain range search's own plan, member for member -- the scan emits excluded rows
+//                             like any others and the re-rank (k_range_refine<true>) drops them while it compacts: no bias, no scrub
+//                             launch (k_excl_pq_scrub serves k_kth_floor, which a range search never runs).
+// m (tags per query) changes nothing of the plan: m == 0 is answered by the plain range path outright (knn.hip).
+constexpr int KNN_RANGE_EXCL_BATCH = 0;
+constexpr int KNN_RANGE_EXCL_PER_QUERY = 1;
+struct RangeExclPlan {
+    int mode = KNN_RANGE_EXCL_BATCH;
+    int route = RADAD_RANGE_EXACT;
+    StoreFacts facts;
+    ScanPlan plan;
+    int launches = 0;            // tile route: launches of the scan (1); exact route: 0
+    int prepass_launches = 0;    // batch mode, tile route: the bias pre-pass (1)
+    int scrub_launches = 0;      // always 0
+};
+static RangeExclPlan knn_range_excl_plan(const StoreFacts& s, int64_t nq, int max_per_query, int mode, int m, int fp32_searches_left) {
+    (void)m;
+    const RangePlan r = knn_range_plan(s, nq, max_per_query, fp32_searches_left);
+    RangeExclPlan x;
+    x.mode = mode; x.route = r.route; x.facts = r.facts; x.plan = r.plan; x.launches = r.launches;
+    if (mode == KNN_RANGE_EXCL_BATCH) {
+        x.plan.biased = x.plan.hi_q;
+        x.prepass_launches = r.route == RADAD_RANGE_TILE ? 1 : 0;
+    }
+    return x;
+}
+// The exclusion workspace of the batch mode: the exact pass's partial lists (RangeLayout, unchanged) | the admission bitmap | on the
+// tile route the per-call bias array (ExclScanLayout's two arrays, moved behind the lists).
+struct RangeExclLayout {
+    RangeLayout lists;
+    size_t admit = 0, bias = 0, bytes = 0;
+    int64_t n_words = 0;
+};
+static RangeExclLayout knn_range_excl_layout(const StoreFacts& s, int64_t nq, int max_per_query, int route) {
+    RangeExclLayout L;
+    L.lists = knn_range_layout(s, nq, max_per_query);
+    const ExclScanLayout e = knn_excl_scan_layout(s, route == RADAD_RANGE_TILE ? RADAD_EXCL_SCAN_TILE : RADAD_EXCL_SCAN_EXACT);
+    L.n_words = e.n_words;
+    L.admit = L.lists.bytes + e.admit;
+    L.bias = L.lists.bytes + e.bias;
+    L.bytes = L.lists.bytes + e.bytes;
+    return L;
+}
+
 // ---- adaptive tuning --------------------------------------------------------------------------------------------------------------
 // What a handle does when the certificate rejects more than a quarter of a batch of >= 64 queries: re-decide the plane if rows were
 // appended since it was decided, else widen the candidate buffers once (cap_boost 1 -> 4), else leave the certified f16 kernels for

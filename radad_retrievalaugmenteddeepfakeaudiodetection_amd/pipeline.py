@@ -90,12 +90,23 @@ class HotPathPipeline:
         return ["unknown"] * batch_size
 
     # ---- audit by content ---------------------------------------------------------------------------------
-    def near_duplicates(self, query_vectors, thresh: float, max_per_query: int = 128, query_paths: Optional[List[str]] = None):
+    def near_duplicates(self, query_vectors, thresh: float, max_per_query: int = 128, query_paths: Optional[List[str]] = None,
+                        exact_exclusion: bool = False, exclude: str = "file", query_speakers: Optional[List[str]] = None):
         """Per query the stored rows within `thresh` of it (VectorDatabase.range_search_batch: cosine / inner product > thresh, or
         squared L2 < thresh, exactly), as a list of (path, label, score), best first, at most max_per_query.  The content
         counterpart of validate_no_leakage (pipeline.py:1105-1110), which compares basenames and so passes a re-encoded or renamed
         copy of a training clip.  With `query_paths`, entries whose basename equals the query's own are dropped (the file itself),
-        a copy under another name stays."""
+        a copy under another name stays.
+        That default filters AFTER the search: the query's own rows have taken slots of max_per_query by then, and nothing says how
+        many other rows exist.  exact_exclusion=True runs the exclusion IN the search
+        (VectorDatabase.range_search_excluding_per_query_batch) and returns (hits, counts): counts[j] is the exact number of admissible
+        rows within the radius, and all max_per_query slots go to admissible rows.  exclude="file": query j excludes the rows whose
+        basename is that of query_paths[j]; exclude="speaker": the rows whose stored speaker_id metadata equals query_speakers[j]
+        (leave-one-speaker-out)."""
+        if exclude not in ("file", "speaker"):
+            raise ValueError(f"exclude must be 'file' or 'speaker', got {exclude!r}")
+        if exact_exclusion:
+            return self._near_duplicates_excluding(query_vectors, thresh, max_per_query, query_paths, exclude, query_speakers)
         lims, dist, idx = self.vector_db.range_search_batch(query_vectors, thresh, max_per_query=max_per_query)[:3]
         if hasattr(lims, "cpu"):
             lims, dist, idx = lims.cpu().numpy(), dist.cpu().numpy(), idx.cpu().numpy()
@@ -111,6 +122,44 @@ class HotPathPipeline:
                 hits.append((path, self.vector_db.vector_labels[int(i) - base], float(d)))
             out.append(hits)
         return out
+
+    @staticmethod
+    def _speaker_tag(speaker) -> int:
+        """stable 63-bit tag of a speaker id, as path_tag is of a basename"""
+        import hashlib
+        h = hashlib.blake2b(str(speaker).encode("utf-8", "surrogatepass"), digest_size=8).digest()
+        return int.from_bytes(h, "little") & 0x7FFFFFFFFFFFFFFF
+
+    def _near_duplicates_excluding(self, query_vectors, thresh, max_per_query, query_paths, exclude, query_speakers):
+        import torch
+        from .vector_database import path_tag
+        vdb = self.vector_db
+        nq = 1 if getattr(query_vectors, "ndim", 2) == 1 else len(query_vectors)
+        if exclude == "file":
+            if query_paths is None:
+                raise ValueError("exact_exclusion with exclude='file' needs query_paths")
+            row_tags, q_tags = None, [path_tag(p) for p in query_paths]               # (the per-row basename tags the store keeps)
+        else:
+            if query_speakers is None:
+                raise ValueError("exact_exclusion with exclude='speaker' needs query_speakers")
+            stored = vdb.vector_metadata.get("speaker_id") if isinstance(vdb.vector_metadata, dict) else None
+            if stored is None or len(stored) != len(vdb.vector_paths):
+                raise ValueError("exclude='speaker' needs the speaker_id metadata of every stored row")
+            cache = getattr(self, "_speaker_tags", None)
+            if cache is None or cache.numel() != len(stored):
+                cache = self._speaker_tags = torch.tensor([self._speaker_tag(s_) for s_ in stored], dtype=torch.int64,
+                                                          device=torch.device("cuda", vdb.device_id))
+            row_tags, q_tags = cache, [self._speaker_tag(s_) for s_ in query_speakers]
+        if len(q_tags) != nq:
+            raise ValueError(f"{nq} queries, {len(q_tags)} {'query_paths' if exclude == 'file' else 'query_speakers'}")
+        lims, dist, idx, counts = vdb.range_search_excluding_per_query_batch(query_vectors, thresh, query_tags=q_tags, max_per_query=max_per_query,
+                                                                             return_counts=True, row_tags=row_tags)
+        if hasattr(lims, "cpu"):
+            lims, dist, idx, counts = lims.cpu().numpy(), dist.cpu().numpy(), idx.cpu().numpy(), counts.cpu().numpy()
+        base = vdb.index.id_base if hasattr(vdb.index, "id_base") else 0
+        out = [[(vdb.vector_paths[int(i) - base], vdb.vector_labels[int(i) - base], float(d))
+                for d, i in zip(dist[lims[j]:lims[j + 1]], idx[lims[j]:lims[j + 1]])] for j in range(len(lims) - 1)]
+        return out, counts
 
     # ---- retrieve -----------------------------------------------------------------------------------------
     def retrieve_similar_vectors(self, query_vectors, query_paths: Optional[List[str]] = None, exclude_self: bool = True,

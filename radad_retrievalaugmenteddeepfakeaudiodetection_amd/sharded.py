@@ -250,6 +250,16 @@ class ShardedSearch:
                          "row of that shard within the radius, so concatenating the shards' lists per query (and adding their counts) "
                          "is the merge")
 
+    def range_search_excluding(self, *args, **kwargs):
+        raise ValueError("range_search_excluding has no sharded form of its own: a shard's result of HipFlatIndex.range_search_excluding "
+                         "is already every admissible row of that shard within the radius, so concatenating the shards' lists per query "
+                         "(and adding their counts) is the merge")
+
+    def range_search_excluding_per_query(self, *args, **kwargs):
+        raise ValueError("range_search_excluding_per_query has no sharded form of its own: a shard's result of "
+                         "HipFlatIndex.range_search_excluding_per_query is already every admissible row of that shard within the radius, so "
+                         "concatenating the shards' lists per query (and adding their counts) is the merge")
+
     def search_excluding(self, q_local, k: int, exclude_tags_local=None, k_fetch=None, return_all: bool = False,
                          query_tags_local=None, query_tag_counts_local=None):
         """The exclusion-aware search (HipFlatIndex.search_excluding) over the row shards: q_local [Q_r, D], exclude_tags_local int64
@@ -424,6 +434,14 @@ class ReplicatedSearch:
     def range_search(self, *args, **kwargs):
         raise ValueError("range_search has no replicated form of its own: every rank holds the whole store, so "
                          "HipFlatIndex.range_search on the rank's store with the rank's own queries is the answer")
+
+    def range_search_excluding(self, *args, **kwargs):
+        raise ValueError("range_search_excluding has no replicated form of its own: every rank holds the whole store, so "
+                         "HipFlatIndex.range_search_excluding on the rank's store with the rank's own queries and set is the answer")
+
+    def range_search_excluding_per_query(self, *args, **kwargs):
+        raise ValueError("range_search_excluding_per_query has no replicated form of its own: every rank holds the whole store, so "
+                         "HipFlatIndex.range_search_excluding_per_query on the rank's store with the rank's own queries is the answer")
 
     def search_excluding(self, q_local, k: int, exclude_tags_local=None, k_fetch=None):
         """local_search_excluding(q_local, k, exclude_tags_local, k_fetch) on the rank's own queries with the rank's OWN exclusion set

@@ -354,10 +354,14 @@ class HipFlatIndex:
         lims[i]:lims[i + 1], best first.  Unlike faiss a query's list is cut to its `max_per_query` (<= 1024) best rows; a warning is
         logged once per call when any query was cut, and with return_counts the exact int32 counts (cut or not) come back as a fourth
         value.  numpy in -> numpy out; a CUDA tensor in -> CUDA tensors out."""
+        return self._range_csr(x, max_per_query, return_counts, lambda q: self.range_search_device(q, thresh, max_per_query))
+
+    def _range_csr(self, x, max_per_query: int, return_counts: bool, run):
+        """range_search's packing of a padded device result: run(q) -> (counts, D, I) for the device queries q"""
         import torch
         is_dev = hasattr(x, "is_cuda") and x.is_cuda
         q = x if is_dev else torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(torch.device("cuda", self.device))
-        counts, D, I = self.range_search_device(q, thresh, max_per_query)
+        counts, D, I = run(q)
         kept = counts.to(torch.int64).clamp(max=int(max_per_query))
         lims = torch.zeros((q.shape[0] + 1,), dtype=torch.int64, device=q.device)
         lims[1:] = torch.cumsum(kept, 0)
@@ -368,6 +372,55 @@ class HipFlatIndex:
         mask = torch.arange(D.shape[1], device=q.device).unsqueeze(0) < kept.unsqueeze(1)
         out = (lims, D[mask], I[mask]) + ((counts,) if return_counts else ())
         return out if is_dev else tuple(t.cpu().numpy() for t in out)
+
+    def range_search_excluding_device(self, q, thresh: float, row_tags, exclude_tags, max_per_query: int = 128, return_f64: bool = False):
+        """range_search_device among the rows whose tag is not in ONE set for the batch (radad_knn_range_search_excl): row_tags int64
+        CUDA tensor [ntotal] (indexed by id - id_base), exclude_tags int64 CUDA tensor sorted ascending, or None / empty.  The counts
+        are the exact numbers of ADMISSIBLE rows within the radius; an excluded row is never counted and never takes a slot."""
+        import torch
+        q, q_dtype = _prep_queries(q, self.d)
+        m = int(max_per_query)
+        row_tags, exclude_tags, n_excl = _prep_tags(row_tags, exclude_tags, self.ntotal)
+        counts = torch.empty((q.shape[0],), device=q.device, dtype=torch.int32)
+        D, I, K64 = _alloc_out(q, max(m, 0), return_f64)
+        with torch.cuda.device(q.device):
+            _lib.check(self._lib.radad_knn_range_search_excl(self._h, q.data_ptr(), q_dtype, q.shape[0], float(thresh), m, _ptr(row_tags),
+                                                             _ptr(exclude_tags), n_excl, counts.data_ptr(), D.data_ptr(), I.data_ptr(),
+                                                             _ptr(K64), _lib.stream_ptr(q.device)), "radad_knn_range_search_excl")
+        return (counts, D, I, K64) if return_f64 else (counts, D, I)
+
+    def range_search_excluding_per_query_device(self, q, thresh: float, row_tags, query_tags, query_tag_counts=None, max_per_query: int = 128,
+                                                return_f64: bool = False):
+        """range_search_device with one exclusion set PER QUERY (radad_knn_range_search_excl_pq; leave-one-file-out, leave-one-speaker-
+        out): row r is admissible for query j iff row_tags[r] is not among the first query_tag_counts[j] entries of query_tags[j].
+        Tag arguments as search_excluding_per_query (m <= 64 tags per query, any order, repeats allowed, counts clamped to [0, m],
+        None = m)."""
+        import torch
+        q, q_dtype = _prep_queries(q, self.d)
+        m = int(max_per_query)
+        row_tags, query_tags, tag_counts, n_tags = _prep_query_tags(row_tags, query_tags, query_tag_counts, q.shape[0], self.ntotal)
+        counts = torch.empty((q.shape[0],), device=q.device, dtype=torch.int32)
+        D, I, K64 = _alloc_out(q, max(m, 0), return_f64)
+        with torch.cuda.device(q.device):
+            _lib.check(self._lib.radad_knn_range_search_excl_pq(self._h, q.data_ptr(), q_dtype, q.shape[0], float(thresh), m, _ptr(row_tags),
+                                                                _ptr(query_tags), n_tags, _ptr(tag_counts), counts.data_ptr(), D.data_ptr(),
+                                                                I.data_ptr(), _ptr(K64), _lib.stream_ptr(q.device)),
+                       "radad_knn_range_search_excl_pq")
+        return (counts, D, I, K64) if return_f64 else (counts, D, I)
+
+    def range_search_excluding(self, x, thresh: float, row_tags, exclude_tags, max_per_query: int = 128, return_counts: bool = False):
+        """range_search among the rows whose tag is not in exclude_tags (one set for the batch): the same CSR result, the counts those
+        of the admissible rows.  The tags are CUDA tensors, as for search_excluding_in_scan."""
+        return self._range_csr(x, max_per_query, return_counts,
+                               lambda q: self.range_search_excluding_device(q, thresh, row_tags, exclude_tags, max_per_query))
+
+    def range_search_excluding_per_query(self, x, thresh: float, row_tags, query_tags, query_tag_counts=None, max_per_query: int = 128,
+                                         return_counts: bool = False):
+        """range_search with one exclusion set per query: the same CSR result, the counts those of each query's admissible rows.  The
+        tags are CUDA tensors, as for search_excluding_per_query_in_scan."""
+        return self._range_csr(x, max_per_query, return_counts,
+                               lambda q: self.range_search_excluding_per_query_device(q, thresh, row_tags, query_tags, query_tag_counts,
+                                                                                      max_per_query))
 
     def last_range(self):
         """{"queries", "route", "exact"} of the most recent range search: its batch size, "tile" or "exact", and how many of its queries
@@ -787,6 +840,14 @@ class HipIVFFlatIndex:
         raise ValueError("range_search is the flat store's search: an IVF search sees the probed lists, not the store, so it cannot "
                          "say that no other row is within the radius")
 
+    def range_search_excluding(self, *args, **kwargs):
+        raise ValueError("range_search_excluding is the flat store's search: an IVF search sees the probed lists, not the store, so it "
+                         "cannot say that no other admissible row is within the radius")
+
+    def range_search_excluding_per_query(self, *args, **kwargs):
+        raise ValueError("range_search_excluding_per_query is the flat store's search: an IVF search sees the probed lists, not the "
+                         "store, so it cannot say that no other admissible row is within the radius")
+
     MAX_K_PROBED = 26  # csrc/ivf.inc: the largest k the list scans hold (k + 6 <= 32 entries per (query, list))
 
     def search_probed_excluding(self, q, k: int, row_tags, exclude_tags):
@@ -1016,10 +1077,17 @@ class VectorDatabase:
         """Every stored row within `thresh` of each query, exactly, in faiss's CSR form (HipFlatIndex.range_search): -> (lims int64
         [B + 1], D, I), with return_counts also the exact int32 counts.  Inputs as search_batch: numpy in -> numpy out, a CUDA tensor
         in -> CUDA tensors out, a 1-d query is one query; an empty store returns empty results.  Flat stores only."""
+        query_vectors, empty = self._range_front("range_search_batch", query_vectors, return_counts)
+        if empty is not None:
+            return empty
+        return self.index.range_search(query_vectors, thresh, max_per_query=max_per_query, return_counts=return_counts)
+
+    def _range_front(self, name: str, query_vectors, return_counts: bool):
+        """the front of the range searches -> (query_vectors [B, d], None), or (query_vectors, the empty result of an empty store)"""
         if self.index is None:
             raise ValueError("Vector database is empty. Build the database first.")
         if not isinstance(self.index, HipFlatIndex):
-            raise ValueError("range_search_batch is flat and single-handle only (vector_db_index_type 'L2' or 'IP'): an IVF search "
+            raise ValueError(f"{name} is flat and single-handle only (vector_db_index_type 'L2' or 'IP'): an IVF search "
                              "sees the probed lists, not the store")
         is_dev = hasattr(query_vectors, "is_cuda") and query_vectors.is_cuda
         if not is_dev:
@@ -1034,10 +1102,47 @@ class VectorDatabase:
                 dev = query_vectors.device
                 out = (torch.zeros((nq + 1,), dtype=torch.int64, device=dev), torch.zeros((0,), dtype=torch.float32, device=dev),
                        torch.zeros((0,), dtype=torch.int64, device=dev))
-                return out + ((torch.zeros((nq,), dtype=torch.int32, device=dev),) if return_counts else ())
+                return query_vectors, out + ((torch.zeros((nq,), dtype=torch.int32, device=dev),) if return_counts else ())
             out = (np.zeros((nq + 1,), np.int64), np.zeros((0,), np.float32), np.zeros((0,), np.int64))
-            return out + ((np.zeros((nq,), np.int32),) if return_counts else ())
-        return self.index.range_search(query_vectors, thresh, max_per_query=max_per_query, return_counts=return_counts)
+            return query_vectors, out + ((np.zeros((nq,), np.int32),) if return_counts else ())
+        return query_vectors, None
+
+    def range_search_excluding_batch(self, query_vectors, thresh: float, exclude_tags=None, max_per_query: int = 128,
+                                     return_counts: bool = False, row_tags=None):
+        """range_search_batch among the rows whose tag is not in `exclude_tags` -- ONE set for the batch
+        (HipFlatIndex.range_search_excluding): the counts are the exact numbers of admissible rows within the radius, and an excluded
+        row never takes one of the max_per_query slots.  exclude_tags: int64 tensor / sequence of tags, or None / empty.  row_tags:
+        None = the basename tags (path_tag) kept per row, or an int64 [ntotal] column of the caller's own.  Flat stores only."""
+        import torch
+        query_vectors, empty = self._range_front("range_search_excluding_batch", query_vectors, return_counts)
+        if empty is not None:
+            return empty
+        dev = torch.device("cuda", self.device_id)
+        excl = None
+        if exclude_tags is not None and len(exclude_tags) > 0:
+            excl = torch.unique(torch.as_tensor(exclude_tags, dtype=torch.int64).to(dev).reshape(-1))       # sorted, as the kernel's search needs
+        tags = None if excl is None else (self.row_tags_device() if row_tags is None else torch.as_tensor(row_tags, dtype=torch.int64).to(dev))
+        return self.index.range_search_excluding(query_vectors, thresh, tags, excl, max_per_query=max_per_query, return_counts=return_counts)
+
+    def range_search_excluding_per_query_batch(self, query_vectors, thresh: float, query_tags=None, query_tag_counts=None,
+                                               max_per_query: int = 128, return_counts: bool = False, row_tags=None):
+        """range_search_batch with one exclusion set PER QUERY (HipFlatIndex.range_search_excluding_per_query; leave-one-file-out,
+        leave-one-speaker-out): query i excludes the rows whose tag is among the first query_tag_counts[i] entries of query_tags[i].
+        query_tags: int64 tensor / nested sequence [B, m] (or [B]), m <= 64, None = nothing excluded; query_tag_counts: [B] or None.
+        row_tags: None = the basename tags (path_tag) kept per row, or an int64 [ntotal] column of the caller's own.  Flat stores
+        only."""
+        import torch
+        query_vectors, empty = self._range_front("range_search_excluding_per_query_batch", query_vectors, return_counts)
+        if empty is not None:
+            return empty
+        dev = torch.device("cuda", self.device_id)
+        if query_tags is not None:
+            query_tags = torch.as_tensor(query_tags, dtype=torch.int64).to(dev)
+        if query_tag_counts is not None:
+            query_tag_counts = torch.as_tensor(query_tag_counts, dtype=torch.int32).to(dev)
+        tags = None if query_tags is None else (self.row_tags_device() if row_tags is None else torch.as_tensor(row_tags, dtype=torch.int64).to(dev))
+        return self.index.range_search_excluding_per_query(query_vectors, thresh, tags, query_tags, query_tag_counts,
+                                                           max_per_query=max_per_query, return_counts=return_counts)
 
     def _excluding_args(self, index_cls, wrong_index: str, query_vectors, k, exclude_tags, k_fetch=None):
         """the front of search_excluding / search_probed_excluding -> (query_vectors [B, d], k clamped to ntotal, k_fetch, row tags,
