@@ -98,6 +98,8 @@ int radad_knn_create_ex(int dim, int metric, int store_dtype, int device, int64_
  *   RADAD_KNN_OPT_ABANDON    1 (default) / 0: the certified tile scan leaves a 256 x 256 tile after its first K stages when no score
  *                            of it can still reach its query's admission floor (it pays on stores whose k-th neighbour stands clear
  *                            of the bulk of the rows; where it cannot, a scalar gate keeps the test from running) / it never does
+ *   RADAD_KNN_OPT_RANGE_SMALLQ  0 (default) / 1: the three range calls answer a batch of <= 16 queries on the float64 exact kernel / by
+ *                            streaming the f16 plane once (RADAD_RANGE_STREAM, below); no environment override
  * The environment variables RADAD_KNN_HI, RADAD_KNN_CENTRE, RADAD_KNN_SMALLQ_HI, RADAD_WIDE_MIN_Q override the DEFAULTS of handles
  * created while they are set (announced once per process on stderr); the product path never needs them. */
 #define RADAD_KNN_OPT_HI_PLANE 0
@@ -106,6 +108,7 @@ int radad_knn_create_ex(int dim, int metric, int store_dtype, int device, int64_
 #define RADAD_KNN_OPT_WIDE_MIN_Q 3
 #define RADAD_KNN_OPT_DENSE 4
 #define RADAD_KNN_OPT_ABANDON 5
+#define RADAD_KNN_OPT_RANGE_SMALLQ 6
 int radad_knn_set_option(radad_knn_t h, int option, int value);
 int radad_knn_destroy(radad_knn_t h);
 int radad_knn_dim(radad_knn_t h, int* dim);
@@ -488,12 +491,25 @@ int radad_knn_search_excl_scan_pq(radad_knn_t h, const void* q_dev, int q_dtype,
  *                 emitted rows in float64 from the stored rows, applies the strict test, counts, sorts the rows that pass by
  *                 (key, id) in LDS (48 KB) and writes the best M.  A query that emitted more than 4096 rows proves nothing: it goes,
  *                 driven from the device, to the exact range kernel.
+ *   RADAD_RANGE_STREAM only with RADAD_KNN_OPT_RANGE_SMALLQ set (default 0), and then exactly when the tile route is not taken, the
+ *                 handle is not on its fp32 fallback and the plain search of the batch could stream the plane: <= 16 queries,
+ *                 dim % 64 == 0, at least 16 384 rows, the plane on, RADAD_KNN_OPT_SMALLQ_HI set, the f16 query block within the LDS
+ *                 (16 queries of dim 5376 are not: they take the tile route, as before).  The small-batch search's query
+ *                 preparation and eps, the same k_range_floor, then ONE launch of k_range_hi_smallq: the stream body of
+ *                 k_knn_hi_smallq (queries in LDS, one wave per row slice, 16 rows per step, two MFMA chains) without lists -- a row
+ *                 whose score reaches its query's floor takes a slot of the query's 4096-entry buffer with one returning atomic.
+ *                 The same overflow rule and exact pass; the re-rank is k_range_refine's exact-order instantiation, whose float64
+ *                 re-score adds a row's products in the exact range kernel's order and with its roundings: counts, ids and the
+ *                 float64 keys of such a batch are, bit for bit, what RADAD_RANGE_EXACT returns for it (the plain re-rank's keys
+ *                 are 1 - 2 units of the last place off beyond 64 elements).  One wave per slice whatever the store: the
+ *                 K-split form of the plain small-batch search (small stores of wide rows) has no range kernel.
  *   RADAD_RANGE_EXACT  every other shape: k_exact_scan_any<false, false, true> for every query -- the float64 key of every row, the
  *                 strict test before the list insertion, one count per wave and slice added to out_count, top-M lists merged as in
  *                 any exact pass.  Correct everywhere; it streams the store once per group of <= 8 queries.
  * The call posts no certificate report, takes no turn off the tuning state and leaves radad_knn_tuning_info, radad_knn_last_recheck
  * and radad_knn_last_certificate as it found them; it may build the plane.  After a tile-route call radad_knn_last_emitted reports
- * the rows emitted per query and the floors T - eps, and radad_knn_last_abandon the one launch's tile tasks.
+ * the rows emitted per query and the floors T - eps, and radad_knn_last_abandon the one launch's tile tasks; after a stream-route
+ * call radad_knn_last_emitted reports the same, radad_knn_last_launch the stream's workgroups, and there are no tile tasks.
  * Errors, before anything is enqueued (outputs untouched, the handle usable): RADAD_EINVAL for M outside [1, RADAD_KNN_MAX_K], beyond
  * the width x k limit with M for k, for a NaN radius, NULL out_count / out_dist / out_idx, or a handle with a begun search;
  * RADAD_ESTATE on an empty store; nq == 0 returns RADAD_OK.  Stream-ordered and serialised like every search.
@@ -503,12 +519,19 @@ int radad_knn_search_excl_scan_pq(radad_knn_t h, const void* q_dev, int q_dtype,
  * run on one MI355X): 0.86 / 0.88 / 1.42 ms with 0 / 10 / 1000 rows above the threshold per query against 0.98 / 0.99 / 1.04 ms for
  * the plain k = 10 search of the same handle -- cheaper than the plain search while few rows pass (no sample pre-pass, one launch),
  * +37 % at 1000 hits (the re-score reads ~2 KB of row per emitted row: 0.36 ms; the scan's emits: +0.25 ms).  The scan's eps on that
- * store: 5.5e-4.  Not measured: the exact route's time per query, and stores on which the early abandon skips tiles.
+ * store: 5.5e-4.  Not measured: stores on which the early abandon skips tiles.
+ * Measured, <= 16 queries (tools/bench_range_smallq.py, profiles/README.md, "Range search", small batches; the same store shape, 1 / 8 /
+ * 16 queries, one run on one MI355X, the three legs alternated on one handle).  RADAD_RANGE_STREAM: 0.18 / 0.18 / 0.18 ms with no row
+ * above the threshold, 0.19 / 0.19 / 0.20 ms with 10, 0.38 / 0.37 / 0.42 ms with 1000 per query (the stream launch 0.17 - 0.24 ms, the
+ * re-rank of 1000 emitted rows per query 0.18 ms).  RADAD_RANGE_EXACT on the same handle: 3.6 / 10.9 / 10.8 ms whatever passes -- the
+ * stream takes 2 - 5 % of it.  The plain k = 10 search of the same handle (k_knn_hi_smallq<16>): 0.23 / 0.28 / 0.33 ms.  The default
+ * of RADAD_KNN_OPT_RANGE_SMALLQ is still 0: switching it is a change of its own.
  * Not offered: a begin / finish pair and sharded range search (a shard's answer is exact: concatenating the shards' lists is the
- * merge); the IVF index; a certified route for 16 or fewer queries; results beyond RADAD_KNN_MAX_K per query (the count is exact:
- * the caller can narrow the radius).  Exclusion sets combined with a radius: the two calls below. */
+ * merge); the IVF index; results beyond RADAD_KNN_MAX_K per query (the count is exact: the caller can narrow the radius).
+ * Exclusion sets combined with a radius: the two calls below. */
 #define RADAD_RANGE_TILE 0
 #define RADAD_RANGE_EXACT 1
+#define RADAD_RANGE_STREAM 2
 int radad_knn_range_search(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, float radius, int max_per_query,
                            int32_t* out_count_dev /*[nq]*/, float* out_dist_dev /*[nq,M]*/, int64_t* out_idx_dev /*[nq,M]*/,
                            double* out_key_dev /*[nq,M] or NULL*/, void* stream);
@@ -542,6 +565,10 @@ int radad_knn_last_range(radad_knn_t h, int64_t* n_queries, int* route, int* n_e
  *                 the buffer holds, excluded rows included": such a query goes to k_exact_scan_any<true, true, true> with the query
  *                 tags.  m == 0 takes the plain range path outright.  radad_knn_last_emitted counts the emitted rows, excluded ones
  *                 included.
+ *   RADAD_RANGE_STREAM (RADAD_KNN_OPT_RANGE_SMALLQ, <= 16 queries), one set for the batch: the same bitmap and bias pre-pass, the
+ *                 queries prepared for the biased instantiation, and k_range_hi_smallq reads the per-call bias as its row bias: a NaN
+ *                 score passes no compare, also against a floor of -inf.  One set per query: the plain stream launch and
+ *                 k_range_refine's per-query form, as on the tile route.  Overflow goes to the same exact kernels.
  *   RADAD_RANGE_EXACT: those exact kernels for every query.  With both a radius and a filter the strict test, the count and the list
  *                 insertion happen only for the queries that admit the row; a row nobody admits is not loaded.
  * State: as the sibling calls -- KnnTuning is read (hi_skip), never written; no certificate report, no turn off the tuning state;

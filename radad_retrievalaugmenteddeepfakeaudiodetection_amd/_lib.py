@@ -21,8 +21,9 @@ MAX_LEVELS = 8
 KNN_MAX_K = 1024
 EXCL_PQ_MAX_TAGS = 64     # RADAD_EXCL_PQ_MAX_TAGS
 EXCL_SCAN_TILE, EXCL_SCAN_EXACT = 0, 1      # RADAD_EXCL_SCAN_*
-RANGE_TILE, RANGE_EXACT = 0, 1                # RADAD_RANGE_*
+RANGE_TILE, RANGE_EXACT, RANGE_STREAM = 0, 1, 2     # RADAD_RANGE_*
 KNN_OPT_HI_PLANE, KNN_OPT_CENTRE, KNN_OPT_SMALLQ_HI, KNN_OPT_WIDE_MIN_Q, KNN_OPT_DENSE, KNN_OPT_ABANDON = 0, 1, 2, 3, 4, 5
+KNN_OPT_RANGE_SMALLQ = 6                      # RADAD_KNN_OPT_RANGE_SMALLQ
 IVF_OPT_HI_SCAN = 0
 IVF_OPT_PQ_FILTER = 1      # RADAD_IVF_OPT_PQ_FILTER
 IVF_SCAN_KINDS = ("f32_lists", "hi_lists", "exact_flat")

@@ -1012,6 +1012,88 @@ __global__ __launch_bounds__(SQ_THREADS, 2) void k_knn_hi_smallq(SmallQHiParams 
     }
 }
 
+// ---- the same stream as a threshold filter: the range search of a small batch (RADAD_RANGE_STREAM) -----------------------------------
+// k_knn_hi_smallq's stream body -- queries in LDS, one wave per slice of rows_per_wave rows, 16 rows per step, two MFMA chains, the
+// same scale / bias / query terms -- with nothing to select: a range search's floor is fixed per query (thr[q] = T - eps(q),
+// k_range_floor), so there are no register lists, no slot buffer and no hand-over between waves.  A (row, query) pair whose score
+// reaches the floor takes the next slot of the query's candidate buffer idx[q][cap] with one returning atomic on cnt[q]; the counter
+// counts past cap (cnt > cap: overflow, k_range_refine sends the query to the exact range kernel) while nothing is written past it.
+// Scores are not stored: k_range_refine re-scores every emitted row in float64 and reads nothing else of the scan.  A NaN score (the
+// per-call bias of an excluded row) passes no compare, also against a floor of -inf.  The order of a query's entries depends on the
+// order its atomics arrive in; the set does not, and the re-rank sorts.  LDS: the query block alone.
+struct RangeSmallQParams : SmallQHiParams {       // (k, n_parts, part_score, part_idx: not read)
+    const float* thr = nullptr;        // [nq] admission floors
+    int* cnt = nullptr;                // [nq] rows emitted, zeroed before the launch
+    int* idx = nullptr;                // [nq][cap] emitted rows
+    int cap = 0;
+};
+static_assert(std::is_trivially_copyable_v<RangeSmallQParams>, "kernel argument");
+
+__global__ __launch_bounds__(SQ_THREADS, 2) void k_range_hi_smallq(RangeSmallQParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int qld = p.dim + 8;                                    // padded query row (halfs), as k_knn_hi_smallq's
+    _Float16* sQ = reinterpret_cast<_Float16*>(smem);             // [nq][dim + 8]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r16 = lane & 15, g = lane >> 4;
+    for (int i = tid; i < p.nq * (p.dim >> 3); i += SQ_THREADS) {
+        const int qq = i / (p.dim >> 3), c8 = i % (p.dim >> 3);
+        *reinterpret_cast<f16x8*>(sQ + qq * qld + c8 * 8) = *reinterpret_cast<const f16x8*>(p.q + (int64_t)qq * p.dim + c8 * 8);
+    }
+    __syncthreads();
+
+    const int part = blockIdx.x * 4 + wave;      // this wave's slice of the store (beyond the store: w_end <= w_begin, no step runs)
+    const int64_t w_begin = (int64_t)part * p.rows_per_wave;
+    const int64_t w_end = min(w_begin + p.rows_per_wave, p.n);
+
+    const bool live = r16 < p.nq;                // columns >= nq repeat the last query and never emit
+    const float thr = live ? p.thr[r16] : INFINITY;
+    const float qs = live ? p.qscale[r16] * p.mult : 0.f;
+    const float qc = (live && p.qconst) ? p.qconst[r16] : 0.f;
+    const _Float16* qrow = sQ + min(r16, p.nq - 1) * qld + 8 * g;
+    const int nkb = p.dim >> 5;
+    int* my_cnt = p.cnt + min(r16, p.nq - 1);
+    int* my_idx = p.idx + (int64_t)min(r16, p.nq - 1) * p.cap;
+
+    for (int64_t row0 = w_begin; row0 < w_end; row0 += 16) {
+        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};       // even / odd K blocks: two MFMA chains
+        const int64_t ra = min(row0 + r16, p.n - 1);                             // clamp: masked below
+        const _Float16* pa = p.db + ra * p.dim + 8 * g;
+        float rs[4], yn[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int64_t row = min(row0 + 4 * g + e, p.n - 1);
+            rs[e] = p.rscale ? p.rscale[row] : p.uscale;
+            yn[e] = p.rbias ? p.bias_sign * p.rbias[row] + qc : qc;
+        }
+        constexpr int PKB = 16;                       // K blocks per panel
+        for (int kp = 0; kp < nkb; kp += PKB) {
+            const int nb = min(PKB, nkb - kp);
+            f16x8 v[PKB];
+#pragma unroll
+            for (int kb = 0; kb < PKB; ++kb)
+                if (kb < nb) v[kb] = *reinterpret_cast<const f16x8*>(pa + (kp + kb) * 32);
+#pragma unroll
+            for (int kb = 0; kb < PKB; ++kb)
+                if (kb < nb) {
+                    const f16x8 b = *reinterpret_cast<const f16x8*>(qrow + (kp + kb) * 32);
+                    if (kb & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(v[kb], b, acc1, 0, 0, 0);
+                    else acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(v[kb], b, acc0, 0, 0, 0);
+                }
+        }
+        // acc0[e] + acc1[e]: row row0 + 4g + e, query r16
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int64_t row = row0 + 4 * g + e;
+            const float sc = fmaf((acc0[e] + acc1[e]) * rs[e], qs, yn[e]);
+            if (row < w_end && live && sc >= thr) {
+                const int slot = atomicAdd(my_cnt, 1);
+                if (slot < p.cap) my_idx[slot] = (int)row;           // (the counter stays below 2^31: a store holds fewer rows)
+            }
+        }
+    }
+}
+
 // ---- the same streaming scan, K SPLIT over the four waves of a workgroup (small stores of wide rows) ---------------------------
 // The reference's own online search is ONE query of dim 5376 against 25 423 rows (pipeline.py:1038-1054, config.py:48-56): 1 589
 // 16-row steps in all.  With a wave per row slice that is at most 1 589 waves (6 per CU) each streaming 10.5 KB rows: too few loads
@@ -1297,6 +1379,15 @@ __global__ __launch_bounds__(RF_THREADS) void k_floor_from_sample(const float* _
 // 16 lanes per candidate, 32 candidates per pass (two per 16-lane group), all row loads of a pass issued before the first multiply
 // (the stored rows are random 2 KB reads: latency-bound unless many are in flight).  L2 as sum (q - y)^2: no cancellation.  Called by all
 // RF_THREADS threads; a candidate's key depends on its row and the query alone, not on its place in c_id.
+// EXACT_ORDER (the stream route of a range search, k_range_refine<.., true>): the key is k_exact_scan_any's bit for bit, so that a
+// batch of <= 16 queries gets the same float64 keys whether RADAD_KNN_OPT_RANGE_SMALLQ sends it to the stream or to the exact route.
+// That kernel gives chunk c (4 elements) of a row to lane c % 64, adds a lane's products in ascending c (L2: subtracts the squares),
+// folds lanes l and l ^ 32, then ^ 16, ^ 8 ... and negates an L2 sum at the end.  Here lane l16 of a candidate's 16 keeps four partial
+// sums -- those of lanes l16, l16 + 16, l16 + 32, l16 + 48 there: chunk u * 16 + l16 of a sweep belongs to partial u % 4 -- and folds
+// them (0 + 2) + (1 + 3) before the 16-lane fold both forms share.  The plain form is the code it was.
+// (tests/test_gpu_knn_range_smallq.py compares the two routes' keys bit for bit at dim 64, 128 and 576, inner product and L2: a
+// change of either kernel's sums shows there.)
+template <bool EXACT_ORDER = false>
 __device__ __forceinline__ void refine_rescore_f64(const void* db, int db_f16, const float* qrow, int dim, int l2, const int* c_id,
                                                    double* c_key, int nsel) {
     const int tid = threadIdx.x, sub = tid >> 4, l16 = tid & 15;
@@ -1305,6 +1396,7 @@ __device__ __forceinline__ void refine_rescore_f64(const void* db, int db_f16, c
         bool on[2];
         int64_t rid[2];
         double acc[2] = {0.0, 0.0};
+        double part[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};       // (EXACT_ORDER)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             cc[h] = c0 + 16 * h + sub;
@@ -1337,17 +1429,27 @@ __device__ __forceinline__ void refine_rescore_f64(const void* db, int db_f16, c
                     for (int h = 0; h < 2; ++h)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            if (l2) { const double d = (double)a[e] - (double)b[h][u][e]; acc[h] += d * d; }
-                            else acc[h] += (double)a[e] * (double)b[h][u][e];
+                            if constexpr (EXACT_ORDER) {
+                                // (the roundings of that kernel as compiled: the first element of a chunk joins the sum fused,
+                                // the other three as a rounded product -- stated here, not left to the contraction of this loop)
+#pragma clang fp contract(off)
+                                const double x = (double)a[e], y = (double)b[h][u][e], d = x - y;
+                                if (e == 0) part[h][u & 3] = l2 ? __builtin_fma(-d, d, part[h][u & 3]) : __builtin_fma(x, y, part[h][u & 3]);
+                                else { const double t = l2 ? d * -d : x * y; part[h][u & 3] = part[h][u & 3] + t; }
+                            } else {
+                                if (l2) { const double d = (double)a[e] - (double)b[h][u][e]; acc[h] += d * d; }
+                                else acc[h] += (double)a[e] * (double)b[h][u][e];
+                            }
                         }
                 }
             }
         }
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
+            if constexpr (EXACT_ORDER) acc[h] = (part[h][0] + part[h][2]) + (part[h][1] + part[h][3]);
 #pragma unroll
             for (int ofs = 8; ofs > 0; ofs >>= 1) acc[h] += __shfl_xor(acc[h], ofs, 64);
-            if (on[h] && l16 == 0) c_key[cc[h]] = acc[h];
+            if (on[h] && l16 == 0) c_key[cc[h]] = (EXACT_ORDER && l2) ? -acc[h] : acc[h];
         }
     }
 }
@@ -1745,7 +1847,8 @@ static_assert(std::is_trivially_copyable_v<RangeRefinePqParams>, "kernel argumen
 constexpr size_t range_refine_pq_lds_bytes() { return range_refine_lds_bytes() + (size_t)RADAD_EXCL_PQ_MAX_TAGS * sizeof(int64_t); }
 static_assert(range_refine_lds_bytes() % 8 == 0, "the tags behind the plain form's LDS are 8-byte entries");
 
-template <bool PER_QUERY = false>
+// EXACT_ORDER (k_range_refine<.., true>, the stream route): refine_rescore_f64<true>, the exact range kernel's keys bit for bit.
+template <bool PER_QUERY = false, bool EXACT_ORDER = false>
 __global__ __launch_bounds__(RF_THREADS) void k_range_refine(std::conditional_t<PER_QUERY, RangeRefinePqParams, RangeRefineParams> p) {
     extern __shared__ __attribute__((aligned(16))) char smem_g[];
     double* c_key = reinterpret_cast<double*>(smem_g);                   // [RG_MAX_CAP]
@@ -1796,7 +1899,7 @@ __global__ __launch_bounds__(RF_THREADS) void k_range_refine(std::conditional_t<
     for (int w = 0; w < 4; ++w) { if (w < wave) slot += w_cnt[w]; nsel += w_cnt[w]; }
     for (int i = tid; i < NE; i += RF_THREADS) { const int id = ebuf[i]; if (taken(id)) c_id[slot++] = id; }
     __syncthreads();
-    refine_rescore_f64(p.db, p.db_f16, p.q + q * p.dim, p.dim, p.l2, c_id, c_key, nsel);
+    refine_rescore_f64<EXACT_ORDER>(p.db, p.db_f16, p.q + q * p.dim, p.dim, p.l2, c_id, c_key, nsel);
     __syncthreads();
     // membership, and "larger is better" keys for the ranking
     int P = 1;
@@ -2838,6 +2941,7 @@ struct radad_knn_s {
     // rows the statistics kernel has seen -- built with the plane, extended by appends (only the tiles touched: an atomic max, which an
     // append can only raise), started over whenever the statistics start over (a new plane, a loaded snapshot)
     int opt_abandon = 1;         // RADAD_KNN_OPT_ABANDON
+    int opt_range_smallq = 0;    // RADAD_KNN_OPT_RANGE_SMALLQ
     float* tile_ry = nullptr;    // [2][tile_ry_cap]: per tile the largest suffix norm, then the largest accumulator start (bias_sign x bias)
     int64_t tile_ry_cap = 0;     // tiles
     int64_t ab_rows = 0;         // rows [0, ab_rows) are in tile_ry ...
@@ -3253,6 +3357,10 @@ int radad_knn_set_option(radad_knn_t h, int option, int value) {
             RADAD_REQUIRE(value == 0 || value == 1, "radad_knn_set_option: ABANDON takes 0 or 1");
             h->opt_abandon = value;
             return RADAD_OK;
+        case RADAD_KNN_OPT_RANGE_SMALLQ:
+            RADAD_REQUIRE(value == 0 || value == 1, "radad_knn_set_option: RANGE_SMALLQ takes 0 or 1");
+            h->opt_range_smallq = value;
+            return RADAD_OK;
         default:
             radad_set_error("radad_knn_set_option: unknown option %d", option);
             return RADAD_EINVAL;
@@ -3431,6 +3539,7 @@ static StoreFacts knn_store_facts(radad_knn_t h) {
     s.ntotal = h->ntotal; s.dim = h->dim; s.metric = h->metric; s.f16 = h->f16; s.hi_off = h->hi_off;
     s.opt_centre = h->opt_centre; s.opt_smallq_hi = h->opt_smallq_hi; s.opt_wide_min_q = h->opt_wide_min_q; s.opt_dense = h->opt_dense;
     s.cap_boost = h->tune.cap_boost;
+    s.opt_range_smallq = h->opt_range_smallq;
     return s;
 }
 
@@ -3735,8 +3844,8 @@ static int knn_launch_smallq(radad_knn_t h, void (*fn)(Params), const Params& sp
     return RADAD_OK;
 }
 
-static int knn_scan_hi_smallq(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, hipStream_t st) {
-    SmallQHiParams sp;
+// what every stream of the f16 plane is launched with
+static void knn_fill_smallq_hi(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, SmallQHiParams& sp) {
     sp.db = h->f16 ? (const _Float16*)h->rows : h->hi;
     sp.rscale = h->f16 ? nullptr : h->rscale;
     sp.uscale = h->f16 ? 1.0f : (h->uniform_e != HI_E_PER_ROW ? ldexpf(1.0f, -h->uniform_e) : (h->metric == RADAD_METRIC_COSINE ? 0x1p-14f : 1.0f));
@@ -3744,9 +3853,25 @@ static int knn_scan_hi_smallq(radad_knn_t h, const ScanPlan& p, const SearchLayo
     sp.qconst = p.biased ? ws_at<float>(h, L.qconst) : nullptr;
     sp.q = ws_at<_Float16>(h, L.qh); sp.qscale = ws_at<float>(h, L.qscale); sp.n = h->ntotal; sp.nq = (int)p.nq; sp.dim = h->dim; sp.k = p.ksel_sq;
     sp.rows_per_wave = p.sq_rows_per_wave; sp.n_parts = p.n_splits; sp.part_score = ws_at<float>(h, L.ps); sp.part_idx = ws_at<int>(h, L.pi);
+}
+
+static int knn_scan_hi_smallq(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, hipStream_t st) {
+    SmallQHiParams sp;
+    knn_fill_smallq_hi(h, p, L, sp);
     const bool l16 = p.ksel_sq <= 16;
     const auto fn = p.sq_ksplit ? (l16 ? k_knn_hi_smallq_ksplit<16> : k_knn_hi_smallq_ksplit<32>) : (l16 ? k_knn_hi_smallq<16> : k_knn_hi_smallq<32>);
     return knn_launch_smallq(h, fn, sp, p.n_splits, p.sq_lds, st);
+}
+
+// the range search of a small batch (RADAD_RANGE_STREAM): one launch of k_range_hi_smallq from the floors in L.thr into the candidate
+// buffers (L.pi, L.cnt: zeroed by knn_prepare_queries).  row_bias: the per-call bias array (one set for the batch), or NULL
+static_assert(KNN_RANGE_STREAM_CAP == RG_MAX_CAP, "the stream's candidate buffers are what k_range_refine's sort is sized for");
+static int knn_scan_range_smallq(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, hipStream_t st, const float* row_bias) {
+    RangeSmallQParams sp;
+    knn_fill_smallq_hi(h, p, L, sp);
+    if (row_bias) sp.rbias = row_bias;
+    sp.thr = ws_at<const float>(h, L.thr); sp.cnt = ws_at<int>(h, L.cnt); sp.idx = ws_at<int>(h, L.pi); sp.cap = p.emit_cap;
+    return knn_launch_smallq(h, k_range_hi_smallq, sp, p.n_splits, p.sq_lds, st);
 }
 
 static int knn_scan_f32_smallq(radad_knn_t h, const ScanPlan& p, const SearchLayout& L, const float* q_use, hipStream_t st) {
@@ -4398,6 +4523,9 @@ static int knn_search_excl_scan_pq_locked(radad_knn_t h, const void* q_in, int q
 // Route, facts, plan and the one scan launch are knn_range_plan's (knn_plan.h).  Tile route: the PLAIN search's preparation, RSC and
 // bias (as knn_search_excl_scan_pq_locked), k_range_floor into the search's floor array, one scan launch from those floors (early
 // abandon included), k_range_refine; the queries whose buffer overflowed go, driven from the device, to the exact range kernel.
+// Stream route (RADAD_KNN_OPT_RANGE_SMALLQ, <= 16 queries): the small-batch search's preparation and eps, the same floors, ONE launch of
+// k_range_hi_smallq into the same buffers, and everything behind the scan as on the tile route -- but for the re-rank's re-score,
+// which takes its sums in the exact kernel's order (k_range_refine<.., true>): the keys are the exact route's bit for bit.
 // Exact route: that kernel for every query.  Like the siblings above: KnnTuning is read (hi_skip) and never written, no report is
 // posted, no turn is taken.
 // rule: NULL (radad_knn_range_search), or what the queries exclude (radad_knn_range_search_excl / _excl_pq; knn_range_excl_plan):
@@ -4424,17 +4552,17 @@ static int knn_range_search_locked(const char* fn, radad_knn_t h, const void* q_
         }
     };
     make_plan();
-    bool tile = X.route == RADAD_RANGE_TILE;
-    if (tile && !knn_ensure_hi(h, st, true)) {                     // (a plane that cannot be allocated switches itself off: exact route)
-        tile = false;
+    bool tile = X.route == RADAD_RANGE_TILE, stream = X.route == RADAD_RANGE_STREAM;
+    if ((tile || stream) && !knn_ensure_hi(h, st, true)) {         // (a plane that cannot be allocated switches itself off: exact route)
+        tile = stream = false;
         make_plan();
-        RADAD_REQUIRE(X.route == RADAD_RANGE_EXACT, "%s: a store without a plane planned the tile route", fn);
+        RADAD_REQUIRE(X.route == RADAD_RANGE_EXACT, "%s: a store without a plane planned the tile or the stream route", fn);
     }
-    if (!tile && !knn_ensure_hi(h, st, false)) { radad_set_error("store statistics could not be computed"); return RADAD_EHIP; }
+    if (!tile && !stream && !knn_ensure_hi(h, st, false)) { radad_set_error("store statistics could not be computed"); return RADAD_EHIP; }
     ScanPlan p = X.plan;
     p.mu = (p.hi_q && !h->f16) ? h->cmu : nullptr;                 // the plain search's instantiation (knn_plan_scan) ...
     if (!batch) p.biased = p.hi_q && (p.l2 || p.mu);               // ... (one set for the batch: the biased one whatever the plane, the plan's)
-    RADAD_REQUIRE(!tile || p.emit_cap <= RG_MAX_CAP, "%s: %d-entry candidate buffers exceed the re-rank's %d", fn, p.emit_cap, RG_MAX_CAP);
+    RADAD_REQUIRE(!(tile || stream) || p.emit_cap <= RG_MAX_CAP, "%s: %d-entry candidate buffers exceed the re-rank's %d", fn, p.emit_cap, RG_MAX_CAP);
     const SearchLayout L = knn_search_layout(X.facts, p, q_dtype);
     if (L.bytes > h->ws_bytes) {
         RADAD_HIP_CHECK(hipDeviceSynchronize());
@@ -4442,7 +4570,7 @@ static int knn_range_search_locked(const char* fn, radad_knn_t h, const void* q_
         if (rc) return rc;
     }
     // the exact pass's partial lists, k = m; one set for the batch: the bitmap and the bias array behind them
-    const RangeExclLayout E = knn_range_excl_layout(X.facts, nq, m, tile ? RADAD_RANGE_TILE : RADAD_RANGE_EXACT);
+    const RangeExclLayout E = knn_range_excl_layout(X.facts, nq, m, X.route);
     const RangeLayout B = E.lists;
     rc = knn_excl_reserve(h, batch ? E.bytes : B.bytes);
     if (rc) return rc;
@@ -4465,7 +4593,7 @@ static int knn_range_search_locked(const char* fn, radad_knn_t h, const void* q_
     int* flag_count = ws_at<int>(h, L.fcount);
     int* flag_sel = ws_at<int>(h, L.fsel);
 
-    if (tile) {
+    if (tile || stream) {
         // one set for the batch: the per-call bias, NaN for the rows the bitmap does not admit (no compare of the scan passes a NaN)
         float* bias = nullptr;
         if (batch) {
@@ -4479,7 +4607,11 @@ static int knn_range_search_locked(const char* fn, radad_knn_t h, const void* q_
                            p.l2 ? -radius : radius, floors, nq);
         RADAD_HIP_CHECK(hipGetLastError());
         h->prof.next_search();
-        rc = knn_scan_hi_tile(h, p, L, st, bias, nullptr, floors);
+        if (tile) rc = knn_scan_hi_tile(h, p, L, st, bias, nullptr, floors);
+        else {                                                     // <= 16 queries: the plane streamed once, one launch
+            rc = knn_scan_range_smallq(h, p, L, st, bias);
+            h->last_splits = p.n_splits; h->last_scan_launches = h->last_scan_phases = 1; h->last_ab_tasks = 0;
+        }
         if (rc) return rc;
         RADAD_HIP_CHECK(hipGetLastError());
         RADAD_REQUIRE(h->last_scan_launches == X.launches, "%s: %d scan launches, planned %d", fn, h->last_scan_launches, X.launches);
@@ -4491,11 +4623,15 @@ static int knn_range_search_locked(const char* fn, radad_knn_t h, const void* q_
         g.out_count = out_count_dev; g.out_dist = out_dist_dev; g.out_idx = out_idx_dev; g.out_key = out_key_dev;
         if (pq) { g.tags = rule->tags; g.q_tags = rule->q_tags; g.q_cnt = rule->q_cnt; g.n_tags = rule->m(); }
         const size_t glds = pq ? range_refine_pq_lds_bytes() : range_refine_lds_bytes();
-        const void* refine = pq ? reinterpret_cast<const void*>(k_range_refine<true>) : reinterpret_cast<const void*>(k_range_refine<false>);
+        // (the stream route: the instantiations whose float64 keys are the exact route's bit for bit -- a batch of <= 16 queries gets the
+        // same keys with the option on and off)
+        void (*const refine_pq)(RangeRefinePqParams) = stream ? k_range_refine<true, true> : k_range_refine<true, false>;
+        void (*const refine_plain)(RangeRefineParams) = stream ? k_range_refine<false, true> : k_range_refine<false, false>;
+        const void* refine = pq ? reinterpret_cast<const void*>(refine_pq) : reinterpret_cast<const void*>(refine_plain);
         RADAD_HIP_CHECK(hipFuncSetAttribute(refine, hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds));
         h->prof.begin(st);                                         // (the call's second profile entry: its re-rank)
-        if (pq) hipLaunchKernelGGL(k_range_refine<true>, dim3((unsigned)nq), dim3(RF_THREADS), glds, st, g);
-        else hipLaunchKernelGGL(k_range_refine<false>, dim3((unsigned)nq), dim3(RF_THREADS), glds, st, static_cast<const RangeRefineParams&>(g));
+        if (pq) hipLaunchKernelGGL(refine_pq, dim3((unsigned)nq), dim3(RF_THREADS), glds, st, g);
+        else hipLaunchKernelGGL(refine_plain, dim3((unsigned)nq), dim3(RF_THREADS), glds, st, static_cast<const RangeRefineParams&>(g));
         h->prof.end(st);
     } else {
         RADAD_HIP_CHECK(hipMemsetAsync(out_count_dev, 0, (size_t)nq * sizeof(int32_t), st));
@@ -4503,7 +4639,7 @@ static int knn_range_search_locked(const char* fn, radad_knn_t h, const void* q_
     }
     RADAD_HIP_CHECK(hipGetLastError());
 
-    // ---- the listed queries (tile route: k_range_refine zeroed their counts): the float64 exact range kernel, sized and driven by the
+    // ---- the listed queries (tile and stream routes: k_range_refine zeroed their counts): the float64 exact range kernel, sized and driven by the
     // device-side count; no report
     {
         ExactParams x;
@@ -4531,7 +4667,7 @@ static int knn_range_search_locked(const char* fn, radad_knn_t h, const void* q_
         RADAD_HIP_CHECK(hipGetLastError());
     }
     RADAD_HIP_CHECK(hipMemcpyAsync(h->host_count + 18, flag_count, sizeof(int), hipMemcpyDeviceToHost, st));
-    h->last_rg_nq = nq; h->last_rg_route = tile ? RADAD_RANGE_TILE : RADAD_RANGE_EXACT;
+    h->last_rg_nq = nq; h->last_rg_route = tile ? RADAD_RANGE_TILE : stream ? RADAD_RANGE_STREAM : RADAD_RANGE_EXACT;
     return RADAD_OK;
 }
 

@@ -55,6 +55,7 @@ struct StoreFacts {
     int hi_off = 0;              // 1: no f16 plane (switched off, or its allocation failed)
     int opt_centre = -1, opt_smallq_hi = 1, opt_wide_min_q = SQ_NQ + 1, opt_dense = 1;     // radad_knn_set_option
     int cap_boost = 1;           // KnnTuning::cap_boost
+    int opt_range_smallq = 0;    // RADAD_KNN_OPT_RANGE_SMALLQ: range searches of <= 16 queries may stream the plane (knn_range_plan)
 };
 
 // ---- the exact kernel's grouping --------------------------------------------------------------------------------------------------
@@ -222,6 +223,27 @@ static bool knn_smallq_hi_eligible(const StoreFacts& s, int64_t nq, int k, int m
            knn_sq_lds_hi(nq, s.dim) <= SQ_LDS_BUDGET;
 }
 
+// The launch geometry of a streaming kernel with one wave per row slice (not the K-split form): rows per wave, workgroups of 4 waves.
+// a wave streams >= 128 KB (128 rows at dim 512) so that its lists' hand-over stays small beside the stream, but no more
+// rows than leave 8 waves for every CU; the lists of a query (one per workgroup, `list_len` entries each; 0: the kernel keeps no
+// lists) should fit the re-rank's staged form
+// one full round of resident waves: 1024 SIMDs x `waves_per_simd`, the waves per SIMD the kernel's registers allow.  (Measured: no
+// difference against 2048 waves on the 1 M x 512 store -- 0.2075 vs 0.208 ms, 4.93 TB/s either way: the stream is not limited by
+// the number of waves in flight.)
+struct SqStream {
+    int rows_per_wave = 0, n_splits = 0;
+};
+static SqStream knn_sq_stream_geometry(int64_t ntotal, size_t row_bytes, int waves_per_simd, int list_len) {
+    const int64_t waves_wanted = 1024 * waves_per_simd;
+    const int64_t rows_min = std::max<int64_t>(16, std::min<int64_t>(128, ceil_div64(ceil_div64(128 * 1024, (int64_t)row_bytes), 16) * 16));
+    int64_t rpw = std::max<int64_t>(ceil_div64(ceil_div64(ntotal, waves_wanted), 16) * 16, rows_min);
+    while (rpw < 128 && ceil_div64(ceil_div64(ntotal, rpw), 4) * list_len > RF_STAGE_MAX_SMALLQ) rpw += 16;
+    SqStream g;
+    g.rows_per_wave = (int)rpw;
+    g.n_splits = (int)ceil_div64(ceil_div64(ntotal, rpw), 4);
+    return g;
+}
+
 // The rest of the plan, once it is settled which certified f16 scan (if any) the search takes: `use_hi` the tile scan, `smallq_hi`
 // the small-batch stream of the plane.  (ScanPlan::mu / ::biased depend on the plane's centring: the caller fills them in.)
 static ScanPlan knn_finish_plan(const StoreFacts& s, int64_t nq, int k, int margin, const TileEligibility& t, bool use_hi, bool smallq_hi) {
@@ -255,18 +277,11 @@ static ScanPlan knn_finish_plan(const StoreFacts& s, int64_t nq, int k, int marg
         p.n_splits = (int)ceil_div64(s.ntotal, rpg);
         p.n_qtiles = 1;
     } else if (smallq || smallq_hi) {
-        // a wave streams >= 128 KB (128 rows at dim 512) so that its lists' hand-over stays small beside the stream, but no more
-        // rows than leave 8 waves for every CU; the lists of a query (one per workgroup) should fit the re-rank's staged form
-        // one full round of resident waves: 1024 SIMDs x the waves per SIMD the kernel's registers allow (k_knn_hi_smallq<16>: 155
-        // VGPRs = 3; the 32-entry and fp32 variants: 2).  (Measured: no difference against 2048 waves on the 1 M x 512 store -- 0.2075
-        // vs 0.208 ms, 4.93 TB/s either way: the stream is not limited by the number of waves in flight.)
-        const int64_t waves_wanted = 1024 * ((smallq_hi && p.ksel_sq <= 16) ? 3 : 2);
-        const size_t rb = smallq_hi ? (size_t)s.dim * 2 : (size_t)s.dim * 4;
-        const int64_t rows_min = std::max<int64_t>(16, std::min<int64_t>(128, ceil_div64(ceil_div64(128 * 1024, (int64_t)rb), 16) * 16));
-        int64_t rpw = std::max<int64_t>(ceil_div64(ceil_div64(s.ntotal, waves_wanted), 16) * 16, rows_min);
-        while (rpw < 128 && ceil_div64(ceil_div64(s.ntotal, rpw), 4) * p.ksel_sq > RF_STAGE_MAX_SMALLQ) rpw += 16;
-        p.sq_rows_per_wave = (int)rpw;
-        p.n_splits = (int)ceil_div64(ceil_div64(s.ntotal, rpw), 4);              // workgroups of 4 waves = lists per query
+        // (waves per SIMD the kernel's registers allow: k_knn_hi_smallq<16>: 155 VGPRs = 3; the 32-entry and fp32 variants: 2)
+        const SqStream g = knn_sq_stream_geometry(s.ntotal, smallq_hi ? (size_t)s.dim * 2 : (size_t)s.dim * 4,
+                                                  (smallq_hi && p.ksel_sq <= 16) ? 3 : 2, p.ksel_sq);
+        p.sq_rows_per_wave = g.rows_per_wave;
+        p.n_splits = g.n_splits;                                                 // workgroups of 4 waves = lists per query
         p.n_qtiles = 1;
     }
     p.sq_lds = smallq_hi ? sq_lds_hi : sq_lds_f32;
@@ -529,22 +544,48 @@ static ExclScanPqPlan knn_excl_scan_pq_plan(const StoreFacts& s, int64_t nq, int
 // Facts: the caller's with the widened candidate buffers (cap_boost 4: 4096 entries per query, whatever the handle's tuning state).
 // The plan is the plain search's at k = 1 (mu / biased: the caller's, as for any plan); on the exact route it is the plan the queries
 // are prepared and the workspace laid out with.
+//
+// Batches of <= 16 queries (RADAD_RANGE_STREAM; only with StoreFacts::opt_range_smallq, off by default): the one-query question "does
+// a copy of THIS clip sit in the store" streams the f16 plane once (k_range_hi_smallq) instead of the fp32 rows in float64.  Chosen
+// exactly when the option is set, the tuning state is not on its fp32 fallback, the tile route is not taken and the plain search of
+// this batch at k = 1 could stream the plane (knn_smallq_hi_eligible: <= 16 queries, dim % 64 == 0, >= 16 384 rows, the plane on,
+// opt_smallq_hi, the query block within SQ_LDS_BUDGET).  A batch of <= 16 queries too wide for the LDS takes the tile route as before.
+// The plan: the plain small-batch search's (kind RADAD_SCAN_HI_SMALLQ, f16 queries with a scale) with ONE candidate buffer of
+// KNN_RANGE_STREAM_CAP entries per query in place of the per-workgroup lists, one launch, and the one-wave-per-slice geometry whatever
+// the store: the K-split form (small stores of wide rows) has no range kernel, such a store streams with one wave per slice here.
+constexpr int KNN_RANGE_STREAM_CAP = 4096;       // = RG_MAX_CAP, what k_range_refine's sort is sized for (knn.hip asserts it)
+static size_t knn_sq_lds_range(int64_t nq, int dim) { return 2 * (size_t)nq * (dim + 8); }     // the f16 query block alone: no slots, no lists
 struct RangePlan {
     int route = RADAD_RANGE_EXACT;
     StoreFacts facts;
     ScanPlan plan;
-    int launches = 0;            // tile route: launches of the scan (1); exact route: 0
+    int launches = 0;            // tile and stream routes: launches of the scan (1); exact route: 0
 };
 static RangePlan knn_range_plan(const StoreFacts& s, int64_t nq, int max_per_query, int fp32_searches_left) {
     (void)max_per_query;
     RangePlan x;
     const bool tile = knn_excl_scan_route(s, nq, 1, fp32_searches_left) == RADAD_EXCL_SCAN_TILE;
-    x.route = tile ? RADAD_RANGE_TILE : RADAD_RANGE_EXACT;
+    const bool stream = !tile && s.opt_range_smallq && fp32_searches_left == 0 && knn_smallq_hi_eligible(s, nq, 1, KNN_MARGIN, false, false);
+    x.route = tile ? RADAD_RANGE_TILE : stream ? RADAD_RANGE_STREAM : RADAD_RANGE_EXACT;
     x.facts = s;
     x.facts.cap_boost = KNN_EXCL_SCAN_PQ_CAP_BOOST;
     const TileEligibility t = knn_tile_eligibility(x.facts, nq, 1, KNN_MARGIN);
-    x.plan = knn_finish_plan(x.facts, nq, 1, KNN_MARGIN, t, tile, false);
+    x.plan = knn_finish_plan(x.facts, nq, 1, KNN_MARGIN, t, tile, stream);
     if (tile) x.launches = (int)knn_hi_phases(s.ntotal, nq, (int64_t)8 * x.plan.s_splits * KW_M, true).size() - 1;
+    if (stream) {
+        ScanPlan& p = x.plan;                      // (kind, hi_q, block_threads, n_qtiles: the small-batch search's, from knn_finish_plan)
+        // (k_range_hi_smallq keeps no lists: 120 VGPRs, 4 waves per SIMD by registers.  The geometry asks for the plain small-batch
+        // kernel's 3 all the same, so that the two streams are cut alike: the stream is not limited by the waves in flight, above)
+        const SqStream g = knn_sq_stream_geometry(s.ntotal, (size_t)s.dim * 2, 3, 0);
+        p.sq_ksplit = false;
+        p.sq_rows_per_wave = g.rows_per_wave;
+        p.n_splits = g.n_splits;
+        p.n_qtiles = p.reported_qtiles = 1;
+        p.sq_lds = knn_sq_lds_range(nq, s.dim);
+        p.emit_cap = p.plen = KNN_RANGE_STREAM_CAP;
+        p.n_parts = 1;
+        x.launches = 1;
+    }
     return x;
 }
 // The exact range pass keeps lists of max_per_query entries, not of the plan's k = 1: its partial lists live in the handle's exclusion
@@ -566,7 +607,7 @@ static RangeLayout knn_range_layout(const StoreFacts& s, int64_t nq, int max_per
 
 // ---- certified range search among the rows a query does not exclude (radad_knn_range_search_excl / _excl_pq) ----------------------
 // Route, facts (4096-entry buffers) and the ONE scan launch are knn_range_plan's, whatever the mode and whatever is excluded.
-//   KNN_RANGE_EXCL_BATCH      one set for the batch: the pre-pass (k_excl_scan_bias, 1 launch on the tile route) writes a per-call bias
+//   KNN_RANGE_EXCL_BATCH      one set for the batch: the pre-pass (k_excl_scan_bias, 1 launch on the tile and stream routes) writes a per-call bias
 //                             that is NaN for the excluded rows, so the plan carries the BIASED instantiation whatever the plane, as
 //                             radad_knn_search_excl_scan's does (RSC 2 / 3; mu is the caller's: without a centre the query constant is 0);
 //   KNN_RANGE_EXCL_PER_QUERY  <= 64 tags per query: the plain range search's own plan, member for member -- the scan emits excluded rows
@@ -580,8 +621,8 @@ struct RangeExclPlan {
     int route = RADAD_RANGE_EXACT;
     StoreFacts facts;
     ScanPlan plan;
-    int launches = 0;            // tile route: launches of the scan (1); exact route: 0
-    int prepass_launches = 0;    // batch mode, tile route: the bias pre-pass (1)
+    int launches = 0;            // tile and stream routes: launches of the scan (1); exact route: 0
+    int prepass_launches = 0;    // batch mode, tile and stream routes: the bias pre-pass (1)
     int scrub_launches = 0;      // always 0
 };
 static RangeExclPlan knn_range_excl_plan(const StoreFacts& s, int64_t nq, int max_per_query, int mode, int m, int fp32_searches_left) {
@@ -591,12 +632,12 @@ static RangeExclPlan knn_range_excl_plan(const StoreFacts& s, int64_t nq, int ma
     x.mode = mode; x.route = r.route; x.facts = r.facts; x.plan = r.plan; x.launches = r.launches;
     if (mode == KNN_RANGE_EXCL_BATCH) {
         x.plan.biased = x.plan.hi_q;
-        x.prepass_launches = r.route == RADAD_RANGE_TILE ? 1 : 0;
+        x.prepass_launches = r.route != RADAD_RANGE_EXACT ? 1 : 0;
     }
     return x;
 }
 // The exclusion workspace of the batch mode: the exact pass's partial lists (RangeLayout, unchanged) | the admission bitmap | on the
-// tile route the per-call bias array (ExclScanLayout's two arrays, moved behind the lists).
+// tile and stream routes the per-call bias array (ExclScanLayout's two arrays, moved behind the lists).
 struct RangeExclLayout {
     RangeLayout lists;
     size_t admit = 0, bias = 0, bytes = 0;
@@ -605,7 +646,7 @@ struct RangeExclLayout {
 static RangeExclLayout knn_range_excl_layout(const StoreFacts& s, int64_t nq, int max_per_query, int route) {
     RangeExclLayout L;
     L.lists = knn_range_layout(s, nq, max_per_query);
-    const ExclScanLayout e = knn_excl_scan_layout(s, route == RADAD_RANGE_TILE ? RADAD_EXCL_SCAN_TILE : RADAD_EXCL_SCAN_EXACT);
+    const ExclScanLayout e = knn_excl_scan_layout(s, route != RADAD_RANGE_EXACT ? RADAD_EXCL_SCAN_TILE : RADAD_EXCL_SCAN_EXACT);
     L.n_words = e.n_words;
     L.admit = L.lists.bytes + e.admit;
     L.bias = L.lists.bytes + e.bias;

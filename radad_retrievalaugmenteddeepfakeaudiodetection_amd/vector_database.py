@@ -74,14 +74,15 @@ def write_faiss_flat(path: str, rows: np.ndarray, metric: str):
 
 def knn_options_from_config(config):
     """the optional scan knobs, read the way the reference reads its own optional ones (getattr with a default,
-    vector_database.py:43,67,80): knn_hi_plane, knn_centre, knn_smallq_hi, knn_wide_min_q, knn_dense, knn_abandon; absent / None = the library's default.
+    vector_database.py:43,67,80): knn_hi_plane, knn_centre, knn_smallq_hi, knn_wide_min_q, knn_dense, knn_abandon, knn_range_smallq; absent / None = the library's default.
     knn_live_floor is still recognised, but only None / 0 (the default): the one-launch scan form it selected was removed"""
     if getattr(config, "knn_live_floor", None) not in (None, 0):
         raise ValueError("knn_live_floor: the one-launch scan form was measured slower and removed (DESIGN §4.1); "
                          "leave it None / 0 for the default, one launch per phase")
     opts = dict(hi_plane=getattr(config, "knn_hi_plane", None), centre=getattr(config, "knn_centre", None),
                 smallq_hi=getattr(config, "knn_smallq_hi", None), wide_min_q=getattr(config, "knn_wide_min_q", None),
-                dense=getattr(config, "knn_dense", None), abandon=getattr(config, "knn_abandon", None))
+                dense=getattr(config, "knn_dense", None), abandon=getattr(config, "knn_abandon", None),
+                range_smallq=getattr(config, "knn_range_smallq", None))
     return {k: v for k, v in opts.items() if v is not None}
 
 
@@ -165,9 +166,10 @@ class HipFlatIndex:
     is_trained = True   # flat indexes need no training (vector_database.py:124)
 
     def __init__(self, d: int, metric: int, device: int = 0, id_base: int = 0, store_f16: bool = False, hi_plane=None, centre=None,
-                 smallq_hi=None, wide_min_q=None, dense=None, abandon=None):
-        """hi_plane / centre / smallq_hi / wide_min_q / dense / abandon: kernel choices of the handle (radad_knn_set_option; None = the library's
-        default).  They change speed, never results: A/B measurements and the parity tests select kernels through them."""
+                 smallq_hi=None, wide_min_q=None, dense=None, abandon=None, range_smallq=None):
+        """hi_plane / centre / smallq_hi / wide_min_q / dense / abandon / range_smallq: kernel choices of the handle (radad_knn_set_option;
+        None = the library's default).  They change speed, never results: A/B measurements and the parity tests select kernels through
+        them.  range_smallq (default off): range searches of <= 16 queries stream the f16 plane instead of the float64 exact kernel."""
         self._lib = _lib.load()
         self.d = int(d)
         self.metric = int(metric)
@@ -178,9 +180,11 @@ class HipFlatIndex:
         _lib.check(self._lib.radad_knn_create_ex(self.d, self.metric, _lib.STORE_F16 if self.store_f16 else _lib.STORE_F32,
                                                  self.device, self.id_base, C.byref(h)), "radad_knn_create")
         self._h = h
-        self.options = dict(hi_plane=hi_plane, centre=centre, smallq_hi=smallq_hi, wide_min_q=wide_min_q, dense=dense, abandon=abandon)
+        self.options = dict(hi_plane=hi_plane, centre=centre, smallq_hi=smallq_hi, wide_min_q=wide_min_q, dense=dense, abandon=abandon,
+                            range_smallq=range_smallq)
         for opt, val in ((_lib.KNN_OPT_HI_PLANE, hi_plane), (_lib.KNN_OPT_CENTRE, centre), (_lib.KNN_OPT_SMALLQ_HI, smallq_hi),
-                         (_lib.KNN_OPT_WIDE_MIN_Q, wide_min_q), (_lib.KNN_OPT_DENSE, dense), (_lib.KNN_OPT_ABANDON, abandon)):
+                         (_lib.KNN_OPT_WIDE_MIN_Q, wide_min_q), (_lib.KNN_OPT_DENSE, dense), (_lib.KNN_OPT_ABANDON, abandon),
+                         (_lib.KNN_OPT_RANGE_SMALLQ, range_smallq)):
             if val is not None:
                 _lib.check(self._lib.radad_knn_set_option(self._h, opt, int(val)), "radad_knn_set_option")
 
@@ -423,11 +427,13 @@ class HipFlatIndex:
                                                                                       max_per_query))
 
     def last_range(self):
-        """{"queries", "route", "exact"} of the most recent range search: its batch size, "tile" or "exact", and how many of its queries
-        the exact float64 kernel answered (radad_knn_last_range; synchronises with that search)"""
+        """{"queries", "route", "exact"} of the most recent range search: its batch size, "tile", "stream" (<= 16 queries with
+        range_smallq) or "exact", and how many of its queries the exact float64 kernel answered (radad_knn_last_range; synchronises
+        with that search)"""
         nq, route, ex = C.c_int64(), C.c_int(), C.c_int()
         _lib.check(self._lib.radad_knn_last_range(self._h, C.byref(nq), C.byref(route), C.byref(ex)), "radad_knn_last_range")
-        return {"queries": nq.value, "route": "tile" if route.value == _lib.RANGE_TILE else "exact", "exact": ex.value}
+        name = {_lib.RANGE_TILE: "tile", _lib.RANGE_STREAM: "stream"}.get(route.value, "exact")
+        return {"queries": nq.value, "route": name, "exact": ex.value}
 
     def search_excluding_begin(self, q, k: int, row_tags, exclude_tags, k_fetch=None):
         """first half of search_excluding over a ROW SHARD (radad_knn_search_excl_begin; sharded.ShardedSearch.search_excluding): the
