@@ -100,6 +100,11 @@ int radad_knn_create_ex(int dim, int metric, int store_dtype, int device, int64_
  *                            of the bulk of the rows; where it cannot, a scalar gate keeps the test from running) / it never does
  *   RADAD_KNN_OPT_RANGE_SMALLQ  0 (default) / 1: the three range calls answer a batch of <= 16 queries on the float64 exact kernel / by
  *                            streaming the f16 plane once (RADAD_RANGE_STREAM, below); no environment override
+ *   RADAD_KNN_OPT_ABANDON_DEAL  0 (default) / 1: every launch of the tile scan walks static chunks / an abandoning launch of <= 8 query
+ *                            tiles whose resident workgroups would each draw at least two granules deals its row tiles to the
+ *                            workgroups by ticket, so that a skip pattern that is not spread evenly over the store does not leave the
+ *                            launch waiting for its slowest chunk.  Off by default: on the benchmark it measured no gain that stands
+ *                            clear of the run-to-run spread (profiles/abandon_deal_ab.txt); no environment override
  * The environment variables RADAD_KNN_HI, RADAD_KNN_CENTRE, RADAD_KNN_SMALLQ_HI, RADAD_WIDE_MIN_Q override the DEFAULTS of handles
  * created while they are set (announced once per process on stderr); the product path never needs them. */
 #define RADAD_KNN_OPT_HI_PLANE 0
@@ -109,6 +114,7 @@ int radad_knn_create_ex(int dim, int metric, int store_dtype, int device, int64_
 #define RADAD_KNN_OPT_DENSE 4
 #define RADAD_KNN_OPT_ABANDON 5
 #define RADAD_KNN_OPT_RANGE_SMALLQ 6
+#define RADAD_KNN_OPT_ABANDON_DEAL 7
 int radad_knn_set_option(radad_knn_t h, int option, int value);
 int radad_knn_destroy(radad_knn_t h);
 int radad_knn_dim(radad_knn_t h, int* dim);
@@ -220,6 +226,9 @@ int radad_knn_last_emitted(radad_knn_t h, int* counts_host, float* floors_host, 
  * covered, how many ran the test (`checked`: the gate let them) and how many were left after it (`skipped`).  All three are 0 when
  * no launch of the last search took the abandoning scan. */
 int radad_knn_last_abandon(radad_knn_t h, int64_t* checked, int64_t* skipped, int64_t* tasks);
+/* ... and how its abandoning launches got their row tiles (no synchronisation: the host's plan): how many of them were dealt by ticket
+ * (RADAD_KNN_OPT_ABANDON_DEAL), and of the last dealt one the workgroups launched and the row tiles per granule.  All 0 when none was. */
+int radad_knn_last_abandon_deal(radad_knn_t h, int* launches, int* workgroups, int* granule);
 /* the f16 plane the certified scans read, once a search has built it: built (0/1); centred = the common component (column mean)
  * of the rows is subtracted before rounding (stores of embeddings that share most of their mean); one_scale = one power-of-two
  * scale for all rows (rows of one magnitude: the scan applies no per-score arithmetic) */

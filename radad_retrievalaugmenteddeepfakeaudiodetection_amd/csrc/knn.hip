@@ -2951,6 +2951,12 @@ struct radad_knn_s {
     bool ab_search_ready = false;// this search's per-query terms are written (knn_prepare_queries decides, once; the scan reads it)
     size_t last_o_ab = 0;        // the last search's abandon counters in the workspace, and the tile tasks of its abandoning launches
     int64_t last_ab_tasks = -1;  // (-1: no search yet)
+    // the abandoning scan's tiles dealt by ticket (knn_abandon_deal, knn_plan.h): KNN_DEAL_SETS sets of counters, one per launch of a
+    // search, all zeroed by the search's query preparation (allocated with the per-query terms: knn_abandon_terms_ready)
+    int opt_abandon_deal = 0;    // RADAD_KNN_OPT_ABANDON_DEAL (off by default: profiles/abandon_deal_ab.txt)
+    int n_cus = 0;               // compute units of the device (radad_knn_create)
+    int* deal_cnt = nullptr;     // [KNN_DEAL_COUNTERS]
+    int last_deal_launches = 0, last_deal_workgroups = 0, last_deal_granule = 0;      // radad_knn_last_abandon_deal
     // queries the certificate rejected in the most recent search: counted on the device, copied to pinned host memory
     // behind the search (no synchronisation inside search); feeds the adaptive tuning and radad_knn_last_recheck
     int* host_count = nullptr;   // pinned [2][8]: rejected queries, sum of candidates, rejections by reason x 4, [6] the report's stamp, [7] its batch size
@@ -3284,6 +3290,7 @@ int radad_knn_create_ex(int dim, int metric, int store_dtype, int device, int64_
             return RADAD_EHIP;
         }
         memset(h->host_count, 0, 24 * sizeof(int));
+        { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) h->n_cus = cus; }
         if (hipHostGetDevicePointer(reinterpret_cast<void**>(&h->host_count_dev), h->host_count, 0) != hipSuccess) {
             radad_set_error("radad_knn_create: pinned counter is not device-visible");
             radad_knn_destroy(h);
@@ -3314,6 +3321,7 @@ int radad_knn_destroy(radad_knn_t h) {
         if (h->rs_count) (void)hipFree(h->rs_count);
         if (h->tile_ry) (void)hipFree(h->tile_ry);
         if (h->ab_ws) (void)hipFree(h->ab_ws);
+        if (h->deal_cnt) (void)hipFree(h->deal_cnt);
         if (h->host_count) (void)hipHostFree(h->host_count);
         if (h->ev_done) (void)hipEventDestroy(h->ev_done);
         if (h->ev_begun) (void)hipEventDestroy(h->ev_begun);
@@ -3356,6 +3364,10 @@ int radad_knn_set_option(radad_knn_t h, int option, int value) {
         case RADAD_KNN_OPT_ABANDON:
             RADAD_REQUIRE(value == 0 || value == 1, "radad_knn_set_option: ABANDON takes 0 or 1");
             h->opt_abandon = value;
+            return RADAD_OK;
+        case RADAD_KNN_OPT_ABANDON_DEAL:
+            RADAD_REQUIRE(value == 0 || value == 1, "radad_knn_set_option: ABANDON_DEAL takes 0 or 1");
+            h->opt_abandon_deal = value;
             return RADAD_OK;
         case RADAD_KNN_OPT_RANGE_SMALLQ:
             RADAD_REQUIRE(value == 0 || value == 1, "radad_knn_set_option: RANGE_SMALLQ takes 0 or 1");
@@ -3578,6 +3590,8 @@ static bool knn_abandon_terms_ready(radad_knn_t h, int64_t nq) {
         if (hipMalloc(&h->ab_ws, A.bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
         h->ab_ws_bytes = A.bytes;
     }
+    // (the ticket counters of dealt launches: without them the launches stay static)
+    if (h->opt_abandon_deal && !h->deal_cnt && hipMalloc(&h->deal_cnt, KNN_DEAL_COUNTERS * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); h->deal_cnt = nullptr; }
     return true;
 }
 
@@ -3615,6 +3629,7 @@ static const float* knn_prepare_queries(radad_knn_t h, const ScanPlan& p, const 
             hp.suf_from = h->ab_from;
             hp.suf_out = reinterpret_cast<float*>(static_cast<char*>(h->ab_ws) + A.rq);
             hp.ab_slack_out = reinterpret_cast<float*>(static_cast<char*>(h->ab_ws) + A.slack);
+            hp.zero_deal = h->opt_abandon_deal ? h->deal_cnt : nullptr;         // every launch's ticket counters, once per search, in a kernel the search runs anyway
         }
         launch_hi_rows(hp, st);
     }
@@ -3738,6 +3753,7 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
     af.terms_current = h->ab_search_ready;
     const AbandonLayout AL = knn_abandon_layout(nq);
     h->last_ab_tasks = 0; h->last_o_ab = L.fcount + KNN_AB_COUNTER0 * sizeof(int);
+    h->last_deal_launches = h->last_deal_workgroups = h->last_deal_granule = 0;
     RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(sample), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // sample pre-pass: the (k + margin)-th best score over the first rows of the store is a score at least k rows reach, so the
@@ -3805,6 +3821,18 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
             launch_lds = knn_hi_lds_bytes(true);
             RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(launch_fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)launch_lds));
             h->last_ab_tasks += (int64_t)gq * ceil_div64(rp.n, KW_M);
+            // dealt by ticket where that can help (knn_abandon_deal); each launch of the search has its own counter set
+            DealFacts df;
+            df.opt_deal = h->deal_cnt ? h->opt_abandon_deal : 0; df.ab_ck = ab_ck; df.launch = (int)i; df.row_tiles = ceil_div64(rp.n, KW_M);
+            df.n_qtiles = gq; df.n_splits = gs; df.cus = h->n_cus;
+            const DealPlan dp = knn_abandon_deal(df);
+            if (dp.dealt) {
+                rp.deal_g = dp.granule; rp.deal_tiles = (int)df.row_tiles;
+                rp.deal_cnt = h->deal_cnt + knn_deal_counter((int)i, 0, 0);
+                launch_fn = rsc == 0 ? k_knn_hi_abandon_deal<0> : k_knn_hi_abandon_deal<3>;
+                RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(launch_fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)launch_lds));
+                ++h->last_deal_launches; h->last_deal_workgroups = dp.workgroups; h->last_deal_granule = dp.granule;
+            }
         }
         h->prof.begin(st);      // the event pair brackets a scan launch only (the kernel the roofline is quoted on; the phases of one
                                 // search are two entries)
@@ -5098,6 +5126,15 @@ int radad_knn_last_abandon(radad_knn_t h, int64_t* checked, int64_t* skipped, in
     int c2[2] = {0, 0};
     RADAD_HIP_CHECK(hipMemcpy(c2, (const char*)h->ws + h->last_o_ab, sizeof(c2), hipMemcpyDeviceToHost));
     *checked = c2[0]; *skipped = c2[1]; *tasks = h->last_ab_tasks;
+    return RADAD_OK;
+}
+
+int radad_knn_last_abandon_deal(radad_knn_t h, int* launches, int* workgroups, int* granule) {
+    RADAD_REQUIRE(h && launches && workgroups && granule, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    *launches = *workgroups = *granule = 0;
+    if (h->last_ab_tasks <= 0) return RADAD_OK;                 // the last search launched no abandoning scan
+    *launches = h->last_deal_launches; *workgroups = h->last_deal_workgroups; *granule = h->last_deal_granule;
     return RADAD_OK;
 }
 

@@ -76,6 +76,11 @@ struct KnnHiParams {
     const float* ab_ry = nullptr;         // [tiles of this launch] max over the tile's rows of |yh_i[64 ck:]|
     const float* ab_b = nullptr;          // RSC 3: [tiles of this launch] max over the tile's rows of bias_sign x bias (what the accumulators start from, x s_qs)
     int* ab_count = nullptr;              // [2] tile tasks tested, tile tasks abandoned (one atomic each per workgroup)
+    // DEALT launches (k_knn_hi_abandon_deal; which launches are: knn_abandon_deal, knn_plan.h): a workgroup draws granules of deal_g row
+    // tiles from the counter of its (XCD slot, query tile) instead of walking a static chunk
+    int deal_g = 0;                       // row tiles per granule (a power of two)
+    int deal_tiles = 0;                   // row tiles of this launch
+    int* deal_cnt = nullptr;              // [KNN_DEAL_SLOTS][KNN_DEAL_MAX_QTILES] this launch's ticket counters (zeroed once per search: k_hi_rows)
 };
 static_assert(std::is_trivially_copyable_v<KnnHiParams>, "kernel argument");
 
@@ -146,9 +151,11 @@ __device__ __forceinline__ bool knn_hi_gate(float amin, float rmax, float ry, fl
 // ABANDON: after p.ab_ck K stages a tile whose partial scores provably cannot reach any query's floor is left (the test, its gate and
 // the proof are at the checkpoint below).  Instantiations without it compile to the code they had before it existed.
 // (ab_amin, ab_rmax: the gate's query side, from knn_hi_gate_open)
-template <int RSC, bool SAMPLE, bool ABANDON = false>
-__device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab_amin = 0.f, const float ab_rmax = 0.f) {
+// DEAL (with ABANDON only): the tiles come by ticket.  deal_ticket: the first of the TWO tickets the gate pass drew for this workgroup.
+template <int RSC, bool SAMPLE, bool ABANDON = false, bool DEAL = false>
+__device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab_amin = 0.f, const float ab_rmax = 0.f, const int deal_ticket = 0) {
     static_assert(!ABANDON || (!SAMPLE && (RSC == 0 || RSC == 3)), "the abandon covers the one-scale scans");
+    static_assert(!DEAL || ABANDON, "only the abandoning scan is dealt");
     int stamp_n = 0;
     (void)stamp_n;
     // acc[mt][nt][r] = row wm*128 + mt*16 + 4*lq + r, query wn*64 + nt*16 + l15   (l15 = lane & 15, lq = lane >> 4)
@@ -183,8 +190,9 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
     int qt, split;
     if (!knn_hi_task(p, bid, qt, split)) return;     // (block-uniform, before any barrier)
     const int q0 = qt * KW_N;
-    const int64_t chunk_begin = (int64_t)split * p.chunk_stride;
-    const int64_t chunk_end = min(chunk_begin + p.chunk_rows, p.n);
+    // (DEAL: the "chunk" is the launch -- every tile but the launch's last is whole -- and `split` is not used)
+    const int64_t chunk_begin = DEAL ? (int64_t)0 : (int64_t)split * p.chunk_stride;
+    const int64_t chunk_end = DEAL ? p.n : min(chunk_begin + p.chunk_rows, p.n);
     const bool owner = tid < KW_N && q0 + tid < p.nq;
     const int nk_all = p.row_bytes >> 7;             // 128-byte K steps per row
     const int k_lo = part * (nk_all >> 1);           // this workgroup's K steps [k_lo, k_lo + nk)
@@ -274,11 +282,34 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
             s_rb[par * KW_M + t] = (RSC >= 2 && in && part == 0) ? (RSC == 2 ? p.bias_sign * p.rbias[r0 + t] / rs : p.bias_sign * p.rbias[r0 + t]) : 0.f;
         }
     };
+    // ---- DEAL: which tile comes next ------------------------------------------------------------------------------------------------
+    // Tickets map to granules of deal_g consecutive tiles (knn_deal_ticket, knn_plan.h: the text the host's check enumerates).  A
+    // granule begins on a multiple of deal_g, so "first / last tile of its granule" is read off the tile's number, and the state that
+    // lives across the tile loop is three scalars: the tile, the granule after this one (d_next) and the one after that (d_next2),
+    // each as its first tile, d_tiles = none.  The next tile must be known at the top of a tile (a skip issues its stage 0 at the
+    // checkpoint barrier, the last K stage prefetches it), so the draw runs a whole granule ahead: thread 0 issues the atomic in front
+    // of the first stage of a granule's first tile, parks the ticket in s_veto[2] behind that stage's MFMAs, the stage's own barrier --
+    // which waits vmcnt(0) anyway -- publishes it.  (The word is read right behind that barrier and written again a granule later:
+    // at least one more barrier lies between.)
+    const int d_tiles = DEAL ? p.deal_tiles : 0, d_mask = DEAL ? p.deal_g - 1 : 0;
+    int d_next = 0, d_next2 = 0;
+    int64_t row_first = chunk_begin, d_row_adv = 0;
+    (void)d_mask; (void)d_next; (void)d_next2; (void)d_row_adv;
+    auto deal_tile = [&](int ticket) {        // ticket -> the granule's first tile, or d_tiles
+        const DealRange g = knn_deal_ticket(bid & 7, ticket, d_tiles, p.deal_g);
+        return __builtin_amdgcn_readfirstlane(g.tiles > 0 ? g.tile0 : d_tiles);
+    };
+    if constexpr (DEAL) {
+        const int d_first = deal_tile(deal_ticket);
+        if (d_first >= d_tiles) return;              // a workgroup beyond the resident ones: its counter is used up (block-uniform, no barrier pending)
+        d_next = d_next2 = deal_tile(deal_ticket + 1);
+        row_first = (int64_t)d_first * KW_M;
+    }
     int gbuf = 0;
-    if (chunk_begin < chunk_end) {
-        if (grp_half == 0) dma_half(tile_desc(chunk_begin), 0, k_lo, 0);
+    if (row_first < chunk_end) {
+        if (grp_half == 0) dma_half(tile_desc(row_first), 0, k_lo, 0);
         else dma_half(q_desc, 0, k_lo, 1);
-        park_row_terms(chunk_begin, 0);
+        park_row_terms(row_first, 0);
     }
     __syncthreads();
 
@@ -388,8 +419,20 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
     int ab_ck = 0, ab_checked = 0, ab_skipped = 0;
     if constexpr (ABANDON) ab_ck = p.ab_ck;
     int tile_par = 0;
-    for (int64_t row0 = chunk_begin; row0 < chunk_end; row0 += KW_M, tile_par ^= 1) {
-        const bool has_next = row0 + KW_M < chunk_end;
+    for (int64_t row0 = row_first; row0 < chunk_end; row0 = DEAL ? d_row_adv : row0 + KW_M, tile_par ^= 1) {
+        int64_t row_next = row0 + KW_M;
+        bool d_draw = false;
+        if constexpr (DEAL) {
+            const int t = __builtin_amdgcn_readfirstlane((int)(row0 >> 8));
+            const bool first = (t & d_mask) == 0;
+            if (first) d_next = d_next2;             // (a granule's first tile is only ever reached from the granule before it)
+            const bool last = (t & d_mask) == d_mask || t + 1 >= d_tiles;
+            row_next = (int64_t)(last ? d_next : t + 1) * KW_M;      // none = d_tiles: at or past chunk_end
+            d_row_adv = row_next;
+            d_draw = first && d_next < d_tiles;      // (a used-up counter stays used up: nothing more to ask)
+        }
+        (void)d_draw;
+        const bool has_next = row_next < chunk_end;
         // THE GATE, tile side (scalars only): the test runs iff it can succeed
         float ab_ry = 0.f;
         bool ab_check = false, ab_skip = false;
@@ -400,7 +443,7 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
         static_assert(KW_M == 256, "row0 >> 8 is the tile's number");
         const int rowlimit = (int)min((int64_t)KW_M, chunk_end - row0);
         const __amdgpu_buffer_rsrc_t cur_desc = tile_desc(row0);
-        const __amdgpu_buffer_rsrc_t next_desc = tile_desc(row0 + KW_M);
+        const __amdgpu_buffer_rsrc_t next_desc = tile_desc(row_next);
         for (int kc = 0; kc < nk; ++kc) {
             const int stage = gbuf & 1;
             const bool more_k = kc + 1 < nk;
@@ -413,6 +456,18 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
             const float* rb_t = s_rb + tile_par * KW_M + wm * 128 + 4 * lq;
             const bool at_ck = ABANDON && ab_check && kc + 1 == ab_ck;      // the checkpoint stage (wave-uniform)
             const bool after_ck = ABANDON && ab_check && kc == ab_ck;
+            int d_ticket = 0;
+            if constexpr (DEAL) {
+                // (the counter's address goes through an OPAQUE per-lane zero: with an address it can prove uniform hipcc rewrites the
+                // atomic into its wave-aggregated form, which reads the result back -- s_waitcnt vmcnt(0) -- right behind the
+                // instruction: wave 0 then sat through the atomic's round trip in front of every granule's first DMA, ~1 us per
+                // granule for the whole workgroup.  As written the result is first touched at the LDS store behind the stage.)
+                if (kc == 0 && d_draw && tid == 0) {
+                    int z = 0;
+                    asm volatile("" : "+v"(z));
+                    d_ticket = atomicAdd(p.deal_cnt + (bid & 7) * KNN_DEAL_MAX_QTILES + qt + z, 1);
+                }
+            }
             if (kc == 0) stage_body(a_row, b_row, std::true_type{}, more_k && !at_ck, true, rb_t, dma_a, dma_b);      // first stage of a tile: C = 0 / the bias
             else stage_body(a_row, b_row, std::false_type{}, more_k && !at_ck, !after_ck, rb_t, dma_a, dma_b);       // (the last stage leaves nothing over)
             if constexpr (ABANDON) {
@@ -433,13 +488,19 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
                     if (!__all(ok) && (lane_t & 63) == 0) s_veto[tile_par] = (int)(row0 >> 8);
                 }
             }
+            if constexpr (DEAL) {
+                if (kc == 0 && d_draw && tid == 0) s_veto[2] = d_ticket;
+            }
 #ifdef RADAD_DEBUG_HOOKS
             if (p.stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); KH_STAMP(10); }   // own DMA landed (stamps only)
 #endif
             __syncthreads();     // waits vmcnt(0): the stage issued above has landed for everyone
             KH_STAMP(6);
             ++gbuf;
-            if (kc == 0 && has_next) park_row_terms(row0 + KW_M, tile_par ^ 1);
+            if (kc == 0 && has_next) park_row_terms(row_next, tile_par ^ 1);
+            if constexpr (DEAL) {
+                if (kc == 0 && d_draw) d_next2 = deal_tile(__builtin_amdgcn_readfirstlane(s_veto[2]));
+            }
             if constexpr (ABANDON) {
                 if (at_ck) {
                     ++ab_checked;
@@ -666,13 +727,20 @@ __global__ __launch_bounds__(KW_THREADS, 1) void k_knn_hi(KnnHiParams p) { knn_h
 // Whether the gate can open for ANY tile of this workgroup's chunk, and its query side (amin, rmax: knn_hi_gate).  Decided once, in front
 // of the body, so that a workgroup that can never test runs the plain body: the abandoning one carries a wave-uniform branch around
 // every stage's held-back MFMAs, measured at 2.5 % of the scan on unstructured queries.
-template <int RSC>
-__device__ __forceinline__ bool knn_hi_gate_open(const KnnHiParams& p, float& amin, float& rmax) {
+// WHOLE (a dealt launch): decided per QUERY TILE over all of the launch's tiles, so that every workgroup of a query tile reaches the same
+// answer from the same inputs -- were some to draw tickets while others walked their static chunks, tiles would be multiplied twice or
+// never.  The workgroup's first two tickets are drawn here, under the loads of the per-query terms (*ticket: the first of them; a query
+// tile whose gate stays shut draws too, and nobody reads its counters).
+template <int RSC, bool WHOLE = false>
+__device__ __forceinline__ bool knn_hi_gate_open(const KnnHiParams& p, float& amin, float& rmax, int* ticket = nullptr) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* s_pre = reinterpret_cast<float*>(smem);           // [16]: the stage buffers are not in use yet
+    float* s_pre = reinterpret_cast<float*>(smem);           // [16] (+ the ticket): the stage buffers are not in use yet
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int qt, split;
     if (!knn_hi_task(p, (int)blockIdx.x, qt, split)) return false;       // (the plain body returns at the same test)
+    if constexpr (WHOLE) {
+        if (tid == 0) reinterpret_cast<int*>(s_pre)[16] = atomicAdd(p.deal_cnt + ((int)blockIdx.x & 7) * KNN_DEAL_MAX_QTILES + qt, 2);
+    }
     const int q = qt * KW_N + tid;
     float a = INFINITY, r = 0.f;
     if (tid < KW_N && q < p.nq) {
@@ -687,8 +755,9 @@ __device__ __forceinline__ bool knn_hi_gate_open(const KnnHiParams& p, float& am
     __syncthreads();
     amin = fminf(fminf(s_pre[0], s_pre[1]), fminf(s_pre[2], s_pre[3]));
     rmax = fmaxf(fmaxf(s_pre[8], s_pre[9]), fmaxf(s_pre[10], s_pre[11]));
-    const int64_t chunk_begin = (int64_t)split * p.chunk_stride;
-    const int64_t chunk_end = min(chunk_begin + p.chunk_rows, p.n);
+    if constexpr (WHOLE) *ticket = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(s_pre)[16]);
+    const int64_t chunk_begin = WHOLE ? (int64_t)0 : (int64_t)split * p.chunk_stride;
+    const int64_t chunk_end = WHOLE ? p.n : min(chunk_begin + p.chunk_rows, p.n);
     int open = 0;
     for (int64_t r0 = chunk_begin + (int64_t)tid * KW_M; r0 < chunk_end; r0 += (int64_t)KW_THREADS * KW_M)
         open |= knn_hi_gate(amin, rmax, p.ab_ry[r0 >> 8], RSC == 3 ? p.ab_b[r0 >> 8] : 0.f) ? 1 : 0;
@@ -710,6 +779,17 @@ template <int RSC>
 __global__ __launch_bounds__(KW_THREADS, 1) void k_knn_hi_abandon(KnnHiParams p) {
     float amin, rmax;
     if (knn_hi_gate_open<RSC>(p, amin, rmax)) knn_hi_body<RSC, false, true>(p, amin, rmax);
+    else knn_hi_body<RSC, false, false>(p);
+}
+
+// the abandoning scan of a DEALT launch (knn_abandon_deal, knn_plan.h): own symbol, so that a launch that is not dealt runs
+// k_knn_hi_abandon as it was, instruction for instruction.  A query tile whose gate is shut runs the plain body over its static chunks,
+// exactly as before: the grid is the one the static chunks are cut for.
+template <int RSC>
+__global__ __launch_bounds__(KW_THREADS, 1) void k_knn_hi_abandon_deal(KnnHiParams p) {
+    float amin, rmax;
+    int ticket = 0;
+    if (knn_hi_gate_open<RSC, true>(p, amin, rmax, &ticket)) knn_hi_body<RSC, false, true, true>(p, amin, rmax, ticket);
     else knn_hi_body<RSC, false, false>(p);
 }
 
@@ -804,6 +884,7 @@ struct HiRowsParams {
     float* suf_out = nullptr;        // query side, [n]: |xh[suf_from:]|, inflated like the other norms
     float* ab_slack_out = nullptr;   // query side, [n] (with eps_out): 2 dim 2^-23 (|qh| max |yh| + |c0|max), true units
     int* zero_ab = nullptr;          // optional [2]: the abandon's counters, cleared with zero_counters
+    int* zero_deal = nullptr;        // optional [KNN_DEAL_COUNTERS]: the ticket counters of the search's dealt launches, cleared by row 0's team
 };
 static_assert(std::is_trivially_copyable_v<HiRowsParams>, "kernel argument");
 constexpr int HI_E_PER_ROW = -0x7fffffff - 1;
@@ -841,6 +922,7 @@ __device__ __forceinline__ void hi_rows_body(const HiRowsParams& p) {
     const int64_t row = WPR == 1 ? (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6) : (int64_t)blockIdx.x;
     if (row >= p.n) return;                                                       // (WPR 4: uniform per workgroup)
     const int nv = p.dim >> 2;
+    if (p.zero_deal && row == 0) { for (int i = lane; i < KNN_DEAL_COUNTERS; i += TEAM) p.zero_deal[i] = 0; }
     if (lane == 0) {
         if (p.zero_flags) p.zero_flags[row] = 0;
         if (p.zero_flags2) p.zero_flags2[row] = 0;

@@ -401,6 +401,75 @@ static int64_t knn_abandon_tiles(int64_t rows) { return ceil_div64(rows, KW_M); 
 // ints of the search's counter block (SearchLayout::fcount, 64 ints: flag_count + 6 statistics first) the abandon counts in
 constexpr int KNN_AB_COUNTER0 = 8;       // [8] tile tasks tested, [9] tile tasks abandoned
 
+// ---- the abandoning scan's tiles, dealt by ticket (knn_hi.inc, k_knn_hi_abandon_deal) ---------------------------------------------
+// A static chunk of an abandoning launch holds as many tiles that cannot be skipped as the store happens to put there, and the launch
+// ends with its slowest workgroup.  The scan keeps no per-chunk state (candidates go to per-query buffers by atomics, the re-rank does
+// not depend on their order), so which workgroup multiplies a tile is free: in a DEALT launch a workgroup keeps its query tile and its
+// XCD slot (bid & 7: knn_hi_task) and draws GRANULES of `granule` consecutive row tiles from a counter of its (slot, query tile) until
+// the slot's share is used up.  The launch's granules go to the eight slots round-robin -- granule g belongs to slot g % 8, ticket t of
+// slot s is granule 8 t + s -- so a store filled cluster by cluster spreads over all slots, and the query tiles of a slot walk the
+// same sequence of row tiles (they share them through the XCD's L2, as the static chunks did).  Nothing depends on which physical
+// XCD a workgroup runs on: the slot is a number, the counter is device-wide.
+// The grid stays the one knn_geometry_wide gives: a launch whose gate is closed for a query tile (knn_hi.inc) runs that query tile's
+// static chunks exactly as before, and of an open one the workgroups beyond the resident ones find their counter used up.
+constexpr int KNN_DEAL_SLOTS = 8;            // XCD slots: bid & 7
+constexpr int KNN_DEAL_MAX_QTILES = 8;       // the first branch of knn_hi_task
+constexpr int KNN_DEAL_SETS = 4;             // counter sets of a search, one per launch (the phases of <= 9.5 M rows are three)
+constexpr int KNN_DEAL_COUNTERS = KNN_DEAL_SETS * KNN_DEAL_SLOTS * KNN_DEAL_MAX_QTILES;      // ints the query preparation zeroes
+#ifndef KNN_DEAL_GRANULE
+#define KNN_DEAL_GRANULE 4                   // (measured against 1 and 2: profiles/abandon_deal_ab.txt; 8 granules within 40 tiles)
+#endif
+constexpr int knn_deal_counter(int set, int slot, int qt) { return (set * KNN_DEAL_SLOTS + slot) * KNN_DEAL_MAX_QTILES + qt; }
+
+// ticket -> row tiles [tile0, tile0 + tiles) of the launch; tiles == 0: the slot's share is used up (every later ticket too).
+// Host and device read this same text (constexpr: callable from both sides).  granule: a power of two.
+struct DealRange {
+    int tile0 = 0, tiles = 0;
+};
+constexpr int64_t knn_deal_granules(int64_t row_tiles, int granule) { return (row_tiles + granule - 1) / granule; }
+constexpr DealRange knn_deal_ticket(int slot, int64_t ticket, int64_t row_tiles, int granule) {
+    DealRange r;
+    const int64_t first = (ticket * KNN_DEAL_SLOTS + slot) * granule;      // (no division: the kernel runs this once per granule)
+    if (ticket < 0 || first >= row_tiles) return r;
+    r.tile0 = (int)first;
+    r.tiles = (int)(row_tiles - first < granule ? row_tiles - first : granule);
+    return r;
+}
+
+// Whether a launch is dealt.  Only where it can help: the launch takes the ABANDON instantiation (ab_ck > 0: knn_abandon_launch), its
+// query tiles are at most 8 (knn_hi_task's first branch: one stream of row tiles per (slot, query tile)), it is one of the search's
+// first KNN_DEAL_SETS launches, and a resident workgroup -- one per CU, the CUs shared out over 8 slots x the query tiles, no more than
+// the grid has -- would draw at least two granules of the smallest slot's share; the granule halves until that holds.  Everything else
+// launches exactly what it launched before: the 20 000-row stores of the tests, K-split launches and the sample pre-pass (ab_ck 0),
+// sharded batches of more than 8 query tiles.
+struct DealFacts {
+    int opt_deal = 1;            // RADAD_KNN_OPT_ABANDON_DEAL
+    int ab_ck = 0;               // knn_abandon_launch of this launch
+    int launch = 0;              // the launch's number in its search
+    int64_t row_tiles = 0;       // KW_M-row tiles of the launch
+    int n_qtiles = 0, n_splits = 0;      // knn_geometry_wide of the launch: the grid is n_qtiles x n_splits workgroups
+    int cus = 0;                 // compute units of the device
+};
+struct DealPlan {
+    bool dealt = false;
+    int workgroups = 0;          // the launch's grid (unchanged)
+    int resident = 0;            // workgroups of one (slot, query tile) that run at once and draw
+    int granule = 0;
+};
+static DealPlan knn_abandon_deal(const DealFacts& f) {
+    DealPlan d;
+    if (!f.opt_deal || f.ab_ck <= 0 || f.launch < 0 || f.launch >= KNN_DEAL_SETS || f.row_tiles <= 0 || f.cus <= 0) return d;
+    if (f.n_qtiles < 1 || f.n_qtiles > KNN_DEAL_MAX_QTILES || f.n_splits < KNN_DEAL_SLOTS || f.n_splits % KNN_DEAL_SLOTS != 0) return d;
+    const int resident = std::min(f.n_splits / KNN_DEAL_SLOTS, std::max(1, f.cus / (KNN_DEAL_SLOTS * f.n_qtiles)));
+    for (int g = KNN_DEAL_GRANULE; g >= 1; g /= 2) {
+        if (knn_deal_granules(f.row_tiles, g) / KNN_DEAL_SLOTS >= 2 * (int64_t)resident) {
+            d.dealt = true; d.workgroups = f.n_qtiles * f.n_splits; d.resident = resident; d.granule = g;
+            return d;
+        }
+    }
+    return d;
+}
+
 // ---- workspace layouts ------------------------------------------------------------------------------------------------------------
 // byte offsets of a search's buffers in the handle's workspace (knn_search_layout)
 struct SearchLayout {

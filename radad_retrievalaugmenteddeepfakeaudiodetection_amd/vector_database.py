@@ -646,6 +646,19 @@ class HipFlatIndex:
         _lib.check(self._lib.radad_knn_last_abandon(self._h, C.byref(c), C.byref(s), C.byref(t)), "radad_knn_last_abandon")
         return {"checked": c.value, "skipped": s.value, "tasks": t.value}
 
+    def set_abandon_deal(self, value):
+        """RADAD_KNN_OPT_ABANDON_DEAL at any time: 1 = abandoning launches that qualify deal their row tiles to the workgroups by ticket,
+        0 = every launch walks static chunks (the default; same results; A/B measurements and the parity tests)"""
+        _lib.check(self._lib.radad_knn_set_option(self._h, _lib.KNN_OPT_ABANDON_DEAL, int(value)), "radad_knn_set_option")
+        self.options["abandon_deal"] = int(value)
+
+    def last_abandon_deal(self):
+        """{"launches", "workgroups", "granule"}: how many abandoning launches of the last search were dealt by ticket, and the grid and
+        the row tiles per granule of the last of them (radad_knn_last_abandon_deal; all 0 when none was)"""
+        n, w, g = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(self._lib.radad_knn_last_abandon_deal(self._h, C.byref(n), C.byref(w), C.byref(g)), "radad_knn_last_abandon_deal")
+        return {"launches": n.value, "workgroups": w.value, "granule": g.value}
+
     def tuning_info(self):
         """{"cap_boost", "fp32_searches_left", "reports_consumed"} (radad_knn_tuning_info): read without synchronising"""
         a, b, n = C.c_int(), C.c_int(), C.c_int64()
@@ -663,6 +676,7 @@ class HipFlatIndex:
         _lib.check(self._lib.radad_knn_last_scan_phases(self._h, C.byref(nph)))
         return {"query_tiles": a.value, "db_splits": b.value, "block_threads": c.value, "rechecked_queries": st[0],
                 "scan_launches": nl.value, "scan_phases": nph.value, "early_abandon": self.last_abandon(),
+                "abandon_deal": self.last_abandon_deal(),
                 "scan_kind": ("f32_tile", "hi_tile", "f32_smallq", "hi_smallq", "f16_tile", "f32_dense")[kind.value],
                 "certificate": {"queries": nq.value, "rejected": st[0], "candidates_rescored": st[1],
                                 "rejected_buffer_full": st[2], "rejected_list_used_up": st[3],
