@@ -2931,9 +2931,9 @@ struct radad_knn_s {
     size_t excl_ws_bytes = 0, excl_o_count = 0;
     int64_t last_excl_nq = 0;    // batch size of the most recent exclusion-aware search (radad_knn_last_excl)
     int64_t last_xs_nq = 0;      // radad_knn_search_excl_scan: batch size and route of the most recent one (radad_knn_last_excl_scan; its
-    int last_xs_route = RADAD_EXCL_SCAN_EXACT;      // count of exactly answered queries is copied to host_count[17] behind it)
+    int last_xs_route = RADAD_EXCL_SCAN_EXACT;      // count of exactly answered queries is copied to host_count[HC_XS_EXACT] behind it)
     int64_t last_rg_nq = 0;      // radad_knn_range_search: batch size and route of the most recent one (radad_knn_last_range; its count
-    int last_rg_route = RADAD_RANGE_EXACT;          // of exactly answered queries is copied to host_count[18] behind it)
+    int last_rg_route = RADAD_RANGE_EXACT;          // of exactly answered queries is copied to host_count[HC_RG_EXACT] behind it)
     double* rs_key = nullptr;    // k_refine_small: [SQ_NQ][KNN_CERT_CAP] float64 keys of the candidates, where the query's workgroups meet
     int* rs_count = nullptr;     // ... and [SQ_NQ] arrival counters (zero between launches)
     int uniform_e = HI_E_PER_ROW; // one power-of-two scale 2^e for every row of the plane (rows of one magnitude), or HI_E_PER_ROW
@@ -2960,6 +2960,10 @@ struct radad_knn_s {
     // queries the certificate rejected in the most recent search: counted on the device, copied to pinned host memory
     // behind the search (no synchronisation inside search); feeds the adaptive tuning and radad_knn_last_recheck
     int* host_count = nullptr;   // pinned [2][8]: rejected queries, sum of candidates, rejections by reason x 4, [6] the report's stamp, [7] its batch size
+    // ... and behind the two reports one slot each for a count that is copied behind its search and read after a wait:
+    static constexpr int HC_LOOK = 16;        // the look before the exact pass: queries the certificate rejected (knn_search_phase2)
+    static constexpr int HC_XS_EXACT = 17;    // queries the exact kernel answered in the last in-scan exclusion search (radad_knn_last_excl_scan)
+    static constexpr int HC_RG_EXACT = 18;    // ... in the last range search (radad_knn_last_range)
     // what the handle does about batches the certificate mostly rejected -- reports, the look before the exact pass, re-deciding the
     // plane, wider buffers, the fp32 fallback: ONE policy, described and kept in KnnTuning (knn_plan.h); this file reads the pinned
     // slots, synchronises, rebuilds the plane and hands plain integers to it
@@ -3020,8 +3024,10 @@ static int knn_grow(radad_knn_t h, int64_t need) {
     return knn_realloc(h, std::max<int64_t>(cap, 1024));
 }
 
+// grow the search workspace to `bytes` (every search lays its buffers out first and calls this with the layout's size)
 static int knn_workspace(radad_knn_t h, size_t bytes) {
     if (bytes <= h->ws_bytes) return RADAD_OK;
+    RADAD_HIP_CHECK(hipDeviceSynchronize());       // a search on another stream may still read the old one
     if (h->ws) (void)hipFree(h->ws);
     h->ws = nullptr;
     h->ws_bytes = 0;
@@ -3985,11 +3991,8 @@ static int knn_search_phase1(radad_knn_t h, const void* q_in, int q_dtype, int64
     rc = knn_plan_scan(h, nq, k, margin, st, &p);
     if (rc) return rc;
     const SearchLayout L = knn_search_layout(knn_store_facts(h), p, q_dtype);
-    if (L.bytes > h->ws_bytes) {
-        RADAD_HIP_CHECK(hipDeviceSynchronize());
-        rc = knn_workspace(h, L.bytes);
-        if (rc) return rc;
-    }
+    rc = knn_workspace(h, L.bytes);
+    if (rc) return rc;
     const float* q_use = knn_prepare_queries(h, p, L, q_in, q_dtype, st);
     RADAD_HIP_CHECK(hipGetLastError());
 
@@ -4093,7 +4096,36 @@ static int knn_ensure_xarrive(radad_knn_t h, int64_t nq, hipStream_t st) {
     return RADAD_OK;
 }
 
-constexpr int RADAD_RETRY_INTERNAL = 1;      // knn_search_phase2 -> knn_search_core: retuned after a mass rejection, run the search again
+// The one place an exact pass is launched, whatever the instantiation of k_exact_scan_any: the queries x.sel[0, *x.count) of a batch
+// of nq at k results (a range search: at most k listed), sized and driven by the device-side count.  The caller's `x` holds what
+// its family owns -- queries, the listed ones, partial lists with their grouping (group, nslots), outputs, the admission rule, the
+// range fields, stamp / nq_report; the store, k, the slices, the arrival counters (the caller made room for nq of them:
+// knn_ensure_xarrive) and the launches are filled in here.
+// first_host_stats: where the launch of the first slots leaves the search's report (knn_search_phase2); NULL for every family that
+// posts none -- the handle's certificate report and its tuning belong to the plain search.
+static int knn_launch_exact(radad_knn_t h, void (*kern)(ExactParams), ExactParams x, int64_t nq, int k, hipStream_t st,
+                            int* first_host_stats = nullptr) {
+    x.db = h->rows; x.db_f16 = h->f16; x.n = h->ntotal; x.dim = h->dim; x.k = k; x.id_base = h->id_base;
+    x.slice_rows = ceil_div64(std::max<int64_t>(h->ntotal, 1), KX_SLICES);
+    x.arrive = h->xarrive;
+    // (with the kernel's static arrival flag <= KX_LDS_MAX: every entry point checked knn_exact_fits.  Until the width tests
+    // searched 16380 x 1024 the launch asked for 16 bytes more than the kernel indexes, and the widest rows the limit admits
+    // were refused by hipFuncSetAttribute: 160 KB of dynamic LDS plus the static flag)
+    const size_t xlds = knn_exact_dyn_lds_bytes(h->dim, k);
+    RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
+    // (k beyond KNN_F16_MAX_K: groups of one or two queries, each a long insert and merge -- more of them in flight; the
+    // geometry of k <= 128 is the measured one)
+    const unsigned gy = k <= KNN_F16_MAX_K ? KX_GROUPS_Y : 8 * KX_GROUPS_Y;
+    for (int64_t s0 = 0; s0 < nq; s0 += x.nslots) {      // (launches past the device-side count leave at once)
+        x.slot0 = (int)s0;
+        x.host_stats = s0 == 0 ? first_host_stats : nullptr;
+        hipLaunchKernelGGL(kern, dim3(KX_SLICES, gy), dim3(KX_THREADS), xlds, st, x);
+    }
+    RADAD_HIP_CHECK(hipGetLastError());
+    return RADAD_OK;
+}
+
+constexpr int RADAD_RETRY_INTERNAL = 1;     // knn_search_phase2 -> knn_search_core: retuned after a mass rejection, run the search again
 static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* global_lb, bool may_retry, float* out_dist_dev, int64_t* out_idx_dev,
                              double* out_key_dev, hipStream_t st) {
     int* flag_count = ws_at<int>(h, c.ws.fcount);
@@ -4105,7 +4137,7 @@ static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* glo
 
     // ---- look before the exact pass (see KnnTuning) ------------------------------------------------------------------------------
     if (h->tune.looks_before_exact(c.hi_tile, nq, h->ntotal, h->dim)) {
-        int* rej = h->host_count + 16;
+        int* rej = h->host_count + h->HC_LOOK;
         RADAD_HIP_CHECK(hipMemcpyAsync(rej, flag_count, sizeof(int), hipMemcpyDeviceToHost, st));
         RADAD_HIP_CHECK(hipStreamSynchronize(st));
         if (h->tune.look_outcome(*rej, nq, may_retry, h->tune.appended_since_plane(h->hi != nullptr, h->ntotal))) return RADAD_RETRY_INTERNAL;
@@ -4114,34 +4146,19 @@ static int knn_search_phase2(radad_knn_t h, const SearchCtx& c, const float* glo
     // ---- the queries the certificate rejected: exact float64 search, sized and driven by the device-side count ------
     {
         ExactParams x;
-        x.db = h->rows; x.db_f16 = h->f16; x.q = c.q_use; x.sel = flag_sel; x.count = flag_count;
-        x.n = h->ntotal; x.dim = h->dim; x.k = k; x.l2 = c.l2; x.group = c.xgroup;
-        x.slice_rows = ceil_div64(std::max<int64_t>(h->ntotal, 1), KX_SLICES);
-        x.pkey = ws_at<double>(h, c.ws.xk); x.pidx = ws_at<int>(h, c.ws.xi); x.id_base = h->id_base;
+        x.q = c.q_use; x.sel = flag_sel; x.count = flag_count; x.l2 = c.l2;
+        x.pkey = ws_at<double>(h, c.ws.xk); x.pidx = ws_at<int>(h, c.ws.xi);
+        x.group = c.xgroup; x.nslots = (int)knn_exact_slots(nq, k, c.xgroup);
         x.out_dist = out_dist_dev; x.out_idx = out_idx_dev; x.out_key = out_key_dev;
         x.stamp = h->tune.stamp();
         // (a search beyond KNN_F16_MAX_K took no f16 scan: its rejections say nothing about the f16 scans' tuning, which reads
         // batch sizes of >= 64 only -- knn_consume_reports)
         x.nq_report = k <= KNN_F16_MAX_K ? (int)std::min<int64_t>(nq, 0x7fffffff) : 0;
-        // (with the kernel's static arrival flag <= KX_LDS_MAX: every entry point checked knn_exact_fits.  Until the width tests
-        // searched 16380 x 1024 the launch asked for 16 bytes more than the kernel indexes, and the widest rows the limit admits
-        // were refused by hipFuncSetAttribute: 160 KB of dynamic LDS plus the static flag)
-        const size_t xlds = knn_exact_dyn_lds_bytes(h->dim, k);
-        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_exact_scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
         rc = knn_ensure_xarrive(h, nq, st);
         if (rc) return rc;
-        x.arrive = h->xarrive;
-        // (k beyond KNN_F16_MAX_K: groups of one or two queries, each a long insert and merge -- more of them in flight; the
-        // geometry of k <= 128 is the measured one)
-        const unsigned gy = k <= KNN_F16_MAX_K ? KX_GROUPS_Y : 8 * KX_GROUPS_Y;
-        x.nslots = (int)knn_exact_slots(nq, k, c.xgroup);
-        for (int64_t s0 = 0; s0 < nq; s0 += x.nslots) {  // (launches past the device-side count leave at once)
-            x.slot0 = (int)s0;
-            x.host_stats = s0 == 0 ? h->host_count_dev + 8 * c.cslot : nullptr;
-            hipLaunchKernelGGL(k_exact_scan, dim3(KX_SLICES, gy), dim3(KX_THREADS), xlds, st, x);
-        }
-        RADAD_HIP_CHECK(hipGetLastError());
-        h->count_nq[c.cslot] = nq;                                     // (k_exact_scan writes the counters and its stamp to the pinned host copy)
+        rc = knn_launch_exact(h, k_exact_scan, x, nq, k, st, h->host_count_dev + 8 * c.cslot);
+        if (rc) return rc;
+        h->count_nq[c.cslot] = nq;                                    // (k_exact_scan writes the counters and its stamp to the pinned host copy)
         h->tune.search_issued();
     }
     h->last_stream = st;
@@ -4196,41 +4213,37 @@ static int knn_excl_reserve(radad_knn_t h, size_t bytes) {
     return RADAD_OK;
 }
 
+// the admission bitmap of a batch rule, one bit per row in admit[0, n_words): all ones when nothing is excluded (the tags may be
+// NULL then).  count: NULL, or a device-side count of listed queries -- the bitmap is built only when *count > 0
+static int knn_admit_bitmap(radad_knn_t h, const ExclRule& r, const int* count, unsigned long long* admit, int64_t n_words, hipStream_t st) {
+    if (r.n_excl > 0)
+        hipLaunchKernelGGL(k_admit_bitmap<false>, dim3((unsigned)ceil_div64(n_words * 64, 256)), dim3(256), 0, st, r.tags,
+                           (const int64_t*)nullptr, h->ntotal, r.excl, r.n_excl, count, admit, n_words);
+    else
+        RADAD_HIP_CHECK(hipMemsetAsync(admit, 0xff, (size_t)n_words * sizeof(unsigned long long), st));
+    RADAD_HIP_CHECK(hipGetLastError());
+    return RADAD_OK;
+}
+
 // the row-filtered exact pass for the queries in sel[0, *count): bitmap (built only when *count > 0), then k_exact_scan_excl sized and
 // driven by the device-side count like the exact pass of any search; it overwrites those queries' rows of out_*
 // (per-query rule: no bitmap; k_exact_scan_excl_pq compares the row's tag with the group's query tags)
 static int knn_excl_exact_pass(radad_knn_t h, const ExclLayout& L, int64_t nq, int k, int l2, const float* q_use, const ExclRule& r,
                                float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, hipStream_t st) {
     auto at = [&](size_t o) { return (char*)h->excl_ws + o; };
-    int* count = (int*)at(L.count);
-    unsigned long long* admit = r.per_query ? nullptr : (unsigned long long*)at(L.admit);
-    if (!r.per_query) {
-        hipLaunchKernelGGL(k_admit_bitmap<false>, dim3((unsigned)ceil_div64(L.n_words * 64, 256)), dim3(256), 0, st, r.tags,
-                           (const int64_t*)nullptr, h->ntotal, r.excl, r.n_excl, (const int*)count, admit, L.n_words);
-        RADAD_HIP_CHECK(hipGetLastError());
-    }
     ExactParams x;
-    x.db = h->rows; x.db_f16 = h->f16; x.q = q_use; x.sel = (int*)at(L.sel); x.count = count;
-    x.n = h->ntotal; x.dim = h->dim; x.k = k; x.l2 = l2; x.group = L.xgroup;
-    x.slice_rows = ceil_div64(h->ntotal, KX_SLICES);
-    x.pkey = (double*)at(L.xk); x.pidx = (int*)at(L.xi); x.id_base = h->id_base;
+    x.q = q_use; x.sel = (int*)at(L.sel); x.count = (int*)at(L.count); x.l2 = l2;
+    x.pkey = (double*)at(L.xk); x.pidx = (int*)at(L.xi); x.group = L.xgroup; x.nslots = (int)L.xslots;
     x.out_dist = out_dist_dev; x.out_idx = out_idx_dev; x.out_key = out_key_dev;
-    x.host_stats = nullptr;                                    // the handle's certificate report and its tuning belong to the fast pass
-    x.arrive = h->xarrive;                                     // (the fast pass made room for nq groups; zero between launches)
-    x.admit = admit;
     if (r.per_query) { x.row_tags = r.tags; x.q_tags = r.q_tags; x.q_cnt = r.q_cnt; x.m = r.m(); }
-    const auto kern = r.per_query ? k_exact_scan_excl_pq : k_exact_scan_excl;
-    const size_t xlds = knn_exact_dyn_lds_bytes(h->dim, k);      // (with the static arrival flag <= KX_LDS_MAX: knn_excl_check_args)
-    RADAD_REQUIRE(h->xarrive && nq <= h->xarrive_cap, "radad_knn_search_excl: the fast pass left no arrival counters for %lld queries", (long long)nq);
-    RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
-    const unsigned gy = k <= KNN_F16_MAX_K ? KX_GROUPS_Y : 8 * KX_GROUPS_Y;
-    x.nslots = (int)L.xslots;
-    for (int64_t s0 = 0; s0 < nq; s0 += x.nslots) {            // (launches past the device-side count leave at once)
-        x.slot0 = (int)s0;
-        hipLaunchKernelGGL(kern, dim3(KX_SLICES, gy), dim3(KX_THREADS), xlds, st, x);
+    else {
+        const int rc = knn_admit_bitmap(h, r, x.count, (unsigned long long*)at(L.admit), L.n_words, st);
+        if (rc) return rc;
+        x.admit = (const unsigned long long*)at(L.admit);
     }
-    RADAD_HIP_CHECK(hipGetLastError());
-    return RADAD_OK;
+    // (the fast pass made room for nq groups; zero between launches)
+    RADAD_REQUIRE(h->xarrive && nq <= h->xarrive_cap, "radad_knn_search_excl: the fast pass left no arrival counters for %lld queries", (long long)nq);
+    return knn_launch_exact(h, r.per_query ? k_exact_scan_excl_pq : k_exact_scan_excl, x, nq, k, st);
 }
 
 // the part the whole-store call and the shard's first half share: layout -> workspace -> the fast pass at kf into fd / fi / fk ->
@@ -4355,132 +4368,73 @@ __global__ __launch_bounds__(256) void k_excl_scan_pad(float* __restrict__ dist,
     }
 }
 
-// One call, two routes (knn_excl_scan_route).  Neither consumes a certificate report, takes a turn off the tuning state, looks before
-// its exact pass or posts a report: KnnTuning is read (hi_skip) and otherwise left as it was found.
-static int knn_search_excl_scan_locked(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, const ExclRule& r,
-                                       float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, hipStream_t st) {
-    int rc = knn_order_behind_last(h, st);
-    if (rc) return rc;
-    const TileEligibility t = knn_tile_eligibility(knn_store_facts(h), nq, k, KNN_MARGIN);
-    bool tile = knn_excl_scan_route(knn_store_facts(h), nq, k, h->tune.hi_skip) == RADAD_EXCL_SCAN_TILE;
-    if (tile) tile = knn_ensure_hi(h, st, true);                   // (a plane that cannot be allocated switches itself off: exact route)
-    if (!tile && !knn_ensure_hi(h, st, false)) { radad_set_error("store statistics could not be computed"); return RADAD_EHIP; }
-    // the plan of the plain search, with the biased instantiation whatever the plane: RSC 0 / 1 run as RSC 3 / 2 with a zero bias for
-    // the admitted rows and a zero query constant (k_hi_rows writes mu.q' + |mu|^2 = 0 without a centre)
-    ScanPlan p = knn_finish_plan(knn_store_facts(h), nq, k, KNN_MARGIN, t, tile, false);
-    p.mu = (p.hi_q && !h->f16) ? h->cmu : nullptr;
-    p.biased = p.hi_q;
-    const SearchLayout L = knn_search_layout(knn_store_facts(h), p, q_dtype);
-    if (L.bytes > h->ws_bytes) {
-        RADAD_HIP_CHECK(hipDeviceSynchronize());
-        rc = knn_workspace(h, L.bytes);
-        if (rc) return rc;
-    }
-    const int route = tile ? RADAD_EXCL_SCAN_TILE : RADAD_EXCL_SCAN_EXACT;
-    const ExclScanLayout X = knn_excl_scan_layout(knn_store_facts(h), route);
-    rc = knn_excl_reserve(h, X.bytes);
-    if (rc) return rc;
-    rc = knn_ensure_xarrive(h, nq, st);
-    if (rc) return rc;
-    h->last_emit_nq = 0;                                           // (the workspace no longer holds the last plain tile scan's counters)
-    h->last_xs_nq = 0;
-
-    // ---- pre-pass: admission bitmap (all ones when nothing is excluded: the tags may be NULL then) -----------------------------------
-    unsigned long long* admit = reinterpret_cast<unsigned long long*>((char*)h->excl_ws + X.admit);
-    if (r.n_excl > 0)
-        hipLaunchKernelGGL(k_admit_bitmap<false>, dim3((unsigned)ceil_div64(X.n_words * 64, 256)), dim3(256), 0, st, r.tags,
-                           (const int64_t*)nullptr, h->ntotal, r.excl, r.n_excl, (const int*)nullptr, admit, X.n_words);
-    else
-        RADAD_HIP_CHECK(hipMemsetAsync(admit, 0xff, (size_t)X.n_words * sizeof(unsigned long long), st));
-    const float* q_use = knn_prepare_queries(h, p, L, q_in, q_dtype, st);      // (clears the listed-query counter and the candidate counters)
-    RADAD_HIP_CHECK(hipGetLastError());
-    int* flag_count = ws_at<int>(h, L.fcount);
-    int* flag_sel = ws_at<int>(h, L.fsel);
-
-    if (tile) {
-        // ... and the bias array; then the plain search's scan, re-rank and certificate over the admitted rows
-        float* bias = reinterpret_cast<float*>((char*)h->excl_ws + X.bias);
-        hipLaunchKernelGGL(k_excl_scan_bias, dim3((unsigned)ceil_div64(h->ntotal, 256)), dim3(256), 0, st, (const unsigned long long*)admit,
-                           (const float*)(p.mu ? h->rbias : (p.l2 ? h->ynorm : nullptr)), h->ntotal, bias);
-        RADAD_HIP_CHECK(hipGetLastError());
-        h->prof.next_search();
-        rc = knn_scan_hi_tile(h, p, L, st, bias);
-        if (rc) return rc;
-        RADAD_HIP_CHECK(hipGetLastError());
-        SearchCtx c;
-        c.valid = true;
-        c.nq = nq; c.k = k; c.l2 = p.l2; c.n_parts = p.n_parts; c.plen = p.plen; c.cap = p.cap; c.xgroup = p.xgroup;
-        c.emit = true; c.use_floor = true; c.hi_tile = true; c.canonical = true; c.q_use = q_use; c.ws = L;
-        h->last_o_cnt = L.cnt; h->last_o_thr = L.thr; h->last_emit_nq = nq;
-        rc = knn_rerank(h, c, nullptr, out_dist_dev, out_idx_dev, out_key_dev, st);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_excl_scan_pad, dim3((unsigned)ceil_div64(nq * k, 256)), dim3(256), 0, st, out_dist_dev, (const int64_t*)out_idx_dev,
-                           out_key_dev, nq * k);
-    } else {
-        hipLaunchKernelGGL(k_excl_scan_list_all, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, st, flag_sel, flag_count, nq);
-    }
-    RADAD_HIP_CHECK(hipGetLastError());
-
-    // ---- the listed queries (tile route: the ones the certificate rejected): the ROW-FILTERED float64 exact kernel, sized and driven
-    // by the device-side count.  No report: host_stats stays NULL.
-    {
-        ExactParams x;
-        x.db = h->rows; x.db_f16 = h->f16; x.q = q_use; x.sel = flag_sel; x.count = flag_count;
-        x.n = h->ntotal; x.dim = h->dim; x.k = k; x.l2 = p.l2; x.group = p.xgroup;
-        x.slice_rows = ceil_div64(h->ntotal, KX_SLICES);
-        x.pkey = ws_at<double>(h, L.xk); x.pidx = ws_at<int>(h, L.xi); x.id_base = h->id_base;
-        x.out_dist = out_dist_dev; x.out_idx = out_idx_dev; x.out_key = out_key_dev;
-        x.host_stats = nullptr;
-        x.arrive = h->xarrive;
-        x.admit = admit;
-        const size_t xlds = knn_exact_dyn_lds_bytes(h->dim, k);
-        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_exact_scan_excl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
-        const unsigned gy = k <= KNN_F16_MAX_K ? KX_GROUPS_Y : 8 * KX_GROUPS_Y;
-        x.nslots = (int)knn_exact_slots(nq, k, p.xgroup);
-        for (int64_t s0 = 0; s0 < nq; s0 += x.nslots) {            // (launches past the device-side count leave at once)
-            x.slot0 = (int)s0;
-            hipLaunchKernelGGL(k_exact_scan_excl, dim3(KX_SLICES, gy), dim3(KX_THREADS), xlds, st, x);
-        }
-        RADAD_HIP_CHECK(hipGetLastError());
-    }
-    // how many queries the exact kernel answered, for radad_knn_last_excl_scan (pinned memory: no synchronisation here)
-    RADAD_HIP_CHECK(hipMemcpyAsync(h->host_count + 17, flag_count, sizeof(int), hipMemcpyDeviceToHost, st));
-    h->last_xs_nq = nq; h->last_xs_route = route;
+// the steps the in-scan families share (the two forms of knn_search_excl_scan_locked, knn_range_search_locked):
+// the per-call bias array of a batch rule, at `off` of the exclusion workspace, in front of a scan that runs the biased instantiation
+static float* knn_launch_excl_scan_bias(radad_knn_t h, const ScanPlan& p, const unsigned long long* admit, size_t off, hipStream_t st) {
+    float* bias = reinterpret_cast<float*>((char*)h->excl_ws + off);
+    hipLaunchKernelGGL(k_excl_scan_bias, dim3((unsigned)ceil_div64(h->ntotal, 256)), dim3(256), 0, st, admit,
+                       (const float*)(p.mu ? h->rbias : (p.l2 ? h->ynorm : nullptr)), h->ntotal, bias);
+    return bias;
+}
+// the exact route answers the whole batch: every query is listed
+static void knn_launch_list_all(int* flag_sel, int* flag_count, int64_t nq, hipStream_t st) {
+    hipLaunchKernelGGL(k_excl_scan_list_all, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, st, flag_sel, flag_count, nq);
+}
+// the end of a call: how many queries the exact kernel answered, into the family's pinned slot for its read-back (radad_knn_last_excl_scan
+// / radad_knn_last_range; pinned memory: no synchronisation here)
+static int knn_post_exact_count(radad_knn_t h, int slot, const int* flag_count, hipStream_t st) {
+    RADAD_HIP_CHECK(hipMemcpyAsync(h->host_count + slot, flag_count, sizeof(int), hipMemcpyDeviceToHost, st));
     return RADAD_OK;
 }
 
-// ---- per-query exclusion sets on the certified tile scan (radad_knn_search_excl_scan_pq) ----------------------------------------------
-// Routes, facts, plan and scrub launches are knn_excl_scan_pq_plan's (knn_plan.h).  Tile route: the PLAIN search's preparation, scan
-// launches (early abandon included) and re-rank over widened candidate buffers, with k_excl_pq_scrub in front of every reader of the
-// sample's entries and of the candidate buffers (knn_scan_hi_tile); the queries the certificate rejects -- overflow of a buffer by a
-// large crowd among them -- go to the per-query exact kernel with the query tags.  Like the sibling above: KnnTuning is read (hi_skip)
-// and never written, no report is posted, no turn is taken.
-static int knn_search_excl_scan_pq_locked(radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, const ExclRule& r,
-                                          float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, hipStream_t st) {
+// One call, two routes (knn_excl_scan_route), two forms of the rule.  Neither consumes a certificate report, takes a turn off the
+// tuning state, looks before its exact pass or posts a report: KnnTuning is read (hi_skip) and otherwise left as it was found.
+//   one set for the batch   (radad_knn_search_excl_scan) the plan of the plain search over the handle's own facts; the bitmap and, on
+//                           the tile route, the NaN bias in front of the scan, which runs the biased instantiation; the listed queries
+//                           go to k_exact_scan_excl with the same bitmap;
+//   a set per query         (radad_knn_search_excl_scan_pq) routes, facts, plan and scrub launches are knn_excl_scan_pq_plan's
+//                           (knn_plan.h).  Tile route: the PLAIN search's preparation, scan launches (early abandon included) and
+//                           re-rank over widened candidate buffers, with k_excl_pq_scrub in front of every reader of the sample's
+//                           entries and of the candidate buffers (knn_scan_hi_tile); the queries the certificate rejects -- overflow
+//                           of a buffer by a large crowd among them -- go to k_exact_scan_excl_pq with the query tags.
+static int knn_search_excl_scan_locked(const char* fn, radad_knn_t h, const void* q_in, int q_dtype, int64_t nq, int k, const ExclRule& r,
+                                       float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, hipStream_t st) {
     int rc = knn_order_behind_last(h, st);
     if (rc) return rc;
-    ExclScanPqPlan X = knn_excl_scan_pq_plan(knn_store_facts(h), nq, k, r.m(), h->tune.hi_skip);
+    const bool pq = r.per_query;
+    // (one set for the batch: the sample geometry of the eligibility taken HERE stays the plan's when a plane that could not be
+    // allocated has the plan made again)
+    const TileEligibility t = knn_tile_eligibility(knn_store_facts(h), nq, k, KNN_MARGIN);
+    ExclScanPqPlan X;
+    auto make_plan = [&] {
+        if (pq) { X = knn_excl_scan_pq_plan(knn_store_facts(h), nq, k, r.m(), h->tune.hi_skip); return; }
+        X = ExclScanPqPlan();                                      // (no scrub launches, no phase count to hold the scan to)
+        X.facts = knn_store_facts(h);
+        X.route = knn_excl_scan_route(X.facts, nq, k, h->tune.hi_skip);
+        X.plan = knn_finish_plan(X.facts, nq, k, KNN_MARGIN, t, X.route == RADAD_EXCL_SCAN_TILE, false);
+    };
+    make_plan();
     bool tile = X.route == RADAD_EXCL_SCAN_TILE;
     if (tile && !knn_ensure_hi(h, st, true)) {                     // (a plane that cannot be allocated switches itself off: exact route)
         tile = false;
-        X = knn_excl_scan_pq_plan(knn_store_facts(h), nq, k, r.m(), h->tune.hi_skip);
-        RADAD_REQUIRE(X.route == RADAD_EXCL_SCAN_EXACT, "radad_knn_search_excl_scan_pq: a store without a plane planned the tile route");
+        make_plan();
+        RADAD_REQUIRE(X.route == RADAD_EXCL_SCAN_EXACT, "%s: a store without a plane planned the tile route", fn);
     }
     if (!tile && !knn_ensure_hi(h, st, false)) { radad_set_error("store statistics could not be computed"); return RADAD_EHIP; }
     ScanPlan p = X.plan;
-    p.mu = (p.hi_q && !h->f16) ? h->cmu : nullptr;                 // the plain search's instantiation (knn_plan_scan)
-    p.biased = p.hi_q && (p.l2 || p.mu);
+    p.mu = (p.hi_q && !h->f16) ? h->cmu : nullptr;                 // the plain search's instantiation (knn_plan_scan) ...
+    // ... (one set for the batch: the biased one whatever the plane -- RSC 0 / 1 run as RSC 3 / 2 with a zero bias for the admitted rows
+    // and a zero query constant: k_hi_rows writes mu.q' + |mu|^2 = 0 without a centre)
+    p.biased = p.hi_q && (!pq || p.l2 || p.mu);
     const SearchLayout L = knn_search_layout(X.facts, p, q_dtype);
-    if (L.bytes > h->ws_bytes) {
-        RADAD_HIP_CHECK(hipDeviceSynchronize());
-        rc = knn_workspace(h, L.bytes);
-        if (rc) return rc;
-    }
-    // m == 0: nothing is excluded and the tags may be NULL -- the per-query exact kernel reads a tag per row, so the rejected queries of
-    // such a call take the bitmap form with every bit set
-    const bool no_rule = r.m() == 0;
-    const ExclScanLayout B = knn_excl_scan_layout(X.facts, RADAD_EXCL_SCAN_EXACT);
-    if (no_rule) {
+    rc = knn_workspace(h, L.bytes);
+    if (rc) return rc;
+    // the admission bitmap, with the bias array behind it on the tile route: one set for the batch -- and m == 0, where nothing is
+    // excluded and the tags may be NULL: the per-query exact kernel reads a tag per row, so the rejected queries of such a call take
+    // the bitmap form with every bit set
+    const bool bitmap = !pq || r.m() == 0;
+    const ExclScanLayout B = knn_excl_scan_layout(X.facts, pq ? RADAD_EXCL_SCAN_EXACT : X.route);
+    if (bitmap) {
         rc = knn_excl_reserve(h, B.bytes);
         if (rc) return rc;
     }
@@ -4488,23 +4442,33 @@ static int knn_search_excl_scan_pq_locked(radad_knn_t h, const void* q_in, int q
     if (rc) return rc;
     h->last_emit_nq = 0;                                           // (the workspace no longer holds the last plain tile scan's counters)
     h->last_xs_nq = 0;
-    unsigned long long* admit = no_rule ? reinterpret_cast<unsigned long long*>((char*)h->excl_ws + B.admit) : nullptr;
-    if (no_rule) RADAD_HIP_CHECK(hipMemsetAsync(admit, 0xff, (size_t)B.n_words * sizeof(unsigned long long), st));
+    unsigned long long* admit = bitmap ? reinterpret_cast<unsigned long long*>((char*)h->excl_ws + B.admit) : nullptr;
+    if (bitmap) {
+        rc = knn_admit_bitmap(h, r, nullptr, admit, B.n_words, st);
+        if (rc) return rc;
+    }
     const float* q_use = knn_prepare_queries(h, p, L, q_in, q_dtype, st);      // (clears the listed-query counter and the candidate counters)
     RADAD_HIP_CHECK(hipGetLastError());
     int* flag_count = ws_at<int>(h, L.fcount);
     int* flag_sel = ws_at<int>(h, L.fsel);
 
     if (tile) {
+        // the plain search's scan, re-rank and certificate: over the admitted rows (one set for the batch: the bias array), or with the
+        // scrub launches between the scan's (a set per query)
+        float* bias = nullptr;
+        if (!pq) {
+            bias = knn_launch_excl_scan_bias(h, p, admit, B.bias, st);
+            RADAD_HIP_CHECK(hipGetLastError());
+        }
         ScanScrub scrub;
         scrub.rule = &r; scrub.grid = X.scrub_grid;
         h->prof.next_search();
-        rc = knn_scan_hi_tile(h, p, L, st, nullptr, X.scrub_launches > 0 ? &scrub : nullptr);
+        rc = knn_scan_hi_tile(h, p, L, st, bias, X.scrub_launches > 0 ? &scrub : nullptr);
         if (rc) return rc;
         RADAD_HIP_CHECK(hipGetLastError());
-        RADAD_REQUIRE(scrub.launched == X.scrub_launches && h->last_scan_phases == X.phases,
-                      "radad_knn_search_excl_scan_pq: %d scrub launches over %d phases, planned %d over %d", scrub.launched, h->last_scan_phases,
-                      X.scrub_launches, X.phases);
+        RADAD_REQUIRE(!pq || (scrub.launched == X.scrub_launches && h->last_scan_phases == X.phases),
+                      "%s: %d scrub launches over %d phases, planned %d over %d", fn, scrub.launched, h->last_scan_phases, X.scrub_launches,
+                      X.phases);
         SearchCtx c;
         c.valid = true;
         c.nq = nq; c.k = k; c.l2 = p.l2; c.n_parts = p.n_parts; c.plen = p.plen; c.cap = p.cap; c.xgroup = p.xgroup;
@@ -4515,42 +4479,32 @@ static int knn_search_excl_scan_pq_locked(radad_knn_t h, const void* q_in, int q
         hipLaunchKernelGGL(k_excl_scan_pad, dim3((unsigned)ceil_div64(nq * k, 256)), dim3(256), 0, st, out_dist_dev, (const int64_t*)out_idx_dev,
                            out_key_dev, nq * k);
     } else {
-        hipLaunchKernelGGL(k_excl_scan_list_all, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, st, flag_sel, flag_count, nq);
+        knn_launch_list_all(flag_sel, flag_count, nq, st);
     }
     RADAD_HIP_CHECK(hipGetLastError());
 
-    // ---- the listed queries: the float64 exact kernel with each query's own tags, sized and driven by the device-side count; no report
-    {
-        ExactParams x;
-        x.db = h->rows; x.db_f16 = h->f16; x.q = q_use; x.sel = flag_sel; x.count = flag_count;
-        x.n = h->ntotal; x.dim = h->dim; x.k = k; x.l2 = p.l2; x.group = p.xgroup;
-        x.slice_rows = ceil_div64(h->ntotal, KX_SLICES);
-        x.pkey = ws_at<double>(h, L.xk); x.pidx = ws_at<int>(h, L.xi); x.id_base = h->id_base;
-        x.out_dist = out_dist_dev; x.out_idx = out_idx_dev; x.out_key = out_key_dev;
-        x.host_stats = nullptr;
-        x.arrive = h->xarrive;
-        if (no_rule) x.admit = admit;
-        else { x.row_tags = r.tags; x.q_tags = r.q_tags; x.q_cnt = r.q_cnt; x.m = r.m(); }
-        const auto kern = no_rule ? k_exact_scan_excl : k_exact_scan_excl_pq;
-        const size_t xlds = knn_exact_dyn_lds_bytes(h->dim, k);
-        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
-        const unsigned gy = k <= KNN_F16_MAX_K ? KX_GROUPS_Y : 8 * KX_GROUPS_Y;
-        x.nslots = (int)knn_exact_slots(nq, k, p.xgroup);
-        for (int64_t s0 = 0; s0 < nq; s0 += x.nslots) {            // (launches past the device-side count leave at once)
-            x.slot0 = (int)s0;
-            hipLaunchKernelGGL(kern, dim3(KX_SLICES, gy), dim3(KX_THREADS), xlds, st, x);
-        }
-        RADAD_HIP_CHECK(hipGetLastError());
-    }
-    RADAD_HIP_CHECK(hipMemcpyAsync(h->host_count + 17, flag_count, sizeof(int), hipMemcpyDeviceToHost, st));
+    // ---- the listed queries (tile route: the ones the certificate rejected): the ROW-FILTERED float64 exact kernel, by the bitmap or
+    // with each query's own tags.  No report.
+    ExactParams x;
+    x.q = q_use; x.sel = flag_sel; x.count = flag_count; x.l2 = p.l2;
+    x.pkey = ws_at<double>(h, L.xk); x.pidx = ws_at<int>(h, L.xi);
+    x.group = p.xgroup; x.nslots = (int)knn_exact_slots(nq, k, p.xgroup);
+    x.out_dist = out_dist_dev; x.out_idx = out_idx_dev; x.out_key = out_key_dev;
+    if (bitmap) x.admit = admit;
+    else { x.row_tags = r.tags; x.q_tags = r.q_tags; x.q_cnt = r.q_cnt; x.m = r.m(); }
+    rc = knn_launch_exact(h, bitmap ? k_exact_scan_excl : k_exact_scan_excl_pq, x, nq, k, st);
+    if (rc) return rc;
+    rc = knn_post_exact_count(h, h->HC_XS_EXACT, flag_count, st);
+    if (rc) return rc;
     h->last_xs_nq = nq; h->last_xs_route = tile ? RADAD_EXCL_SCAN_TILE : RADAD_EXCL_SCAN_EXACT;
     return RADAD_OK;
 }
 
 // ---- certified range search (radad_knn_range_search) ------------------------------------------------------------------------------
 // Route, facts, plan and the one scan launch are knn_range_plan's (knn_plan.h).  Tile route: the PLAIN search's preparation, RSC and
-// bias (as knn_search_excl_scan_pq_locked), k_range_floor into the search's floor array, one scan launch from those floors (early
-// abandon included), k_range_refine; the queries whose buffer overflowed go, driven from the device, to the exact range kernel.
+// bias (as the per-query form of knn_search_excl_scan_locked), k_range_floor into the search's floor array, one scan launch from
+// those floors (early abandon included), k_range_refine; the queries whose buffer overflowed go, driven from the device, to the exact
+// range kernel.
 // Stream route (RADAD_KNN_OPT_RANGE_SMALLQ, <= 16 queries): the small-batch search's preparation and eps, the same floors, ONE launch of
 // k_range_hi_smallq into the same buffers, and everything behind the scan as on the tile route -- but for the re-rank's re-score,
 // which takes its sums in the exact kernel's order (k_range_refine<.., true>): the keys are the exact route's bit for bit.
@@ -4592,11 +4546,8 @@ static int knn_range_search_locked(const char* fn, radad_knn_t h, const void* q_
     if (!batch) p.biased = p.hi_q && (p.l2 || p.mu);               // ... (one set for the batch: the biased one whatever the plane, the plan's)
     RADAD_REQUIRE(!(tile || stream) || p.emit_cap <= RG_MAX_CAP, "%s: %d-entry candidate buffers exceed the re-rank's %d", fn, p.emit_cap, RG_MAX_CAP);
     const SearchLayout L = knn_search_layout(X.facts, p, q_dtype);
-    if (L.bytes > h->ws_bytes) {
-        RADAD_HIP_CHECK(hipDeviceSynchronize());
-        rc = knn_workspace(h, L.bytes);
-        if (rc) return rc;
-    }
+    rc = knn_workspace(h, L.bytes);
+    if (rc) return rc;
     // the exact pass's partial lists, k = m; one set for the batch: the bitmap and the bias array behind them
     const RangeExclLayout E = knn_range_excl_layout(X.facts, nq, m, X.route);
     const RangeLayout B = E.lists;
@@ -4607,14 +4558,10 @@ static int knn_range_search_locked(const char* fn, radad_knn_t h, const void* q_
     h->last_emit_nq = 0;                                           // (the workspace no longer holds the last plain tile scan's counters)
     h->last_xs_nq = 0;
     h->last_rg_nq = 0;
-    // one set for the batch: the admission bitmap (all ones when nothing is excluded: the tags may be NULL then)
     unsigned long long* admit = batch ? reinterpret_cast<unsigned long long*>((char*)h->excl_ws + E.admit) : nullptr;
     if (batch) {
-        if (rule->n_excl > 0)
-            hipLaunchKernelGGL(k_admit_bitmap<false>, dim3((unsigned)ceil_div64(E.n_words * 64, 256)), dim3(256), 0, st, rule->tags,
-                               (const int64_t*)nullptr, h->ntotal, rule->excl, rule->n_excl, (const int*)nullptr, admit, E.n_words);
-        else
-            RADAD_HIP_CHECK(hipMemsetAsync(admit, 0xff, (size_t)E.n_words * sizeof(unsigned long long), st));
+        rc = knn_admit_bitmap(h, *rule, nullptr, admit, E.n_words, st);
+        if (rc) return rc;
     }
     const float* q_use = knn_prepare_queries(h, p, L, q_in, q_dtype, st);      // (clears the listed-query counter and the candidate counters)
     RADAD_HIP_CHECK(hipGetLastError());
@@ -4623,12 +4570,7 @@ static int knn_range_search_locked(const char* fn, radad_knn_t h, const void* q_
 
     if (tile || stream) {
         // one set for the batch: the per-call bias, NaN for the rows the bitmap does not admit (no compare of the scan passes a NaN)
-        float* bias = nullptr;
-        if (batch) {
-            bias = reinterpret_cast<float*>((char*)h->excl_ws + E.bias);
-            hipLaunchKernelGGL(k_excl_scan_bias, dim3((unsigned)ceil_div64(h->ntotal, 256)), dim3(256), 0, st, (const unsigned long long*)admit,
-                               (const float*)(p.mu ? h->rbias : (p.l2 ? h->ynorm : nullptr)), h->ntotal, bias);
-        }
+        float* bias = batch ? knn_launch_excl_scan_bias(h, p, admit, E.bias, st) : nullptr;
         // scan scores estimate q.y (IP / cosine) or -|q - y|^2 (L2): the threshold in their units
         float* floors = ws_at<float>(h, L.thr);
         hipLaunchKernelGGL(k_range_floor, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, st, ws_at<const float>(h, L.eps),
@@ -4663,40 +4605,41 @@ static int knn_range_search_locked(const char* fn, radad_knn_t h, const void* q_
         h->prof.end(st);
     } else {
         RADAD_HIP_CHECK(hipMemsetAsync(out_count_dev, 0, (size_t)nq * sizeof(int32_t), st));
-        hipLaunchKernelGGL(k_excl_scan_list_all, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, st, flag_sel, flag_count, nq);
+        knn_launch_list_all(flag_sel, flag_count, nq, st);
     }
     RADAD_HIP_CHECK(hipGetLastError());
 
-    // ---- the listed queries (tile and stream routes: k_range_refine zeroed their counts): the float64 exact range kernel, sized and driven by the
-    // device-side count; no report
-    {
-        ExactParams x;
-        x.db = h->rows; x.db_f16 = h->f16; x.q = q_use; x.sel = flag_sel; x.count = flag_count;
-        x.n = h->ntotal; x.dim = h->dim; x.k = m; x.l2 = p.l2; x.group = B.xgroup;
-        x.slice_rows = ceil_div64(h->ntotal, KX_SLICES);
-        x.pkey = reinterpret_cast<double*>((char*)h->excl_ws + B.xk); x.pidx = reinterpret_cast<int*>((char*)h->excl_ws + B.xi);
-        x.id_base = h->id_base;
-        x.out_dist = out_dist_dev; x.out_idx = out_idx_dev; x.out_key = out_key_dev;
-        x.host_stats = nullptr;
-        x.arrive = h->xarrive;
-        x.out_count = out_count_dev;
-        x.range_t = p.l2 ? -(double)radius : (double)radius;
-        if (batch) x.admit = admit;
-        if (pq) { x.row_tags = rule->tags; x.q_tags = rule->q_tags; x.q_cnt = rule->q_cnt; x.m = rule->m(); }
-        const auto kern = batch ? k_exact_scan_range_excl : pq ? k_exact_scan_range_excl_pq : k_exact_scan_range;
-        const size_t xlds = knn_exact_dyn_lds_bytes(h->dim, m);      // (with the static arrival flag <= KX_LDS_MAX: the entry point checked)
-        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xlds));
-        const unsigned gy = m <= KNN_F16_MAX_K ? KX_GROUPS_Y : 8 * KX_GROUPS_Y;
-        x.nslots = (int)B.xslots;
-        for (int64_t s0 = 0; s0 < nq; s0 += x.nslots) {            // (launches past the device-side count leave at once)
-            x.slot0 = (int)s0;
-            hipLaunchKernelGGL(kern, dim3(KX_SLICES, gy), dim3(KX_THREADS), xlds, st, x);
-        }
-        RADAD_HIP_CHECK(hipGetLastError());
-    }
-    RADAD_HIP_CHECK(hipMemcpyAsync(h->host_count + 18, flag_count, sizeof(int), hipMemcpyDeviceToHost, st));
+    // ---- the listed queries (tile and stream routes: k_range_refine zeroed their counts): the float64 exact range kernel at k = m,
+    // its partial lists in the exclusion workspace; no report
+    ExactParams x;
+    x.q = q_use; x.sel = flag_sel; x.count = flag_count; x.l2 = p.l2;
+    x.pkey = reinterpret_cast<double*>((char*)h->excl_ws + B.xk); x.pidx = reinterpret_cast<int*>((char*)h->excl_ws + B.xi);
+    x.group = B.xgroup; x.nslots = (int)B.xslots;
+    x.out_dist = out_dist_dev; x.out_idx = out_idx_dev; x.out_key = out_key_dev;
+    x.out_count = out_count_dev;
+    x.range_t = p.l2 ? -(double)radius : (double)radius;
+    if (batch) x.admit = admit;
+    if (pq) { x.row_tags = rule->tags; x.q_tags = rule->q_tags; x.q_cnt = rule->q_cnt; x.m = rule->m(); }
+    rc = knn_launch_exact(h, batch ? k_exact_scan_range_excl : pq ? k_exact_scan_range_excl_pq : k_exact_scan_range, x, nq, m, st);
+    if (rc) return rc;
+    rc = knn_post_exact_count(h, h->HC_RG_EXACT, flag_count, st);
+    if (rc) return rc;
     h->last_rg_nq = nq; h->last_rg_route = tile ? RADAD_RANGE_TILE : stream ? RADAD_RANGE_STREAM : RADAD_RANGE_EXACT;
     return RADAD_OK;
+}
+
+// the four top-k exclusion calls behind their own argument checks (as knn_range_search_entry for the range calls): in_scan = the
+// admission test inside the tile scan (k_fetch is not used), else the two-pass search at k_fetch
+static int knn_excl_search_entry(const char* fn, radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, int k_fetch, bool in_scan,
+                                 const ExclRule& r, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, void* stream) {
+    if (nq == 0) return RADAD_OK;
+    RADAD_REQUIRE(q_dev && out_dist_dev && out_idx_dev, "%s: NULL buffer", fn);
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "%s: a radad_knn_search_begin on this handle has not been finished", fn);
+    if (h->ntotal == 0) { radad_set_error("%s: the store is empty", fn); return RADAD_ESTATE; }
+    if (in_scan) return knn_search_excl_scan_locked(fn, h, q_dev, q_dtype, nq, k, r, out_dist_dev, out_idx_dev, out_key_dev, (hipStream_t)stream);
+    return knn_search_excl_locked(h, q_dev, q_dtype, nq, k, k_fetch, r, out_dist_dev, out_idx_dev, out_key_dev, (hipStream_t)stream);
 }
 
 extern "C" {
@@ -4743,65 +4686,45 @@ int radad_knn_search_finish(radad_knn_t h, const float* global_lower_bound_dev, 
 int radad_knn_search_excl(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* row_tags_dev,
                           const int64_t* excl_sorted_dev, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
                           void* stream) {
-    const int bad = knn_excl_check_args("radad_knn_search_excl", h, q_dtype, nq, 0, k, k_fetch, row_tags_dev, excl_sorted_dev, n_excl);
+    const char* fn = "radad_knn_search_excl";
+    const int bad = knn_excl_check_args(fn, h, q_dtype, nq, 0, k, k_fetch, row_tags_dev, excl_sorted_dev, n_excl);
     if (bad) return bad;
-    if (nq == 0) return RADAD_OK;
-    RADAD_REQUIRE(q_dev && out_dist_dev && out_idx_dev, "radad_knn_search_excl: NULL buffer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard g(h->device);
-    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_search_excl: a radad_knn_search_begin on this handle has not been finished");
-    if (h->ntotal == 0) { radad_set_error("radad_knn_search_excl: the store is empty"); return RADAD_ESTATE; }
-    return knn_search_excl_locked(h, q_dev, q_dtype, nq, k, k_fetch, knn_excl_rule_batch(row_tags_dev, excl_sorted_dev, n_excl), out_dist_dev,
-                                  out_idx_dev, out_key_dev, (hipStream_t)stream);
+    return knn_excl_search_entry(fn, h, q_dev, q_dtype, nq, k, k_fetch, false, knn_excl_rule_batch(row_tags_dev, excl_sorted_dev, n_excl),
+                                 out_dist_dev, out_idx_dev, out_key_dev, stream);
 }
 
 int radad_knn_search_excl_pq(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, int k_fetch, const int64_t* row_tags_dev,
                              const int64_t* q_tags_dev, int m, const int32_t* q_tag_counts_dev, float* out_dist_dev, int64_t* out_idx_dev,
                              double* out_key_dev, void* stream) {
-    int bad = knn_excl_check_args("radad_knn_search_excl_pq", h, q_dtype, nq, 0, k, k_fetch, nullptr, nullptr, 0);
+    const char* fn = "radad_knn_search_excl_pq";
+    int bad = knn_excl_check_args(fn, h, q_dtype, nq, 0, k, k_fetch, nullptr, nullptr, 0);
     if (bad) return bad;
     ExclRule r;
-    bad = knn_excl_pq_rule("radad_knn_search_excl_pq", row_tags_dev, q_tags_dev, m, q_tag_counts_dev, &r);
+    bad = knn_excl_pq_rule(fn, row_tags_dev, q_tags_dev, m, q_tag_counts_dev, &r);
     if (bad) return bad;
-    if (nq == 0) return RADAD_OK;
-    RADAD_REQUIRE(q_dev && out_dist_dev && out_idx_dev, "radad_knn_search_excl_pq: NULL buffer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard g(h->device);
-    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_search_excl_pq: a radad_knn_search_begin on this handle has not been finished");
-    if (h->ntotal == 0) { radad_set_error("radad_knn_search_excl_pq: the store is empty"); return RADAD_ESTATE; }
-    return knn_search_excl_locked(h, q_dev, q_dtype, nq, k, k_fetch, r, out_dist_dev, out_idx_dev, out_key_dev, (hipStream_t)stream);
+    return knn_excl_search_entry(fn, h, q_dev, q_dtype, nq, k, k_fetch, false, r, out_dist_dev, out_idx_dev, out_key_dev, stream);
 }
 
 int radad_knn_search_excl_scan(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, const int64_t* row_tags_dev,
                                const int64_t* excl_sorted_dev, int64_t n_excl, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev,
                                void* stream) {
-    const int bad = knn_excl_check_args("radad_knn_search_excl_scan", h, q_dtype, nq, 0, k, k, row_tags_dev, excl_sorted_dev, n_excl);
+    const char* fn = "radad_knn_search_excl_scan";
+    const int bad = knn_excl_check_args(fn, h, q_dtype, nq, 0, k, k, row_tags_dev, excl_sorted_dev, n_excl);
     if (bad) return bad;
-    if (nq == 0) return RADAD_OK;
-    RADAD_REQUIRE(q_dev && out_dist_dev && out_idx_dev, "radad_knn_search_excl_scan: NULL buffer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard g(h->device);
-    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_search_excl_scan: a radad_knn_search_begin on this handle has not been finished");
-    if (h->ntotal == 0) { radad_set_error("radad_knn_search_excl_scan: the store is empty"); return RADAD_ESTATE; }
-    return knn_search_excl_scan_locked(h, q_dev, q_dtype, nq, k, knn_excl_rule_batch(row_tags_dev, excl_sorted_dev, n_excl), out_dist_dev,
-                                       out_idx_dev, out_key_dev, (hipStream_t)stream);
+    return knn_excl_search_entry(fn, h, q_dev, q_dtype, nq, k, k, true, knn_excl_rule_batch(row_tags_dev, excl_sorted_dev, n_excl),
+                                 out_dist_dev, out_idx_dev, out_key_dev, stream);
 }
 
 int radad_knn_search_excl_scan_pq(radad_knn_t h, const void* q_dev, int q_dtype, int64_t nq, int k, const int64_t* row_tags_dev,
                                   const int64_t* q_tags_dev, int m, const int32_t* q_tag_counts_dev, float* out_dist_dev, int64_t* out_idx_dev,
                                   double* out_key_dev, void* stream) {
-    int bad = knn_excl_check_args("radad_knn_search_excl_scan_pq", h, q_dtype, nq, 0, k, k, nullptr, nullptr, 0);
+    const char* fn = "radad_knn_search_excl_scan_pq";
+    int bad = knn_excl_check_args(fn, h, q_dtype, nq, 0, k, k, nullptr, nullptr, 0);
     if (bad) return bad;
     ExclRule r;
-    bad = knn_excl_pq_rule("radad_knn_search_excl_scan_pq", row_tags_dev, q_tags_dev, m, q_tag_counts_dev, &r);
+    bad = knn_excl_pq_rule(fn, row_tags_dev, q_tags_dev, m, q_tag_counts_dev, &r);
     if (bad) return bad;
-    if (nq == 0) return RADAD_OK;
-    RADAD_REQUIRE(q_dev && out_dist_dev && out_idx_dev, "radad_knn_search_excl_scan_pq: NULL buffer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard g(h->device);
-    RADAD_REQUIRE(!h->pending.valid && !h->pending_excl.valid, "radad_knn_search_excl_scan_pq: a radad_knn_search_begin on this handle has not been finished");
-    if (h->ntotal == 0) { radad_set_error("radad_knn_search_excl_scan_pq: the store is empty"); return RADAD_ESTATE; }
-    return knn_search_excl_scan_pq_locked(h, q_dev, q_dtype, nq, k, r, out_dist_dev, out_idx_dev, out_key_dev, (hipStream_t)stream);
+    return knn_excl_search_entry(fn, h, q_dev, q_dtype, nq, k, k, true, r, out_dist_dev, out_idx_dev, out_key_dev, stream);
 }
 
 // the three range calls behind their own argument checks: rule NULL = nothing is excluded
@@ -4869,7 +4792,7 @@ int radad_knn_last_range(radad_knn_t h, int64_t* n_queries, int* route, int* n_e
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
     RADAD_HIP_CHECK(knn_wait_last_search(h));
-    *n_exact = h->last_rg_nq > 0 ? *reinterpret_cast<volatile int*>(h->host_count + 18) : 0;
+    *n_exact = h->last_rg_nq > 0 ? *reinterpret_cast<volatile int*>(h->host_count + h->HC_RG_EXACT) : 0;
     *route = h->last_rg_route;
     if (n_queries) *n_queries = h->last_rg_nq;
     return RADAD_OK;
@@ -4880,7 +4803,7 @@ int radad_knn_last_excl_scan(radad_knn_t h, int64_t* n_queries, int* route, int*
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
     RADAD_HIP_CHECK(knn_wait_last_search(h));
-    *n_exact = h->last_xs_nq > 0 ? *reinterpret_cast<volatile int*>(h->host_count + 17) : 0;
+    *n_exact = h->last_xs_nq > 0 ? *reinterpret_cast<volatile int*>(h->host_count + h->HC_XS_EXACT) : 0;
     *route = h->last_xs_route;
     if (n_queries) *n_queries = h->last_xs_nq;
     return RADAD_OK;
