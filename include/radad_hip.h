@@ -926,6 +926,43 @@ int64_t radad_projection_workspace_bytes(int64_t batch, int k, int dim, int hidd
 int radad_projection_fold(const radad_proj_weights* w, int dim, int hidden, float* w54t_out_dev, float* b54_out_dev,
                           int device, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * ProjectionLayer training forward and backward (projection.py:68-106 under autograd; csrc/proj_train.inc).
+ *   forward:  p = W1 x + b1, t = tanh p, s = W2 t + b2, a = softmax_K s           (:69-71, :87)
+ *             q = W3 x + b3, h = relu q, hbar = sum_K a h, u = W4 hbar + b4       (:74-76, :88-89; sum_K taken before W4)
+ *             v = W5 u + b5, xh = LN-normalised v, n = xh g + beta                 (:94-99; biased variance, eps 1e-6)
+ *             out = W6 (n * mask * inv_keep) + b6                                  (:100-101; dropout by the caller's mask)
+ *   backward: the gradient of out with respect to all 14 parameters and, when asked for, x.
+ * The fold pointers w54t / b54 of radad_proj_weights are ignored: the weights move every step.
+ * mask_dev [B,H] holds 0 / 1 floats drawn by the caller; NULL means no dropout (inv_keep is then ignored).
+ * The forward fills the saved-activation buffers, the backward reads them (with the same x, weights, mask and inv_keep).
+ * A NULL pointer in radad_proj_grads skips that gradient (dw1 and dw3 come from one product: both or neither); dx_dev NULL
+ * skips the input gradient.  No float atomics: every sum has a fixed order, two runs give the same bits.
+ * Shapes as the inference forward (any dim, any 4-byte-aligned pointers); limits, each one RADAD_EINVAL: hidden and
+ * out_dim <= 4096, dim <= 2^22 - 64, batch * k < 2^31 - 128, and the inference tail's LDS bound on k * hidden.  batch == 0 is
+ * RADAD_OK without a launch.  One workspace size serves both calls; -1 for a bad shape.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct radad_proj_saved {
+    float *t, *h;               /* tanh(p), relu(q)  [B*K, H]      */
+    float *a;                   /* softmax weights   [B*K]         */
+    float *hbar;                /* sum_K a h         [B, H]        */
+    float *u;                   /* W4 hbar + b4      [B, D]        */
+    float *xh;                  /* normalised v      [B, H]        */
+    float *rstd;                /* 1 / sqrt(var+eps) [B]           */
+} radad_proj_saved;
+typedef struct radad_proj_grads {   /* shapes of the matching radad_proj_weights members */
+    float *dw1, *db1, *dw2, *db2, *dw3, *db3, *dw4, *db4, *dw5, *db5, *dln_g, *dln_b, *dw6, *db6;
+} radad_proj_grads;
+int64_t radad_projection_train_workspace_bytes(int64_t batch, int k, int dim, int hidden, int out_dim);
+int radad_projection_train_forward(const radad_proj_weights* w, const float* x_dev /*[B,K,D]*/, const float* mask_dev /*[B,H] or NULL*/,
+                                   float inv_keep /* 1/(1-p) */, int64_t batch, int k, int dim, int hidden, int out_dim,
+                                   const radad_proj_saved* saved, float* out_dev /*[B,O]*/, float* workspace_dev,
+                                   int64_t workspace_bytes, int device, void* stream);
+int radad_projection_backward(const radad_proj_weights* w, const float* x_dev, const float* mask_dev, float inv_keep,
+                              const radad_proj_saved* saved, const float* grad_out_dev /*[B,O] contiguous*/, int64_t batch, int k,
+                              int dim, int hidden, int out_dim, const radad_proj_grads* grads, float* dx_dev /*[B,K,D] or NULL*/,
+                              float* workspace_dev, int64_t workspace_bytes, int device, void* stream);
+
 /* out[r, :] = act(W x[r, :] + bias)   nn.Linear forward, W [out_features, in_features] with row stride ldw;
  * act 0 none / 1 tanh / 2 relu; bias_dev may be NULL.  Split-K MFMA GEMM (few rows x wide in_features still fills
  * the chip).  Any in_features, any strides with ldx, ldw >= in_features and ldo >= out_features, any 4-byte-aligned

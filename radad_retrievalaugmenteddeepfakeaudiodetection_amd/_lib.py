@@ -49,6 +49,17 @@ class ProjWeights(C.Structure):
                                           "ln_g", "ln_b", "w6", "b6", "w54t", "b54")]
 
 
+class ProjSaved(C.Structure):      # radad_proj_saved: what the training forward keeps for the backward
+    _fields_ = [(n, C.c_void_p) for n in ("t", "h", "a", "hbar", "u", "xh", "rstd")]
+
+
+PROJ_GRAD_NAMES = ("dw1", "db1", "dw2", "db2", "dw3", "db3", "dw4", "db4", "dw5", "db5", "dln_g", "dln_b", "dw6", "db6")
+
+
+class ProjGrads(C.Structure):      # radad_proj_grads, in the order of ProjWeights' first 14 members
+    _fields_ = [(n, C.c_void_p) for n in PROJ_GRAD_NAMES]
+
+
 HEAD_MAX_LAYERS = 6
 
 
@@ -191,6 +202,13 @@ SIGNATURES = {
     "radad_projection_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
     "radad_projection_fold": (C.c_int, [C.POINTER(ProjWeights), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                         C.c_void_p]),
+    "radad_projection_train_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "radad_projection_train_forward": (C.c_int, [C.POINTER(ProjWeights), C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_int,
+                                                 C.c_int, C.c_int, C.c_int, C.POINTER(ProjSaved), C.c_void_p, C.c_void_p,
+                                                 C.c_int64, C.c_int, C.c_void_p]),
+    "radad_projection_backward": (C.c_int, [C.POINTER(ProjWeights), C.c_void_p, C.c_void_p, C.c_float, C.POINTER(ProjSaved),
+                                            C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ProjGrads),
+                                            C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "radad_linear_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64,
                                        C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int,
                                        C.c_void_p]),

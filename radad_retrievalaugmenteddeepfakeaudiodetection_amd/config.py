@@ -34,6 +34,7 @@ class Config:
         self.use_mixed_precision = False
         self.use_gradient_checkpointing = False
         self.fuse_attention_ops = True
+        self.projection_train_hip = False   # True: a training-mode forward runs the HIP forward + backward (csrc/proj_train.inc) instead of raising "inference-only"
         # detection head (config.py:63, 82-86; the later assignment of detection_dropout wins there too)
         self.detection_hidden_dims = [64, 32]
         self.detection_dropout = 0.1

@@ -493,3 +493,5 @@ int radad_fuse_head_forward(const radad_head_weights* w, const float* tpp_dev, c
 }
 
 }  // extern "C"
+
+#include "proj_train.inc"

@@ -5,8 +5,10 @@ state_dict trained with the reference loads unchanged (the unfused layout of pro
 nn.Sequential -- is renamed on load, and written back under those names by a layer configured with fuse_attention_ops=False):
     attention_score [H,D]  attention_final [1,H]  cst_hidden [H,D]  cst_output [D,H]
     weight_sum [H,D]  normalization (LayerNorm H, eps 1e-6)  unified_embedding [O,H]
-forward([B,K,D]) -> [B,O] runs csrc/proj.hip (eval semantics: dropout is the identity).  Training stays in
-the reference; a forward that needs gradients raises instead of silently falling back.
+forward([B,K,D]) -> [B,O] runs csrc/proj.hip (eval semantics: dropout is the identity).  Training is opt-in: with
+`config.projection_train_hip = True` a training-mode forward that needs gradients goes through `_ProjectionTrainFn`, whose
+forward and backward are the HIP kernels of csrc/proj_train.inc (fp32; under autocast the inputs are cast to fp32).  With the
+default (False) such a forward raises instead of silently falling back, and training stays in the reference.
 """
 import ctypes as C
 
@@ -14,6 +16,108 @@ from . import _lib
 
 import torch
 import torch.nn as nn
+
+
+_PARAM_ORDER = (("attention_score", "weight"), ("attention_score", "bias"), ("attention_final", "weight"), ("attention_final", "bias"),
+                ("cst_hidden", "weight"), ("cst_hidden", "bias"), ("cst_output", "weight"), ("cst_output", "bias"),
+                ("weight_sum", "weight"), ("weight_sum", "bias"), ("normalization", "weight"), ("normalization", "bias"),
+                ("unified_embedding", "weight"), ("unified_embedding", "bias"))     # the order of radad_proj_weights / radad_proj_grads
+_WEIGHT_FIELDS = ("w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4", "w5", "b5", "ln_g", "ln_b", "w6", "b6")
+
+
+def _train_workspace(lib, x, B, K, D, H, O):
+    need = lib.radad_projection_train_workspace_bytes(B, K, D, H, O)
+    if need < 0:
+        raise ValueError(f"projection training: shape B={B} K={K} D={D} H={H} O={O} is outside the kernels' limits")
+    return torch.empty(max(int(need), 1), dtype=torch.uint8, device=x.device)
+
+
+def _check_train_inputs(x, mask, params):
+    """TypeError / ValueError unless x [B,K,D], the 14 parameters and the mask are float32 tensors on one ROCm device with the
+    shapes the kernels index by."""
+    if len(params) != len(_PARAM_ORDER):
+        raise ValueError(f"expected {len(_PARAM_ORDER)} parameters, got {len(params)}")
+    _lib.require_cuda(x, "input_embeddings")
+    if x.dim() != 3:
+        raise ValueError(f"expected [B, K, D], got {tuple(x.shape)}")
+    B, K, D = x.shape
+    if params[0].dim() != 2 or params[12].dim() != 2:
+        raise ValueError("attention_score.weight and unified_embedding.weight must be matrices")
+    H, O = params[0].shape[0], params[12].shape[0]
+    want = ((H, D), (H,), (1, H), (1,), (H, D), (H,), (D, H), (D,), (H, D), (H,), (H,), (H,), (O, H), (O,))
+    named = [("input_embeddings", x, (B, K, D))] + [(f"{m}.{leaf}", p, sh) for (m, leaf), p, sh in zip(_PARAM_ORDER, params, want)]
+    if mask is not None:
+        named.append(("dropout mask", mask, (B, H)))
+    for name, t, shape in named:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"{name} must be a float32 tensor (cast with .float(); ProjectionLayer.forward does), got "
+                            f"{getattr(t, 'dtype', type(t))}")
+        if t.device != x.device:
+            raise ValueError(f"{name} is on {t.device}, input_embeddings on {x.device}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+
+
+class _ProjectionTrainFn(torch.autograd.Function):
+    """projection.py:68-106 with a hand-written backward (csrc/proj_train.inc).  fp32: under autocast the inputs are cast to
+    fp32 and the output is fp32 (the reference trains under autocast + GradScaler, pipeline.py:784-829).
+    apply(x [B,K,D], mask [B,H] of 0/1 or None, inv_keep, *the 14 parameters in _PARAM_ORDER) -> out [B,O].  Every tensor must be
+    float32 (checked: TypeError otherwise); ProjectionLayer._train_forward casts before it calls.  A parameter that needs no
+    gradient is not computed (NULL in radad_proj_grads); with all of the score and cst branch frozen and no dx, that branch of the
+    backward is not run at all."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, x, mask, inv_keep, *params):
+        lib = _lib.load()
+        _check_train_inputs(x, mask, params)        # the kernels take raw pointers: dtype, device and every shape are checked here
+        x = x.contiguous()
+        params = tuple(p.contiguous() for p in params)
+        mask = None if mask is None else mask.contiguous()
+        B, K, D = x.shape
+        H, O = params[0].shape[0], params[12].shape[0]
+        M = B * K
+        new = lambda *shape: torch.empty(shape, device=x.device, dtype=torch.float32)
+        saved = (new(M, H), new(M, H), new(M), new(B, H), new(B, D), new(B, H), new(B))     # t, h, a, hbar, u, xh, rstd
+        out = new(B, O)
+        ws = _train_workspace(lib, x, B, K, D, H, O)
+        w = _lib.ProjWeights(**{f: p.data_ptr() for f, p in zip(_WEIGHT_FIELDS, params)})
+        sv = _lib.ProjSaved(*[t.data_ptr() for t in saved])
+        with torch.cuda.device(x.device):
+            _lib.check(lib.radad_projection_train_forward(C.byref(w), x.data_ptr(), mask.data_ptr() if mask is not None else None,
+                                                          float(inv_keep), B, K, D, H, O, C.byref(sv), out.data_ptr(),
+                                                          ws.data_ptr(), int(ws.numel()), x.device.index,
+                                                          _lib.stream_ptr(x.device)), "radad_projection_train_forward")
+        ctx.save_for_backward(x, *params, *saved, *(() if mask is None else (mask,)))
+        ctx.inv_keep = float(inv_keep)
+        ctx.has_mask = mask is not None
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        tensors = ctx.saved_tensors
+        x, params, saved = tensors[0], tensors[1:15], tensors[15:22]
+        mask = tensors[22] if ctx.has_mask else None
+        g = grad_out.contiguous().float()            # out.sum().backward() hands over a stride-0 expand
+        B, K, D = x.shape
+        H, O = params[0].shape[0], params[12].shape[0]
+        need = list(ctx.needs_input_grad[3:17])
+        need[0] = need[4] = need[0] or need[4]       # dW1 and dW3 come from one product
+        grads = [torch.empty(p.shape, device=x.device, dtype=torch.float32) if n else None for p, n in zip(params, need)]
+        dx = torch.empty(x.shape, device=x.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        ws = _train_workspace(lib, x, B, K, D, H, O)
+        w = _lib.ProjWeights(**{f: p.data_ptr() for f, p in zip(_WEIGHT_FIELDS, params)})
+        sv = _lib.ProjSaved(*[t.data_ptr() for t in saved])
+        gr = _lib.ProjGrads(*[None if t is None else t.data_ptr() for t in grads])   # NULL: the library skips that gradient
+        with torch.cuda.device(x.device):
+            _lib.check(lib.radad_projection_backward(C.byref(w), x.data_ptr(), mask.data_ptr() if mask is not None else None,
+                                                     ctx.inv_keep, C.byref(sv), g.data_ptr(), B, K, D, H, O, C.byref(gr),
+                                                     dx.data_ptr() if dx is not None else None, ws.data_ptr(), int(ws.numel()),
+                                                     x.device.index, _lib.stream_ptr(x.device)), "radad_projection_backward")
+        return (dx, None, None) + tuple(gp if ctx.needs_input_grad[3 + i] else None for i, gp in enumerate(grads))
 
 
 class ProjectionLayer(nn.Module):
@@ -72,6 +176,10 @@ class ProjectionLayer(nn.Module):
         """projection.py:108-117 (eval path).  input [B, top_k, D] -> [B, output_dim]."""
         if input_embeddings.device != self.device:
             input_embeddings = input_embeddings.to(self.device)
+        if self.training and torch.is_grad_enabled() and bool(getattr(self.config, "projection_train_hip", False)):
+            # training mode means dropout (projection.py:100), also when nothing here needs a gradient (a frozen projection under a
+            # trained head): the training kernels run whenever the module is in training mode and autograd is on
+            return self._train_forward(input_embeddings)
         if torch.is_grad_enabled() and (input_embeddings.requires_grad or any(p.requires_grad for p in self.parameters())) \
                 and self.training:
             raise RuntimeError("ProjectionLayer here is inference-only (HIP forward); call .eval() / torch.no_grad(), "
@@ -92,6 +200,29 @@ class ProjectionLayer(nn.Module):
                                                     out.data_ptr(), self._ws.data_ptr(), int(self._ws.numel()),
                                                     x.device.index, _lib.stream_ptr(x.device)), "radad_projection_forward")
         return out
+
+    def _train_forward(self, input_embeddings: torch.Tensor) -> torch.Tensor:
+        """projection.py:108-117 in training mode (config.projection_train_hip): HIP forward and backward through
+        _ProjectionTrainFn.  The dropout mask (config.projection_dropout, projection.py:53) is drawn by torch on the device under
+        torch's generator, so torch.manual_seed reproduces a step; p == 0 draws nothing.  `use_gradient_checkpointing`
+        (projection.py:110-115) is accepted and ignored: what the backward keeps beside x is H wide (t, h: 2 H per neighbour row
+        against D for x, a few percent at D = 5376), so there is nothing worth recomputing.  The kernels are float32: an input or
+        parameters of another float dtype are cast up here (differentiably) and the output is float32, as in eval."""
+        _lib.require_cuda(input_embeddings, "input_embeddings")
+        x = input_embeddings
+        if x.dim() != 3 or x.shape[2] != self.input_dim:
+            raise ValueError(f"expected [B, K, {self.input_dim}], got {tuple(x.shape)}")
+        if not x.is_floating_point():
+            raise TypeError(f"input_embeddings must be a floating-point tensor, got {x.dtype}")
+        x = x.float()       # any float dtype is accepted, as in eval: a differentiable cast, so dx comes back in the caller's dtype
+        p = float(getattr(self.config, "projection_dropout", 0.0))
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"projection_dropout must be in [0, 1), got {p}")
+        mask = None
+        if p > 0.0:
+            mask = torch.empty((x.shape[0], self.hidden_dim), device=x.device, dtype=torch.float32).bernoulli_(1.0 - p)
+        params = [getattr(getattr(self, m), leaf).float() for m, leaf in _PARAM_ORDER]    # (.double() / .half() modules: same cast)
+        return _ProjectionTrainFn.apply(x, mask, 1.0 / (1.0 - p), *params)
 
     def _weights(self, device):
         """C struct of device pointers (+ the tensors that must outlive the launch) with the cached W5*W4 fold."""

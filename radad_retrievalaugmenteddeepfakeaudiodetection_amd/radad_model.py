@@ -4,7 +4,10 @@ Module tree and parameter names equal the reference's (`projection_layer.*`, `fu
 with the same nn.Sequential indices), so `load_state_dict` of a reference checkpoint works unchanged.  forward()
 runs csrc/proj.hip: the projection (one pass over the neighbour tensor), then `radad_fuse_head_forward` --
 fuse Linear over [tpp ; proj] without building the concatenation, and the detection MLP with BatchNorm in its
-eval form (running statistics as scale/shift).  Training stays in the reference: a training-mode forward raises.
+eval form (running statistics as scale/shift).  Training is opt-in (`config.projection_train_hip = True`): a training-mode
+forward then runs the projection's HIP forward + backward (csrc/proj_train.inc) and the fuse Linear and the detection MLP as the
+plain torch modules they are (a 10 k-parameter head; BatchNorm updates its running statistics as in the reference).  With the
+default a training-mode forward raises, and training stays in the reference.
 """
 import ctypes as C
 
@@ -73,6 +76,9 @@ class RADADModel(nn.Module):
         self.to(self.device)
         self._ws = None
 
+    def _training_path(self) -> bool:
+        return self.training and torch.is_grad_enabled() and bool(getattr(self.config, "projection_train_hip", False))
+
     def _check_eval(self, *tensors):
         if self.training and torch.is_grad_enabled():
             raise RuntimeError("RADADModel here is inference-only (HIP forward); call .eval() / torch.no_grad(), "
@@ -82,6 +88,10 @@ class RADADModel(nn.Module):
 
     def fuse_and_detect(self, tpp_vecs: torch.Tensor, proj: torch.Tensor, return_fused: bool = False):
         """radad_model.py:39-40 given the projection output."""
+        if self._training_path():      # torch modules under autograd: fuse Linear over the concatenation, then the MLP
+            fused = self.fuse(torch.cat([tpp_vecs, proj], dim=1))
+            logits = self.detection_model.model(fused).squeeze(-1)             # detection_model.py:125
+            return (logits, fused) if return_fused else logits
         self._check_eval(tpp_vecs, proj)
         t = tpp_vecs.detach().contiguous().float()
         pr = proj.detach().contiguous().float()
@@ -129,7 +139,8 @@ class RADADModel(nn.Module):
             neighbor_vecs = neighbor_vecs.to(self.device)
         if tpp_vecs.device != self.device:
             tpp_vecs = tpp_vecs.to(self.device)
-        self._check_eval(neighbor_vecs, tpp_vecs)
+        if not self._training_path():
+            self._check_eval(neighbor_vecs, tpp_vecs)
         proj = self.projection_layer(neighbor_vecs)                            # :38
         return self.fuse_and_detect(tpp_vecs, proj)                            # :39-40
 
