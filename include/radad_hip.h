@@ -105,6 +105,11 @@ int radad_knn_create_ex(int dim, int metric, int store_dtype, int device, int64_
  *                            workgroups by ticket, so that a skip pattern that is not spread evenly over the store does not leave the
  *                            launch waiting for its slowest chunk.  Off by default: on the benchmark it measured no gain that stands
  *                            clear of the run-to-run spread (profiles/abandon_deal_ab.txt); no environment override
+ *   RADAD_KNN_OPT_ABANDON_DEFER  1 (default) / 0: an abandoning launch of <= 8 query tiles that is not dealt and whose rows span less
+ *                            than 4 GiB of the plane lists the live rows of a vetoed tile that has at most 16 of them, leaves the tile as
+ *                            a skipped one, and scores the listed rows in full against their query tile in a tail launch behind the scan
+ *                            launch / a vetoed tile is multiplied in full.  Same candidates either way.  Measured:
+ *                            profiles/abandon_defer_ab.txt; RADAD_KNN_OPT_ABANDON 0 turns it off too; no environment override
  * The environment variables RADAD_KNN_HI, RADAD_KNN_CENTRE, RADAD_KNN_SMALLQ_HI, RADAD_WIDE_MIN_Q override the DEFAULTS of handles
  * created while they are set (announced once per process on stderr); the product path never needs them. */
 #define RADAD_KNN_OPT_HI_PLANE 0
@@ -115,6 +120,7 @@ int radad_knn_create_ex(int dim, int metric, int store_dtype, int device, int64_
 #define RADAD_KNN_OPT_ABANDON 5
 #define RADAD_KNN_OPT_RANGE_SMALLQ 6
 #define RADAD_KNN_OPT_ABANDON_DEAL 7
+#define RADAD_KNN_OPT_ABANDON_DEFER 8
 int radad_knn_set_option(radad_knn_t h, int option, int value);
 int radad_knn_destroy(radad_knn_t h);
 int radad_knn_dim(radad_knn_t h, int* dim);
@@ -229,6 +235,10 @@ int radad_knn_last_abandon(radad_knn_t h, int64_t* checked, int64_t* skipped, in
 /* ... and how its abandoning launches got their row tiles (no synchronisation: the host's plan): how many of them were dealt by ticket
  * (RADAD_KNN_OPT_ABANDON_DEAL), and of the last dealt one the workgroups launched and the row tiles per granule.  All 0 when none was. */
 int radad_knn_last_abandon_deal(radad_knn_t h, int* launches, int* workgroups, int* granule);
+/* ... and what its deferring launches (RADAD_KNN_OPT_ABANDON_DEFER) handed to their tails (synchronises with the search): the vetoed tile
+ * tasks that listed their live rows and left (`checked` counts them, `skipped` does not), the rows listed over all query tiles, and the
+ * tail launches made.  All 0 when no launch deferred. */
+int radad_knn_last_abandon_defer(radad_knn_t h, int64_t* tile_tasks_deferred, int64_t* rows_listed, int* tail_launches);
 /* the f16 plane the certified scans read, once a search has built it: built (0/1); centred = the common component (column mean)
  * of the rows is subtracted before rounding (stores of embeddings that share most of their mean); one_scale = one power-of-two
  * scale for all rows (rows of one magnitude: the scan applies no per-score arithmetic) */

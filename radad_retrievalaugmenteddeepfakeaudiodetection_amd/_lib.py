@@ -25,6 +25,7 @@ RANGE_TILE, RANGE_EXACT, RANGE_STREAM = 0, 1, 2     # RADAD_RANGE_*
 KNN_OPT_HI_PLANE, KNN_OPT_CENTRE, KNN_OPT_SMALLQ_HI, KNN_OPT_WIDE_MIN_Q, KNN_OPT_DENSE, KNN_OPT_ABANDON = 0, 1, 2, 3, 4, 5
 KNN_OPT_RANGE_SMALLQ = 6                      # RADAD_KNN_OPT_RANGE_SMALLQ
 KNN_OPT_ABANDON_DEAL = 7                      # RADAD_KNN_OPT_ABANDON_DEAL
+KNN_OPT_ABANDON_DEFER = 8                     # RADAD_KNN_OPT_ABANDON_DEFER
 IVF_OPT_HI_SCAN = 0
 IVF_OPT_PQ_FILTER = 1      # RADAD_IVF_OPT_PQ_FILTER
 IVF_SCAN_KINDS = ("f32_lists", "hi_lists", "exact_flat")
@@ -123,6 +124,7 @@ SIGNATURES = {
     "radad_knn_last_emitted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "radad_knn_last_abandon": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "radad_knn_last_abandon_deal": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "radad_knn_last_abandon_defer": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "radad_knn_plane_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "radad_knn_plane_rebuilds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "radad_knn_tuning_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),

@@ -2957,6 +2957,13 @@ struct radad_knn_s {
     int n_cus = 0;               // compute units of the device (radad_knn_create)
     int* deal_cnt = nullptr;     // [KNN_DEAL_COUNTERS]
     int last_deal_launches = 0, last_deal_workgroups = 0, last_deal_granule = 0;      // radad_knn_last_abandon_deal
+    // a vetoed tile's few live rows deferred to a dense tail (knn_abandon_defer, knn_plan.h): a deferring launch counts in its own set
+    // of deal_cnt (it is never dealt too: knn_defer_counter); the lists are a buffer of the handle's own, sized for the whole store
+    int opt_abandon_defer = 1;   // RADAD_KNN_OPT_ABANDON_DEFER (measured: profiles/abandon_defer_ab.txt)
+    int* defer_list = nullptr;   // [KNN_DEFER_MAX_QTILES][defer_list_cap]
+    int64_t defer_list_cap = 0;
+    int last_defer_launches = 0; // tails launched by the last search (radad_knn_last_abandon_defer) ...
+    unsigned last_defer_sets = 0;// ... and the counter sets they used, one bit each
     // queries the certificate rejected in the most recent search: counted on the device, copied to pinned host memory
     // behind the search (no synchronisation inside search); feeds the adaptive tuning and radad_knn_last_recheck
     int* host_count = nullptr;   // pinned [2][8]: rejected queries, sum of candidates, rejections by reason x 4, [6] the report's stamp, [7] its batch size
@@ -3328,6 +3335,7 @@ int radad_knn_destroy(radad_knn_t h) {
         if (h->tile_ry) (void)hipFree(h->tile_ry);
         if (h->ab_ws) (void)hipFree(h->ab_ws);
         if (h->deal_cnt) (void)hipFree(h->deal_cnt);
+        if (h->defer_list) (void)hipFree(h->defer_list);
         if (h->host_count) (void)hipHostFree(h->host_count);
         if (h->ev_done) (void)hipEventDestroy(h->ev_done);
         if (h->ev_begun) (void)hipEventDestroy(h->ev_begun);
@@ -3374,6 +3382,10 @@ int radad_knn_set_option(radad_knn_t h, int option, int value) {
         case RADAD_KNN_OPT_ABANDON_DEAL:
             RADAD_REQUIRE(value == 0 || value == 1, "radad_knn_set_option: ABANDON_DEAL takes 0 or 1");
             h->opt_abandon_deal = value;
+            return RADAD_OK;
+        case RADAD_KNN_OPT_ABANDON_DEFER:
+            RADAD_REQUIRE(value == 0 || value == 1, "radad_knn_set_option: ABANDON_DEFER takes 0 or 1");
+            h->opt_abandon_defer = value;
             return RADAD_OK;
         case RADAD_KNN_OPT_RANGE_SMALLQ:
             RADAD_REQUIRE(value == 0 || value == 1, "radad_knn_set_option: RANGE_SMALLQ takes 0 or 1");
@@ -3597,7 +3609,16 @@ static bool knn_abandon_terms_ready(radad_knn_t h, int64_t nq) {
         h->ab_ws_bytes = A.bytes;
     }
     // (the ticket counters of dealt launches: without them the launches stay static)
-    if (h->opt_abandon_deal && !h->deal_cnt && hipMalloc(&h->deal_cnt, KNN_DEAL_COUNTERS * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); h->deal_cnt = nullptr; }
+    if ((h->opt_abandon_deal || h->opt_abandon_defer) && !h->deal_cnt && hipMalloc(&h->deal_cnt, KNN_DEAL_COUNTERS * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); h->deal_cnt = nullptr; }
+    // the deferral's lists: one per query tile, each as long as a launch over the whole store could fill (without them nothing defers)
+    if (h->opt_abandon_defer && h->deal_cnt && h->defer_list_cap < knn_defer_list_cap(h->ntotal)) {
+        (void)hipDeviceSynchronize();
+        if (h->defer_list) (void)hipFree(h->defer_list);
+        h->defer_list = nullptr; h->defer_list_cap = 0;
+        const int64_t cap = knn_defer_list_cap(h->capacity > h->ntotal ? h->capacity : h->ntotal);
+        if (hipMalloc(&h->defer_list, (size_t)KNN_DEFER_MAX_QTILES * cap * sizeof(int)) == hipSuccess) h->defer_list_cap = cap;
+        else { (void)hipGetLastError(); h->defer_list = nullptr; }
+    }
     return true;
 }
 
@@ -3635,7 +3656,7 @@ static const float* knn_prepare_queries(radad_knn_t h, const ScanPlan& p, const 
             hp.suf_from = h->ab_from;
             hp.suf_out = reinterpret_cast<float*>(static_cast<char*>(h->ab_ws) + A.rq);
             hp.ab_slack_out = reinterpret_cast<float*>(static_cast<char*>(h->ab_ws) + A.slack);
-            hp.zero_deal = h->opt_abandon_deal ? h->deal_cnt : nullptr;         // every launch's ticket counters, once per search, in a kernel the search runs anyway
+            hp.zero_deal = (h->opt_abandon_deal || h->opt_abandon_defer) ? h->deal_cnt : nullptr;         // every launch's ticket counters, once per search, in a kernel the search runs anyway
         }
         launch_hi_rows(hp, st);
     }
@@ -3760,6 +3781,7 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
     const AbandonLayout AL = knn_abandon_layout(nq);
     h->last_ab_tasks = 0; h->last_o_ab = L.fcount + KNN_AB_COUNTER0 * sizeof(int);
     h->last_deal_launches = h->last_deal_workgroups = h->last_deal_granule = 0;
+    h->last_defer_launches = 0; h->last_defer_sets = 0;
     RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(sample), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // sample pre-pass: the (k + margin)-th best score over the first rows of the store is a score at least k rows reach, so the
@@ -3840,9 +3862,42 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
                 ++h->last_deal_launches; h->last_deal_workgroups = dp.workgroups; h->last_deal_granule = dp.granule;
             }
         }
-        h->prof.begin(st);      // the event pair brackets a scan launch only (the kernel the roofline is quoted on; the phases of one
-                                // search are two entries)
+        // a deferring launch (knn_abandon_defer) lists the few live rows of its vetoed tiles and is followed by its tail, which scores
+        // them in full with this launch's floors before anything reads the candidate buffers
+        DeferPlan fp;
+        if (ab_ck > 0) {
+            DeferFacts ff;
+            ff.opt_defer = (h->deal_cnt && h->defer_list) ? h->opt_abandon_defer : 0; ff.ab_ck = ab_ck; ff.dealt = rp.deal_cnt != nullptr;
+            ff.launch = (int)i; ff.rows = rp.n; ff.row_bytes = rp.row_bytes; ff.n_qtiles = std::max(gq, rp.n_qtiles); ff.cus = h->n_cus;
+            fp = knn_abandon_defer(ff);
+            if (fp.defer && fp.list_cap > h->defer_list_cap) fp.defer = false;
+        }
+        KnnHiParams tp;
+        auto tail_fn = launch_fn;
+        if (fp.defer) {
+            rp.df_cnt = h->deal_cnt + knn_defer_counter((int)i, 0);
+            rp.df_list = h->defer_list; rp.df_cap = (int)fp.list_cap;
+            rp.df_tasks = h->deal_cnt + knn_defer_tasks_counter((int)i);
+            launch_fn = rsc == 0 ? k_knn_hi_abandon_defer<0> : k_knn_hi_abandon_defer<3>;
+            launch_lds = knn_hi_lds_bytes(true, true);
+            RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(launch_fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)launch_lds));
+            tp = rp;
+            tp.ab_ck = 0; tp.n_splits = fp.tail_splits; tp.chunk_rows = tp.chunk_stride = KW_M; tp.ksplit = 1;
+            tp.df_bytes = (unsigned)(rp.n * rp.row_bytes);
+            // (the counting form of the emit: every row of a tail tile is a candidate of some query, and reserving slot by slot a wave
+            // sat through ~30 atomic round trips one after the other -- 85 us per tail on the benchmark, measured; the set emitted is
+            // the same, and nothing reads the buffers' order)
+            tp.loose_floor = 1;
+            tail_fn = rsc == 0 ? k_knn_hi_tail<0> : k_knn_hi_tail<3>;
+            RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tail_fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        }
+        h->prof.begin(st);      // the event pair brackets a scan launch (the kernel the roofline is quoted on; the phases of one
+                                // search are two entries) and, behind a deferring one, its tail
         hipLaunchKernelGGL(launch_fn, dim3((unsigned)(gq_grid * gs * rp.ksplit)), dim3(KW_THREADS), launch_lds, st, rp);
+        if (fp.defer) {
+            hipLaunchKernelGGL(tail_fn, dim3((unsigned)(gq_grid * fp.tail_splits)), dim3(KW_THREADS), lds, st, tp);
+            ++h->last_defer_launches; h->last_defer_sets |= 1u << i;
+        }
         h->prof.end(st);
     }
     if (scrub) knn_launch_scrub(h, scrub, ps, pi, wp.cand_cnt, p.emit_cap, st);     // (for the re-rank)
@@ -5058,6 +5113,24 @@ int radad_knn_last_abandon_deal(radad_knn_t h, int* launches, int* workgroups, i
     *launches = *workgroups = *granule = 0;
     if (h->last_ab_tasks <= 0) return RADAD_OK;                 // the last search launched no abandoning scan
     *launches = h->last_deal_launches; *workgroups = h->last_deal_workgroups; *granule = h->last_deal_granule;
+    return RADAD_OK;
+}
+
+int radad_knn_last_abandon_defer(radad_knn_t h, int64_t* tile_tasks_deferred, int64_t* rows_listed, int* tail_launches) {
+    RADAD_REQUIRE(h && tile_tasks_deferred && rows_listed && tail_launches, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    *tile_tasks_deferred = *rows_listed = 0; *tail_launches = 0;
+    if (h->last_ab_tasks <= 0 || h->last_defer_launches <= 0 || !h->deal_cnt) return RADAD_OK;       // the last search deferred nothing
+    RADAD_HIP_CHECK(knn_wait_last_search(h));
+    int c[KNN_DEAL_COUNTERS];
+    RADAD_HIP_CHECK(hipMemcpy(c, h->deal_cnt, sizeof(c), hipMemcpyDeviceToHost));
+    for (int s = 0; s < KNN_DEFER_SETS; ++s) {
+        if (!(h->last_defer_sets >> s & 1u)) continue;
+        for (int qt = 0; qt < KNN_DEFER_MAX_QTILES; ++qt) *rows_listed += c[knn_defer_counter(s, qt)];
+        *tile_tasks_deferred += c[knn_defer_tasks_counter(s)];
+    }
+    *tail_launches = h->last_defer_launches;
     return RADAD_OK;
 }
 

@@ -81,12 +81,20 @@ struct KnnHiParams {
     int deal_g = 0;                       // row tiles per granule (a power of two)
     int deal_tiles = 0;                   // row tiles of this launch
     int* deal_cnt = nullptr;              // [KNN_DEAL_SLOTS][KNN_DEAL_MAX_QTILES] this launch's ticket counters (zeroed once per search: k_hi_rows)
+    // DEFERRING launches (k_knn_hi_abandon_defer; which launches are: knn_abandon_defer, knn_plan.h) append a vetoed tile's few live rows
+    // to the list of their query tile; the launch's tail (k_knn_hi_tail) reads the same three fields
+    int* df_cnt = nullptr;                // [KNN_DEFER_MAX_QTILES] entries of each query tile's list, this launch (zeroed once per search: k_hi_rows)
+    int* df_list = nullptr;               // [KNN_DEFER_MAX_QTILES][df_cap] launch-relative rows
+    int df_cap = 0;                       // row tiles of the launch x KNN_DEFER_MAX_ROWS: a list cannot overflow
+    int* df_tasks = nullptr;              // [1] tile tasks deferred (one atomic per workgroup)
+    unsigned df_bytes = 0;                // the tail: bytes of the launch's rows (the plane is addressed through ONE 32-bit descriptor)
 };
 static_assert(std::is_trivially_copyable_v<KnnHiParams>, "kernel argument");
 
-constexpr size_t knn_hi_lds_bytes(bool abandon = false) {
-    // (ABANDON: + three per-query arrays and the two veto words)
-    return 2 * KW_STAGE_BYTES + sizeof(float) * KW_N * 4 + sizeof(float) * 2 * KW_M * 2 + 16 + (abandon ? sizeof(float) * KW_N * 3 + 16 : 0);
+constexpr size_t knn_hi_lds_bytes(bool abandon = false, bool defer = false) {
+    // (ABANDON: + three per-query arrays and the two veto words; DEFER: + the two 256-bit masks of live rows)
+    return 2 * KW_STAGE_BYTES + sizeof(float) * KW_N * 4 + sizeof(float) * 2 * KW_M * 2 + 16 + (abandon ? sizeof(float) * KW_N * 3 + 16 : 0) +
+           (defer ? 64 : 0);
 }
 
 // RSC: 0 = IP with one scale for all rows (un-centred cosine stores, fp16 stores): no per-score arithmetic at all;
@@ -152,10 +160,16 @@ __device__ __forceinline__ bool knn_hi_gate(float amin, float rmax, float ry, fl
 // the proof are at the checkpoint below).  Instantiations without it compile to the code they had before it existed.
 // (ab_amin, ab_rmax: the gate's query side, from knn_hi_gate_open)
 // DEAL (with ABANDON only): the tiles come by ticket.  deal_ticket: the first of the TWO tickets the gate pass drew for this workgroup.
-template <int RSC, bool SAMPLE, bool ABANDON = false, bool DEAL = false>
-__device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab_amin = 0.f, const float ab_rmax = 0.f, const int deal_ticket = 0) {
+// DEFER (with ABANDON only, not DEAL): a vetoed tile with 1 ... KNN_DEFER_MAX_ROWS live rows lists them and is left like a skipped one.
+// MAPPED (the tail of a deferring launch, no ABANDON): ONE tile per call, rows map_tile * KW_M ... of this query tile's LIST; the A
+// operand is fetched row by row from where the list says, everything else -- K order, accumulator start, emit -- is the scan's.
+template <int RSC, bool SAMPLE, bool ABANDON = false, bool DEAL = false, bool DEFER = false, bool MAPPED = false>
+__device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab_amin = 0.f, const float ab_rmax = 0.f, const int deal_ticket = 0,
+                                            const int map_tile = 0) {
     static_assert(!ABANDON || (!SAMPLE && (RSC == 0 || RSC == 3)), "the abandon covers the one-scale scans");
     static_assert(!DEAL || ABANDON, "only the abandoning scan is dealt");
+    static_assert(!DEFER || (ABANDON && !DEAL), "only the abandoning scan over static chunks defers");
+    static_assert(!MAPPED || (!SAMPLE && !ABANDON && (RSC == 0 || RSC == 3)), "the tail scores what an abandoning launch listed");
     int stamp_n = 0;
     (void)stamp_n;
     // acc[mt][nt][r] = row wm*128 + mt*16 + 4*lq + r, query wn*64 + nt*16 + l15   (l15 = lane & 15, lq = lane >> 4)
@@ -173,6 +187,9 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
     float* s_arq = s_at + KW_N;                                              // [KW_N] |qh_j[64 ck:]|
     float* s_asl = s_arq + KW_N;                                             // [KW_N] accumulation slack, accumulator units
     int* s_veto = reinterpret_cast<int*>(s_asl + KW_N);                      // [2] by tile parity: the tile (row0 / KW_M) a wave vetoed last
+    unsigned* s_live = reinterpret_cast<unsigned*>(s_veto + 4);              // DEFER: [2][8] by tile parity: bit r of the 256 = row r is live
+    int* s_map = reinterpret_cast<int*>(s_rs);                               // MAPPED: [KW_M] the tile's rows of the launch, -1 past the list's
+                                                                             // end (s_rs: RSC 0 and 3 never use it)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -191,8 +208,10 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
     if (!knn_hi_task(p, bid, qt, split)) return;     // (block-uniform, before any barrier)
     const int q0 = qt * KW_N;
     // (DEAL: the "chunk" is the launch -- every tile but the launch's last is whole -- and `split` is not used)
-    const int64_t chunk_begin = DEAL ? (int64_t)0 : (int64_t)split * p.chunk_stride;
-    const int64_t chunk_end = DEAL ? p.n : min(chunk_begin + p.chunk_rows, p.n);
+    // (MAPPED: the "store" is the query tile's list, the chunk its tile map_tile)
+    const int64_t chunk_begin = DEAL ? (int64_t)0 : MAPPED ? (int64_t)map_tile * KW_M : (int64_t)split * p.chunk_stride;
+    const int64_t chunk_end = DEAL ? p.n : MAPPED ? min(chunk_begin + KW_M, (int64_t)min(p.df_cnt[qt], p.df_cap)) : min(chunk_begin + p.chunk_rows, p.n);
+    if constexpr (MAPPED) { if (chunk_begin >= chunk_end) return; }          // (block-uniform, before any barrier)
     const bool owner = tid < KW_N && q0 + tid < p.nq;
     const int nk_all = p.row_bytes >> 7;             // 128-byte K steps per row
     const int k_lo = part * (nk_all >> 1);           // this workgroup's K steps [k_lo, k_lo + nk)
@@ -216,6 +235,12 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
         }
     }
     if constexpr (ABANDON) { if (tid < 2) s_veto[tid] = -1; }
+    if constexpr (DEFER) { if (tid < 16) s_live[tid] = 0u; }
+    if constexpr (MAPPED) {
+        // the tile's rows, in LDS before the first fetch needs them (one tile per call: no parity)
+        if (tid < KW_M) s_map[tid] = chunk_begin + tid < chunk_end ? p.df_list[(int64_t)qt * p.df_cap + chunk_begin + tid] : -1;
+        __syncthreads();
+    }
 
     // DMA plan.  One LDS-DMA instruction fills an 8-row group (1 KB, lane-linear) of an operand tile; 32 groups per operand
     // and stage.  Waves 0-3 fetch the A (store) tile, 8 groups each, right after the stage's barrier (it comes from HBM: the
@@ -247,6 +272,8 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
         const_cast<char*>(reinterpret_cast<const char*>(p.q) + (int64_t)q0 * p.row_bytes), 0,
         min(KW_N, p.nq - q0) * p.row_bytes, 0x00020000);
     auto tile_desc = [&](int64_t r0) {
+        // (MAPPED: the whole launch, whatever the tile: the per-lane offsets say which rows)
+        if constexpr (MAPPED) return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.db)), 0, (int)p.df_bytes, 0x00020000);
         const int rows = (int)max((int64_t)0, min((int64_t)KW_M, chunk_end - r0));
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.db) + r0 * p.row_bytes), 0,
                                                  rows * p.row_bytes, 0x00020000);
@@ -258,6 +285,24 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
         // (opaque copies: hipcc would otherwise keep all eight per-group offsets in registers across the K loop -- and spill them)
         unsigned vo_par[2] = {dma_vo[0], dma_vo[1]};
         asm volatile("" : "+v"(vo_par[0]), "+v"(vo_par[1]));
+        if constexpr (MAPPED) {
+            if (operand == 0) {
+                // row 8 g + (lane >> 3) of the tile is row s_map[..] of the launch; a slot past the list's end points past the
+                // descriptor's end and reads as a zero row
+                int lane_m = lane;
+                asm volatile("" : "+v"(lane_m));
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const int g = g0 + i;
+                    const int r = 8 * g + (lane_m >> 3);
+                    const int m = s_map[r];
+                    const unsigned lc = (unsigned)((lane_m & 7) ^ ((r >> 1) & 7));
+                    const unsigned vo = m < 0 ? p.df_bytes : (unsigned)m * (unsigned)p.row_bytes + lc * 16u;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(desc, (lds_ptr_t)(base + g * 1024), 16, vo, soff, 0, 0);
+                }
+                return;
+            }
+        }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int g = g0 + i;
@@ -274,12 +319,14 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
         asm volatile("" : "+v"(t));                  // opaque: the addresses are formed here, not kept (or spilled) across the K loop
         if (RSC != 0 && t < KW_M) {
             const bool in = r0 + t < chunk_end;
+            int64_t rb_row = r0 + t;
+            if constexpr (MAPPED) { if (in) rb_row = p.df_list[(int64_t)qt * p.df_cap + r0 + t]; }
             float rs = (in && p.rscale) ? p.rscale[r0 + t] : p.uscale;
             if (RSC == 2) rs *= p.mult;
             if (RSC != 3) s_rs[par * KW_M + t] = in ? rs : 0.f;
             // RSC 2: bias / (row scale) (a power of two: exact); RSC 3: the bias itself (the one scale sits in the query's factor)
             // (K split: the bias starts the FIRST half's accumulators only)
-            s_rb[par * KW_M + t] = (RSC >= 2 && in && part == 0) ? (RSC == 2 ? p.bias_sign * p.rbias[r0 + t] / rs : p.bias_sign * p.rbias[r0 + t]) : 0.f;
+            s_rb[par * KW_M + t] = (RSC >= 2 && in && part == 0) ? (RSC == 2 ? p.bias_sign * p.rbias[r0 + t] / rs : p.bias_sign * p.rbias[rb_row]) : 0.f;
         }
     };
     // ---- DEAL: which tile comes next ------------------------------------------------------------------------------------------------
@@ -416,7 +463,8 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
     // into s_veto[parity]; the stage's own barrier publishes it; everyone reads it: the decision is workgroup-uniform, no spinning, no
     // communication between workgroups.  (The word holds a tile NUMBER and is never reset; the next write to the same parity is two
     // tiles on, behind at least two more barriers.)
-    int ab_ck = 0, ab_checked = 0, ab_skipped = 0;
+    int ab_ck = 0, ab_checked = 0, ab_skipped = 0, ab_deferred = 0;
+    (void)ab_deferred;
     if constexpr (ABANDON) ab_ck = p.ab_ck;
     int tile_par = 0;
     for (int64_t row0 = row_first; row0 < chunk_end; row0 = DEAL ? d_row_adv : row0 + KW_M, tile_par ^= 1) {
@@ -435,7 +483,9 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
         const bool has_next = row_next < chunk_end;
         // THE GATE, tile side (scalars only): the test runs iff it can succeed
         float ab_ry = 0.f;
-        bool ab_check = false, ab_skip = false;
+        bool ab_check = false, ab_skip = false, ab_defer = false;
+        int df_ns = 0;
+        (void)ab_defer; (void)df_ns;
         if constexpr (ABANDON) {
             ab_ry = p.ab_ry[row0 >> 8] * (1.0f + 0x1p-10f);
             ab_check = knn_hi_gate(ab_amin, ab_rmax, p.ab_ry[row0 >> 8], RSC == 3 ? p.ab_b[row0 >> 8] : 0.f);
@@ -485,8 +535,49 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
                         // (fmaxf drops a NaN score: a NaN score is never emitted either.  Rows past the tile's end read as zero rows.)
                         ok = ok && (gm + fmaf(s_arq[ql], ab_ry, s_asl[ql]) < s_at[ql]);
                     }
-                    if (!__all(ok) && (lane_t & 63) == 0) s_veto[tile_par] = (int)(row0 >> 8);
+                    if constexpr (!DEFER) {
+                        if (!__all(ok) && (lane_t & 63) == 0) s_veto[tile_par] = (int)(row0 >> 8);
+                    } else {
+                        // DEFER: a wave that vetoes also says WHICH of its 128 rows are live: row i is live iff for some query j of the
+                        // wave the same comparison, with the same terms, is not true (any NaN keeps the row live).  gm is the maximum of
+                        // the column and the addition is monotonic, so a wave that does not veto has no live row.  Bit mt * 4 + r of
+                        // `live` is row mt * 16 + 4 lq + r of the wave; word (mt >> 1) of the wave's four holds it at bit
+                        // (mt & 1) * 16 + 4 lq + r.  The stage's barrier publishes the words with the veto.
+                        if (!__all(ok)) {            // (wave-uniform)
+                            if ((lane_t & 63) == 0) s_veto[tile_par] = (int)(row0 >> 8);
+                            unsigned live = 0u;
+                            float bd[NT], at[NT];
+#pragma unroll
+                            for (int nt = 0; nt < NT; ++nt) {
+                                const int ql = wn * 64 + nt * 16 + (lane_t & 15);
+                                bd[nt] = fmaf(s_arq[ql], ab_ry, s_asl[ql]);
+                                at[nt] = s_at[ql];
+                            }
+                            // (shifted in from the top row down -- a select between 32 different one-bit constants had hipcc keep all
+                            // 32 of them in registers across the tile loop, and spill)
+#pragma unroll
+                            for (int mt = MT - 1; mt >= 0; --mt)
+#pragma unroll
+                                for (int r = 3; r >= 0; --r) {
+                                    bool all_true = true;
+#pragma unroll
+                                    for (int nt = 0; nt < NT; ++nt) all_true = all_true && (acc[mt][nt][r] + bd[nt] < at[nt]);
+                                    live = (live << 1) | (all_true ? 0u : 1u);
+                                }
+                            const int sh = 4 * (lane_t >> 4);
+#pragma unroll
+                            for (int w = 0; w < 4; ++w) {
+                                const unsigned v = (((live >> (8 * w)) & 15u) << sh) | (((live >> (8 * w + 4)) & 15u) << (16 + sh));
+                                if (v) atomicOr(&s_live[tile_par * 8 + wm * 4 + w], v);
+                            }
+                        }
+                    }
                 }
+            }
+            if constexpr (DEFER) {
+                // the OTHER parity's mask is cleared for the tile after this one: its readers left it behind a barrier (the rest of
+                // the last tile's K loop, or its skip's), its next writers come behind this tile's
+                if (kc == 0 && tid < 8) s_live[(tile_par ^ 1) * 8 + tid] = 0u;
             }
             if constexpr (DEAL) {
                 if (kc == 0 && d_draw && tid == 0) s_veto[2] = d_ticket;
@@ -505,7 +596,67 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
                 if (at_ck) {
                     ++ab_checked;
                     if (__builtin_amdgcn_readfirstlane(s_veto[tile_par]) != (int)(row0 >> 8)) { ab_skip = true; break; }
+                    if constexpr (DEFER) {
+                        // vetoed: how many rows of the tile (positions < rowlimit) are live; everyone reads the same eight words
+                        int ns = 0;
+#pragma unroll
+                        for (int w = 0; w < 8; ++w) {
+                            const int valid = min(32, max(0, rowlimit - 32 * w));
+                            const unsigned keep = valid >= 32 ? 0xffffffffu : ((1u << valid) - 1u);
+                            ns += __popc((unsigned)__builtin_amdgcn_readfirstlane((int)s_live[tile_par * 8 + w]) & keep);
+                        }
+                        if (ns >= 1 && ns <= KNN_DEFER_MAX_ROWS) { ab_defer = true; df_ns = ns; break; }
+                    }
                 }
+            }
+        }
+        if constexpr (DEFER) {
+            if (ab_defer) {
+                // DEFERRED: the tile's live rows go to this query tile's list and the workgroup leaves as a skip does.  Wave 0 appends:
+                // lane l holds rows 4 l ... 4 l + 3 (a nibble of word l >> 3) and their rank among the tile's live rows; lane 0
+                // reserves the ns entries with ONE returning atomic, issued in front of the next tile's DMA and first read behind the
+                // barrier that waits for that DMA anyway.  (The counter's address goes through an opaque zero, as the dealt kernel's
+                // does: a provably uniform address makes hipcc aggregate the atomic over the wave and wait for it on the spot.)
+                // The list holds ns x row tiles entries at least: no decision depends on the slot.
+                ++ab_deferred;
+                unsigned df_nib = 0u;
+                int df_rank = 0, df_slot = 0;
+                if (wave == 0) {
+                    int lane_d = lane;
+                    asm volatile("" : "+v"(lane_d));
+                    const int wd = lane_d >> 3;
+#pragma unroll
+                    for (int w = 0; w < 8; ++w) {
+                        const int valid = min(32, max(0, rowlimit - 32 * w));
+                        const unsigned keep = valid >= 32 ? 0xffffffffu : ((1u << valid) - 1u);
+                        const unsigned word = s_live[tile_par * 8 + w] & keep;
+                        if (w < wd) df_rank += __popc(word);
+                        if (w == wd) {
+                            const int sh = 4 * (lane_d & 7);
+                            df_nib = (word >> sh) & 15u;
+                            df_rank += __popc(word & ((1u << sh) - 1u));
+                        }
+                    }
+                    if (lane_d == 0) {
+                        int z = 0;
+                        asm volatile("" : "+v"(z));
+                        df_slot = atomicAdd(p.df_cnt + qt + z, df_ns);
+                    }
+                }
+                if (has_next) {
+                    if (grp_half == 0) dma_half(next_desc, gbuf & 1, 0, 0);
+                    else dma_half(q_desc, gbuf & 1, 0, 1);
+                    __syncthreads();
+                }
+                if (wave == 0) {
+                    int* dst = p.df_list + (int64_t)qt * p.df_cap + __builtin_amdgcn_readfirstlane(df_slot) + df_rank;
+                    const int row_l = (int)row0 + 4 * (lane & 63);
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) {
+                        if (df_nib & (1u << b)) { *dst = row_l + b; ++dst; }
+                    }
+                }
+                continue;
             }
         }
         if constexpr (ABANDON) {
@@ -665,7 +816,7 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
                                 if (rl < rowlimit && acc[mt][nt][r] >= thr4[nt]) {
                                     if (sl < p.cand_cap) {
                                         p.part_score[cbase + sl] = fmaf(acc[mt][nt][r], qi, qc);
-                                        p.part_idx[cbase + sl] = (int)(p.id_off + row0 + rl);
+                                        p.part_idx[cbase + sl] = MAPPED ? (int)(p.id_off + s_map[rl]) : (int)(p.id_off + row0 + rl);
                                     }
                                     ++sl;
                                 }
@@ -701,7 +852,7 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
                                     const int sl = atomicAdd(cnt, 1);
                                     if (sl < p.cand_cap) {
                                         p.part_score[cbase + sl] = fmaf(acc[mt][nt][r], qi, qc);
-                                        p.part_idx[cbase + sl] = (int)(p.id_off + row0 + rl);
+                                        p.part_idx[cbase + sl] = MAPPED ? (int)(p.id_off + s_map[rl]) : (int)(p.id_off + row0 + rl);
                                     }
                                 }
                             }
@@ -717,6 +868,7 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
         if (tid == 0 && ab_checked > 0) {
             atomicAdd(p.ab_count, ab_checked);
             if (ab_skipped > 0) atomicAdd(p.ab_count + 1, ab_skipped);
+            if constexpr (DEFER) { if (ab_deferred > 0) atomicAdd(p.df_tasks, ab_deferred); }
         }
     }
 }
@@ -791,6 +943,29 @@ __global__ __launch_bounds__(KW_THREADS, 1) void k_knn_hi_abandon_deal(KnnHiPara
     int ticket = 0;
     if (knn_hi_gate_open<RSC, true>(p, amin, rmax, &ticket)) knn_hi_body<RSC, false, true, true>(p, amin, rmax, ticket);
     else knn_hi_body<RSC, false, false>(p);
+}
+
+// the abandoning scan of a DEFERRING launch (knn_abandon_defer, knn_plan.h): own symbol, so that every other launch runs the kernel it
+// ran.  A workgroup whose gate is shut runs the plain body and lists nothing.
+template <int RSC>
+__global__ __launch_bounds__(KW_THREADS, 1) void k_knn_hi_abandon_defer(KnnHiParams p) {
+    float amin, rmax;
+    if (knn_hi_gate_open<RSC>(p, amin, rmax)) knn_hi_body<RSC, false, true, false, true>(p, amin, rmax);
+    else knn_hi_body<RSC, false, false>(p);
+}
+
+// the tail of a deferring launch: every listed row against its query tile, in full, with the launch's floors.  The grid is
+// n_qtiles x n_splits workgroups (knn_hi_task); workgroup `split` takes tiles split, split + n_splits, ... of its query tile's list and
+// leaves before any barrier when the list ends in front of its first.
+template <int RSC>
+__global__ __launch_bounds__(KW_THREADS, 1) void k_knn_hi_tail(KnnHiParams p) {
+    int qt, split;
+    if (!knn_hi_task(p, (int)blockIdx.x, qt, split)) return;
+    const int cnt = min(p.df_cnt[qt], p.df_cap);
+    for (int t = split; (int64_t)t * KW_M < cnt; t += p.n_splits) {
+        knn_hi_body<RSC, false, false, false, false, true>(p, 0.f, 0.f, 0, t);
+        __syncthreads();                                     // (the next tile's map and per-query terms go over this one's)
+    }
 }
 
 // the threshold pre-pass over the first rows of the store: same K loop, own symbol (profiles keep the two apart);

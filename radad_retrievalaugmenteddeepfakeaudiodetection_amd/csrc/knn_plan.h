@@ -470,6 +470,59 @@ static DealPlan knn_abandon_deal(const DealFacts& f) {
     return d;
 }
 
+// ---- a vetoed tile's few live rows, deferred to a dense tail (knn_hi.inc, k_knn_hi_abandon_defer / k_knn_hi_tail) --------------------
+// A tile task one wave vetoes is usually kept alive by a handful of its 256 rows.  In a DEFERRING launch the vetoing waves also find
+// WHICH rows fail the abandon's inequality; a tile with 1 ... KNN_DEFER_MAX_ROWS of them appends those rows (launch-relative numbers)
+// to the list of its QUERY TILE and is left exactly as a skipped tile is.  Behind the launch, on the same stream and in front of
+// everything that reads the candidate buffers, the tail kernel scores each list's rows in full against that query tile alone, with the
+// launch's floors and the scan's own stage loop and emit: a pair's accumulator does not depend on where its row sits in a tile, so the
+// candidates are the parent's.  The tail fetches the listed rows straight from the plane by per-lane 32-bit offsets (no copy, no
+// compact buffer of `capacity` rows), which is why a launch must address its rows in 32 bits.
+constexpr int KNN_DEFER_MAX_ROWS = 16;       // live rows a deferred tile task may list
+constexpr int KNN_DEFER_MAX_QTILES = 8;      // the first branch of knn_hi_task: one list per query tile
+// A launch is dealt or defers, never both, and the query preparation zeroes every launch's set of deal counters anyway: a deferring
+// launch counts in ITS set -- the entries of query tile qt's list where slot 0's ticket counters would be, the tile tasks deferred in
+// slot 1's first.
+constexpr int KNN_DEFER_SETS = KNN_DEAL_SETS;
+static_assert(KNN_DEFER_MAX_QTILES <= KNN_DEAL_MAX_QTILES && KNN_DEAL_SLOTS >= 2, "the deferral counts inside a deal counter set");
+constexpr int knn_defer_counter(int set, int qt) { return knn_deal_counter(set, 0, qt); }
+constexpr int knn_defer_tasks_counter(int set) { return knn_deal_counter(set, 1, 0); }
+constexpr int64_t KNN_DEFER_MAX_BYTES = ((int64_t)1 << 32) - ((int64_t)1 << 16);     // plane bytes of a launch the tail's offsets reach
+
+struct DeferFacts {
+    int opt_defer = 1;           // RADAD_KNN_OPT_ABANDON_DEFER
+    int ab_ck = 0;               // knn_abandon_launch of this launch (0: the sample, a K split, a per-call bias, the abandon off ...)
+    bool dealt = false;          // knn_abandon_deal of this launch
+    int launch = 0;              // the launch's number in its search
+    int64_t rows = 0;            // rows of the launch
+    int row_bytes = 0;
+    int n_qtiles = 0;            // knn_geometry_wide of the launch
+    int cus = 0;                 // compute units of the device
+};
+struct DeferPlan {
+    bool defer = false;
+    int64_t list_cap = 0;        // entries of one query tile's list: it cannot overflow
+    int tail_tiles = 0;          // KW_M-row tiles of a full list
+    int tail_splits = 0;         // the tail's grid is n_qtiles x tail_splits workgroups (a multiple of 8: knn_hi_task) ...
+    int tail_rounds = 0;         // ... and workgroup `split` takes tiles split, split + tail_splits, ...: at most this many
+};
+// entries of one query tile's list for a store of `rows` rows: every tile task lists at most KNN_DEFER_MAX_ROWS
+static int64_t knn_defer_list_cap(int64_t rows) { return ceil_div64(rows, KW_M) * KNN_DEFER_MAX_ROWS; }
+static DeferPlan knn_abandon_defer(const DeferFacts& f) {
+    DeferPlan d;
+    if (!f.opt_defer || f.ab_ck <= 0 || f.dealt || f.launch < 0 || f.launch >= KNN_DEFER_SETS || f.rows <= 0 || f.cus <= 0) return d;
+    if (f.n_qtiles < 1 || f.n_qtiles > KNN_DEFER_MAX_QTILES) return d;
+    if (f.row_bytes <= 0 || f.rows * f.row_bytes > KNN_DEFER_MAX_BYTES) return d;
+    d.defer = true;
+    d.list_cap = knn_defer_list_cap(f.rows);
+    d.tail_tiles = (int)ceil_div64(d.list_cap, KW_M);
+    // about one workgroup per CU over all query tiles, in eights, and no more than a full list has tiles
+    const int per_qt = std::max(8, f.cus / f.n_qtiles / 8 * 8);
+    d.tail_splits = std::min(per_qt, (d.tail_tiles + 7) / 8 * 8);
+    d.tail_rounds = (d.tail_tiles + d.tail_splits - 1) / d.tail_splits;
+    return d;
+}
+
 // ---- workspace layouts ------------------------------------------------------------------------------------------------------------
 // byte offsets of a search's buffers in the handle's workspace (knn_search_layout)
 struct SearchLayout {
