@@ -1011,6 +1011,66 @@ int radad_fuse_head_forward(const radad_head_weights* w, const float* tpp_dev /*
 int64_t radad_fuse_head_workspace_bytes(int64_t batch, int dim, int proj_dim);
 
 /* ------------------------------------------------------------------------------------------------
+ * RADADModel after the projection in training mode, forward and backward (radad_model.py:38-41,
+ * detection_model.py:41-72,123-126 under autograd; csrc/head_train.inc).  a_0 = fused; hidden layer i:
+ *   fused = Wf[:, :D] tpp + Wf[:, D:] proj + bf                              (the concatenation is never built)
+ *   z = W_i a_{i-1} + b_i;  per column over the batch: mean, var = mean_b (z - mean)^2 (biased), rstd = 1 / sqrt(var + eps)
+ *   xh = (z - mean) rstd;  y = xh gamma + beta;  a_i = max(y, 0) * mask_i * inv_keep
+ *   running_mean <- (1 - f) running_mean + f mean;  running_var <- (1 - f) running_var + f var B / (B - 1)    (in place)
+ *   logits = W_L a + b_L                                                      (the last layer: Linear only)
+ *   backward, G = d logits:  dW_L = G^T a, db_L = sum_b G, da = G W_L;  per hidden layer from last to first
+ *     dy = da * mask * inv_keep [a_i > 0], dgamma = sum_b dy xh, dbeta = sum_b dy, dxh = dy gamma,
+ *     dz = rstd (dxh - mean_b dxh - xh mean_b(dxh xh)), dW_i = dz^T a_{i-1}, db_i = sum_b dz, da_{i-1} = dz W_i;
+ *     df = da_0, dWf = df^T [tpp | proj], dbf = sum_b df, dproj = df Wf[:, D:], dtpp = df Wf[:, :D].
+ * A hidden layer whose bn_gamma / bn_beta are both NULL has no BatchNorm (xh is then z itself, dz = dy, rstd unused); NULL
+ * bn_running_mean / bn_running_var leave the running statistics alone.  masks_dev is a host array of n_layers - 1 device
+ * pointers, masks_dev[i] a [B, dims[i+1]] array of 0 / 1 floats drawn by the caller (NULL entry, or masks_dev NULL: no dropout
+ * there; inv_keep = 1 / (1 - p)).  The forward fills the saved buffers, the backward reads them (same weights, inputs, masks).
+ * A NULL member of radad_head_grads skips that gradient; dtpp_dev / dproj_dev NULL skip those products.  No float atomics:
+ * every sum has a fixed order, two runs give the same bits.  fp32 throughout.
+ * Limits, each one RADAD_EINVAL before any HIP call: 1 <= n_layers <= RADAD_HEAD_MAX_LAYERS; no width (proj_dim, dims[i])
+ * above 8192; dims[0] == proj_dim; dim <= 2^22 - 64; batch < 2^31 - 128; batch == 1 with a BatchNorm layer; a NULL required
+ * buffer, weight or saved array; a half-NULL gamma / beta or running mean / var pair; a short workspace.  batch == 0 is RADAD_OK
+ * without a launch.  One workspace size serves both calls; -1 for a bad shape.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct radad_head_train_weights {
+    const float *wf, *bf;                                /* fuse [P, D+P], [P]                                  */
+    int32_t n_layers;                                    /* Linear layers of the detection MLP                  */
+    int32_t dims[RADAD_HEAD_MAX_LAYERS + 1];             /* dims[0] = P, dims[i+1] = out width of layer i       */
+    const float* lw[RADAD_HEAD_MAX_LAYERS];              /* [dims[i+1], dims[i]]                                */
+    const float* lb[RADAD_HEAD_MAX_LAYERS];              /* [dims[i+1]]                                         */
+    const float* bn_gamma[RADAD_HEAD_MAX_LAYERS];        /* hidden layers: [dims[i+1]], or NULL with bn_beta    */
+    const float* bn_beta[RADAD_HEAD_MAX_LAYERS];
+    float* bn_running_mean[RADAD_HEAD_MAX_LAYERS];       /* updated in place by the forward, or NULL pair       */
+    float* bn_running_var[RADAD_HEAD_MAX_LAYERS];
+    float bn_eps[RADAD_HEAD_MAX_LAYERS];
+    float bn_factor[RADAD_HEAD_MAX_LAYERS];              /* f: momentum, or 1 / num_batches_tracked             */
+} radad_head_train_weights;
+typedef struct radad_head_saved {
+    float* fused;                                        /* [B, P]                                              */
+    float* xh[RADAD_HEAD_MAX_LAYERS];                    /* hidden layers: normalised pre-activation [B, d]     */
+    float* rstd[RADAD_HEAD_MAX_LAYERS];                  /* [d] (BatchNorm layers only)                         */
+    float* act[RADAD_HEAD_MAX_LAYERS];                   /* what the next layer reads [B, d]                    */
+} radad_head_saved;
+typedef struct radad_head_grads {   /* shapes of the matching radad_head_train_weights members */
+    float *dwf, *dbf;
+    float* dlw[RADAD_HEAD_MAX_LAYERS];
+    float* dlb[RADAD_HEAD_MAX_LAYERS];
+    float* dgamma[RADAD_HEAD_MAX_LAYERS];
+    float* dbeta[RADAD_HEAD_MAX_LAYERS];
+} radad_head_grads;
+int64_t radad_fuse_head_train_workspace_bytes(int64_t batch, int dim, int proj_dim, int n_layers, const int32_t* dims);
+int radad_fuse_head_train_forward(const radad_head_train_weights* w, const float* tpp_dev /*[B,D]*/, const float* proj_dev /*[B,P]*/,
+                                  const float* const* masks_dev, float inv_keep, int64_t batch, int dim, int proj_dim,
+                                  const radad_head_saved* saved, float* logits_out_dev /*[B, dims[n_layers]]*/,
+                                  float* workspace_dev, int64_t workspace_bytes, int device, void* stream);
+int radad_fuse_head_backward(const radad_head_train_weights* w, const float* tpp_dev, const float* proj_dev,
+                             const float* const* masks_dev, float inv_keep, const radad_head_saved* saved,
+                             const float* grad_logits_dev /*[B, dims[n_layers]] contiguous*/, int64_t batch, int dim, int proj_dim,
+                             const radad_head_grads* grads, float* dtpp_dev /*[B,D] or NULL*/, float* dproj_dev /*[B,P] or NULL*/,
+                             float* workspace_dev, int64_t workspace_bytes, int device, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Synthetic inputs (bench / tests only): a stateless integer hash so host and device produce the
  * SAME bits for element (seed, row, col).  See oracle/synth.py for the host twin.
  * ---------------------------------------------------------------------------------------------- */

@@ -71,6 +71,29 @@ class HeadWeights(C.Structure):
                 ("bn_scale", C.c_void_p * HEAD_MAX_LAYERS), ("bn_shift", C.c_void_p * HEAD_MAX_LAYERS)]
 
 
+class HeadTrainWeights(C.Structure):    # radad_head_train_weights
+    _fields_ = [("wf", C.c_void_p), ("bf", C.c_void_p), ("n_layers", C.c_int32),
+                ("dims", C.c_int32 * (HEAD_MAX_LAYERS + 1)),
+                ("lw", C.c_void_p * HEAD_MAX_LAYERS), ("lb", C.c_void_p * HEAD_MAX_LAYERS),
+                ("bn_gamma", C.c_void_p * HEAD_MAX_LAYERS), ("bn_beta", C.c_void_p * HEAD_MAX_LAYERS),
+                ("bn_running_mean", C.c_void_p * HEAD_MAX_LAYERS), ("bn_running_var", C.c_void_p * HEAD_MAX_LAYERS),
+                ("bn_eps", C.c_float * HEAD_MAX_LAYERS), ("bn_factor", C.c_float * HEAD_MAX_LAYERS)]
+
+
+class HeadSaved(C.Structure):           # radad_head_saved: what the training forward keeps for the backward
+    _fields_ = [("fused", C.c_void_p), ("xh", C.c_void_p * HEAD_MAX_LAYERS), ("rstd", C.c_void_p * HEAD_MAX_LAYERS),
+                ("act", C.c_void_p * HEAD_MAX_LAYERS)]
+
+
+class HeadGrads(C.Structure):           # radad_head_grads
+    _fields_ = [("dwf", C.c_void_p), ("dbf", C.c_void_p), ("dlw", C.c_void_p * HEAD_MAX_LAYERS),
+                ("dlb", C.c_void_p * HEAD_MAX_LAYERS), ("dgamma", C.c_void_p * HEAD_MAX_LAYERS),
+                ("dbeta", C.c_void_p * HEAD_MAX_LAYERS)]
+
+
+HeadMasks = C.c_void_p * HEAD_MAX_LAYERS    # host array of per-hidden-layer dropout mask pointers
+
+
 # name -> (restype, argtypes); every symbol include/radad_hip.h declares
 SIGNATURES = {
     "radad_abi_version": (C.c_int, []),
@@ -218,6 +241,13 @@ SIGNATURES = {
     "radad_fuse_head_forward": (C.c_int, [C.POINTER(HeadWeights), C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "radad_fuse_head_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "radad_fuse_head_train_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.c_int, c_i32p]),
+    "radad_fuse_head_train_forward": (C.c_int, [C.POINTER(HeadTrainWeights), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                                C.c_float, C.c_int64, C.c_int, C.c_int, C.POINTER(HeadSaved), C.c_void_p,
+                                                C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "radad_fuse_head_backward": (C.c_int, [C.POINTER(HeadTrainWeights), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_float,
+                                           C.POINTER(HeadSaved), C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(HeadGrads),
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "radad_synth_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_uint64, C.c_int, C.c_void_p]),
     "radad_synth_audio": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int, C.c_void_p]),
 }

@@ -40,6 +40,7 @@ class Config:
         self.detection_dropout = 0.1
         self.use_batch_norm = True
         self.use_layer_norm = False
+        self.head_train_hip = False   # True: a training-mode fuse_and_detect runs the fuse Linear and the detection MLP's HIP forward + backward (csrc/head_train.inc) instead of the torch modules
         # device (config.py:89)
         import torch
         self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")

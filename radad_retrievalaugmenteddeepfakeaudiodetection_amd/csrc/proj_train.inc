@@ -382,14 +382,11 @@ inline size_t km_part_bytes(int64_t M, int N, int64_t Kr, bool stacked_out) {
     return (S > 1 || stacked_out) ? al256((size_t)S * (size_t)M * (size_t)N * sizeof(float)) : 0;
 }
 
-// out [M,N] = op(A) B with B = [b; b_hi] stacked at reduction row kr_lo; rows [m_lo, M) of the result go to out_hi when given
+// part (or the result itself, with one split) = op(A) B over S reduction splits of cps chunks, B = [b; b_hi] stacked at row kr_lo
 template <bool A_KM>
-int gemm_km(const float* a, int64_t lda, const float* b, const float* b_hi, int kr_lo, int64_t ldb, int64_t M, int N, int64_t Kr,
-            float* part, float* out, float* out_hi, int64_t m_lo, hipStream_t st) {
-    int S, cps;
-    red_plan(M, N, Kr, &S, &cps);
-    const bool direct = S == 1 && !out_hi;
-    GemmKmParams p{a, lda, b, b_hi ? b_hi : b, b_hi ? kr_lo : (int)Kr, ldb, direct ? out : part, (int)M, N, (int)Kr, cps};
+int gemm_km_launch(const float* a, int64_t lda, const float* b, const float* b_hi, int kr_lo, int64_t ldb, int64_t M, int N, int64_t Kr,
+                   float* dst, int S, int cps, hipStream_t st) {
+    GemmKmParams p{a, lda, b, b_hi ? b_hi : b, b_hi ? kr_lo : (int)Kr, ldb, dst, (int)M, N, (int)Kr, cps};
     auto a16 = [](const float* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     const bool vec = N % 4 == 0 && ldb % 4 == 0 && a16(p.b) && a16(p.b_hi) && lda % 4 == 0 && a16(a) && (A_KM ? M % 4 == 0 : Kr % 4 == 0);
     const auto kern = vec ? k_gemm_km<A_KM, true> : k_gemm_km<A_KM, false>;
@@ -400,6 +397,17 @@ int gemm_km(const float* a, int64_t lda, const float* b, const float* b_hi, int 
     hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div64(M, GT), (unsigned)ceil_div64(N, GT), (unsigned)S), dim3(G_THREADS), lds, st,
                        p);
     RADAD_HIP_CHECK(hipGetLastError());
+    return RADAD_OK;
+}
+
+// out [M,N] = op(A) B with B = [b; b_hi] stacked at reduction row kr_lo; rows [m_lo, M) of the result go to out_hi when given
+template <bool A_KM>
+int gemm_km(const float* a, int64_t lda, const float* b, const float* b_hi, int kr_lo, int64_t ldb, int64_t M, int N, int64_t Kr,
+            float* part, float* out, float* out_hi, int64_t m_lo, hipStream_t st) {
+    int S, cps, rc;
+    red_plan(M, N, Kr, &S, &cps);
+    const bool direct = S == 1 && !out_hi;
+    if ((rc = gemm_km_launch<A_KM>(a, lda, b, b_hi, kr_lo, ldb, M, N, Kr, direct ? out : part, S, cps, st))) return rc;
     if (!direct) {
         const int64_t total = M * N;
         hipLaunchKernelGGL(k_km_finish, dim3((unsigned)std::min<int64_t>(ceil_div64(total, 256), 4096)), dim3(256), 0, st, part, S,
