@@ -110,6 +110,17 @@ int radad_knn_create_ex(int dim, int metric, int store_dtype, int device, int64_
  *                            a skipped one, and scores the listed rows in full against their query tile in a tail launch behind the scan
  *                            launch / a vetoed tile is multiplied in full.  Same candidates either way.  Measured:
  *                            profiles/abandon_defer_ab.txt; RADAD_KNN_OPT_ABANDON 0 turns it off too; no environment override
+ *   RADAD_KNN_OPT_ABANDON_AHEAD  1 (default) / 0: in an abandoning launch that is not dealt, the checkpoint stage of a tile that is
+ *                            expected to leave (skipped or deferred: the workgroup's last tested tile left, or it has tested none yet)
+ *                            fetches the NEXT tile's first stage instead of its own next one, so that a leaving tile costs one barrier
+ *                            and no exposed DMA round trip; a tile that stays after all fetches its own stage then and waits one barrier
+ *                            more than before / the checkpoint stage fetches the tile's own next stage, and a leaving tile fetches
+ *                            the next tile's head behind its checkpoint.  Same scores, candidates and counts either way.  Measured
+ *                            (profiles/abandon_ahead_ab.txt): 1.021-1.025 -> 0.942-0.945 ms per benchmark step, where every tile task
+ *                            leaves.  KNOWN LOSS: a store whose tiles strictly alternate between leaving and staying is predicted wrongly
+ *                            at every tile and searches 3 % slower with 1 than with 0 (1 M x 512, 1024 queries: 0.975 -> 1.005 ms); the
+ *                            predictor has no hysteresis.  A store where every tile stays costs the same either way.
+ *                            RADAD_KNN_OPT_ABANDON 0 turns it off too; no environment override
  * The environment variables RADAD_KNN_HI, RADAD_KNN_CENTRE, RADAD_KNN_SMALLQ_HI, RADAD_WIDE_MIN_Q override the DEFAULTS of handles
  * created while they are set (announced once per process on stderr); the product path never needs them. */
 #define RADAD_KNN_OPT_HI_PLANE 0
@@ -121,6 +132,7 @@ int radad_knn_create_ex(int dim, int metric, int store_dtype, int device, int64_
 #define RADAD_KNN_OPT_RANGE_SMALLQ 6
 #define RADAD_KNN_OPT_ABANDON_DEAL 7
 #define RADAD_KNN_OPT_ABANDON_DEFER 8
+#define RADAD_KNN_OPT_ABANDON_AHEAD 9
 int radad_knn_set_option(radad_knn_t h, int option, int value);
 int radad_knn_destroy(radad_knn_t h);
 int radad_knn_dim(radad_knn_t h, int* dim);
@@ -239,6 +251,10 @@ int radad_knn_last_abandon_deal(radad_knn_t h, int* launches, int* workgroups, i
  * tasks that listed their live rows and left (`checked` counts them, `skipped` does not), the rows listed over all query tiles, and the
  * tail launches made.  All 0 when no launch deferred. */
 int radad_knn_last_abandon_defer(radad_knn_t h, int64_t* tile_tasks_deferred, int64_t* rows_listed, int* tail_launches);
+/* ... and what became of the heads its launches fetched ahead (RADAD_KNN_OPT_ABANDON_AHEAD; synchronises with the search): the tile tasks
+ * that left into a next tile's head already fetched (`heads_used`), and those that stayed and fetched their own stage over one
+ * (`heads_wasted`).  Both 0 when no launch of the last search fetched ahead. */
+int radad_knn_last_abandon_ahead(radad_knn_t h, int64_t* heads_used, int64_t* heads_wasted);
 /* the f16 plane the certified scans read, once a search has built it: built (0/1); centred = the common component (column mean)
  * of the rows is subtracted before rounding (stores of embeddings that share most of their mean); one_scale = one power-of-two
  * scale for all rows (rows of one magnitude: the scan applies no per-score arithmetic) */

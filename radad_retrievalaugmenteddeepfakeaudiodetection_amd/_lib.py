@@ -26,6 +26,7 @@ KNN_OPT_HI_PLANE, KNN_OPT_CENTRE, KNN_OPT_SMALLQ_HI, KNN_OPT_WIDE_MIN_Q, KNN_OPT
 KNN_OPT_RANGE_SMALLQ = 6                      # RADAD_KNN_OPT_RANGE_SMALLQ
 KNN_OPT_ABANDON_DEAL = 7                      # RADAD_KNN_OPT_ABANDON_DEAL
 KNN_OPT_ABANDON_DEFER = 8                     # RADAD_KNN_OPT_ABANDON_DEFER
+KNN_OPT_ABANDON_AHEAD = 9                     # RADAD_KNN_OPT_ABANDON_AHEAD
 IVF_OPT_HI_SCAN = 0
 IVF_OPT_PQ_FILTER = 1      # RADAD_IVF_OPT_PQ_FILTER
 IVF_SCAN_KINDS = ("f32_lists", "hi_lists", "exact_flat")
@@ -148,6 +149,7 @@ SIGNATURES = {
     "radad_knn_last_abandon": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "radad_knn_last_abandon_deal": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "radad_knn_last_abandon_defer": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "radad_knn_last_abandon_ahead": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "radad_knn_plane_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "radad_knn_plane_rebuilds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "radad_knn_tuning_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),

@@ -2964,6 +2964,9 @@ struct radad_knn_s {
     int64_t defer_list_cap = 0;
     int last_defer_launches = 0; // tails launched by the last search (radad_knn_last_abandon_defer) ...
     unsigned last_defer_sets = 0;// ... and the counter sets they used, one bit each
+    // the next tile's head fetched at the abandon checkpoint (knn_abandon_ahead, knn_plan.h): two counters per launch in its set of deal_cnt
+    int opt_abandon_ahead = 1;   // RADAD_KNN_OPT_ABANDON_AHEAD (measured: profiles/abandon_ahead_ab.txt)
+    unsigned last_ahead_sets = 0;// the counter sets the last search's prefetching launches used, one bit each (radad_knn_last_abandon_ahead)
     // queries the certificate rejected in the most recent search: counted on the device, copied to pinned host memory
     // behind the search (no synchronisation inside search); feeds the adaptive tuning and radad_knn_last_recheck
     int* host_count = nullptr;   // pinned [2][8]: rejected queries, sum of candidates, rejections by reason x 4, [6] the report's stamp, [7] its batch size
@@ -3387,6 +3390,10 @@ int radad_knn_set_option(radad_knn_t h, int option, int value) {
             RADAD_REQUIRE(value == 0 || value == 1, "radad_knn_set_option: ABANDON_DEFER takes 0 or 1");
             h->opt_abandon_defer = value;
             return RADAD_OK;
+        case RADAD_KNN_OPT_ABANDON_AHEAD:
+            RADAD_REQUIRE(value == 0 || value == 1, "radad_knn_set_option: ABANDON_AHEAD takes 0 or 1");
+            h->opt_abandon_ahead = value;
+            return RADAD_OK;
         case RADAD_KNN_OPT_RANGE_SMALLQ:
             RADAD_REQUIRE(value == 0 || value == 1, "radad_knn_set_option: RANGE_SMALLQ takes 0 or 1");
             h->opt_range_smallq = value;
@@ -3609,7 +3616,7 @@ static bool knn_abandon_terms_ready(radad_knn_t h, int64_t nq) {
         h->ab_ws_bytes = A.bytes;
     }
     // (the ticket counters of dealt launches: without them the launches stay static)
-    if ((h->opt_abandon_deal || h->opt_abandon_defer) && !h->deal_cnt && hipMalloc(&h->deal_cnt, KNN_DEAL_COUNTERS * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); h->deal_cnt = nullptr; }
+    if ((h->opt_abandon_deal || h->opt_abandon_defer || h->opt_abandon_ahead) && !h->deal_cnt && hipMalloc(&h->deal_cnt, KNN_DEAL_COUNTERS * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); h->deal_cnt = nullptr; }
     // the deferral's lists: one per query tile, each as long as a launch over the whole store could fill (without them nothing defers)
     if (h->opt_abandon_defer && h->deal_cnt && h->defer_list_cap < knn_defer_list_cap(h->ntotal)) {
         (void)hipDeviceSynchronize();
@@ -3656,7 +3663,7 @@ static const float* knn_prepare_queries(radad_knn_t h, const ScanPlan& p, const 
             hp.suf_from = h->ab_from;
             hp.suf_out = reinterpret_cast<float*>(static_cast<char*>(h->ab_ws) + A.rq);
             hp.ab_slack_out = reinterpret_cast<float*>(static_cast<char*>(h->ab_ws) + A.slack);
-            hp.zero_deal = (h->opt_abandon_deal || h->opt_abandon_defer) ? h->deal_cnt : nullptr;         // every launch's ticket counters, once per search, in a kernel the search runs anyway
+            hp.zero_deal = (h->opt_abandon_deal || h->opt_abandon_defer || h->opt_abandon_ahead) ? h->deal_cnt : nullptr;         // every launch's ticket counters, once per search, in a kernel the search runs anyway
         }
         launch_hi_rows(hp, st);
     }
@@ -3782,6 +3789,7 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
     h->last_ab_tasks = 0; h->last_o_ab = L.fcount + KNN_AB_COUNTER0 * sizeof(int);
     h->last_deal_launches = h->last_deal_workgroups = h->last_deal_granule = 0;
     h->last_defer_launches = 0; h->last_defer_sets = 0;
+    h->last_ahead_sets = 0;
     RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(sample), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // sample pre-pass: the (k + margin)-th best score over the first rows of the store is a score at least k rows reach, so the
@@ -3871,6 +3879,13 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
             ff.launch = (int)i; ff.rows = rp.n; ff.row_bytes = rp.row_bytes; ff.n_qtiles = std::max(gq, rp.n_qtiles); ff.cus = h->n_cus;
             fp = knn_abandon_defer(ff);
             if (fp.defer && fp.list_cap > h->defer_list_cap) fp.defer = false;
+        }
+        // the checkpoint stage fetches the next tile's head where the tile is expected to leave (knn_abandon_ahead): the static-chunk
+        // kernels, deferring or not
+        if (h->deal_cnt && knn_abandon_ahead(h->opt_abandon_ahead, ab_ck, rp.deal_cnt != nullptr, (int)i)) {
+            rp.ab_ahead = 1;
+            rp.ah_count = h->deal_cnt + knn_ahead_counter((int)i);
+            h->last_ahead_sets |= 1u << i;
         }
         KnnHiParams tp;
         auto tail_fn = launch_fn;
@@ -5131,6 +5146,23 @@ int radad_knn_last_abandon_defer(radad_knn_t h, int64_t* tile_tasks_deferred, in
         *tile_tasks_deferred += c[knn_defer_tasks_counter(s)];
     }
     *tail_launches = h->last_defer_launches;
+    return RADAD_OK;
+}
+
+int radad_knn_last_abandon_ahead(radad_knn_t h, int64_t* heads_used, int64_t* heads_wasted) {
+    RADAD_REQUIRE(h && heads_used && heads_wasted, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    *heads_used = *heads_wasted = 0;
+    if (h->last_ab_tasks <= 0 || h->last_ahead_sets == 0 || !h->deal_cnt) return RADAD_OK;          // the last search prefetched no head
+    RADAD_HIP_CHECK(knn_wait_last_search(h));
+    int c[KNN_DEAL_COUNTERS];
+    RADAD_HIP_CHECK(hipMemcpy(c, h->deal_cnt, sizeof(c), hipMemcpyDeviceToHost));
+    for (int s = 0; s < KNN_DEAL_SETS; ++s) {
+        if (!(h->last_ahead_sets >> s & 1u)) continue;
+        *heads_used += c[knn_ahead_counter(s)];
+        *heads_wasted += c[knn_ahead_counter(s) + 1];
+    }
     return RADAD_OK;
 }
 

@@ -88,13 +88,17 @@ struct KnnHiParams {
     int df_cap = 0;                       // row tiles of the launch x KNN_DEFER_MAX_ROWS: a list cannot overflow
     int* df_tasks = nullptr;              // [1] tile tasks deferred (one atomic per workgroup)
     unsigned df_bytes = 0;                // the tail: bytes of the launch's rows (the plane is addressed through ONE 32-bit descriptor)
+    // THE HEAD PREFETCH (ABANDON without DEAL; RADAD_KNN_OPT_ABANDON_AHEAD): the checkpoint stage of a tile predicted to leave
+    // (knn_ahead_speculate, knn_plan.h) fetches the NEXT tile's stage 0 instead of its own stage ab_ck
+    int ab_ahead = 0;
+    int* ah_count = nullptr;              // [2] tile tasks that left into a head already fetched, tile tasks that stayed and threw one away
 };
 static_assert(std::is_trivially_copyable_v<KnnHiParams>, "kernel argument");
 
 constexpr size_t knn_hi_lds_bytes(bool abandon = false, bool defer = false) {
-    // (ABANDON: + three per-query arrays and the two veto words; DEFER: + the two 256-bit masks of live rows)
+    // (ABANDON: + three per-query arrays and the two veto words; DEFER: + the three 256-bit masks of live rows)
     return 2 * KW_STAGE_BYTES + sizeof(float) * KW_N * 4 + sizeof(float) * 2 * KW_M * 2 + 16 + (abandon ? sizeof(float) * KW_N * 3 + 16 : 0) +
-           (defer ? 64 : 0);
+           (defer ? 96 : 0);
 }
 
 // RSC: 0 = IP with one scale for all rows (un-centred cosine stores, fp16 stores): no per-score arithmetic at all;
@@ -187,7 +191,7 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
     float* s_arq = s_at + KW_N;                                              // [KW_N] |qh_j[64 ck:]|
     float* s_asl = s_arq + KW_N;                                             // [KW_N] accumulation slack, accumulator units
     int* s_veto = reinterpret_cast<int*>(s_asl + KW_N);                      // [2] by tile parity: the tile (row0 / KW_M) a wave vetoed last
-    unsigned* s_live = reinterpret_cast<unsigned*>(s_veto + 4);              // DEFER: [2][8] by tile parity: bit r of the 256 = row r is live
+    unsigned* s_live = reinterpret_cast<unsigned*>(s_veto + 4);              // DEFER: [3][8] by tile number mod 3: bit r of the 256 = row r is live
     int* s_map = reinterpret_cast<int*>(s_rs);                               // MAPPED: [KW_M] the tile's rows of the launch, -1 past the list's
                                                                              // end (s_rs: RSC 0 and 3 never use it)
 
@@ -235,7 +239,7 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
         }
     }
     if constexpr (ABANDON) { if (tid < 2) s_veto[tid] = -1; }
-    if constexpr (DEFER) { if (tid < 16) s_live[tid] = 0u; }
+    if constexpr (DEFER) { if (tid < 24) s_live[tid] = 0u; }
     if constexpr (MAPPED) {
         // the tile's rows, in LDS before the first fetch needs them (one tile per call: no parity)
         if (tid < KW_M) s_map[tid] = chunk_begin + tid < chunk_end ? p.df_list[(int64_t)qt * p.df_cap + chunk_begin + tid] : -1;
@@ -461,13 +465,58 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
     // the tile emits nothing and its remaining stages and its epilogue are left out.  The set of emitted candidates is the parent's.
     // Every lane takes the maximum of its 32 partial scores per query (4 queries); a wave that cannot agree writes the tile's number
     // into s_veto[parity]; the stage's own barrier publishes it; everyone reads it: the decision is workgroup-uniform, no spinning, no
-    // communication between workgroups.  (The word holds a tile NUMBER and is never reset; the next write to the same parity is two
-    // tiles on, behind at least two more barriers.)
+    // communication between workgroups.  (The word holds a tile NUMBER and is never reset.  Tile t's word is read between t's checkpoint
+    // barrier and the next barrier anyone reaches, which is at the latest the first barrier of tile t + 1 -- every tile has one, a
+    // leaving tile exactly one since the head prefetch.  The next write to the same parity is in a stage of tile t + 2, behind that
+    // barrier: one barrier per leaving tile is enough.)
+    // THE HEAD PREFETCH (ahead_on; DESIGN §4.1).  A tile that leaves at its checkpoint used to have fetched its own stage ab_ck for nothing,
+    // then issued the next tile's stage 0 over it and sat through a barrier that waited for nothing else.  With ahead_on the checkpoint
+    // stage of a tested tile that has a next tile and is PREDICTED to leave (one scalar per workgroup: knn_ahead_speculate / knn_ahead_next,
+    // knn_plan.h -- the text the host model walks) fetches the next tile's stage 0 instead.  A tile that leaves then goes straight into
+    // the next tile's first stage: ONE barrier per leaving tile.  A tile that stays issues its own stage ab_ck over the head and waits one
+    // barrier for it -- the bubble a leaving tile used to pay -- and the K loop goes on as it was; its last stage fetches the next tile's
+    // head as ever.  What is fetched when changes no accumulator: the scores are the same bit for bit.
+    // What relied on the second barrier of a leaving tile, with the argument for one:
+    //   s_veto[parity]: above.
+    //   s_live: three masks by tile number mod 3, below where they are cleared.
+    //   s_rb (RSC 3): tile t + 1's accumulator starts used to be parked behind tile t's first barrier, and with the checkpoint at stage 0
+    //     nothing would separate that store from tile t + 1's first stage, which reads them.  With ahead_on they are loaded in front of
+    //     tile t's first stage and stored in front of its first barrier.  The parity they go to was last read by tile t - 1's FIRST stage
+    //     (RSC 3's epilogue reads neither s_rs nor s_rb), which lies in front of tile t - 1's first barrier.
+    //   the dealt kernel's s_veto[2]: a dealt launch does not prefetch heads (ahead_on is false for DEAL) and keeps its two barriers.
+    //   the deferral's list append: carried to behind the next tile's first barrier (df_flush).
     int ab_ck = 0, ab_checked = 0, ab_skipped = 0, ab_deferred = 0;
     (void)ab_deferred;
     if constexpr (ABANDON) ab_ck = p.ab_ck;
-    int tile_par = 0;
-    for (int64_t row0 = row_first; row0 < chunk_end; row0 = DEAL ? d_row_adv : row0 + KW_M, tile_par ^= 1) {
+    const bool ahead_on = ABANDON && !DEAL && p.ab_ahead != 0;      // (a kernel argument: uniform)
+    bool ah_pred = knn_ahead_initial();
+    int ah_used = 0, ah_wasted = 0;
+    (void)ah_pred; (void)ah_used; (void)ah_wasted;
+    // DEFER: a deferred tile's list entries, written behind the NEXT tile's first barrier (or behind the tile loop): lane 0 of wave 0
+    // holds the returning atomic's slot, lane l the nibble of rows 4 l ... 4 l + 3 and their rank among the tile's live rows (rank << 4
+    // | nibble); df_row = the tile's first row.  Nothing waits for the atomic in front of the next tile's stage: the barrier behind that
+    // stage waits vmcnt(0) anyway.
+    // (REGISTERS: df_slot and df_pack, and RSC 3's park_v below, are live across a whole stage.  With them the deferring kernels stand
+    // at 246 (RSC 0) / 250 (RSC 3) VGPRs, no scratch -- 6 below the 256 at which hipcc starts to spill inside the K loop.  Anything
+    // more carried across a stage here has to be paid for elsewhere: check -Rpass-analysis=kernel-resource-usage before a GPU run.)
+    bool df_pend = false;
+    int df_slot = 0, df_row = 0;
+    unsigned df_pack = 0u;
+    (void)df_pend; (void)df_slot; (void)df_row; (void)df_pack;
+    auto df_flush = [&]() {
+        if (wave == 0) {
+            int* dst = p.df_list + (int64_t)qt * p.df_cap + __builtin_amdgcn_readfirstlane(df_slot) + (int)(df_pack >> 4);
+            const int row_l = df_row + 4 * (lane & 63);
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                if (df_pack & (1u << b)) { *dst = row_l + b; ++dst; }
+            }
+        }
+        df_pend = false;
+    };
+    int tile_par = 0, live_slot = 0;
+    (void)live_slot;
+    for (int64_t row0 = row_first; row0 < chunk_end; row0 = DEAL ? d_row_adv : row0 + KW_M, tile_par ^= 1, live_slot = (live_slot == 2 ? 0 : live_slot + 1)) {
         int64_t row_next = row0 + KW_M;
         bool d_draw = false;
         if constexpr (DEAL) {
@@ -483,9 +532,9 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
         const bool has_next = row_next < chunk_end;
         // THE GATE, tile side (scalars only): the test runs iff it can succeed
         float ab_ry = 0.f;
-        bool ab_check = false, ab_skip = false, ab_defer = false;
+        bool ab_check = false, ab_skip = false, ab_defer = false, ab_spec = false;
         int df_ns = 0;
-        (void)ab_defer; (void)df_ns;
+        (void)ab_defer; (void)df_ns; (void)ab_spec;
         if constexpr (ABANDON) {
             ab_ry = p.ab_ry[row0 >> 8] * (1.0f + 0x1p-10f);
             ab_check = knn_hi_gate(ab_amin, ab_rmax, p.ab_ry[row0 >> 8], RSC == 3 ? p.ab_b[row0 >> 8] : 0.f);
@@ -498,14 +547,27 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
             const int stage = gbuf & 1;
             const bool more_k = kc + 1 < nk;
             const bool fetch = (more_k || has_next) && !RADAD_DBG(p.debug, 2);
-            const int nkc = k_lo + (more_k ? kc + 1 : 0);
-            auto dma_a = [&]() { if (fetch && grp_half == 0) dma_half(more_k ? cur_desc : next_desc, stage ^ 1, nkc, 0); };
+            const bool at_ck = ABANDON && ab_check && kc + 1 == ab_ck;      // the checkpoint stage (wave-uniform)
+            const bool after_ck = ABANDON && ab_check && kc == ab_ck;
+            // the head prefetch: this stage fetches what the tile's LAST stage would, the next tile's stage 0 (block-uniform)
+            const bool spec = ABANDON && !DEAL && ahead_on && at_ck && more_k && knn_ahead_speculate(ah_pred, has_next);
+            const bool own_k = more_k && !spec;
+            const int nkc = k_lo + (own_k ? kc + 1 : 0);
+            auto dma_a = [&]() { if (fetch && grp_half == 0) dma_half(own_k ? cur_desc : next_desc, stage ^ 1, nkc, 0); };
             auto dma_b = [&]() { if (fetch && grp_half == 1) dma_half(q_desc, stage ^ 1, nkc, 1); };
             const char* a_row = smem + stage * KW_STAGE_BYTES + rd_a;
             const char* b_row = smem + stage * KW_STAGE_BYTES + rd_b;
             const float* rb_t = s_rb + tile_par * KW_M + wm * 128 + 4 * lq;
-            const bool at_ck = ABANDON && ab_check && kc + 1 == ab_ck;      // the checkpoint stage (wave-uniform)
-            const bool after_ck = ABANDON && ab_check && kc == ab_ck;
+            // (ahead_on, RSC 3: the next tile's accumulator starts, loaded here and stored in front of this stage's barrier: see above)
+            const bool park_early = ABANDON && !DEAL && RSC == 3 && ahead_on && kc == 0 && has_next;
+            float park_v = 0.f;
+            if constexpr (ABANDON && !DEAL && RSC == 3) {
+                if (park_early) {
+                    int t = tid;
+                    asm volatile("" : "+v"(t));
+                    if (t < KW_M && row_next + t < chunk_end) park_v = p.bias_sign * p.rbias[row_next + t];
+                }
+            }
             int d_ticket = 0;
             if constexpr (DEAL) {
                 // (the counter's address goes through an OPAQUE per-lane zero: with an address it can prove uniform hipcc rewrites the
@@ -568,16 +630,27 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
 #pragma unroll
                             for (int w = 0; w < 4; ++w) {
                                 const unsigned v = (((live >> (8 * w)) & 15u) << sh) | (((live >> (8 * w + 4)) & 15u) << (16 + sh));
-                                if (v) atomicOr(&s_live[tile_par * 8 + wm * 4 + w], v);
+                                if (v) atomicOr(&s_live[live_slot * 8 + wm * 4 + w], v);
                             }
                         }
                     }
                 }
             }
             if constexpr (DEFER) {
-                // the OTHER parity's mask is cleared for the tile after this one: its readers left it behind a barrier (the rest of
-                // the last tile's K loop, or its skip's), its next writers come behind this tile's
-                if (kc == 0 && tid < 8) s_live[(tile_par ^ 1) * 8 + tid] = 0u;
+                // the mask the NEXT tile will write (tile number + 1 mod 3 -- the one tile t - 2 wrote) is cleared here, in front of this
+                // tile's first barrier.  Its readers read it between tile t - 2's checkpoint barrier and the next barrier they reach, at
+                // the latest tile t - 1's first; this store lies behind that one.  Its next writers are in a stage of tile t + 1, behind
+                // this tile's first barrier.  (Two masks by parity needed the leaving tile's second barrier: with one, wave 0 clears tile
+                // t - 1's mask here while another wave still counts its bits; cleared behind this tile's first barrier instead, the store
+                // races with the next tile's atomicOr.)
+                if (kc == 0 && tid < 8) s_live[(live_slot == 2 ? 0 : live_slot + 1) * 8 + tid] = 0u;
+            }
+            if constexpr (ABANDON && !DEAL && RSC == 3) {
+                if (park_early) {
+                    int t = tid;
+                    asm volatile("" : "+v"(t));
+                    if (t < KW_M) s_rb[(tile_par ^ 1) * KW_M + t] = park_v;
+                }
             }
             if constexpr (DEAL) {
                 if (kc == 0 && d_draw && tid == 0) s_veto[2] = d_ticket;
@@ -588,13 +661,17 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
             __syncthreads();     // waits vmcnt(0): the stage issued above has landed for everyone
             KH_STAMP(6);
             ++gbuf;
-            if (kc == 0 && has_next) park_row_terms(row_next, tile_par ^ 1);
+            if (kc == 0 && has_next && !park_early) park_row_terms(row_next, tile_par ^ 1);
+            if constexpr (DEFER) {
+                if (kc == 0 && df_pend) df_flush();          // the tile before this one was deferred: its atomic has returned
+            }
             if constexpr (DEAL) {
                 if (kc == 0 && d_draw) d_next2 = deal_tile(__builtin_amdgcn_readfirstlane(s_veto[2]));
             }
             if constexpr (ABANDON) {
                 if (at_ck) {
                     ++ab_checked;
+                    ab_spec = spec;
                     if (__builtin_amdgcn_readfirstlane(s_veto[tile_par]) != (int)(row0 >> 8)) { ab_skip = true; break; }
                     if constexpr (DEFER) {
                         // vetoed: how many rows of the tile (positions < rowlimit) are live; everyone reads the same eight words
@@ -603,33 +680,48 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
                         for (int w = 0; w < 8; ++w) {
                             const int valid = min(32, max(0, rowlimit - 32 * w));
                             const unsigned keep = valid >= 32 ? 0xffffffffu : ((1u << valid) - 1u);
-                            ns += __popc((unsigned)__builtin_amdgcn_readfirstlane((int)s_live[tile_par * 8 + w]) & keep);
+                            ns += __popc((unsigned)__builtin_amdgcn_readfirstlane((int)s_live[live_slot * 8 + w]) & keep);
                         }
                         if (ns >= 1 && ns <= KNN_DEFER_MAX_ROWS) { ab_defer = true; df_ns = ns; break; }
                     }
+                    // the tile STAYS
+                    ah_pred = knn_ahead_next(ah_pred, false);
+                    if (spec) {
+                        // ... over a head fetched for nothing: its own stage ab_ck goes over it, and one barrier waits for that
+                        ++ah_wasted;
+                        if (grp_half == 0) dma_half(cur_desc, gbuf & 1, k_lo + kc + 1, 0);
+                        else dma_half(q_desc, gbuf & 1, k_lo + kc + 1, 1);
+                        __syncthreads();
+                    }
                 }
+            }
+        }
+        if constexpr (ABANDON) {
+            if (ab_skip || ab_defer) {
+                ah_pred = knn_ahead_next(ah_pred, true);
+                if (ab_spec) ++ah_used;
             }
         }
         if constexpr (DEFER) {
             if (ab_defer) {
                 // DEFERRED: the tile's live rows go to this query tile's list and the workgroup leaves as a skip does.  Wave 0 appends:
                 // lane l holds rows 4 l ... 4 l + 3 (a nibble of word l >> 3) and their rank among the tile's live rows; lane 0
-                // reserves the ns entries with ONE returning atomic, issued in front of the next tile's DMA and first read behind the
-                // barrier that waits for that DMA anyway.  (The counter's address goes through an opaque zero, as the dealt kernel's
+                // reserves the ns entries with ONE returning atomic, issued here and first read behind the next tile's first barrier
+                // (df_flush), which waits vmcnt(0) anyway.  (The counter's address goes through an opaque zero, as the dealt kernel's
                 // does: a provably uniform address makes hipcc aggregate the atomic over the wave and wait for it on the spot.)
                 // The list holds ns x row tiles entries at least: no decision depends on the slot.
                 ++ab_deferred;
-                unsigned df_nib = 0u;
-                int df_rank = 0, df_slot = 0;
                 if (wave == 0) {
                     int lane_d = lane;
                     asm volatile("" : "+v"(lane_d));
                     const int wd = lane_d >> 3;
+                    unsigned df_nib = 0u;
+                    int df_rank = 0;
 #pragma unroll
                     for (int w = 0; w < 8; ++w) {
                         const int valid = min(32, max(0, rowlimit - 32 * w));
                         const unsigned keep = valid >= 32 ? 0xffffffffu : ((1u << valid) - 1u);
-                        const unsigned word = s_live[tile_par * 8 + w] & keep;
+                        const unsigned word = s_live[live_slot * 8 + w] & keep;
                         if (w < wd) df_rank += __popc(word);
                         if (w == wd) {
                             const int sh = 4 * (lane_d & 7);
@@ -637,34 +729,24 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
                             df_rank += __popc(word & ((1u << sh) - 1u));
                         }
                     }
+                    df_pack = ((unsigned)df_rank << 4) | df_nib;
                     if (lane_d == 0) {
                         int z = 0;
                         asm volatile("" : "+v"(z));
                         df_slot = atomicAdd(p.df_cnt + qt + z, df_ns);
                     }
                 }
-                if (has_next) {
-                    if (grp_half == 0) dma_half(next_desc, gbuf & 1, 0, 0);
-                    else dma_half(q_desc, gbuf & 1, 0, 1);
-                    __syncthreads();
-                }
-                if (wave == 0) {
-                    int* dst = p.df_list + (int64_t)qt * p.df_cap + __builtin_amdgcn_readfirstlane(df_slot) + df_rank;
-                    const int row_l = (int)row0 + 4 * (lane & 63);
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) {
-                        if (df_nib & (1u << b)) { *dst = row_l + b; ++dst; }
-                    }
-                }
-                continue;
+                df_pend = true;
+                df_row = (int)row0;
             }
         }
         if constexpr (ABANDON) {
-            if (ab_skip) {
-                // the stage fetched during the checkpoint stage (this tile's stage ck) has landed behind the barrier and is not read:
-                // the next tile's stage 0 goes over it, and one barrier waits for it (the skip's DMA bubble)
-                ++ab_skipped;
-                if (has_next) {
+            if (ab_skip || ab_defer) {
+                // without a head fetched ahead: the stage fetched during the checkpoint stage (this tile's stage ck) has landed behind
+                // the barrier and is not read; the next tile's stage 0 goes over it, and one barrier waits for it (the leaving tile's
+                // DMA bubble)
+                if (ab_skip) ++ab_skipped;
+                if (has_next && !ab_spec) {
                     if (grp_half == 0) dma_half(next_desc, gbuf & 1, 0, 0);
                     else dma_half(q_desc, gbuf & 1, 0, 1);
                     __syncthreads();
@@ -864,11 +946,18 @@ __device__ __forceinline__ void knn_hi_body(const KnnHiParams& p, const float ab
         KH_STAMP(9);
         if (nk < 2 && has_next) __syncthreads();     // one K step per tile: the next tile's only barrier comes after park_row_terms' reader
     }
+    if constexpr (DEFER) {
+        if (df_pend) df_flush();                     // the workgroup's last tile was deferred
+    }
     if constexpr (ABANDON) {
         if (tid == 0 && ab_checked > 0) {
             atomicAdd(p.ab_count, ab_checked);
             if (ab_skipped > 0) atomicAdd(p.ab_count + 1, ab_skipped);
             if constexpr (DEFER) { if (ab_deferred > 0) atomicAdd(p.df_tasks, ab_deferred); }
+            if constexpr (!DEAL) {
+                if (ah_used > 0) atomicAdd(p.ah_count, ah_used);
+                if (ah_wasted > 0) atomicAdd(p.ah_count + 1, ah_wasted);
+            }
         }
     }
 }

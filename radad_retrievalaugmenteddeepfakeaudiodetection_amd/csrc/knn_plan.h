@@ -523,6 +523,47 @@ static DeferPlan knn_abandon_defer(const DeferFacts& f) {
     return d;
 }
 
+// ---- the next tile's head, fetched at the abandon checkpoint (knn_hi.inc, ahead_on) ------------------------------------------------
+// A tile that leaves at its checkpoint (skipped or deferred) has no use for its own next stage.  With RADAD_KNN_OPT_ABANDON_AHEAD the
+// checkpoint stage of a TESTED tile that has a next tile and is predicted to leave fetches the next tile's stage 0 instead.  The
+// prediction is one scalar per workgroup; kernel and host model read this same text (constexpr: callable from both sides).
+//   initial state: "leaves" -- the workgroup's gate is open, which is already evidence;
+//   after a tested tile: what that tile did.  An untested tile (its own gate shut) neither consults nor updates it.
+constexpr bool knn_ahead_initial() { return true; }
+constexpr bool knn_ahead_next(bool /*pred*/, bool left) { return left; }
+constexpr bool knn_ahead_speculate(bool pred, bool has_next) { return pred && has_next; }
+// The walk of one workgroup's tiles, as the kernel makes it: what happens at each tile (host only; tests/knn_abandon_ahead_check.cpp
+// and the GPU test's expectations).
+enum AheadOutcome { KNN_AHEAD_UNTESTED = 0, KNN_AHEAD_LEAVE = 1, KNN_AHEAD_STAY = 2 };
+struct AheadCounts {
+    int64_t used = 0;            // tile tasks that left into a head already fetched: one barrier
+    int64_t wasted = 0;          // tile tasks that stayed and threw a fetched head away: one barrier more than without the option
+    int64_t bubbles = 0;         // barriers that wait for a DMA nothing overlaps: a leaving tile that did not speculate and has a next
+                                 // tile, and every wasted head
+};
+static AheadCounts knn_ahead_walk(const int* outcome, int tiles, bool ahead_on) {
+    AheadCounts c;
+    bool pred = knn_ahead_initial();
+    for (int t = 0; t < tiles; ++t) {
+        if (outcome[t] == KNN_AHEAD_UNTESTED) continue;
+        const bool has_next = t + 1 < tiles;
+        const bool spec = ahead_on && knn_ahead_speculate(pred, has_next);
+        const bool left = outcome[t] == KNN_AHEAD_LEAVE;
+        if (left) { if (spec) ++c.used; else if (has_next) ++c.bubbles; }
+        else if (spec) { ++c.wasted; ++c.bubbles; }
+        pred = knn_ahead_next(pred, left);
+    }
+    return c;
+}
+// the two counters of a launch live in its own set of the deal counters (zeroed with them): slot 2's first two ints.  A launch that
+// prefetches heads is never dealt, and a deferring launch counts in slots 0 and 1 (knn_defer_counter).
+static_assert(KNN_DEAL_SLOTS >= 3 && KNN_DEAL_MAX_QTILES >= 2, "the head prefetch counts inside a deal counter set");
+constexpr int knn_ahead_counter(int set) { return knn_deal_counter(set, 2, 0); }
+// Whether a launch prefetches heads: an abandoning launch that is not dealt, one of the search's first KNN_DEAL_SETS (its counters).
+static bool knn_abandon_ahead(int opt_ahead, int ab_ck, bool dealt, int launch) {
+    return opt_ahead != 0 && ab_ck > 0 && !dealt && launch >= 0 && launch < KNN_DEAL_SETS;
+}
+
 // ---- workspace layouts ------------------------------------------------------------------------------------------------------------
 // byte offsets of a search's buffers in the handle's workspace (knn_search_layout)
 struct SearchLayout {

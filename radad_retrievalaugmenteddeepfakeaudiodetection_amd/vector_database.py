@@ -74,7 +74,7 @@ def write_faiss_flat(path: str, rows: np.ndarray, metric: str):
 
 def knn_options_from_config(config):
     """the optional scan knobs, read the way the reference reads its own optional ones (getattr with a default,
-    vector_database.py:43,67,80): knn_hi_plane, knn_centre, knn_smallq_hi, knn_wide_min_q, knn_dense, knn_abandon, knn_abandon_defer, knn_range_smallq; absent / None = the library's default.
+    vector_database.py:43,67,80): knn_hi_plane, knn_centre, knn_smallq_hi, knn_wide_min_q, knn_dense, knn_abandon, knn_abandon_defer, knn_abandon_ahead, knn_range_smallq; absent / None = the library's default.
     knn_live_floor is still recognised, but only None / 0 (the default): the one-launch scan form it selected was removed"""
     if getattr(config, "knn_live_floor", None) not in (None, 0):
         raise ValueError("knn_live_floor: the one-launch scan form was measured slower and removed (DESIGN §4.1); "
@@ -82,7 +82,8 @@ def knn_options_from_config(config):
     opts = dict(hi_plane=getattr(config, "knn_hi_plane", None), centre=getattr(config, "knn_centre", None),
                 smallq_hi=getattr(config, "knn_smallq_hi", None), wide_min_q=getattr(config, "knn_wide_min_q", None),
                 dense=getattr(config, "knn_dense", None), abandon=getattr(config, "knn_abandon", None),
-                range_smallq=getattr(config, "knn_range_smallq", None), abandon_defer=getattr(config, "knn_abandon_defer", None))
+                range_smallq=getattr(config, "knn_range_smallq", None), abandon_defer=getattr(config, "knn_abandon_defer", None),
+                abandon_ahead=getattr(config, "knn_abandon_ahead", None))
     return {k: v for k, v in opts.items() if v is not None}
 
 
@@ -166,8 +167,8 @@ class HipFlatIndex:
     is_trained = True   # flat indexes need no training (vector_database.py:124)
 
     def __init__(self, d: int, metric: int, device: int = 0, id_base: int = 0, store_f16: bool = False, hi_plane=None, centre=None,
-                 smallq_hi=None, wide_min_q=None, dense=None, abandon=None, range_smallq=None, abandon_defer=None):
-        """hi_plane / centre / smallq_hi / wide_min_q / dense / abandon / range_smallq / abandon_defer: kernel choices of the handle (radad_knn_set_option;
+                 smallq_hi=None, wide_min_q=None, dense=None, abandon=None, range_smallq=None, abandon_defer=None, abandon_ahead=None):
+        """hi_plane / centre / smallq_hi / wide_min_q / dense / abandon / range_smallq / abandon_defer / abandon_ahead: kernel choices of the handle (radad_knn_set_option;
         None = the library's default).  They change speed, never results: A/B measurements and the parity tests select kernels through
         them.  range_smallq (default off): range searches of <= 16 queries stream the f16 plane instead of the float64 exact kernel."""
         self._lib = _lib.load()
@@ -181,10 +182,11 @@ class HipFlatIndex:
                                                  self.device, self.id_base, C.byref(h)), "radad_knn_create")
         self._h = h
         self.options = dict(hi_plane=hi_plane, centre=centre, smallq_hi=smallq_hi, wide_min_q=wide_min_q, dense=dense, abandon=abandon,
-                            range_smallq=range_smallq, abandon_defer=abandon_defer)
+                            range_smallq=range_smallq, abandon_defer=abandon_defer, abandon_ahead=abandon_ahead)
         for opt, val in ((_lib.KNN_OPT_HI_PLANE, hi_plane), (_lib.KNN_OPT_CENTRE, centre), (_lib.KNN_OPT_SMALLQ_HI, smallq_hi),
                          (_lib.KNN_OPT_WIDE_MIN_Q, wide_min_q), (_lib.KNN_OPT_DENSE, dense), (_lib.KNN_OPT_ABANDON, abandon),
-                         (_lib.KNN_OPT_RANGE_SMALLQ, range_smallq), (_lib.KNN_OPT_ABANDON_DEFER, abandon_defer)):
+                         (_lib.KNN_OPT_RANGE_SMALLQ, range_smallq), (_lib.KNN_OPT_ABANDON_DEFER, abandon_defer),
+                         (_lib.KNN_OPT_ABANDON_AHEAD, abandon_ahead)):
             if val is not None:
                 _lib.check(self._lib.radad_knn_set_option(self._h, opt, int(val)), "radad_knn_set_option")
 
@@ -672,6 +674,19 @@ class HipFlatIndex:
         _lib.check(self._lib.radad_knn_last_abandon_defer(self._h, C.byref(t), C.byref(r), C.byref(n)), "radad_knn_last_abandon_defer")
         return {"tile_tasks_deferred": t.value, "rows_listed": r.value, "tail_launches": n.value}
 
+    def set_abandon_ahead(self, value):
+        """RADAD_KNN_OPT_ABANDON_AHEAD at any time: 1 = the checkpoint stage of a tile expected to leave fetches the next tile's head,
+        0 = it fetches the tile's own next stage (same results; A/B measurements and the parity tests)"""
+        _lib.check(self._lib.radad_knn_set_option(self._h, _lib.KNN_OPT_ABANDON_AHEAD, int(value)), "radad_knn_set_option")
+        self.options["abandon_ahead"] = int(value)
+
+    def last_abandon_ahead(self):
+        """{"used", "wasted"}: tile tasks of the last search that left into a head fetched ahead, and tile tasks that stayed and threw
+        one away (radad_knn_last_abandon_ahead; both 0 when no launch fetched ahead)"""
+        u, w = C.c_int64(), C.c_int64()
+        _lib.check(self._lib.radad_knn_last_abandon_ahead(self._h, C.byref(u), C.byref(w)), "radad_knn_last_abandon_ahead")
+        return {"used": u.value, "wasted": w.value}
+
     def tuning_info(self):
         """{"cap_boost", "fp32_searches_left", "reports_consumed"} (radad_knn_tuning_info): read without synchronising"""
         a, b, n = C.c_int(), C.c_int(), C.c_int64()
@@ -690,6 +705,7 @@ class HipFlatIndex:
         return {"query_tiles": a.value, "db_splits": b.value, "block_threads": c.value, "rechecked_queries": st[0],
                 "scan_launches": nl.value, "scan_phases": nph.value, "early_abandon": self.last_abandon(),
                 "abandon_deal": self.last_abandon_deal(), "abandon_defer": self.last_abandon_defer(),
+                "abandon_ahead": self.last_abandon_ahead(),
                 "scan_kind": ("f32_tile", "hi_tile", "f32_smallq", "hi_smallq", "f16_tile", "f32_dense")[kind.value],
                 "certificate": {"queries": nq.value, "rejected": st[0], "candidates_rescored": st[1],
                                 "rejected_buffer_full": st[2], "rejected_list_used_up": st[3],
