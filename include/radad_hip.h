@@ -107,9 +107,11 @@ int radad_knn_create_ex(int dim, int metric, int store_dtype, int device, int64_
  *                            clear of the run-to-run spread (profiles/abandon_deal_ab.txt); no environment override
  *   RADAD_KNN_OPT_ABANDON_DEFER  1 (default) / 0: an abandoning launch of <= 8 query tiles that is not dealt and whose rows span less
  *                            than 4 GiB of the plane lists the live rows of a vetoed tile that has at most 16 of them, leaves the tile as
- *                            a skipped one, and scores the listed rows in full against their query tile in a tail launch behind the scan
- *                            launch / a vetoed tile is multiplied in full.  Same candidates either way.  Measured:
- *                            profiles/abandon_defer_ab.txt; RADAD_KNN_OPT_ABANDON 0 turns it off too; no environment override
+ *                            a skipped one, and scores the listed rows in full against their query tile in a tail behind the scan
+ *                            launch (short lists in 16-row groups spread over every CU, long ones in 256-row tiles: each list is
+ *                            taken by one of the two) / a vetoed tile is multiplied in full.  Same candidates either way.  Measured:
+ *                            profiles/abandon_defer_ab.txt, profiles/row_tail_ab.txt; RADAD_KNN_OPT_ABANDON 0 turns it off too; no
+ *                            environment override
  *   RADAD_KNN_OPT_ABANDON_AHEAD  1 (default) / 0: in an abandoning launch that is not dealt, the checkpoint stage of a tile that is
  *                            expected to leave (skipped or deferred: the workgroup's last tested tile left, or it has tested none yet)
  *                            fetches the NEXT tile's first stage instead of its own next one, so that a leaving tile costs one barrier
@@ -249,7 +251,7 @@ int radad_knn_last_abandon(radad_knn_t h, int64_t* checked, int64_t* skipped, in
 int radad_knn_last_abandon_deal(radad_knn_t h, int* launches, int* workgroups, int* granule);
 /* ... and what its deferring launches (RADAD_KNN_OPT_ABANDON_DEFER) handed to their tails (synchronises with the search): the vetoed tile
  * tasks that listed their live rows and left (`checked` counts them, `skipped` does not), the rows listed over all query tiles, and the
- * tail launches made.  All 0 when no launch deferred. */
+ * tails run (one per deferring launch, whichever kernel took its lists).  All 0 when no launch deferred. */
 int radad_knn_last_abandon_defer(radad_knn_t h, int64_t* tile_tasks_deferred, int64_t* rows_listed, int* tail_launches);
 /* ... and what became of the heads its launches fetched ahead (RADAD_KNN_OPT_ABANDON_AHEAD; synchronises with the search): the tile tasks
  * that left into a next tile's head already fetched (`heads_used`), and those that stayed and fetched their own stage over one

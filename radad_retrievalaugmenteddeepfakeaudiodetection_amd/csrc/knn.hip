@@ -3887,7 +3887,8 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
             rp.ah_count = h->deal_cnt + knn_ahead_counter((int)i);
             h->last_ahead_sets |= 1u << i;
         }
-        KnnHiParams tp;
+        KnnHiParams tp, rtp;
+        RowTailPlan rt;
         auto tail_fn = launch_fn;
         if (fp.defer) {
             rp.df_cnt = h->deal_cnt + knn_defer_counter((int)i, 0);
@@ -3905,12 +3906,21 @@ static int knn_scan_hi_tile(radad_knn_t h, const ScanPlan& p, const SearchLayout
             tp.loose_floor = 1;
             tail_fn = rsc == 0 ? k_knn_hi_tail<0> : k_knn_hi_tail<3>;
             RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tail_fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            // short lists -- the usual case -- go to the row tail: 16-row groups over every CU (knn_defer_rowtail); each of the two
+            // kernels reads the count and leaves a list that is the other's (knn_rowtail_takes)
+            rt = knn_defer_rowtail(fp.list_cap, gq_grid, h->n_cus);
+            rtp = tp;
+            rtp.n_splits = rt.n_splits;
         }
         h->prof.begin(st);      // the event pair brackets a scan launch (the kernel the roofline is quoted on; the phases of one
                                 // search are two entries) and, behind a deferring one, its tail
         hipLaunchKernelGGL(launch_fn, dim3((unsigned)(gq_grid * gs * rp.ksplit)), dim3(KW_THREADS), launch_lds, st, rp);
         if (fp.defer) {
-            hipLaunchKernelGGL(tail_fn, dim3((unsigned)(gq_grid * fp.tail_splits)), dim3(KW_THREADS), lds, st, tp);
+            if (rsc == 0) hipLaunchKernelGGL(k_knn_hi_rowtail<0>, dim3((unsigned)(gq_grid * rt.n_splits)), dim3(KNN_ROWTAIL_THREADS), 0, st, rtp);
+            else hipLaunchKernelGGL(k_knn_hi_rowtail<3>, dim3((unsigned)(gq_grid * rt.n_splits)), dim3(KNN_ROWTAIL_THREADS), 0, st, rtp);
+            // (a list can only be the tile tail's where its capacity reaches past the row tail's share)
+            if (!knn_rowtail_takes((int)std::min<int64_t>(fp.list_cap, INT_MAX)))
+                hipLaunchKernelGGL(tail_fn, dim3((unsigned)(gq_grid * fp.tail_splits)), dim3(KW_THREADS), lds, st, tp);
             ++h->last_defer_launches; h->last_defer_sets |= 1u << i;
         }
         h->prof.end(st);

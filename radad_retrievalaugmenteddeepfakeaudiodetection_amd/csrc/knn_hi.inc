@@ -82,12 +82,13 @@ struct KnnHiParams {
     int deal_tiles = 0;                   // row tiles of this launch
     int* deal_cnt = nullptr;              // [KNN_DEAL_SLOTS][KNN_DEAL_MAX_QTILES] this launch's ticket counters (zeroed once per search: k_hi_rows)
     // DEFERRING launches (k_knn_hi_abandon_defer; which launches are: knn_abandon_defer, knn_plan.h) append a vetoed tile's few live rows
-    // to the list of their query tile; the launch's tail (k_knn_hi_tail) reads the same three fields
+    // to the list of their query tile; the launch's tails (k_knn_hi_rowtail for short lists, k_knn_hi_tail for long ones) read the same
+    // three fields
     int* df_cnt = nullptr;                // [KNN_DEFER_MAX_QTILES] entries of each query tile's list, this launch (zeroed once per search: k_hi_rows)
     int* df_list = nullptr;               // [KNN_DEFER_MAX_QTILES][df_cap] launch-relative rows
     int df_cap = 0;                       // row tiles of the launch x KNN_DEFER_MAX_ROWS: a list cannot overflow
     int* df_tasks = nullptr;              // [1] tile tasks deferred (one atomic per workgroup)
-    unsigned df_bytes = 0;                // the tail: bytes of the launch's rows (the plane is addressed through ONE 32-bit descriptor)
+    unsigned df_bytes = 0;                // the tails: bytes of the launch's rows (the plane is addressed through ONE 32-bit descriptor)
     // THE HEAD PREFETCH (ABANDON without DEAL; RADAD_KNN_OPT_ABANDON_AHEAD): the checkpoint stage of a tile predicted to leave
     // (knn_ahead_speculate, knn_plan.h) fetches the NEXT tile's stage 0 instead of its own stage ab_ck
     int ab_ahead = 0;
@@ -1043,17 +1044,191 @@ __global__ __launch_bounds__(KW_THREADS, 1) void k_knn_hi_abandon_defer(KnnHiPar
     else knn_hi_body<RSC, false, false>(p);
 }
 
-// the tail of a deferring launch: every listed row against its query tile, in full, with the launch's floors.  The grid is
+// the TILE tail of a deferring launch, for lists too long for the row tail below (knn_rowtail_takes): every listed row against its query
+// tile, in full, with the launch's floors.  The grid is
 // n_qtiles x n_splits workgroups (knn_hi_task); workgroup `split` takes tiles split, split + n_splits, ... of its query tile's list and
 // leaves before any barrier when the list ends in front of its first.
 template <int RSC>
 __global__ __launch_bounds__(KW_THREADS, 1) void k_knn_hi_tail(KnnHiParams p) {
     int qt, split;
     if (!knn_hi_task(p, (int)blockIdx.x, qt, split)) return;
-    const int cnt = min(p.df_cnt[qt], p.df_cap);
+    const int cnt_all = p.df_cnt[qt];
+    if (knn_rowtail_takes(cnt_all)) return;                  // a short list: the row tail's (k_knn_hi_rowtail)
+    const int cnt = min(cnt_all, p.df_cap);
     for (int t = split; (int64_t)t * KW_M < cnt; t += p.n_splits) {
         knn_hi_body<RSC, false, false, false, false, true>(p, 0.f, 0.f, 0, t);
         __syncthreads();                                     // (the next tile's map and per-query terms go over this one's)
+    }
+}
+
+// THE ROW TAIL: the tail of a deferring launch whose lists are short (knn_rowtail_takes, knn_plan.h) -- on the benchmark 3 % of their
+// capacity.  The tile tail above scores such a list as a handful of 256-row tiles, each a chain of K stages (DMA, barrier, MFMAs) alone
+// on its CU: its time is latency, not work.  Here the unit is a GROUP of KNN_ROWTAIL_GROUP = 16 consecutive list entries against the
+// query tile's <= 256 queries, on a workgroup of 4 waves; the grid is persistent and host-planned (knn_defer_rowtail): workgroup `split`
+// of a query tile walks groups split, split + n_splits, ... (knn_rowtail_span) and one whose first group lies beyond the list's end
+// leaves after the load of the count.  Wave w takes queries 64 w ... 64 w + 63 as four 16-query blocks (4 f32x4 accumulators).  Lane
+// (l15, lq) fetches the 16-byte chunk 4 s + lq of K step s (32 elements) of listed row l15 straight from the plane into registers --
+// KR_RING_A steps are requested before anything waits, a step's registers are requested again for step s + KR_RING_A right behind its
+// MFMAs -- and the same chunk of its four queries KR_RING_B steps ahead (the query tile is L2-resident).  No LDS staging, no barrier
+// in the K loop; the per-query terms are parked in LDS once per workgroup.
+// THE SCORE IS THE SCAN'S, bit for bit: the accumulator of (row, query) starts at 0 (RSC 0) or (bias_sign rbias[row]) s_qs[query] (RSC
+// 3: the one multiply `rb4 * qs4` of knn_hi_body), then takes v_mfma_f32_16x16x32_f16 with rows as A and queries as B over the K steps
+// in ascending order, chunk lq of each 64-byte half stage in lane quarter lq -- knn_hi_body's chain; where a row sits among the 16 of
+// an MFMA changes nothing.  The test (acc >= (s_thr - s_qc) s_qs, +inf past nq) and the value written (fmaf(acc, qi, qc), id_off + row)
+// are the body's counting form.  An entry past the list's end is a zero row that never emits (its offset lies past the descriptor).
+// THE EMIT: the four lane quarters of a wave hold rows 4 lq ... 4 lq + 3 of the SAME 16 queries, so their counts are added inside the
+// wave and quarter 0 reserves the slots of all four with one returning atomic per (query block, query), the four of a lane issued
+// together; the slots are dealt by lane quarter.  (Nearly every listed row is a candidate of most queries, and same-address atomics
+// serialise at ~10 ns each: hi_rows_body.)
+constexpr int KR_THREADS = KNN_ROWTAIL_THREADS;
+constexpr int KR_RING_A = 16;            // K steps of the rows in flight: dim 512 whole (64 VGPRs)
+constexpr int KR_RING_B = 2;             // K steps of the queries in flight (16 VGPRs each)
+static_assert(KR_THREADS == 256 && KW_N == 256 && KNN_ROWTAIL_GROUP == 16, "4 waves x 64 queries, one 16-row MFMA operand");
+static_assert(KR_RING_A % KR_RING_B == 0 && KR_RING_B == 2, "a ring slot is named by the step's position in its block");
+
+template <int RSC>
+__global__ __launch_bounds__(KR_THREADS, 4) void k_knn_hi_rowtail(KnnHiParams p) {
+    static_assert(RSC == 0 || RSC == 3, "the tail scores what an abandoning launch listed");
+    __shared__ float s_at[KW_N], s_qs[KW_N], s_qi[KW_N], s_qc[KW_N];
+    int qt, split;
+    if (!knn_hi_task(p, (int)blockIdx.x, qt, split)) return;
+    const int cnt_all = p.df_cnt[qt];
+    if (!knn_rowtail_takes(cnt_all)) return;                 // (the tile tail's: block-uniform, before any barrier)
+    const int cnt = min(cnt_all, p.df_cap);
+    if (knn_rowtail_span(split, 0, p.n_splits, cnt).n <= 0) return;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l15 = lane & 15, lq = lane >> 4;
+    const int q0 = qt * KW_N;
+    {
+        // the per-query terms, as knn_hi_body forms them; s_at: what the epilogue compares against
+        const bool owner = q0 + tid < p.nq;
+        float qi = owner ? p.qscale[q0 + tid] : 1.f;
+        if (RSC == 0) qi *= p.uscale;
+        if (RSC == 3) qi *= p.uscale * p.mult;
+        const float qs = 1.0f / qi;                          // powers of two: exact
+        const float qc = (RSC >= 2 && owner && p.qconst) ? p.qconst[q0 + tid] : 0.f;
+        const float thr = (owner && p.thr_init) ? p.thr_init[q0 + tid] : -INFINITY;
+        s_qi[tid] = qi; s_qs[tid] = qs; s_qc[tid] = qc;
+        s_at[tid] = (owner && !RADAD_DBG(p.debug, 32)) ? (thr - qc) * qs : INFINITY;         // (debug bit 32: no emit, as in the body)
+    }
+    __syncthreads();
+    const int nk = p.row_bytes >> 6;                         // 64-byte K steps per row: EVEN and >= 2 = KR_RING_B, because row_bytes is a
+                                                             // multiple of 128 (KnnHiParams; the tile scan's own condition, dim % 64 == 0)
+    // rows: the launch's plane through one 32-bit descriptor (KNN_DEFER_MAX_BYTES); queries: this query tile's, the ones past nq read as zero
+    const __amdgpu_buffer_rsrc_t a_desc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.db)), 0, (int)p.df_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t q_desc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<char*>(reinterpret_cast<const char*>(p.q) + (int64_t)q0 * p.row_bytes), 0, min(KW_N, p.nq - q0) * p.row_bytes, 0x00020000);
+    const unsigned vb0 = (unsigned)((wave * 64 + l15) * p.row_bytes + lq * 16);
+    const unsigned vb_nt = (unsigned)(16 * p.row_bytes);
+    auto load_b = [&](f16x8 (&dst)[4], int s, bool in = true) {
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+            dst[nt] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(q_desc, in ? vb0 + nt * vb_nt : 0x7FFF0000u, s * 64, 0));
+    };
+    const int* list = p.df_list + (int64_t)qt * p.df_cap;
+    for (int round = 0;; ++round) {
+        const RowTailSpan span = knn_rowtail_span(split, round, p.n_splits, cnt);
+        if (span.n <= 0) break;
+        f16x8 a[KR_RING_A], b[KR_RING_B][4];
+#pragma unroll
+        for (int j = 0; j < KR_RING_B; ++j) load_b(b[j], j);         // (nk >= 2 = KR_RING_B)
+        const int row = l15 < span.n ? list[span.first + l15] : -1;
+        float rb_own = 0.f;
+        if (RSC == 3) rb_own = row >= 0 ? p.bias_sign * p.rbias[row] : 0.f;
+        const unsigned va = row < 0 ? p.df_bytes : (unsigned)row * (unsigned)p.row_bytes + (unsigned)(lq * 16);
+#pragma unroll
+        for (int j = 0; j < KR_RING_A; ++j) {
+            // (a step the row does not have is requested past the descriptor's end -- zeros, no memory access -- and never multiplied:
+            // every ring register is DEFINED in every round, or hipcc carries the ring across the emit and spills around it)
+            a[j] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(a_desc, j < nk ? va : p.df_bytes, j * 64, 0));
+        }
+        // acc[nt][r] = listed row 4 lq + r, query wave * 64 + nt * 16 + l15
+        f32x4 acc[4];
+        if (RSC == 3) {
+            int lane_s = lane;
+            asm volatile("" : "+v"(lane_s));             // (opaque, as in the emit below)
+            f32x4 rb4;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) rb4[r] = __shfl(rb_own, 4 * (lane_s >> 4) + r, 64);
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) acc[nt] = rb4 * s_qs[wave * 64 + nt * 16 + (lane_s & 15)];
+        } else {
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        // whole blocks of KR_RING_A steps run as straight-line code (no branch around a load or an MFMA: hipcc counts the loads in flight
+        // per path and, across branches, waits for ALL of them at every step).  A step past the row's end is requested past the
+        // descriptor's end, as above.
+        int s0 = 0;
+        for (; s0 + KR_RING_A <= nk; s0 += KR_RING_A) {
+#pragma unroll
+            for (int j = 0; j < KR_RING_A; ++j) {
+                const int s = s0 + j;
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[j], b[j % KR_RING_B][nt], acc[nt], 0, 0, 0);
+                a[j] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(a_desc, s + KR_RING_A < nk ? va : p.df_bytes, (s + KR_RING_A) * 64, 0));
+                load_b(b[j % KR_RING_B], s + KR_RING_B, s + KR_RING_B < nk);
+                __builtin_amdgcn_sched_barrier(0);       // (pins the order: hipcc otherwise hoists the block's loads and spills)
+            }
+        }
+        // the rest of the row, in pairs of steps (nk is even); its rows are in the ring already
+#pragma unroll
+        for (int j = 0; j < KR_RING_A; j += 2) {
+            if (s0 + j < nk) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                    for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[j + h], b[h][nt], acc[nt], 0, 0, 0);
+                }
+                load_b(b[0], s0 + j + 2, s0 + j + 2 < nk);
+                load_b(b[1], s0 + j + 3, s0 + j + 3 < nk);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        // the emit: count per lane, add over the lane quarters, one atomic per (query block, query), slots dealt by quarter
+        // (the lane-derived indices come from an OPAQUE copy of the lane id, as in knn_hi_body's epilogue: hipcc otherwise hoists every
+        // address of the emit out of the group loop and spills them around the K loop)
+        int lane_e = lane;
+        asm volatile("" : "+v"(lane_e));
+        const int e15 = lane_e & 15, eq = lane_e >> 4;
+        const int ql0 = wave * 64 + e15;
+        int tot4[4], off4[4], base4[4], row_e[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) row_e[r] = __shfl(row, 4 * eq + r, 64);
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            const float at = s_at[ql0 + nt * 16];
+            int c = 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) c += (row_e[r] >= 0 && acc[nt][r] >= at) ? 1 : 0;
+            const int c0 = __shfl(c, e15, 64), c1 = __shfl(c, 16 + e15, 64), c2 = __shfl(c, 32 + e15, 64), c3 = __shfl(c, 48 + e15, 64);
+            tot4[nt] = c0 + c1 + c2 + c3;
+            off4[nt] = (eq > 0 ? c0 : 0) + (eq > 1 ? c1 : 0) + (eq > 2 ? c2 : 0);
+        }
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+            base4[nt] = (eq == 0 && tot4[nt] > 0) ? atomicAdd(p.cand_cnt + (q0 + ql0 + nt * 16), tot4[nt]) : 0;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            int sl = __shfl(base4[nt], e15, 64) + off4[nt];
+            if (tot4[nt] > 0) {
+                const int ql = ql0 + nt * 16;
+                const float at = s_at[ql], qi = s_qi[ql], qc = s_qc[ql];
+                const int64_t cbase = (int64_t)(q0 + ql) * p.cand_cap;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    if (row_e[r] >= 0 && acc[nt][r] >= at) {
+                        if (sl < p.cand_cap) {
+                            p.part_score[cbase + sl] = fmaf(acc[nt][r], qi, qc);
+                            p.part_idx[cbase + sl] = (int)(p.id_off + row_e[r]);
+                        }
+                        ++sl;
+                    }
+                }
+            }
+        }
     }
 }
 

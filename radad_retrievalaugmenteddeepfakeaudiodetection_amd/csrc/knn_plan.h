@@ -523,6 +523,43 @@ static DeferPlan knn_abandon_defer(const DeferFacts& f) {
     return d;
 }
 
+// ---- the row tail: short lists scored in 16-row groups on every CU (knn_hi.inc, k_knn_hi_rowtail) ------------------------------------
+// Behind a deferring launch BOTH tails are launched; each reads its query tile's count and leaves unless the list is on its side of
+// KNN_ROWTAIL_MAX_ENTRIES (device-side: the host never sees a count).  The row tail's unit is a GROUP of KNN_ROWTAIL_GROUP consecutive
+// entries of one query tile's list against that query tile; its grid is n_qtiles x n_splits workgroups of KNN_ROWTAIL_THREADS, workgroup
+// `split` walks groups split, split + n_splits, ... until the list ends (knn_rowtail_span: the text kernel and host check both read).
+constexpr int KNN_ROWTAIL_GROUP = 16;        // one MFMA's rows
+constexpr int KNN_ROWTAIL_THREADS = 256;     // 4 waves x 64 queries
+constexpr int KNN_ROWTAIL_WG_PER_CU = 2;     // workgroups per CU the grid is cut for (4 fit: the kernel leaves room for 4 waves per SIMD; the
+                                             // benchmark's lists are one round either way, and half the workgroups of an empty tail leave sooner)
+// A list of more entries than this goes to the tile tail: every group re-reads its query tile from L2, a 256-row tile reads it once.
+// Measured at 1 M x 512, 4 query tiles, one launch (tools/bench_row_tail.py; profiles/row_tail_ab.txt, section 3): with 2960 entries a
+// query tile the row tail is 0.016 ms faster than the tile tail, with 8720 it is 0.052 ms slower, with 62 496 0.50 ms slower; the
+// two lines cross at about 4300 entries.
+constexpr int KNN_ROWTAIL_MAX_ENTRIES = 4096;
+constexpr bool knn_rowtail_takes(int count) { return count <= KNN_ROWTAIL_MAX_ENTRIES; }
+struct RowTailSpan { int first, n; };        // entries [first, first + n) of the list; n == 0: the workgroup is done
+constexpr RowTailSpan knn_rowtail_span(int split, int round, int n_splits, int count) {
+    const long long first = ((long long)round * n_splits + split) * KNN_ROWTAIL_GROUP;
+    if (first >= count) return RowTailSpan{0, 0};
+    return RowTailSpan{(int)first, count - first < KNN_ROWTAIL_GROUP ? (int)(count - first) : KNN_ROWTAIL_GROUP};
+}
+struct RowTailPlan {
+    int groups = 0;              // groups of a full list
+    int n_splits = 0;            // workgroups per query tile (a multiple of 8: knn_hi_task)
+    int rounds = 0;              // groups a workgroup takes at most
+};
+// KNN_ROWTAIL_WG_PER_CU workgroups per CU over all query tiles, in eights, and no more than a full list has groups
+static RowTailPlan knn_defer_rowtail(int64_t list_cap, int n_qtiles, int cus) {
+    RowTailPlan r;
+    if (list_cap <= 0 || n_qtiles < 1 || cus <= 0) return r;
+    r.groups = (int)ceil_div64(list_cap, KNN_ROWTAIL_GROUP);
+    const int per_qt = std::max(8, KNN_ROWTAIL_WG_PER_CU * cus / n_qtiles / 8 * 8);
+    r.n_splits = std::min(per_qt, (r.groups + 7) / 8 * 8);
+    r.rounds = (r.groups + r.n_splits - 1) / r.n_splits;
+    return r;
+}
+
 // ---- the next tile's head, fetched at the abandon checkpoint (knn_hi.inc, ahead_on) ------------------------------------------------
 // A tile that leaves at its checkpoint (skipped or deferred) has no use for its own next stage.  With RADAD_KNN_OPT_ABANDON_AHEAD the
 // checkpoint stage of a TESTED tile that has a next tile and is predicted to leave fetches the next tile's stage 0 instead.  The
