@@ -785,10 +785,14 @@ typedef struct radad_embed_s* radad_embed_t;
 /* mel_filters_host [201, 80] fp32 (bins x mels); proj_w_host [80, F] fp32; proj_b_host [F] fp32 */
 int radad_embed_create(const radad_embed_cfg* cfg, const float* mel_filters_host, const float* proj_w_host,
                        const float* proj_b_host, int device, radad_embed_t* out);
-/* same with a choice of log-mel kernel (all give feature_extraction_whisper.py:135-168 per segment within the 1e-4 bar; for A/B
- * measurements and parity tests): flags = 0 is radad_embed_create.
+/* same with a choice of log-mel kernel (for A/B measurements and parity tests): flags = 0 is radad_embed_create.  All give
+ * feature_extraction_whisper.py:135-168 per segment; how closely, row by row against the float64 oracle on tones, a chirp, noise
+ * floors, a gated clip, level and DC steps (tests/test_gpu_logmel_designed.py, profiles/logmel_designed.md; final (log10 + 4) / 4
+ * units): k_logmel_fft_clip and k_logmel within the 1e-4 bar everywhere (worst 8.1e-5 and 4.6e-5).  The two f16-matrix-pipe kernels
+ * within it except in cells 7 to 8 decades under the segment maximum of a pure tone over a quiet floor, where the tone's accumulated
+ * rounding noise shows: k_logmel_h_clip up to 1.2e-4, k_logmel_h up to 1.6e-4 (numpy's float32 FFT: 2.1e-5).
  *   RADAD_EMBED_NO_SHARED_FRAMES  one transform per (segment, frame) even where overlapping segments share frames (k_logmel_h)
- *   RADAD_EMBED_LOGMEL_F32        the folded DFT on the fp32 matrix pipe (k_logmel, ~2x slower than k_logmel_h)
+ *   RADAD_EMBED_LOGMEL_F32        the folded DFT on the fp32 matrix pipe, short sums met in float64 (k_logmel, ~3x slower than k_logmel_h)
  *   RADAD_EMBED_LOGMEL_DFT_GEMM   shared frames as a DFT-as-GEMM on the f16 matrix pipe (k_logmel_h_clip) instead of the radix FFT on the
  *                                 vector ALU (k_logmel_fft_clip, the default where the configuration allows sharing)
  * The environment variables RADAD_LOGMEL_SHARED=0, RADAD_LOGMEL_F32=1, RADAD_LOGMEL_FFT=0 set the same bits for extractors created
@@ -874,6 +878,14 @@ int radad_embed_last_plan(radad_embed_t h, int64_t* info8, int64_t* clip_seg_hos
  * the f16 matrix pipe (k_logmel_h_clip: RADAD_LOGMEL_FFT=0, or a filter bank that is not triangular).  All give
  * feature_extraction_whisper.py:135-168 per zero-mean/unit-variance segment. */
 int radad_embed_last_logmel_kind(radad_embed_t h, int* kind_out);
+/* Diagnostic (tests/test_gpu_logmel_designed.py compares it row by row with the float64 oracle): the log-mel rows the handle's most
+ * recent radad_embed_forward* or stage call computed, [S, frames, 80] fp32 with the segments in plan order, clamped with the handle's
+ * own segment maxima and scaled (x + 4) / 4 exactly as radad_embed_logmel returns them -- the rows the projection kernel read.
+ * Enqueues one small kernel on `stream` (the one that call was enqueued on) and changes nothing in the handle; the hot path does not
+ * know about it.  *n_segments_out = S (device-resident offsets: the plan's own count, after waiting for `stream`), written before
+ * the capacity is checked; out_dev NULL: the count alone.  RADAD_ESTATE when the handle holds no rows (no forward yet, or its
+ * buffers were released), RADAD_EINVAL when segment_capacity < S (nothing is written to out_dev). */
+int radad_embed_last_logmel(radad_embed_t h, float* out_dev, int64_t segment_capacity, int64_t* n_segments_out, void* stream);
 /* How k_logmel_h_clip cuts a clip of n_segments segments (frames_per_segment frames each, segment hop = hop_frames frames) into
  * workgroup chunks -- host arithmetic only, no device needed (the kernel, the plan kernel and the host share it): out5 = { full
  * chunks of 104 interior frames, interior frames of the tail chunk, edge frames the tail chunk carries, edge-only chunks of <= 32

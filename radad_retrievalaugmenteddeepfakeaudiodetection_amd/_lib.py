@@ -214,6 +214,7 @@ SIGNATURES = {
     "radad_embed_last_plan": (C.c_int, [C.c_void_p, c_i64p, c_i64p, C.c_int64, c_i64p, c_i32p, C.c_int64, c_i64p, c_i32p, C.c_int64,
                                         C.c_void_p]),
     "radad_embed_last_logmel_kind": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "radad_embed_last_logmel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, c_i64p, C.c_void_p]),
     "radad_embed_clip_chunks": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "radad_embed_fft_clip_chunks": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "radad_embed_fft_tables": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32)]),

@@ -109,7 +109,8 @@ struct LogmelParams {
     int debug;                   // timing experiments only (RADAD_DEBUG_LOGMEL): 1 = skip the MFMA loop, 2 = skip the prologue
 };
 
-__global__ __launch_bounds__(LM_THREADS, 2) void k_logmel(LogmelParams p) {
+// (one workgroup per CU: the segment's 148 KB of LDS allow no second one, and the float64 sums below want the registers)
+__global__ __launch_bounds__(LM_THREADS, 1) void k_logmel(LogmelParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* sig = reinterpret_cast<float*>(smem);                 // [SIG_FLOATS]
     float* sbas = sig + SIG_FLOATS;                              // [2][CHUNK_FLOATS]
@@ -214,9 +215,13 @@ __global__ __launch_bounds__(LM_THREADS, 2) void k_logmel(LogmelParams p) {
 
     int step = 0;   // global chunk counter (bt*NCH + ch)
     for (int bt = 0; bt < (RADAD_DBG(p.debug, 1) ? 0 : NBT); ++bt) {
-        f32x16 re, im;
+        // The 200-tap sums of a bin far from a tone are 1e-4 of their largest partial sum, and an fp32 accumulator that is rounded after
+        // every product carries 200 roundings of that partial sum into them: cells 7-8 decades under the segment maximum were off by
+        // 3e-4 in final units (tests/test_gpu_logmel_designed.py).  So the matrix pipe only adds up FOUR taps at a time (two MFMAs from
+        // zero), and the 50 short sums meet in float64 on the vector ALU: what is left is the rounding of the inputs.
+        double re_d[16], im_d[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { re[r] = 0.f; im[r] = 0.f; }
+        for (int r = 0; r < 16; ++r) { re_d[r] = 0.0; im_d[r] = 0.0; }
         for (int ch = 0; ch < NCH; ++ch, ++step) {
             const int buf = step & 1;
             // prefetch the next chunk (global -> registers) while this one is consumed
@@ -231,17 +236,26 @@ __global__ __launch_bounds__(LM_THREADS, 2) void k_logmel(LogmelParams p) {
             const float* p1 = sig + (pb1 + 40 * ch + (ch == 4 ? 1 : 0));
             const float* p2 = sig + (pb2 - 40 * ch + (ch <= 1 ? 2 : 1));
             const float* p1s = p1 + ((ch == 3) ? lh : 0);      // the one tap that crosses n = 160
-#pragma unroll
+#pragma unroll 1
             for (int kq = 0; kq < KCH; ++kq) {
                 const f32x4 bc = *reinterpret_cast<const f32x4*>(cb + (kq * 2 + 0) * 256 + lane * 4);
                 const f32x4 bs = *reinterpret_cast<const f32x4*>(cb + (kq * 2 + 1) * 256 + lane * 4);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int o = 8 * kq + j + 1;               // compile-time
-                    const float x1 = (kq == 4 && j == 3) ? p1s[o] : p1[o];
-                    const float x2 = p2[40 - o];
-                    re = __builtin_amdgcn_mfma_f32_32x32x2f32(bc[j], x1 + x2, re, 0, 0, 0);
-                    im = __builtin_amdgcn_mfma_f32_32x32x2f32(bs[j], x1 - x2, im, 0, 0, 0);
+                for (int jp = 0; jp < 4; jp += 2) {
+                    f32x16 rg, ig;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) { rg[r] = 0.f; ig[r] = 0.f; }
+#pragma unroll
+                    for (int j = jp; j < jp + 2; ++j) {
+                        const int o = 8 * kq + j + 1;               // compile-time
+                        const float x1 = (kq == 4 && j == 3) ? p1s[o] : p1[o];
+                        const float x2 = p2[40 - o];
+                        rg = __builtin_amdgcn_mfma_f32_32x32x2f32(bc[j], x1 + x2, rg, 0, 0, 0);
+                        ig = __builtin_amdgcn_mfma_f32_32x32x2f32(bs[j], x1 - x2, ig, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) { re_d[r] += (double)rg[r]; im_d[r] += (double)ig[r]; }
+                    __builtin_amdgcn_sched_barrier(0);          // one group's 32 partial sums live at a time (unrolled and overlapped, ten of them spilled)
                 }
             }
             if (more) {
@@ -254,7 +268,10 @@ __global__ __launch_bounds__(LM_THREADS, 2) void k_logmel(LogmelParams p) {
         // |X|^2 for 16 bins of this lane's frame, then mel += fb^T . pow on the matrix core
         f32x16 pw;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) pw[r] = re[r] * re[r] + im[r] * im[r];
+        for (int r = 0; r < 16; ++r) {
+            const float re = (float)re_d[r], im = (float)im_d[r];
+            pw[r] = re * re + im * im;
+        }
 #pragma unroll
         for (int mt = 0; mt < NMT; ++mt) {
             if ((p.nzmask >> (bt * NMT + mt)) & 1u) {
@@ -279,7 +296,7 @@ __global__ __launch_bounds__(LM_THREADS, 2) void k_logmel(LogmelParams p) {
                 f32x4 v;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    v[i] = log10f(fmaxf(zacc[mt][4 * g + i], 1e-10f));
+                    v[i] = fmaxf(log10f(zacc[mt][4 * g + i]), -10.f);     // log10(max(mel, 1e-10)), the floor exactly -10
                     lmax = fmaxf(lmax, v[i]);
                 }
                 if (fvalid) *reinterpret_cast<f32x4*>(orow + m0) = v;
@@ -1062,7 +1079,7 @@ static bool fc_build_tables(const float* fb /* [201][80] */, float* tab /* [FC_T
         n_slots[k2] = bnd[25 * k2 + 24] - bnd[25 * k2] + 2;
         total += n_slots[k2];
     }
-    if (total > FC_ROW_X1) return false;
+    if (total > FC_ROW_X1IM) return false;
     int* comb = reinterpret_cast<int*>(tab + FC_COMB);
     for (int m = 0; m < N_MELS; ++m) {
         int n = 0;
@@ -1158,6 +1175,9 @@ struct radad_embed_s {
     bool plan_has_chunks = false;        // the cached plan carries the chunk arrays
     DevBuf seg_stats, chunk_rec;
     int last_logmel_kind = 0;            // 0 per segment, 1 shared clip frames (radad_embed_last_logmel_kind)
+    // the rows the most recent log-mel launch left in `logmel` / `seg_max` (radad_embed_last_logmel reads these; nothing else does)
+    int64_t rows_nseg = -1;              // segments of that launch, or their upper bound (-1: no launch yet)
+    bool rows_count_on_device = false;   // the true count is n_seg_dev[0] (device-built plan)
     int n_cus = 256;                     // compute units of the device (two chunk workgroups run on each)
     int* levels_dev = nullptr;
     // plan cache + scratch
@@ -1324,6 +1344,8 @@ static int launch_logmel(radad_embed_t h, const float* wave_dev, int64_t n_seg, 
     const int wg_frames = std::max(p.split_f0, h->nf - p.split_f0);
     p.plane_halfs = lh_plane_halfs(wg_frames);
     h->last_logmel_kind = clip_frames ? (h->logmel_fft ? 2 : 1) : 0;
+    h->rows_nseg = n_seg;
+    h->rows_count_on_device = n_seg_dev != nullptr;
     if (clip_frames) {
         // the segments' statistics first (the transform is shared, the normalisation is not), then chunks and edge frames in one grid
         if ((rc = h->seg_stats.ensure((size_t)n_seg * 4 * sizeof(float)))) return rc;
@@ -1535,7 +1557,7 @@ int radad_embed_create_ex(const radad_embed_cfg* cfg, int flags, const float* me
         h->fb1[0] = mel_filters_host[1 * N_MELS + 0];
         h->fb1[1] = mel_filters_host[1 * N_MELS + 1];
     }
-    { const char* e = radad_env_override("RADAD_LOGMEL_F32", "non-zero selects the fp32-MFMA log-mel kernel (k_logmel, ~2x slower) for extractors created from now on"); h->logmel_f32 = ((e && atoi(e) != 0) || (flags & RADAD_EMBED_LOGMEL_F32)) ? 1 : 0; }
+    { const char* e = radad_env_override("RADAD_LOGMEL_F32", "non-zero selects the fp32-MFMA log-mel kernel (k_logmel, ~3x slower) for extractors created from now on"); h->logmel_f32 = ((e && atoi(e) != 0) || (flags & RADAD_EMBED_LOGMEL_F32)) ? 1 : 0; }
     std::vector<float> fft_tab(FC_TAB_FLOATS);
     {
         // the shared-frame work list as a radix FFT on the vector ALU whenever the configuration allows sharing and the filter bank is triangular
@@ -1863,6 +1885,41 @@ int radad_embed_last_logmel_kind(radad_embed_t h, int* kind_out) {
     RADAD_REQUIRE(h && kind_out, "radad_embed_last_logmel_kind: NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
     *kind_out = h->last_logmel_kind;
+    return RADAD_OK;
+}
+
+// Diagnostic: the log-mel rows the most recent forward / stage call left in the handle, finalised the way the stage API finalises them
+// (k_logmel_finalize with the handle's own segment maxima).  Reads only: one launch on `stream` behind that call, nothing of the handle
+// changes.
+int radad_embed_last_logmel(radad_embed_t h, float* out_dev, int64_t segment_capacity, int64_t* n_segments_out, void* stream) {
+    RADAD_REQUIRE(h && n_segments_out, "radad_embed_last_logmel: NULL argument");
+    RADAD_REQUIRE(segment_capacity >= 0, "radad_embed_last_logmel: negative capacity");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->rows_nseg < 0 || !h->logmel.p || !h->seg_max.p) {
+        radad_set_error("radad_embed_last_logmel: the handle holds no log-mel rows (no forward yet, or its buffers were released)");
+        return RADAD_ESTATE;
+    }
+    DeviceGuard g(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    int64_t n_seg = h->rows_nseg;
+    if (h->rows_count_on_device) {                        // k_build_plan's own count; the launch was sized for an upper bound
+        int count = 0;
+        RADAD_HIP_CHECK(hipMemcpyAsync(&count, h->n_seg_dev.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        RADAD_HIP_CHECK(hipStreamSynchronize(st));
+        if (count < 0 || count > h->rows_nseg) {
+            radad_set_error("radad_embed_last_logmel: the plan's segment count %d exceeds its cap %lld", count, (long long)h->rows_nseg);
+            return RADAD_ESTATE;
+        }
+        n_seg = count;
+    }
+    *n_segments_out = n_seg;
+    if (!out_dev) return RADAD_OK;                        // the count alone, to size the buffer
+    RADAD_REQUIRE(segment_capacity >= n_seg, "radad_embed_last_logmel: the rows of %lld segments need room, capacity is %lld",
+                  (long long)n_seg, (long long)segment_capacity);
+    if (n_seg == 0) return RADAD_OK;
+    hipLaunchKernelGGL(k_logmel_finalize, dim3(2048), dim3(256), 0, st, (const float*)h->logmel.p, (const float*)h->seg_max.p, h->nf,
+                       h->T, n_seg, out_dev);
+    RADAD_HIP_CHECK(hipGetLastError());
     return RADAD_OK;
 }
 

@@ -34,8 +34,8 @@ constexpr int FC_OCT = 2;                          // octets (8 frames) a wave t
 static_assert(FC_OCT == 2 && FC_WAVES * FC_OCT * 8 == FC_SLOTS, "every slot has a lane octet; the two octets of a wave are the two halves of a packed fp32 pair");
 constexpr int FC_CAP = FFT_HOP * (FC_SLOTS - 1) + N_FFT;     // floats of sample storage: 64 consecutive frames
 constexpr int FC_EDGE_CHUNK = FC_CAP / N_FFT;      // edge frames of an edge-only chunk (each its own 400-sample window)
-constexpr int FC_LMS = 112;                        // floats per row of the LDS mel tile: the 8 lanes' band slots, Re X'[1], a zero
-constexpr int FC_ROW_X1 = 110, FC_ROW_ZERO = 111;  // (floats) where a row keeps Re X'[1] and a slot nobody writes after it was zeroed
+constexpr int FC_LMS = 112;                        // floats per row of the LDS mel tile: the 8 lanes' band slots, X'[1], a zero
+constexpr int FC_ROW_X1IM = 109, FC_ROW_X1 = 110, FC_ROW_ZERO = 111;  // (floats) where a row keeps Im and Re X'[1], and a slot nobody writes after it was zeroed
 constexpr int FC_TABK = 80;                        // floats per k1 of the lane tables: [window 2][W200 2][W400 2][mel 4] x 8 lanes
 constexpr int FC_NET = 25 * FC_TABK;               // then 8 floats x 8 lanes of exchange-stage constants
 constexpr int FC_COMB = FC_NET + 64;               // then per band the byte offsets of the (at most two) slots that add up to it
@@ -323,7 +323,9 @@ __device__ __forceinline__ void fc_process(const LogmelParams& p, const FcGeom& 
             const f32x2 e1 = ar + br, o1 = ar - br, e2 = ai + bi, o2 = ai - bi;
             const f32x2 re2 = fc_fma(-pw.y, o1, fc_fma(pw.x, e2, e1));      // 2 Re X
             const f32x2 im2 = fc_fma(-pw.y, e2, fc_fma(-pw.x, o1, o2));     // 2 Im X
-            const f32x2 pw4 = fc_fma(re2, re2, im2 * im2);                  // 4 |X|^2
+            f32x2 pw4 = fc_fma(re2, re2, im2 * im2);                        // 4 |X|^2
+            // bin 1 (k1 = 1 of lane 0) stays out of the shared sums: every owner adds it with its own mean folded in (epilogue)
+            if (k1 == 1) pw4 = pl == 0 ? f32x2{0.f, 0.f} : pw4;
             a0 = fc_fma(ml[0], pw4, a0);
             a1 = fc_fma(ml[1], pw4, a1);
             if (!RADAD_DBG(p.debug, 4)) {
@@ -339,9 +341,11 @@ __device__ __forceinline__ void fc_process(const LogmelParams& p, const FcGeom& 
                 a0 = fc_fma(take, a1, keep * a0);
             } else a0 = fc_fma(1.f - keep, a1, keep * a0);
             a1 = keep * a1;
-            if (k1 == 1 && pl == 0) {                          // Re X'[1]
+            if (k1 == 1 && pl == 0) {                          // X'[1]
                 reinterpret_cast<float*>(rowp0)[FC_ROW_X1] = 0.5f * re2.x;
                 reinterpret_cast<float*>(rowp1)[FC_ROW_X1] = 0.5f * re2.y;
+                reinterpret_cast<float*>(rowp0)[FC_ROW_X1IM] = 0.5f * im2.x;
+                reinterpret_cast<float*>(rowp1)[FC_ROW_X1IM] = 0.5f * im2.y;
             }
         }
         // (the table marks the last bin as advancing: a0 now holds the band after the last bin's first one)
@@ -390,8 +394,8 @@ __device__ __forceinline__ void fc_process(const LogmelParams& p, const FcGeom& 
             z[i][2] = *reinterpret_cast<const float*>(lrowb + c1.x) + *reinterpret_cast<const float*>(lrowb + c1.y);
             z[i][3] = *reinterpret_cast<const float*>(lrowb + c1.z) + *reinterpret_cast<const float*>(lrowb + c1.w);
         }
-        const float z0 = z[0][0], z1 = z[0][1];              // linear mel' of bands 0, 1 (lanes gq == 0)
-        const float x1re = lrow[FC_ROW_X1];
+        const float z0 = z[0][0], z1 = z[0][1];              // linear mel' of bands 0, 1 without bin 1 (lanes gq == 0)
+        const float x1re = lrow[FC_ROW_X1], x1im = lrow[FC_ROW_X1IM];
 #pragma unroll
         for (int i = 0; i < 5; ++i)
 #pragma unroll
@@ -405,16 +409,16 @@ __device__ __forceinline__ void fc_process(const LogmelParams& p, const FcGeom& 
                 const int fl = edge ? (e_kind < 2 ? e_kind : T - 1) : jf - (sg - g.clip_seg0) * H;
                 const float g2 = st_o[o][2], lg = st_o[o][3];
                 const float d = p.normalize ? -100.f * (pivot - st_o[o][0]) : 0.f;
-                const float corr = 2.f * d * x1re + d * d;
+                const float p1 = fmaf(x1re + d, x1re + d, x1im * x1im);    // |X'[1] + d|^2: bin 1 of this owner, before its 1 / sd^2
                 float* orow = p.logmel + ((int64_t)sg * T + fl) * N_MELS;
 #pragma unroll
                 for (int i = 0; i < 5; ++i) {
                     f32x4 v;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = fmaxf(z[i][e] + lg, -10.f);
-                    if (i == 0 && gq == 0 && d != 0.f) {
-                        v[0] = log10f(fmaxf((z0 + p.fb1[0] * corr) * g2, 1e-10f));
-                        v[1] = log10f(fmaxf((z1 + p.fb1[1] * corr) * g2, 1e-10f));
+                    if (i == 0 && gq == 0) {
+                        v[0] = fmaxf(log10f(fmaf(p.fb1[0], p1, z0) * g2), -10.f);
+                        v[1] = fmaxf(log10f(fmaf(p.fb1[1], p1, z1) * g2), -10.f);
                     }
 #pragma unroll
                     for (int e = 0; e < 4; ++e) lmax_o[o] = fmaxf(lmax_o[o], v[e]);

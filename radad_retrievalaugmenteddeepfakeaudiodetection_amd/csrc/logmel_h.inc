@@ -61,10 +61,14 @@ __device__ __forceinline__ float block_max4(float v, float* scratch) {   // LH_W
 // frames); the segments differ only in their normalisation, which is affine -- x^ = (x - m_s) / sd_s -- and passes through the DFT:
 //     X^_s[k] = (X'[k] + (c - m_s) W[k]) / sd_s,      X' = DFT of the windowed (x - c),  W = DFT of the window itself = (200, -100, 0, ..)
 // for ANY pivot c.  Bin 0 has no weight in the Slaney filter bank (its first filter starts at 0 Hz), so the power spectrum of segment s
-// is that of x - c scaled by 1 / sd_s^2 except in bin 1, which reaches mel bands 0 and 1 only:
-//     mel_s[m] = (mel'[m] + fb[1][m] (2 d Re X'[1] + d^2)) / sd_s^2,   d = -100 (c - m_s)
-// and log10 of it is log10 mel' - 2 log10 sd_s for the other 78 bands.  c is the mean of the segment the chunk starts in (no correction
-// at all for that owner; for its neighbours d is the difference of two overlapping segments' means -- a DC offset cancels).  What is
+// is that of x - c scaled by 1 / sd_s^2 except in bin 1, which reaches mel bands 0 and 1 only.  Bin 1 therefore stays OUT of the
+// shared sums mel' and every owner adds its own:
+//     mel_s[m] = (mel'[m] + fb[1][m] ((Re X'[1] + d)^2 + Im X'[1]^2)) / sd_s^2,   d = -100 (c - m_s)
+// and log10 of it is log10 mel' - 2 log10 sd_s for the other 78 bands.  (The expanded form mel' + fb[1][m] (2 d Re X'[1] + d^2) with
+// bin 1 inside mel' is the same number on paper and was the first form here: three large terms that cancel when d is large against
+// what the frame holds in bin 1 -- a loud passage before a quiet one, a DC step inside a clip, digital silence after sound: bands 0-1
+// were off by 1e-3 .. 1 in final units, tests/test_gpu_logmel_designed.py.)  c is the mean of the segment the chunk starts in (d = 0
+// for that owner; for its neighbours d is the difference of two overlapping segments' means -- a DC offset cancels).  What is
 // NOT shared: a segment's frames 0, 1 and T - 1, whose windows reach past the segment and see its reflection.  So the work list is
 //     per clip:    its INTERIOR clip frames j in [2, (S - 1) H + T - 2], in chunks of LH_CLIP_FRAMES = 104 consecutive frames (one workgroup
 //                  each: the planes hold the 16 880 samples the chunk touches), every frame written to each segment s that owns it
@@ -447,7 +451,7 @@ __device__ __forceinline__ void logmel_h_body(const LogmelParams& p) {
     const int xoff = (CLIP && tf >= nfr_int) ? edge_off + LH_EDGE_STRIDE * (tf - nfr_int) : LH_FRAME_STRIDE * tf;
     const _Float16* xb_hi = shi + xoff + 8 * lh;
     const _Float16* xb_lo = slo + xoff + 8 * lh;
-    float x1re = 0.f;            // CLIP: Re X'[1] of the lane's frame (lanes 0-31 hold bin 1 in register 1 of bin tile 0)
+    float x1re = 0.f, x1im = 0.f;  // CLIP: X'[1] of the lane's frame (lanes 0-31 hold bin 1 in register 1 of bin tile 0)
     f16x8 xh = *reinterpret_cast<const f16x8*>(xb_hi);
     f16x8 xl = *reinterpret_cast<const f16x8*>(xb_lo);
 #define LH_STEP(SLOT, d)                                                                                                \
@@ -476,7 +480,7 @@ __device__ __forceinline__ void logmel_h_body(const LogmelParams& p) {
             LH_STEP(LH_SLOT4, 4)
         }
         asm volatile("s_nop 15\n s_nop 3" : "+v"(re), "+v"(im));      // MFMA result -> VALU read wait states (see LH_MEL_STEP)
-        if constexpr (CLIP) { if (bt == 0) x1re = re[1] * unscale; }
+        if constexpr (CLIP) { if (bt == 0) { x1re = re[1] * unscale; x1im = im[1] * unscale; } }
         // |X|^2 -> mel, also on the f16 pipe: the lane's 16 power values (bins (r&3) + 8(r>>2) + 4lh) are the B operand of
         // two 16-deep MFMAs whose k order is permuted to match (k' = 8lh + j  <->  register 8h + j); the filter bank comes
         // pre-split in that order.  Powers span many decades, so each FRAME (lane pair l, l+32) gets its own power-of-two
@@ -490,6 +494,7 @@ __device__ __forceinline__ void logmel_h_body(const LogmelParams& p) {
             for (int r = 0; r < 16; ++r) {
                 const float a = re[r] * unscale, b = im[r] * unscale;
                 pwv[r] = a * a + b * b;
+                if (CLIP && r == 1) pwv[r] = (bt == 0 && lh == 0) ? 0.f : pwv[r];    // bin 1 stays out of the shared sums (see above)
                 m = fmaxf(m, pwv[r]);
             }
             m = fmaxf(m, __shfl_xor(m, 32));
@@ -565,7 +570,7 @@ __device__ __forceinline__ void logmel_h_body(const LogmelParams& p) {
                     f32x4 v;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        v[i] = log10f(fmaxf(zacc[mt][4 * g + i], 1e-10f));
+                        v[i] = fmaxf(log10f(zacc[mt][4 * g + i]), -10.f);     // log10(max(mel, 1e-10)), the floor exactly -10 (fmaxf drops the NaN of a rounding-negative sum)
                         if (fvalid) lmax = fmaxf(lmax, v[i]);
                     }
                     if (fvalid) *reinterpret_cast<f32x4*>(orow + m0) = v;
@@ -601,7 +606,7 @@ __device__ __forceinline__ void logmel_h_body(const LogmelParams& p) {
             st_o[o] = f32x4{0.f, 1.f, 1.f, 0.f};
             if (p.normalize && s_lo + o <= s_hi) st_o[o] = reinterpret_cast<const f32x4*>(p.seg_stats)[s_lo + o];
         }
-        const float z0 = zacc[0][0], z1 = zacc[0][1];  // linear mel' of bands 0, 1 (lanes 0-31)
+        const float z0 = zacc[0][0], z1 = zacc[0][1];  // linear mel' of bands 0, 1 without bin 1 (lanes 0-31)
         // log10 mel' once, in place
 #pragma unroll
         for (int mt = 0; mt < NMT; ++mt)
@@ -617,7 +622,7 @@ __device__ __forceinline__ void logmel_h_body(const LogmelParams& p) {
                 const float g2 = st_o[o][2], lg = st_o[o][3];
                 const float d = p.normalize ? -100.f * (pivot - st_o[o][0]) : 0.f;
                 float* orow = p.logmel + ((int64_t)sg * T + fl) * N_MELS;
-                const float corr = 2.f * d * x1re + d * d;
+                const float p1 = fmaf(x1re + d, x1re + d, x1im * x1im);    // |X'[1] + d|^2: bin 1 of this owner, before its 1 / sd^2
 #pragma unroll
                 for (int mt = 0; mt < NMT; ++mt)
 #pragma unroll
@@ -627,9 +632,9 @@ __device__ __forceinline__ void logmel_h_body(const LogmelParams& p) {
                             f32x4 v;
 #pragma unroll
                             for (int i = 0; i < 4; ++i) v[i] = fmaxf(zacc[mt][4 * g + i] + lg, -10.f);
-                            if (mt == 0 && g == 0 && lh == 0 && d != 0.f) {
-                                v[0] = log10f(fmaxf((z0 + p.fb1[0] * corr) * g2, 1e-10f));
-                                v[1] = log10f(fmaxf((z1 + p.fb1[1] * corr) * g2, 1e-10f));
+                            if (mt == 0 && g == 0 && lh == 0) {
+                                v[0] = fmaxf(log10f(fmaf(p.fb1[0], p1, z0) * g2), -10.f);
+                                v[1] = fmaxf(log10f(fmaf(p.fb1[1], p1, z1) * g2), -10.f);
                             }
 #pragma unroll
                             for (int i = 0; i < 4; ++i) lmax_o[o] = fmaxf(lmax_o[o], v[i]);
@@ -664,7 +669,10 @@ __global__ __launch_bounds__(LH_THREADS, 2) __attribute__((amdgpu_num_vgpr(LH_FR
 }
 
 // [S][4]: mean, inv = 1 / sqrt(var + 1e-7), inv^2 and 2 log10(inv) of every segment (zero padded to L), mean and variance as
-// k_logmel_h's prologue computes them: two passes from registers
+// k_logmel_h's prologue computes them: two passes from registers.  A segment whose variance is exactly zero -- every sample equals the
+// mean: digital silence inside a live clip -- normalises to zeros whatever 1 / sqrt(1e-7) is, and the per-segment kernels give it
+// log10(1e-10) in every cell.  The shared transform of x - c cannot: its rounding noise around a pivot taken from a live neighbour,
+// times 1 / 1e-7, rises above 1e-10.  Such a segment therefore gets inv^2 = 0 and 2 log10(inv) = -inf: every owner row of it is the floor.
 __global__ __launch_bounds__(LH_THREADS) void k_seg_stats(const float* __restrict__ wave, const int64_t* __restrict__ seg_start,
                                                           const int* __restrict__ seg_valid, int L, int n_seg,
                                                           const int* __restrict__ n_seg_dev, float* __restrict__ stats,
@@ -713,7 +721,8 @@ __global__ __launch_bounds__(LH_THREADS) void k_seg_stats(const float* __restric
     const float var = block_sum(lsq, scratch, LH_WAVES) / (float)L;
     if (tid == 0) {
         const float inv = 1.0f / sqrtf(var + 1e-7f);
-        reinterpret_cast<f32x4*>(stats)[s] = f32x4{mean, inv, inv * inv, 2.f * log10f(inv)};
+        const bool flat = var == 0.f;
+        reinterpret_cast<f32x4*>(stats)[s] = f32x4{mean, inv, flat ? 0.f : inv * inv, flat ? -INFINITY : 2.f * log10f(inv)};
         seg_max[s] = seg_max_init;                      // the running maximum k_logmel_h_clip raises (saves the fill launch)
     }
 }

@@ -240,6 +240,19 @@ class MelProjectionFeatureExtractor:
         _lib.check(self._lib.radad_embed_last_logmel_kind(self._h, C.byref(k)), "radad_embed_last_logmel_kind")
         return {0: "per_segment", 1: "clip_frames", 2: "clip_frames_fft"}[k.value]
 
+    def last_logmel(self):
+        """Diagnostic: the log-mel rows [S, T, 80] the most recent embed_clips / stage call of this extractor computed, segments in plan
+        order, clamped at each segment's max - 8 and scaled (x + 4) / 4 as log_mel() returns them (radad_embed_last_logmel: one small
+        kernel on the current stream, nothing of the handle changes)."""
+        import torch
+        n = C.c_int64()
+        with torch.cuda.device(self.device):
+            st = _lib.stream_ptr(self.device)
+            _lib.check(self._lib.radad_embed_last_logmel(self._h, None, 0, C.byref(n), st), "radad_embed_last_logmel")
+            out = torch.empty((n.value, self.num_frames, N_MELS), device=self.device, dtype=torch.float32)
+            _lib.check(self._lib.radad_embed_last_logmel(self._h, out.data_ptr(), n.value, C.byref(n), st), "radad_embed_last_logmel")
+        return out
+
     def profile(self, enable: bool = True):
         _lib.check(self._lib.radad_embed_profile(self._h, 1 if enable else 0), "radad_embed_profile")
 
