@@ -1101,6 +1101,73 @@ int radad_fuse_head_backward(const radad_head_train_weights* w, const float* tpp
                              float* workspace_dev, int64_t workspace_bytes, int device, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The training step behind the backward (pipeline.py:815-836; csrc/optim_step.inc): loss, gradient norms, clipping, Adam and
+ * the loss-scale bookkeeping in four launches, without a host round trip.  Everything the loop logs stays on the device.
+ * fp32 data; every sum in fp64 in a fixed order, no float atomics: two runs give the same bits.
+ *
+ * radad_bce_logits -- BCEWithLogitsLoss(pos_weight) (pipeline.py:768-770,815), scaler.scale(loss).backward()'s gradient for
+ * the logits (:820) and the accuracy count (:835-836) in one launch.  With w_i = 1 + (pos_weight - 1) y_i:
+ *   loss = mean_i (1 - y_i) x_i + w_i (log1p(exp(-|x_i|)) + max(-x_i, 0))           (unscaled, finite at x = +-100)
+ *   dlogits_i = (s / n) ((1 - y_i) - w_i sigmoid(-x_i))     s = *scale_dev, or 1 when scale_dev is NULL
+ *   correct = #{i : (x_i > 0) == (y_i == 1)}
+ * labels are 0 / 1 as float32.  RADAD_EINVAL before any HIP call: n <= 0, pos_weight <= 0 (or NaN), a NULL buffer.
+ *
+ * radad_optim_step -- scaler.unscale_ x3 (:822-824), clip_grad_norm_ x3 (:825-827), scaler.step x3 over torch.optim.Adam
+ * (:829-831, pipeline.py:96-107) and scaler.update (:832), for up to RADAD_OPTIM_MAX_GROUPS optimizers ("groups") at once.
+ * Per group g over its tensors that have a gradient, inv = 1 / scale as it stands when the call begins:
+ *   grad_norm[g] = sqrt(sum (grad inv)^2)      found_inf[g] = some grad element is inf or NaN
+ *   coef = min(1, max_norm / (grad_norm[g] + 1e-6))      (max_norm <= 0: the norm is reported, coef = 1)
+ * A group with found_inf set is skipped as a whole when a scale is in use: its param, exp_avg, exp_avg_sq and step count stay
+ * as they are, and what its gradients hold afterwards is unspecified.  So is a group none of whose tensors has a gradient
+ * (norm 0, step count unchanged).  Every other group steps: t = ++steps[g], and per element
+ *   grad <- grad inv coef      (in place: what unscale_ and clip_grad_norm_ leave)
+ *   g = grad + weight_decay param     exp_avg <- beta1 exp_avg + (1 - beta1) g     exp_avg_sq <- beta2 exp_avg_sq + (1 - beta2) g^2
+ *   param <- param - lr / (1 - beta1^t) * exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - beta2^t) + eps)
+ * (torch.optim.Adam's defaults: weight decay added to the gradient, no amsgrad).  The hyperparameters are float32: beta2 =
+ * 0.999 is the float nearest to it, and 1 - beta is formed from that float in double.
+ * Then GradScaler.update: some group found a non-finite gradient -> scale *= backoff, growth_tracker = 0; else
+ * ++growth_tracker, and at growth_interval scale *= growth (if that is finite), growth_tracker = 0.
+ * state->scale and state->growth_tracker both NULL: no scaling and no skipping, plain clip + Adam; a non-finite gradient then
+ * spreads as it does in torch (found_inf is still reported).
+ * A tensor with grad == NULL (a parameter whose .grad is None) or numel == 0 takes no part.  Tensors may be views: an array
+ * that does not start on a 16-byte boundary is read and written element by element.  tensors_host and groups_host are host
+ * arrays, read during the call; pointers inside them and in state are device pointers.  Stream-ordered, no synchronisation,
+ * no allocation, no copy: the tables travel as kernel arguments.
+ * RADAD_EINVAL before any HIP call: n_tensors outside 0..RADAD_OPTIM_MAX_TENSORS, n_groups outside 1..RADAD_OPTIM_MAX_GROUPS,
+ * a NULL struct, state pointer, workspace or (beside a gradient) param / exp_avg / exp_avg_sq, scale / growth_tracker half
+ * NULL, a group index out of range, numel < 0, a beta outside [0, 1), eps <= 0, lr < 0, weight_decay < 0, with a scale growth
+ * < 1, backoff outside (0, 1] or growth_interval < 1, a workspace below radad_optim_workspace_bytes (which covers every
+ * listed tensor, with or without a gradient; -1 for n_tensors out of range, a NULL list or a negative numel).
+ * ---------------------------------------------------------------------------------------------- */
+#define RADAD_OPTIM_MAX_TENSORS 64
+#define RADAD_OPTIM_MAX_GROUPS 8
+typedef struct radad_optim_tensor {
+    float* param;
+    float* grad;                                         /* NULL: the tensor takes no part in this step         */
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t numel;
+    int32_t group;
+} radad_optim_tensor;
+typedef struct radad_optim_group {
+    float lr, beta1, beta2, eps, weight_decay, max_norm;
+} radad_optim_group;
+typedef struct radad_optim_state {   /* device pointers */
+    float* scale;                                        /* [1], or NULL with growth_tracker: no loss scale     */
+    int32_t* growth_tracker;                             /* [1]                                                 */
+    int32_t* steps;                                      /* [n_groups] Adam's t per group                       */
+    float* grad_norm;                                    /* [n_groups] out: norm of the unscaled gradients      */
+    int32_t* found_inf;                                  /* [n_groups] out: 0 / 1                               */
+} radad_optim_state;
+int64_t radad_optim_workspace_bytes(const int64_t* numels, int n_tensors);
+int radad_optim_step(const radad_optim_tensor* tensors_host, int n_tensors, const radad_optim_group* groups_host, int n_groups,
+                     const radad_optim_state* state, float growth, float backoff, int growth_interval, void* ws_dev,
+                     int64_t ws_bytes, int device, void* stream);
+int radad_bce_logits(const float* logits_dev /*[n]*/, const float* labels_dev /*[n]*/, int64_t n, float pos_weight,
+                     const float* scale_dev /*[1] or NULL*/, float* loss_out_dev /*[1]*/, float* dlogits_out_dev /*[n]*/,
+                     int32_t* correct_out_dev /*[1]*/, int device, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Synthetic inputs (bench / tests only): a stateless integer hash so host and device produce the
  * SAME bits for element (seed, row, col).  See oracle/synth.py for the host twin.
  * ---------------------------------------------------------------------------------------------- */

@@ -94,6 +94,21 @@ class HeadGrads(C.Structure):           # radad_head_grads
 
 HeadMasks = C.c_void_p * HEAD_MAX_LAYERS    # host array of per-hidden-layer dropout mask pointers
 
+OPTIM_MAX_TENSORS, OPTIM_MAX_GROUPS = 64, 8     # RADAD_OPTIM_MAX_*
+
+
+class OptimTensor(C.Structure):         # radad_optim_tensor
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("numel", C.c_int64), ("group", C.c_int32)]
+
+
+class OptimGroup(C.Structure):          # radad_optim_group
+    _fields_ = [(n, C.c_float) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "max_norm")]
+
+
+class OptimState(C.Structure):          # radad_optim_state: device pointers
+    _fields_ = [(n, C.c_void_p) for n in ("scale", "growth_tracker", "steps", "grad_norm", "found_inf")]
+
 
 # name -> (restype, argtypes); every symbol include/radad_hip.h declares
 SIGNATURES = {
@@ -251,6 +266,11 @@ SIGNATURES = {
     "radad_fuse_head_backward": (C.c_int, [C.POINTER(HeadTrainWeights), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_float,
                                            C.POINTER(HeadSaved), C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(HeadGrads),
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "radad_optim_workspace_bytes": (C.c_int64, [c_i64p, C.c_int]),
+    "radad_optim_step": (C.c_int, [C.POINTER(OptimTensor), C.c_int, C.POINTER(OptimGroup), C.c_int, C.POINTER(OptimState),
+                                   C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "radad_bce_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_int, C.c_void_p]),
     "radad_synth_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_uint64, C.c_int, C.c_void_p]),
     "radad_synth_audio": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int, C.c_void_p]),
 }
