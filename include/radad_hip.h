@@ -1168,6 +1168,79 @@ int radad_bce_logits(const float* logits_dev /*[n]*/, const float* labels_dev /*
                      int32_t* correct_out_dev /*[1]*/, int device, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The validation pass (pipeline.py:691-756, 862-872, 964-987; csrc/eval_metrics.inc, planned by csrc/eval_plan.h): what
+ * evaluate_with_scores reads back per batch and what train() / evaluate() then compute in numpy, on the device.
+ *
+ * radad_eval_append -- per validation batch, replaces loss.item(), (preds == labels).sum().item(), logits.cpu().tolist() and
+ * lbls.cpu().tolist() (pipeline.py:727-733).  One launch, stream-ordered, no synchronisation, no allocation.  Writes one
+ * 64-bit sort key per sample at keys_dev[offset + i]:
+ *   group id (0 .. 2^31 - 1; 0 where group_ids_dev is NULL) << 33 | image(score) << 1 | (label == 1)
+ * image() is the order-preserving 32-bit image of the float32 score, with -0.0 mapped to +0.0 (numpy's unique / searchsorted
+ * treat them as one threshold).  Adds into acc_dev (RADAD_EVAL_ACC_BYTES: double loss_sum, int64 correct, int64 count, int64
+ * nonfinite) the batch's sum of BCEWithLogitsLoss(pos_weight) terms (radad_bce_logits' formula, unscaled, fp64 terms summed in
+ * fp64 in one order), #{(x > 0) == (y == 1)}, n and #{x not finite}, by plain read-add-write of one thread: appends that share
+ * acc_dev must be ordered on one stream.  val_loss is loss_sum / count (the reference weights batch means by batch size: the
+ * same number up to rounding), val_acc is correct / count (:754-755).
+ * RADAD_EINVAL before any HIP call: n <= 0, offset < 0, offset + n > RADAD_EVAL_MAX_N, pos_weight <= 0 (or NaN), a NULL
+ * logits / labels / keys / acc.
+ *
+ * radad_eval_metrics -- _compute_eer (:152-175), _compute_macro_eer_by_group (:178-193), _compute_min_tDCF (:277-326),
+ * _roc_curve / _auc (:196-234; _roc_curve's three outputs, :196-229, are the columns _plot_and_save_roc_det, :619, writes to
+ * its CSV) over keys_dev[0 .. n).  Stream-ordered, no
+ * host round trip, bitwise reproducible; keys_dev is not modified (more appends and another call are fine).  Hand-written
+ * sort (LDS bitonic tiles + merge-path passes), counts by scan, then per distinct score t of a segment, in ascending order
+ * behind -inf and in front of +inf:  fnr = #{positives < t} / P,  fpr = #{negatives >= t} / N  (fp64 divisions of integers).
+ *   out[RADAD_EVAL_EER], [_EER_THRESHOLD]   (fnr + fpr) / 2 * 100 at the first candidate with the least |fnr - fpr|, and it
+ *   out[RADAD_EVAL_MACRO_EER], [_GROUPS_SCORED]   the fp64 mean of the same EER per group id over the groups that hold both
+ *                                classes, added one by one in ascending group id, and how many did; NaN and 0 if none.  has_groups == 0 (every id equal by the
+ *                                caller's word) or all ids equal on the device: the pooled EER (1 group, or NaN and 0)
+ *   out[RADAD_EVAL_MIN_TDCF], [_MIN_TDCF_THRESHOLD]   the first least ((c0 + (c1 (1 - fnr)) p_fa_spoof_asv) + c2 fnr) / c_def,
+ *                                no FMA contraction; NaN, NaN with consts == NULL.  consts is a host struct read during the call:
+ *                                c0 = C_miss_asv pi_tar P_miss_asv + C_fa_asv pi_non P_fa_asv, c1 = C_fa_cm pi_spoof,
+ *                                c2 = C_miss_cm pi_tar, c_def = min(C_miss_asv pi_tar, C_fa_asv pi_non) (:303-323)
+ *   out[RADAD_EVAL_AUC]          sum over distinct scores descending of (fp_i - fp_{i-1}) (tp_i + tp_{i-1}) in int64, exact,
+ *                                divided once by 2 P N
+ *   out[RADAD_EVAL_NONFINITE], [_POSITIVES], [_NEGATIVES], [_ROC_POINTS], [_DISTINCT]   counts, as doubles
+ *   roc_dev (or NULL)            double[3 (n + 2)]: fpr at [0, n + 2), tpr at [n + 2, 2 (n + 2)), threshold behind; the first
+ *                                out[RADAD_EVAL_ROC_POINTS] of each are written: (0, 0, max + 1e-6), one point per distinct
+ *                                score descending, (1, 1, min - 1e-6)
+ *   group_eer_dev (or NULL)      double[n]: the first out[RADAD_EVAL_GROUPS_SCORED] are written: the EER of every group that
+ *                                holds both classes, in ascending group id (the terms of the macro-EER)
+ * DEVIATION from the reference on tied scores: _roc_curve keeps the first element of each run of equal scores after an unstable
+ * argsort, so its ROC points and AUC depend on an unspecified order inside the run.  Here a point carries the counts at the END
+ * of its run, which gives the usual AUC = (#{pos > neg} + #{pos == neg} / 2) / (P N).  Without ties the two coincide.
+ * P == 0 or N == 0: EER and t-DCF NaN, AUC 0.5, ROC (0, 0, inf), (1, 1, -inf), as the reference.  A non-finite score is outside
+ * the contract: every metric is NaN, the count is reported, nothing faults.
+ * RADAD_EINVAL before any HIP call: n outside 1..RADAD_EVAL_MAX_N, a NULL keys / out / workspace, a workspace that does not
+ * start on a 16-byte boundary or is below radad_eval_metrics_workspace_bytes(n, has_groups) (-1 for n out of range).
+ * ---------------------------------------------------------------------------------------------- */
+#define RADAD_EVAL_MAX_N (1 << 24)
+#define RADAD_EVAL_ACC_BYTES 32
+#define RADAD_EVAL_OUT_DOUBLES 16
+#define RADAD_EVAL_AUC 0
+#define RADAD_EVAL_EER 1
+#define RADAD_EVAL_EER_THRESHOLD 2
+#define RADAD_EVAL_MACRO_EER 3
+#define RADAD_EVAL_GROUPS_SCORED 4
+#define RADAD_EVAL_MIN_TDCF 5
+#define RADAD_EVAL_MIN_TDCF_THRESHOLD 6
+#define RADAD_EVAL_NONFINITE 7
+#define RADAD_EVAL_POSITIVES 8
+#define RADAD_EVAL_NEGATIVES 9
+#define RADAD_EVAL_ROC_POINTS 10
+#define RADAD_EVAL_DISTINCT 11
+typedef struct radad_tdcf_consts {
+    double c0, c1, c2, p_fa_spoof_asv, c_def;
+} radad_tdcf_consts;
+int64_t radad_eval_metrics_workspace_bytes(int64_t n, int has_groups);
+int radad_eval_append(const float* logits_dev /*[n]*/, const float* labels_dev /*[n]*/, const int32_t* group_ids_dev /*[n] or NULL*/,
+                      int64_t n, float pos_weight, int64_t offset, uint64_t* keys_dev, void* acc_dev, int device, void* stream);
+int radad_eval_metrics(const uint64_t* keys_dev, int64_t n, int has_groups, const radad_tdcf_consts* consts /*host, or NULL*/,
+                       double* out_dev /*[RADAD_EVAL_OUT_DOUBLES]*/, double* roc_dev /*[3 (n + 2)] or NULL*/,
+                       double* group_eer_dev /*[n] or NULL*/, void* ws_dev,
+                       int64_t ws_bytes, int device, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Synthetic inputs (bench / tests only): a stateless integer hash so host and device produce the
  * SAME bits for element (seed, row, col).  See oracle/synth.py for the host twin.
  * ---------------------------------------------------------------------------------------------- */

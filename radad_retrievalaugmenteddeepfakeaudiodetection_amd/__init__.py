@@ -16,8 +16,9 @@ from .projection import ProjectionLayer
 from .radad_model import DetectionModel, RADADModel
 from .sharded import ReplicatedSearch, ShardedSearch, shard_bounds
 from .train_step import HipTrainStep
+from .eval_step import HipEvalMetrics
 
 __all__ = ["Config", "AudioSegmenter", "TemporalPyramidPooling", "HipFlatIndex", "HipIVFFlatIndex", "VectorDatabase",
            "MelProjectionFeatureExtractor", "Wav2Vec2FeatureExtractor", "WhisperFeatureExtractor", "WavLMFeatureExtractor",
            "build_feature_extractor", "HotPathPipeline", "ProjectionLayer", "DetectionModel", "RADADModel",
-           "ShardedSearch", "ReplicatedSearch", "shard_bounds", "HipTrainStep"]
+           "ShardedSearch", "ReplicatedSearch", "shard_bounds", "HipTrainStep", "HipEvalMetrics"]

@@ -110,6 +110,15 @@ class OptimState(C.Structure):          # radad_optim_state: device pointers
     _fields_ = [(n, C.c_void_p) for n in ("scale", "growth_tracker", "steps", "grad_norm", "found_inf")]
 
 
+EVAL_MAX_N, EVAL_ACC_BYTES, EVAL_OUT_DOUBLES = 1 << 24, 32, 16     # RADAD_EVAL_*
+EVAL_OUT = ("auc", "eer_percent", "eer_threshold", "macro_eer_percent", "groups_scored", "min_tDCF", "min_tDCF_threshold",
+            "nonfinite", "positives", "negatives", "roc_points", "distinct")      # RADAD_EVAL_AUC .. RADAD_EVAL_DISTINCT
+
+
+class TdcfConsts(C.Structure):          # radad_tdcf_consts
+    _fields_ = [(n, C.c_double) for n in ("c0", "c1", "c2", "p_fa_spoof_asv", "c_def")]
+
+
 # name -> (restype, argtypes); every symbol include/radad_hip.h declares
 SIGNATURES = {
     "radad_abi_version": (C.c_int, []),
@@ -271,6 +280,11 @@ SIGNATURES = {
                                    C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "radad_bce_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_int, C.c_void_p]),
+    "radad_eval_metrics_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int]),
+    "radad_eval_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_int, C.c_void_p]),
+    "radad_eval_metrics": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(TdcfConsts), C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "radad_synth_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_uint64, C.c_int, C.c_void_p]),
     "radad_synth_audio": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int, C.c_void_p]),
 }

@@ -497,3 +497,4 @@ int radad_fuse_head_forward(const radad_head_weights* w, const float* tpp_dev, c
 #include "proj_train.inc"
 #include "head_train.inc"
 #include "optim_step.inc"
+#include "eval_metrics.inc"
