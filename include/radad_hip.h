@@ -19,6 +19,9 @@
  *     hipMalloc of 2 bytes per element, one small read-back -- i.e. it stalls every stream of the device once (0.84 ms of
  *     kernel time per million rows of 512).  Build-then-search callers never notice; a caller that interleaves adds and
  *     searches on several streams should radad_knn_reserve up front and run one warm-up search after the last add.
+ *   - the maintenance calls synchronise by design: radad_knn_reserve, radad_knn_load / _load_range, radad_knn_save and
+ *     radad_knn_remove_ids / _remove_ids_host wait for the whole device before they touch the rows (searches on other streams
+ *     may still read them), and the last of these also reads its counts back and returns with its moves complete.
  *
  * Each group cites the reference interface (file:line under the RADAD repository) it replaces.
  */
@@ -135,6 +138,10 @@ int radad_knn_create_ex(int dim, int metric, int store_dtype, int device, int64_
 #define RADAD_KNN_OPT_ABANDON_DEAL 7
 #define RADAD_KNN_OPT_ABANDON_DEFER 8
 #define RADAD_KNN_OPT_ABANDON_AHEAD 9
+/*   RADAD_KNN_OPT_REMOVE_STAGE_ROWS  0 (default: as many rows as 64 MiB hold) / n > 0: radad_knn_remove_ids walks the store in slabs of n
+ *                            rows and stages a slab in a buffer of n rows; values below 64 are raised to 64.  Same store afterwards
+ *                            whatever the value: it exists so that a test store of a few thousand rows spans dozens of slabs. */
+#define RADAD_KNN_OPT_REMOVE_STAGE_ROWS 10
 int radad_knn_set_option(radad_knn_t h, int option, int value);
 int radad_knn_destroy(radad_knn_t h);
 int radad_knn_dim(radad_knn_t h, int* dim);
@@ -149,6 +156,30 @@ int radad_knn_reserve(radad_knn_t h, int64_t capacity);
 int radad_knn_add(radad_knn_t h, const float* rows_dev, int64_t n, void* stream);
 /* same, from a host buffer (what index.add(np.ndarray) does); synchronous */
 int radad_knn_add_host(radad_knn_t h, const float* rows_host, int64_t n);
+/* Remove rows in place, on the device (faiss IndexFlat.remove_ids): the rows named by `ids` go, the others keep their bits and their
+ * relative order and hold positions 0 ... ntotal - 1 afterwards, so row i stays aligned with whatever the caller keeps per row.
+ *   ids_dev         [n_ids] GLOBAL ids (id_base + position), in any order, repeats allowed.  An id that names no stored row --
+ *                   negative, below id_base, at or beyond id_base + ntotal -- is ignored and not counted.  n_ids == 0 removes nothing
+ *   old_to_new_dev  NULL, or [ntotal before the call] int64: the new global id of every old position, -1 for a removed one (for the
+ *                   caller's own per-row columns, e.g. speaker tags)
+ *   n_removed_out   host, may be NULL: the number of DISTINCT rows removed; ntotal falls by it.  capacity is unchanged (no shrink)
+ * A synchronising maintenance call like radad_knn_reserve and radad_knn_load: it waits for the device before it touches anything
+ * (searches on other streams may still read the rows), reads the removed count back, and returns with the moves complete.  The mark,
+ * the prefix sum (integers only: deterministic) and the moves run on `stream`.  Workspace: 5 bytes per stored row plus a staging
+ * buffer of RADAD_KNN_OPT_REMOVE_STAGE_ROWS rows (64 MiB by default, never proportional to the store), taken from the handle's search
+ * workspace; when it cannot be allocated the call returns RADAD_ENOMEM and the store is exactly as it was.
+ * Refused with RADAD_ESTATE while a two-half search is pending (radad_knn_search_begin / _search_excl_begin without its _finish or
+ * radad_knn_search_abort), as radad_knn_add is refused; the handle stays usable.  RADAD_EINVAL for NULL ids with n_ids > 0.
+ * Afterwards every search path keeps its exactness contract: the f16 plane, its scales and the per-tile terms are kept for the rows
+ * in front of the first removed one and brought up to date behind it by the next search that wants them, as after an append -- the
+ * plane is not rebuilt.  A store emptied this way behaves like a new one that keeps its capacity.
+ * On a row shard (id_base != 0) ids outside the shard's own range are ignored and ids shift inside the shard only: the global id
+ * space then has a gap in front of the next shard. */
+int radad_knn_remove_ids(radad_knn_t h, const int64_t* ids_dev, int64_t n_ids, int64_t* old_to_new_dev, int64_t* n_removed_out, void* stream);
+/* same, with the id list on the host */
+int radad_knn_remove_ids_host(radad_knn_t h, const int64_t* ids_host, int64_t n_ids, int64_t* n_removed_out);
+/* the last removal's plan (no synchronisation): its move launches and the bytes they read + wrote; 0 / 0 when nothing moved */
+int radad_knn_last_remove(radad_knn_t h, int* n_launches, int64_t* bytes_moved);
 /* top-k of every query against the whole store.
  *   q_dev        [nq, dim] fp32
  *   out_dist_dev [nq, k] fp32  L2: squared distances ascending; IP/cosine: inner products descending

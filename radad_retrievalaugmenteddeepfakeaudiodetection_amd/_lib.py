@@ -27,6 +27,8 @@ KNN_OPT_RANGE_SMALLQ = 6                      # RADAD_KNN_OPT_RANGE_SMALLQ
 KNN_OPT_ABANDON_DEAL = 7                      # RADAD_KNN_OPT_ABANDON_DEAL
 KNN_OPT_ABANDON_DEFER = 8                     # RADAD_KNN_OPT_ABANDON_DEFER
 KNN_OPT_ABANDON_AHEAD = 9                     # RADAD_KNN_OPT_ABANDON_AHEAD
+KNN_OPT_REMOVE_STAGE_ROWS = 10                # RADAD_KNN_OPT_REMOVE_STAGE_ROWS
+KNN_REMOVE_MIN_STAGE_ROWS = 64                # KNN_REMOVE_MIN_STAGE_ROWS (knn_plan.h): smaller values are raised to it
 IVF_OPT_HI_SCAN = 0
 IVF_OPT_PQ_FILTER = 1      # RADAD_IVF_OPT_PQ_FILTER
 IVF_SCAN_KINDS = ("f32_lists", "hi_lists", "exact_flat")
@@ -134,6 +136,9 @@ SIGNATURES = {
     "radad_knn_reserve": (C.c_int, [C.c_void_p, C.c_int64]),
     "radad_knn_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "radad_knn_add_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "radad_knn_remove_ids": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, c_i64p, C.c_void_p]),
+    "radad_knn_remove_ids_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, c_i64p]),
+    "radad_knn_last_remove": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), c_i64p]),
     "radad_knn_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "radad_knn_search_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),

@@ -72,7 +72,8 @@ class Config:
         self.knn_abandon_defer = None       # 0 / 1: a vetoed tile's few live rows go to a dense tail (RADAD_KNN_OPT_ABANDON_DEFER; same results)
         self.knn_abandon_ahead = None       # 0 / 1: the abandon checkpoint fetches the next tile's head (RADAD_KNN_OPT_ABANDON_AHEAD; same results)
         self.knn_range_smallq = None        # True: range searches of <= 16 queries stream the f16 plane (RADAD_KNN_OPT_RANGE_SMALLQ 1; same results; default off)
-        self.knn_live_floor = None          # None / 0 only: the one-launch scan form was removed; kept as a key for old callers
+        self.knn_remove_stage_rows = None   # slab size of VectorDatabase.remove_vectors in rows (RADAD_KNN_OPT_REMOVE_STAGE_ROWS; None = 64 MiB of rows)
+        self.knn_live_floor = None         # None / 0 only: the one-launch scan form was removed; kept as a key for old callers
         # retrieval with exclusions (retrieve_similar_vectors): False = the reference's search K + 10, drop, pad (pipeline.py:478,491-515)
         self.exact_exclusion = False        # True: the K nearest rows that are not excluded, exactly (flat stores)
         self.exclusion_k_fetch = None       # ... size of the certified search in front of the exact pass (None = top_k + 10)

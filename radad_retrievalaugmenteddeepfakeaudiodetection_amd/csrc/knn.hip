@@ -2967,6 +2967,10 @@ struct radad_knn_s {
     // the next tile's head fetched at the abandon checkpoint (knn_abandon_ahead, knn_plan.h): two counters per launch in its set of deal_cnt
     int opt_abandon_ahead = 1;   // RADAD_KNN_OPT_ABANDON_AHEAD (measured: profiles/abandon_ahead_ab.txt)
     unsigned last_ahead_sets = 0;// the counter sets the last search's prefetching launches used, one bit each (radad_knn_last_abandon_ahead)
+    // removing rows in place (knn_remove.inc; the plan: knn_remove_plan, knn_plan.h)
+    int opt_remove_stage_rows = 0;       // RADAD_KNN_OPT_REMOVE_STAGE_ROWS: slab size in rows, 0 = what KNN_REMOVE_STAGE_BYTES holds
+    int last_remove_launches = 0;        // move launches of the last removal and the bytes they read + wrote (radad_knn_last_remove)
+    int64_t last_remove_bytes = 0;
     // queries the certificate rejected in the most recent search: counted on the device, copied to pinned host memory
     // behind the search (no synchronisation inside search); feeds the adaptive tuning and radad_knn_last_recheck
     int* host_count = nullptr;   // pinned [2][8]: rejected queries, sum of candidates, rejections by reason x 4, [6] the report's stamp, [7] its batch size
@@ -3397,6 +3401,10 @@ int radad_knn_set_option(radad_knn_t h, int option, int value) {
         case RADAD_KNN_OPT_RANGE_SMALLQ:
             RADAD_REQUIRE(value == 0 || value == 1, "radad_knn_set_option: RANGE_SMALLQ takes 0 or 1");
             h->opt_range_smallq = value;
+            return RADAD_OK;
+        case RADAD_KNN_OPT_REMOVE_STAGE_ROWS:
+            RADAD_REQUIRE(value >= 0, "radad_knn_set_option: REMOVE_STAGE_ROWS takes a row count, or 0 for the default");
+            h->opt_remove_stage_rows = value == 0 ? 0 : (int)std::max<int64_t>(value, KNN_REMOVE_MIN_STAGE_ROWS);
             return RADAD_OK;
         default:
             radad_set_error("radad_knn_set_option: unknown option %d", option);
@@ -5454,4 +5462,5 @@ int radad_rownorm(const float* in_dev, float* out_dev, int64_t n, int dim, int d
 
 }  // extern "C"
 
+#include "knn_remove.inc"
 #include "ivf.inc"

@@ -951,9 +951,141 @@ struct KnnTuning {
     void plane_wanted() { replan = false; }          // whatever asked for a new decision is being served now
     void plane_is_new() { verify_next = true; }
     void plane_decided(float max_abs, float max_residual, int64_t ntotal) { plane_stat[0] = max_abs; plane_stat[1] = max_residual; plane_decided_rows = ntotal; }
+    // rows were removed (radad_knn_remove_ids) and the store now holds `ntotal_after`.  The comparisons above assume a store that only
+    // grows: without this step a store cut from 1000 rows to 600 and refilled to 700 would not count as appended to.  The plane's
+    // decision now stands for at most the rows that are left: rows appended from here on are noticed, and the plane re-decided at twice
+    // that count, exactly as after a decision taken at `ntotal_after` rows.  A removal that leaves more rows than the plane was decided
+    // at (rows appended since, not yet seen by a search) changes nothing.
+    void rows_removed(int64_t ntotal_after) { plane_decided_rows = std::min(plane_decided_rows, std::max<int64_t>(ntotal_after, 0)); }
     // what the plane's operands measure after an append.  true: rows beyond what the scale was chosen for -- decide again, now
     bool plane_outgrown(float max_abs, float max_residual) {
         if ((plane_stat[0] > 0.f && max_abs > 8.f * plane_stat[0]) || (plane_stat[1] > 0.f && max_residual > 8.f * plane_stat[1])) { replan = true; return true; }
         return false;
     }
 };
+
+// ---- removing rows in place (knn_remove.inc, radad_knn_remove_ids) -------------------------------------------------------------------
+// A removal marks the rows to drop (one byte each), takes the exclusive prefix sum of the marks (excl[i] = rows dropped in front of
+// row i: per-block counts, a scan of the counts, in-block offsets -- integers only) and then moves every kept row i to i - excl[i].
+// Destinations never exceed sources, but a launch whose workgroups read and write the same row range would still race, so the moves
+// are planned here such that NO ROW IS WRITTEN WHILE ANY WORKGROUP OF THE SAME LAUNCH MAY STILL READ IT; what orders two launches is
+// the stream.  The store is walked in ascending SLABS of S rows from the slab that holds the first removed row r0 (nothing in front
+// of r0 moves):
+//   - a slab with at least S removed rows in front of it is DIRECT: its kept rows land in [a - d, b - d') with d, d' >= S >= b - a,
+//     i.e. wholly below its own start a.  Consecutive direct slabs share one launch while the launch's span b - a stays <= the rows
+//     removed in front of a (the same argument with the launch for the slab);
+//   - any other slab is STAGED: one launch gathers its kept rows into a staging buffer of S rows (reads the store, writes staging),
+//     the next launch on the stream copies them to their destination (reads staging, writes the store).
+// Every launch reads only rows at or above its own start that no earlier step of the SAME launch writes, and everything below a
+// launch's start is final before it runs.  tests/knn_remove_plan_check.cpp executes plans on integer arrays and checks both.
+constexpr int64_t KNN_REMOVE_MIN_STAGE_ROWS = 64;               // RADAD_KNN_OPT_REMOVE_STAGE_ROWS is clamped to this minimum
+constexpr size_t KNN_REMOVE_STAGE_BYTES = (size_t)64 << 20;     // default staging buffer: 64 MiB of rows, whatever the store holds
+constexpr int KNN_REMOVE_SCAN_ROWS = 2048;                      // rows per workgroup of the count / offset kernels (256 threads x 8)
+enum { KNN_REMOVE_GATHER = 0, KNN_REMOVE_SCATTER = 1, KNN_REMOVE_DIRECT = 2 };
+
+// slab size in rows: the option when set (> 0), else what the default staging bytes hold; never below the minimum
+static int64_t knn_remove_stage_rows(size_t row_bytes, int64_t opt_stage_rows) {
+    const int64_t s = opt_stage_rows > 0 ? opt_stage_rows : (int64_t)(KNN_REMOVE_STAGE_BYTES / std::max<size_t>(row_bytes, 1));
+    return std::max<int64_t>(KNN_REMOVE_MIN_STAGE_ROWS, s);
+}
+
+// byte offsets in the handle's workspace: flags [ntotal] bytes | block counts [n_blocks + 1] int | excl [ntotal] int |
+// slab counts [max_slabs + 1] int | head: first removed row, removed count (2 x int64) | staged rows [S] | staged norms [S] (L2)
+struct RemoveLayout {
+    size_t flags = 0, blk = 0, excl = 0, slab_rb = 0, head = 0, stage = 0, stage_norm = 0, bytes = 0;
+    int64_t n_blocks = 0, max_slabs = 0;
+};
+static RemoveLayout knn_remove_layout(int64_t ntotal, size_t row_bytes, int64_t stage_rows, bool l2) {
+    RemoveLayout L;
+    L.n_blocks = ceil_div64(std::max<int64_t>(ntotal, 1), KNN_REMOVE_SCAN_ROWS);
+    L.max_slabs = ceil_div64(std::max<int64_t>(ntotal, 1), stage_rows);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += al256(bytes); return o; };
+    // (the count kernel reads the flags eight at a time: the array is padded to whole blocks)
+    L.flags = take((size_t)L.n_blocks * KNN_REMOVE_SCAN_ROWS);
+    L.blk = take((size_t)(L.n_blocks + 1) * sizeof(int));
+    L.excl = take((size_t)std::max<int64_t>(ntotal, 1) * sizeof(int));
+    L.slab_rb = take((size_t)(L.max_slabs + 1) * sizeof(int));
+    L.head = take(2 * sizeof(int64_t));
+    L.stage = take((size_t)stage_rows * row_bytes);
+    L.stage_norm = take(l2 ? (size_t)stage_rows * sizeof(float) : 0);
+    L.bytes = off;
+    return L;
+}
+
+struct RemoveSlab {
+    int64_t row0 = 0, rows = 0;
+    int64_t removed_before = 0;      // rows removed in front of row0
+    int64_t kept = 0;                // rows of the slab that stay
+    bool direct = false;
+};
+// one kernel launch: rows [row0, row0 + rows) of the store (GATHER, DIRECT) or `rows` staged rows (SCATTER); dst0 = where the first
+// kept row of the range lands (row0 minus the rows removed in front of it)
+struct RemoveLaunch {
+    int kind = KNN_REMOVE_DIRECT;
+    int64_t row0 = 0, rows = 0, dst0 = 0;
+};
+struct RemovePlan {
+    int64_t stage_rows = 0;          // S
+    int64_t slab0 = 0;               // first row of the first slab: r0 / S * S
+    std::vector<RemoveSlab> slabs;
+    std::vector<RemoveLaunch> launches;
+    int64_t rows_moved = 0;          // kept rows that change position
+    size_t bytes_moved = 0;          // bytes read + written by the launches (a staged row is read and written twice)
+    RemoveLayout layout;
+};
+// the slabs of a removal whose first removed row is r0: [slab0, ntotal) in steps of S
+static int64_t knn_remove_slab0(int64_t first_removed_row, int64_t stage_rows) { return first_removed_row / stage_rows * stage_rows; }
+static int64_t knn_remove_n_slabs(int64_t ntotal, int64_t first_removed_row, int64_t stage_rows) {
+    if (first_removed_row < 0 || first_removed_row >= ntotal) return 0;
+    return ceil_div64(ntotal - knn_remove_slab0(first_removed_row, stage_rows), stage_rows);
+}
+// removed_before: [n_slabs + 1] rows removed in front of every slab's first row, then the removed count of the whole store (what the
+// device's prefix sum says at those rows).  opt_stage_rows: RADAD_KNN_OPT_REMOVE_STAGE_ROWS, 0 = default.
+static RemovePlan knn_remove_plan(int64_t ntotal, size_t row_bytes, int64_t first_removed_row, int64_t opt_stage_rows, bool l2,
+                                  const int* removed_before) {
+    RemovePlan p;
+    const int64_t S = p.stage_rows = knn_remove_stage_rows(row_bytes, opt_stage_rows);
+    p.layout = knn_remove_layout(ntotal, row_bytes, S, l2);
+    const int64_t n_slabs = knn_remove_n_slabs(ntotal, first_removed_row, S);
+    p.slab0 = n_slabs ? knn_remove_slab0(first_removed_row, S) : ntotal;
+    const size_t moved_row = row_bytes + (l2 ? sizeof(float) : 0);
+    for (int64_t j = 0; j < n_slabs; ++j) {
+        RemoveSlab s;
+        s.row0 = p.slab0 + j * S;
+        s.rows = std::min<int64_t>(S, ntotal - s.row0);
+        s.removed_before = removed_before[j];
+        s.kept = s.rows - (removed_before[j + 1] - removed_before[j]);
+        s.direct = s.removed_before >= S;
+        p.slabs.push_back(s);
+    }
+    for (size_t j = 0; j < p.slabs.size(); ++j) {
+        const RemoveSlab& s = p.slabs[j];
+        if (s.direct) {
+            // this slab and the direct ones behind it, while the launch's span stays within the rows removed in front of it
+            RemoveLaunch l;
+            l.kind = KNN_REMOVE_DIRECT; l.row0 = s.row0; l.rows = s.rows; l.dst0 = s.row0 - s.removed_before;
+            int64_t kept = s.kept;
+            while (j + 1 < p.slabs.size() && l.rows + p.slabs[j + 1].rows <= s.removed_before) {
+                ++j;
+                l.rows += p.slabs[j].rows; kept += p.slabs[j].kept;
+            }
+            if (kept > 0) { p.launches.push_back(l); p.rows_moved += kept; p.bytes_moved += 2 * (size_t)kept * moved_row; }
+            continue;
+        }
+        // staged.  The first slab's rows in front of r0 stay where they are: its range starts at r0 (nothing is removed in front of it)
+        RemoveLaunch g;
+        g.kind = KNN_REMOVE_GATHER;
+        g.row0 = j == 0 ? first_removed_row : s.row0;
+        g.rows = s.row0 + s.rows - g.row0;
+        g.dst0 = g.row0 - s.removed_before;
+        const int64_t kept = s.kept - (g.row0 - s.row0);
+        if (kept <= 0) continue;
+        RemoveLaunch c;
+        c.kind = KNN_REMOVE_SCATTER; c.row0 = 0; c.rows = kept; c.dst0 = g.dst0;
+        p.launches.push_back(g);
+        p.launches.push_back(c);
+        p.rows_moved += kept; p.bytes_moved += 4 * (size_t)kept * moved_row;
+    }
+    return p;
+}

@@ -79,6 +79,13 @@ class HotPathPipeline:
             self.vector_db.save()                                             # pipeline.py:446
         return n
 
+    def remove_files(self, paths) -> int:
+        """Act on an audit (near_duplicates, validate_no_leakage): take every stored row of these files out of the store, in place
+        (VectorDatabase.remove_files: matched by basename), and their basenames out of training_file_ids.  -> rows removed."""
+        removed = self.vector_db.remove_files(paths)                # (raises before anything changes on a store that cannot remove)
+        self.training_file_ids.difference_update(os.path.basename(p) for p in ([paths] if isinstance(paths, str) else paths))
+        return removed
+
     @staticmethod
     def _extract_batch_speakers(metas, batch_size):
         """the speaker_id column the reference keeps beside each vector (pipeline.py:433-443)"""

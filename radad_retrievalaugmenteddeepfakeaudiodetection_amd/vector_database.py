@@ -74,7 +74,7 @@ def write_faiss_flat(path: str, rows: np.ndarray, metric: str):
 
 def knn_options_from_config(config):
     """the optional scan knobs, read the way the reference reads its own optional ones (getattr with a default,
-    vector_database.py:43,67,80): knn_hi_plane, knn_centre, knn_smallq_hi, knn_wide_min_q, knn_dense, knn_abandon, knn_abandon_defer, knn_abandon_ahead, knn_range_smallq; absent / None = the library's default.
+    vector_database.py:43,67,80): knn_hi_plane, knn_centre, knn_smallq_hi, knn_wide_min_q, knn_dense, knn_abandon, knn_abandon_defer, knn_abandon_ahead, knn_range_smallq, knn_remove_stage_rows; absent / None = the library's default.
     knn_live_floor is still recognised, but only None / 0 (the default): the one-launch scan form it selected was removed"""
     if getattr(config, "knn_live_floor", None) not in (None, 0):
         raise ValueError("knn_live_floor: the one-launch scan form was measured slower and removed (DESIGN §4.1); "
@@ -83,7 +83,8 @@ def knn_options_from_config(config):
                 smallq_hi=getattr(config, "knn_smallq_hi", None), wide_min_q=getattr(config, "knn_wide_min_q", None),
                 dense=getattr(config, "knn_dense", None), abandon=getattr(config, "knn_abandon", None),
                 range_smallq=getattr(config, "knn_range_smallq", None), abandon_defer=getattr(config, "knn_abandon_defer", None),
-                abandon_ahead=getattr(config, "knn_abandon_ahead", None))
+                abandon_ahead=getattr(config, "knn_abandon_ahead", None),
+                remove_stage_rows=getattr(config, "knn_remove_stage_rows", None))
     return {k: v for k, v in opts.items() if v is not None}
 
 
@@ -167,10 +168,12 @@ class HipFlatIndex:
     is_trained = True   # flat indexes need no training (vector_database.py:124)
 
     def __init__(self, d: int, metric: int, device: int = 0, id_base: int = 0, store_f16: bool = False, hi_plane=None, centre=None,
-                 smallq_hi=None, wide_min_q=None, dense=None, abandon=None, range_smallq=None, abandon_defer=None, abandon_ahead=None):
+                 smallq_hi=None, wide_min_q=None, dense=None, abandon=None, range_smallq=None, abandon_defer=None, abandon_ahead=None,
+                 remove_stage_rows=None):
         """hi_plane / centre / smallq_hi / wide_min_q / dense / abandon / range_smallq / abandon_defer / abandon_ahead: kernel choices of the handle (radad_knn_set_option;
         None = the library's default).  They change speed, never results: A/B measurements and the parity tests select kernels through
-        them.  range_smallq (default off): range searches of <= 16 queries stream the f16 plane instead of the float64 exact kernel."""
+        them.  range_smallq (default off): range searches of <= 16 queries stream the f16 plane instead of the float64 exact kernel.
+        remove_stage_rows: slab size of remove_ids in rows (None = 64 MiB of rows; at least 64)."""
         self._lib = _lib.load()
         self.d = int(d)
         self.metric = int(metric)
@@ -182,11 +185,12 @@ class HipFlatIndex:
                                                  self.device, self.id_base, C.byref(h)), "radad_knn_create")
         self._h = h
         self.options = dict(hi_plane=hi_plane, centre=centre, smallq_hi=smallq_hi, wide_min_q=wide_min_q, dense=dense, abandon=abandon,
-                            range_smallq=range_smallq, abandon_defer=abandon_defer, abandon_ahead=abandon_ahead)
+                            range_smallq=range_smallq, abandon_defer=abandon_defer, abandon_ahead=abandon_ahead,
+                            remove_stage_rows=remove_stage_rows)
         for opt, val in ((_lib.KNN_OPT_HI_PLANE, hi_plane), (_lib.KNN_OPT_CENTRE, centre), (_lib.KNN_OPT_SMALLQ_HI, smallq_hi),
                          (_lib.KNN_OPT_WIDE_MIN_Q, wide_min_q), (_lib.KNN_OPT_DENSE, dense), (_lib.KNN_OPT_ABANDON, abandon),
                          (_lib.KNN_OPT_RANGE_SMALLQ, range_smallq), (_lib.KNN_OPT_ABANDON_DEFER, abandon_defer),
-                         (_lib.KNN_OPT_ABANDON_AHEAD, abandon_ahead)):
+                         (_lib.KNN_OPT_ABANDON_AHEAD, abandon_ahead), (_lib.KNN_OPT_REMOVE_STAGE_ROWS, remove_stage_rows)):
             if val is not None:
                 _lib.check(self._lib.radad_knn_set_option(self._h, opt, int(val)), "radad_knn_set_option")
 
@@ -239,6 +243,32 @@ class HipFlatIndex:
             raise ValueError(f"add expects [n, {self.d}], got {tuple(x.shape)}")
         with torch.cuda.device(x.device):
             _lib.check(self._lib.radad_knn_add(self._h, x.data_ptr(), x.shape[0], _lib.stream_ptr(x.device)), "radad_knn_add")
+
+    def remove_ids(self, ids, return_map: bool = False):
+        """Remove the rows with these GLOBAL ids (id_base + position) in place, on the device, as faiss IndexFlat.remove_ids does: the
+        kept rows keep their bits and their order and hold positions 0 ... ntotal - 1 afterwards (radad_knn_remove_ids).  ids: a list, a
+        numpy array or a CPU / CUDA int64 tensor, in any order; repeats and ids that name no stored row are ignored.  -> the number of
+        distinct rows removed; with return_map also an int64 CUDA tensor [ntotal before]: the new global id of every old position, -1
+        for a removed one (to compact per-row columns of the caller's own).  On a row shard (id_base != 0) only ids of the shard's own
+        range count, and ids shift inside the shard only.  Synchronises; a ValueError while a search_begin awaits its finish."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(ids, torch.Tensor):
+            t = ids.detach().reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))).to(dev)
+        omap = torch.empty((self.ntotal,), device=dev, dtype=torch.int64) if return_map else None
+        removed = C.c_int64(0)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.radad_knn_remove_ids(self._h, t.data_ptr() if t.numel() else None, int(t.numel()), _ptr(omap),
+                                                      C.byref(removed), _lib.stream_ptr(dev)), "radad_knn_remove_ids")
+        return (int(removed.value), omap) if return_map else int(removed.value)
+
+    def last_remove(self):
+        """{"launches", "bytes_moved"} of the last remove_ids: the move launches of its plan and the bytes they read + wrote"""
+        n, b = C.c_int(), C.c_int64()
+        _lib.check(self._lib.radad_knn_last_remove(self._h, C.byref(n), C.byref(b)))
+        return {"launches": n.value, "bytes_moved": b.value}
 
     def search_device(self, q, k: int, return_f64: bool = False):
         """q [nq, d] CUDA tensor (float32, or bfloat16 = BASELINE config 5's bf16 embeddings, handed to the library as
@@ -843,7 +873,11 @@ class HipIVFFlatIndex:
 
     add_device = add
 
-    MAX_K = 128     # csrc/ivf.inc: up to k = 26 the probed lists are scanned (k + 6 candidates per (query, list) in 32-entry register
+    def remove_ids(self, ids, return_map: bool = False):
+        raise ValueError("HipIVFFlatIndex.remove_ids: an IVF store keeps list-major copies of its rows, which cannot be compacted in "
+                         "place; rebuild the index from the rows that stay (or keep the store flat: HipFlatIndex.remove_ids)")
+
+    MAX_K = 128    # csrc/ivf.inc: up to k = 26 the probed lists are scanned (k + 6 candidates per (query, list) in 32-entry register
                     # lists); 27..128 is answered by the exact certified scan of the same rows (recall 1.0, the flat scan's cost)
 
     def search_device(self, q, k: int):
@@ -1094,6 +1128,47 @@ class VectorDatabase:
     def add_vectors(self, vectors, paths: List[str], labels: List[int], metadata: Dict):
         self.add_vectors_batch(vectors, paths, labels, metadata, getattr(self.config, "vector_add_batch_size", 10000))
 
+    # ---- acting on an audit: forget rows (faiss remove_ids; the reference's VectorDatabase never got one) ------------------------
+    def remove_vectors(self, ids) -> int:
+        """Remove the rows with these ids (as search_batch returns them) from a flat store, in place on the device, and cut
+        vector_paths, vector_labels and every vector_metadata column to the rows that stay: row i stays aligned with vector_paths[i].
+        ids: list / numpy / int64 tensor, any order; repeats and ids that name no row are ignored.  -> rows removed.  An IVF store
+        raises ValueError and is left as it was.  On a row shard (load(shard=...)) only ids of the shard's own range count and ids
+        shift inside the shard only: the global id space then has a gap in front of the next shard."""
+        if self.index is None:
+            raise ValueError("Vector database is empty. Build the database first.")
+        n_before = self.index.ntotal
+        removed, omap = self.index.remove_ids(ids, return_map=True)       # (HipIVFFlatIndex raises before anything changes)
+        if removed == 0:
+            return 0
+        keep = np.flatnonzero(omap.cpu().numpy() >= 0)
+        assert len(keep) == n_before - removed == self.index.ntotal
+        self.vector_paths = [self.vector_paths[i] for i in keep]
+        self.vector_labels = [self.vector_labels[i] for i in keep]
+        if isinstance(self.vector_metadata, dict):
+            self.vector_metadata = {key: ([vals[i] for i in keep] if hasattr(vals, "__getitem__") and len(vals) == n_before else vals)
+                                    for key, vals in self.vector_metadata.items()}
+        # The device columns are dropped, not patched: row_tags_device() / labels_device() take an equal LENGTH as proof that their
+        # cache is current, and a removal followed by an add of as many rows has that length with other rows behind it.  The host
+        # tags are cut like the paths (or dropped when they were not current: row_tags_device() then takes them from the paths).
+        # _tag_names (tag -> basename, the collision check) is LEFT as it is: a basename that is gone keeps its tag reserved, which
+        # can only make the check stricter, and the same file added again finds its own entry.
+        self._tags_host = [self._tags_host[i] for i in keep] if len(self._tags_host) == n_before else []
+        self._tags_dev = self._labels_dev = None
+        return removed
+
+    def remove_files(self, paths) -> int:
+        """Remove every stored row whose BASENAME equals that of one of `paths` (the match the exclusion makes, pipeline.py:495-502;
+        two rows that share a basename both go).  -> rows removed."""
+        if self.index is None:
+            raise ValueError("Vector database is empty. Build the database first.")
+        names = {os.path.basename(p_) for p_ in ([paths] if isinstance(paths, str) else paths)}
+        base = getattr(self.index, "id_base", 0)
+        ids = [base + i for i, p_ in enumerate(self.vector_paths) if os.path.basename(p_) in names]
+        if not ids and not isinstance(self.index, HipFlatIndex):
+            self.index.remove_ids(ids)           # an IVF store refuses whether or not a name matched
+        return self.remove_vectors(ids) if ids else 0
+
     # vector_database.py:159-182
     def search_batch(self, query_vectors, k: int = None):
         """numpy in -> (float32 [B,k], int64 [B,k]) numpy out, as the reference; a CUDA tensor in -> CUDA tensors out."""
@@ -1321,7 +1396,8 @@ class VectorDatabase:
 
     # ---- device-side columns for retrieve_similar_vectors ------------------------------------------------------
     def row_tags_device(self):
-        """int64 [ntotal] CUDA tensor: path_tag(vector_paths[i])"""
+        """int64 [ntotal] CUDA tensor: path_tag(vector_paths[i]).  (The cache is trusted by its length: whatever changes rows without
+        changing their number -- remove_vectors followed by an add -- resets it.)"""
         import torch
         if self._tags_dev is None or self._tags_dev.numel() != len(self.vector_paths):
             if len(self._tags_host) != len(self.vector_paths):          # e.g. after load()
