@@ -595,7 +595,8 @@ int radad_knn_search_excl_scan_pq(radad_knn_t h, const void* q_dev, int q_dtype,
  * stream takes 2 - 5 % of it.  The plain k = 10 search of the same handle (k_knn_hi_smallq<16>): 0.23 / 0.28 / 0.33 ms.  The default
  * of RADAD_KNN_OPT_RANGE_SMALLQ is still 0: switching it is a change of its own.
  * Not offered: a begin / finish pair and sharded range search (a shard's answer is exact: concatenating the shards' lists is the
- * merge); the IVF index; results beyond RADAD_KNN_MAX_K per query (the count is exact: the caller can narrow the radius).
+ * merge); results beyond RADAD_KNN_MAX_K per query (the count is exact: the caller can narrow the radius).  The IVF index has its
+ * own call, radad_ivf_range_search below; still not offered on IVF: exclusion sets combined with a radius, and M > 128.
  * Exclusion sets combined with a radius: the two calls below. */
 #define RADAD_RANGE_TILE 0
 #define RADAD_RANGE_EXACT 1
@@ -775,6 +776,55 @@ int radad_ivf_last_search_counts(radad_ivf_t h, int* rejected_out, int* exact_ou
  * skipped and every row counts as suspect, so the per-(row, query) test decides every row.  Same results, bit for bit. */
 #define RADAD_IVF_OPT_PQ_FILTER 1
 int radad_ivf_set_option(radad_ivf_t h, int option, int value);
+
+/* Certified range search over the probed lists: every row of the nprobe lists nearest to each query that lies within a radius,
+ * exactly -- faiss's range_search on an IndexIVFFlat (the reference's third index type, vector_database.py:65-70, searched at
+ * nprobe, :174-181), which the near-duplicate audit of a store (validate_no_leakage, pipeline.py:1105-1110) needs on the index a
+ * user picks because the store is too large to scan whole.  The answer is the exact range search restricted to the union of the
+ * probed lists, as radad_ivf_search is the exact top-k restricted to them; with nprobe == nlist it equals radad_knn_range_search on
+ * the same rows.  L2 only (an IVF index has no other metric).
+ * Every output rule of radad_knn_range_search holds: the key is the float64 sum (q - y)^2 over the stored fp32 values; a row is a
+ * member iff key < (double)radius, strictly (a NaN key never passes; radius +inf = every row of the probed lists); out_count[j] is
+ * the EXACT number of members, also beyond M = max_per_query; slots 0 .. min(count, M) - 1 hold the best members ordered by (key,
+ * lower insertion id) -- insertion ids, not list positions, also in the tie-break --, out_dist the key rounded once to float32; all
+ * other slots hold -1 / NaN / NaN.  M lies in [1, 128].
+ * Routes, chosen on the host (ivf_plan_range, ivf_plan.h), reported by radad_ivf_last_range:
+ *   RADAD_IVF_RANGE_HI     exactly when radad_ivf_search would take the certified f16 list scan (RADAD_IVF_SCAN_HI).  That route's query
+ *                 preparation and eps(q); k_range_floor writes thr[q] = -radius - eps(q), two ulps lower; k_ivf_range_hi has the task,
+ *                 split and chunk structure of the top-k list scan without its selection, carry and running bound (and so without
+ *                 its score tile in LDS): a (row, query) pair whose f16 score reaches thr[q] takes a slot of the query's buffer of
+ *                 4096 positions with one returning atomic.  k_ivf_range_refine, one workgroup per query, re-scores every emitted
+ *                 position in float64 from the list-major rows (the plain re-score of the flat range search's tile route: its keys
+ *                 may differ from the exact route's in the last place or two, never in what the tests can tell), maps positions to
+ *                 insertion ids, applies the strict test, counts, sorts the members by (key, id) in LDS and writes the best M.  A
+ *                 query that emitted more than 4096 positions goes, driven from the device, to the exact pass.
+ *   RADAD_IVF_RANGE_EXACT  every other shape (no plane: dim % 64 != 0, RADAD_IVF_OPT_HI_SCAN 0): k_ivf_range_exact for every query -- the
+ *                 float64 key of every row of the probed lists, the strict test before the list insertion, one count per wave and
+ *                 (query, list) pair added to out_count, top-M lists per pair merged by the pair that arrives last.
+ * RADAD_IVF_OPT_HI_SCAN 2 (tests) sends every query to the exact pass behind the hi route.
+ * Errors, before anything is enqueued (outputs untouched, the handle usable): RADAD_EINVAL for M outside [1, 128], a NaN radius,
+ * nprobe < 1, NULL out_count / out_dist / out_idx or a plan the index refuses; RADAD_ESTATE for an untrained index.  nq == 0 returns
+ * RADAD_OK; a trained index without rows answers count 0 and padding.  Stream-ordered and serialised like every IVF search.
+ * radad_ivf_last_range synchronises with the most recent radad_ivf_range_search: its batch size, route, the number of queries the
+ * exact pass answered (all of them on the exact route) and the largest number of positions one query emitted (0 on the exact
+ * route); any of the four may be NULL.  RADAD_ESTATE when the most recent search of the handle was not a range search; in the
+ * opposite case radad_ivf_last_search_info / _counts return RADAD_ESTATE (they describe a top-k search).
+ * Measured (tools/bench_ivf_range.py, profiles/ivf_range.md; 1 M x 512 noise rows, nlist 4096, nprobe 32, M = 128, one run on one
+ * MI355X, the three legs alternated on one store).  64 groups of near-identical queries: 0.09 / 0.68 / 1.52 ms for 1 / 256 / 1024
+ * queries with no member, 0.10 / 0.75 / 1.64 ms with 10 per query, 0.23 / 0.98 / 1.95 ms with 1000 (the re-score of 1000 emitted
+ * rows per query: 0.13 / 0.30 / 0.44 ms), against 0.14 / 1.07 / 1.90 ms for radad_ivf_search at k = 10 on the same handle and
+ * queries -- 0.64 - 0.89 of it up to 10 members, 1.5 / 0.90 / 1.0 of it at 1000.  Unstructured queries, no member: 0.09 / 0.78 /
+ * 1.63 ms against 0.15 / 1.13 / 1.93 ms.  No query left the hi route; max_emitted equalled the members.  The flat store's
+ * radad_knn_range_search of the same rows: 3.58 ms for one query (no certified route by default), 0.30 / 0.89 ms for 256 / 1024 --
+ * faster than both IVF calls on this store, whose list scans take four times what tools/bench_ivf.py records for its own.
+ * Not measured: that tool's store, the exact route at this scale, buffers that overflow.
+ * Not offered: exclusion sets combined with a radius, M > 128, sharded IVF. */
+#define RADAD_IVF_RANGE_HI 0
+#define RADAD_IVF_RANGE_EXACT 1
+int radad_ivf_range_search(radad_ivf_t h, const float* q_dev, int64_t nq, int nprobe, float radius, int max_per_query,
+                           int32_t* out_count_dev /*[nq]*/, float* out_dist_dev /*[nq,M]*/, int64_t* out_idx_dev /*[nq,M]*/,
+                           double* out_key_dev /*[nq,M] or NULL*/, void* stream);
+int radad_ivf_last_range(radad_ivf_t h, int64_t* n_queries, int* route, int* n_exact, int* max_emitted);
 int radad_ivf_reconstruct(radad_ivf_t h, const int64_t* idx_dev, int64_t n, float* out_dev, void* stream);
 
 /* out[r] = the k-th largest of the groups x per_group values of row r, value (g, i) at in[(g n + r) per_group + i] -- the layout

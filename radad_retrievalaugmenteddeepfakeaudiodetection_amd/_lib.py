@@ -32,6 +32,8 @@ KNN_REMOVE_MIN_STAGE_ROWS = 64                # KNN_REMOVE_MIN_STAGE_ROWS (knn_p
 IVF_OPT_HI_SCAN = 0
 IVF_OPT_PQ_FILTER = 1      # RADAD_IVF_OPT_PQ_FILTER
 IVF_SCAN_KINDS = ("f32_lists", "hi_lists", "exact_flat")
+IVF_RANGE_ROUTES = ("hi_lists", "exact_lists")    # RADAD_IVF_RANGE_HI, RADAD_IVF_RANGE_EXACT
+IVF_MAX_K = 128            # IVF_MAX_K (ivf_plan.h): the largest k of radad_ivf_search and max_per_query of radad_ivf_range_search
 EMBED_NO_SHARED_FRAMES, EMBED_LOGMEL_F32, EMBED_LOGMEL_DFT_GEMM = 1, 2, 4
 PLAN_KINDS = ("none", "host_offsets", "device_offsets", "segments")      # RADAD_PLAN_*
 PLAN_CHUNKS = ("none", "gemm_104", "fft_64")                             # RADAD_PLAN_CHUNKS_*
@@ -224,6 +226,9 @@ SIGNATURES = {
     "radad_ivf_last_search_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "radad_ivf_last_search_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "radad_ivf_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "radad_ivf_range_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "radad_ivf_last_range": (C.c_int, [C.c_void_p, c_i64p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "radad_ivf_reconstruct": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "radad_rownorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "radad_embed_create": (C.c_int, [C.POINTER(EmbedCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,

@@ -35,6 +35,7 @@
 // Exclusion-aware searches (radad_ivf_search_excl: one set for the batch; radad_ivf_search_excl_pq: one per query) run the same launches
 // with the ADM instantiations of the three list kernels behind a bitmap pre-pass: "exclusion inside the list scans", below.
 // What a search launches and allocates is decided by ivf_plan.h (host-only: tests/ivf_plan_check.cpp); ivf_search_lists is its glue.
+// Range search over the probed lists (radad_ivf_range_search): ivf_plan_range, the k_ivf_range_* kernels and ivf_range_lists, below.
 #include "ivf_plan.h"
 namespace {
 
@@ -896,6 +897,377 @@ __global__ __launch_bounds__(IVX_THREADS) void k_ivf_exact(IvfExactParams p) {
     }
 }
 
+// ---- range search over the probed lists (radad_ivf_range_search) -------------------------------------------------------------------
+// Every row of a query's probed lists whose float64 key sum (q - y)^2 is < radius, the best m listed, the count exact.  The f16 list
+// scan is a FILTER with a measured error bound eps(q) (k_hi_rows, as for the top-k search): with T = -radius and the floor
+// thr[q] = T - eps(q), two ulps lower (knn.hip's k_range_floor, as it is), exact score > T implies scan score >= thr, so every member is
+// emitted.  What the top-k scan derives from rows -- the k-th best of a chunk, the carry, the published bound -- does not exist here.
+//   k_ivf_range_hi      the task, split and step structure of k_ivf_scan_hi<IVF_ADM_NONE>; a (row, query) pair at or above the floor takes
+//                       a slot of the query's position buffer
+//   k_ivf_range_refine  one workgroup per query: float64 re-score of every emitted position, strict test, count, (key, insertion id)
+//                       sort in LDS, the best m; a buffer that overflowed proves nothing -- the query is listed for the exact pass
+//   k_ivf_range_exact   the listed queries (or all of them: IVF_RANGE_EXACT), float64 over their probed lists
+// Integer atomics only (slot counters, counts, arrival counters); every result is written with plain vector stores.
+static_assert(IVF_RANGE_CAP == RG_MAX_CAP, "the candidate buffers are what the re-rank's LDS sort is sized for");
+static_assert(IVF_RANGE_HI == RADAD_IVF_RANGE_HI && IVF_RANGE_EXACT == RADAD_IVF_RANGE_EXACT, "ivf_plan.h's routes are the header's");
+static_assert(ivf_range_refine_lds_bytes() == range_refine_lds_bytes(), "k_ivf_range_refine has k_range_refine's LDS layout");
+
+struct IvfRangeHiParams {
+    const _Float16* lhi = nullptr; // [N][dim] list-major f16 plane
+    const float* lscale = nullptr; // [N] per-row scale, or nullptr: uscale for every row
+    float uscale = 1.f;
+    const float* lbias = nullptr;  // [N]
+    const int* loff = nullptr;     // [nlist + 1]
+    const _Float16* qh = nullptr;  // [nq][dim]
+    const float* qscale = nullptr; // [nq]
+    const float* qconst = nullptr; // [nq]
+    const float* thr = nullptr;    // [nq] the floor: -radius - eps(q), two ulps lower
+    const int* task_list = nullptr; const int* task_pbeg = nullptr; const int* task_cnt = nullptr; const int* n_tasks_dev = nullptr; const int* pair_q = nullptr;
+    int dim = 0, qcap = 0, split = 1;
+    int* cand_cnt = nullptr;       // [nq] positions emitted, 0 at launch; it keeps counting past cand_cap (overflow)
+    int cand_cap = 0;
+    int* cand_idx = nullptr;       // [nq][cand_cap] positions in the list-major order
+};
+static_assert(std::is_trivially_copyable_v<IvfRangeHiParams>, "kernel argument");
+
+// k_ivf_scan_hi<IVF_ADM_NONE> without its second half.  That kernel parks the scores of a 256-row chunk in LDS because a wave per
+// query then SELECTS among them; with a floor fixed before the launch the lane that holds the score of (row 4 g + e, query r16) in
+// its accumulator decides alone.  So there is no score tile (LDS = the task's f16 queries: 16.6 KB at dim 512 instead of 37 KB), no
+// barrier inside the row loop, and the 16-row steps are dealt to the four waves as before (step i of the share to wave i % 4).
+// A NaN score is never emitted (`sc >= thr` is false).  Rows past l_end and the query rows past the task's count emit nothing.
+__global__ __launch_bounds__(SQ_THREADS, 4) void k_ivf_range_hi(IvfRangeHiParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem_rh[];
+    const int qld = p.dim + 8;
+    _Float16* sQ = reinterpret_cast<_Float16*>(smem_rh);                       // [qcap][dim + 8]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r16 = lane & 15, g = lane >> 4;
+    const int task = blockIdx.x / p.split, sub = blockIdx.x % p.split;
+    if (task >= *p.n_tasks_dev) return;                                        // (uniform per workgroup)
+    const int list = p.task_list[task];
+    int64_t l_begin = p.loff[list], l_end = p.loff[list + 1];
+    if (p.split > 1) {                                                         // this workgroup's share of the list: whole 16-row steps
+        const int64_t len = ((l_end - l_begin + p.split - 1) / p.split + 15) / 16 * 16;
+        l_begin += sub * len;
+        l_end = min(l_end, l_begin + len);
+        if (l_begin >= l_end) return;
+    }
+    const int pbeg = p.task_pbeg[task], cnt = p.task_cnt[task];
+    for (int i = tid; i < p.qcap * (p.dim >> 3); i += SQ_THREADS) {
+        const int qq = i / (p.dim >> 3), c8 = i % (p.dim >> 3);
+        f16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (qq < cnt) v = *reinterpret_cast<const f16x8*>(p.qh + (int64_t)p.pair_q[pbeg + qq] * p.dim + c8 * 8);
+        *reinterpret_cast<f16x8*>(sQ + qq * qld + c8 * 8) = v;
+    }
+    const bool q_on = r16 < cnt;
+    const int pq = q_on ? p.pair_q[pbeg + r16] : 0;
+    const float qs = q_on ? p.qscale[pq] * 2.f : 0.f;
+    const float qc = q_on ? p.qconst[pq] : 0.f;
+    const float thr = q_on ? p.thr[pq] : 0.f;
+    int* my_cnt = p.cand_cnt + pq;
+    int* my_idx = p.cand_idx + (int64_t)pq * p.cand_cap;
+    __syncthreads();
+
+    const _Float16* qrow = sQ + min(r16, p.qcap - 1) * qld + 8 * g;
+    const int nkb = p.dim >> 5;
+    for (int64_t row0 = l_begin + 16 * wave; row0 < l_end; row0 += 4 * 16) {     // (wave-uniform)
+        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+        const int64_t ra = min(row0 + r16, l_end - 1);
+        const _Float16* pa = p.lhi + ra * p.dim + 8 * g;
+        float rs[4], yb[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int64_t row = min(row0 + 4 * g + e, l_end - 1);
+            rs[e] = p.lscale ? p.lscale[row] : p.uscale;
+            yb[e] = qc - p.lbias[row];
+        }
+        constexpr int HKB = 16;
+        for (int kp = 0; kp < nkb; kp += HKB) {
+            const int nb = min(HKB, nkb - kp);
+            f16x8 v[HKB];
+#pragma unroll
+            for (int kb = 0; kb < HKB; ++kb)
+                if (kb < nb) v[kb] = *reinterpret_cast<const f16x8*>(pa + (kp + kb) * 32);
+#pragma unroll
+            for (int kb = 0; kb < HKB; ++kb)
+                if (kb < nb) {
+                    const f16x8 b = *reinterpret_cast<const f16x8*>(qrow + (kp + kb) * 32);
+                    if (kb & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(v[kb], b, acc1, 0, 0, 0);
+                    else acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(v[kb], b, acc0, 0, 0, 0);
+                }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int64_t row = row0 + 4 * g + e;
+            const float sc = fmaf((acc0[e] + acc1[e]) * rs[e], qs, yb[e]);      // the top-k scan's score, operation for operation
+            if (q_on && row < l_end && sc >= thr) {
+                const int slot = atomicAdd(my_cnt, 1);
+                if (slot < p.cand_cap) my_idx[slot] = (int)row;
+            }
+        }
+    }
+}
+
+struct IvfRangeRefineParams {
+    const int* idx = nullptr;           // [nq][cap] positions the scan emitted
+    const int* cnt = nullptr;           // [nq] positions emitted (> cap: overflow)
+    int cap = 0, dim = 0, m = 0;
+    const float* lrows = nullptr;       // [N, dim] list-major
+    const int64_t* lids = nullptr;      // [N] insertion id of every position
+    int64_t n_pos = 0;                  // N
+    const float* q = nullptr;           // [nq, dim]
+    double radius = 0.0;
+    int* flag_count = nullptr;          // [8]: [0] queries left to the exact pass, [2] the largest cnt of the call
+    int* flag_sel = nullptr;            // the queries left to the exact pass
+    int* out_count = nullptr;           // [nq]
+    float* out_dist = nullptr;          // [nq, m]
+    int64_t* out_idx = nullptr;         // [nq, m]
+    double* out_key = nullptr;          // optional [nq, m]
+};
+static_assert(std::is_trivially_copyable_v<IvfRangeRefineParams>, "kernel argument");
+
+// k_range_refine's plain form (knn.hip) over list-major positions: the same compaction, the same float64 re-score (refine_rescore_f64's
+// plain form, not its exact-order one: a key may differ from k_ivf_range_exact's in its last place or two, as between the flat range
+// search's tile and exact routes), the same strict test and bitonic sort.  What differs: a row is read at its POSITION in lrows, and
+// once it has its key the position is replaced by the row's insertion id (an index holds fewer than 2^31 rows: positions are ints,
+// and so are the ids), which is what ties are broken by and what is written.
+__global__ __launch_bounds__(RF_THREADS) void k_ivf_range_refine(IvfRangeRefineParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem_rr[];
+    double* c_key = reinterpret_cast<double*>(smem_rr);                  // [RG_MAX_CAP]
+    int* c_id = reinterpret_cast<int*>(c_key + RG_MAX_CAP);              // [RG_MAX_CAP]
+    int* w_cnt = c_id + RG_MAX_CAP;                                      // [4]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t q = blockIdx.x;
+    const int filled = p.cnt[q];
+    if (tid == 0) atomicMax(&p.flag_count[2], filled);
+    if (filled > p.cap) {                                                // (workgroup-uniform)
+        if (tid == 0) { p.flag_sel[atomicAdd(p.flag_count, 1)] = (int)q; p.out_count[q] = 0; }
+        return;
+    }
+    // the emitted positions (every slot below cnt was written; one outside the layout is left out all the same)
+    const int NE = max(filled, 0);
+    const int* ebuf = p.idx + q * p.cap;
+    auto taken = [&](int id) -> bool { return id >= 0 && id < p.n_pos; };
+    int mine = 0;
+    for (int i = tid; i < NE; i += RF_THREADS) mine += taken(ebuf[i]) ? 1 : 0;
+    int incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) w_cnt[wave] = incl;
+    __syncthreads();
+    int slot = incl - mine, nsel = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { if (w < wave) slot += w_cnt[w]; nsel += w_cnt[w]; }
+    for (int i = tid; i < NE; i += RF_THREADS) { const int id = ebuf[i]; if (taken(id)) c_id[slot++] = id; }
+    __syncthreads();
+    refine_rescore_f64<false>(p.lrows, 0, p.q + q * p.dim, p.dim, 1, c_id, c_key, nsel);
+    __syncthreads();
+    // membership, "larger is better" keys for the ranking, insertion ids for the tie-break and the output
+    int P = 1;
+    while (P < nsel) P <<= 1;                                            // <= RG_MAX_CAP: nsel <= cap == RG_MAX_CAP
+    int n_pass = 0;
+    for (int i0 = 0; i0 < P; i0 += RF_THREADS) {
+        const int i = i0 + tid;
+        bool pass = false;
+        if (i < nsel) {
+            const double key = c_key[i];
+            pass = key < p.radius;
+            c_key[i] = pass ? -key : -(double)INFINITY;
+            c_id[i] = pass ? (int)p.lids[c_id[i]] : IDX_SENTINEL;
+        } else if (i < P) {
+            c_key[i] = -(double)INFINITY;
+            c_id[i] = IDX_SENTINEL;
+        }
+        n_pass += __syncthreads_count(pass);
+    }
+    for (int k2 = 2; k2 <= P; k2 <<= 1)
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < P; i += RF_THREADS) {
+                const int o = i ^ j;
+                if (o > i) {
+                    const double ka = c_key[i], kb = c_key[o];
+                    const int ia = c_id[i], ib = c_id[o];
+                    const bool b_first = kb > ka || (kb == ka && ib < ia);
+                    const bool a_first = ka > kb || (ka == kb && ia < ib);
+                    if ((i & k2) == 0 ? b_first : a_first) { c_key[i] = kb; c_id[i] = ib; c_key[o] = ka; c_id[o] = ia; }
+                }
+            }
+            __syncthreads();
+        }
+    if (tid == 0) p.out_count[q] = n_pass;
+    const int n_out = min(n_pass, p.m);
+    const float nan_f = __int_as_float(0x7fc00000);
+    for (int o = tid; o < p.m; o += RF_THREADS) {
+        const bool have = o < n_out;
+        const double kd = have ? -c_key[o] : (double)nan_f;
+        p.out_dist[q * p.m + o] = have ? (float)kd : nan_f;
+        p.out_idx[q * p.m + o] = have ? (int64_t)c_id[o] : -1;
+        if (p.out_key) p.out_key[q * p.m + o] = kd;
+    }
+}
+
+struct IvfRangeExactParams {
+    const float* lrows = nullptr;      // [N, dim] list-major
+    const int64_t* lids = nullptr;     // [N] insertion id of every position
+    const int* loff = nullptr;         // [nlist + 1]
+    const float* q = nullptr;          // [nq, dim]
+    const int64_t* probes = nullptr;   // [nq, nprobe] lists; outside [0, nlist) = none
+    const int* sel = nullptr;          // the listed queries (IVF_RANGE_EXACT: all of them, ivf_launch_range_list_all)
+    const int* count = nullptr;        // [1] how many
+    int* done = nullptr;               // [1] queries answered here (radad_ivf_last_range)
+    int dim = 0, m = 0, nprobe = 0, nlist = 0;
+    int slot0 = 0, nslots = 0;         // this launch's queries: slots slot0 .. slot0 + nslots
+    double radius = 0.0;
+    double* pkey = nullptr;            // [nslots][nprobe][m]
+    int64_t* pid = nullptr;
+    int* arrive = nullptr;             // [nslots] arrival counters (zero between launches: the last arrival resets its own)
+    int* out_count = nullptr;          // [nq], zero at launch for the queries answered here
+    float* out_dist = nullptr; int64_t* out_idx = nullptr; double* out_key = nullptr;
+};
+static_assert(std::is_trivially_copyable_v<IvfRangeExactParams>, "kernel argument");
+
+// k_ivf_exact<IVF_ADM_NONE> with a radius: the same pairs in turn, the same float64 sums (keys are minus the squared distance inside the
+// kernel: larger is better).  A row that fails the strict test -(key) < radius is skipped BEFORE the list insertion; the rows that
+// pass are counted per wave, and each wave adds its count of the pair to out_count once.  m reaches 128, so a wave's sorted list is
+// TWO entries per lane (lane e holds entries e and e + 64); an insertion shifts both halves one lane up, entry 63 crossing over.
+// Insertions are rare once a list is full.  The waves' lists are ranked into the pair's partial list (only the entries the waves
+// hold are compared: sLen), and the pair that arrives last for a query merges the nprobe partial lists and writes the m slots,
+// -1 / NaN / NaN where there is no member.
+__global__ __launch_bounds__(IVX_THREADS) void k_ivf_range_exact(IvfRangeExactParams p) {
+    const int count = min(*p.count - p.slot0, p.nslots);
+    if (count <= 0) return;
+    extern __shared__ __attribute__((aligned(16))) char smem_re[];
+    __shared__ int s_last;
+    float* sQ = reinterpret_cast<float*>(smem_re);                                  // [dim]
+    double* sKey = reinterpret_cast<double*>(sQ + p.dim);                           // [IVX_WAVES][m]
+    long long* sId = reinterpret_cast<long long*>(sKey + IVX_WAVES * p.m);          // [IVX_WAVES][m]
+    int* sLen = reinterpret_cast<int*>(sId + IVX_WAVES * p.m);                      // [IVX_WAVES] entries of every wave's list
+    int* sPos = sLen + IVX_WAVES;                                                   // [nprobe] heads of the final merge
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nv = p.dim >> 2, K = p.m;
+    const float nan_f = __int_as_float(0x7fc00000);
+    const int64_t npairs = (int64_t)count * p.nprobe;
+    for (int64_t pr = blockIdx.x; pr < npairs; pr += gridDim.x) {                    // (uniform)
+        const int slot = (int)(pr / p.nprobe), j = (int)(pr % p.nprobe);
+        const int64_t qi = p.sel[p.slot0 + slot];
+        const int64_t list = p.probes[qi * p.nprobe + j];
+        int64_t r0 = 0, r1 = 0;
+        if ((uint64_t)list < (uint64_t)p.nlist) { r0 = p.loff[list]; r1 = p.loff[list + 1]; }
+        __syncthreads();                                                             // (the previous pair's LDS is free)
+        for (int i = tid; i < nv; i += IVX_THREADS)
+            reinterpret_cast<f32x4*>(sQ)[i] = reinterpret_cast<const f32x4*>(p.q + qi * p.dim)[i];
+        __syncthreads();
+        double ek0 = -INFINITY, ek1 = -INFINITY;                                     // lane e: entries e and e + 64 of the wave's sorted list
+        long long ei0 = IVX_NO_ID, ei1 = IVX_NO_ID;
+        int members = 0;                                                             // (wave-uniform) rows of this wave that passed
+        for (int64_t row = r0 + wave * IVX_ROWS; row < r1; row += IVX_WAVES * IVX_ROWS) {
+            double acc[IVX_ROWS];
+#pragma unroll
+            for (int u = 0; u < IVX_ROWS; ++u) acc[u] = 0.0;
+            for (int i = lane; i < nv; i += 64) {
+                f32x4 y[IVX_ROWS];
+#pragma unroll
+                for (int u = 0; u < IVX_ROWS; ++u) y[u] = reinterpret_cast<const f32x4*>(p.lrows + min(row + u, r1 - 1) * p.dim)[i];
+                const f32x4 x = reinterpret_cast<const f32x4*>(sQ)[i];
+#pragma unroll
+                for (int u = 0; u < IVX_ROWS; ++u)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { const double d = (double)x[e] - (double)y[u][e]; acc[u] -= d * d; }
+            }
+#pragma unroll
+            for (int u = 0; u < IVX_ROWS; ++u) {
+                if (row + u >= r1) break;                                            // (wave-uniform)
+                double v = acc[u];
+#pragma unroll
+                for (int ofs = 32; ofs > 0; ofs >>= 1) v += __shfl_xor(v, ofs, 64);
+                if (!(-v < p.radius)) continue;                                      // (wave-uniform) the strict test; a NaN key fails it
+                ++members;
+                const long long gid = p.lids[row + u];
+                const double lk = K <= 64 ? __shfl(ek0, K - 1, 64) : __shfl(ek1, K - 65, 64);
+                const long long li = K <= 64 ? __shfl(ei0, K - 1, 64) : __shfl(ei1, K - 65, 64);
+                if (ivx_better(v, gid, lk, li)) {                                    // (wave-uniform) beats the m-th entry
+                    // the better entries are a prefix of the sorted list: the new one goes behind them, the rest moves one entry up
+                    const int nb = __popcll(__ballot(lane < K && ivx_better(ek0, ei0, v, gid))) +
+                                   __popcll(__ballot(lane + 64 < K && ivx_better(ek1, ei1, v, gid)));
+                    const double t_k = __shfl(ek0, 63, 64);
+                    const long long t_i = __shfl(ei0, 63, 64);
+                    double pk0 = __shfl_up(ek0, 1, 64), pk1 = __shfl_up(ek1, 1, 64);
+                    long long pi0 = __shfl_up(ei0, 1, 64), pi1 = __shfl_up(ei1, 1, 64);
+                    if (lane == 0) { pk1 = t_k; pi1 = t_i; }
+                    if (lane > nb) { ek0 = pk0; ei0 = pi0; }
+                    else if (lane == nb) { ek0 = v; ei0 = gid; }
+                    if (lane + 64 > nb) { ek1 = pk1; ei1 = pi1; }
+                    else if (lane + 64 == nb) { ek1 = v; ei1 = gid; }
+                }
+            }
+        }
+        if (lane < K) { sKey[wave * K + lane] = ek0; sId[wave * K + lane] = ei0; }
+        if (lane + 64 < K) { sKey[wave * K + lane + 64] = ek1; sId[wave * K + lane + 64] = ei1; }
+        if (lane == 0) {
+            sLen[wave] = min(members, K);
+            if (members > 0) atomicAdd(&p.out_count[qi], members);
+        }
+        const int64_t ob = ((int64_t)slot * p.nprobe + j) * K;
+        if (tid < K) { p.pkey[ob + tid] = -INFINITY; p.pid[ob + tid] = IVX_NO_ID; }
+        __syncthreads();
+        for (int i = tid; i < IVX_WAVES * K; i += IVX_THREADS) {                      // rank of every listed row among the waves' entries
+            const int w = i / K, e = i - w * K;
+            if (e >= sLen[w]) continue;
+            const double kc = sKey[i];
+            const long long ic = sId[i];
+            int rank = 0;
+            for (int w2 = 0; w2 < IVX_WAVES; ++w2) {
+                const int n2 = sLen[w2];
+                for (int e2 = 0; e2 < n2; ++e2) rank += (int)ivx_better(sKey[w2 * K + e2], sId[w2 * K + e2], kc, ic);
+            }
+            if (rank < K) { p.pkey[ob + rank] = kc; p.pid[ob + rank] = ic; }
+        }
+        __threadfence();                                 // release: this pair's list is visible device-wide before the counter moves
+        __syncthreads();
+        if (tid == 0) {
+            const int old = atomicAdd(&p.arrive[slot], 1);
+            s_last = old == p.nprobe - 1;
+            if (s_last) p.arrive[slot] = 0;              // ready for the next launch
+        }
+        __syncthreads();
+        if (s_last && wave == 0) {                       // the query's last pair: merge its nprobe partial lists (lane l owns lists l, l + 64, ...)
+            __threadfence();                             // acquire
+            for (int part = lane; part < p.nprobe; part += 64) sPos[part] = 0;
+            const int64_t lb = (int64_t)slot * p.nprobe * K;
+            for (int o = 0; o < K; ++o) {
+                double bk = -INFINITY;
+                long long bi = IVX_NO_ID;
+                int bp = -1;
+                for (int part = lane; part < p.nprobe; part += 64) {
+                    const int pos = sPos[part];
+                    if (pos >= K) continue;
+                    const long long id = p.pid[lb + (int64_t)part * K + pos];
+                    if (id == IVX_NO_ID) continue;
+                    const double key = p.pkey[lb + (int64_t)part * K + pos];
+                    if (bp < 0 || ivx_better(key, id, bk, bi)) { bk = key; bi = id; bp = part; }
+                }
+#pragma unroll
+                for (int ofs = 32; ofs > 0; ofs >>= 1) {
+                    const double ok = __shfl_xor(bk, ofs, 64);
+                    const long long oi = __shfl_xor(bi, ofs, 64);
+                    const int op = __shfl_xor(bp, ofs, 64);
+                    if (op >= 0 && (bp < 0 || ivx_better(ok, oi, bk, bi))) { bk = ok; bi = oi; bp = op; }
+                }
+                if (bp >= 0 && (bp & 63) == lane) sPos[bp] += 1;
+                if (lane == 0) {
+                    const double kd = bp < 0 ? (double)nan_f : -bk;
+                    p.out_dist[qi * K + o] = bp < 0 ? nan_f : (float)kd;
+                    p.out_idx[qi * K + o] = bp < 0 ? (int64_t)-1 : (int64_t)bi;
+                    if (p.out_key) p.out_key[qi * K + o] = kd;
+                }
+            }
+            if (lane == 0) atomicAdd(p.done, 1);
+        }
+    }
+}
+
 struct DevMem {
     void* p = nullptr;
     size_t bytes = 0;
@@ -936,6 +1308,9 @@ struct radad_ivf_s {
     const int* last_fcount = nullptr;   // device counters of the most recent list-scan search: [0] queries its certificate rejected, [1] queries the
                                         // exact list scan answered
     bool last_exact = false;            // the most recent search was answered by the exact flat scan (k > 26): radad_ivf_last_search_exact
+    bool last_range = false;            // the most recent search was a radad_ivf_range_search (radad_ivf_last_range describes it: last_fcount [1] the
+    int64_t last_range_nq = 0;          // queries the exact pass answered, [2] the largest number of positions a query emitted)
+    int last_range_route = IVF_RANGE_EXACT;
     bool have_last = false;             // since all searches share the workspaces below and nothing synchronises with the host: a search on
     hipStream_t last_stream = nullptr;  // ANOTHER stream than the last records the event behind that stream's work first (knn.hip does the same)
     std::mutex mu;
@@ -1328,6 +1703,7 @@ static int ivf_search_lists(const char* fn, radad_ivf_t h, const float* q_dev, i
                             const IvfPqRule* pq = nullptr) {
     std::lock_guard<std::mutex> lk(h->mu);
     h->last_exact = false;
+    h->last_range = false;
     DeviceGuard g(h->device);
     hipStream_t st = (hipStream_t)stream;
     int rc;
@@ -1366,7 +1742,154 @@ static int ivf_search_lists(const char* fn, radad_ivf_t h, const float* q_dev, i
     return RADAD_OK;
 }
 
+// ---- the range search's launches (ivf_plan_range decides; an IvfPlan, so IvfSearch, ivf_ensure_buffers and ivf_launch_coarse_group serve
+// as they are) ---------------------------------------------------------------------------------------------------------------------
+struct IvfRangeOut { float radius; int32_t* count; float* dist; int64_t* idx; double* key; };
+
+// IVF_RANGE_HI: the top-k hi route's query preparation (k_hi_rows: f16 side, eps; it zeroes cand_cnt and the 8 counters), the floors,
+// the scan, the re-rank
+static int ivf_launch_range_hi(const IvfSearch& s, const IvfRangeOut& o) {
+    radad_ivf_t h = s.h;
+    const IvfPlan& p = s.p;
+    const hipStream_t st = s.st;
+    radad_knn_t f = h->flat;
+    _Float16* qh = s.qbuf<_Float16>(p.qbuf.qh);
+    float* qscale = s.qbuf<float>(p.qbuf.qscale); float* qconst = s.qbuf<float>(p.qbuf.qconst);
+    float* eps = s.qbuf<float>(p.qbuf.eps); float* thr = s.qbuf<float>(p.qbuf_thr);
+    int* cand_cnt = s.qbuf<int>(p.qbuf.cand_cnt);
+    HiRowsParams hp;
+    hp.in = s.q; hp.hi = qh; hp.scale_out = qscale; hp.eps_out = eps; hp.ystat = f->stat;
+    hp.n = p.nq; hp.dim = h->dim; hp.fixed_e = HI_E_PER_ROW; hp.l2 = 1;
+    hp.zero_flags = cand_cnt; hp.zero_counters = s.fcount();
+    hp.mu = f->cmu; hp.mu_norm = f->cmu ? f->mu_norm : 0.f; hp.mu_sq = f->cmu ? f->mu_sq : 0.f; hp.biased = 1;
+    hp.qconst_out = qconst;
+    launch_hi_rows(hp, st);
+    hipLaunchKernelGGL(k_range_floor, dim3((unsigned)ceil_div64(p.nq, 256)), dim3(256), 0, st, (const float*)eps, -o.radius, thr, p.nq);
+    IvfRangeHiParams ip;
+    ip.lhi = (const _Float16*)h->lhi.p; ip.lscale = f->rscale ? (const float*)h->lscale.p : nullptr;
+    ip.uscale = f->uniform_e != HI_E_PER_ROW ? ldexpf(1.0f, -f->uniform_e) : 1.0f;
+    ip.lbias = (const float*)h->lbias.p; ip.loff = (const int*)h->loff.p; ip.qh = qh; ip.qscale = qscale; ip.qconst = qconst; ip.thr = thr;
+    ip.task_list = s.tasks(p.tasks.tl); ip.task_pbeg = s.tasks(p.tasks.tp); ip.task_cnt = s.tasks(p.tasks.tc);
+    ip.n_tasks_dev = s.tasks(p.tasks.nt); ip.pair_q = s.tasks(p.tasks.pq);
+    ip.dim = h->dim; ip.qcap = p.qcap; ip.split = p.split;
+    ip.cand_cnt = cand_cnt; ip.cand_cap = p.ccap; ip.cand_idx = (int*)h->cand_i.p;
+    RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_range_hi), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.scan_lds));
+    hipLaunchKernelGGL(k_ivf_range_hi, dim3((unsigned)p.scan_grid), dim3(SQ_THREADS), p.scan_lds, st, ip);
+    IvfRangeRefineParams g;
+    g.idx = (const int*)h->cand_i.p; g.cnt = cand_cnt; g.cap = p.ccap; g.dim = h->dim; g.m = p.k;
+    g.lrows = (const float*)h->lrows.p; g.lids = (const int64_t*)h->lids.p; g.n_pos = (int64_t)h->assign.size(); g.q = s.q;
+    g.radius = (double)o.radius; g.flag_count = s.fcount(); g.flag_sel = s.qbuf<int>(p.qbuf.fsel);
+    g.out_count = o.count; g.out_dist = o.dist; g.out_idx = o.idx; g.out_key = o.key;
+    RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_range_refine), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.refine_lds));
+    hipLaunchKernelGGL(k_ivf_range_refine, dim3((unsigned)p.nq), dim3(RF_THREADS), p.refine_lds, st, g);
+    RADAD_HIP_CHECK(hipGetLastError());
+    return RADAD_OK;
+}
+
+// every query of the batch listed for the exact pass, its count zero: IVF_RANGE_EXACT (fresh: the 8 counters are cleared here), or
+// behind the hi route under RADAD_IVF_OPT_HI_SCAN 2 (the counters keep what the re-rank recorded)
+static int ivf_launch_range_list_all(const IvfSearch& s, const IvfRangeOut& o, bool fresh) {
+    if (fresh) RADAD_HIP_CHECK(hipMemsetAsync(s.fcount(), 0, 8 * sizeof(int), s.st));
+    RADAD_HIP_CHECK(hipMemsetAsync(o.count, 0, (size_t)s.p.nq * sizeof(int32_t), s.st));
+    knn_launch_list_all(s.qbuf<int>(s.p.qbuf.fsel), s.fcount(), s.p.nq, s.st);
+    RADAD_HIP_CHECK(hipGetLastError());
+    return RADAD_OK;
+}
+
+// the listed queries: k_ivf_range_exact, driven from the device (it leaves at once when nobody is listed); one launch unless the
+// batch's partial lists exceed IVX_PART_BUDGET
+static int ivf_launch_range_exact(const IvfSearch& s, const IvfRangeOut& o) {
+    radad_ivf_t h = s.h;
+    const IvfPlan& p = s.p;
+    IvfRangeExactParams x;
+    x.lrows = (const float*)h->lrows.p; x.lids = (const int64_t*)h->lids.p; x.loff = (const int*)h->loff.p; x.q = s.q;
+    x.probes = s.probes(); x.sel = s.qbuf<int>(p.qbuf.fsel); x.count = s.fcount(); x.done = s.fcount() + 1;
+    x.dim = h->dim; x.m = p.k; x.nprobe = p.nprobe; x.nlist = h->nlist; x.nslots = (int)p.nslots; x.radius = (double)o.radius;
+    x.pkey = (double*)h->xkey.p; x.pid = (int64_t*)h->xid.p; x.arrive = (int*)h->xarrive.p;
+    x.out_count = o.count; x.out_dist = o.dist; x.out_idx = o.idx; x.out_key = o.key;
+    RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_range_exact), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.xlds));
+    for (int64_t i = 0; i < p.xlaunches; ++i) {
+        x.slot0 = (int)(i * p.nslots);
+        hipLaunchKernelGGL(k_ivf_range_exact, dim3((unsigned)p.xgrid), dim3(IVX_THREADS), p.xlds, s.st, x);
+    }
+    RADAD_HIP_CHECK(hipGetLastError());
+    return RADAD_OK;
+}
+
+// The range search behind radad_ivf_range_search, beside ivf_search_lists: the same ordering, preparation, plane, buffers, coarse
+// search and grouping; then the route's launches.  The caller has checked the arguments; this takes the handle's lock.
+static int ivf_range_lists(const char* fn, radad_ivf_t h, const float* q_dev, int64_t nq, int nprobe, int m, const IvfRangeOut& o, void* stream) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard g(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if (!h->ev_done) RADAD_HIP_CHECK(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
+    if (h->have_last && st != h->last_stream) {
+        if (hipEventRecord(h->ev_done, h->last_stream) == hipSuccess) RADAD_HIP_CHECK(hipStreamWaitEvent(st, h->ev_done, 0));
+        else { (void)hipGetLastError(); RADAD_HIP_CHECK(hipDeviceSynchronize()); }
+    }
+    if ((rc = ivf_prepare(h, st))) return rc;
+    IvfFacts facts;
+    facts.dim = h->dim; facts.nlist = h->nlist; facts.rows = (int64_t)h->assign.size();
+    if (facts.rows == 0) {                               // count 0 and the padding (an all-ones float64 is a NaN too)
+        RADAD_HIP_CHECK(hipMemsetAsync(o.count, 0, (size_t)nq * sizeof(int32_t), st));
+        if ((rc = ivf_answer_empty(nq, m, true, o.dist, o.idx, st))) return rc;
+        if (o.key) RADAD_HIP_CHECK(hipMemsetAsync(o.key, 0xff, (size_t)nq * m * sizeof(double), st));
+        h->last_exact = false; h->last_hi = false; h->last_fcount = nullptr;
+        h->last_range = true; h->last_range_nq = nq; h->last_range_route = IVF_RANGE_EXACT;
+        h->last_stream = st; h->have_last = true;
+        return RADAD_OK;
+    }
+    facts.plane = ivf_ensure_plane(h, st);
+    const IvfPlan p = ivf_plan_range(facts, nq, m, nprobe);
+    if ((rc = ivf_plan_refused(fn, h, p))) return rc;
+    if ((rc = ivf_ensure_buffers(h, p, st))) return rc;
+    const IvfSearch s{h, p, q_dev, o.dist, o.idx, st, nullptr, IvfPqRule()};
+    if ((rc = ivf_launch_coarse_group(s))) return rc;
+    const bool hi = p.range_route == IVF_RANGE_HI;
+    if (hi && (rc = ivf_launch_range_hi(s, o))) return rc;
+    if ((!hi || h->opt_hi == 2) && (rc = ivf_launch_range_list_all(s, o, !hi))) return rc;
+    if ((rc = ivf_launch_range_exact(s, o))) return rc;
+    h->last_exact = false; h->last_hi = hi; h->last_fcount = s.fcount();
+    h->last_range = true; h->last_range_nq = nq; h->last_range_route = p.range_route;
+    h->last_stream = st;
+    h->have_last = true;
+    return RADAD_OK;
+}
+
 extern "C" {
+
+int radad_ivf_range_search(radad_ivf_t h, const float* q_dev, int64_t nq, int nprobe, float radius, int max_per_query, int32_t* out_count_dev,
+                           float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, void* stream) {
+    const char* fn = "radad_ivf_range_search";
+    RADAD_REQUIRE(h, "%s: NULL handle", fn);
+    if (!h->trained) { radad_set_error("%s: the index is not trained", fn); return RADAD_ESTATE; }
+    RADAD_REQUIRE(max_per_query >= 1 && max_per_query <= IVF_MAX_K, "%s: max_per_query=%d outside [1,%d]", fn, max_per_query, IVF_MAX_K);
+    RADAD_REQUIRE(radius == radius, "%s: the radius is NaN", fn);
+    RADAD_REQUIRE(nq >= 0 && nq < (1 << 24), "%s: bad nq", fn);
+    RADAD_REQUIRE(nprobe >= 1, "%s: nprobe=%d must be >= 1", fn, nprobe);
+    if (nq == 0) return RADAD_OK;
+    RADAD_REQUIRE(q_dev && out_count_dev && out_dist_dev && out_idx_dev, "%s: NULL buffer", fn);
+    const IvfRangeOut o{radius, out_count_dev, out_dist_dev, out_idx_dev, out_key_dev};
+    return ivf_range_lists(fn, h, q_dev, nq, nprobe, max_per_query, o, stream);
+}
+
+int radad_ivf_last_range(radad_ivf_t h, int64_t* n_queries, int* route, int* n_exact, int* max_emitted) {
+    RADAD_REQUIRE(h, "radad_ivf_last_range: NULL handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->last_range) { radad_set_error("radad_ivf_last_range: the most recent search of this index was not a range search"); return RADAD_ESTATE; }
+    int c[3] = {0, 0, 0};
+    if (h->last_fcount) {
+        DeviceGuard g(h->device);
+        ivf_wait_searches(h);
+        RADAD_HIP_CHECK(hipMemcpy(c, h->last_fcount, sizeof(c), hipMemcpyDeviceToHost));
+    }
+    if (n_queries) *n_queries = h->last_range_nq;
+    if (route) *route = h->last_range_route;
+    if (n_exact) *n_exact = c[1];
+    if (max_emitted) *max_emitted = c[2];
+    return RADAD_OK;
+}
 
 int radad_ivf_create(int dim, int nlist, int device, radad_ivf_t* out) {
     RADAD_REQUIRE(out, "radad_ivf_create: out is NULL");
@@ -1552,6 +2075,7 @@ int radad_ivf_set_option(radad_ivf_t h, int option, int value) {
 int radad_ivf_last_search_info(radad_ivf_t h, int* kind_out, int* rejected_out) {
     RADAD_REQUIRE(h && kind_out && rejected_out, "radad_ivf_last_search_info: NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
+    if (h->last_range) { radad_set_error("radad_ivf_last_search_info: the most recent search of this index was a range search (radad_ivf_last_range)"); return RADAD_ESTATE; }
     *kind_out = h->last_exact ? RADAD_IVF_SCAN_EXACT_FLAT : (h->last_hi ? RADAD_IVF_SCAN_HI : RADAD_IVF_SCAN_F32);
     return ivf_last_counts(h, rejected_out, nullptr);
 }
@@ -1559,6 +2083,7 @@ int radad_ivf_last_search_info(radad_ivf_t h, int* kind_out, int* rejected_out) 
 int radad_ivf_last_search_counts(radad_ivf_t h, int* rejected_out, int* exact_out) {
     RADAD_REQUIRE(h && rejected_out && exact_out, "radad_ivf_last_search_counts: NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
+    if (h->last_range) { radad_set_error("radad_ivf_last_search_counts: the most recent search of this index was a range search (radad_ivf_last_range)"); return RADAD_ESTATE; }
     return ivf_last_counts(h, rejected_out, exact_out);
 }
 
@@ -1583,7 +2108,7 @@ int radad_ivf_search(radad_ivf_t h, const float* q_dev, int64_t nq, int k, int n
     // the caller can tell from radad_ivf_last_search_exact.
     RADAD_REQUIRE(nprobe >= 1, "radad_ivf_search: nprobe=%d must be >= 1", nprobe);
     if (k + KNN_MARGIN > 32) {
-        { std::lock_guard<std::mutex> lk(h->mu); h->last_exact = true; }
+        { std::lock_guard<std::mutex> lk(h->mu); h->last_exact = true; h->last_range = false; }
         return radad_knn_search(h->flat, q_dev, nq, k, out_dist_dev, out_idx_dev, stream);
     }
     return ivf_search_lists("radad_ivf_search", h, q_dev, nq, k, nprobe, false, nullptr, nullptr, 0, out_dist_dev, out_idx_dev, stream);

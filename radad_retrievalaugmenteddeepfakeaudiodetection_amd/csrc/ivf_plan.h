@@ -96,6 +96,9 @@ struct IvfPlan {
     size_t pq_lds = 0;               // the tag block, part of scan_lds on both routes (at offset scan_lds - pq_lds)
     int64_t pq_bits = 0;             // bits of the pre-pass's hash bitset (a power of two)
     size_t pq_bitset = 0;            // its bytes
+    // ivf_plan_range only (ivf_plan_search leaves both as they are): the route and where the floors thr[q] lie in `qbuf`
+    int range_route = -1;            // IVF_RANGE_HI / IVF_RANGE_EXACT
+    size_t qbuf_thr = 0;
 };
 
 // The plan of radad_ivf_search / radad_ivf_search_excl / radad_ivf_search_excl_pq on the probed lists (k + KNN_MARGIN <= 32).
@@ -192,5 +195,68 @@ static IvfPlan ivf_plan_search(const IvfFacts& s, int64_t nq, int k, int nprobe,
     p.xarrive = (size_t)slots * sizeof(int);
     p.xgrid = std::min<int64_t>(slots * nprobe, IVX_MAX_GRID);
     p.xlaunches = ceil_div64(nq, slots);      // (one launch unless the batch's partial lists exceed IVX_PART_BUDGET)
+    return p;
+}
+
+// ---- range search over the probed lists (radad_ivf_range_search) --------------------------------------------------------------------
+// The routes (radad_hip.h: RADAD_IVF_RANGE_HI / RADAD_IVF_RANGE_EXACT; ivf.inc asserts the values)
+constexpr int IVF_RANGE_HI = 0, IVF_RANGE_EXACT = 1;
+constexpr int IVF_RANGE_CAP = 4096;              // positions of a query's candidate buffer = RG_MAX_CAP, what the re-rank's LDS sort is sized for
+constexpr size_t ivf_range_hi_lds_bytes(int qcap, int dim) { return (size_t)qcap * (dim + 8) * 2; }      // the task's f16 queries: no score tile
+constexpr size_t ivf_range_refine_lds_bytes() { return (size_t)IVF_RANGE_CAP * 12 + 64; }                // float64 key + id per entry, 4 wave counts
+constexpr size_t ivf_range_exact_lds_bytes(int dim, int m, int nprobe) {                                  // query | 8 waves x m (key, id) | 8 lengths | nprobe heads
+    return (size_t)dim * 4 + (size_t)IVX_WAVES * m * 16 + (size_t)IVX_WAVES * 4 + (size_t)nprobe * 4;
+}
+
+// The plan of radad_ivf_range_search: every member (float64 key < radius) of the nprobe probed lists, the best m <= IVF_MAX_K of them
+// listed.  An IvfPlan whose coarse and grouping section (ws_a / ws_b, tasks, qcap, T, group_small) is ivf_plan_search's; k = m and
+// ksel = 0 (no per-pair partial lists: part_s = part_i = 0, and the grouping kernels write nothing for a pair without a list).
+//   IVF_RANGE_HI    exactly when ivf_plan_search takes hi_route (the plane is there and ivf_hi_lds_bytes <= 160 KB): k_hi_rows, the floors
+//                   thr[q] (qbuf_thr), k_ivf_range_hi into buffers of IVF_RANGE_CAP POSITIONS per query (cand_i; no scores: cand_s = 0),
+//                   k_ivf_range_refine; a query that emitted more goes to the exact pass.  split comes from the task count alone: no
+//                   workgroup has a bound of its own, so the (ccap / 2) / (nprobe (k + 8)) clause of the top-k plan has no meaning here.
+//   IVF_RANGE_EXACT k_ivf_range_exact for every query.
+// The exact pass keeps nprobe x m x 16 B of partial lists per query, in launches of nslots queries within IVX_PART_BUDGET.
+static IvfPlan ivf_plan_range(const IvfFacts& s, int64_t nq, int m, int nprobe) {
+    // the coarse and grouping section is the top-k plan's own (k plays no part in it; the plan's later, k-dependent fields are not read)
+    const IvfPlan b = ivf_plan_search(s, nq, 1, nprobe, false);
+    IvfPlan p;
+    nprobe = b.nprobe;
+    const int64_t npairs = b.npairs, T = b.T;
+    const int qcap = b.qcap;
+    p.nq = nq; p.k = m; p.ksel = 0; p.nprobe = nprobe; p.npairs = npairs;
+    p.ws_a = b.ws_a; p.ws_b = b.ws_b;
+    p.cmargin = b.cmargin; p.qcap = qcap; p.T = T;
+    if (b.status == IVF_PLAN_TOO_MANY_PAIRS) { p.status = IVF_PLAN_TOO_MANY_PAIRS; return p; }
+    p.tasks = b.tasks;
+    p.group_small = b.group_small; p.group_lds = b.group_lds;
+
+    // the route is the top-k plan's choice, and so is the layout of `qbuf`: a range search has no running bound, so its floors thr[q]
+    // stand where gbound does; fcount [8]: [0] queries left to the exact pass, [1] answered by it, [2] the largest cand_cnt
+    const bool hi = b.hi_route;
+    p.hi_route = hi;
+    p.range_route = hi ? IVF_RANGE_HI : IVF_RANGE_EXACT;
+    p.qbuf = b.qbuf;
+    p.qbuf_thr = b.qbuf.gbound;
+    if (hi) {
+        p.ccap = IVF_RANGE_CAP;
+        p.cand_i = (size_t)nq * IVF_RANGE_CAP * sizeof(int);
+        p.split = T <= 64 ? 8 : (T <= 128 ? 4 : (T <= 256 ? 2 : 1));
+        p.scan_grid = T * p.split;
+        p.scan_lds = ivf_range_hi_lds_bytes(qcap, s.dim);
+        p.cap = IVF_RANGE_CAP;
+        p.refine_lds = ivf_range_refine_lds_bytes();
+    }
+    const size_t xlds = ivf_range_exact_lds_bytes(s.dim, m, nprobe);
+    p.xlds = xlds;
+    if (!(xlds <= 160 * 1024)) { p.status = IVF_PLAN_NPROBE_TOO_LARGE; return p; }
+    const int64_t per_q = (int64_t)nprobe * m * 16;
+    const int64_t slots = std::min<int64_t>(nq, std::max<int64_t>(1, (int64_t)IVX_PART_BUDGET / per_q));
+    p.nslots = slots;
+    p.xkey = (size_t)slots * nprobe * m * sizeof(double);
+    p.xid = (size_t)slots * nprobe * m * sizeof(int64_t);
+    p.xarrive = (size_t)slots * sizeof(int);
+    p.xgrid = std::min<int64_t>(slots * nprobe, IVX_MAX_GRID);
+    p.xlaunches = ceil_div64(nq, slots);
     return p;
 }

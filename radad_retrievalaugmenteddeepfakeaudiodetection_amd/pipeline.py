@@ -98,7 +98,8 @@ class HotPathPipeline:
 
     # ---- audit by content ---------------------------------------------------------------------------------
     def near_duplicates(self, query_vectors, thresh: float, max_per_query: int = 128, query_paths: Optional[List[str]] = None,
-                        exact_exclusion: bool = False, exclude: str = "file", query_speakers: Optional[List[str]] = None):
+                        exact_exclusion: bool = False, exclude: str = "file", query_speakers: Optional[List[str]] = None,
+                        probed: bool = False):
         """Per query the stored rows within `thresh` of it (VectorDatabase.range_search_batch: cosine / inner product > thresh, or
         squared L2 < thresh, exactly), as a list of (path, label, score), best first, at most max_per_query.  The content
         counterpart of validate_no_leakage (pipeline.py:1105-1110), which compares basenames and so passes a re-encoded or renamed
@@ -109,12 +110,18 @@ class HotPathPipeline:
         (VectorDatabase.range_search_excluding_per_query_batch) and returns (hits, counts): counts[j] is the exact number of admissible
         rows within the radius, and all max_per_query slots go to admissible rows.  exclude="file": query j excludes the rows whose
         basename is that of query_paths[j]; exclude="speaker": the rows whose stored speaker_id metadata equals query_speakers[j]
-        (leave-one-speaker-out)."""
+        (leave-one-speaker-out).
+        probed=True (IVF stores; a ValueError on a flat one): the same lists from the rows of the probed lists
+        (VectorDatabase.range_search_probed_batch, config.vector_db_nprobe; squared L2 < thresh) -- the audit on a store that is too
+        large to scan whole.  Not offered with exact_exclusion."""
         if exclude not in ("file", "speaker"):
             raise ValueError(f"exclude must be 'file' or 'speaker', got {exclude!r}")
+        if probed and exact_exclusion:
+            raise ValueError("near_duplicates: exact_exclusion is not offered with probed=True (an IVF range search takes no exclusion sets)")
         if exact_exclusion:
             return self._near_duplicates_excluding(query_vectors, thresh, max_per_query, query_paths, exclude, query_speakers)
-        lims, dist, idx = self.vector_db.range_search_batch(query_vectors, thresh, max_per_query=max_per_query)[:3]
+        search = self.vector_db.range_search_probed_batch if probed else self.vector_db.range_search_batch
+        lims, dist, idx = search(query_vectors, thresh, max_per_query=max_per_query)[:3]
         if hasattr(lims, "cpu"):
             lims, dist, idx = lims.cpu().numpy(), dist.cpu().numpy(), idx.cpu().numpy()
         base = self.vector_db.index.id_base if hasattr(self.vector_db.index, "id_base") else 0

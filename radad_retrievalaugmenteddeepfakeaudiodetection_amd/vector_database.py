@@ -931,6 +931,53 @@ class HipIVFFlatIndex:
         raise ValueError("range_search_excluding_per_query is the flat store's search: an IVF search sees the probed lists, not the "
                          "store, so it cannot say that no other admissible row is within the radius")
 
+    def range_search_probed_device(self, q, thresh: float, max_per_query: int = 128, return_f64: bool = False):
+        """Every row of the self.nprobe probed lists within `thresh` of each query, exactly (radad_ivf_range_search): squared L2 <
+        thresh, strictly, decided on the float64 key -- the exact range search restricted to the probed lists, as search is the exact
+        top-k restricted to them (nprobe == nlist: HipFlatIndex.range_search on the same rows).  q [nq, d] float32 CUDA tensor ->
+        (counts i32 [nq], D f32 [nq, M], I i64 [nq, M]) on the device, M = max_per_query <= 128: counts are the EXACT numbers of
+        members, also beyond M; each query's first min(count, M) slots hold its best members in (key, lower insertion id) order, the
+        rest -1 / NaN.  With return_f64 also the float64 keys."""
+        import torch
+        m = self._range_probed_m(thresh, max_per_query)
+        q = self._to_dev(q)
+        if q.dim() != 2 or q.shape[1] != self.d:
+            raise ValueError(f"range_search_probed expects [nq, {self.d}], got {tuple(q.shape)}")
+        counts = torch.empty((q.shape[0],), device=q.device, dtype=torch.int32)
+        D, I, K64 = _alloc_out(q, m, return_f64)
+        with torch.cuda.device(q.device):
+            _lib.check(self._lib.radad_ivf_range_search(self._h, q.data_ptr(), q.shape[0], int(self.nprobe), float(thresh), m,
+                                                        counts.data_ptr(), D.data_ptr(), I.data_ptr(), _ptr(K64),
+                                                        _lib.stream_ptr(q.device)), "radad_ivf_range_search")
+        return (counts, D, I, K64) if return_f64 else (counts, D, I)
+
+    @staticmethod
+    def _range_probed_m(thresh, max_per_query) -> int:
+        """the argument checks of range_search_probed*, before anything goes to the device"""
+        m = int(max_per_query)
+        if not 1 <= m <= _lib.IVF_MAX_K:
+            raise ValueError(f"range_search_probed supports 1 <= max_per_query <= {_lib.IVF_MAX_K} (asked for {m}); the count is exact: "
+                             "narrow the radius")
+        if thresh != thresh:
+            raise ValueError("range_search_probed: the radius is NaN")
+        return m
+
+    _range_csr = HipFlatIndex._range_csr      # the packing of a padded device result into faiss's CSR form (it reads self.device)
+
+    def range_search_probed(self, x, thresh: float, max_per_query: int = 128, return_counts: bool = False):
+        """range_search_probed_device in faiss's CSR form, as HipFlatIndex.range_search: -> (lims int64 [nq + 1], D float32
+        [lims[-1]], I int64 [lims[-1]]) (+ the exact int32 counts with return_counts); numpy in -> numpy out, CUDA in -> CUDA out."""
+        self._range_probed_m(thresh, max_per_query)
+        return self._range_csr(x, max_per_query, return_counts, lambda q: self.range_search_probed_device(q, thresh, max_per_query))
+
+    def last_range(self) -> dict:
+        """{"queries", "route": "hi_lists" | "exact_lists", "exact": queries the exact float64 list scan answered, "max_emitted": the
+        largest number of positions one query's f16 scan emitted (0 on the exact route)} of the most recent range_search_probed
+        (radad_ivf_last_range; synchronises with it; a ValueError when the most recent search was not a range search)"""
+        nq, route, ex, me = C.c_int64(), C.c_int(), C.c_int(), C.c_int()
+        _lib.check(self._lib.radad_ivf_last_range(self._h, C.byref(nq), C.byref(route), C.byref(ex), C.byref(me)), "radad_ivf_last_range")
+        return {"queries": nq.value, "route": _lib.IVF_RANGE_ROUTES[route.value], "exact": ex.value, "max_emitted": me.value}
+
     MAX_K_PROBED = 26  # csrc/ivf.inc: the largest k the list scans hold (k + 6 <= 32 entries per (query, list))
 
     def search_probed_excluding(self, q, k: int, row_tags, exclude_tags):
@@ -1206,11 +1253,25 @@ class VectorDatabase:
             return empty
         return self.index.range_search(query_vectors, thresh, max_per_query=max_per_query, return_counts=return_counts)
 
-    def _range_front(self, name: str, query_vectors, return_counts: bool):
+    def range_search_probed_batch(self, query_vectors, thresh: float, max_per_query: int = 128, return_counts: bool = False):
+        """IVF stores: every row of the probed lists (config.vector_db_nprobe, vector_database.py:174-179) within `thresh` (squared L2,
+        strictly) of each query, exactly, in the CSR form of range_search_batch (HipIVFFlatIndex.range_search_probed): the exact
+        range search restricted to the probed lists.  max_per_query <= 128.  Inputs and the empty-store result as range_search_batch."""
+        query_vectors, empty = self._range_front("range_search_probed_batch", query_vectors, return_counts, probed=True)
+        if empty is not None:
+            return empty
+        if hasattr(self.config, "vector_db_nprobe"):        # vector_database.py:174-179
+            self.index.nprobe = int(self.config.vector_db_nprobe)
+        return self.index.range_search_probed(query_vectors, thresh, max_per_query=max_per_query, return_counts=return_counts)
+
+    def _range_front(self, name: str, query_vectors, return_counts: bool, probed: bool = False):
         """the front of the range searches -> (query_vectors [B, d], None), or (query_vectors, the empty result of an empty store)"""
         if self.index is None:
             raise ValueError("Vector database is empty. Build the database first.")
-        if not isinstance(self.index, HipFlatIndex):
+        if probed:
+            if not isinstance(self.index, HipIVFFlatIndex):
+                raise ValueError(f"{name} is the IVF store's range search (vector_db_index_type 'IVF'); a flat store has range_search_batch")
+        elif not isinstance(self.index, HipFlatIndex):
             raise ValueError(f"{name} is flat and single-handle only (vector_db_index_type 'L2' or 'IP'): an IVF search "
                              "sees the probed lists, not the store")
         is_dev = hasattr(query_vectors, "is_cuda") and query_vectors.is_cuda
