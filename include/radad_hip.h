@@ -596,7 +596,7 @@ int radad_knn_search_excl_scan_pq(radad_knn_t h, const void* q_dev, int q_dtype,
  * of RADAD_KNN_OPT_RANGE_SMALLQ is still 0: switching it is a change of its own.
  * Not offered: a begin / finish pair and sharded range search (a shard's answer is exact: concatenating the shards' lists is the
  * merge); results beyond RADAD_KNN_MAX_K per query (the count is exact: the caller can narrow the radius).  The IVF index has its
- * own call, radad_ivf_range_search below; still not offered on IVF: exclusion sets combined with a radius, and M > 128.
+ * own calls, radad_ivf_range_search and radad_ivf_range_search_excl / _excl_pq below; still not offered on IVF: M > 128.
  * Exclusion sets combined with a radius: the two calls below. */
 #define RADAD_RANGE_TILE 0
 #define RADAD_RANGE_EXACT 1
@@ -818,13 +818,71 @@ int radad_ivf_set_option(radad_ivf_t h, int option, int value);
  * radad_knn_range_search of the same rows: 3.58 ms for one query (no certified route by default), 0.30 / 0.89 ms for 256 / 1024 --
  * faster than both IVF calls on this store, whose list scans take four times what tools/bench_ivf.py records for its own.
  * Not measured: that tool's store, the exact route at this scale, buffers that overflow.
- * Not offered: exclusion sets combined with a radius, M > 128, sharded IVF. */
+ * Exclusion sets combined with a radius: radad_ivf_range_search_excl / radad_ivf_range_search_excl_pq below.
+ * Not offered: M > 128, sharded IVF. */
 #define RADAD_IVF_RANGE_HI 0
 #define RADAD_IVF_RANGE_EXACT 1
 int radad_ivf_range_search(radad_ivf_t h, const float* q_dev, int64_t nq, int nprobe, float radius, int max_per_query,
                            int32_t* out_count_dev /*[nq]*/, float* out_dist_dev /*[nq,M]*/, int64_t* out_idx_dev /*[nq,M]*/,
                            double* out_key_dev /*[nq,M] or NULL*/, void* stream);
 int radad_ivf_last_range(radad_ivf_t h, int64_t* n_queries, int* route, int* n_exact, int* max_emitted);
+
+/* Certified range search among the rows of the probed lists that a query does not exclude: radad_ivf_range_search over the ADMISSIBLE
+ * rows.  The near-duplicate audit of an IVF store asks how many OTHER rows lie within the radius; filtering radad_ivf_range_search's
+ * lists afterwards leaves the unfiltered count, lets a clip's own segments or a speaker's rows take all M slots, and in the
+ * training_file_ids mode (most of the store excluded) lets excluded rows alone push a query past its 4096-position buffer.
+ * Outputs: every output rule of radad_ivf_range_search with "row of the probed lists" replaced by "admissible row of the probed lists"
+ * -- float64 key over the stored fp32 values, member iff key < (double)radius strictly, out_count[j] the EXACT number of admissible
+ * members also beyond M = max_per_query, slots 0 .. min(count, M) - 1 the best admissible members by (key, lower insertion id),
+ * -1 / NaN / NaN behind them, M in [1, 128].  An excluded row is never counted, never listed and never takes a slot of a query's
+ * candidate buffer, on either route: overflow, and so the cost, depends on the admissible rows near a query alone.
+ *   radad_ivf_range_search_excl     ONE set for the batch, the rule of radad_ivf_search_excl: row_tags_dev [ntotal] by insertion id,
+ *                 excl_sorted_dev [n_excl] ASCENDING (the caller's contract, not checked); both may be NULL only when n_excl == 0.
+ *   radad_ivf_range_search_excl_pq  one set PER QUERY, the rule of radad_ivf_search_excl_pq: row r is admissible for query j iff
+ *                 row_tags[r] is not among the first cnt_j entries of q_tags[j, :], cnt_j = q_tag_counts[j] clamped on the device to
+ *                 [0, m] (NULL = m for every query); any order, repeats allowed; 0 <= m <= RADAD_EXCL_PQ_MAX_TAGS.
+ *   n_excl == 0, m == 0, or no query excludes a stored row: the four outputs equal radad_ivf_range_search's bit for bit (same route)
+ *   every query carries the same set S:                      _excl_pq equals _excl with S sorted, bit for bit
+ * How: a range scan's floor thr[q] is fixed before the launch and no row sets a bound, so -- unlike the top-k list scans, which must
+ * keep excluded rows out of their bounds and therefore fetch admission bits for every step -- admission is decided only for a (row,
+ * query) pair that has already passed the score test.
+ *   RADAD_IVF_RANGE_HI     k_ivf_range_hi<ADM>: the lane holding a pair at or above the floor asks, before it takes a slot, the pair's bit
+ *                 of the admission bitmap (one set for the batch: k_admit_bitmap by list-major position, built on `stream` behind the
+ *                 layout as in radad_ivf_search_excl) or compares the row's tag with its query's tags, staged per task in LDS behind
+ *                 the f16 queries (one set per query).  The per-query form has NO pre-pass: no suspect bitmap, no hash bitset, and
+ *                 RADAD_IVF_OPT_PQ_FILTER has no effect on it.  k_ivf_range_refine runs unchanged: everything emitted is admissible.
+ *                 The tag block counts towards the scan's LDS; a shape whose top-k search with the same sets would leave the f16 list
+ *                 scan takes the exact route.
+ *   RADAD_IVF_RANGE_EXACT, overflow and RADAD_IVF_OPT_HI_SCAN 2: k_ivf_range_exact<ADM>, the admission test behind the strict radius
+ *                 test and in front of the count and the list insertion, so only members pay for a tag gather -- the bit, or one
+ *                 ballot per member against the query's tags held across a wave's lanes (lane t tag t).
+ * Errors, before anything is enqueued (outputs untouched, the handle usable): RADAD_EINVAL for everything radad_ivf_range_search
+ * refuses, for n_excl < 0, for m outside [0, RADAD_EXCL_PQ_MAX_TAGS], for NULL row_tags_dev or excl_sorted_dev with n_excl > 0, for NULL
+ * row_tags_dev or q_tags_dev with m > 0; RADAD_ESTATE for an untrained index.  nq == 0 returns RADAD_OK; a trained index without rows
+ * answers count 0 and padding.  Stream-ordered, serialised by the handle's mutex and ordered against searches on other streams like
+ * every IVF search; the tag arrays must stay alive until the call's device work ends.  radad_ivf_last_range describes both calls with
+ * the same four fields -- max_emitted counts admissible (row, query) pairs only --, and radad_ivf_last_search_info / _counts return
+ * RADAD_ESTATE after either, as after radad_ivf_range_search.
+ * Measured (tools/bench_ivf_range_excl.py, profiles/ivf_range_excl.md; 1 M x 512 noise rows, nlist 4096, nprobe 32, M = 128, 10 planted
+ * rows of other files per query within the radius, one run on one MI355X, each leg alternated with radad_ivf_range_search on the same
+ * handle; 1 / 256 / 1024 queries).  One set per query, every query excluding its own speaker of c rows within the radius: 0.104 /
+ * 0.774 / 1.778 ms at c = 0 against 0.102 / 0.772 / 1.738 ms for the plain call (1.02 / 1.00 / 1.02 of it); 0.104 / 0.762 / 1.654 ms
+ * at c = 200 (0.83 / 0.96 / 0.98); 0.104 / 0.719 / 1.493 ms at c = 1500 against 0.337 / 1.148 / 2.006 ms (0.31 / 0.63 / 0.74): the crowd
+ * takes no slot and is never re-scored, max_emitted 10 instead of 1510.  One set for the batch covering 0 / 50 / 90 % of the rows:
+ * 1.01 / 1.17 / 1.08 of the plain call for one query (the bitmap pre-pass over 1 M positions, 0.017 ms), 1.00 / 1.02 / 1.02 for 256,
+ * 1.00 / 1.01 / 1.00 for 1024.  Not measured: buffers that overflow at this scale, the exact route at this scale, m = 64.
+ * Not offered: M > 128, a batch-wide set combined with per-query sets in one call, sharded IVF, removal from an IVF store. */
+int radad_ivf_range_search_excl(radad_ivf_t h, const float* q_dev, int64_t nq, int nprobe, float radius, int max_per_query,
+                                const int64_t* row_tags_dev /*[ntotal], by insertion id*/,
+                                const int64_t* excl_sorted_dev /*[n_excl] ascending, NULL when n_excl == 0*/, int64_t n_excl,
+                                int32_t* out_count_dev /*[nq]*/, float* out_dist_dev /*[nq,M]*/, int64_t* out_idx_dev /*[nq,M]*/,
+                                double* out_key_dev /*[nq,M] or NULL*/, void* stream);
+int radad_ivf_range_search_excl_pq(radad_ivf_t h, const float* q_dev, int64_t nq, int nprobe, float radius, int max_per_query,
+                                   const int64_t* row_tags_dev /*[ntotal], by insertion id*/,
+                                   const int64_t* q_tags_dev /*[nq, m] row-major; any order, duplicates allowed*/, int m,
+                                   const int32_t* q_tag_counts_dev /*[nq] or NULL = m for every query*/, int32_t* out_count_dev /*[nq]*/,
+                                   float* out_dist_dev /*[nq,M]*/, int64_t* out_idx_dev /*[nq,M]*/, double* out_key_dev /*[nq,M] or NULL*/,
+                                   void* stream);
 int radad_ivf_reconstruct(radad_ivf_t h, const int64_t* idx_dev, int64_t n, float* out_dev, void* stream);
 
 /* out[r] = the k-th largest of the groups x per_group values of row r, value (g, i) at in[(g n + r) per_group + i] -- the layout

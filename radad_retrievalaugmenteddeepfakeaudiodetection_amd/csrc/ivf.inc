@@ -35,7 +35,8 @@
 // Exclusion-aware searches (radad_ivf_search_excl: one set for the batch; radad_ivf_search_excl_pq: one per query) run the same launches
 // with the ADM instantiations of the three list kernels behind a bitmap pre-pass: "exclusion inside the list scans", below.
 // What a search launches and allocates is decided by ivf_plan.h (host-only: tests/ivf_plan_check.cpp); ivf_search_lists is its glue.
-// Range search over the probed lists (radad_ivf_range_search): ivf_plan_range, the k_ivf_range_* kernels and ivf_range_lists, below.
+// Range search over the probed lists (radad_ivf_range_search, and among the rows a query does not exclude: radad_ivf_range_search_excl /
+// _excl_pq): ivf_plan_range, the k_ivf_range_* kernels and ivf_range_lists, below.
 #include "ivf_plan.h"
 namespace {
 
@@ -927,6 +928,8 @@ struct IvfRangeHiParams {
     int* cand_cnt = nullptr;       // [nq] positions emitted, 0 at launch; it keeps counting past cand_cap (overflow)
     int cand_cap = 0;
     int* cand_idx = nullptr;       // [nq][cand_cap] positions in the list-major order
+    const unsigned long long* admit = nullptr;      // IVF_ADM_BITMAP: the admission bitmap by list-major position (k_admit_bitmap<true>)
+    IvfPqRule pq;                                   // IVF_ADM_PQ: the per-query rule (no bitmap: see the kernel)
 };
 static_assert(std::is_trivially_copyable_v<IvfRangeHiParams>, "kernel argument");
 
@@ -935,6 +938,15 @@ static_assert(std::is_trivially_copyable_v<IvfRangeHiParams>, "kernel argument")
 // its accumulator decides alone.  So there is no score tile (LDS = the task's f16 queries: 16.6 KB at dim 512 instead of 37 KB), no
 // barrier inside the row loop, and the 16-row steps are dealt to the four waves as before (step i of the share to wave i % 4).
 // A NaN score is never emitted (`sc >= thr` is false).  Rows past l_end and the query rows past the task's count emit nothing.
+// ADM (radad_ivf_range_search_excl / _excl_pq): an excluded row never takes a slot.  The top-k scans must keep excluded rows out of
+// their bounds, so they fetch admission bits for every step and need a suspect pre-pass for the per-query form.  Here the floor is
+// fixed before the launch and no row sets a bound: admission is asked only of a (row, query) pair that has ALREADY passed `sc >= thr`,
+// by the lane that holds the pair.
+//   IVF_ADM_BITMAP  the pair's bit of the admission bitmap (absolute list-major position)
+//   IVF_ADM_PQ      the row's tag (through lids) against the tags of the lane's query r16, staged per task behind the f16 queries
+//                   (ivf_pq_stage at tag_off = scan_lds - pq_lds).  No suspect bitmap, no hash bitset, no pre-pass.
+// Both cost a gather per pair at or above the floor and nothing per row below it; the loop stays free of barriers.
+template <int ADM>
 __global__ __launch_bounds__(SQ_THREADS, 4) void k_ivf_range_hi(IvfRangeHiParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem_rh[];
     const int qld = p.dim + 8;
@@ -958,6 +970,7 @@ __global__ __launch_bounds__(SQ_THREADS, 4) void k_ivf_range_hi(IvfRangeHiParams
         if (qq < cnt) v = *reinterpret_cast<const f16x8*>(p.qh + (int64_t)p.pair_q[pbeg + qq] * p.dim + c8 * 8);
         *reinterpret_cast<f16x8*>(sQ + qq * qld + c8 * 8) = v;
     }
+    if constexpr (ADM == IVF_ADM_PQ) ivf_pq_stage(p.pq, smem_rh, p.qcap, p.pair_q, pbeg, cnt, tid, SQ_THREADS);
     const bool q_on = r16 < cnt;
     const int pq = q_on ? p.pair_q[pbeg + r16] : 0;
     const float qs = q_on ? p.qscale[pq] * 2.f : 0.f;
@@ -1000,6 +1013,8 @@ __global__ __launch_bounds__(SQ_THREADS, 4) void k_ivf_range_hi(IvfRangeHiParams
             const int64_t row = row0 + 4 * g + e;
             const float sc = fmaf((acc0[e] + acc1[e]) * rs[e], qs, yb[e]);      // the top-k scan's score, operation for operation
             if (q_on && row < l_end && sc >= thr) {
+                if constexpr (ADM == IVF_ADM_BITMAP) { if (!ivf_admitted(p.admit, row)) continue; }
+                if constexpr (ADM == IVF_ADM_PQ) { if (ivf_pq_excludes(p.pq, smem_rh, p.qcap, r16, row)) continue; }      // (q_on: r16 < cnt <= qcap)
                 const int slot = atomicAdd(my_cnt, 1);
                 if (slot < p.cand_cap) my_idx[slot] = (int)row;
             }
@@ -1125,6 +1140,8 @@ struct IvfRangeExactParams {
     int* arrive = nullptr;             // [nslots] arrival counters (zero between launches: the last arrival resets its own)
     int* out_count = nullptr;          // [nq], zero at launch for the queries answered here
     float* out_dist = nullptr; int64_t* out_idx = nullptr; double* out_key = nullptr;
+    const unsigned long long* admit = nullptr;      // IVF_ADM_BITMAP: the admission bitmap by list-major position
+    IvfPqRule pq;                                   // IVF_ADM_PQ: the per-query rule (row_tags, lids, q_tags, q_cnt, m; no bitmap)
 };
 static_assert(std::is_trivially_copyable_v<IvfRangeExactParams>, "kernel argument");
 
@@ -1135,6 +1152,11 @@ static_assert(std::is_trivially_copyable_v<IvfRangeExactParams>, "kernel argumen
 // Insertions are rare once a list is full.  The waves' lists are ranked into the pair's partial list (only the entries the waves
 // hold are compared: sLen), and the pair that arrives last for a query merges the nprobe partial lists and writes the m slots,
 // -1 / NaN / NaN where there is no member.
+// ADM: the admission test sits behind the strict radius test and in front of the count and the insertion, so only members pay for a
+// tag gather.  IVF_ADM_BITMAP: the row's bit.  IVF_ADM_PQ: a pair has ONE query; lane t of every wave holds tag t of it (t < its
+// clamped count) and one ballot per member row finds the row's tag among them -- the rule and the shape of k_ivf_exact<IVF_ADM_PQ>
+// without its bitmap short-cut (there is no suspect bitmap here).  Either decision is wave-uniform.
+template <int ADM>
 __global__ __launch_bounds__(IVX_THREADS) void k_ivf_range_exact(IvfRangeExactParams p) {
     const int count = min(*p.count - p.slot0, p.nslots);
     if (count <= 0) return;
@@ -1162,6 +1184,12 @@ __global__ __launch_bounds__(IVX_THREADS) void k_ivf_range_exact(IvfRangeExactPa
         double ek0 = -INFINITY, ek1 = -INFINITY;                                     // lane e: entries e and e + 64 of the wave's sorted list
         long long ei0 = IVX_NO_ID, ei1 = IVX_NO_ID;
         int members = 0;                                                             // (wave-uniform) rows of this wave that passed
+        int64_t my_tag = 0;                                                          // (IVF_ADM_PQ) tag `lane` of the pair's query ...
+        bool my_tag_on = false;                                                      // ... when the query's clamped count reaches it
+        if constexpr (ADM == IVF_ADM_PQ) {
+            my_tag_on = lane < min(max(p.pq.q_cnt ? p.pq.q_cnt[qi] : p.pq.m, 0), p.pq.m);
+            if (my_tag_on) my_tag = p.pq.q_tags[qi * p.pq.m + lane];
+        }
         for (int64_t row = r0 + wave * IVX_ROWS; row < r1; row += IVX_WAVES * IVX_ROWS) {
             double acc[IVX_ROWS];
 #pragma unroll
@@ -1183,6 +1211,11 @@ __global__ __launch_bounds__(IVX_THREADS) void k_ivf_range_exact(IvfRangeExactPa
 #pragma unroll
                 for (int ofs = 32; ofs > 0; ofs >>= 1) v += __shfl_xor(v, ofs, 64);
                 if (!(-v < p.radius)) continue;                                      // (wave-uniform) the strict test; a NaN key fails it
+                if constexpr (ADM == IVF_ADM_BITMAP) { if (!ivf_admitted(p.admit, row + u)) continue; }      // (wave-uniform)
+                if constexpr (ADM == IVF_ADM_PQ) {                                   // (wave-uniform: one row, one query)
+                    const int64_t t = p.pq.row_tags[p.pq.lids[row + u]];
+                    if (__ballot(my_tag_on && my_tag == t) != 0ull) continue;
+                }
                 ++members;
                 const long long gid = p.lids[row + u];
                 const double lk = K <= 64 ? __shfl(ek0, K - 1, 64) : __shfl(ek1, K - 65, 64);
@@ -1746,6 +1779,10 @@ static int ivf_search_lists(const char* fn, radad_ivf_t h, const float* q_dev, i
 // as they are) ---------------------------------------------------------------------------------------------------------------------
 struct IvfRangeOut { float radius; int32_t* count; float* dist; int64_t* idx; double* key; };
 
+// the instantiation both range kernels run (the scan and the exact pass behind it always the same one).  Unlike IvfSearch::adm, the
+// per-query form has no bitmap: pq.m > 0 alone selects it.
+static int ivf_range_adm(const IvfSearch& s) { return s.pq.m > 0 ? IVF_ADM_PQ : (s.admit ? IVF_ADM_BITMAP : IVF_ADM_NONE); }
+
 // IVF_RANGE_HI: the top-k hi route's query preparation (k_hi_rows: f16 side, eps; it zeroes cand_cnt and the 8 counters), the floors,
 // the scan, the re-rank
 static int ivf_launch_range_hi(const IvfSearch& s, const IvfRangeOut& o) {
@@ -1772,9 +1809,19 @@ static int ivf_launch_range_hi(const IvfSearch& s, const IvfRangeOut& o) {
     ip.task_list = s.tasks(p.tasks.tl); ip.task_pbeg = s.tasks(p.tasks.tp); ip.task_cnt = s.tasks(p.tasks.tc);
     ip.n_tasks_dev = s.tasks(p.tasks.nt); ip.pair_q = s.tasks(p.tasks.pq);
     ip.dim = h->dim; ip.qcap = p.qcap; ip.split = p.split;
-    ip.cand_cnt = cand_cnt; ip.cand_cap = p.ccap; ip.cand_idx = (int*)h->cand_i.p;
-    RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_range_hi), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.scan_lds));
-    hipLaunchKernelGGL(k_ivf_range_hi, dim3((unsigned)p.scan_grid), dim3(SQ_THREADS), p.scan_lds, st, ip);
+    ip.cand_cnt = cand_cnt; ip.cand_cap = p.ccap; ip.cand_idx = (int*)h->cand_i.p; ip.admit = s.admit; ip.pq = s.pq;
+    auto scan = [&](auto kern) -> int {
+        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.scan_lds));
+        hipLaunchKernelGGL(kern, dim3((unsigned)p.scan_grid), dim3(SQ_THREADS), p.scan_lds, st, ip);
+        return RADAD_OK;
+    };
+    int rc;
+    switch (ivf_range_adm(s)) {
+        case IVF_ADM_PQ: rc = scan(k_ivf_range_hi<IVF_ADM_PQ>); break;
+        case IVF_ADM_BITMAP: rc = scan(k_ivf_range_hi<IVF_ADM_BITMAP>); break;
+        default: rc = scan(k_ivf_range_hi<IVF_ADM_NONE>);
+    }
+    if (rc) return rc;
     IvfRangeRefineParams g;
     g.idx = (const int*)h->cand_i.p; g.cnt = cand_cnt; g.cap = p.ccap; g.dim = h->dim; g.m = p.k;
     g.lrows = (const float*)h->lrows.p; g.lids = (const int64_t*)h->lids.p; g.n_pos = (int64_t)h->assign.size(); g.q = s.q;
@@ -1806,19 +1853,31 @@ static int ivf_launch_range_exact(const IvfSearch& s, const IvfRangeOut& o) {
     x.probes = s.probes(); x.sel = s.qbuf<int>(p.qbuf.fsel); x.count = s.fcount(); x.done = s.fcount() + 1;
     x.dim = h->dim; x.m = p.k; x.nprobe = p.nprobe; x.nlist = h->nlist; x.nslots = (int)p.nslots; x.radius = (double)o.radius;
     x.pkey = (double*)h->xkey.p; x.pid = (int64_t*)h->xid.p; x.arrive = (int*)h->xarrive.p;
-    x.out_count = o.count; x.out_dist = o.dist; x.out_idx = o.idx; x.out_key = o.key;
-    RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ivf_range_exact), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.xlds));
-    for (int64_t i = 0; i < p.xlaunches; ++i) {
-        x.slot0 = (int)(i * p.nslots);
-        hipLaunchKernelGGL(k_ivf_range_exact, dim3((unsigned)p.xgrid), dim3(IVX_THREADS), p.xlds, s.st, x);
+    x.out_count = o.count; x.out_dist = o.dist; x.out_idx = o.idx; x.out_key = o.key; x.admit = s.admit; x.pq = s.pq;
+    auto exact = [&](auto kern) -> int {
+        RADAD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.xlds));
+        for (int64_t i = 0; i < p.xlaunches; ++i) {
+            x.slot0 = (int)(i * p.nslots);
+            hipLaunchKernelGGL(kern, dim3((unsigned)p.xgrid), dim3(IVX_THREADS), p.xlds, s.st, x);
+        }
+        RADAD_HIP_CHECK(hipGetLastError());
+        return RADAD_OK;
+    };
+    switch (ivf_range_adm(s)) {
+        case IVF_ADM_PQ: return exact(k_ivf_range_exact<IVF_ADM_PQ>);
+        case IVF_ADM_BITMAP: return exact(k_ivf_range_exact<IVF_ADM_BITMAP>);
+        default: return exact(k_ivf_range_exact<IVF_ADM_NONE>);
     }
-    RADAD_HIP_CHECK(hipGetLastError());
-    return RADAD_OK;
 }
 
 // The range search behind radad_ivf_range_search, beside ivf_search_lists: the same ordering, preparation, plane, buffers, coarse
 // search and grouping; then the route's launches.  The caller has checked the arguments; this takes the handle's lock.
-static int ivf_range_lists(const char* fn, radad_ivf_t h, const float* q_dev, int64_t nq, int nprobe, int m, const IvfRangeOut& o, void* stream) {
+// The exclusion arguments are ivf_search_lists's: row_tags with excl_sorted / n_excl (radad_ivf_range_search_excl; n_excl == 0: every
+// row is admissible, the IVF_ADM_NONE kernels run), or pq with pq->m > 0 (radad_ivf_range_search_excl_pq: its row_tags, q_tags, q_cnt
+// and m are the caller's; lids and tag_off are filled in here).  The bitmap of the batch-wide form is built by ivf_launch_admit on the
+// call's stream behind ivf_prepare; the per-query form has no pre-pass.
+static int ivf_range_lists(const char* fn, radad_ivf_t h, const float* q_dev, int64_t nq, int nprobe, int m, const IvfRangeOut& o, void* stream,
+                           const int64_t* row_tags = nullptr, const int64_t* excl_sorted = nullptr, int64_t n_excl = 0, const IvfPqRule* pq = nullptr) {
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard g(h->device);
     hipStream_t st = (hipStream_t)stream;
@@ -1841,10 +1900,14 @@ static int ivf_range_lists(const char* fn, radad_ivf_t h, const float* q_dev, in
         return RADAD_OK;
     }
     facts.plane = ivf_ensure_plane(h, st);
-    const IvfPlan p = ivf_plan_range(facts, nq, m, nprobe);
+    const int pq_m = pq ? pq->m : 0;
+    const IvfPlan p = ivf_plan_range(facts, nq, m, nprobe, n_excl > 0 || pq_m > 0, pq_m);
     if ((rc = ivf_plan_refused(fn, h, p))) return rc;
     if ((rc = ivf_ensure_buffers(h, p, st))) return rc;
-    const IvfSearch s{h, p, q_dev, o.dist, o.idx, st, nullptr, IvfPqRule()};
+    IvfPqRule rule;
+    if (p.pq_m > 0) { rule = *pq; rule.lids = (const int64_t*)h->lids.p; rule.tag_off = (int)(p.scan_lds - p.pq_lds); }
+    const IvfSearch s{h, p, q_dev, o.dist, o.idx, st, p.admit_words ? (const unsigned long long*)h->admit.p : nullptr, rule};
+    if (p.admit_words && (rc = ivf_launch_admit(s, row_tags, excl_sorted, n_excl))) return rc;
     if ((rc = ivf_launch_coarse_group(s))) return rc;
     const bool hi = p.range_route == IVF_RANGE_HI;
     if (hi && (rc = ivf_launch_range_hi(s, o))) return rc;
@@ -1872,6 +1935,46 @@ int radad_ivf_range_search(radad_ivf_t h, const float* q_dev, int64_t nq, int np
     RADAD_REQUIRE(q_dev && out_count_dev && out_dist_dev && out_idx_dev, "%s: NULL buffer", fn);
     const IvfRangeOut o{radius, out_count_dev, out_dist_dev, out_idx_dev, out_key_dev};
     return ivf_range_lists(fn, h, q_dev, nq, nprobe, max_per_query, o, stream);
+}
+
+// The range search among the admissible rows of the probed lists (the header's contract): ivf_range_lists with one set for the batch.
+int radad_ivf_range_search_excl(radad_ivf_t h, const float* q_dev, int64_t nq, int nprobe, float radius, int max_per_query,
+                                const int64_t* row_tags_dev, const int64_t* excl_sorted_dev, int64_t n_excl, int32_t* out_count_dev,
+                                float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, void* stream) {
+    const char* fn = "radad_ivf_range_search_excl";
+    RADAD_REQUIRE(h, "%s: NULL handle", fn);
+    if (!h->trained) { radad_set_error("%s: the index is not trained", fn); return RADAD_ESTATE; }
+    RADAD_REQUIRE(max_per_query >= 1 && max_per_query <= IVF_MAX_K, "%s: max_per_query=%d outside [1,%d]", fn, max_per_query, IVF_MAX_K);
+    RADAD_REQUIRE(radius == radius, "%s: the radius is NaN", fn);
+    RADAD_REQUIRE(nq >= 0 && nq < (1 << 24), "%s: bad nq", fn);
+    RADAD_REQUIRE(nprobe >= 1, "%s: nprobe=%d must be >= 1", fn, nprobe);
+    RADAD_REQUIRE(n_excl >= 0, "%s: n_excl=%lld is negative", fn, (long long)n_excl);
+    if (nq == 0) return RADAD_OK;
+    RADAD_REQUIRE(q_dev && out_count_dev && out_dist_dev && out_idx_dev, "%s: NULL buffer", fn);
+    RADAD_REQUIRE(n_excl == 0 || (row_tags_dev && excl_sorted_dev), "%s: row_tags_dev / excl_sorted_dev may be NULL only when n_excl == 0", fn);
+    const IvfRangeOut o{radius, out_count_dev, out_dist_dev, out_idx_dev, out_key_dev};
+    return ivf_range_lists(fn, h, q_dev, nq, nprobe, max_per_query, o, stream, row_tags_dev, excl_sorted_dev, n_excl);
+}
+
+// ... with one set per query: the IVF_ADM_PQ kernels, no pre-pass.  m == 0: nothing is excluded, the plain kernels run.
+int radad_ivf_range_search_excl_pq(radad_ivf_t h, const float* q_dev, int64_t nq, int nprobe, float radius, int max_per_query,
+                                   const int64_t* row_tags_dev, const int64_t* q_tags_dev, int m, const int32_t* q_tag_counts_dev,
+                                   int32_t* out_count_dev, float* out_dist_dev, int64_t* out_idx_dev, double* out_key_dev, void* stream) {
+    const char* fn = "radad_ivf_range_search_excl_pq";
+    RADAD_REQUIRE(h, "%s: NULL handle", fn);
+    if (!h->trained) { radad_set_error("%s: the index is not trained", fn); return RADAD_ESTATE; }
+    RADAD_REQUIRE(max_per_query >= 1 && max_per_query <= IVF_MAX_K, "%s: max_per_query=%d outside [1,%d]", fn, max_per_query, IVF_MAX_K);
+    RADAD_REQUIRE(radius == radius, "%s: the radius is NaN", fn);
+    RADAD_REQUIRE(nq >= 0 && nq < (1 << 24), "%s: bad nq", fn);
+    RADAD_REQUIRE(nprobe >= 1, "%s: nprobe=%d must be >= 1", fn, nprobe);
+    RADAD_REQUIRE(m >= 0 && m <= RADAD_EXCL_PQ_MAX_TAGS, "%s: m=%d tags per query outside [0,%d] (RADAD_EXCL_PQ_MAX_TAGS)", fn, m, RADAD_EXCL_PQ_MAX_TAGS);
+    if (nq == 0) return RADAD_OK;             // (an empty batch has no tags to point at)
+    RADAD_REQUIRE(q_dev && out_count_dev && out_dist_dev && out_idx_dev, "%s: NULL buffer", fn);
+    RADAD_REQUIRE(m == 0 || (q_tags_dev && row_tags_dev), "%s: %d tags per query need the query tags and the row tags", fn, m);
+    const IvfRangeOut o{radius, out_count_dev, out_dist_dev, out_idx_dev, out_key_dev};
+    IvfPqRule rule;
+    rule.row_tags = row_tags_dev; rule.q_tags = q_tags_dev; rule.q_cnt = m > 0 ? (const int*)q_tag_counts_dev : nullptr; rule.m = m;
+    return ivf_range_lists(fn, h, q_dev, nq, nprobe, max_per_query, o, stream, row_tags_dev, nullptr, 0, &rule);
 }
 
 int radad_ivf_last_range(radad_ivf_t h, int64_t* n_queries, int* route, int* n_exact, int* max_emitted) {

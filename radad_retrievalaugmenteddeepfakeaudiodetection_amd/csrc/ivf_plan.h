@@ -217,9 +217,12 @@ constexpr size_t ivf_range_exact_lds_bytes(int dim, int m, int nprobe) {        
 //                   workgroup has a bound of its own, so the (ccap / 2) / (nprobe (k + 8)) clause of the top-k plan has no meaning here.
 //   IVF_RANGE_EXACT k_ivf_range_exact for every query.
 // The exact pass keeps nprobe x m x 16 B of partial lists per query, in launches of nslots queries within IVX_PART_BUDGET.
-static IvfPlan ivf_plan_range(const IvfFacts& s, int64_t nq, int m, int nprobe) {
+// has_admit / pq_m (radad_ivf_range_search_excl / _excl_pq) mean what they mean to ivf_plan_search, which picks the route with them:
+// the tag block of pq_m tags per query counts towards its 160 KB, so IVF_RANGE_HI implies scan_lds = the f16 queries + the tag block
+// <= 160 KB.  With both at their defaults the plan is field for field what it was (tests/ivf_range_excl_plan_check.cpp).
+static IvfPlan ivf_plan_range(const IvfFacts& s, int64_t nq, int m, int nprobe, bool has_admit = false, int pq_m = 0) {
     // the coarse and grouping section is the top-k plan's own (k plays no part in it; the plan's later, k-dependent fields are not read)
-    const IvfPlan b = ivf_plan_search(s, nq, 1, nprobe, false);
+    const IvfPlan b = ivf_plan_search(s, nq, 1, nprobe, has_admit, pq_m);
     IvfPlan p;
     nprobe = b.nprobe;
     const int64_t npairs = b.npairs, T = b.T;
@@ -238,12 +241,18 @@ static IvfPlan ivf_plan_range(const IvfFacts& s, int64_t nq, int m, int nprobe) 
     p.range_route = hi ? IVF_RANGE_HI : IVF_RANGE_EXACT;
     p.qbuf = b.qbuf;
     p.qbuf_thr = b.qbuf.gbound;
+    // exclusion: one set for the batch reads the admission bitmap (the top-k plan's, spare word included); one set per query reads no
+    // bitmap at all -- a pair is decided against the query's tags once it has passed the floor, so neither a suspect bitmap nor the
+    // pre-pass's hash bitset exists (admit_words = pq_bits = pq_bitset = 0), only the tag block behind the f16 queries in LDS
+    p.pq_m = b.pq_m;
+    p.pq_lds = b.pq_lds;
+    if (p.pq_m == 0) { p.admit_words = b.admit_words; p.admit = b.admit; }
     if (hi) {
         p.ccap = IVF_RANGE_CAP;
         p.cand_i = (size_t)nq * IVF_RANGE_CAP * sizeof(int);
         p.split = T <= 64 ? 8 : (T <= 128 ? 4 : (T <= 256 ? 2 : 1));
         p.scan_grid = T * p.split;
-        p.scan_lds = ivf_range_hi_lds_bytes(qcap, s.dim);
+        p.scan_lds = ivf_range_hi_lds_bytes(qcap, s.dim) + p.pq_lds;
         p.cap = IVF_RANGE_CAP;
         p.refine_lds = ivf_range_refine_lds_bytes();
     }

@@ -99,7 +99,7 @@ class HotPathPipeline:
     # ---- audit by content ---------------------------------------------------------------------------------
     def near_duplicates(self, query_vectors, thresh: float, max_per_query: int = 128, query_paths: Optional[List[str]] = None,
                         exact_exclusion: bool = False, exclude: str = "file", query_speakers: Optional[List[str]] = None,
-                        probed: bool = False):
+                        probed: bool = False, probed_exclusion: bool = False):
         """Per query the stored rows within `thresh` of it (VectorDatabase.range_search_batch: cosine / inner product > thresh, or
         squared L2 < thresh, exactly), as a list of (path, label, score), best first, at most max_per_query.  The content
         counterpart of validate_no_leakage (pipeline.py:1105-1110), which compares basenames and so passes a re-encoded or renamed
@@ -113,11 +113,19 @@ class HotPathPipeline:
         (leave-one-speaker-out).
         probed=True (IVF stores; a ValueError on a flat one): the same lists from the rows of the probed lists
         (VectorDatabase.range_search_probed_batch, config.vector_db_nprobe; squared L2 < thresh) -- the audit on a store that is too
-        large to scan whole.  Not offered with exact_exclusion."""
+        large to scan whole.  Not offered with exact_exclusion (the flat store's call); its own switch is
+        probed_exclusion=True (only with probed=True): the exclusion runs inside the IVF list scans
+        (VectorDatabase.range_search_probed_excluding_per_query_batch) and the call returns (hits, counts) as exact_exclusion does --
+        counts[j] the exact number of admissible rows of query j's probed lists within the radius, every slot an admissible row;
+        exclude="file" and exclude="speaker" as above.  Without it the probed audit filters by basename after the search."""
         if exclude not in ("file", "speaker"):
             raise ValueError(f"exclude must be 'file' or 'speaker', got {exclude!r}")
         if probed and exact_exclusion:
             raise ValueError("near_duplicates: exact_exclusion is not offered with probed=True (an IVF range search takes no exclusion sets)")
+        if probed_exclusion and not probed:
+            raise ValueError("near_duplicates: probed_exclusion needs probed=True (a flat store has exact_exclusion)")
+        if probed_exclusion:
+            return self._near_duplicates_excluding(query_vectors, thresh, max_per_query, query_paths, exclude, query_speakers, probed=True)
         if exact_exclusion:
             return self._near_duplicates_excluding(query_vectors, thresh, max_per_query, query_paths, exclude, query_speakers)
         search = self.vector_db.range_search_probed_batch if probed else self.vector_db.range_search_batch
@@ -144,18 +152,19 @@ class HotPathPipeline:
         h = hashlib.blake2b(str(speaker).encode("utf-8", "surrogatepass"), digest_size=8).digest()
         return int.from_bytes(h, "little") & 0x7FFFFFFFFFFFFFFF
 
-    def _near_duplicates_excluding(self, query_vectors, thresh, max_per_query, query_paths, exclude, query_speakers):
+    def _near_duplicates_excluding(self, query_vectors, thresh, max_per_query, query_paths, exclude, query_speakers, probed=False):
         import torch
         from .vector_database import path_tag
         vdb = self.vector_db
         nq = 1 if getattr(query_vectors, "ndim", 2) == 1 else len(query_vectors)
+        what = "probed_exclusion" if probed else "exact_exclusion"
         if exclude == "file":
             if query_paths is None:
-                raise ValueError("exact_exclusion with exclude='file' needs query_paths")
+                raise ValueError(f"{what} with exclude='file' needs query_paths")
             row_tags, q_tags = None, [path_tag(p) for p in query_paths]               # (the per-row basename tags the store keeps)
         else:
             if query_speakers is None:
-                raise ValueError("exact_exclusion with exclude='speaker' needs query_speakers")
+                raise ValueError(f"{what} with exclude='speaker' needs query_speakers")
             stored = vdb.vector_metadata.get("speaker_id") if isinstance(vdb.vector_metadata, dict) else None
             if stored is None or len(stored) != len(vdb.vector_paths):
                 raise ValueError("exclude='speaker' needs the speaker_id metadata of every stored row")
@@ -166,8 +175,8 @@ class HotPathPipeline:
             row_tags, q_tags = cache, [self._speaker_tag(s_) for s_ in query_speakers]
         if len(q_tags) != nq:
             raise ValueError(f"{nq} queries, {len(q_tags)} {'query_paths' if exclude == 'file' else 'query_speakers'}")
-        lims, dist, idx, counts = vdb.range_search_excluding_per_query_batch(query_vectors, thresh, query_tags=q_tags, max_per_query=max_per_query,
-                                                                             return_counts=True, row_tags=row_tags)
+        search = vdb.range_search_probed_excluding_per_query_batch if probed else vdb.range_search_excluding_per_query_batch
+        lims, dist, idx, counts = search(query_vectors, thresh, query_tags=q_tags, max_per_query=max_per_query, return_counts=True, row_tags=row_tags)
         if hasattr(lims, "cpu"):
             lims, dist, idx, counts = lims.cpu().numpy(), dist.cpu().numpy(), idx.cpu().numpy(), counts.cpu().numpy()
         base = vdb.index.id_base if hasattr(vdb.index, "id_base") else 0

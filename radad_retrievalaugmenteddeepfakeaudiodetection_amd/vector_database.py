@@ -970,9 +970,66 @@ class HipIVFFlatIndex:
         self._range_probed_m(thresh, max_per_query)
         return self._range_csr(x, max_per_query, return_counts, lambda q: self.range_search_probed_device(q, thresh, max_per_query))
 
+    def range_search_probed_excluding_device(self, q, thresh: float, row_tags, exclude_tags, max_per_query: int = 128,
+                                             return_f64: bool = False):
+        """range_search_probed_device among the rows whose tag is not in ONE set for the batch (radad_ivf_range_search_excl): row_tags
+        int64 CUDA tensor [ntotal] by insertion id, exclude_tags int64 CUDA tensor sorted ascending, or None / empty.  The counts are
+        the exact numbers of ADMISSIBLE members of the probed lists; an excluded row is never counted, never takes one of the M slots
+        and never takes a slot of a query's candidate buffer inside the list scan."""
+        import torch
+        m = self._range_probed_m(thresh, max_per_query)
+        q = self._to_dev(q)
+        if q.dim() != 2 or q.shape[1] != self.d:
+            raise ValueError(f"range_search_probed_excluding expects [nq, {self.d}], got {tuple(q.shape)}")
+        row_tags, exclude_tags, n_excl = _prep_tags(row_tags, exclude_tags, self.ntotal)
+        counts = torch.empty((q.shape[0],), device=q.device, dtype=torch.int32)
+        D, I, K64 = _alloc_out(q, m, return_f64)
+        with torch.cuda.device(q.device):
+            _lib.check(self._lib.radad_ivf_range_search_excl(self._h, q.data_ptr(), q.shape[0], int(self.nprobe), float(thresh), m,
+                                                             _ptr(row_tags), _ptr(exclude_tags), n_excl, counts.data_ptr(), D.data_ptr(),
+                                                             I.data_ptr(), _ptr(K64), _lib.stream_ptr(q.device)),
+                       "radad_ivf_range_search_excl")
+        return (counts, D, I, K64) if return_f64 else (counts, D, I)
+
+    def range_search_probed_excluding_per_query_device(self, q, thresh: float, row_tags, query_tags, query_tag_counts=None,
+                                                       max_per_query: int = 128, return_f64: bool = False):
+        """range_search_probed_device with one exclusion set PER QUERY (radad_ivf_range_search_excl_pq; leave-one-file-out, leave-one-
+        speaker-out): row r is admissible for query j iff row_tags[r] is not among the first query_tag_counts[j] entries of
+        query_tags[j].  Tag arguments as search_probed_excluding_per_query (m <= 64 tags per query, any order, repeats allowed, counts
+        clamped to [0, m], None = m)."""
+        import torch
+        m = self._range_probed_m(thresh, max_per_query)
+        q = self._to_dev(q)
+        if q.dim() != 2 or q.shape[1] != self.d:
+            raise ValueError(f"range_search_probed_excluding_per_query expects [nq, {self.d}], got {tuple(q.shape)}")
+        row_tags, query_tags, tag_counts, n_tags = _prep_query_tags(row_tags, query_tags, query_tag_counts, q.shape[0], self.ntotal)
+        counts = torch.empty((q.shape[0],), device=q.device, dtype=torch.int32)
+        D, I, K64 = _alloc_out(q, m, return_f64)
+        with torch.cuda.device(q.device):
+            _lib.check(self._lib.radad_ivf_range_search_excl_pq(self._h, q.data_ptr(), q.shape[0], int(self.nprobe), float(thresh), m,
+                                                                _ptr(row_tags), _ptr(query_tags), n_tags, _ptr(tag_counts),
+                                                                counts.data_ptr(), D.data_ptr(), I.data_ptr(), _ptr(K64),
+                                                                _lib.stream_ptr(q.device)), "radad_ivf_range_search_excl_pq")
+        return (counts, D, I, K64) if return_f64 else (counts, D, I)
+
+    def range_search_probed_excluding(self, x, thresh: float, row_tags, exclude_tags, max_per_query: int = 128, return_counts: bool = False):
+        """range_search_probed_excluding_device in faiss's CSR form, as range_search_probed; the tags are CUDA tensors."""
+        self._range_probed_m(thresh, max_per_query)
+        return self._range_csr(x, max_per_query, return_counts,
+                               lambda q: self.range_search_probed_excluding_device(q, thresh, row_tags, exclude_tags, max_per_query))
+
+    def range_search_probed_excluding_per_query(self, x, thresh: float, row_tags, query_tags, query_tag_counts=None, max_per_query: int = 128,
+                                                return_counts: bool = False):
+        """range_search_probed_excluding_per_query_device in faiss's CSR form, as range_search_probed; the tags are CUDA tensors."""
+        self._range_probed_m(thresh, max_per_query)
+        return self._range_csr(x, max_per_query, return_counts,
+                               lambda q: self.range_search_probed_excluding_per_query_device(q, thresh, row_tags, query_tags,
+                                                                                             query_tag_counts, max_per_query))
+
     def last_range(self) -> dict:
         """{"queries", "route": "hi_lists" | "exact_lists", "exact": queries the exact float64 list scan answered, "max_emitted": the
-        largest number of positions one query's f16 scan emitted (0 on the exact route)} of the most recent range_search_probed
+        largest number of positions one query's f16 scan emitted (0 on the exact route; admissible (row, query) pairs only after an
+        exclusion-aware call)} of the most recent range_search_probed* call
         (radad_ivf_last_range; synchronises with it; a ValueError when the most recent search was not a range search)"""
         nq, route, ex, me = C.c_int64(), C.c_int(), C.c_int(), C.c_int()
         _lib.check(self._lib.radad_ivf_last_range(self._h, C.byref(nq), C.byref(route), C.byref(ex), C.byref(me)), "radad_ivf_last_range")
@@ -1264,13 +1321,13 @@ class VectorDatabase:
             self.index.nprobe = int(self.config.vector_db_nprobe)
         return self.index.range_search_probed(query_vectors, thresh, max_per_query=max_per_query, return_counts=return_counts)
 
-    def _range_front(self, name: str, query_vectors, return_counts: bool, probed: bool = False):
+    def _range_front(self, name: str, query_vectors, return_counts: bool, probed: bool = False, flat_name: str = "range_search_batch"):
         """the front of the range searches -> (query_vectors [B, d], None), or (query_vectors, the empty result of an empty store)"""
         if self.index is None:
             raise ValueError("Vector database is empty. Build the database first.")
         if probed:
             if not isinstance(self.index, HipIVFFlatIndex):
-                raise ValueError(f"{name} is the IVF store's range search (vector_db_index_type 'IVF'); a flat store has range_search_batch")
+                raise ValueError(f"{name} is the IVF store's range search (vector_db_index_type 'IVF'); a flat store has {flat_name}")
         elif not isinstance(self.index, HipFlatIndex):
             raise ValueError(f"{name} is flat and single-handle only (vector_db_index_type 'L2' or 'IP'): an IVF search "
                              "sees the probed lists, not the store")
@@ -1328,6 +1385,50 @@ class VectorDatabase:
         tags = None if query_tags is None else (self.row_tags_device() if row_tags is None else torch.as_tensor(row_tags, dtype=torch.int64).to(dev))
         return self.index.range_search_excluding_per_query(query_vectors, thresh, tags, query_tags, query_tag_counts,
                                                            max_per_query=max_per_query, return_counts=return_counts)
+
+    def range_search_probed_excluding_batch(self, query_vectors, thresh: float, exclude_tags=None, max_per_query: int = 128,
+                                            return_counts: bool = False):
+        """IVF stores: range_search_probed_batch among the rows whose basename tag (path_tag) is not in `exclude_tags` -- ONE set for the
+        batch (HipIVFFlatIndex.range_search_probed_excluding): the counts are the exact numbers of admissible members of the probed
+        lists, and an excluded row never takes one of the max_per_query (<= 128) slots.  exclude_tags: int64 tensor / sequence of tags,
+        or None / empty.  The IVF twin of range_search_excluding_batch; a flat store raises."""
+        import torch
+        query_vectors, empty = self._range_front("range_search_probed_excluding_batch", query_vectors, return_counts, probed=True,
+                                                 flat_name="range_search_excluding_batch")
+        if empty is not None:
+            return empty
+        dev = torch.device("cuda", self.device_id)
+        excl = None
+        if exclude_tags is not None and len(exclude_tags) > 0:
+            excl = torch.unique(torch.as_tensor(exclude_tags, dtype=torch.int64).to(dev).reshape(-1))       # sorted, as the kernel's search needs
+        tags = None if excl is None else self.row_tags_device()
+        if hasattr(self.config, "vector_db_nprobe"):        # vector_database.py:174-179
+            self.index.nprobe = int(self.config.vector_db_nprobe)
+        return self.index.range_search_probed_excluding(query_vectors, thresh, tags, excl, max_per_query=max_per_query,
+                                                        return_counts=return_counts)
+
+    def range_search_probed_excluding_per_query_batch(self, query_vectors, thresh: float, query_tags=None, query_tag_counts=None,
+                                                      max_per_query: int = 128, return_counts: bool = False, row_tags=None):
+        """IVF stores: range_search_probed_batch with one exclusion set PER QUERY (HipIVFFlatIndex.range_search_probed_excluding_per_query;
+        leave-one-file-out, leave-one-speaker-out): query i excludes the rows whose tag is among the first query_tag_counts[i] entries
+        of query_tags[i].  query_tags: int64 tensor / nested sequence [B, m] (or [B]), m <= 64, None = nothing excluded;
+        query_tag_counts: [B] or None.  row_tags: None = the basename tags (path_tag) kept per row, or an int64 [ntotal] column of the
+        caller's own.  The IVF twin of range_search_excluding_per_query_batch; a flat store raises."""
+        import torch
+        query_vectors, empty = self._range_front("range_search_probed_excluding_per_query_batch", query_vectors, return_counts, probed=True,
+                                                 flat_name="range_search_excluding_per_query_batch")
+        if empty is not None:
+            return empty
+        dev = torch.device("cuda", self.device_id)
+        if query_tags is not None:
+            query_tags = torch.as_tensor(query_tags, dtype=torch.int64).to(dev)
+        if query_tag_counts is not None:
+            query_tag_counts = torch.as_tensor(query_tag_counts, dtype=torch.int32).to(dev)
+        tags = None if query_tags is None else (self.row_tags_device() if row_tags is None else torch.as_tensor(row_tags, dtype=torch.int64).to(dev))
+        if hasattr(self.config, "vector_db_nprobe"):        # vector_database.py:174-179
+            self.index.nprobe = int(self.config.vector_db_nprobe)
+        return self.index.range_search_probed_excluding_per_query(query_vectors, thresh, tags, query_tags, query_tag_counts,
+                                                                  max_per_query=max_per_query, return_counts=return_counts)
 
     def _excluding_args(self, index_cls, wrong_index: str, query_vectors, k, exclude_tags, k_fetch=None):
         """the front of search_excluding / search_probed_excluding -> (query_vectors [B, d], k clamped to ntotal, k_fetch, row tags,
